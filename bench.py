@@ -14,14 +14,17 @@ untimed), so the measured context length -- and with it the KV bytes per step --
 (mean context = prompt + 256 +- a few), not that of its first K steps.
 
     python bench.py --gpus 1 --steps 512 --warmup 16
-    python bench.py --gpus 8 ...                 # no env needed: re-executes itself through torch.distributed.run
+    python bench.py --gpus 8 ...                 # no env needed: runs torch.distributed.run as a child process
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+    python bench.py --full                       # + the RTF leg, the extra legs and the CPU baseline
+    python bench.py --dump-outputs DIR           # + the headline leg's token ids and hidden states as DIR/*.npy
 
 N > 1: utterances are independent -> every rank decodes its own batch (weak scaling); the only collective on the
-path is one RCCL broadcast of the speaker-embedding table before the timed region.  The JSON line also carries an `extra`
-block (same process, after the headline leg): batch 32 per GPU (configs[2]; aggregated over the ranks = configs[3] at N=8),
-batch 32 with mixed-length left-padded prompts, a 512-token prompt (north_star's "synthetic 512-token prompts"), and batch 32
-through a LoRA-merged engine (configs[4]).  `--no-extras` skips them.
+path is one RCCL broadcast of the speaker-embedding table before the timed region.  A plain run times the headline leg and
+nothing else.  With `--full` the JSON line also carries the end-to-end RTF (DVAE decoder + Vocos on the generated hiddens), the
+CPU baseline and an `extra` block (same process, after the headline leg): batch 32 per GPU (configs[2]; aggregated over the ranks
+= configs[3] at N=8), batch 32 with mixed-length left-padded prompts, a 512-token prompt (north_star's "synthetic 512-token
+prompts"), and batch 32 through a LoRA-merged engine (configs[4]).  `--full --no-extras` skips the extra legs.
 """
 import argparse
 import ctypes as C
@@ -93,14 +96,16 @@ def _free_port():
 
 
 def self_spawn(args):
-    """`python bench.py --gpus N` without a launcher: replace this process by torch.distributed.run with N ranks on this node."""
+    """`python bench.py --gpus N` without a launcher: run torch.distributed.run with N ranks on this node as a child process and exit with
+    its status (a fresh process, not an exec: this one may already have initialised the GPU runtime to count the devices)."""
+    import subprocess
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.setdefault("OMP_NUM_THREADS", "16")
     sys.stdout.flush()
-    os.execvpe(cmd[0], cmd, env)
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 
@@ -266,25 +271,27 @@ def dry_run(args, world, rank):
         return float(dt), [float(p) for p in per]
 
     dt, per = leg(args.batch, args.steps, 0.05)
-    extra = {}
-    d32, p32 = leg(32, args.steps, 0.01)
-    extra["batch32"] = {"tokens_per_s": round(32 * args.steps * world / d32, 1), "per_rank_tokens_per_s": [round(32 * args.steps / p, 1) for p in p32],
-                        "rtf_end_to_end": round(32 * args.steps * world * (512 / 24000.0) / d32, 2)}
-    # the sharded-request leg on the same control flow: real ChatTTSPlusPipeline.infer_sharded host code (partition, speaker + seed broadcast, per-rank
-    # slices / continuous batching, length all-reduce) around CPU stand-ins for the engines
-    import tempfile
-    from chatttsplus_amd.pipeline import ChatTTSPlusPipeline
-    with tempfile.TemporaryDirectory() as td:
-        pipe = ChatTTSPlusPipeline.from_components(_DryGPT(), _DrySynth(), synth.toy_tokenizer(td), "cpu")
-        extra["sharded_request"] = sharded_request_leg(pipe, torch.device("cpu"), rank, world, n_utt=48, rows=8, reps=1, max_new=160)
-    d5, p5 = leg(1, args.steps, 0.01)
-    extra["prompt512_batch1"] = {"tokens_per_s": round(args.steps * world / d5, 1), "per_rank_tokens_per_s": [round(args.steps / p, 1) for p in p5]}
+    extra = None
+    if args.full and not args.no_extras:
+        extra = {}
+        d32, p32 = leg(32, args.steps, 0.01)
+        extra["batch32"] = {"tokens_per_s": round(32 * args.steps * world / d32, 1), "per_rank_tokens_per_s": [round(32 * args.steps / p, 1) for p in p32],
+                            "rtf_end_to_end": round(32 * args.steps * world * (512 / 24000.0) / d32, 2)}
+        # the sharded-request leg on the same control flow: real ChatTTSPlusPipeline.infer_sharded host code (partition, speaker + seed broadcast, per-rank
+        # slices / continuous batching, length all-reduce) around CPU stand-ins for the engines
+        import tempfile
+        from chatttsplus_amd.pipeline import ChatTTSPlusPipeline
+        with tempfile.TemporaryDirectory() as td:
+            pipe = ChatTTSPlusPipeline.from_components(_DryGPT(), _DrySynth(), synth.toy_tokenizer(td), "cpu")
+            extra["sharded_request"] = sharded_request_leg(pipe, torch.device("cpu"), rank, world, n_utt=48, rows=8, reps=1, max_new=160)
+        d5, p5 = leg(1, args.steps, 0.01)
+        extra["prompt512_batch1"] = {"tokens_per_s": round(args.steps * world / d5, 1), "per_rank_tokens_per_s": [round(args.steps / p, 1) for p in p5]}
     pg = {"backend": dist.get_backend(), "world_size": dist.get_world_size(), "forced_at_world_1": bool(args.force_pg and world == 1)} if grouped else None
     if grouped:
         dist.destroy_process_group()
     if rank == 0:
         # rank 0 alone, after the last rendezvous -- as in the real run (a tiny sample here: the dry run checks the control flow, not the number)
-        cpu = cpu_baseline(8, 8) if args.cpu_steps > 0 else None
+        cpu = cpu_baseline(8, 8) if args.full and args.cpu_steps > 0 else None
         print(json.dumps({"metric": "decode tokens/s", "value": round(args.batch * args.steps * world / dt, 2), "unit": "tokens/s",
                           "extra": extra, "cpu_baseline": cpu, "process_group": pg,
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 5),
@@ -370,7 +377,7 @@ class Leg:
             dist.all_gather(per, torch.tensor([mine], device=dev, dtype=torch.float64))
         valid = (mask.sum(1)).astype(np.float64)                                   # attended prompt tokens per sequence
         mean_ctx = float(valid.mean()) + s0 + K / 2.0
-        return dict(B=B, P=P, K=K, s0=s0, dt=float(tmax.item()), ev_ms=ev_ms, prefill_ms=prefill_ms, hid=hid, expect=expect, mean_ctx=mean_ctx,
+        return dict(B=B, P=P, K=K, s0=s0, dt=float(tmax.item()), ev_ms=ev_ms, prefill_ms=prefill_ms, ids=out_ids, hid=hid, expect=expect, mean_ctx=mean_ctx,
                     per_rank_s=[float(p.item()) for p in per], step_bytes=g.step_bytes(B, mean_ctx))
 
 
@@ -524,6 +531,27 @@ def _summary(r, world, step_ms, ach):
             "achieved_GBps": round(ach, 1), "frac_of_8TBps": round(ach / HBM_PEAK_GBS, 4), "prefill_plus_first_sample_ms": round(r["prefill_ms"], 3)}
 
 
+DUMP_BYTES = 60 << 20               # all files of --dump-outputs together: under 64 MB
+
+
+def dump_outputs(out_dir, r):
+    """What a caller of the timed path receives once its last step is done, from the headline leg: the code indices of every generated token
+    (`token_ids.npy`, [B, n, 4], float64) and the hidden states the vocoder takes (`hiddens.npy`, [B, n, 768], float32).  Where the files would
+    exceed DUMP_BYTES, `hiddens.npy` holds a fixed seeded sample of the [B * n] rows, sorted, and `hidden_rows.npy` their indices."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = r["expect"]
+    ids = r["ids"][:, :n].cpu().numpy().astype(np.float64)
+    np.save(os.path.join(out_dir, "token_ids.npy"), ids)
+    hid = r["hid"][:, :n].cpu().numpy()
+    budget = DUMP_BYTES - ids.nbytes
+    if hid.nbytes > budget:
+        rows = hid.reshape(-1, hid.shape[-1])
+        keep = np.sort(np.random.default_rng(0).choice(rows.shape[0], size=budget // (rows[0].nbytes + 8), replace=False))
+        np.save(os.path.join(out_dir, "hidden_rows.npy"), keep.astype(np.float64))
+        hid = rows[keep]
+    np.save(os.path.join(out_dir, "hiddens.npy"), hid)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -532,10 +560,12 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--prompt", type=int, default=48)
     ap.add_argument("--dtype", default="fp32", choices=["fp16", "fp32"], help="fp32 = parity mode (default, what the YAML ships); fp16 = fast mode")
-    ap.add_argument("--cpu-steps", type=int, default=192, help="decode steps of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also measure the end-to-end RTF, the extra legs and the CPU baseline (a plain run times the headline leg only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the headline leg's token ids and hidden states as DIR/<name>.npy after the timed steps")
+    ap.add_argument("--cpu-steps", type=int, default=192, help="decode steps of the CPU baseline sample with --full (0 = skip)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--gen-tokens", type=int, default=GEN_TOKENS, help="length of the generation the timed window is centred in (0: the window starts right after the warm-up; used by the short profiler passes)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra legs (batch 32, mixed prompts, 512-token prompt, LoRA)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra legs (batch 32, mixed prompts, 512-token prompt, LoRA)")
     ap.add_argument("--extra-steps", type=int, default=128, help="timed steps of each extra leg")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE", help="engine option (ctts_gpt_set_option) for A/B runs, e.g. --option persistent_rows=0")
     ap.add_argument("--request-utterances", type=int, default=256, help="utterances of the sharded-request leg (BASELINE configs[3]: 256)")
@@ -573,11 +603,12 @@ def main():
     from chatttsplus_amd.hip_models.gpt import GPT
 
     B, P, K, W = args.batch, args.prompt, args.steps, args.warmup
-    extras = not args.no_extras
+    extras = args.full and not args.no_extras
+    sized_for_extras = not args.no_extras            # a plain run builds the same engine as --full: its headline leg runs on the same shapes
     EB, EK = 32, args.extra_steps
     sd = synth.gpt_state_dict(synth.GPT_REAL, 1234)                    # every rank holds a full replica (0.45 GB fp16)
-    need_seq = max(P, 512 if extras else 0) + W + max(GEN_TOKENS, args.gen_tokens, K) + 16     # (96: the sharded request's longest prompt)
-    g = GPT(LLAMA, max_batch=max(B, EB if extras else 1), max_seq_len=need_seq, weight_dtype=args.dtype, device=str(dev))
+    need_seq = max(P, 512 if sized_for_extras else 0) + W + max(GEN_TOKENS, args.gen_tokens, K) + 16     # (96: the sharded request's longest prompt)
+    g = GPT(LLAMA, max_batch=max(B, EB if sized_for_extras else 1), max_seq_len=need_seq, weight_dtype=args.dtype, device=str(dev))
     g.load_state_dict(sd)
     for kv in args.option:
         k, v = kv.split("=")
@@ -594,25 +625,28 @@ def main():
     XR = max(1, args.extra_reps)
     r = leg.run(B, P, K, W, spk=spk, use_graph=use_graph, keep_hidden=True, gen_tokens=args.gen_tokens)
     dt, expect, hid = r["dt"], r["expect"], r["hid"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r)
 
     # RTF leg (outside the timed decode region): DVAE decoder + Vocos on the generated hiddens of every local sequence
     voc_ms = None
-    try:
-        from chatttsplus_amd.hip_models import Synth
-        syn = Synth(dict(synth.DVAE_REAL), dict(synth.VOCOS_REAL), max_frames=2 * expect + 64, device=str(dev), max_batch=min(B, 64))   # decode_batch slices
-        syn.load("dvae.", synth.dvae_state_dict(synth.DVAE_REAL, 1234))
-        syn.load("vocos.", synth.vocos_state_dict(synth.VOCOS_REAL, 1234))
-        batch = [hid[b, :expect] for b in range(B)]
-        wav = syn.decode_batch(batch)[-1]                                  # warm (same shapes as the timed call)
-        torch.cuda.synchronize(dev)
-        tv = time.perf_counter()
-        wav = syn.decode_batch(batch)[-1]
-        torch.cuda.synchronize(dev)
-        voc_ms = (time.perf_counter() - tv) * 1e3
-        assert wav.shape[0] == 256 * (2 * expect - 1) and bool(torch.isfinite(wav).all())
-        del syn
-    except Exception as e:          # the decode metric stays valid; report the failure instead of hiding it
-        voc_ms = f"failed: {e}"
+    if args.full:
+        try:
+            from chatttsplus_amd.hip_models import Synth
+            syn = Synth(dict(synth.DVAE_REAL), dict(synth.VOCOS_REAL), max_frames=2 * expect + 64, device=str(dev), max_batch=min(B, 64))   # decode_batch slices
+            syn.load("dvae.", synth.dvae_state_dict(synth.DVAE_REAL, 1234))
+            syn.load("vocos.", synth.vocos_state_dict(synth.VOCOS_REAL, 1234))
+            batch = [hid[b, :expect] for b in range(B)]
+            wav = syn.decode_batch(batch)[-1]                                  # warm (same shapes as the timed call)
+            torch.cuda.synchronize(dev)
+            tv = time.perf_counter()
+            wav = syn.decode_batch(batch)[-1]
+            torch.cuda.synchronize(dev)
+            voc_ms = (time.perf_counter() - tv) * 1e3
+            assert wav.shape[0] == 256 * (2 * expect - 1) and bool(torch.isfinite(wav).all())
+            del syn
+        except Exception as e:          # the decode metric stays valid; report the failure instead of hiding it
+            voc_ms = f"failed: {e}"
     del hid
     r["hid"] = None
 
@@ -795,7 +829,8 @@ def main():
             "rtf_end_to_end": (round(B * 256 * (2 * expect - 1) / 24000.0 / ((r["prefill_ms"] + (dt / K) * 1e3 * (expect - 1) + voc_ms) / 1e3), 2)
                                if isinstance(voc_ms, float) else None),
             "vocoder_ms_for_batch": voc_ms if not isinstance(voc_ms, float) else round(voc_ms, 3),
-            "rtf_note": f"audio seconds of {B} utterances x {expect} tokens / (prompt pass + {expect - 1} decode steps at the measured rate + DVAE-decoder + Vocos), rank 0",
+            "rtf_note": (f"audio seconds of {B} utterances x {expect} tokens / (prompt pass + {expect - 1} decode steps at the measured rate + DVAE-decoder + Vocos), rank 0"
+                         if args.full else None),
             "prefill_plus_first_sample_ms": round(r["prefill_ms"], 3),
             "reference_published_tok_s": {"tensorrt_fp16_rtx3060": 110, "pytorch_fp16_rtx3060": 28},
             "extra": extra if extras else None,
@@ -806,7 +841,7 @@ def main():
         dist.destroy_process_group()
     if rank == 0:
         # the CPU baseline runs on rank 0 only, AFTER the last rendezvous (the other ranks are done): an N > 1 line carries it too
-        res["cpu_baseline"] = cpu_baseline(P, args.cpu_steps) if args.cpu_steps > 0 else None
+        res["cpu_baseline"] = cpu_baseline(P, args.cpu_steps) if args.full and args.cpu_steps > 0 else None
         print(json.dumps(res))
 
 

@@ -2,7 +2,8 @@
 
 TEST INFRASTRUCTURE.  Runs only in the build container (needs /root/reference):
 
-    python -m oracle.make_golden_text
+    python -m oracle.make_golden_text             # tests/golden/text_frontend.json
+    python -m oracle.make_golden_text --random    # tests/golden/text_frontend_random.json.gz
 
 What is imported: chattts_plus/commons/text_utils.py (num_to_english, get_lang, num2text, remove_brackets, split_text,
 split_text_by_punctuation) and chattts_plus/commons/norm.py (Normalizer).  Their import-time third-party dependencies are absent
@@ -29,6 +30,7 @@ sys.path.insert(0, ROOT)
 from oracle.ref_import import REFERENCE_ROOT, reference_available  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden", "text_frontend.json")
+OUT_RANDOM = os.path.join(ROOT, "tests", "golden", "text_frontend_random.json.gz")
 
 HOMOPHONES = {"粘": "年", "吗": "嘛", "呗": "贝", "嗯": "恩", "哦": "喔"}          # made-up map in the format of homophones_map.json
 
@@ -149,6 +151,44 @@ def _run(f, *a):
         return {"raises": type(e).__name__}
 
 
+def random_cases(tu, nm):
+    """Seeded random numbers and strings through every function (tests/test_text_frontend.py compares against them): inputs + the
+    reference's outputs, None where the reference raises (its missing "ten" / scale words)."""
+    import random
+    rng = random.Random(20240927)
+    numbers = []
+    for _ in range(3000):
+        num = rng.randint(0, 10 ** rng.randint(1, 15))
+        want = _run(tu.num_to_english, num)
+        numbers.append([num, None if isinstance(want, dict) else want])
+    alphabet = list("abc XYZ 0123456789 .,;:!?%+-*/=x()[]{}<>_'\"~\n\t") + list("你好世界天气今很，。！？；：（）【】《》「」…—　粘吗哦") + ["[uv_break]", "[laugh]", "[lbreak]", "[break]", " 12.5% ", " 3/4 ", "1,000"]
+    with tempfile.TemporaryDirectory() as d:
+        mp = os.path.join(d, "h.json")
+        with open(mp, "w", encoding="utf-8") as f:
+            json.dump(HOMOPHONES, f, ensure_ascii=False)
+        norm = nm.Normalizer(mp)
+        texts = []
+        for _ in range(1500):
+            text = "".join(rng.choice(alphabet) for _ in range(rng.randint(0, 60)))
+            reps = rng.randint(1, 8)
+            n2t = _run(tu.num2text, text)
+            texts.append(dict(text=text, lang=tu.get_lang(text), remove_brackets=tu.remove_brackets(text), reps=reps,
+                              split_text_by_punctuation=tu.split_text_by_punctuation(text * reps),
+                              normalizer=[norm(text, *flags) for flags in NORM_FLAGS], num2text=None if isinstance(n2t, dict) else n2t))
+    return dict(homophones=HOMOPHONES, normalizer_flags=NORM_FLAGS, numbers=numbers, texts=texts)
+
+
+NORM_FLAGS = [[True, True, None], [False, True, None], [True, False, "zh"], [True, True, "en"]]
+
+
+def write_random():
+    import gzip
+    tu, nm = load_text_reference()
+    with gzip.GzipFile(OUT_RANDOM, "wb", mtime=0) as f:
+        f.write(json.dumps(random_cases(tu, nm), ensure_ascii=False).encode("utf-8"))
+    print("wrote", OUT_RANDOM)
+
+
 def main():
     import contextlib
     import io
@@ -182,4 +222,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    write_random() if "--random" in sys.argv else main()

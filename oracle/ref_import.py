@@ -1,9 +1,8 @@
-"""Import the *unmodified* reference modules from /root/reference (build container only).
+"""Import the *unmodified* reference modules from the reference tree (``CTTS_REFERENCE_ROOT``).
 
 TEST INFRASTRUCTURE -- not part of the product.  This file is only used by
-``oracle/make_golden.py`` (to mint the committed fixtures under ``tests/golden/``)
-and by CPU tests that are skipped automatically when ``/root/reference`` is
-absent (it does not exist on the GPU box).  Nothing from the reference is
+the ``oracle/make_golden*.py`` scripts, which mint the committed fixtures under
+``tests/golden/``; the tests themselves read only those fixtures.  Nothing from the reference is
 copied; we only *import* it, after installing the small compatibility shims
 SURVEY.md section 8(c) lists (the vendored llama.py targets transformers 4.41,
 this image has 5.x; tokenizer/dvae import-time deps are absent).

@@ -15,7 +15,7 @@ def _free_port():
 
 def test_bench_dry_run_world2():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2", "--dry-run"]
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2", "--dry-run", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -33,7 +33,7 @@ def test_bench_dry_run_world2():
     sr = d["extra"]["sharded_request"]
     assert sr["utterances"] == 48 and len(sr["per_rank_useful_tokens"]) == 2 and all(t > 0 for t in sr["per_rank_useful_tokens"])
     assert sum(sr["per_rank_useful_tokens"]) == sr["useful_tokens"] and sr["load_imbalance_max_over_mean"] < 1.2
-    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "4"], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--full", "--steps", "4"], capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert one.returncode == 0, one.stderr[-2000:]
     sr1 = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][0])["extra"]["sharded_request"]
     assert sr1["ids_digest"] == sr["ids_digest"] and sr1["lengths_digest"] == sr["lengths_digest"]
@@ -44,13 +44,14 @@ def test_bench_dry_run_single():
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert d["n_gpus"] == 1 and d["process_group"] is None
+    assert d["extra"] is None and d["cpu_baseline"] is None              # a plain run times the headline leg only; the rest is behind --full
 
 
 def test_bench_force_pg_takes_the_group_path_at_world_1():
     """`--force-pg`: a one-rank process group and every rendezvous of the N > 1 path at --gpus 1 (gloo here; "nccl" = RCCL on the GPU box, where the same
     switch makes the first contact with RCCL a one-GPU run instead of the driver's 8-GPU one)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "4", "--force-pg"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--full", "--steps", "4", "--force-pg"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert d["process_group"] == {"backend": "gloo", "world_size": 1, "forced_at_world_1": True}

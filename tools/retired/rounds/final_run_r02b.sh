@@ -20,5 +20,5 @@ timeout 100 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCL
 db=$(find /tmp/pmc_mfma_prefill -name '*.db' | head -1)
 [ -n "$db" ] && python $R/tools/rocpd_mfma.py $db $R/$O/pmc_mfma_prefill.json 2>> $R/$O/pmc_errors.log || echo "no db for mfma prefill" >> $R/$O/pmc_errors.log
 cd $R
-timeout 200 python bench.py > $O/bench_b1_fp16.json 2> $O/bench_b1_fp16.err; cut -c1-300 $O/bench_b1_fp16.json
+timeout 200 python bench.py --full > $O/bench_b1_fp16.json 2> $O/bench_b1_fp16.err; cut -c1-300 $O/bench_b1_fp16.json
 ls -la $O; head -8 $O/pre_kernel_stats.csv | cut -c1-160

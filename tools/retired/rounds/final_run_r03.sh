@@ -8,8 +8,8 @@ mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.log
 tail -3 $O/pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')" > $O/smoke.log 2>&1; tail -2 $O/smoke.log
-timeout 900 python bench.py > $O/bench_b1_fp32.json 2> $O/bench_b1_fp32.err; cut -c1-200 $O/bench_b1_fp32.json
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_b1_fp32_driver_args.json 2>/dev/null; cut -c1-200 $O/bench_b1_fp32_driver_args.json
+timeout 900 python bench.py --full > $O/bench_b1_fp32.json 2> $O/bench_b1_fp32.err; cut -c1-200 $O/bench_b1_fp32.json
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_b1_fp32_driver_args.json 2>/dev/null; cut -c1-200 $O/bench_b1_fp32_driver_args.json
 for B in 32 64 128; do timeout 300 python bench.py --batch $B --steps 256 --cpu-steps 0 --no-extras > $O/bench_b${B}_fp32.json 2>/dev/null; cut -c1-160 $O/bench_b${B}_fp32.json; done
 timeout 300 python bench.py --dtype fp16 --steps 512 --cpu-steps 0 --no-extras > $O/bench_b1_fp16.json 2>/dev/null; cut -c1-160 $O/bench_b1_fp16.json
 for B in 32 64 128; do timeout 300 python bench.py --dtype fp16 --batch $B --steps 256 --cpu-steps 0 --no-extras > $O/bench_b${B}_fp16.json 2>/dev/null; cut -c1-160 $O/bench_b${B}_fp16.json; done
