@@ -183,6 +183,11 @@ struct ctts_gpt {
     int persist_poll = -1;                       //   PersistArgs.poll; -1 = by row count: the sentinel pass costs one serial poll at 1-2 rows (batch 1 379.2 -> 387.1 us,
                                                  //   batch 2 430.7 -> 437.8) and pays from 3 rows on, where a full sweep re-reads up to 96 granules per lane (batch 4 547.5 -> 537.6)
     int no_prepack = 0, prefill_gemm_rows = 1536, xh_heads = 1;   // diagnostic builds only: see run_layers / run_decode_step
+    int batch_inv = 0;                           // "batch_invariant" (fp32 engines): one arithmetic per row whatever the schedule (include/ctts_hip.h states the contract).  Decode: the split
+                                                 //   projections on 16-row chunks at every row count, the down projection's K always sliced in the launch, layer 0 and the heads in one form, unsplit
+                                                 //   8-wave attention, no persistent launch, no VALU rows.  Prompt: the split GEMMs at every pass height, K never sliced, attention chunks anchored
+                                                 //   at the first real key.  begin: the last prompt token runs through the first decode step's layer pass, as after ctts_gpt_admit
+    float* rope_dec0 = nullptr;                  //   ... the decode rows' RoPE rows at begin (ctts_gpt_restart replays the first layer pass)
     RowMeta *meta_pre = nullptr, *meta_dec = nullptr, *meta_dec0 = nullptr;
     DevState* st = nullptr;
     int* last_rows = nullptr;
@@ -366,6 +371,13 @@ static int persist_images(ctts_gpt* h) {
 extern "C" int ctts_gpt_get_option(ctts_gpt* h, const char* name, int* value) {
     if (!h || !name || !value) { ctts_set_error("get_option: null argument"); return 1; }
     const std::string n(name);
+    if (n == "batch_invariant") { *value = h->batch_inv; return 0; }
+    if (h->batch_inv) {          // what the launches use while the option is on (the tuning values set meanwhile are kept for when it is switched off)
+        static const struct { const char* name; int value; } eff[] = {
+            {"persistent_rows", 0}, {"valu_rows", 0}, {"split_decode_rows", 1}, {"split_rows", 0}, {"down_splitk_rows", 1}, {"nbg2_rows", 0},
+            {"split_nbg2_rows", 0}, {"decode_splits", 1}, {"attn_wide_blocks", 0x7FFFFFFF}, {"prefill_split_rows", 1}, {"prefill_splitk_rows", 0}};
+        for (const auto& e : eff) if (n == e.name) { *value = e.value; return 0; }
+    }
     if (n == "persistent_rows") *value = (h->persist_ok || !h->finalized) ? h->persist_rows : 0;      // the EFFECTIVE value (0 when the mode is unavailable)
     else if (n == "persistent_heads") *value = h->persist_heads;
     else if (n == "persistent_lora") *value = h->persist_lora;
@@ -397,7 +409,14 @@ extern "C" int ctts_gpt_get_option(ctts_gpt* h, const char* name, int* value) {
 extern "C" int ctts_gpt_set_option(ctts_gpt* h, const char* name, int value) {
     if (!h || !name) { ctts_set_error("set_option: null argument"); return 1; }
     const std::string n(name);
-    if (n == "prefill_split_rows") {             // prompt passes of >= this many rows use the head / tail fp16 split GEMMs (fp32 engines); 0 = never.  Before finalize.
+    if (n == "batch_invariant") {                // fp32 engines: bit-identical rows whatever the batch / schedule (see batch_inv); before or after finalize
+        if (h->cfg.dtype != CTTS_DTYPE_F32) { ctts_set_error("set_option(batch_invariant): fp32 (parity) engines only"); return 1; }
+        if (value && h->finalized && !(h->split_ok && h->wsplit && h->whead_sp)) {
+            ctts_set_error("set_option(batch_invariant): this engine holds no head / tail weight images (a weight beyond the fp16 range, or split_decode_rows and prefill_split_rows were 0 at finalize)");
+            return 1;
+        }
+        h->batch_inv = value ? 1 : 0;
+    } else if (n == "prefill_split_rows") {             // prompt passes of >= this many rows use the head / tail fp16 split GEMMs (fp32 engines); 0 = never.  Before finalize.
         // before finalize: also decides whether the images are built; afterwards the pass can be switched off (0: a checkpoint that leaves the fp16 range, see
         // ctts_gpt_saturations) or moved while the images exist
         if (h->finalized && value > 0 && !(h->split_ok && h->wsplit)) { ctts_set_error("set_option(prefill_split_rows): this engine holds no head / tail weight images (fp16 engine, a weight beyond the fp16 range, or the option was 0 at finalize)"); return 1; }
@@ -493,7 +512,7 @@ extern "C" void ctts_gpt_destroy(ctts_gpt* h) {
     void* bufs[] = {h->sk_scratch, h->dyn, h->wblob, h->wsplit, h->whead_sp, h->sp_x_hi, h->sp_x_lo, h->sp_act_hi, h->sp_act_lo, h->whead_text, h->lnf, h->emb_code, h->emb_text, h->rope, h->x_dec, h->x_last, h->x_pre, h->q_buf, h->part_ml, h->part_o, h->logits,
                     h->act, h->attn_packed, h->norm_packed, h->dpart, h->rope_pre, h->rope_dec, h->meta_pre, h->meta_dec, h->meta_dec0, h->st, h->last_rows,
                     h->hist_ring, h->sat, h->finend, h->xh, h->ssq, h->scale_o, h->scale_d, h->cx, h->crope, h->cmeta, h->cring, h->cfin, h->keep_dev,
-                    h->lora_A, h->lora_B, h->lora_Af, h->lora_scale, h->ln1, h->lora_slot_of_seq, h->lora_dqkv, h->lora_do, h->lora_g, h->pimg, h->pimg_head, h->pl_g, h->pl_epoch, h->pl_error, h->pl_ts, h->sk_slab, h->sk_cnt};
+                    h->lora_A, h->lora_B, h->lora_Af, h->lora_scale, h->ln1, h->lora_slot_of_seq, h->lora_dqkv, h->lora_do, h->lora_g, h->pimg, h->pimg_head, h->pl_g, h->pl_epoch, h->pl_error, h->pl_ts, h->sk_slab, h->sk_cnt, h->rope_dec0};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (h->host_pin) (void)hipHostFree(h->host_pin);
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
@@ -718,7 +737,7 @@ static int finalize_t(ctts_gpt* h) {
     h->lw.resize(L);
     if (dev_alloc((void**)&h->wblob, total * sizeof(WT))) return 1;
     // fp32 engine whose prompt passes can reach the split-GEMM threshold, or whose decode batches can reach split_decode_rows: head / tail fp16 images of the layer matrices too
-    const bool want_split = (sizeof(WT) == 4) && ((h->split_rows_min > 0 && (long)h->cfg.max_batch * h->cfg.max_seq >= h->split_rows_min) ||
+    const bool want_split = (sizeof(WT) == 4) && (h->batch_inv || (h->split_rows_min > 0 && (long)h->cfg.max_batch * h->cfg.max_seq >= h->split_rows_min) ||
                                                    (h->split_dec_rows > 0 && h->cfg.max_batch >= h->split_dec_rows));
     std::vector<half_t> sblob;
     if (want_split) {
@@ -818,7 +837,7 @@ static int finalize_t(ctts_gpt* h) {
         return pr < nvalid ? folded.data() + (size_t)pr * H : nullptr;
     }, nf->data());
     h->whead = h->wblob + per_layer * L * sizeof(WT);
-    if (h->split_ok && h->split_dec_rows > 0) {      // the code heads' split images (the decode path's last projection)
+    if (h->split_ok && (h->split_dec_rows > 0 || h->batch_inv)) {      // the code heads' split images (the decode path's last projection)
         std::vector<half_t> hs((size_t)head_tiles * 16 * H * 2);
         const bool ok = pack_tiles_split(hs.data(), head_tiles, H, [&](int pr) -> const float* { return pr < nvalid ? folded.data() + (size_t)pr * H : nullptr; }, nf->data());
         if (ok) {
@@ -890,7 +909,8 @@ extern "C" int ctts_gpt_finalize(ctts_gpt* h) {
         dev_alloc((void**)&h->cmeta, CTTS_MAX_B * sizeof(RowMeta)) || dev_alloc((void**)&h->cring, (size_t)CTTS_MAX_B * CTTS_NUM_VQ * 16 * 4) ||
         dev_alloc((void**)&h->cfin, (size_t)CTTS_MAX_B * sizeof(RowState)) || dev_alloc((void**)&h->keep_dev, CTTS_MAX_B * 4) ||
         dev_alloc(&h->xh, (size_t)((CTTS_MAX_B + 32) / 16) * (H / (h->esz == 2 ? 32 : 16)) * 1024) || dev_alloc((void**)&h->ssq, (size_t)(CTTS_MAX_B + 32) * (H / 16) * 4) ||
-        dev_alloc((void**)&h->scale_o, (size_t)(CTTS_MAX_B + 32) * 4) || dev_alloc((void**)&h->scale_d, (size_t)(CTTS_MAX_B + 32) * 4))
+        dev_alloc((void**)&h->scale_o, (size_t)(CTTS_MAX_B + 32) * 4) || dev_alloc((void**)&h->scale_d, (size_t)(CTTS_MAX_B + 32) * 4) ||
+        dev_alloc((void**)&h->rope_dec0, (size_t)CTTS_MAX_B * 64 * 4))
         return 1;
     if (h->wsplit) {     // operand images of the prompt rows for the split GEMMs: heads / tails of the normalised rows | attention outputs (K = 768) and of the SwiGLU outputs (K = 3072)
         const size_t rows = (size_t)PASS_ROWS + PASS_PAD;
@@ -955,6 +975,7 @@ static inline void* kv_layer(ctts_gpt* h, int l, int which) {
 // in o_proj (S = 1 lets the attention write o_proj's packed operand directly): from 4 rows on, split only when one
 // 8-wave block would otherwise loop over more than ~768 keys.
 static inline int decode_splits(const ctts_gpt* h, int B, int L) {
+    if (h->batch_inv) return 1;                            // a function of neither the batch nor the longest row
     if (h->lora_rows) return 1;                            // per-utterance LoRA reads the attention output from o_proj's packed operand (S = 1 path)
     if (h->force_splits) return h->force_splits;
     int cap = 256 / (B * h->NH);
@@ -973,15 +994,17 @@ struct StreamForm { bool parts; bool xh; bool logits; bool split; };     // x = 
 static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* rope_rows, int R, int S, const DevState* st, hipStream_t s, StreamForm* form = nullptr) {
     const int dt = h->cfg.dtype;
     const bool lora = h->lora_rows != 0;                   // per-utterance adapters: the residual stream must be materialised in x (no split-K partials)
+    const bool inv = h->batch_inv != 0;                    // "batch_invariant": every choice below that depends on R is pinned (ctts_gpt_begin refuses adapters then)
     // fp32 engines, decode batches of >= split_decode_rows rows: head / tail fp16 operands (the predicate is completed below; it needs the packed-residual path)
-    const bool spd_ok = st != nullptr && dt == CTTS_DTYPE_F32 && h->xh_mode && h->split_ok && h->wsplit != nullptr && h->split_dec_rows > 0 && R >= h->split_dec_rows && R > h->split_rows && !lora && S == 1;
-    const int nbg = (R <= 16 || (st != nullptr && R < (spd_ok ? h->split_nbg2_rows : h->nbg2_rows))) ? 1 : 2;     // decode rows: see nbg2_rows / split_nbg2_rows
+    const bool spd_ok = st != nullptr && dt == CTTS_DTYPE_F32 && h->xh_mode && h->split_ok && h->wsplit != nullptr && !lora && S == 1 &&
+                        (inv || (h->split_dec_rows > 0 && R >= h->split_dec_rows && R > h->split_rows));      // (invariant: 1..8 rows too, one padded 16-row chunk)
+    const int nbg = (R <= 16 || (st != nullptr && (inv || R < (spd_ok ? h->split_nbg2_rows : h->nbg2_rows)))) ? 1 : 2;     // decode rows: see nbg2_rows / split_nbg2_rows
     const int NB = 16 * nbg;
     const int chunks = (R + NB - 1) / NB;
     // small decode batches: the down projection is launched as 4 split-K slices (192 blocks instead of 48 x 1024 threads);
     // its partial sums dp[0..3] are added, in order, by the next consumers of the residual stream (QKV RMSNorm, o_proj
     // residual, final heads) -- deterministic, no atomics.  x itself is re-materialised by every o_proj.
-    const bool splitd = (st != nullptr) && (R <= h->split_rows) && (nbg == 1) && !lora;
+    const bool splitd = (st != nullptr) && (R <= h->split_rows) && (nbg == 1) && !lora && !inv;
     // prompt pass over more than a few chunks: normalise every row once (norm_pack_kernel) instead of in every GEMM block
     const bool prepack = (st == nullptr) && (nbg == 2) && (R > 64) && !h->no_prepack;
     // prompt pass over >= 1536 rows, fp16: LDS-staged 256/128 x 128 MFMA GEMM (prefill_gemm.hip) instead of one weight tile per 32-row block
@@ -991,9 +1014,11 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
     // prompt pass over >= 384 rows, fp32 engine: the same tiling on the fp16 pipes with head / tail operands -- 3 MFMAs per product instead of 16,
     // fp32-level accuracy (prefill_split.hip); the attention stays the fp32 row kernel
     // (round 5: also with per-utterance adapters -- their low-rank terms come from the two lora.hip launches per layer and are added in the split GEMMs' epilogues)
-    const bool pfs = prepack && (dt == CTTS_DTYPE_F32) && h->wsplit != nullptr && h->split_rows_min > 0 && (R >= h->split_rows_min);
+    // (invariant: every pass height, 1 row included -- the block shapes give bit-identical rows, tools/prefill_fuzz.py -- and the down projection's K never sliced)
+    const bool pfs = (dt == CTTS_DTYPE_F32) && h->wsplit != nullptr &&
+                     (inv ? (st == nullptr && h->split_ok) : (prepack && h->split_rows_min > 0 && (R >= h->split_rows_min)));
     const float sp_scale = 1.0f / 64.0f;
-    const SplitGemmPolicy sp_pol = {h->prefill_pp_blocks, h->prefill_sk_rows, h->sk_scratch, h->sk_cap_floats, h->prefill_small_blocks, h->prefill_ring4_blocks};
+    const SplitGemmPolicy sp_pol = {h->prefill_pp_blocks, inv ? 0 : h->prefill_sk_rows, h->sk_scratch, h->sk_cap_floats, h->prefill_small_blocks, h->prefill_ring4_blocks};
     // decode above the split-K batch sizes: the residual stream travels between kernels as a packed B operand in the engine dtype + per-tile
     // sums of squares (EPI_RESID_XH -> PRO_XH, kernels.h); layer 0 still normalises the sampler's fp32 rows itself.  (Handing gate|up
     // the packed copy at batches <= 4 too was measured slower in fp16: batch 1 393 vs 381 us/step, 2 415 vs 403, 4 450 vs 443.)
@@ -1004,7 +1029,7 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
     // exact-f32 ones (common.h split_t; the prompt pass's arithmetic, prefill_split.hip).  Layer 0's q|k|v projection normalises the sampler's fp32 rows and stays exact.
     const bool spd = xhm && spd_ok;
     const int dts = spd ? 2 : dt;                              // launch_gemm's operand format
-    if (st != nullptr && h->cur_persist && h->pimg != nullptr && R <= PL_MAXR) {
+    if (st != nullptr && h->cur_persist && h->pimg != nullptr && R <= PL_MAXR && !inv) {
         // one persistent launch per layer (persist_layer.hip): the residual stream stays in x, nothing is left in partial or packed form
         // the launch that ends the stack also runs the final norm + the 4 code heads (persist_layer.hip phase H): code mode, paced schedule, images built
         // (ms/step separate heads launch / fused, tools/ab_options.py: fp32 batch 1 0.2798 / 0.2786, 2 0.3396 / 0.3384, 4 0.4711 / 0.4721; fp16 batch 3 0.3793 / 0.3800 -> up to 2 rows)
@@ -1049,7 +1074,7 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
     for (int l = 0; l < h->L; ++l) {
         GemmArgs a = {};
         a.st = st; a.R = R; a.eps = 1e-6f; a.meta = meta; a.Lmax = h->cfg.max_seq; a.sat = h->sat;
-        a.valu = (st != nullptr && dt == CTTS_DTYPE_F32 && R <= h->valu_rows && !lora) ? 1 : 0;
+        a.valu = (st != nullptr && dt == CTTS_DTYPE_F32 && R <= h->valu_rows && !lora && !inv) ? 1 : 0;
         // RMSNorm + QKV + RoPE + KV append
         GemmArgs g1 = a;
         g1.W = h->lw[l].qkv; g1.n_row_tiles = 3 * h->H / 16; g1.K = h->H; g1.x = x;
@@ -1085,7 +1110,8 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
         } else if (launch_gemm(dt, nbg, splitd ? PRO_NORM_P : PRO_NORM, EPI_QKV, g1, chunks, s)) return 1;
         AttnArgs at = {};
         at.q = h->q_buf; at.k_cache = g1.k_cache; at.v_cache = g1.v_cache; at.Lmax = h->cfg.max_seq; at.NH = h->NH; at.R = R; at.S = S;
-        at.meta = meta; at.st = st; at.part_ml = h->part_ml; at.part_o = h->part_o; at.wide_blocks = h->attn_wide_blocks;
+        at.meta = meta; at.st = st; at.part_ml = h->part_ml; at.part_o = h->part_o; at.wide_blocks = inv ? 0x7FFFFFFF : h->attn_wide_blocks;
+        at.anchor = inv ? 1 : 0;
         if (st == nullptr) { at.T = h->pre_T; at.row0 = (int)(meta - h->meta_pre); }       // prompt pass: position of this pass in the flattened [B][T] prompt
         at.packed_out = (S == 1) ? h->attn_packed : nullptr; at.nbg = nbg; at.packed_split = spd ? 1 : 0;
         if (pfs && S == 1) { if (launch_attention_split(at, h->sp_x_hi, h->sp_x_lo, s)) return 1; }      // writes o_proj's head / tail operand images directly
@@ -1142,7 +1168,7 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
         } else if (xhm) {                          // (the last layer's copy is for the heads: run_heads)
             g4.xh = h->xh; g4.ssq = h->ssq; g4.scale_in = h->scale_d;
             if (spd) g4.W = h->lw[l].d_sp;
-            if ((nbg == 1 || spd) && R >= h->down_sk_rows && h->down_sk_rows > 0) {
+            if (inv || ((nbg == 1 || spd) && R >= h->down_sk_rows && h->down_sk_rows > 0)) {
                 // K sliced 4 ways inside the launch, last arriver combines (EPI_RESID_XH_SK, kernels.h)
                 g4.ktiles_total = h->I / ((h->esz == 2 || spd) ? 32 : 16); g4.sk_slab = h->sk_slab; g4.sk_cnt = h->sk_cnt;
                 if (launch_gemm(dts, nbg, PRO_PACKED, EPI_RESID_XH_SK, g4, chunks, s)) return 1;
@@ -1154,11 +1180,11 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
 
 // final RMSNorm + heads on the h->B decode rows; `form` = how the last run_layers left them (all false after a prompt pass / restart)
 static int run_heads(ctts_gpt* h, bool write_hidden, StreamForm form, hipStream_t s) {
-    const int nbg = (h->B <= 16 || h->B < (form.split ? h->split_nbg2_rows : h->nbg2_rows)) ? 1 : 2;      // (the packed rows' layout does not depend on the producer's block height)
+    const int nbg = (h->B <= 16 || h->batch_inv || h->B < (form.split ? h->split_nbg2_rows : h->nbg2_rows)) ? 1 : 2;      // (the packed rows' layout does not depend on the producer's block height)
     const int chunks = (h->B + 16 * nbg - 1) / (16 * nbg);
     GemmArgs a = {};
     a.st = h->st; a.R = h->B; a.eps = 1e-6f; a.meta = h->meta_dec;
-    a.valu = (h->cfg.dtype == CTTS_DTYPE_F32 && h->B <= h->valu_rows) ? 1 : 0;
+    a.valu = (h->cfg.dtype == CTTS_DTYPE_F32 && h->B <= h->valu_rows && !h->batch_inv) ? 1 : 0;
     const int nv = h->text_mode ? h->vocab_text_head : h->NVQ * h->V;
     a.W = h->text_mode ? h->whead_text : h->whead; a.n_row_tiles = (nv + 15) / 16; a.K = h->H; a.x = h->x_dec; a.lnw = h->lnf;
     a.logits = h->logits; a.n_valid = nv;
@@ -1218,6 +1244,10 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
         if (sc->use_penalty) { ctts_set_error("begin: infer_text supports repetition_penalty == 1 only (the reference's processor mis-broadcasts the [B,n,1] history in this mode)"); return 1; }
         if (sc->eos_token >= h->vocab_text_head) { ctts_set_error("begin: eos out of range"); return 1; }
     } else if (sc->past_window > 16 || sc->eos_token >= h->V) { ctts_set_error("begin: past_window>16 or eos out of range"); return 1; }
+    if (h->batch_inv && !(h->split_ok && h->wsplit && h->whead_sp)) {
+        ctts_set_error("begin: batch_invariant needs the head / tail weight images, and a weight of this checkpoint is beyond the fp16 range (x 64)");
+        return 1;
+    }
     hipStream_t s = (hipStream_t)stream;
     h->B = B; h->B0 = B; h->T = T; h->io = *io;
     h->admitted = false;
@@ -1241,6 +1271,11 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
         bool any = false;
         for (int b = 0; b < CTTS_MAX_B; ++b) { h->lora_row_slots[b] = (signed char)h->lora_slot_host[b]; any = any || (b < B && h->lora_slot_host[b] >= 0); }
         h->lora_rows = any ? 1 : 0;
+        if (h->lora_rows && h->batch_inv) {
+            h->lora_rows = 0; h->B = 0;
+            ctts_set_error("begin: per-utterance adapters (ctts_gpt_set_row_adapters) are outside the batch_invariant contract; set the option to 0 or merge the adapter");
+            return 1;
+        }
         if (h->lora_slot_of_seq)        // (pageable source: staged before the call returns)
             CTTS_HIP_CHECK(hipMemcpyAsync(h->lora_slot_of_seq, h->lora_slot_host.data(), CTTS_MAX_B * 4, hipMemcpyHostToDevice, (hipStream_t)stream));
         // the folded launches tag their granules with the sampler's draw counter, which restarts at every begin(): forget the previous call's granules, or a tile could
@@ -1260,15 +1295,59 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
     d.rows0 = B * (h->text_mode ? 1 : CTTS_NUM_VQ);
     CTTS_HIP_CHECK(hipMemcpyAsync(h->dyn, &d, sizeof(d), hipMemcpyHostToDevice, s));       // pageable source: staged before the call returns
     if (launch_fill_meta(h->meta_pre, h->meta_dec0, h->st, mask, B, T, h->rope, h->rope_pre, s)) return 1;
+    if (h->batch_inv) {
+        // the prompt is laid out like an admission of every row (ctts_gpt_admit): T - 1 prompt rows per sequence for the prompt pass, the decode rows at the last
+        // token (slot T - 1: the same RowMeta as meta_dec0) with its RoPE row -- ctts_gpt_prefill fills x_dec with the last tokens' embeddings
+        h->pre_T = T - 1;
+        h->keep_host.resize(B);
+        for (int b = 0; b < B; ++b) h->keep_host[b] = b;
+        CTTS_HIP_CHECK(hipMemcpyAsync(h->keep_dev, h->keep_host.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));      // rows == KV lanes
+        CTTS_HIP_CHECK(hipMemcpyAsync(h->cfin, h->rows_host.data(), (size_t)B * sizeof(RowState), hipMemcpyHostToDevice, s));
+        AdmitArgs a = {};
+        a.mask = mask; a.emb = nullptr; a.rows = h->keep_dev; a.seqs = h->keep_dev; a.fresh = h->cfin; a.n = B; a.T = T; a.H = h->H;
+        a.pm = h->meta_pre; a.rope_pre = h->rope_pre; a.dm = h->meta_dec; a.rope_dec = h->rope_dec; a.x_dec = h->x_dec; a.ring = h->hist_ring; a.finend = h->finend;
+        a.rope = h->rope; a.st = h->st; a.finish = io->finish; a.end_idx = io->end_idx; a.begin = 1;
+        if (launch_admit_rows(a, s)) return 1;
+        CTTS_HIP_CHECK(hipMemcpyAsync(h->rope_dec0, h->rope_dec, (size_t)B * 64 * 4, hipMemcpyDeviceToDevice, s));
+    }
     CTTS_HIP_CHECK(hipMemsetAsync(h->sat, 0, 4, s));
     if (h->pl_error) CTTS_HIP_CHECK(hipMemsetAsync(h->pl_error, 0, 4, s));
     return reset_state(h, false, s);
+}
+
+// batch_invariant prompt pass: the first T - 1 tokens of every sequence, laid out [B][T - 1] (ctts_gpt_begin), in passes of at most pass_rows rows; the last
+// token's embedding becomes the decode row's input, which ctts_gpt_sample runs through the first layer pass -- the admission path (ctts_gpt_admit), so a begun
+// utterance and an admitted one take the same arithmetic
+static int prefill_invariant(ctts_gpt* h, const float* emb, hipStream_t s) {
+    const int B = h->B, T = h->T, Tm = T - 1, H = h->H;
+    const long R = (long)B * Tm;
+    for (long r0 = 0; r0 < R; r0 += h->pass_rows) {
+        const int n = (int)(R - r0 < h->pass_rows ? R - r0 : h->pass_rows);
+        for (long r = r0; r < r0 + n;) {             // x_pre[0, n) <- prompt rows r0 .. r0 + n - 1 of the [B][T - 1] layout (emb is [B][T])
+            const long b = r / Tm, t = r % Tm, left = r0 + n - r;
+            if (t == 0 && left >= Tm) {
+                const long nb = left / Tm;
+                CTTS_HIP_CHECK(hipMemcpy2DAsync(h->x_pre + (size_t)(r - r0) * H, (size_t)Tm * H * 4, emb + (size_t)b * T * H, (size_t)T * H * 4, (size_t)Tm * H * 4, nb,
+                                                hipMemcpyDeviceToDevice, s));
+                r += nb * Tm;
+            } else {
+                const long len = (Tm - t < left) ? Tm - t : left;
+                CTTS_HIP_CHECK(hipMemcpyAsync(h->x_pre + (size_t)(r - r0) * H, emb + ((size_t)b * T + t) * H, (size_t)len * H * 4, hipMemcpyDeviceToDevice, s));
+                r += len;
+            }
+        }
+        if (run_layers(h, h->x_pre, h->meta_pre + r0, h->rope_pre + (size_t)r0 * 64, n, 1, nullptr, s)) return 1;
+    }
+    CTTS_HIP_CHECK(hipMemcpy2DAsync(h->x_dec, (size_t)H * 4, emb + (size_t)Tm * H, (size_t)T * H * 4, (size_t)H * 4, B, hipMemcpyDeviceToDevice, s));
+    CTTS_HIP_CHECK(hipMemcpyAsync(h->x_last, h->x_dec, (size_t)B * H * 4, hipMemcpyDeviceToDevice, s));       // (ensure_non_empty restarts replay from here)
+    return 0;
 }
 
 extern "C" int ctts_gpt_prefill(ctts_gpt* h, const float* emb, void* stream) {
     if (!h || !emb || h->B == 0) { ctts_set_error("prefill: call begin first"); return 1; }
     CTTS_RANGE("ctts_gpt_prefill");             // reference: nvtx "forward" (trt_models/llama_trt_model.py:44,74), q_len > 1
     hipStream_t s = (hipStream_t)stream;
+    if (h->batch_inv) return prefill_invariant(h, emb, s);
     const int R = h->B * h->T;
     const int PASS_ROWS = h->pass_rows;
     for (int r0 = 0; r0 < R; r0 += PASS_ROWS) {
@@ -1283,9 +1362,16 @@ extern "C" int ctts_gpt_prefill(ctts_gpt* h, const float* emb, void* stream) {
     return 0;
 }
 
+static inline int pick_decode_path(ctts_gpt* h, int longest);
+static int run_decode_step(ctts_gpt* h, hipStream_t s);
+
 extern "C" int ctts_gpt_sample(ctts_gpt* h, void* stream) {
     if (!h || h->B == 0) { ctts_set_error("sample: call begin first"); return 1; }
     CTTS_RANGE("ctts_gpt_sample");
+    if (h->batch_inv) {          // the last prompt token's layer pass first (see prefill_invariant): a decode step
+        if (pick_decode_path(h, 0)) return 1;
+        return run_decode_step(h, (hipStream_t)stream);
+    }
     return run_sample_phase(h, StreamForm{false, false, false, false}, (hipStream_t)stream);
 }
 
@@ -1295,6 +1381,7 @@ extern "C" int ctts_gpt_restart(ctts_gpt* h, void* stream) {
     if (h->admitted) { ctts_set_error("restart: rows of this batch were handed to other utterances (ctts_gpt_admit); re-admit the utterance with attempt + 1 instead"); return 1; }
     hipStream_t s = (hipStream_t)stream;
     CTTS_HIP_CHECK(hipMemcpyAsync(h->x_dec, h->x_last, (size_t)h->B * h->H * 4, hipMemcpyDeviceToDevice, s));
+    if (h->batch_inv) CTTS_HIP_CHECK(hipMemcpyAsync(h->rope_dec, h->rope_dec0, (size_t)h->B * 64 * 4, hipMemcpyDeviceToDevice, s));      // the first layer pass again
     return reset_state(h, true, s);
 }
 
@@ -1341,6 +1428,7 @@ static inline int decode_persist(const ctts_gpt* h, int B, int L) {
 
 static inline int pick_decode_path(ctts_gpt* h, int longest) {
     h->cur_splits = decode_splits(h, h->B, longest);
+    if (h->batch_inv) { h->cur_persist = 0; return 0; }      // the launch chain at every row count
     if (h->persist_ok && h->pimg == nullptr && h->persist_rows > 0 && h->B <= h->persist_rows && (!h->lora_rows || h->persist_lora) && persist_images(h)) return 1;
     h->cur_persist = decode_persist(h, h->B, longest);
     return 0;
@@ -1533,6 +1621,7 @@ extern "C" int ctts_gpt_admit_adapters(ctts_gpt* h, int n, const int32_t* rows, 
         if (rows[i] < 0 || rows[i] >= h->B || slots[i] >= CTTS_MAX_ADAPTERS) { ctts_set_error("admit_adapters: row %d / slot %d out of range", rows[i], slots[i]); return 1; }
         any = any || slots[i] >= 0;
     }
+    if (any && h->batch_inv) { ctts_set_error("admit_adapters: per-utterance adapters are outside the batch_invariant contract; set the option to 0 or merge the adapter"); return 1; }
     if (any && lora_ensure_storage(h)) return 1;
     for (int i = 0; i < n; ++i) {
         const int sl = slots[i] < 0 ? -1 : slots[i];
@@ -1555,6 +1644,7 @@ extern "C" int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, co
     if (!h || h->B == 0) { ctts_set_error("admit: call begin first"); return 1; }
     if (!rows || !mask || !emb || !utt_ids || !out_index) { ctts_set_error("admit: null argument"); return 1; }
     if (h->io.noise != nullptr) { ctts_set_error("admit: device noise only (caller-supplied noise is indexed by the batch's draw counter)"); return 1; }
+    if (h->batch_inv && h->lora_rows) { ctts_set_error("admit: per-utterance adapters are outside the batch_invariant contract; set the option to 0 or merge the adapter"); return 1; }
     if (n < 1 || n > h->B || T < 1 || T + h->sc.max_new > h->cfg.max_seq || (long long)n * (T - 1) > h->pass_rows) {
         ctts_set_error("admit: n=%d of %d rows, T=%d (max_seq %d, %d prompt rows per pass)", n, h->B, T, h->cfg.max_seq, h->pass_rows);
         return 1;

@@ -110,6 +110,8 @@ struct AttnArgs {
     int packed_split;       //   fp32 engine: packed_out is the head / tail fp16 image pair of the split decode kernels (common.h split_t), not fp32 fragments
     int T, row0;            // prompt pass (MFMA flash kernel): prompt length and the flattened index b*T + t of the pass's first row
     int wide_blocks;        // decode, unsplit: 8-wave blocks while rows x heads < this (0 = 256: fewer blocks than CUs; option "attn_wide_blocks")
+    int anchor;             // prompt pass, fp32 engine (option "batch_invariant"): 64-key chunks start at the sequence's first real key instead of at multiples of 64,
+                            //   so that the left padding of a batch cannot regroup a query's online-softmax sum
 };
 
 struct SamplerCfgDev {      // mirrors ctts_sampler_cfg
@@ -210,6 +212,8 @@ struct AdmitArgs {
     RowMeta* pm; float* rope_pre;                 // [n][T-1]
     RowMeta* dm; float* rope_dec; float* x_dec; int* ring; RowState* finend;      // decode-row arrays
     const float* rope; DevState* st; int* finish; int* end_idx;
+    int begin;              // 1: ctts_gpt_begin of a batch_invariant engine lays out its prompt like an admission (emb may be null: x_dec is left alone; the batch's
+                            //    finished-row count is left alone -- no finished row is being replaced)
 };
 int launch_admit_rows(const AdmitArgs& a, hipStream_t s);
 int launch_compact_rows(const int* keep, int n_keep, int H, float* x, float* rope_rows, RowMeta* meta, int* ring, RowState* fin,

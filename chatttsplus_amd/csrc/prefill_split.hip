@@ -427,7 +427,7 @@ __global__ __launch_bounds__(64 * FS_WAVES) void attn_prefill_split_kernel(const
     typedef half_t (*ks_t)[64][FS_KPITCH];
     vt_t vth = (vt_t)fs_lds, vtl = (vt_t)(fs_lds + 2 * 64 * FS_PITCH * 2);
     ks_t ksh = (ks_t)(fs_lds + 4 * 64 * FS_PITCH * 2), ksl = (ks_t)(fs_lds + 4 * 64 * FS_PITCH * 2 + 2 * 64 * FS_KPITCH * 2);
-    __shared__ int range_s[FS_WAVES][3];
+    __shared__ int range_s[FS_WAVES][4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int qn = lane & 15, iq = lane >> 4;
     const int b = blockIdx.z, h = blockIdx.y, T = a.T;
@@ -439,14 +439,20 @@ __global__ __launch_bounds__(64 * FS_WAVES) void attn_prefill_split_kernel(const
     const int lo = live ? m.kv_start : 0x7FFFFFFF, hi = live ? m.slot : -1;
     int wlo = lo, whi = hi;                                               // wave-uniform key range
     int wsq = live ? m.seq : -1;                                          // KV lane of this block's sequence (b itself after begin; any lane after ctts_gpt_admit)
+    int wan = live ? m.kv_start : -1;                                     // the sequence's first real key: the largest kv_start (a pad query's kv_start is its own slot, before it)
 #pragma unroll
-    for (int off = 1; off < 16; off <<= 1) { wlo = min(wlo, __shfl_xor(wlo, off)); whi = max(whi, __shfl_xor(whi, off)); wsq = max(wsq, __shfl_xor(wsq, off)); }
-    if (lane == 0) { range_s[wave][0] = wlo; range_s[wave][1] = whi; range_s[wave][2] = wsq; }
+    for (int off = 1; off < 16; off <<= 1) {
+        wlo = min(wlo, __shfl_xor(wlo, off)); whi = max(whi, __shfl_xor(whi, off)); wsq = max(wsq, __shfl_xor(wsq, off)); wan = max(wan, __shfl_xor(wan, off));
+    }
+    if (lane == 0) { range_s[wave][0] = wlo; range_s[wave][1] = whi; range_s[wave][2] = wsq; range_s[wave][3] = wan; }
     __syncthreads();
-    int blo = range_s[0][0], bhi = range_s[0][1], cseq = range_s[0][2];
+    int blo = range_s[0][0], bhi = range_s[0][1], cseq = range_s[0][2], ban = range_s[0][3];
 #pragma unroll
-    for (int w = 1; w < FS_WAVES; ++w) { blo = min(blo, range_s[w][0]); bhi = max(bhi, range_s[w][1]); cseq = max(cseq, range_s[w][2]); }
+    for (int w = 1; w < FS_WAVES; ++w) { blo = min(blo, range_s[w][0]); bhi = max(bhi, range_s[w][1]); cseq = max(cseq, range_s[w][2]); ban = max(ban, range_s[w][3]); }
     if (bhi < 0) return;                                                  // no live query in this block (uniform)
+    // a.anchor (option "batch_invariant"): chunk boundaries at ban + 64 j, extended downwards over the pad queries -- a real query's keys [kv_start, slot] then fall into
+    // the same chunks, at the same lanes, whatever the padding in front of them (the default: absolute multiples of 64)
+    const int c0 = a.anchor ? ban - 64 * ((ban - blo + 63) / 64) : (blo & ~63);
     wlo = __builtin_amdgcn_readfirstlane(wlo); whi = __builtin_amdgcn_readfirstlane(whi);
     const size_t head_off = ((size_t)cseq * NHp + h) * a.Lmax * CTTS_HEAD_DIM;
     const float* kb = k_p + head_off;
@@ -478,7 +484,8 @@ __global__ __launch_bounds__(64 * FS_WAVES) void attn_prefill_split_kernel(const
     const int skey = tid / SPK, sdim = 4 * (tid % SPK);
     f32x4 vst[SNI], kst[SNI];
     auto vload = [&](int c) {
-        const int key = min(c + skey, bhi);                               // clamp: a valid slot of this sequence (masked later)
+        int key = min(c + skey, bhi);                                     // clamp: a valid slot of this sequence (masked later)
+        if (a.anchor) key = max(key, blo);                                //   (an anchored first chunk may start below slot 0)
         const f32x4* vp = (const f32x4*)(vb + (size_t)key * CTTS_HEAD_DIM + sdim);
         const f32x4* kp = (const f32x4*)(kb + (size_t)key * CTTS_HEAD_DIM + sdim);
 #pragma unroll
@@ -496,7 +503,6 @@ __global__ __launch_bounds__(64 * FS_WAVES) void attn_prefill_split_kernel(const
             *(half4*)&ksl[buf][skey][sdim + 4 * SPK * i] = kl;
         }
     };
-    const int c0 = blo & ~63;
     vload(c0);
     vstore(0);
     __syncthreads();

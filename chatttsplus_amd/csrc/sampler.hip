@@ -754,7 +754,8 @@ __global__ __launch_bounds__(64) void admit_rows_kernel(const AdmitArgs a) {
     const int pos_last = max(cum - 1, 0);
     a.rope_dec[(size_t)row * 64 + lane] = a.rope[(size_t)pos_last * 64 + lane];
     a.ring[(size_t)row * 64 + lane] = -1;
-    for (int k = lane; k < a.H; k += 64) a.x_dec[(size_t)row * a.H + k] = a.emb[((size_t)i * T + T - 1) * a.H + k];
+    if (a.emb != nullptr)
+        for (int k = lane; k < a.H; k += 64) a.x_dec[(size_t)row * a.H + k] = a.emb[((size_t)i * T + T - 1) * a.H + k];
     if (lane == 0) {
         RowMeta d;
         d.seq = seq; d.pos = pos_last; d.slot = T - 1; d.kv_start = pad;
@@ -762,7 +763,7 @@ __global__ __launch_bounds__(64) void admit_rows_kernel(const AdmitArgs a) {
         const RowState r = a.fresh[i];
         a.finend[row] = r;
         a.finish[r.out] = 0; a.end_idx[r.out] = 0;
-        if (i == 0) { a.st->ticket -= a.n << 16; a.st->all_done = 0; }
+        if (i == 0 && !a.begin) { a.st->ticket -= a.n << 16; a.st->all_done = 0; }
     }
 }
 int launch_admit_rows(const AdmitArgs& a, hipStream_t s) {

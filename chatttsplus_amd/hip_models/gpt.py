@@ -347,11 +347,15 @@ class GPT:
 
     def set_row_adapters(self, slots) -> None:
         """Adapter slot (or -1 / None) per sequence for the following generate() calls; None switches the per-row path off.  With it
-        every q/k/v/o projection evaluates W x + scale * B (A x) per row (decode: inside the projection launches, lora_worker.h; prompt pass: two more launches per layer)."""
+        every q/k/v/o projection evaluates W x + scale * B (A x) per row (decode: inside the projection launches, lora_worker.h; prompt pass: two more launches per layer).
+        Not under options={"batch_invariant": 1}: per-utterance adapters are outside its contract (a merged adapter, with_lora(), is covered)."""
         with torch.cuda.device(self.device):
             if slots is None:
                 _lib.check(self._lib.ctts_gpt_set_row_adapters(self._h, None, 0), "set_row_adapters")
                 return
+            if self.options.get("batch_invariant", 0) and any(s is not None and int(s) >= 0 for s in slots):
+                raise _lib.HipBackendError("set_row_adapters: per-utterance adapters are outside the batch_invariant contract; construct the GPT with "
+                                           "options={'batch_invariant': 0}, or merge the adapter into a sibling engine (with_lora)")
             arr = np.ascontiguousarray([(-1 if s is None else int(s)) for s in slots], dtype=np.int32)
             _lib.check(self._lib.ctts_gpt_set_row_adapters(self._h, arr.ctypes.data_as(C.c_void_p), int(arr.size)), "set_row_adapters")
 
@@ -404,6 +408,11 @@ class GPT:
             import warnings
             if self.dtype_code == _lib.DTYPE_F16:
                 msg = f"use weight_dtype='fp32' for this checkpoint"
+            elif self.options.get("batch_invariant", 0):
+                # the option's contract is one arithmetic per row: switching kernels between calls would break it, so they stay
+                msg = ("the fp32 engine keeps silu(gate) * up / 16 and the scaled residual rows as fp16 head / tail images; THIS call's values were clipped there.  "
+                       "batch_invariant is on, so the engine keeps these kernels (results stay schedule-independent, and clipped); construct the GPT with "
+                       "options={'batch_invariant': 0, 'prefill_split_rows': 0, 'split_decode_rows': 0} to run this checkpoint on the exact fp32 kernels")
             else:
                 msg = ("the fp32 engine's prompt passes of more than 64 rows and its decode batches of >= 9 rows keep silu(gate) * up / 16 and the scaled residual rows as fp16 "
                        "head / tail images; THIS call's values were clipped there.  The engine now keeps the exact fp32 kernels (split_decode_rows=0, prefill_split_rows=0) for "
@@ -743,6 +752,16 @@ class GPT:
                 order = sorted(range(N), key=(lambda u: (-lims[u], u)) if row_limits is not None else (lambda u: (-lens[u], u)))
             else:
                 order = list(range(N))
+            back = list(range(N))                                  # position in the buffers below -> utterance index
+            if order != back:
+                # ctts_gpt_begin writes row r's outputs at index r: the request is served permuted (position j holds utterance order[j]) and every index
+                # handed back is mapped through `back` -- seating utterance order[r] in row r had them written at r and read at order[r]
+                pt = torch.as_tensor(order, dtype=torch.long, device=dev)
+                emb, mask = emb.index_select(0, pt), mask.index_select(0, pt)
+                lens, uids, lims = [lens[u] for u in order], [uids[u] for u in order], [lims[u] for u in order]
+                if slots is not None:
+                    slots = [slots[u] for u in order]
+                back, order = order, list(range(N))
             first = order[:R]
             Ta, emb_a, mask_a = prompts_of(first)
             uid_arr = np.ascontiguousarray([uids[u] for u in first], dtype=np.uint64)
@@ -781,13 +800,13 @@ class GPT:
                 if progress:
                     live = [(book.tickets[tk][0], int(end)) for tk, (fin, end) in zip(lay, states) if tk is not None and tk in book.tickets and not fin and end > 0]
                     if live:
-                        yield ("progress", [(u, n, ids[u, :n, 0].to(torch.long) if infer_text else ids[u, :n].to(torch.long), hid[u, :n] if hid is not None else None)
+                        yield ("progress", [(back[u], n, ids[u, :n, 0].to(torch.long) if infer_text else ids[u, :n].to(torch.long), hid[u, :n] if hid is not None else None)
                                             for u, n in live])
                 finished_now, again = book.report(lay, states, ensure_non_empty, max_restarts)
                 queue = again + queue                              # first token was EOS (gpt.py:496-525): next noise attempt, ahead of the queue
                 n_done += len(finished_now)
                 if finished_now:
-                    yield [(u, ids[u, :n, 0].to(torch.long) if infer_text else ids[u, :n].to(torch.long), hid[u, :n] if hid is not None else None) for u, n in finished_now]
+                    yield [(back[u], ids[u, :n, 0].to(torch.long) if infer_text else ids[u, :n].to(torch.long), hid[u, :n] if hid is not None else None) for u, n in finished_now]
                 free = book.free_rows()
                 since_free = since_free + 1 if free else 0
                 if queue and free and (len(free) >= min(admit_min, len(queue)) or since_free >= 4 or len(free) == len(book.row_tk)):
@@ -825,6 +844,10 @@ class GPT:
             steps, alld = C.c_int32(0), C.c_int32(0)
             _lib.check(lib.ctts_gpt_progress(h, C.byref(steps), C.byref(alld), st), "progress")
             self.saturations = self._report_saturations(h, st, "generate_many()")
+            if back != order:                                      # input order again
+                inv = torch.as_tensor(np.argsort(np.asarray(back)), dtype=torch.long, device=dev)
+                ids, end_idx = ids.index_select(0, inv), end_idx.index_select(0, inv)
+                hid = hid.index_select(0, inv) if hid is not None else None
             return self._outputs(ids, hid, end_idx, infer_text)
 
     def _staging(self, rows: int, V: int, cap: int):

@@ -105,6 +105,28 @@ void ctts_gpt_destroy(ctts_gpt* h);
  *   "lora_fold"           per-utterance adapters at decode: 1 (default) = the rows' low-rank terms come from worker workgroups inside the QKV / o_proj launches
  *                         (lora_worker.h), 0 = two more launches per layer (lora.hip; the prompt pass always uses those)
  *   "persistent_fault"    test hook: one workgroup withholds a hand-off in layer value - 1 (the bounded waits must end the step with an error)
+ *   "batch_invariant"     fp32 (parity) engines, default 0 (fp16 engines: setting it is an error).  1 = the batch-invariance contract below.  Before or after
+ *                         finalize (after: the engine must hold the head / tail weight images).
+ *       CONTRACT (device noise, ctts_gen_io.noise == NULL; one engine = weights + max_seq): an utterance's hidden rows, token ids, end_idx -- and the mel computed
+ *       from them -- are identical BIT FOR BIT whatever the schedule.  They are a function of its own inputs only (prompt ids, speaker, sampling parameters,
+ *       token limit, utterance id, attempt), not of: the batch size, max_batch or its row; the other utterances of the batch, their prompt lengths (the left
+ *       padding); finished-row compaction (ctts_gpt_compact); being started by ctts_gpt_begin or seated by ctts_gpt_admit, and at which step; the service
+ *       order, slice size or number of ranks of the host.  (The repetition-penalty row quirk, SURVEY F8, needs >= 157 rows: beyond CTTS_MAX_BATCH.)
+ *       How: every choice that depended on the row count, the pass height or the padding is pinned -- decode projections on the 3-term fp16 head / tail split
+ *       MFMAs in 16-row chunks at every row count (1..8 rows too, one padded chunk), the down projection's K always sliced 4 ways with the fixed-order
+ *       last-arriver combine, layer 0's q|k|v and the heads in one form, decode attention unsplit on 8-wave blocks (key loop anchored at the row's first
+ *       real key), no persistent launch, no VALU rows; every prompt pass on the split GEMMs of prefill_split.hip (the 1-row pass too), K never sliced, the
+ *       prompt attention's 64-key chunks anchored at the first real key; ctts_gpt_prefill passes T - 1 prompt tokens and the last one runs through the
+ *       layer pass of the first decode step (ctts_gpt_sample), exactly as after ctts_gpt_admit (ctts_gpt_restart replays that pass).
+ *       While the option is on, the tuning options it pins are IGNORED (their stored values return when it is switched off) and ctts_gpt_get_option reads the
+ *       effective values: persistent_rows 0, valu_rows 0, split_decode_rows 1, split_rows 0, down_splitk_rows 1, nbg2_rows / split_nbg2_rows 0 (never),
+ *       decode_splits 1, attn_wide_blocks INT_MAX, prefill_split_rows 1, prefill_splitk_rows 0.  Block-shape options (prefill_pp_blocks, prefill_small_blocks,
+ *       prefill_ring4_blocks, weight_prefetch_kb) stay live: they do not change the arithmetic.
+ *       OUTSIDE the contract: caller-supplied noise (indexed by the batch's draw counter); per-utterance adapters (ctts_gpt_set_row_adapters /
+ *       ctts_gpt_admit_adapters: begin / admit with a live adapter row return an error naming the option; a merged adapter, ctts_gpt_merge_lora, is just
+ *       weights and is covered); ensure_non_empty restarts of a whole generate() batch (ctts_gpt_restart: the reference regenerates the slice, so an
+ *       utterance's attempt number depends on its slice -- reference semantics).  The refine-text pass (infer_text) runs the same pinned stack and is covered.
+ *       A checkpoint with a weight beyond the fp16 range (x 64) cannot take the option (begin returns an error).
  * Unknown names are an error. */
 int ctts_gpt_set_option(ctts_gpt* h, const char* name, int value);
 int ctts_gpt_get_option(ctts_gpt* h, const char* name, int* value);      /* the EFFECTIVE value ("persistent_rows" reads 0 where the mode is unavailable) */
