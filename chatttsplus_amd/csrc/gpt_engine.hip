@@ -242,6 +242,8 @@ struct ctts_gpt {
     int graph_steps_persist = 16;                // ... and per graph of the persistent paths (2 nodes per step: 32 nodes): the replay gap is 8.1 us whatever the graph
                                                  // holds (profiles/r05_trace_gaps_b1.json), 2.0 us per step at 4 steps, 0.5 us at 16
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    struct DecodeSeg { int n, splits, persist; };
+    std::vector<DecodeSeg> segs;                 // plan_decode: the steps of one decode call as runs of equal decode paths
 };
 
 static int dev_alloc(void** p, size_t bytes) {
@@ -1402,6 +1404,7 @@ static int advance_rows(ctts_gpt* h, int n_steps) {
 // within what one workgroup per (row, head) serves.
 // Returns the key splits per (row, head) (0 = launch chain): as many shares as keep every share within what a workgroup prefetches, at most 64 / (12 B) and
 // PL_SMAX; a context beyond twice that many prefetchable keys goes back to the launch chain (its attention spreads the keys over up to 96 workgroups).
+// Asked once per step (plan_decode): L is that step's longest context, so a step's share count does not depend on how its decode call was chunked.
 static inline int decode_persist(const ctts_gpt* h, int B, int L) {
     if (!(h->persist_rows > 0 && h->pimg != nullptr && B <= h->persist_rows && B <= PL_MAXR)) return 0;
     if (h->lora_rows && !(h->persist_lora && h->persist_sched == 3 && h->lora_Af != nullptr && h->H == PL_H)) return 0;      // per-utterance adapters ride inside the launch (round 6, paced schedule)
@@ -1517,28 +1520,50 @@ static int ensure_graph(ctts_gpt* h, int n_steps) {
     return 0;
 }
 
+// The decode path of every coming step (key splits, persistent share count) from THAT step's context alone: step i of the next n_steps sees the longest
+// row after i steps (what a call of i steps would pick).  A generation then runs the same kernels at every step however its caller chunks the calls (one
+// 512-step call used to run all its steps with the share count of its LAST context).  Consecutive steps with equal paths form one segment.
+static int plan_decode(ctts_gpt* h, int n_steps) {
+    h->segs.clear();
+    for (int i = 1; i <= n_steps; ++i) {
+        int longest = 1;
+        for (int r = 0; r < h->B; ++r) { const int c = std::min(h->row_ctx[r] + i, h->row_cap[r]); if (c > longest) longest = c; }
+        if (pick_decode_path(h, longest + 1)) return 1;
+        if (!h->segs.empty() && h->segs.back().splits == h->cur_splits && h->segs.back().persist == h->cur_persist) ++h->segs.back().n;
+        else h->segs.push_back({1, h->cur_splits, h->cur_persist});
+    }
+    return 0;
+}
+
+// one segment's steps: whole graph spans as replays, the rest (at most graph_steps - 1 steps) eagerly; launch = false: only capture the graphs
+static int run_segment(ctts_gpt* h, const ctts_gpt::DecodeSeg& sg, bool graphs, bool launch, hipStream_t s) {
+    h->cur_splits = sg.splits;
+    h->cur_persist = sg.persist;
+    int left = sg.n;
+    if (graphs) {
+        while (left >= h->graph_steps) {
+            const int span = graph_span(h, left);
+            if (ensure_graph(h, span)) return 1;
+            for (; left >= span; left -= span) if (launch) CTTS_HIP_CHECK(hipGraphLaunch(h->gexec, s));
+        }
+    }
+    if (launch) for (; left > 0; --left) if (run_decode_step(h, s)) return 1;
+    return 0;
+}
+
 extern "C" int ctts_gpt_decode(ctts_gpt* h, int n_steps, int use_graph, void* stream) {
     if (!h || h->B == 0) { ctts_set_error("decode: call begin first"); return 1; }
     CTTS_RANGE("ctts_gpt_decode");              // reference: nvtx "forward" per decode step + "execute" (trt_models/predictor.py:164)
     hipStream_t s = (hipStream_t)stream;
-    {
-        const int longest = advance_rows(h, n_steps) + 1;
-        if (pick_decode_path(h, longest)) return 1;
-    }
+    if (n_steps < 1) { h->launched += n_steps; return pick_decode_path(h, advance_rows(h, n_steps) + 1); }
+    if (plan_decode(h, n_steps)) return 1;
+    (void)advance_rows(h, n_steps);
     h->launched += n_steps;
-    PersistTurnGuard turn(h->cur_persist != 0, s);
+    bool persistent = false;
+    for (const auto& sg : h->segs) persistent = persistent || sg.persist != 0;
+    PersistTurnGuard turn(persistent, s);
     if (turn.rc) { ctts_set_error("decode: hipStreamWaitEvent failed"); return 1; }
-    if (use_graph) {
-        int left = n_steps;
-        while (left >= h->graph_steps) {
-            const int span = graph_span(h, left);
-            if (ensure_graph(h, span)) return 1;
-            for (; left >= span; left -= span) CTTS_HIP_CHECK(hipGraphLaunch(h->gexec, s));
-        }
-        for (; left > 0; --left) if (run_decode_step(h, s)) return 1;
-    } else {
-        for (int i = 0; i < n_steps; ++i) if (run_decode_step(h, s)) return 1;
-    }
+    for (const auto& sg : h->segs) if (run_segment(h, sg, use_graph != 0, true, s)) return 1;
     return 0;
 }
 
@@ -1766,27 +1791,15 @@ extern "C" int ctts_sampler_run(const ctts_sampler_cfg* sc, const float* logits,
 extern "C" int ctts_gpt_time_decode(ctts_gpt* h, int n_steps, float* ms_per_step, void* stream) {
     if (!h || h->B == 0 || n_steps < 1 || !ms_per_step) { ctts_set_error("time_decode: bad argument"); return 1; }
     hipStream_t s = (hipStream_t)stream;
-    // same chunking as generate(): 32 steps at a time, each chunk with the key-split count its context length asks for;
-    // the graphs of every split count the run will need are captured before the clock starts
+    // the steps run as ctts_gpt_decode runs them (plan_decode: each step's path from its own context); the graphs of every segment are captured
+    // before the clock starts
     n_steps = (n_steps + h->graph_steps - 1) / h->graph_steps * h->graph_steps;
-    const int CH = 32 / h->graph_steps * h->graph_steps > 0 ? 32 / h->graph_steps * h->graph_steps : h->graph_steps;
-    for (int pass = 0; pass < 2; ++pass) {
-        int launched = h->launched;
-        if (pass == 1) CTTS_HIP_CHECK(hipEventRecord(h->ev0, s));
-        for (int i = 0; i < n_steps; i += CH) {
-            const int n = (n_steps - i < CH) ? n_steps - i : CH;
-            int longest = 1;
-            for (int r = 0; r < h->B; ++r) { const int c = std::min(h->row_ctx[r] + (launched - h->launched) + n, h->row_cap[r]); if (c > longest) longest = c; }
-            if (pick_decode_path(h, longest + 1)) return 1;
-            launched += n;
-            for (int left = n; left > 0;) {              // (n is a multiple of graph_steps)
-                const int span = graph_span(h, left);
-                if (ensure_graph(h, span)) return 1;
-                for (; left >= span; left -= span) if (pass == 1) CTTS_HIP_CHECK(hipGraphLaunch(h->gexec, s));
-            }
-        }
-        if (pass == 1) { (void)advance_rows(h, launched - h->launched); h->launched = launched; }
-    }
+    if (plan_decode(h, n_steps)) return 1;
+    for (const auto& sg : h->segs) if (run_segment(h, sg, true, false, s)) return 1;
+    CTTS_HIP_CHECK(hipEventRecord(h->ev0, s));
+    for (const auto& sg : h->segs) if (run_segment(h, sg, true, true, s)) return 1;
+    (void)advance_rows(h, n_steps);
+    h->launched += n_steps;
     CTTS_HIP_CHECK(hipEventRecord(h->ev1, s));
     CTTS_HIP_CHECK(hipEventSynchronize(h->ev1));
     float ms = 0.f;
