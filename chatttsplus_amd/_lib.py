@@ -37,6 +37,21 @@ class SamplerCfg(C.Structure):
     ]
 
 
+class RowSampling(C.Structure):
+    """ctts_row_sampling: one utterance's sampling knobs (the fields of SamplerCfg an utterance may choose for itself)."""
+    _fields_ = [
+        ("temperature", C.c_float * NUM_VQ),
+        ("top_p_threshold", C.c_float),
+        ("top_k", C.c_int32),
+        ("min_tokens_to_keep", C.c_int32),
+        ("use_penalty", C.c_int32),
+        ("penalty_table", C.c_float * 17),
+        ("past_window", C.c_int32),
+        ("min_new_token", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 class GenIO(C.Structure):
     _fields_ = [
         ("ids", C.c_void_p),
@@ -95,9 +110,12 @@ SYMBOLS = [
     ("ctts_sampler_noise", C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     ("ctts_gpt_admit", C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     ("ctts_gpt_admit_adapters", C.c_int, [_P, C.c_int, _P, _P, _P]),
+    ("ctts_gpt_set_row_sampling", C.c_int, [_P, _P, C.c_int]),
+    ("ctts_gpt_admit_sampling", C.c_int, [_P, C.c_int, _P, _P, _P]),
     ("ctts_gpt_logits", C.c_int, [_P, _P, _P]),
     ("ctts_gpt_force_ids", C.c_int, [_P, _P, _P]),
     ("ctts_sampler_run", C.c_int, [C.POINTER(SamplerCfg), _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    ("ctts_sampler_run_rows", C.c_int, [C.POINTER(SamplerCfg), _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     ("ctts_gpt_time_decode", C.c_int, [_P, C.c_int, C.POINTER(C.c_float), _P]),
     ("ctts_gpt_step_bytes", C.c_double, [_P, C.c_int, C.c_double]),
     ("ctts_voc_create", C.c_int, [C.POINTER(VocCfg), C.POINTER(_P)]),

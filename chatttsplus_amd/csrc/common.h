@@ -49,6 +49,23 @@ struct RowState {
     int pad1;
 };
 
+// Per decode ROW sampling knobs (ctts_row_sampling of the header, same layout): what one utterance may choose for itself.  The table lives right
+// behind the RowState table in the same allocation, so the sampler derives its address from a preloaded kernel argument and the entry's loads
+// leave with the kernel's first batch.  Written by ctts_gpt_begin (hipMemcpyAsync) and re-packed / re-seated by the compact and admit kernels
+// (16-byte vector stores).  eos, max_input_ids and max_new stay per call (SamplerCfgDev).  112 bytes = 7 x 16: aligned 16-byte loads and copies.
+struct RowSampling {
+    float temperature[CTTS_NUM_VQ];
+    float top_p_threshold;   // (float)(1 - top_P); < 0 disables top-p
+    int top_k;               // max(top_K, min_keep); <= 0 disables top-k
+    int min_keep;
+    int use_penalty;
+    float penalty_table[17];
+    int past_window;         // 1..16
+    int min_new;
+    int pad;
+};
+static_assert(sizeof(RowSampling) == 112, "RowSampling: 7 x 16 bytes");
+
 // fragment-major ("xfrag") activation layout used for every MFMA B operand:
 //   element (n, k) of a [NB rows][K] chunk lives at
 //     fp16: ((g*KT + k/32)*64 + (n%16) + 16*((k/8)%4))*8 + k%8      halfs

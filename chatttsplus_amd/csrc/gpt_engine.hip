@@ -21,6 +21,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <cmath>
 #include <map>
 #include <mutex>
 #include <string>
@@ -216,6 +217,12 @@ struct ctts_gpt {
     int* hist_ring = nullptr;                    // sampler: repetition-penalty window ring [max_B][4][16] (sampler.hip)
     RowState* finend = nullptr;                  // sampler: per-row state [max_B] (common.h): mirror of {finish, end_idx}, noise key, token limit
     std::vector<RowState> rows_host;             //   its initial image for the current generate() (uploaded by begin)
+    RowSampling* knobs = nullptr;                // sampler: per-row sampling knobs [max_B] (common.h), in the same allocation right behind finend (fixed address: the
+                                                 //   captured graphs hold no per-call state)
+    RowSampling* cknobs = nullptr;               //   compaction gather target / staging of the knobs an admission seats
+    std::vector<RowSampling> knobs_host;         //   begin's image of rows 0..B-1
+    std::vector<RowSampling> knobs_req;          //   what ctts_gpt_set_row_sampling asked for, per sequence ("the following begin calls"; empty = the call's values)
+    std::vector<std::pair<int, RowSampling>> knobs_admit;   //   ctts_gpt_admit_sampling: (row, knobs) of the utterances the next ctts_gpt_admit seats
     // finished-row compaction (ctts_gpt_compact): gather targets + the kept row indices
     float *cx = nullptr, *crope = nullptr; RowMeta* cmeta = nullptr; int* cring = nullptr; RowState* cfin = nullptr; int* keep_dev = nullptr;
     std::vector<int> keep_host;
@@ -514,7 +521,7 @@ extern "C" void ctts_gpt_destroy(ctts_gpt* h) {
     void* bufs[] = {h->sk_scratch, h->dyn, h->wblob, h->wsplit, h->whead_sp, h->sp_x_hi, h->sp_x_lo, h->sp_act_hi, h->sp_act_lo, h->whead_text, h->lnf, h->emb_code, h->emb_text, h->rope, h->x_dec, h->x_last, h->x_pre, h->q_buf, h->part_ml, h->part_o, h->logits,
                     h->act, h->attn_packed, h->norm_packed, h->dpart, h->rope_pre, h->rope_dec, h->meta_pre, h->meta_dec, h->meta_dec0, h->st, h->last_rows,
                     h->hist_ring, h->sat, h->finend, h->xh, h->ssq, h->scale_o, h->scale_d, h->cx, h->crope, h->cmeta, h->cring, h->cfin, h->keep_dev,
-                    h->lora_A, h->lora_B, h->lora_Af, h->lora_scale, h->ln1, h->lora_slot_of_seq, h->lora_dqkv, h->lora_do, h->lora_g, h->pimg, h->pimg_head, h->pl_g, h->pl_epoch, h->pl_error, h->pl_ts, h->sk_slab, h->sk_cnt, h->rope_dec0};
+                    h->lora_A, h->lora_B, h->lora_Af, h->lora_scale, h->ln1, h->lora_slot_of_seq, h->lora_dqkv, h->lora_do, h->lora_g, h->pimg, h->pimg_head, h->pl_g, h->pl_epoch, h->pl_error, h->pl_ts, h->sk_slab, h->sk_cnt, h->rope_dec0, h->cknobs};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (h->host_pin) (void)hipHostFree(h->host_pin);
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
@@ -667,6 +674,65 @@ extern "C" int ctts_gpt_set_row_adapters(ctts_gpt* h, const int32_t* slots, int 
     h->lora_req_host = tab;
     for (int b = 0; b < CTTS_MAX_B; ++b) h->lora_row_slots[b] = (signed char)tab[b];      // rows == sequences until a compaction
     h->lora_rows = 1;
+    return 0;
+}
+
+// ---- per-utterance sampling knobs (RowSampling, common.h) ----------------------------------------
+static_assert(sizeof(ctts_row_sampling) == sizeof(RowSampling), "ctts_row_sampling and RowSampling share one layout");
+// ctts_sampler_cfg -> the device copy the kernels read (ctts_gpt_begin, stand-alone sampler)
+static SamplerCfgDev cfg_of_abi(const ctts_sampler_cfg& sc) {
+    SamplerCfgDev c = {};
+    memcpy(c.temperature, sc.temperature, sizeof(sc.temperature));
+    c.top_p_threshold = sc.top_p_threshold; c.top_k = sc.top_k; c.min_keep = sc.min_tokens_to_keep;
+    c.use_penalty = sc.use_penalty; memcpy(c.penalty_table, sc.penalty_table, sizeof(sc.penalty_table));
+    c.past_window = sc.past_window; c.max_input_ids = sc.max_input_ids; c.eos = sc.eos_token;
+    c.min_new = sc.min_new_token; c.max_new = sc.max_new_token;
+    return c;
+}
+static RowSampling knobs_of_cfg(const SamplerCfgDev& c) {
+    RowSampling r = {};
+    memcpy(r.temperature, c.temperature, sizeof(r.temperature));
+    r.top_p_threshold = c.top_p_threshold; r.top_k = c.top_k; r.min_keep = c.min_keep; r.use_penalty = c.use_penalty;
+    memcpy(r.penalty_table, c.penalty_table, sizeof(r.penalty_table));
+    r.past_window = c.past_window; r.min_new = c.min_new;
+    return r;
+}
+static RowSampling knobs_of_abi(const ctts_row_sampling& p) {
+    RowSampling r;
+    memcpy(&r, &p, sizeof(r));
+    r.pad = 0;
+    return r;
+}
+static int check_knobs(const ctts_row_sampling& p, int max_new, const char* who, int i) {
+    for (int v = 0; v < CTTS_NUM_VQ; ++v)
+        if (!std::isfinite(p.temperature[v]) || !(p.temperature[v] > 0.f)) { ctts_set_error("%s: entry %d: temperature[%d] = %g (must be finite and > 0)", who, i, v, (double)p.temperature[v]); return 1; }
+    if (p.top_k < 0) { ctts_set_error("%s: entry %d: top_k = %d < 0", who, i, p.top_k); return 1; }
+    if (p.min_tokens_to_keep < 1) { ctts_set_error("%s: entry %d: min_tokens_to_keep = %d < 1", who, i, p.min_tokens_to_keep); return 1; }
+    if (p.past_window < 1 || p.past_window > 16) { ctts_set_error("%s: entry %d: past_window = %d outside 1..16 (the penalty ring is 16 deep)", who, i, p.past_window); return 1; }
+    if (p.min_new_token > max_new) { ctts_set_error("%s: entry %d: min_new_token = %d > max_new_token = %d", who, i, p.min_new_token, max_new); return 1; }
+    return 0;
+}
+extern "C" int ctts_gpt_set_row_sampling(ctts_gpt* h, const ctts_row_sampling* per_seq, int B) {
+    if (!h) { ctts_set_error("set_row_sampling: null handle"); return 1; }
+    if (!per_seq || B <= 0) { h->knobs_req.clear(); return 0; }
+    if (B > CTTS_MAX_B) { ctts_set_error("set_row_sampling: B=%d > %d", B, CTTS_MAX_B); return 1; }
+    h->knobs_req.assign(B, RowSampling{});
+    for (int b = 0; b < B; ++b) h->knobs_req[b] = knobs_of_abi(per_seq[b]);      // checked by begin, against that call's max_new_token
+    return 0;
+}
+extern "C" int ctts_gpt_admit_sampling(ctts_gpt* h, int n, const int32_t* rows, const ctts_row_sampling* p, void* stream) {
+    (void)stream;        // host-side request: the next ctts_gpt_admit uploads the entries
+    if (!h || h->B == 0 || !rows || !p || n < 0) { ctts_set_error("admit_sampling: call begin first / null argument"); return 1; }
+    if (h->text_mode) { ctts_set_error("admit_sampling: per-utterance sampling parameters are code mode only (the refine-text pass keeps the call's values)"); return 1; }
+    for (int i = 0; i < n; ++i) {
+        if (rows[i] < 0 || rows[i] >= h->B) { ctts_set_error("admit_sampling: row %d of %d", rows[i], h->B); return 1; }
+        if (check_knobs(p[i], h->sc.max_new, "admit_sampling", i)) return 1;
+    }
+    for (int i = 0; i < n; ++i) {
+        bool found = false;
+        for (auto& e : h->knobs_admit) if (e.first == rows[i]) { e.second = knobs_of_abi(p[i]); found = true; }
+        if (!found) h->knobs_admit.emplace_back(rows[i], knobs_of_abi(p[i]));
+    }
     return 0;
 }
 
@@ -905,7 +971,8 @@ extern "C" int ctts_gpt_finalize(ctts_gpt* h) {
         dev_alloc((void**)&h->meta_dec, CTTS_MAX_B * sizeof(RowMeta)) || dev_alloc((void**)&h->meta_dec0, CTTS_MAX_B * sizeof(RowMeta)) ||
         dev_alloc((void**)&h->st, sizeof(DevState)) || dev_alloc((void**)&h->last_rows, CTTS_MAX_B * 4) ||
         dev_alloc((void**)&h->dyn, sizeof(SamplerDyn)) || dev_alloc((void**)&h->hist_ring, (size_t)CTTS_MAX_B * CTTS_NUM_VQ * 16 * 4) ||
-        dev_alloc((void**)&h->finend, (size_t)CTTS_MAX_B * sizeof(RowState)) || dev_alloc((void**)&h->sat, 4) ||
+        dev_alloc((void**)&h->finend, (size_t)CTTS_MAX_B * (sizeof(RowState) + sizeof(RowSampling))) || dev_alloc((void**)&h->sat, 4) ||
+        dev_alloc((void**)&h->cknobs, (size_t)CTTS_MAX_B * sizeof(RowSampling)) ||
         dev_alloc((void**)&h->sk_slab, (size_t)(H / 16) * (CTTS_MAX_B / 16) * 4 * 256 * 4) || dev_alloc((void**)&h->sk_cnt, (size_t)(H / 16) * (CTTS_MAX_B / 16) * 4) ||
         dev_alloc((void**)&h->cx, (size_t)CTTS_MAX_B * H * 4) || dev_alloc((void**)&h->crope, (size_t)CTTS_MAX_B * 64 * 4) ||
         dev_alloc((void**)&h->cmeta, CTTS_MAX_B * sizeof(RowMeta)) || dev_alloc((void**)&h->cring, (size_t)CTTS_MAX_B * CTTS_NUM_VQ * 16 * 4) ||
@@ -921,6 +988,7 @@ extern "C" int ctts_gpt_finalize(ctts_gpt* h) {
         h->sk_cap_floats = (size_t)4 * (size_t)(((PASS_ROWS < 2048 ? PASS_ROWS : 2048) + 127) / 128 * 128) * H;
         if (dev_alloc((void**)&h->sk_scratch, h->sk_cap_floats * 4)) return 1;
     }
+    h->knobs = (RowSampling*)(h->finend + CTTS_MAX_B);      // (the sampler derives this address from its finend argument)
     CTTS_HIP_CHECK(hipHostMalloc((void**)&h->host_pin, 64));
     {
         auto it = h->host.find("emb_text.weight");
@@ -1250,6 +1318,14 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
         ctts_set_error("begin: batch_invariant needs the head / tail weight images, and a weight of this checkpoint is beyond the fp16 range (x 64)");
         return 1;
     }
+    if (!h->knobs_req.empty()) {       // per-utterance sampling knobs (ctts_gpt_set_row_sampling)
+        if (h->text_mode) { ctts_set_error("begin: per-utterance sampling parameters (set_row_sampling) are code mode only; the refine-text pass (infer_text) keeps the call's values"); return 1; }
+        for (int b = 0; b < B && b < (int)h->knobs_req.size(); ++b) {
+            ctts_row_sampling p;
+            memcpy(&p, &h->knobs_req[b], sizeof(p));
+            if (check_knobs(p, sc->max_new_token, "begin (set_row_sampling)", b)) return 1;
+        }
+    }
     hipStream_t s = (hipStream_t)stream;
     h->B = B; h->B0 = B; h->T = T; h->io = *io;
     h->admitted = false;
@@ -1286,16 +1362,17 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
     }
     h->pre_T = T;
     h->io.utt_ids = nullptr; h->io.row_limits = nullptr;      // host arrays are consumed here, not kept
-    memcpy(h->sc.temperature, sc->temperature, sizeof(sc->temperature));
-    h->sc.top_p_threshold = sc->top_p_threshold; h->sc.top_k = sc->top_k; h->sc.min_keep = sc->min_tokens_to_keep;
-    h->sc.use_penalty = sc->use_penalty; memcpy(h->sc.penalty_table, sc->penalty_table, sizeof(sc->penalty_table));
-    h->sc.past_window = sc->past_window; h->sc.max_input_ids = sc->max_input_ids; h->sc.eos = sc->eos_token;
-    h->sc.min_new = sc->min_new_token; h->sc.max_new = sc->max_new_token;
+    h->sc = cfg_of_abi(*sc);
     SamplerDyn d = {};
     d.cfg = h->sc; d.n_draws = io->n_draws; d.ids = io->ids; d.finish = io->finish; d.end_idx = io->end_idx; d.noise = io->noise;
     d.seed = io->seed; d.hidden_out = io->hiddens; d.hidden_stride = sc->max_new_token * h->H;
     d.rows0 = B * (h->text_mode ? 1 : CTTS_NUM_VQ);
     CTTS_HIP_CHECK(hipMemcpyAsync(h->dyn, &d, sizeof(d), hipMemcpyHostToDevice, s));       // pageable source: staged before the call returns
+    // the rows' sampling knobs: the call's values, then what set_row_sampling requested per sequence
+    h->knobs_host.assign(B, knobs_of_cfg(h->sc));
+    for (int b = 0; b < B && b < (int)h->knobs_req.size(); ++b) h->knobs_host[b] = h->knobs_req[b];
+    h->knobs_admit.clear();
+    CTTS_HIP_CHECK(hipMemcpyAsync(h->knobs, h->knobs_host.data(), (size_t)B * sizeof(RowSampling), hipMemcpyHostToDevice, s));
     if (launch_fill_meta(h->meta_pre, h->meta_dec0, h->st, mask, B, T, h->rope, h->rope_pre, s)) return 1;
     if (h->batch_inv) {
         // the prompt is laid out like an admission of every row (ctts_gpt_admit): T - 1 prompt rows per sequence for the prompt pass, the decode rows at the last
@@ -1623,7 +1700,8 @@ extern "C" int ctts_gpt_compact(ctts_gpt* h, const int32_t* keep_rows, int n_kee
     hipStream_t s = (hipStream_t)stream;
     h->keep_host.assign(keep_rows, keep_rows + n_keep);
     CTTS_HIP_CHECK(hipMemcpyAsync(h->keep_dev, h->keep_host.data(), (size_t)n_keep * 4, hipMemcpyHostToDevice, s));
-    if (launch_compact_rows(h->keep_dev, n_keep, h->H, h->x_dec, h->rope_dec, h->meta_dec, h->hist_ring, h->finend, h->cx, h->crope, h->cmeta, h->cring, h->cfin, h->st, s)) return 1;
+    if (launch_compact_rows(h->keep_dev, n_keep, h->H, h->x_dec, h->rope_dec, h->meta_dec, h->hist_ring, h->finend, h->knobs, h->cx, h->crope, h->cmeta, h->cring, h->cfin,
+                            h->cknobs, h->st, s)) return 1;
     for (int i = 0; i < n_keep; ++i) { h->row_seq[i] = h->row_seq[keep_rows[i]]; h->row_ctx[i] = h->row_ctx[keep_rows[i]]; h->row_cap[i] = h->row_cap[keep_rows[i]]; }
     if (!h->lora_slot_host.empty()) for (int i = 0; i < n_keep; ++i) h->lora_row_slots[i] = (signed char)h->lora_slot_host[h->row_seq[i]];
     h->B = n_keep;
@@ -1667,6 +1745,9 @@ extern "C" int ctts_gpt_admit_adapters(ctts_gpt* h, int n, const int32_t* rows, 
 extern "C" int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, const int32_t* mask, const float* emb, const uint64_t* utt_ids,
                               const int32_t* row_limits, const int32_t* out_index, const int32_t* attempts, void* stream) {
     if (!h || h->B == 0) { ctts_set_error("admit: call begin first"); return 1; }
+    // what ctts_gpt_admit_sampling named is for THIS admission only, whether it goes through or fails below: a later admit never picks up a stale entry
+    std::vector<std::pair<int, RowSampling>> named;
+    named.swap(h->knobs_admit);
     if (!rows || !mask || !emb || !utt_ids || !out_index) { ctts_set_error("admit: null argument"); return 1; }
     if (h->io.noise != nullptr) { ctts_set_error("admit: device noise only (caller-supplied noise is indexed by the batch's draw counter)"); return 1; }
     if (h->batch_inv && h->lora_rows) { ctts_set_error("admit: per-utterance adapters are outside the batch_invariant contract; set the option to 0 or merge the adapter"); return 1; }
@@ -1692,14 +1773,20 @@ extern "C" int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, co
         r.out = out_index[i];
         if (r.out < 0) { ctts_set_error("admit: negative output index"); return 1; }
     }
+    // the new rows' sampling knobs: what ctts_gpt_admit_sampling named for the row, else the call's values (never the finished utterance's)
+    h->knobs_host.assign(n, knobs_of_cfg(h->sc));
+    for (int i = 0; i < n; ++i)
+        for (const auto& e : named) if (e.first == rows[i]) h->knobs_host[i] = e.second;
     int* rows_dev = h->keep_dev;
     int* seqs_dev = h->cring;                    // (compaction scratch: consumed in stream order)
     RowState* fresh_dev = h->cfin;
     CTTS_HIP_CHECK(hipMemcpyAsync(rows_dev, h->keep_host.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
     CTTS_HIP_CHECK(hipMemcpyAsync(seqs_dev, seqs.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
     CTTS_HIP_CHECK(hipMemcpyAsync(fresh_dev, h->fresh_host.data(), (size_t)n * sizeof(RowState), hipMemcpyHostToDevice, s));
+    CTTS_HIP_CHECK(hipMemcpyAsync(h->cknobs, h->knobs_host.data(), (size_t)n * sizeof(RowSampling), hipMemcpyHostToDevice, s));
     AdmitArgs a = {};
     a.mask = mask; a.emb = emb; a.rows = rows_dev; a.seqs = seqs_dev; a.fresh = fresh_dev; a.n = n; a.T = T; a.H = h->H;
+    a.fresh_knobs = h->cknobs; a.knobs = h->knobs;
     a.pm = h->meta_pre; a.rope_pre = h->rope_pre; a.dm = h->meta_dec; a.rope_dec = h->rope_dec; a.x_dec = h->x_dec; a.ring = h->hist_ring; a.finend = h->finend;
     a.rope = h->rope; a.st = h->st; a.finish = h->io.finish; a.end_idx = h->io.end_idx;
     if (launch_admit_rows(a, s)) return 1;
@@ -1759,33 +1846,54 @@ extern "C" int ctts_gpt_force_ids(ctts_gpt* h, const int32_t* ids, void* stream)
     return launch_embed_ids(ids, h->emb_code, h->x_dec, h->B, h->V, h->H, (hipStream_t)stream);
 }
 
-extern "C" int ctts_sampler_run(const ctts_sampler_cfg* sc, const float* logits, const int32_t* history, int hist_len, const float* q,
-                                int rows, int vocab, int step, int32_t* idx, void* stream) {
-    if (!sc || !logits || !q || !idx || (hist_len > 0 && !history)) { ctts_set_error("sampler_run: null argument"); return 1; }
-    // the kernels read their configuration from device memory: a small ring of slots, one per call in flight
+// Stand-alone sampler (ctts_sampler_run / ctts_sampler_run_rows): the kernels read their configuration -- and the per-sequence knobs -- from device
+// memory, a small ring of slots, one per call in flight.  per_seq == nullptr: every row uses the knobs of `sc`.
+static int sampler_run_standalone(const ctts_sampler_cfg* sc, const ctts_row_sampling* per_seq, const float* logits, const int32_t* history, int hist_len,
+                                  const float* q, int rows, int vocab, int step, int32_t* idx, void* stream, const char* who) {
+    if (!sc || !logits || !q || !idx || (hist_len > 0 && !history)) { ctts_set_error("%s: null argument", who); return 1; }
+    const int nseq = (rows + CTTS_NUM_VQ - 1) / CTTS_NUM_VQ;
+    if (per_seq) {
+        if (rows < 1 || nseq > CTTS_MAX_B) { ctts_set_error("%s: rows=%d (at most %d sequences of 4 rows)", who, rows, CTTS_MAX_B); return 1; }
+        for (int i = 0; i < nseq; ++i) if (check_knobs(per_seq[i], sc->max_new_token, who, i)) return 1;
+    }
     static std::mutex mu;
     static SamplerDyn* ring = nullptr;
+    static RowSampling* kring = nullptr;
     static unsigned next = 0;
     const unsigned NSLOT = 64;
-    SamplerDyn* slot;
+    unsigned k;
     {
         std::lock_guard<std::mutex> lk(mu);
         if (!ring) CTTS_HIP_CHECK(hipMalloc((void**)&ring, NSLOT * sizeof(SamplerDyn)));
-        slot = ring + (next++ % NSLOT);
+        if (per_seq && !kring) CTTS_HIP_CHECK(hipMalloc((void**)&kring, (size_t)NSLOT * CTTS_MAX_B * sizeof(RowSampling)));
+        k = next++ % NSLOT;
     }
     SamplerDyn d = {};
-    memcpy(d.cfg.temperature, sc->temperature, sizeof(sc->temperature));
-    d.cfg.top_p_threshold = sc->top_p_threshold; d.cfg.top_k = sc->top_k; d.cfg.min_keep = sc->min_tokens_to_keep;
-    d.cfg.use_penalty = sc->use_penalty; memcpy(d.cfg.penalty_table, sc->penalty_table, sizeof(sc->penalty_table));
-    d.cfg.past_window = sc->past_window; d.cfg.max_input_ids = sc->max_input_ids; d.cfg.eos = sc->eos_token;
-    d.cfg.min_new = sc->min_new_token; d.cfg.max_new = sc->max_new_token;
+    d.cfg = cfg_of_abi(*sc);
     d.noise = q;
-    CTTS_HIP_CHECK(hipMemcpyAsync(slot, &d, sizeof(d), hipMemcpyHostToDevice, (hipStream_t)stream));
+    CTTS_HIP_CHECK(hipMemcpyAsync(ring + k, &d, sizeof(d), hipMemcpyHostToDevice, (hipStream_t)stream));       // pageable sources: staged before the call returns
     SamplerArgs sa = {};
-    sa.dyn = slot;
+    sa.dyn = ring + k;
     sa.logits = logits; sa.V = vocab; sa.B = rows; sa.st = nullptr; sa.history = history; sa.hist_len = hist_len;
     sa.step_override = step; sa.idx_out = idx;
-    return launch_sampler(sa, (rows + 3) / 4, (hipStream_t)stream);
+    if (per_seq) {
+        std::vector<RowSampling> tab(nseq);
+        for (int i = 0; i < nseq; ++i) tab[i] = knobs_of_abi(per_seq[i]);
+        sa.seq_knobs = kring + (size_t)k * CTTS_MAX_B;
+        CTTS_HIP_CHECK(hipMemcpyAsync(kring + (size_t)k * CTTS_MAX_B, tab.data(), (size_t)nseq * sizeof(RowSampling), hipMemcpyHostToDevice, (hipStream_t)stream));
+    }
+    return launch_sampler(sa, nseq, (hipStream_t)stream);
+}
+
+extern "C" int ctts_sampler_run(const ctts_sampler_cfg* sc, const float* logits, const int32_t* history, int hist_len, const float* q,
+                                int rows, int vocab, int step, int32_t* idx, void* stream) {
+    return sampler_run_standalone(sc, nullptr, logits, history, hist_len, q, rows, vocab, step, idx, stream, "sampler_run");
+}
+
+extern "C" int ctts_sampler_run_rows(const ctts_sampler_cfg* sc, const ctts_row_sampling* per_seq, const float* logits, const int32_t* history, int hist_len,
+                                     const float* q, int rows, int vocab, int step, int32_t* idx, void* stream) {
+    if (!per_seq) { ctts_set_error("sampler_run_rows: null argument"); return 1; }
+    return sampler_run_standalone(sc, per_seq, logits, history, hist_len, q, rows, vocab, step, idx, stream, "sampler_run_rows");
 }
 
 extern "C" int ctts_gpt_time_decode(ctts_gpt* h, int n_steps, float* ms_per_step, void* stream) {

@@ -168,6 +168,7 @@ struct SamplerArgs {
     int hist_len;
     int step_override;
     int* idx_out;           // [rows]
+    const RowSampling* seq_knobs;   // ctts_sampler_run_rows: [rows / 4] knobs per sequence (null: every row uses dyn->cfg)
 };
 
 int launch_gemm(int dtype, int nbg, int pro, int epi, const GemmArgs& a, int chunks, hipStream_t s);
@@ -214,8 +215,10 @@ struct AdmitArgs {
     const float* rope; DevState* st; int* finish; int* end_idx;
     int begin;              // 1: ctts_gpt_begin of a batch_invariant engine lays out its prompt like an admission (emb may be null: x_dec is left alone; the batch's
                             //    finished-row count is left alone -- no finished row is being replaced)
+    const RowSampling* fresh_knobs;   // [n] device: the new rows' sampling knobs (null: the table is left alone -- begin uploads it itself)
+    RowSampling* knobs;               // the decode rows' knob table (common.h RowSampling)
 };
 int launch_admit_rows(const AdmitArgs& a, hipStream_t s);
-int launch_compact_rows(const int* keep, int n_keep, int H, float* x, float* rope_rows, RowMeta* meta, int* ring, RowState* fin,
-                        float* cx, float* crope, RowMeta* cmeta, int* cring, RowState* cfin, DevState* st, hipStream_t s);
+int launch_compact_rows(const int* keep, int n_keep, int H, float* x, float* rope_rows, RowMeta* meta, int* ring, RowState* fin, RowSampling* knobs,
+                        float* cx, float* crope, RowMeta* cmeta, int* cring, RowState* cfin, RowSampling* cknobs, DevState* st, hipStream_t s);
 int gemm_configure();

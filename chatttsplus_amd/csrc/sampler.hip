@@ -276,7 +276,11 @@ __global__ __launch_bounds__(256) void sampler_generate_kernel(const int* st_wor
     const int ring_v = ring_p[(size_t)(b * CTTS_NUM_VQ + vq) * 16 + (lane & 15)];
     const int4 fe = ((const int4*)(finend_p + b))[0];              // {fin, end, attempt, limit}
     const int4 uid = ((const int4*)(finend_p + b))[1];             // {uid_lo, uid_hi, out, -}
-    if (tid < 17) tab[tid] = d->cfg.penalty_table[tid];
+    // the row's sampling knobs (common.h RowSampling): indexed by the ROW b, in the table behind the RowState table -- an address known at launch as
+    // well (indexing by the utterance, uid.z, would put a dependent round trip in front of them).  Read through the constant address space, as d->cfg
+    // was: scalar loads off a preloaded argument.  eos / max_input_ids / max_new stay per call (d->cfg)
+    const CTTS_CONST_AS RowSampling* knob = (const CTTS_CONST_AS RowSampling*)(finend_p + CTTS_MAX_B) + b;
+    if (tid < 17) tab[tid] = knob->penalty_table[tid];
     const RowMeta meta_in = meta_p[b];
     if (__builtin_amdgcn_readfirstlane(hdr.z)) return;            // every sequence finished (gpt.py:545)
     const int gstep = __builtin_amdgcn_readfirstlane(hdr.x), draw = __builtin_amdgcn_readfirstlane(hdr.y);
@@ -292,17 +296,19 @@ __global__ __launch_bounds__(256) void sampler_generate_kernel(const int* st_wor
     in.q = (d->noise != nullptr) ? d->noise + ((size_t)min(draw, d->n_draws - 1) * d->rows0 + row) * a.V : nullptr;
     // ring slot p holds the id sampled at the latest step s < `step` with s % 16 == p: it is inside the window of the last
     // min(step, past_window) ids (processors.py:21-23 with gpt.py:455-457) iff its age step - s is at most that
-    const int nh = min(step, d->cfg.past_window);
+    const int nh = min(step, knob->past_window);
     const int age = ((step - 1 - lane) & 15) + 1;
     in.myid = (lane < 16 && age <= nh) ? ring_v : -1;
-    in.T = d->cfg.temperature[vq];
+    in.T = knob->temperature[vq];
     // quirk SURVEY F8: the reference zeroes the penalty for rows >= max_input_ids of the flattened [B * 4] batch IT runs -- the row's place in the
     // decode batch (b * 4 + vq <= 511), not the utterance's place in the caller's output arrays (`row`, which grows without bound under
     // ctts_gpt_admit / generate_many and silently switched the penalty off from utterance 157 on)
-    in.penalize = d->cfg.use_penalty && (b * CTTS_NUM_VQ + vq < d->cfg.max_input_ids) && nh > 0;
+    in.penalize = knob->use_penalty && (b * CTTS_NUM_VQ + vq < d->cfg.max_input_ids) && nh > 0;
     in.step = step;
     in.seed = d->seed; in.uid_lo = (unsigned)uid.x; in.uid_hi = (unsigned)uid.y; in.vq = (unsigned)vq; in.attempt = (unsigned)fe.z;
-    const int idx = sample_row(knobs_of(d), tab, in, a.V, lane, lg, cand_s[vq]);
+    SampleKnobs kn;
+    kn.top_p_threshold = knob->top_p_threshold; kn.top_k = knob->top_k; kn.min_keep = knob->min_keep; kn.eos = d->cfg.eos; kn.min_new = knob->min_new;
+    const int idx = sample_row(kn, tab, in, a.V, lane, lg, cand_s[vq]);
     if (lane == 0) {
         idx_s[vq] = idx;
         if (fin_in == 0) d->ids[((size_t)seq * d->cfg.max_new + step) * CTTS_NUM_VQ + vq] = idx;      // (a finished row's tokens are never read: gpt.py:295-297)
@@ -616,29 +622,38 @@ __global__ __launch_bounds__(1024) void sampler_text_kernel(const SamplerArgs a)
 }
 
 // stand-alone mode (ctts_sampler_run): block = 4 rows
+// ctts_sampler_run_rows: the same with knobs per sequence (sequence = row / 4 = the block), as the generate kernel reads them per decode row
 __global__ __launch_bounds__(256) void sampler_rows_kernel(const SamplerArgs a) {
     const int rows = a.B;
     const SamplerDynPtr d = (SamplerDynPtr)a.dyn;
     __shared__ float tab[17];
     __shared__ unsigned long long cand_s[4][64];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    if (tid < 17) tab[tid] = d->cfg.penalty_table[tid];
+    const RowSampling* sk = (a.seq_knobs != nullptr) ? a.seq_knobs + blockIdx.x : nullptr;
+    if (tid < 17) tab[tid] = sk ? sk->penalty_table[tid] : d->cfg.penalty_table[tid];
     __syncthreads();
     const int row = blockIdx.x * 4 + w;
     if (row >= rows) return;
+    SampleKnobs kn = knobs_of(d);
+    int past_window = d->cfg.past_window, use_penalty = d->cfg.use_penalty;
+    float T = d->cfg.temperature[row % CTTS_NUM_VQ];
+    if (sk) {
+        kn.top_p_threshold = sk->top_p_threshold; kn.top_k = sk->top_k; kn.min_keep = sk->min_keep; kn.min_new = sk->min_new;
+        past_window = sk->past_window; use_penalty = sk->use_penalty; T = sk->temperature[row % CTTS_NUM_VQ];
+    }
     RowIn in;
     const float* logits = a.logits + (size_t)row * a.V;
     in.q = d->noise + (size_t)row * a.V;
-    const int nh = min(a.hist_len, d->cfg.past_window);              // the last nh ids of the row's history (processors.py:21-23)
+    const int nh = min(a.hist_len, past_window);                     // the last nh ids of the row's history (processors.py:21-23)
     in.myid = (lane < nh) ? a.history[(size_t)row * a.hist_len + (a.hist_len - nh) + lane] : -1;
-    in.T = d->cfg.temperature[row % CTTS_NUM_VQ];
-    in.penalize = d->cfg.use_penalty && (row < d->cfg.max_input_ids) && nh > 0;
+    in.T = T;
+    in.penalize = use_penalty && (row < d->cfg.max_input_ids) && nh > 0;
     in.step = a.step_override;
     in.seed = 0; in.uid_lo = (unsigned)row; in.uid_hi = 0; in.vq = 0; in.attempt = 0;      // (stand-alone mode always receives q)
     float lg[VPL];
 #pragma unroll
     for (int i = 0; i < VPL; ++i) { const int j = lane + 64 * i; lg[i] = (j < a.V) ? logits[j] : 0.f; }
-    const int idx = sample_row(knobs_of(d), tab, in, a.V, lane, lg, cand_s[w]);
+    const int idx = sample_row(kn, tab, in, a.V, lane, lg, cand_s[w]);
     if (lane == 0) a.idx_out[row] = idx;
 }
 
@@ -689,19 +704,24 @@ int launch_restart_rows(RowState* rows, int B, hipStream_t s) {
 // Finished-row compaction (ctts_gpt_compact): per-row decode state of the kept rows -> rows 0..n_keep-1.  Two launches (gather into
 // the c* buffers, copy back): a kept row's new place can be another kept row's old one.  The second one also re-derives the step
 // state that depends on the batch: rows in the batch, how many of them have already finished, all-finished flag.
+// The rows' sampling knobs (RowSampling, 7 x 16 bytes) move with them: one 16-byte vector copy per thread of 7.
 __global__ __launch_bounds__(256) void compact_gather_kernel(const int* keep, int H, const float* x, const float* rope_rows, const RowMeta* meta, const int* ring,
-                                                           const RowState* fin, float* cx, float* crope, RowMeta* cmeta, int* cring, RowState* cfin) {
+                                                           const RowState* fin, const RowSampling* knobs, float* cx, float* crope, RowMeta* cmeta, int* cring,
+                                                           RowState* cfin, RowSampling* cknobs) {
     const int r = blockIdx.x, src = keep[r], tid = threadIdx.x;
     for (int k = tid; k < H; k += 256) cx[(size_t)r * H + k] = x[(size_t)src * H + k];
     if (tid < 64) { crope[r * 64 + tid] = rope_rows[src * 64 + tid]; cring[r * 64 + tid] = ring[src * 64 + tid]; }
     if (tid == 0) { cmeta[r] = meta[src]; cfin[r] = fin[src]; }
+    if (tid >= 64 && tid < 64 + 7) ((int4*)(cknobs + r))[tid - 64] = ((const int4*)(knobs + src))[tid - 64];
 }
-__global__ __launch_bounds__(256) void compact_scatter_kernel(int n_keep, int H, float* x, float* rope_rows, RowMeta* meta, int* ring, RowState* fin,
-                                                            const float* cx, const float* crope, const RowMeta* cmeta, const int* cring, const RowState* cfin, DevState* st) {
+__global__ __launch_bounds__(256) void compact_scatter_kernel(int n_keep, int H, float* x, float* rope_rows, RowMeta* meta, int* ring, RowState* fin, RowSampling* knobs,
+                                                            const float* cx, const float* crope, const RowMeta* cmeta, const int* cring, const RowState* cfin,
+                                                            const RowSampling* cknobs, DevState* st) {
     const int r = blockIdx.x, tid = threadIdx.x;
     for (int k = tid; k < H; k += 256) x[(size_t)r * H + k] = cx[(size_t)r * H + k];
     if (tid < 64) { rope_rows[r * 64 + tid] = crope[r * 64 + tid]; ring[r * 64 + tid] = cring[r * 64 + tid]; }
     if (tid == 0) { meta[r] = cmeta[r]; fin[r] = cfin[r]; }
+    if (tid >= 64 && tid < 64 + 7) ((int4*)(knobs + r))[tid - 64] = ((const int4*)(cknobs + r))[tid - 64];
     if (r == 0 && tid == 0) {
         int nfin = 0;
         for (int i = 0; i < n_keep; ++i) nfin += cfin[i].fin ? 1 : 0;
@@ -710,12 +730,12 @@ __global__ __launch_bounds__(256) void compact_scatter_kernel(int n_keep, int H,
         if (nfin == n_keep) st->all_done = 1;
     }
 }
-int launch_compact_rows(const int* keep, int n_keep, int H, float* x, float* rope_rows, RowMeta* meta, int* ring, RowState* fin,
-                        float* cx, float* crope, RowMeta* cmeta, int* cring, RowState* cfin, DevState* st, hipStream_t s) {
+int launch_compact_rows(const int* keep, int n_keep, int H, float* x, float* rope_rows, RowMeta* meta, int* ring, RowState* fin, RowSampling* knobs,
+                        float* cx, float* crope, RowMeta* cmeta, int* cring, RowState* cfin, RowSampling* cknobs, DevState* st, hipStream_t s) {
     hipLaunchKernelGGL(compact_gather_kernel, dim3(n_keep), dim3(256), 0, s, keep, H, (const float*)x, (const float*)rope_rows, (const RowMeta*)meta, (const int*)ring,
-                       (const RowState*)fin, cx, crope, cmeta, cring, cfin);
-    hipLaunchKernelGGL(compact_scatter_kernel, dim3(n_keep), dim3(256), 0, s, n_keep, H, x, rope_rows, meta, ring, fin, (const float*)cx, (const float*)crope,
-                       (const RowMeta*)cmeta, (const int*)cring, (const RowState*)cfin, st);
+                       (const RowState*)fin, (const RowSampling*)knobs, cx, crope, cmeta, cring, cfin, cknobs);
+    hipLaunchKernelGGL(compact_scatter_kernel, dim3(n_keep), dim3(256), 0, s, n_keep, H, x, rope_rows, meta, ring, fin, knobs, (const float*)cx, (const float*)crope,
+                       (const RowMeta*)cmeta, (const int*)cring, (const RowState*)cfin, (const RowSampling*)cknobs, st);
     CTTS_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -754,6 +774,7 @@ __global__ __launch_bounds__(64) void admit_rows_kernel(const AdmitArgs a) {
     const int pos_last = max(cum - 1, 0);
     a.rope_dec[(size_t)row * 64 + lane] = a.rope[(size_t)pos_last * 64 + lane];
     a.ring[(size_t)row * 64 + lane] = -1;
+    if (a.fresh_knobs != nullptr && lane < 7) ((int4*)(a.knobs + row))[lane] = ((const int4*)(a.fresh_knobs + i))[lane];      // the utterance's own knobs
     if (a.emb != nullptr)
         for (int k = lane; k < a.H; k += 64) a.x_dec[(size_t)row * a.H + k] = a.emb[((size_t)i * T + T - 1) * a.H + k];
     if (lane == 0) {

@@ -51,14 +51,28 @@ class Context:                    # gpt.py:87-95
         return self._interrupt
 
 
+# The conversions of the sampling scalars, shared by the per-call configuration (sampler_cfg_from_objects) and the per-utterance knobs
+# (row_sampling_from_values), so that the two cannot drift apart.
+def _temperatures(temperature, num_vq: int) -> List[float]:
+    t = torch.as_tensor(temperature, dtype=torch.float32).flatten().tolist()
+    return t * num_vq if len(t) == 1 else t
+
+
+def _top_p_threshold(top_p) -> float:
+    # torch compares the fp32 cumsum with the python double (1 - top_p) cast to fp32
+    return float(np.float32(1 - float(top_p)))
+
+
+def _penalty_table(penalty) -> torch.Tensor:
+    return torch.pow(float(penalty), torch.arange(0, 17, dtype=torch.int64))     # processors.py:28
+
+
 def sampler_cfg_from_objects(temperature, eos_token, max_new_token, min_new_token, logits_warpers, logits_processors,
                              num_vq=4, infer_text=False) -> _lib.SamplerCfg:
     """Reads the scalars off the HF warpers / reference processor objects that processors.gen_logits builds
     (models/processors.py:37-57).  Unknown object types are rejected (no silent host fallback)."""
     sc = _lib.SamplerCfg()
-    t = torch.as_tensor(temperature, dtype=torch.float32).flatten().tolist()
-    if len(t) == 1:
-        t = t * num_vq
+    t = _temperatures(temperature, num_vq)
     for i in range(num_vq):
         sc.temperature[i] = t[i]
     sc.top_p_threshold = -1.0
@@ -72,8 +86,7 @@ def sampler_cfg_from_objects(temperature, eos_token, max_new_token, min_new_toke
             if seen:
                 raise _lib.HipBackendError("logits_warpers: the hip sampler applies [top-p, top-k] in that order (processors.gen_logits); "
                                            f"got a top-p warper after {seen}")
-            # torch compares the fp32 cumsum with the python double (1 - top_p) cast to fp32
-            sc.top_p_threshold = float(np.float32(1 - float(w.top_p)))
+            sc.top_p_threshold = _top_p_threshold(w.top_p)
             sc.min_tokens_to_keep = int(w.min_tokens_to_keep)
             seen.append("top_p")
         elif hasattr(w, "top_k"):
@@ -92,7 +105,7 @@ def sampler_cfg_from_objects(temperature, eos_token, max_new_token, min_new_toke
             sc.use_penalty = 1
             sc.past_window = int(p.past_window)
             sc.max_input_ids = int(p.max_input_ids)
-            tab = torch.pow(float(p.penalty), torch.arange(0, 17, dtype=torch.int64))     # processors.py:28
+            tab = _penalty_table(p.penalty)
         else:
             raise _lib.HipBackendError(f"unsupported logits processor for the hip backend: {type(p).__name__}")
     for i in range(17):
@@ -105,6 +118,82 @@ def sampler_cfg_from_objects(temperature, eos_token, max_new_token, min_new_toke
         raise _lib.HipBackendError("infer_text=True supports repetition_penalty == 1 only: the reference's processor receives a [B,n,1] "
                                    "history in this mode and mis-broadcasts it (models/processors.py:18-34 with gpt.py:458-467)")
     return sc
+
+
+class _TopP:                                  # scalar carriers with the attribute names the HF warpers expose
+    def __init__(self, top_p, min_tokens_to_keep):
+        self.top_p, self.min_tokens_to_keep = float(top_p), int(min_tokens_to_keep)
+
+
+class _TopK:
+    def __init__(self, top_k, min_tokens_to_keep):
+        self.top_k, self.min_tokens_to_keep = max(int(top_k), int(min_tokens_to_keep)), int(min_tokens_to_keep)
+
+
+class _RepPenalty:
+    def __init__(self, penalty, max_input_ids, past_window):
+        if not isinstance(penalty, float) or not (penalty > 0):
+            raise ValueError(f"`penalty` has to be a strictly positive float, but is {penalty}")   # processors.py:9-12
+        self.penalty, self.max_input_ids, self.past_window = penalty, int(max_input_ids), int(past_window)
+
+
+def gen_logits(num_code: int, top_P=0.7, top_K=20, repetition_penalty=1.0):
+    """models/processors.py:37-57 -- same construction, scalar carriers instead of HF objects (the hip GPT
+    also accepts the real transformers / reference objects: it only reads their attributes)."""
+    warpers, processors = [], []
+    if top_P is not None:
+        warpers.append(_TopP(top_P, 3))
+    if top_K is not None:
+        warpers.append(_TopK(top_K, 3))
+    if repetition_penalty is not None and repetition_penalty != 1:
+        processors.append(_RepPenalty(repetition_penalty, num_code, 16))
+    return warpers, processors
+
+
+SAMPLING_KEYS = ("temperature", "top_P", "top_K", "repetition_penalty", "min_new_token", "past_window")
+
+
+def row_sampling_from_values(base: _lib.SamplerCfg, entry=None, num_vq: int = 4) -> _lib.RowSampling:
+    """One utterance's sampling knobs (ctts_row_sampling) = the call's configuration `base` (sampler_cfg_from_objects) with the overrides of
+    `entry`, a dict with keys among SAMPLING_KEYS (None: the call's values).  The entry's knobs take the very path of a call's: gen_logits builds
+    their objects, sampler_cfg_from_objects reads them -- temperature a scalar or num_vq values; top_P (None = disabled), top_K (None = disabled)
+    and repetition_penalty (None or 1 = off) as gen_logits takes them; past_window (1..16, default 16); min_new_token."""
+    e = dict(entry or {})
+    bad = sorted(set(e) - set(SAMPLING_KEYS))
+    if bad:
+        raise _lib.HipBackendError(f"sampling_per_row: unknown key(s) {bad}; per-utterance keys are {list(SAMPLING_KEYS)}")
+    if "temperature" in e and len(_temperatures(e["temperature"], num_vq)) != num_vq:
+        raise _lib.HipBackendError(f"sampling_per_row: temperature has {len(_temperatures(e['temperature'], num_vq))} values (1 or {num_vq})")
+    if e.get("top_K") is not None and int(e["top_K"]) < 0:
+        raise _lib.HipBackendError(f"sampling_per_row: top_K = {e['top_K']} < 0 (None disables top-k)")
+    pen = e.get("repetition_penalty")
+    if pen is not None and not (float(pen) > 0):
+        raise _lib.HipBackendError(f"sampling_per_row: repetition_penalty = {pen} (must be > 0)")
+    w, p = gen_logits(0, top_P=e.get("top_P"), top_K=e.get("top_K"), repetition_penalty=None if pen is None else float(pen))
+    c = sampler_cfg_from_objects(e.get("temperature", 1.0), 0, 0, 0, w, p, num_vq)
+    src = {k: (c if k in e else base) for k in ("temperature", "top_P", "top_K", "repetition_penalty")}
+    r = _lib.RowSampling()
+    for i in range(num_vq):
+        r.temperature[i] = src["temperature"].temperature[i]
+    r.top_p_threshold, r.min_tokens_to_keep = src["top_P"].top_p_threshold, src["top_P"].min_tokens_to_keep
+    r.top_k = src["top_K"].top_k
+    r.use_penalty, r.past_window = src["repetition_penalty"].use_penalty, src["repetition_penalty"].past_window
+    for i in range(17):
+        r.penalty_table[i] = src["repetition_penalty"].penalty_table[i]
+    if "past_window" in e:
+        r.past_window = int(e["past_window"])
+    r.min_new_token = int(e["min_new_token"]) if "min_new_token" in e else base.min_new_token
+    return r
+
+
+def row_sampling_array(base: _lib.SamplerCfg, entries, n: int, num_vq: int = 4, infer_text: bool = False):
+    """ctypes array [n] of ctts_row_sampling for `entries` (one dict or None per sequence); the engine checks the values (begin / admit_sampling)."""
+    if infer_text:
+        raise _lib.HipBackendError("sampling_per_row: per-utterance sampling parameters are code mode only (the refine-text pass, infer_text=True, keeps the call's values)")
+    entries = list(entries)
+    if len(entries) != n:
+        raise _lib.HipBackendError(f"sampling_per_row: {len(entries)} entries for {n} sequences")
+    return (_lib.RowSampling * n)(*[row_sampling_from_values(base, e, num_vq) for e in entries])
 
 
 def compact_size(n_live: int) -> int:
@@ -431,7 +520,8 @@ class GPT:
                  eos_token: Union[int, torch.Tensor], attention_mask: Optional[torch.Tensor] = None, max_new_token=2048,
                  min_new_token=0, logits_warpers=[], logits_processors=[], infer_text=False, return_attn=False,
                  return_hidden=False, stream=False, show_tqdm=True, ensure_non_empty=True, stream_batch=24,
-                 context=None, noise="auto", seed: Optional[int] = None, max_restarts: int = 64, utt_ids=None, max_new_tokens_per_row=None):
+                 context=None, noise="auto", seed: Optional[int] = None, max_restarts: int = 64, utt_ids=None, max_new_tokens_per_row=None,
+                 sampling_per_row=None):
         """`noise`: "torch" draws q = empty(B*4,V).exponential_() per step from torch's CPU generator -- the very numbers
         torch.multinomial consumes in the reference, so TorchSeedContext(seed) reproduces the CPU path's tokens (costs
         ~21 ns of host time per element: hidden behind the GPU up to batch ~8, 3x the step time at batch 32); "device"
@@ -441,7 +531,9 @@ class GPT:
         (larger batches, the 21178-wide refine-text pass); or an array [n_draws, B*4, V].
         `utt_ids` (device noise): one global utterance id per sequence (default 0..B-1) -- the device noise stream of a sequence is keyed by
         (seed, its utterance id, codebook, its own step and regenerate attempt), not by its batch row, so an utterance samples the same
-        noise in whatever slice / batch position / rank it is served.  `max_new_tokens_per_row`: per-sequence token limits (<= max_new_token)."""
+        noise in whatever slice / batch position / rank it is served.  `max_new_tokens_per_row`: per-sequence token limits (<= max_new_token).
+        `sampling_per_row`: one dict (keys SAMPLING_KEYS; a missing key keeps the call's value) or None per sequence -- the utterance's own temperature,
+        top_P, top_K, repetition_penalty, min_new_token (ctts_gpt_set_row_sampling; code mode only).  eos, max_new_token and the F8 threshold stay per call."""
         if return_attn:
             raise _lib.HipBackendError("return_attn=True is unsupported (the reference's eager attention path is broken, SURVEY F2)")
         if not self._finalized:
@@ -455,13 +547,15 @@ class GPT:
         try:
             yield from self._generate(emb, inputs_ids, temperature, eos_token, attention_mask, max_new_token, min_new_token, logits_warpers,
                                       logits_processors, infer_text, return_hidden, stream, ensure_non_empty, stream_batch, context, noise, seed,
-                                      max_restarts, utt_ids, max_new_tokens_per_row)
+                                      max_restarts, utt_ids, max_new_tokens_per_row, sampling_per_row)
         finally:
+            if sampling_per_row is not None:
+                self._lib.ctts_gpt_set_row_sampling(self._h, None, 0)      # a later plain call takes its own values
             self._busy_token.owner = None
 
     def _generate(self, emb, inputs_ids, temperature, eos_token, attention_mask, max_new_token, min_new_token, logits_warpers, logits_processors,
                   infer_text, return_hidden, stream, ensure_non_empty, stream_batch, context, noise, seed, max_restarts, utt_ids=None,
-                  row_limits=None):
+                  row_limits=None, sampling_per_row=None):
         context = context or Context()
         lib, h = self._lib, self._h
         B, T = int(inputs_ids.shape[0]), int(inputs_ids.shape[1])
@@ -471,6 +565,7 @@ class GPT:
         max_new_token = int(max_new_token)
         sc = sampler_cfg_from_objects(temperature, int(eos_token), max_new_token, min_new_token, logits_warpers, logits_processors, NVQ,
                                       infer_text=infer_text)
+        knobs = row_sampling_array(sc, sampling_per_row, B, NVQ, infer_text) if sampling_per_row is not None else None
         if isinstance(noise, str) and noise == "auto":
             # host draws cost ~21 ns per element and step: 10k elements (4 sequences x 4 x 626) hide behind the GPU step, one
             # 21178-wide refine-text row already does not (measured: 502 vs 423 us/step at batch 1, 1.2 vs 0.5 ms at batch 4)
@@ -550,6 +645,8 @@ class GPT:
         with torch.cuda.device(dev):
             st = self._stream()
             tick("setup")
+            if knobs is not None:
+                _lib.check(lib.ctts_gpt_set_row_sampling(h, knobs, B), "set_row_sampling")
             _lib.check(lib.ctts_gpt_begin(h, B, T, mask.data_ptr(), C.byref(sc), C.byref(io), st), "begin")
             _lib.check(lib.ctts_gpt_prefill(h, emb.data_ptr(), st), "prefill")
             tick("begin+prefill")
@@ -655,7 +752,7 @@ class GPT:
                       attention_mask: Optional[torch.Tensor] = None, max_new_token=2048, min_new_token=0, logits_warpers=[],
                       logits_processors=[], return_hidden=False, ensure_non_empty=True, context=None, seed: Optional[int] = None,
                       max_restarts: int = 64, utt_ids=None, max_new_tokens_per_row=None, rows: Optional[int] = None, admit_min: Optional[int] = None,
-                      on_done=None, infer_text: bool = False, adapter_slots=None) -> GenerationOutputs:
+                      on_done=None, infer_text: bool = False, adapter_slots=None, sampling_per_row=None) -> GenerationOutputs:
         """N utterances (left-padded prompts emb[N,T,H], like generate()) through `rows` <= max_batch decode rows: whenever utterances
         finish, queued ones take over their rows (ctts_gpt_admit) instead of the whole slice waiting for its slowest row as the reference's
         slices of 4 do (pipeline:391-397, gpt.py:527-546); once the queue is empty finished rows are compacted away (ctts_gpt_compact).
@@ -664,13 +761,14 @@ class GPT:
         (gpt.py:496-525) acts per utterance: one whose first token is EOS is admitted again with its next attempt, up to `max_restarts`.
         `on_done(list_of_indices)` is called (on the host, while decoding continues) as utterances complete.
         `adapter_slots` = the resident adapter slot (load_adapter) of every utterance or -1 / None: per-utterance LoRA under row re-use (an admitted
-        utterance brings its own adapter, ctts_gpt_admit_adapters).
+        utterance brings its own adapter, ctts_gpt_admit_adapters).  `sampling_per_row` = one dict of sampling knobs or None per utterance (as in
+        generate()): an admitted utterance brings its own knobs (ctts_gpt_admit_sampling).
         Returns one GenerationOutputs for all N utterances, in input order."""
         gen = self.generate_many_iter(emb, inputs_ids, temperature, eos_token, attention_mask=attention_mask, max_new_token=max_new_token,
                                       min_new_token=min_new_token, logits_warpers=logits_warpers, logits_processors=logits_processors,
                                       return_hidden=return_hidden, ensure_non_empty=ensure_non_empty, context=context, seed=seed, max_restarts=max_restarts,
                                       utt_ids=utt_ids, max_new_tokens_per_row=max_new_tokens_per_row, rows=rows, admit_min=admit_min, infer_text=infer_text,
-                                      adapter_slots=adapter_slots)
+                                      adapter_slots=adapter_slots, sampling_per_row=sampling_per_row)
         try:
             while True:
                 ev = next(gen)
@@ -683,7 +781,7 @@ class GPT:
     def generate_many_iter(self, emb, inputs_ids, temperature, eos_token, attention_mask=None, max_new_token=2048, min_new_token=0, logits_warpers=[],
                            logits_processors=[], return_hidden=False, ensure_non_empty=True, context=None, seed=None, max_restarts: int = 64,
                            utt_ids=None, max_new_tokens_per_row=None, rows=None, admit_min=None, infer_text: bool = False, progress: bool = False,
-                           adapter_slots=None):
+                           adapter_slots=None, sampling_per_row=None):
         """generate_many as a generator: yields [(utterance index, ids [n,4] long, hiddens [n,768] or None)] for the utterances that completed
         since the last yield -- while the rest keeps decoding (what was yielded is final: its rows were written before the report that showed
         the utterance finished) -- and returns (StopIteration.value) the GenerationOutputs of all N utterances.
@@ -698,20 +796,24 @@ class GPT:
         try:
             return (yield from self._generate_many(emb, inputs_ids, temperature, eos_token, attention_mask, int(max_new_token), min_new_token, logits_warpers,
                                                    logits_processors, return_hidden, ensure_non_empty, context or Context(), seed, max_restarts, utt_ids,
-                                                   max_new_tokens_per_row, rows, admit_min, bool(infer_text), bool(progress), adapter_slots))
+                                                   max_new_tokens_per_row, rows, admit_min, bool(infer_text), bool(progress), adapter_slots,
+                                                   sampling_per_row))
         finally:
             if adapter_slots is not None:
                 self.set_row_adapters(None)
+            if sampling_per_row is not None:
+                self._lib.ctts_gpt_set_row_sampling(self._h, None, 0)
             self._busy_token.owner = None
 
     def _generate_many(self, emb, inputs_ids, temperature, eos_token, attention_mask, max_new_token, min_new_token, logits_warpers, logits_processors,
                        return_hidden, ensure_non_empty, context, seed, max_restarts, utt_ids, row_limits, rows, admit_min, infer_text=False, progress=False,
-                       adapter_slots=None):
+                       adapter_slots=None, sampling_per_row=None):
         lib, h, dev = self._lib, self._h, self.device
         N, T = int(inputs_ids.shape[0]), int(inputs_ids.shape[1])
         H, NVQ = self.model_dim, self.num_vq
         R = min(N, int(rows) if rows else self.max_batch, self.max_batch)
         sc = sampler_cfg_from_objects(temperature, int(eos_token), max_new_token, min_new_token, logits_warpers, logits_processors, NVQ, infer_text=infer_text)
+        knobs = list(row_sampling_array(sc, sampling_per_row, N, NVQ, infer_text)) if sampling_per_row is not None else None
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         mask = torch.ones(N, T, dtype=torch.int32, device=dev) if attention_mask is None else attention_mask.to(dev).to(torch.int32).contiguous()
@@ -761,6 +863,8 @@ class GPT:
                 lens, uids, lims = [lens[u] for u in order], [uids[u] for u in order], [lims[u] for u in order]
                 if slots is not None:
                     slots = [slots[u] for u in order]
+                if knobs is not None:
+                    knobs = [knobs[u] for u in order]
                 back, order = order, list(range(N))
             first = order[:R]
             Ta, emb_a, mask_a = prompts_of(first)
@@ -771,6 +875,8 @@ class GPT:
                             row_limits=lim_arr.ctypes.data)
             if slots is not None:
                 self.set_row_adapters([slots[u] for u in first])
+            if knobs is not None:
+                _lib.check(lib.ctts_gpt_set_row_sampling(h, (_lib.RowSampling * R)(*[knobs[u] for u in first]), R), "set_row_sampling")
             _lib.check(lib.ctts_gpt_begin(h, R, Ta, mask_a.data_ptr(), C.byref(sc), C.byref(io), st), "begin")
             _lib.check(lib.ctts_gpt_prefill(h, emb_a.data_ptr(), st), "prefill")
             _lib.check(lib.ctts_gpt_sample(h, st), "sample")
@@ -822,6 +928,9 @@ class GPT:
                     if slots is not None:
                         sl_arr = np.ascontiguousarray([slots[u] for u in idx], dtype=np.int32)
                         _lib.check(lib.ctts_gpt_admit_adapters(h, k, rows_arr.ctypes.data_as(C.c_void_p), sl_arr.ctypes.data_as(C.c_void_p), st), "admit_adapters")
+                    if knobs is not None:         # (re-admissions of ensure_non_empty included: the utterance keeps its own knobs)
+                        _lib.check(lib.ctts_gpt_admit_sampling(h, k, rows_arr.ctypes.data_as(C.c_void_p), (_lib.RowSampling * k)(*[knobs[u] for u in idx]), st),
+                                   "admit_sampling")
                     _lib.check(lib.ctts_gpt_admit(h, k, rows_arr.ctypes.data_as(C.c_void_p), Ta, mask_a.data_ptr(), emb_a.data_ptr(),
                                                   uid_arr.ctypes.data_as(C.c_void_p), lim_arr.ctypes.data_as(C.c_void_p),
                                                   out_arr.ctypes.data_as(C.c_void_p), att_arr.ctypes.data_as(C.c_void_p), st), "admit")

@@ -65,34 +65,53 @@ class TorchSeedContext:                        # reference commons/utils.py:48-5
         torch.random.set_rng_state(self.state)
 
 
-class _TopP:                                  # scalar carriers with the attribute names the HF warpers expose
-    def __init__(self, top_p, min_tokens_to_keep):
-        self.top_p, self.min_tokens_to_keep = float(top_p), int(min_tokens_to_keep)
+# gen_logits and its scalar carriers live beside the sampler configuration they feed (hip_models/gpt.py): one conversion for a call's knobs and for an
+# utterance's (sampling_per_row)
+from .hip_models.gpt import _RepPenalty, _TopK, _TopP, gen_logits  # noqa: E402,F401
 
 
-class _TopK:
-    def __init__(self, top_k, min_tokens_to_keep):
-        self.top_k, self.min_tokens_to_keep = max(int(top_k), int(min_tokens_to_keep)), int(min_tokens_to_keep)
+# params_per_utterance (ChatTTSPlusPipeline.infer / infer_sharded): the InferCodeParams fields one utterance may set for itself.  The sampling knobs
+# reach the engine's per-row table (GPT sampling_per_row, ctts_gpt_set_row_sampling); max_new_token becomes the utterance's token limit, prompt its
+# [speed_N] / [oral_N] prefix, spk_emb its speaker row.  Every other field is per call.
+PER_UTTERANCE_SAMPLING = ("temperature", "top_P", "top_K", "repetition_penalty", "min_new_token")
+PER_UTTERANCE_FIELDS = PER_UTTERANCE_SAMPLING + ("max_new_token", "prompt", "spk_emb")
 
 
-class _RepPenalty:
-    def __init__(self, penalty, max_input_ids, past_window):
-        if not isinstance(penalty, float) or not (penalty > 0):
-            raise ValueError(f"`penalty` has to be a strictly positive float, but is {penalty}")   # processors.py:9-12
-        self.penalty, self.max_input_ids, self.past_window = penalty, int(max_input_ids), int(past_window)
+def _same_value(a, b) -> bool:
+    if torch.is_tensor(a) or torch.is_tensor(b):
+        return torch.is_tensor(a) and torch.is_tensor(b) and a.shape == b.shape and bool(torch.equal(a.cpu(), b.cpu()))
+    try:
+        return bool(a == b)
+    except Exception:       # noqa: BLE001 (values that do not compare are different)
+        return False
 
 
-def gen_logits(num_code: int, top_P=0.7, top_K=20, repetition_penalty=1.0):
-    """models/processors.py:37-57 -- same construction, scalar carriers instead of HF objects (the hip GPT
-    also accepts the real transformers / reference objects: it only reads their attributes)."""
-    warpers, processors = [], []
-    if top_P is not None:
-        warpers.append(_TopP(top_P, 3))
-    if top_K is not None:
-        warpers.append(_TopK(top_K, 3))
-    if repetition_penalty is not None and repetition_penalty != 1:
-        processors.append(_RepPenalty(repetition_penalty, num_code, 16))
-    return warpers, processors
+def per_utterance_overrides(base, entries) -> List[dict]:
+    """`entries` (one InferCodeParams, dict of overrides or None per utterance) -> the fields in which each differs from `base`.  An entry's
+    spk_emb of None means the call's speaker.  A field outside PER_UTTERANCE_FIELDS that differs raises HipBackendError naming it."""
+    names = [f.name for f in dataclasses.fields(InferCodeParams)]
+    out = []
+    for i, e in enumerate(entries):
+        if e is None:
+            vals = {}
+        elif isinstance(e, InferCodeParams):
+            vals = {n: getattr(e, n) for n in names}
+        elif isinstance(e, dict):
+            unknown = sorted(set(e) - set(names))
+            if unknown:
+                raise _lib.HipBackendError(f"params_per_utterance: entry {i}: unknown field(s) {unknown}")
+            vals = dict(e)
+        else:
+            raise _lib.HipBackendError(f"params_per_utterance: entry {i} is a {type(e).__name__} (InferCodeParams, dict or None)")
+        if vals.get("spk_emb", 0) is None:
+            vals.pop("spk_emb")
+        diff = {k: v for k, v in vals.items() if not _same_value(v, getattr(base, k))}
+        bad = [k for k in diff if k not in PER_UTTERANCE_FIELDS]
+        if bad:
+            raise _lib.HipBackendError(f"params_per_utterance: entry {i}: field {bad[0]!r} differs from params_infer_code but is per call "
+                                       f"(per utterance: {', '.join(PER_UTTERANCE_FIELDS)})")
+        out.append(diff)
+    return out
 
 
 def _get(cfg, key, default=None):
@@ -290,9 +309,10 @@ class ChatTTSPlusPipeline:
 
     # -- hot path callers --------------------------------------------------------------------------
     @torch.no_grad()
-    def _infer_code(self, text, stream: bool, return_hidden: bool, params: InferCodeParams, gpt=None, **gen_kwargs):
-        """pipeline:157-235 -- same argument plumbing; the GPT object is the hip backend.  `gen_kwargs` (noise, seed, utt_ids) ride through to
-        GPT.generate: the device noise stream of an utterance is keyed by the request seed and its global utterance id."""
+    def _infer_code(self, text, stream: bool, return_hidden: bool, params: InferCodeParams, gpt=None, prompts=None, **gen_kwargs):
+        """pipeline:157-235 -- same argument plumbing; the GPT object is the hip backend.  `gen_kwargs` (noise, seed, utt_ids, sampling_per_row) ride
+        through to GPT.generate: the device noise stream of an utterance is keyed by the request seed and its global utterance id.  `prompts`: one
+        prompt prefix per text instead of params.prompt (params_per_utterance)."""
         gpt = gpt or self.models_dict["gpt"]
         tok = self.models_dict["tokenizer"]
         if not isinstance(text, list):
@@ -300,7 +320,9 @@ class ChatTTSPlusPipeline:
         assert len(text), "text should not be empty"
         temperature = params.temperature if isinstance(params.temperature, list) else [params.temperature] * gpt.num_vq
         text = [t.replace("[Stts]", "").replace("[spk_emb]", "").replace("[empty_spk]", "").strip() for t in text]
-        if params.prompt:
+        if prompts is not None:
+            text = [p + i for p, i in zip(prompts, text)]
+        elif params.prompt:
             text = [params.prompt + i for i in text]
         txt_smp = "" if params.txt_smp is None else params.txt_smp
         tag = "[spk_emb]" if params.spk_emb is not None else "[empty_spk]"
@@ -423,6 +445,24 @@ class ChatTTSPlusPipeline:
         self._lora_models[lora_path] = base.with_lora(load_lora_adapter(lora_path))
         return self._lora_models[lora_path]
 
+    def _speaker_rows(self, call_spk, diffs) -> torch.Tensor:
+        """[N, 768] speaker rows for params_per_utterance: an utterance's own spk_emb where it sets one, else the call's (a speaker string / vector,
+        or row u of a per-utterance table, infer_sharded)."""
+        dim = self.models_dict["gpt"].model_dim
+
+        def vec(v):
+            return codec.speaker_to_vector(v).view(dim) if isinstance(v, str) else torch.as_tensor(v, dtype=torch.float32).cpu().reshape(dim)
+        table = torch.is_tensor(call_spk) and call_spk.dim() == 2 and call_spk.shape[0] == len(diffs)
+        rows = []
+        for u, d in enumerate(diffs):
+            if "spk_emb" in d:
+                rows.append(vec(d["spk_emb"]))
+            elif call_spk is None:
+                raise _lib.HipBackendError("params_per_utterance: an utterance sets spk_emb and the call has no speaker for the others")
+            else:
+                rows.append(call_spk[u].float().cpu() if table else vec(call_spk))
+        return torch.stack(rows)
+
     def _infer(self, text_in, stream=False, lang=None, skip_refine_text=False, refine_text_only=False, use_decoder=True,
                do_text_normalization=True, do_text_optimization=True, do_homophone_replacement=True,
                params_refine_text=RefineTextParams(), params_infer_code=InferCodeParams(), **kwargs):
@@ -458,6 +498,26 @@ class ChatTTSPlusPipeline:
         utt_limits = kwargs.get("max_new_tokens_per_utterance")
         if utt_limits is not None and len(utt_limits) != len(text_in):
             raise _lib.HipBackendError(f"max_new_tokens_per_utterance: {len(utt_limits)} entries for {len(text_in)} utterances (after text splitting)")
+        # optional per-utterance parameters (no counterpart in the reference, whose InferCodeParams apply to a whole call): one InferCodeParams or dict of
+        # overrides per utterance; the sampling knobs go to the engine's per-row table (GPT sampling_per_row), max_new_token to the per-row limits
+        utt_sampling = utt_prompts = None
+        diffs = kwargs.get("_utt_overrides")       # infer / infer_sharded: the entries already resolved against the params their CALLER passed
+        if diffs is None and kwargs.get("params_per_utterance") is not None:
+            diffs = per_utterance_overrides(params_infer_code, kwargs["params_per_utterance"])
+        if diffs is not None:
+            if len(diffs) != len(text_in):
+                raise _lib.HipBackendError(f"params_per_utterance: {len(diffs)} entries for {len(text_in)} utterances (after text splitting)")
+            if any(set(d) & set(PER_UTTERANCE_SAMPLING) for d in diffs):
+                utt_sampling = [({k: d[k] for k in PER_UTTERANCE_SAMPLING if k in d} or None) for d in diffs]
+            if any("max_new_token" in d for d in diffs):
+                if utt_limits is not None:
+                    raise _lib.HipBackendError("params_per_utterance with a per-utterance max_new_token and max_new_tokens_per_utterance are exclusive")
+                utt_limits = [int(d.get("max_new_token", params_infer_code.max_new_token)) for d in diffs]
+                params_infer_code = dataclasses.replace(params_infer_code, max_new_token=max(utt_limits))
+            if any("prompt" in d for d in diffs):
+                utt_prompts = [d.get("prompt", params_infer_code.prompt) or "" for d in diffs]
+            if any("spk_emb" in d for d in diffs):
+                params_infer_code = dataclasses.replace(params_infer_code, spk_emb=self._speaker_rows(params_infer_code.spk_emb, diffs))
         # `continuous=True` (no counterpart in the reference): the request's utterances are NOT cut into slices that each wait for their slowest
         # row (pipeline:391-397); slice_size decode rows are kept busy -- queued utterances take over the rows of finished ones
         # (GPT.generate_many_iter, ctts_gpt_admit).  Device noise keyed by utterance id: every utterance gets the waveform the sliced path gives it.
@@ -505,7 +565,9 @@ class ChatTTSPlusPipeline:
             events = self._infer_code([texts_all[i] for i in order], False, use_decoder, pic, gpt=gpt, continuous=True, seed=noise_seed,
                                       utt_ids=[utt_ids[i] for i in order], rows=slice_size,
                                       max_new_tokens_per_row=[utt_limits[i] for i in order] if utt_limits is not None else None, progress=bool(stream),
-                                      **({"adapter_slots": [adapter_slots[i] for i in order]} if adapter_slots is not None else {}))
+                                      **({"prompts": [utt_prompts[i] for i in order]} if utt_prompts is not None else {}),
+                                      **({"adapter_slots": [adapter_slots[i] for i in order]} if adapter_slots is not None else {}),
+                                      **({"sampling_per_row": [utt_sampling[i] for i in order]} if utt_sampling is not None else {}))
             if stream:
                 # stream=True with row re-use (no counterpart in the reference, whose stream branch serves one slice, pipeline:440-463): every yield is a list of
                 # (utterance index, sample window) -- the next [emitted, b) samples of that utterance's prefix waveform, vocoded from the tokens inside the window's
@@ -619,7 +681,14 @@ class ChatTTSPlusPipeline:
                 gen_kw = dict(noise=("device" if noise_mode == "auto" else noise_mode), seed=noise_seed, utt_ids=utt_ids[ii:ii + slice_size])
             if utt_limits is not None:
                 gen_kw["max_new_tokens_per_row"] = list(utt_limits[ii:ii + slice_size])
-            results = self._infer_code(text, stream, use_decoder, params_infer_code, gpt=gpt, **gen_kw)
+            if utt_sampling is not None:
+                gen_kw["sampling_per_row"] = list(utt_sampling[ii:ii + slice_size])
+            pic = params_infer_code
+            if torch.is_tensor(pic.spk_emb) and pic.spk_emb.dim() == 2 and pic.spk_emb.shape[0] == len(text_in) and len(text_in) > len(text):
+                pic = dataclasses.replace(pic, spk_emb=pic.spk_emb[ii:ii + len(text)])       # one speaker row per utterance: this slice's rows
+            if utt_prompts is not None:
+                gen_kw["prompts"] = list(utt_prompts[ii:ii + slice_size])
+            results = self._infer_code(text, stream, use_decoder, pic, gpt=gpt, **gen_kw)
             try:
                 for result in results:
                     if not stream:
@@ -664,7 +733,11 @@ class ChatTTSPlusPipeline:
         """pipeline:472-579.  Speaker resolution: `speaker_emb_path` (.pt holding a base16384 str or a tensor),
         else params_infer_code.spk_emb as given (the reference overwrites it with a random speaker whenever no path is passed,
         pipeline:547-556), else a random speaker from spk_stat.  The params object is copied first: the default argument is one shared
-        instance, and the reference's in-place writes make a zero-shot prompt or a sampled speaker stick to every later default call."""
+        instance, and the reference's in-place writes make a zero-shot prompt or a sampled speaker stick to every later default call.
+        `params_per_utterance`: one InferCodeParams or dict per utterance (after text splitting); an entry overrides the fields in which it differs
+        from the params_infer_code passed HERE -- not from the speaker / zero-shot prompt filled in below."""
+        if kwargs.get("params_per_utterance") is not None:
+            kwargs["_utt_overrides"] = per_utterance_overrides(params_infer_code, kwargs.pop("params_per_utterance"))
         params_infer_code = dataclasses.replace(params_infer_code)
         if kwargs.get("speaker_audio_path"):                                      # zero shot (pipeline:486-499)
             from . import audio
@@ -738,6 +811,11 @@ class ChatTTSPlusPipeline:
         lora_all = kwargs.pop("lora_paths", None)                              # one adapter directory (or None) per GLOBAL utterance; each slice gets its own entries
         if lora_all is not None and len(lora_all) != len(texts):
             raise _lib.HipBackendError(f"lora_paths: {len(lora_all)} entries for {len(texts)} utterances")
+        ppu_all = kwargs.pop("params_per_utterance", None)                     # one InferCodeParams / dict of overrides per GLOBAL utterance; each slice gets its own
+        if ppu_all is not None and len(ppu_all) != len(texts):
+            raise _lib.HipBackendError(f"params_per_utterance: {len(ppu_all)} entries for {len(texts)} utterances")
+        # resolved against the caller's params_infer_code: run_local below swaps spk_emb for the rank's speaker rows, which an entry must not be compared with
+        over_all = per_utterance_overrides(params_infer_code, ppu_all) if ppu_all is not None else None
         ids_out = kwargs.pop("ids_out", None)                                  # optional list: receives this rank's generated ids, in `mine` order
         sink = [] if ids_out is not None else None
 
@@ -754,6 +832,8 @@ class ChatTTSPlusPipeline:
                     kw_sl["max_new_tokens_per_utterance"] = [int(limits_all[i]) for i in sl]
                 if lora_all is not None:
                     kw_sl["lora_paths"] = [lora_all[i] for i in sl]
+                if over_all is not None:
+                    kw_sl["_utt_overrides"] = [over_all[i] for i in sl]
                 if sink is not None:
                     kw_sl["_ids_sink"] = sink
                 for wavs in self._infer([texts[i] for i in sl], False, None, skip_refine_text, False, True, True, False, True,

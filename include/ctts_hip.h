@@ -122,6 +122,7 @@ void ctts_gpt_destroy(ctts_gpt* h);
  *       effective values: persistent_rows 0, valu_rows 0, split_decode_rows 1, split_rows 0, down_splitk_rows 1, nbg2_rows / split_nbg2_rows 0 (never),
  *       decode_splits 1, attn_wide_blocks INT_MAX, prefill_split_rows 1, prefill_splitk_rows 0.  Block-shape options (prefill_pp_blocks, prefill_small_blocks,
  *       prefill_ring4_blocks, weight_prefetch_kb) stay live: they do not change the arithmetic.
+ *       An utterance's sampling knobs (ctts_gpt_set_row_sampling / ctts_gpt_admit_sampling) count as its own inputs: they are covered like its token limit.
  *       OUTSIDE the contract: caller-supplied noise (indexed by the batch's draw counter); per-utterance adapters (ctts_gpt_set_row_adapters /
  *       ctts_gpt_admit_adapters: begin / admit with a live adapter row return an error naming the option; a merged adapter, ctts_gpt_merge_lora, is just
  *       weights and is covered); ensure_non_empty restarts of a whole generate() batch (ctts_gpt_restart: the reference regenerates the slice, so an
@@ -186,6 +187,25 @@ typedef struct {
     int32_t infer_text;               /* 1: refine-text pass (gpt.py infer_text=True: 21178-way head_text, temperature[0] only,
                                          next input = emb_text[id], use_penalty must be 0); noise is then [n_draws][B][vocab_text] */
 } ctts_sampler_cfg;
+
+/* Per-utterance sampling knobs (no counterpart in the reference, whose InferCodeParams apply to a whole call): one entry per sequence, the same
+ * fields and conversions as ctts_sampler_cfg.  Per utterance: temperature, top-p, top-k, min_tokens_to_keep, the repetition penalty (its table and
+ * window) and min_new_token.  Per call (ctts_sampler_cfg): eos_token, max_input_ids (the F8 row quirk: a property of the batch row), max_new_token,
+ * infer_text.  Code mode only: the refine-text pass keeps the call's values (begin refuses per-row knobs with infer_text).  Invalid entries
+ * (temperature <= 0 or not finite, top_k < 0, min_tokens_to_keep < 1, past_window outside 1..16, min_new_token > max_new_token) are an error.
+ * Cost: the sampler branches per sequence (one block) between its <= 64-candidate path and the serial one, so mixed knobs add no divergence inside
+ * a wave -- but a batch that holds one row with top_k 0 (disabled) or > 64 runs at the speed of that row's serial path.  112 bytes (7 x 16). */
+typedef struct {
+    float temperature[CTTS_NUM_VQ];   /* per codebook, > 0 */
+    float top_p_threshold;            /* (float)(1 - top_P); < 0 disables top-p */
+    int32_t top_k;                    /* max(top_K, min_tokens_to_keep); 0 disables top-k */
+    int32_t min_tokens_to_keep;       /* >= 1 (3 as processors.py builds it) */
+    int32_t use_penalty;              /* repetition_penalty != 1 */
+    float penalty_table[17];          /* penalty**n, n = 0..16, as torch.pow(float, int64) gives */
+    int32_t past_window;              /* 1..16 */
+    int32_t min_new_token;            /* <= the call's max_new_token */
+    int32_t reserved;                 /* 0 */
+} ctts_row_sampling;
 
 /* Outputs of one generate() call, all device memory provided by the caller:
  *   ids      int32 [B][max_new_token][4]     (gpt.py:368-376 inputs_ids_buf, generated part)
@@ -288,6 +308,16 @@ int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, const int32_t
  * live row carries an adapter any more the engine drops back to the plain launches. */
 int ctts_gpt_admit_adapters(ctts_gpt* h, int n, const int32_t* rows, const int32_t* slots, void* stream);
 
+/* Per-utterance sampling knobs (ctts_row_sampling; no counterpart in the reference).
+ *   set_row_sampling  HOST per_seq [B]: knobs of sequences 0..B-1 for the following ctts_gpt_begin calls (sequences beyond B, and every call after
+ *                     per_seq == NULL / B == 0, take the call's ctts_sampler_cfg values).  The request persists until it is cleared; begin checks it.
+ *   admit_sampling    HOST rows [n], p [n]: knobs of the utterances the NEXT ctts_gpt_admit call seats in `rows` (call it before the admit).  An admitted
+ *                     row that is not named gets the call's values -- never the knobs of the finished utterance whose row it takes.
+ * The knobs follow an utterance through ctts_gpt_compact and ctts_gpt_restart.  The sampler reads them per decode row from a table at a fixed
+ * engine address, so captured decode graphs stay valid. */
+int ctts_gpt_set_row_sampling(ctts_gpt* h, const ctts_row_sampling* per_seq, int B);
+int ctts_gpt_admit_sampling(ctts_gpt* h, int n, const int32_t* rows, const ctts_row_sampling* p, void* stream);
+
 /* Non-blocking variant: enqueues a copy of {steps_done, draws, all_finished, -} into 4 int32 of PINNED host memory; the
  * caller records an event after it and reads the words once the event has completed -- lets the host keep one chunk of
  * decode steps in flight while it inspects the previous one. */
@@ -307,6 +337,10 @@ int ctts_sampler_noise(uint64_t seed, uint64_t utt_id, int stream_id, int step, 
  * [rows][hist_len]; q fp32 [rows][vocab]) -> idx int32 [rows]; A15-A19 of SURVEY 8(a). */
 int ctts_sampler_run(const ctts_sampler_cfg* sc, const float* logits_dev, const int32_t* history_dev, int hist_len,
                      const float* q_dev, int rows, int vocab, int step, int32_t* idx_dev, void* stream);
+/* ... with knobs per sequence: row r uses per_seq[r / 4] (HOST [(rows + 3) / 4], <= CTTS_MAX_BATCH) instead of the knobs of `sc`; eos_token,
+ * max_input_ids and max_new_token still come from `sc`.  The per-row path of the generate-mode sampler, stand-alone (a test hook). */
+int ctts_sampler_run_rows(const ctts_sampler_cfg* sc, const ctts_row_sampling* per_seq, const float* logits_dev, const int32_t* history_dev,
+                          int hist_len, const float* q_dev, int rows, int vocab, int step, int32_t* idx_dev, void* stream);
 
 /* last measured average duration (ms) of one captured decode step, measured with hipEvents on the launch
  * stream around `n` graph replays; used by bench.py for the roofline object. */
