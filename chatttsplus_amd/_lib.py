@@ -99,6 +99,7 @@ SYMBOLS = [
     ("ctts_gpt_embed", C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
     ("ctts_gpt_begin", C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(SamplerCfg), C.POINTER(GenIO), _P]),
     ("ctts_gpt_prefill", C.c_int, [_P, _P, _P]),
+    ("ctts_gpt_score", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
     ("ctts_gpt_sample", C.c_int, [_P, _P]),
     ("ctts_gpt_restart", C.c_int, [_P, _P]),
     ("ctts_gpt_decode", C.c_int, [_P, C.c_int, C.c_int, _P]),

@@ -251,7 +251,12 @@ struct ctts_gpt {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     struct DecodeSeg { int n, splits, persist; };
     std::vector<DecodeSeg> segs;                 // plan_decode: the steps of one decode call as runs of equal decode paths
+    // ctts_gpt_score: the gathered scored rows [SCORE_ROWS][H], their head logits [SCORE_ROWS][4 * V] and output entries [SCORE_ROWS] --
+    // allocated by the first score call (engines that never score keep their footprint)
+    float *score_x = nullptr, *score_logits = nullptr; int* score_oidx = nullptr;
+    size_t score_bytes = 0;
 };
+#define SCORE_ROWS 2048       // scored rows per heads launch: bounds the logits scratch (2048 x 2504 fp32 = 20.5 MB)
 
 static int dev_alloc(void** p, size_t bytes) {
     CTTS_HIP_CHECK(hipMalloc(p, bytes));
@@ -521,7 +526,8 @@ extern "C" void ctts_gpt_destroy(ctts_gpt* h) {
     void* bufs[] = {h->sk_scratch, h->dyn, h->wblob, h->wsplit, h->whead_sp, h->sp_x_hi, h->sp_x_lo, h->sp_act_hi, h->sp_act_lo, h->whead_text, h->lnf, h->emb_code, h->emb_text, h->rope, h->x_dec, h->x_last, h->x_pre, h->q_buf, h->part_ml, h->part_o, h->logits,
                     h->act, h->attn_packed, h->norm_packed, h->dpart, h->rope_pre, h->rope_dec, h->meta_pre, h->meta_dec, h->meta_dec0, h->st, h->last_rows,
                     h->hist_ring, h->sat, h->finend, h->xh, h->ssq, h->scale_o, h->scale_d, h->cx, h->crope, h->cmeta, h->cring, h->cfin, h->keep_dev,
-                    h->lora_A, h->lora_B, h->lora_Af, h->lora_scale, h->ln1, h->lora_slot_of_seq, h->lora_dqkv, h->lora_do, h->lora_g, h->pimg, h->pimg_head, h->pl_g, h->pl_epoch, h->pl_error, h->pl_ts, h->sk_slab, h->sk_cnt, h->rope_dec0, h->cknobs};
+                    h->lora_A, h->lora_B, h->lora_Af, h->lora_scale, h->ln1, h->lora_slot_of_seq, h->lora_dqkv, h->lora_do, h->lora_g, h->pimg, h->pimg_head, h->pl_g, h->pl_epoch, h->pl_error, h->pl_ts, h->sk_slab, h->sk_cnt, h->rope_dec0, h->cknobs,
+                    h->score_x, h->score_logits, h->score_oidx};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (h->host_pin) (void)hipHostFree(h->host_pin);
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
@@ -1300,6 +1306,29 @@ static int reset_state(ctts_gpt* h, bool keep_draw, hipStream_t s) {
     return 0;
 }
 
+// per-utterance adapters of sequences 0..B-1 for a call that starts a prompt pass (begin, score): the call starts from what ctts_gpt_set_row_adapters requested.
+// (lora_rows is the LIVE state: ctts_gpt_compact clears it once every adapter-carrying row has left the batch and ctts_gpt_admit_adapters rewrites the tables --
+// a second generate() after ONE set_row_adapters() call used to run without its adapters, silently)
+static int seat_row_adapters(ctts_gpt* h, int B, const char* who, hipStream_t s) {
+    if (h->lora_slot_host.empty()) return 0;
+    if (h->lora_req_host.empty()) h->lora_slot_host.assign(CTTS_MAX_B, -1);
+    else h->lora_slot_host = h->lora_req_host;
+    bool any = false;
+    for (int b = 0; b < CTTS_MAX_B; ++b) { h->lora_row_slots[b] = (signed char)h->lora_slot_host[b]; any = any || (b < B && h->lora_slot_host[b] >= 0); }
+    h->lora_rows = any ? 1 : 0;
+    if (h->lora_rows && h->batch_inv) {
+        h->lora_rows = 0; h->B = 0;
+        ctts_set_error("%s: per-utterance adapters (ctts_gpt_set_row_adapters) are outside the batch_invariant contract; set the option to 0 or merge the adapter", who);
+        return 1;
+    }
+    if (h->lora_slot_of_seq)        // (pageable source: staged before the call returns)
+        CTTS_HIP_CHECK(hipMemcpyAsync(h->lora_slot_of_seq, h->lora_slot_host.data(), CTTS_MAX_B * 4, hipMemcpyHostToDevice, s));
+    // the folded launches tag their granules with the sampler's draw counter, which restarts at every begin(): forget the previous call's granules, or a tile could
+    // accept a stale term whose tag happens to match (a previous call of exactly as many steps)
+    if (h->lora_rows && h->lora_g) CTTS_HIP_CHECK(hipMemsetAsync(h->lora_g, 0, (size_t)CTTS_MAX_B * 4 * h->H * 8, s));
+    return 0;
+}
+
 extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, const ctts_sampler_cfg* sc, const ctts_gen_io* io, void* stream) {
     if (!h || !h->finalized || !h->kv || !h->rope) { ctts_set_error("begin: handle not ready (finalize / bind_kv / set_rope)"); return 1; }
     if (!mask || !sc || !io || !io->ids || !io->finish || !io->end_idx) { ctts_set_error("begin: null argument"); return 1; }
@@ -1340,26 +1369,7 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
     }
     h->row_seq.resize(B); h->row_ctx.assign(B, T); h->row_cap.resize(B);
     for (int b = 0; b < B; ++b) { h->row_seq[b] = b; h->row_cap[b] = T + h->rows_host[b].limit; }
-    if (!h->lora_slot_host.empty()) {
-        // per-utterance adapters: the call starts from what ctts_gpt_set_row_adapters requested.  (lora_rows is the LIVE state: ctts_gpt_compact clears it once every
-        // adapter-carrying row has left the batch and ctts_gpt_admit_adapters rewrites the tables -- a second generate() after ONE set_row_adapters() call used to
-        // run without its adapters, silently)
-        if (h->lora_req_host.empty()) h->lora_slot_host.assign(CTTS_MAX_B, -1);
-        else h->lora_slot_host = h->lora_req_host;
-        bool any = false;
-        for (int b = 0; b < CTTS_MAX_B; ++b) { h->lora_row_slots[b] = (signed char)h->lora_slot_host[b]; any = any || (b < B && h->lora_slot_host[b] >= 0); }
-        h->lora_rows = any ? 1 : 0;
-        if (h->lora_rows && h->batch_inv) {
-            h->lora_rows = 0; h->B = 0;
-            ctts_set_error("begin: per-utterance adapters (ctts_gpt_set_row_adapters) are outside the batch_invariant contract; set the option to 0 or merge the adapter");
-            return 1;
-        }
-        if (h->lora_slot_of_seq)        // (pageable source: staged before the call returns)
-            CTTS_HIP_CHECK(hipMemcpyAsync(h->lora_slot_of_seq, h->lora_slot_host.data(), CTTS_MAX_B * 4, hipMemcpyHostToDevice, (hipStream_t)stream));
-        // the folded launches tag their granules with the sampler's draw counter, which restarts at every begin(): forget the previous call's granules, or a tile could
-        // accept a stale term whose tag happens to match (a previous call of exactly as many steps)
-        if (h->lora_rows && h->lora_g) CTTS_HIP_CHECK(hipMemsetAsync(h->lora_g, 0, (size_t)CTTS_MAX_B * 4 * h->H * 8, (hipStream_t)stream));
-    }
+    if (seat_row_adapters(h, B, "begin", s)) return 1;
     h->pre_T = T;
     h->io.utt_ids = nullptr; h->io.row_limits = nullptr;      // host arrays are consumed here, not kept
     h->sc = cfg_of_abi(*sc);
@@ -1438,6 +1448,76 @@ extern "C" int ctts_gpt_prefill(ctts_gpt* h, const float* emb, void* stream) {
     }
     // keep a copy of the prompt's last residual rows for ensure_non_empty restarts
     CTTS_HIP_CHECK(hipMemcpyAsync(h->x_last, h->x_dec, (size_t)h->B * h->H * 4, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// Teacher-forced scoring (include/ctts_hip.h ctts_gpt_score): the prompt pass of ctts_gpt_prefill over [B][T], then per pass the scored rows (the last
+// n_b of sequence b) are gathered SCORE_ROWS at a time, the final RMSNorm + code heads run on them (the decode heads' launch, PRO_NORM / EPI_LOGITS, here on
+// up to SCORE_ROWS rows: every row index it forms is size_t, bounded by R, and it reads no decode state -- st, dyn, rows null) and score.hip reduces the logits.
+extern "C" int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* mask, const float* emb, const int32_t* targets, const int32_t* n_targets, int max_targets,
+                              float* logprob, int32_t* argmax, void* stream) {
+    if (!h || !h->finalized || !h->kv || !h->rope) { ctts_set_error("score: handle not ready (finalize / bind_kv / set_rope)"); return 1; }
+    if (!mask || !emb || !targets || !n_targets || !logprob || !argmax) { ctts_set_error("score: null argument"); return 1; }
+    if (B < 1 || B > h->cfg.max_batch) { ctts_set_error("score: B=%d outside 1..max_batch=%d", B, h->cfg.max_batch); return 1; }
+    if (T < 1 || T > h->cfg.max_seq) { ctts_set_error("score: T=%d outside 1..max_seq=%d", T, h->cfg.max_seq); return 1; }
+    if (max_targets < 1) { ctts_set_error("score: max_targets=%d < 1", max_targets); return 1; }
+    for (int b = 0; b < B; ++b) {
+        const int nb = n_targets[b];
+        if (nb < 1 || nb > T || nb > max_targets) {
+            ctts_set_error("score: n_targets[%d]=%d outside 1..min(T=%d, max_targets=%d)", b, nb, T, max_targets);
+            return 1;
+        }
+    }
+    if (h->batch_inv && !(h->split_ok && h->wsplit)) {
+        ctts_set_error("score: batch_invariant needs the head / tail weight images, and a weight of this checkpoint is beyond the fp16 range (x 64)");
+        return 1;
+    }
+    CTTS_RANGE("ctts_gpt_score");
+    hipStream_t s = (hipStream_t)stream;
+    h->B = 0; h->admitted = false;                 // the KV lanes and the prompt workspaces are overwritten: any generate() state ends here
+    h->text_mode = 0;
+    if (seat_row_adapters(h, B, "score", s)) return 1;
+    const int NV = h->NVQ * h->V;
+    if (h->score_oidx == nullptr) {                // (every byte is written before it is read: no fill)
+        if (!h->score_x) CTTS_HIP_CHECK(hipMalloc((void**)&h->score_x, (size_t)SCORE_ROWS * h->H * 4));
+        if (!h->score_logits) CTTS_HIP_CHECK(hipMalloc((void**)&h->score_logits, (size_t)SCORE_ROWS * NV * 4));
+        CTTS_HIP_CHECK(hipMalloc((void**)&h->score_oidx, (size_t)SCORE_ROWS * 4));
+        h->score_bytes = (size_t)SCORE_ROWS * (h->H + NV + 1) * 4;
+    }
+    // entries j >= n_b: logprob 0, argmax -1
+    CTTS_HIP_CHECK(hipMemsetAsync(logprob, 0, (size_t)B * max_targets * CTTS_NUM_VQ * 4, s));
+    CTTS_HIP_CHECK(hipMemsetAsync(argmax, 0xFF, (size_t)B * max_targets * CTTS_NUM_VQ * 4, s));
+    h->pre_T = T;
+    if (launch_fill_meta(h->meta_pre, h->meta_dec0, h->st, mask, B, T, h->rope, h->rope_pre, s)) return 1;
+    const long R = (long)B * T;
+    // batch_invariant: the heads on 16-row chunks whatever the block holds (as run_heads pins nbg = 1); the chunk of SCORE_ROWS rows only bounds the scratch
+    const int nbg = h->batch_inv ? 1 : 2;
+    ScoreRows sr = {};
+    sr.B = B; sr.max_targets = max_targets;
+    for (long r0 = 0; r0 < R; r0 += h->pass_rows) {
+        const int n = (int)(R - r0 < h->pass_rows ? R - r0 : h->pass_rows);
+        CTTS_HIP_CHECK(hipMemcpyAsync(h->x_pre, emb + (size_t)r0 * h->H, (size_t)n * h->H * 4, hipMemcpyDeviceToDevice, s));
+        if (run_layers(h, h->x_pre, h->meta_pre + r0, h->rope_pre + (size_t)r0 * 64, n, 1, nullptr, s)) return 1;
+        // the scored rows of this pass: sequence b's rows [b T + T - n_b, b T + T) clipped to [r0, r0 + n)
+        sr.cum[0] = 0;
+        for (int b = 0; b < B; ++b) {
+            const long s0 = (long)b * T + T - n_targets[b], s1 = (long)b * T + T;
+            const long lo = s0 > r0 ? s0 : r0, hi = s1 < r0 + n ? s1 : r0 + n;
+            const int cnt = hi > lo ? (int)(hi - lo) : 0;
+            sr.first[b] = cnt ? (int)(lo - r0) : 0;
+            sr.j0[b] = cnt ? (int)(lo - s0) : 0;
+            sr.cum[b + 1] = sr.cum[b] + cnt;
+        }
+        for (int g0 = 0; g0 < sr.cum[B]; g0 += SCORE_ROWS) {
+            const int m = sr.cum[B] - g0 < SCORE_ROWS ? sr.cum[B] - g0 : SCORE_ROWS;
+            if (launch_score_gather(h->x_pre, h->score_x, h->score_oidx, g0, m, sr, s)) return 1;
+            GemmArgs a = {};
+            a.R = m; a.eps = 1e-6f; a.W = h->whead; a.n_row_tiles = (NV + 15) / 16; a.K = h->H; a.x = h->score_x; a.lnw = h->lnf;
+            a.logits = h->score_logits; a.n_valid = NV;
+            if (launch_gemm(h->cfg.dtype, nbg, PRO_NORM, EPI_LOGITS, a, (m + 16 * nbg - 1) / (16 * nbg), s)) return 1;
+            if (launch_score_reduce(h->score_logits, h->score_oidx, targets, logprob, argmax, m, h->V, NV, s)) return 1;
+        }
+    }
     return 0;
 }
 

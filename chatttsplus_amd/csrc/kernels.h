@@ -219,6 +219,16 @@ struct AdmitArgs {
     RowSampling* knobs;               // the decode rows' knob table (common.h RowSampling)
 };
 int launch_admit_rows(const AdmitArgs& a, hipStream_t s);
+// ctts_gpt_score (score.hip): the scored rows of one prompt pass, sequence by sequence, as a contiguous block (computed on the host from the targets' counts,
+// passed by value: the call needs no index upload and stays asynchronous)
+struct ScoreRows {
+    int B, max_targets;
+    int cum[CTTS_MAX_B + 1];    // scored rows of sequences < b that live in this pass
+    int first[CTTS_MAX_B];      // row (in the pass) of sequence b's first scored row in this pass
+    int j0[CTTS_MAX_B];         // ... and the target it predicts
+};
+int launch_score_gather(const float* x_pre, float* dst, int* oidx, int g0, int m, const ScoreRows& sr, hipStream_t s);
+int launch_score_reduce(const float* logits, const int* oidx, const int* targets, float* logprob, int* argmax, int m, int V, int n_valid, hipStream_t s);
 int launch_compact_rows(const int* keep, int n_keep, int H, float* x, float* rope_rows, RowMeta* meta, int* ring, RowState* fin, RowSampling* knobs,
                         float* cx, float* crope, RowMeta* cmeta, int* cring, RowState* cfin, RowSampling* cknobs, DevState* st, hipStream_t s);
 int gemm_configure();

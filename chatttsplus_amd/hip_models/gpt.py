@@ -40,6 +40,84 @@ class GenerationOutputs:          # gpt.py:280-284
     hiddens: List[torch.Tensor]
 
 
+@dataclass(repr=False, eq=False)
+class ScoreOutputs:
+    """GPT.score: per sequence b, `logprob[b]` / `argmax[b]` [n_b, 4] (log_softmax of the raw code logits at the target, first argmax), `nll[b]` (the mean of
+    -logprob) and `accuracy[b]` (argmax == target); over the whole batch the token-weighted `loss` and `accuracy` (train_lora.py:455-469)."""
+    logprob: List[torch.Tensor]
+    argmax: List[torch.Tensor]
+    nll: torch.Tensor
+    seq_accuracy: torch.Tensor
+    loss: float
+    accuracy: float
+
+
+def score_reduce(logprob: List[torch.Tensor], argmax: List[torch.Tensor], targets: List[torch.Tensor]):
+    """(nll [B], accuracy [B], loss, accuracy) from per-sequence [n_b, 4] log-probs, argmaxes and targets.  The batch values weight every (target, codebook)
+    entry alike, as cross_entropy(..., ignore_index) and the masked accuracy mean of train_lora.py:455-469 do."""
+    nll = torch.stack([(-lp.double()).mean() for lp in logprob]).float()
+    acc = torch.stack([(am == t.to(am.dtype)).double().mean() for am, t in zip(argmax, targets)]).float()
+    n = sum(int(lp.numel()) for lp in logprob)
+    loss = float(sum(float(-lp.double().sum()) for lp in logprob) / n)
+    accuracy = float(sum(int((am == t.to(am.dtype)).sum()) for am, t in zip(argmax, targets)) / n)
+    return nll, acc, loss, accuracy
+
+
+def score_inputs(input_ids: torch.Tensor, attention_mask: torch.Tensor, text_mask: torch.Tensor, codes, eos_token: int, append_eos: bool = True):
+    """Host helper of GPT.score (CPU): utterance i's codes [n_i, 4] follow its left-padded prompt (input_ids [B, T, 4], attention_mask / text_mask [B, T], as
+    Tokenizer.encode gives them); the joined sequences are left padded again.  Returns dict(ids [B, T', 4], mask [B, T'] int32, text_mask [B, T'] bool,
+    targets [B, max_targets, 4] int32, n_targets [B] int32).
+      append_eos=True:  every code is an input row and the targets are the codes followed by EOS on all 4 codebooks (the extended labels of
+                        train_lora.py:401-404), n_b = n_i + 1; the last code row predicts EOS, no EOS input row is needed.
+      append_eos=False: the targets are the codes, n_b = n_i; the last code is not fed as input.
+    Target j of sequence b is predicted by row T' - n_b + j (ctts_gpt_score)."""
+    ids = torch.as_tensor(input_ids).cpu()
+    mask = torch.as_tensor(attention_mask).cpu().to(torch.int64)
+    tm = torch.as_tensor(text_mask).cpu().bool()
+    if ids.dim() != 3 or mask.shape != ids.shape[:2] or tm.shape != ids.shape[:2]:
+        raise ValueError(f"score_inputs: input_ids [B, T, num_vq] with attention_mask / text_mask [B, T] (got {tuple(ids.shape)}, {tuple(mask.shape)}, {tuple(tm.shape)})")
+    B, nvq = int(ids.shape[0]), int(ids.shape[2])
+    if len(codes) != B:
+        raise ValueError(f"score_inputs: {len(codes)} code sequences for {B} prompts")
+    _check_left_padded(mask)
+    seqs, tms, tgts = [], [], []
+    for b in range(B):
+        c = torch.as_tensor(codes[b]).cpu().to(ids.dtype)
+        if c.dim() != 2 or c.shape[1] != nvq:
+            raise ValueError(f"score_inputs: codes[{b}] must be [n, {nvq}] (got {tuple(c.shape)})")
+        if not append_eos and c.shape[0] < 1:
+            raise ValueError(f"score_inputs: codes[{b}] is empty and append_eos is off: nothing to score")
+        pad = int((mask[b] == 0).sum())
+        inp = c if append_eos else c[:-1]
+        seqs.append(torch.cat([ids[b, pad:], inp], 0))
+        tms.append(torch.cat([tm[b, pad:], torch.zeros(inp.shape[0], dtype=torch.bool)], 0))
+        tgts.append(torch.cat([c, torch.full((1, nvq), int(eos_token), dtype=c.dtype)], 0) if append_eos else c)
+    T = max(int(s.shape[0]) for s in seqs)
+    nt = torch.tensor([int(t.shape[0]) for t in tgts], dtype=torch.int32)
+    out_ids = torch.zeros(B, T, nvq, dtype=ids.dtype)
+    out_mask = torch.zeros(B, T, dtype=torch.int32)
+    out_tm = torch.zeros(B, T, dtype=torch.bool)
+    targets = torch.zeros(B, int(nt.max()), nvq, dtype=torch.int32)
+    for b in range(B):
+        n = int(seqs[b].shape[0])
+        out_ids[b, T - n:] = seqs[b]
+        out_mask[b, T - n:] = 1
+        out_tm[b, T - n:] = tms[b]
+        targets[b, :int(nt[b])] = tgts[b].to(torch.int32)
+    return dict(ids=out_ids, mask=out_mask, text_mask=out_tm, targets=targets, n_targets=nt)
+
+
+def _check_left_padded(mask: torch.Tensor) -> None:
+    """Every row of `mask` [B, T] is 0...0 1...1 with at least one 1: no holes, no right padding."""
+    m = torch.as_tensor(mask).cpu().to(torch.int64)
+    if bool(((m != 0) & (m != 1)).any()):
+        raise ValueError("attention_mask: values must be 0 or 1")
+    if bool((m.sum(1) == 0).any()):
+        raise ValueError("attention_mask: a sequence has no token")
+    if m.shape[1] > 1 and bool((m[:, 1:] < m[:, :-1]).any()):
+        raise ValueError("attention_mask: scoring needs LEFT padding (0...0 1...1 per row); a row has a hole or right padding")
+
+
 class Context:                    # gpt.py:87-95
     def __init__(self):
         self._interrupt = False
@@ -958,6 +1036,57 @@ class GPT:
                 ids, end_idx = ids.index_select(0, inv), end_idx.index_select(0, inv)
                 hid = hid.index_select(0, inv) if hid is not None else None
             return self._outputs(ids, hid, end_idx, infer_text)
+
+    # -- teacher-forced scoring (train_lora.py:430-469; ctts_gpt_score) ----------------------------------------------------------
+    @torch.no_grad()
+    def score(self, emb: torch.Tensor, attention_mask: torch.Tensor, targets: torch.Tensor, n_targets) -> ScoreOutputs:
+        """Log-probabilities and argmax of audio-code targets under the raw code heads, in one prompt pass (inference only).  emb [B, T, H] (this engine's
+        __call__: text rows and code rows, left padded), attention_mask [B, T] left padded, targets [B, max_targets, 4], n_targets [B]: target j of sequence b
+        is predicted by row T - n_b + j (score_inputs builds all four from a prompt and codes).  Positions are cumsum(mask) - 1 as in generate(), so a
+        sequence scores the same alone as inside a padded batch.  Per-utterance adapters (set_row_adapters) apply per sequence.  Ends nothing a caller
+        holds: refused while a generate() generator is live on this engine or on one sharing its KV cache.  Returns ScoreOutputs on the CPU."""
+        if not self._finalized:
+            raise _lib.HipBackendError("weights not loaded")
+        if self._busy_token.owner is not None:
+            raise _lib.HipBackendError("GPT.score: a generate() generator is live on this engine (or on an engine sharing its KV cache), whose KV lanes "
+                                       "scoring would overwrite: exhaust or close it first")
+        dev = self.device
+        emb = emb.to(dev, dtype=torch.float32).contiguous()
+        if emb.dim() != 3 or emb.shape[2] != self.model_dim:
+            raise ValueError(f"score: emb must be [B, T, {self.model_dim}] (got {tuple(emb.shape)})")
+        B, T = int(emb.shape[0]), int(emb.shape[1])
+        mask = torch.as_tensor(attention_mask)
+        if tuple(mask.shape) != (B, T):
+            raise ValueError(f"score: attention_mask must be [{B}, {T}] (got {tuple(mask.shape)})")
+        _check_left_padded(mask)
+        tg = torch.as_tensor(targets).cpu().to(torch.int64)
+        nt = torch.as_tensor(n_targets).cpu().to(torch.int64).flatten()
+        if tg.dim() != 3 or tg.shape[0] != B or tg.shape[2] != self.num_vq or nt.numel() != B:
+            raise ValueError(f"score: targets must be [{B}, max_targets, {self.num_vq}] and n_targets [{B}] (got {tuple(tg.shape)}, {tuple(nt.shape)})")
+        maxt = int(tg.shape[1])
+        for b in range(B):
+            n = int(nt[b])
+            if n < 1 or n > T or n > maxt:
+                raise ValueError(f"score: n_targets[{b}] = {n} outside 1..min(T={T}, max_targets={maxt})")
+            t = tg[b, :n]
+            if bool(((t < 0) | (t >= self.num_audio_tokens)).any()):
+                raise ValueError(f"score: a target of sequence {b} is outside [0, {self.num_audio_tokens})")
+        if B > self.max_batch or T > self.max_seq:
+            raise ValueError(f"score: B={B} T={T} exceed max_batch={self.max_batch} / max_seq_len={self.max_seq}")
+        msk = mask.to(dev).to(torch.int32).contiguous()
+        tgd = tg.to(torch.int32).to(dev).contiguous()
+        nta = np.ascontiguousarray(nt.numpy(), dtype=np.int32)
+        lp = torch.empty(B, maxt, self.num_vq, dtype=torch.float32, device=dev)
+        am = torch.empty(B, maxt, self.num_vq, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.ctts_gpt_score(self._h, B, T, msk.data_ptr(), emb.data_ptr(), tgd.data_ptr(), nta.ctypes.data_as(C.c_void_p), maxt,
+                                                lp.data_ptr(), am.data_ptr(), self._stream()), "score")
+        lp, am = lp.cpu(), am.cpu().to(torch.long)
+        n = nt.tolist()
+        lps = [lp[b, :n[b]] for b in range(B)]
+        ams = [am[b, :n[b]] for b in range(B)]
+        nll, acc, loss, accuracy = score_reduce(lps, ams, [tg[b, :n[b]] for b in range(B)])
+        return ScoreOutputs(logprob=lps, argmax=ams, nll=nll, seq_accuracy=acc, loss=loss, accuracy=accuracy)
 
     def _staging(self, rows: int, V: int, cap: int):
         """Pinned [cap, rows, V] staging slots for the torch-generator noise, kept across calls (pinning is expensive)."""

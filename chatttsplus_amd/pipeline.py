@@ -308,17 +308,13 @@ class ChatTTSPlusPipeline:
         return torch.randn(dim, device=self.std.device, dtype=self.std.dtype).mul_(self.std).add_(self.mean)
 
     # -- hot path callers --------------------------------------------------------------------------
-    @torch.no_grad()
-    def _infer_code(self, text, stream: bool, return_hidden: bool, params: InferCodeParams, gpt=None, prompts=None, **gen_kwargs):
-        """pipeline:157-235 -- same argument plumbing; the GPT object is the hip backend.  `gen_kwargs` (noise, seed, utt_ids, sampling_per_row) ride
-        through to GPT.generate: the device noise stream of an utterance is keyed by the request seed and its global utterance id.  `prompts`: one
-        prompt prefix per text instead of params.prompt (params_per_utterance)."""
-        gpt = gpt or self.models_dict["gpt"]
+    def _code_prompt(self, text, params: InferCodeParams, gpt, prompts=None):
+        """The code-generation prompt of pipeline:157-235 (shared by _infer_code and score): "[Stts]{spk tag}{txt_smp}{prompt}{text}[Ptts]", tokenised
+        with the zero-shot audio prompt (spk_smp) after the text.  Returns input_ids [B, T, 4], attention_mask, text_mask (left padded)."""
         tok = self.models_dict["tokenizer"]
         if not isinstance(text, list):
             text = [text]
         assert len(text), "text should not be empty"
-        temperature = params.temperature if isinstance(params.temperature, list) else [params.temperature] * gpt.num_vq
         text = [t.replace("[Stts]", "").replace("[spk_emb]", "").replace("[empty_spk]", "").strip() for t in text]
         if prompts is not None:
             text = [p + i for p, i in zip(prompts, text)]
@@ -327,7 +323,64 @@ class ChatTTSPlusPipeline:
         txt_smp = "" if params.txt_smp is None else params.txt_smp
         tag = "[spk_emb]" if params.spk_emb is not None else "[empty_spk]"
         text = [f"[Stts]{tag}{txt_smp}{i}[Ptts]" for i in text]
-        input_ids, attention_mask, text_mask = tok.encode(text, gpt.num_vq, prompt_str=params.spk_smp, device=self.device)
+        return tok.encode(text, gpt.num_vq, prompt_str=params.spk_smp, device=self.device)
+
+    @torch.no_grad()
+    def score(self, text, codes=None, wavs=None, params_infer_code: Optional[InferCodeParams] = None, append_eos: bool = True,
+              lora_path: Optional[str] = None, lora_paths: Optional[List[Optional[str]]] = None):
+        """Teacher-forced scoring of audio codes under the code GPT (no counterpart in the reference's pipeline; the evaluation of train_lora.py:430-469):
+        the prompt is built exactly as _infer_code builds it, utterance i's codes [n_i, 4] follow it, and GPT.score returns each code's log-probability
+        and argmax under the raw heads (hip_models.gpt.ScoreOutputs: per utterance logprob / argmax / nll / seq_accuracy, token-weighted loss / accuracy).
+          codes   one [n_i, 4] code array per text (e.g. GenerationOutputs.ids of a generate() call: re-scoring costs one prompt pass), or
+          wavs    one 24 kHz mono waveform per text, encoded by the dvae_encode model along the path of sample_audio_speaker -- with (text, audio) pairs
+                  this gives train_lora's validation metrics
+          append_eos  the targets end with EOS on all 4 codebooks (train_lora.py:401-404); False scores the codes only
+          lora_path   one merged adapter for the call (the engine infer() uses for it); lora_paths: one adapter directory (or None) per utterance,
+                  through the engine's resident slots (_adapter_slots)
+        train_lora's prompts carry no "[speed_5]" prefix (datasets/base_dataset.py:113-115): InferCodeParams(prompt="") reproduces them."""
+        params = params_infer_code if params_infer_code is not None else InferCodeParams()
+        texts = text if isinstance(text, list) else [text]
+        if (codes is None) == (wavs is None):
+            raise ValueError("score: pass exactly one of codes= and wavs=")
+        if codes is None:
+            enc = self.models_dict.get("dvae_encode")
+            if enc is None:
+                raise _lib.HipBackendError("score(wavs=...) needs the dvae_encode checkpoint (DVAE_full.pt) configured with infer_type 'hip'")
+            codes = []
+            for w in (wavs if isinstance(wavs, list) else [wavs]):
+                w = torch.as_tensor(w, dtype=torch.float32)
+                codes.append(enc(w.view(1, -1).to(self.device), "encode")[0].t().cpu())      # [4, n] (sample_audio_speaker) -> [n, 4]
+        elif not isinstance(codes, list):
+            codes = [codes]
+        if len(codes) != len(texts):
+            raise ValueError(f"score: {len(codes)} code sequences / waveforms for {len(texts)} texts")
+        if lora_path and lora_paths:
+            raise ValueError("score: pass lora_path (one merged adapter) or lora_paths (one per utterance), not both")
+        gpt = self._gpt_for_lora(lora_path)
+        tok = self.models_dict["tokenizer"]
+        input_ids, attention_mask, text_mask = self._code_prompt(texts, params, gpt)
+        eos = int(gpt.emb_code[0].num_embeddings - 1)
+        si = hip_models.gpt.score_inputs(input_ids, attention_mask, text_mask, codes, eos, append_eos=append_eos)
+        emb = gpt(si["ids"], si["text_mask"], spk_emb=params.spk_emb, spk_emb_ids=tok.spk_emb_ids)
+        if lora_paths is not None:
+            if len(lora_paths) != len(texts):
+                raise ValueError(f"score: {len(lora_paths)} lora_paths for {len(texts)} texts")
+            gpt.set_row_adapters(self._adapter_slots(gpt, lora_paths))
+        try:
+            return gpt.score(emb, si["mask"], si["targets"], si["n_targets"])
+        finally:
+            if lora_paths is not None:
+                gpt.set_row_adapters(None)
+
+    @torch.no_grad()
+    def _infer_code(self, text, stream: bool, return_hidden: bool, params: InferCodeParams, gpt=None, prompts=None, **gen_kwargs):
+        """pipeline:157-235 -- same argument plumbing; the GPT object is the hip backend.  `gen_kwargs` (noise, seed, utt_ids, sampling_per_row) ride
+        through to GPT.generate: the device noise stream of an utterance is keyed by the request seed and its global utterance id.  `prompts`: one
+        prompt prefix per text instead of params.prompt (params_per_utterance)."""
+        gpt = gpt or self.models_dict["gpt"]
+        tok = self.models_dict["tokenizer"]
+        temperature = params.temperature if isinstance(params.temperature, list) else [params.temperature] * gpt.num_vq
+        input_ids, attention_mask, text_mask = self._code_prompt(text, params, gpt, prompts)
         emb = gpt(input_ids, text_mask, spk_emb=params.spk_emb, spk_emb_ids=tok.spk_emb_ids)     # get_emb + apply_spk_emb, one launch
         num_code = int(gpt.emb_code[0].num_embeddings - 1)
         warpers, processors = gen_logits(num_code=num_code, top_P=params.top_P, top_K=params.top_K,

@@ -128,6 +128,8 @@ void ctts_gpt_destroy(ctts_gpt* h);
  *       weights and is covered); ensure_non_empty restarts of a whole generate() batch (ctts_gpt_restart: the reference regenerates the slice, so an
  *       utterance's attempt number depends on its slice -- reference semantics).  The refine-text pass (infer_text) runs the same pinned stack and is covered.
  *       A checkpoint with a weight beyond the fp16 range (x 64) cannot take the option (begin returns an error).
+ *       Scoring (ctts_gpt_score) is covered too: a sequence's logprob and argmax are identical bit for bit whatever the batch size, its row, the other
+ *       sequences' padding and the pass boundaries (the prompt pass pinned as above, the code heads on 16-row chunks at every row count).
  * Unknown names are an error. */
 int ctts_gpt_set_option(ctts_gpt* h, const char* name, int value);
 int ctts_gpt_get_option(ctts_gpt* h, const char* name, int* value);      /* the EFFECTIVE value ("persistent_rows" reads 0 where the mode is unavailable) */
@@ -251,6 +253,24 @@ int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* attention_mask_dev,
  * cache; prefill_split.hip); smaller prompts go through the decode kernels in 32-row chunks.
  * replaces the i == 0 iteration's LlamaModel.forward (gpt.py:410-418; llama.py:905-1019). */
 int ctts_gpt_prefill(ctts_gpt* h, const float* emb_dev, void* stream);
+
+/* Teacher-forced scoring of audio codes (the evaluation of train_lora.py:430-469: GPT.forward -> gpt.gpt.forward -> head_code[i], then cross-entropy
+ * and argmax accuracy over the code tokens).  Inference only: there is no backward pass.
+ *   attention_mask int32 [B][T] device, LEFT padded; emb fp32 [B][T][hidden] device (ctts_gpt_embed: text rows and code rows, the layout
+ *   Tokenizer.encode gives a zero-shot prompt whose audio codes follow the text).  Sequence b has n_targets_host[b] = n_b targets (HOST array [B]);
+ *   targets int32 [B][max_targets][4] device.  The final-normed hidden row at position T - n_b + j predicts target j (0 <= j < n_b); per codebook c:
+ *     logprob[b][j][c] = log_softmax(head_code[c](hidden))[targets[b][j][c]]   on the RAW logits (no temperature, penalty, top-P / top-K)
+ *     argmax[b][j][c]  = the first index of the largest logit (torch.argmax)
+ *   both [B][max_targets][4] device.  Entries j >= n_b are written as 0 and -1; a target outside [0, vocab_code) gives NaN and -1 (no logit is read for it).
+ * Positions are cumsum(mask) - 1 with pads at 1, exactly as ctts_gpt_begin computes them, so a sequence scores the same alone as left padded inside a
+ * batch.  (train_lora.py:439 passes no position_ids, so its forward uses arange, llama.py:953-954: the two agree for unpadded rows only.)
+ * Errors naming the limit: B > max_batch, T > max_seq, n_b < 1, n_b > T, n_b > max_targets, a handle that is not ready.
+ * The call overwrites KV lanes 0..B-1 and the prompt-pass workspaces: it ENDS any generate state (sample, decode, admit, ... need a new
+ * ctts_gpt_begin, as after create).  It honours the slots of ctts_gpt_set_row_adapters per sequence, as begin does.  fp32 and fp16 engines; the code
+ * heads only.  The first call allocates a scratch of 2048 x (hidden + 4 * vocab_code + 1) words (27 MB at the real widths).  Asynchronous: never
+ * synchronises.  Under "batch_invariant" see the CONTRACT above. */
+int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* attention_mask_dev, const float* emb_dev, const int32_t* targets_dev,
+                   const int32_t* n_targets_host, int max_targets, float* logprob_dev, int32_t* argmax_dev, void* stream);
 
 /* Sample phase for the current hidden rows: final RMSNorm + 4 folded heads + sampler chain +
  * EOS/finish bookkeeping + next-token embedding (gpt.py:422-494,527-532).  Used once after prefill
