@@ -113,10 +113,12 @@ SYMBOLS = [
     ("ctts_gpt_admit_adapters", C.c_int, [_P, C.c_int, _P, _P, _P]),
     ("ctts_gpt_set_row_sampling", C.c_int, [_P, _P, C.c_int]),
     ("ctts_gpt_admit_sampling", C.c_int, [_P, C.c_int, _P, _P, _P]),
+    ("ctts_gpt_set_logprob_out", C.c_int, [_P, _P, _P, _P]),
     ("ctts_gpt_logits", C.c_int, [_P, _P, _P]),
     ("ctts_gpt_force_ids", C.c_int, [_P, _P, _P]),
     ("ctts_sampler_run", C.c_int, [C.POINTER(SamplerCfg), _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     ("ctts_sampler_run_rows", C.c_int, [C.POINTER(SamplerCfg), _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    ("ctts_sampler_run_rows_lp", C.c_int, [C.POINTER(SamplerCfg), _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     ("ctts_gpt_time_decode", C.c_int, [_P, C.c_int, C.POINTER(C.c_float), _P]),
     ("ctts_gpt_step_bytes", C.c_double, [_P, C.c_int, C.c_double]),
     ("ctts_voc_create", C.c_int, [C.POINTER(VocCfg), C.POINTER(_P)]),

@@ -239,6 +239,7 @@ struct ctts_gpt {
     ctts_gen_io io = {};
     hipStream_t cap_stream = nullptr;
     SamplerDyn* dyn = nullptr;                   // device copy of the per-call sampler state (rewritten by begin; read by the heads + sampler nodes)
+    bool sampled = false;                        // a sample phase has been enqueued since begin (ctts_gpt_set_logprob_out is refused from then on)
     // Captured decode graphs, keyed by what shapes the launches (batch, mode, KV binding): caller buffers and sampling
     // parameters are read from `dyn` at run time, so consecutive generate() calls replay the same executable graph.
     struct GraphEntry { hipGraph_t graph; hipGraphExec_t exec; };
@@ -1358,6 +1359,7 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
     hipStream_t s = (hipStream_t)stream;
     h->B = B; h->B0 = B; h->T = T; h->io = *io;
     h->admitted = false;
+    h->sampled = false;
     h->rows_host.assign(B, RowState{});
     for (int b = 0; b < B; ++b) {
         RowState& r = h->rows_host[b];
@@ -1524,9 +1526,22 @@ extern "C" int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* mask, co
 static inline int pick_decode_path(ctts_gpt* h, int longest);
 static int run_decode_step(ctts_gpt* h, hipStream_t s);
 
+// Log-probs of the sampled ids (include/ctts_hip.h): the two destinations are the last words of the per-call block the sampler reads (SamplerDyn), so a
+// captured decode graph serves calls with and without them; begin's rewrite of the block leaves both null.
+extern "C" int ctts_gpt_set_logprob_out(ctts_gpt* h, float* lp_raw, float* lp_sampled, void* stream) {
+    if (!h || h->B == 0) { ctts_set_error("set_logprob_out: no generate state (call ctts_gpt_begin first)"); return 1; }
+    if (h->text_mode) { ctts_set_error("set_logprob_out: the refine-text pass (infer_text) returns no log-probs; code mode only"); return 1; }
+    if (h->sampled) { ctts_set_error("set_logprob_out: called after the first ctts_gpt_sample / ctts_gpt_decode of this call; set the buffers right after ctts_gpt_begin"); return 1; }
+    float* const p[2] = {lp_raw, lp_sampled};
+    static_assert(offsetof(SamplerDyn, lp_sampled) == offsetof(SamplerDyn, lp_raw) + sizeof(float*), "the two destinations are copied as one pair");
+    CTTS_HIP_CHECK(hipMemcpyAsync((char*)h->dyn + offsetof(SamplerDyn, lp_raw), p, sizeof(p), hipMemcpyHostToDevice, (hipStream_t)stream));      // pageable source: staged before the call returns
+    return 0;
+}
+
 extern "C" int ctts_gpt_sample(ctts_gpt* h, void* stream) {
     if (!h || h->B == 0) { ctts_set_error("sample: call begin first"); return 1; }
     CTTS_RANGE("ctts_gpt_sample");
+    h->sampled = true;
     if (h->batch_inv) {          // the last prompt token's layer pass first (see prefill_invariant): a decode step
         if (pick_decode_path(h, 0)) return 1;
         return run_decode_step(h, (hipStream_t)stream);
@@ -1712,6 +1727,7 @@ extern "C" int ctts_gpt_decode(ctts_gpt* h, int n_steps, int use_graph, void* st
     if (!h || h->B == 0) { ctts_set_error("decode: call begin first"); return 1; }
     CTTS_RANGE("ctts_gpt_decode");              // reference: nvtx "forward" per decode step + "execute" (trt_models/predictor.py:164)
     hipStream_t s = (hipStream_t)stream;
+    h->sampled = true;
     if (n_steps < 1) { h->launched += n_steps; return pick_decode_path(h, advance_rows(h, n_steps) + 1); }
     if (plan_decode(h, n_steps)) return 1;
     (void)advance_rows(h, n_steps);
@@ -1929,7 +1945,7 @@ extern "C" int ctts_gpt_force_ids(ctts_gpt* h, const int32_t* ids, void* stream)
 // Stand-alone sampler (ctts_sampler_run / ctts_sampler_run_rows): the kernels read their configuration -- and the per-sequence knobs -- from device
 // memory, a small ring of slots, one per call in flight.  per_seq == nullptr: every row uses the knobs of `sc`.
 static int sampler_run_standalone(const ctts_sampler_cfg* sc, const ctts_row_sampling* per_seq, const float* logits, const int32_t* history, int hist_len,
-                                  const float* q, int rows, int vocab, int step, int32_t* idx, void* stream, const char* who) {
+                                  const float* q, int rows, int vocab, int step, int32_t* idx, float* lp_raw, float* lp_sampled, void* stream, const char* who) {
     if (!sc || !logits || !q || !idx || (hist_len > 0 && !history)) { ctts_set_error("%s: null argument", who); return 1; }
     const int nseq = (rows + CTTS_NUM_VQ - 1) / CTTS_NUM_VQ;
     if (per_seq) {
@@ -1955,7 +1971,7 @@ static int sampler_run_standalone(const ctts_sampler_cfg* sc, const ctts_row_sam
     SamplerArgs sa = {};
     sa.dyn = ring + k;
     sa.logits = logits; sa.V = vocab; sa.B = rows; sa.st = nullptr; sa.history = history; sa.hist_len = hist_len;
-    sa.step_override = step; sa.idx_out = idx;
+    sa.step_override = step; sa.idx_out = idx; sa.lp_raw_out = lp_raw; sa.lp_sampled_out = lp_sampled;
     if (per_seq) {
         std::vector<RowSampling> tab(nseq);
         for (int i = 0; i < nseq; ++i) tab[i] = knobs_of_abi(per_seq[i]);
@@ -1967,13 +1983,19 @@ static int sampler_run_standalone(const ctts_sampler_cfg* sc, const ctts_row_sam
 
 extern "C" int ctts_sampler_run(const ctts_sampler_cfg* sc, const float* logits, const int32_t* history, int hist_len, const float* q,
                                 int rows, int vocab, int step, int32_t* idx, void* stream) {
-    return sampler_run_standalone(sc, nullptr, logits, history, hist_len, q, rows, vocab, step, idx, stream, "sampler_run");
+    return sampler_run_standalone(sc, nullptr, logits, history, hist_len, q, rows, vocab, step, idx, nullptr, nullptr, stream, "sampler_run");
 }
 
 extern "C" int ctts_sampler_run_rows(const ctts_sampler_cfg* sc, const ctts_row_sampling* per_seq, const float* logits, const int32_t* history, int hist_len,
                                      const float* q, int rows, int vocab, int step, int32_t* idx, void* stream) {
     if (!per_seq) { ctts_set_error("sampler_run_rows: null argument"); return 1; }
-    return sampler_run_standalone(sc, per_seq, logits, history, hist_len, q, rows, vocab, step, idx, stream, "sampler_run_rows");
+    return sampler_run_standalone(sc, per_seq, logits, history, hist_len, q, rows, vocab, step, idx, nullptr, nullptr, stream, "sampler_run_rows");
+}
+
+extern "C" int ctts_sampler_run_rows_lp(const ctts_sampler_cfg* sc, const ctts_row_sampling* per_seq, const float* logits, const int32_t* history, int hist_len,
+                                        const float* q, int rows, int vocab, int step, int32_t* idx, float* lp_raw, float* lp_sampled, void* stream) {
+    if (!per_seq) { ctts_set_error("sampler_run_rows_lp: null argument"); return 1; }
+    return sampler_run_standalone(sc, per_seq, logits, history, hist_len, q, rows, vocab, step, idx, lp_raw, lp_sampled, stream, "sampler_run_rows_lp");
 }
 
 extern "C" int ctts_gpt_time_decode(ctts_gpt* h, int n_steps, float* ms_per_step, void* stream) {
@@ -1982,6 +2004,7 @@ extern "C" int ctts_gpt_time_decode(ctts_gpt* h, int n_steps, float* ms_per_step
     // the steps run as ctts_gpt_decode runs them (plan_decode: each step's path from its own context); the graphs of every segment are captured
     // before the clock starts
     n_steps = (n_steps + h->graph_steps - 1) / h->graph_steps * h->graph_steps;
+    h->sampled = true;
     if (plan_decode(h, n_steps)) return 1;
     for (const auto& sg : h->segs) if (run_segment(h, sg, true, false, s)) return 1;
     CTTS_HIP_CHECK(hipEventRecord(h->ev0, s));

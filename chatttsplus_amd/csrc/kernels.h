@@ -143,6 +143,8 @@ struct SamplerDyn {
     int hidden_stride;      //   = max_new_token * H
     int rows0;              // multinomial rows of the batch the call STARTED with (B0 * 4, text mode B0): row stride of `noise`, which stays
                             //   indexed by utterance when finished rows are compacted away
+    float* lp_raw;          // [B][max_new][4] like `ids`, or null: log-probs of the sampled ids (ctts_gpt_set_logprob_out; begin resets both to null)
+    float* lp_sampled;
 };
 #define CTTS_CONST_AS __attribute__((address_space(4)))
 typedef const CTTS_CONST_AS SamplerDyn* SamplerDynPtr;
@@ -169,6 +171,8 @@ struct SamplerArgs {
     int step_override;
     int* idx_out;           // [rows]
     const RowSampling* seq_knobs;   // ctts_sampler_run_rows: [rows / 4] knobs per sequence (null: every row uses dyn->cfg)
+    float* lp_raw_out;      // ctts_sampler_run_rows_lp: [rows] log-probs of idx_out (either may be null)
+    float* lp_sampled_out;
 };
 
 int launch_gemm(int dtype, int nbg, int pro, int epi, const GemmArgs& a, int chunks, hipStream_t s);

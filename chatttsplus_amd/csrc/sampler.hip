@@ -71,7 +71,14 @@ __device__ inline float exp_noise_of(const RowIn& in, int j) {
 //   larger probabilities), accumulated in fp64 in rank order exactly as before, decides the cut for all ranks at once.
 //   Falls back to the serial extraction when top_k > 64 or more than 64 candidates tie at the threshold.
 // `lds64`: 64 x 8 bytes of LDS private to this wave.
-__device__ int sample_row(const SampleKnobs& c, const float* tab, const RowIn& in, int V, int lane, const float (&lg)[VPL], unsigned long long* lds64) {
+//
+// Log-probs of the returned id (`want_lp`, wave-uniform; include/ctts_hip.h ctts_gpt_set_logprob_out).  Both are computed AFTER the race from values the
+// sampling arithmetic has already produced and feed nothing back into it; when `want_lp` is false no extra reduction runs.
+//   lp_raw      log_softmax(lg)[id]: the row as the heads wrote it (before the division by the temperature) -- what ctts_gpt_score gives for the token
+//   lp_sampled  log of the probability the race drew from: e * inv2 of the chosen element (one-element-per-lane race) or e2[i] * inv2 (slot-wise race).
+//               When every ratio is 0 or NaN, element 0 stands in and may lie outside the kept set: then -inf
+__device__ int sample_row(const SampleKnobs& c, const float* tab, const RowIn& in, int V, int lane, const float (&lg)[VPL], unsigned long long* lds64,
+                          const bool want_lp, float& lp_raw, float& lp_sampled) {
     float x[VPL];
     unsigned valid = 0;
 #pragma unroll
@@ -222,6 +229,11 @@ __device__ int sample_row(const SampleKnobs& c, const float* tab, const RowIn& i
             const float ratio = __fdiv_rn(e * inv2, exp_noise_of(in, myi));
             bkey = umax64(bkey, ((unsigned long long)f32_key(ratio) << 32) | (unsigned)(0x7FFFFFFF - myi));
         }
+        bkey = wave_max_u64(bkey);
+        if (want_lp) {                                             // the lane that holds the winner (none: element 0 stood in from outside the kept set)
+            const bool mine = on && myi == 0x7FFFFFFF - (int)(unsigned)bkey;
+            lp_sampled = wave_max(mine ? logf(e * inv2) : -INFINITY);
+        }
     } else {
         float m2 = -INFINITY;
 #pragma unroll
@@ -242,9 +254,31 @@ __device__ int sample_row(const SampleKnobs& c, const float* tab, const RowIn& i
                 bkey = umax64(bkey, ((unsigned long long)f32_key(ratio) << 32) | (unsigned)(0x7FFFFFFF - j));
             }
         }
+        bkey = wave_max_u64(bkey);
+        if (want_lp) {
+            const int bi = 0x7FFFFFFF - (int)(unsigned)bkey;
+            float pe = 0.f;                                        // e2 of the winner's slot; 0 outside the kept set -> log 0 = -inf
+#pragma unroll
+            for (int i = 0; i < VPL; ++i) pe = (i == (bi >> 6)) ? e2[i] : pe;
+            lp_sampled = readlane_f(logf(pe * inv2), bi & 63);
+        }
     }
-    bkey = wave_max_u64(bkey);
     const int besti = 0x7FFFFFFF - (int)(unsigned)bkey;
+    if (want_lp) {
+        float rm = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) rm = ((valid >> i) & 1u) ? fmaxf(rm, lg[i]) : rm;
+        rm = wave_max(rm);
+        float rs = 0.f, rv = 0.f;
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) {
+            const float t = lg[i] - rm;
+            rs += ((valid >> i) & 1u) ? expf(t) : 0.f;
+            rv = (i == (besti >> 6)) ? t : rv;
+        }
+        rs = wave_sum(rs);
+        lp_raw = readlane_f(rv, besti & 63) - logf(rs);
+    }
     return besti;
 }
 
@@ -308,10 +342,21 @@ __global__ __launch_bounds__(256) void sampler_generate_kernel(const int* st_wor
     in.seed = d->seed; in.uid_lo = (unsigned)uid.x; in.uid_hi = (unsigned)uid.y; in.vq = (unsigned)vq; in.attempt = (unsigned)fe.z;
     SampleKnobs kn;
     kn.top_p_threshold = knob->top_p_threshold; kn.top_k = knob->top_k; kn.min_keep = knob->min_keep; kn.eos = d->cfg.eos; kn.min_new = knob->min_new;
-    const int idx = sample_row(kn, tab, in, a.V, lane, lg, cand_s[vq]);
+    // log-probs of the sampled id (ctts_gpt_set_logprob_out): destinations in the per-call block next to `ids` (scalar loads off the preloaded argument,
+    // issued with the others), null = off: one wave-uniform branch
+    float* const lp_raw_out = d->lp_raw;
+    float* const lp_smp_out = d->lp_sampled;
+    const bool want_lp = (lp_raw_out != nullptr) || (lp_smp_out != nullptr);
+    float lp_raw = 0.f, lp_smp = 0.f;
+    const int idx = sample_row(kn, tab, in, a.V, lane, lg, cand_s[vq], want_lp, lp_raw, lp_smp);
     if (lane == 0) {
         idx_s[vq] = idx;
-        if (fin_in == 0) d->ids[((size_t)seq * d->cfg.max_new + step) * CTTS_NUM_VQ + vq] = idx;      // (a finished row's tokens are never read: gpt.py:295-297)
+        if (fin_in == 0) {                                                                           // (a finished row's tokens are never read: gpt.py:295-297)
+            const size_t at = ((size_t)seq * d->cfg.max_new + step) * CTTS_NUM_VQ + vq;
+            d->ids[at] = idx;
+            if (lp_raw_out != nullptr) lp_raw_out[at] = lp_raw;
+            if (lp_smp_out != nullptr) lp_smp_out[at] = lp_smp;
+        }
         a.hist_ring[(size_t)(b * CTTS_NUM_VQ + vq) * 16 + (step & 15)] = idx;
     }
     __syncthreads();
@@ -653,8 +698,14 @@ __global__ __launch_bounds__(256) void sampler_rows_kernel(const SamplerArgs a) 
     float lg[VPL];
 #pragma unroll
     for (int i = 0; i < VPL; ++i) { const int j = lane + 64 * i; lg[i] = (j < a.V) ? logits[j] : 0.f; }
-    const int idx = sample_row(kn, tab, in, a.V, lane, lg, cand_s[w]);
-    if (lane == 0) a.idx_out[row] = idx;
+    const bool want_lp = (a.lp_raw_out != nullptr) || (a.lp_sampled_out != nullptr);
+    float lp_raw = 0.f, lp_smp = 0.f;
+    const int idx = sample_row(kn, tab, in, a.V, lane, lg, cand_s[w], want_lp, lp_raw, lp_smp);
+    if (lane == 0) {
+        a.idx_out[row] = idx;
+        if (a.lp_raw_out != nullptr) a.lp_raw_out[row] = lp_raw;
+        if (a.lp_sampled_out != nullptr) a.lp_sampled_out[row] = lp_smp;
+    }
 }
 
 // test hook (ctts_sampler_noise): the device noise of one multinomial row, through the very function the samplers call

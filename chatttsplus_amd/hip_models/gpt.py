@@ -38,6 +38,13 @@ class GenerationOutputs:          # gpt.py:280-284
     ids: List[torch.Tensor]
     attentions: list
     hiddens: List[torch.Tensor]
+    # return_logprobs=True (no counterpart in the reference): per sequence b, [n_b, 4] aligned with ids[b] --
+    #   logprobs          log_softmax(raw code logits)[id]: what GPT.score gives for the same token
+    #   sampled_logprobs  log p(id) under the distribution the sampler drew from (after temperature, repetition penalty, top-P, top-K, min_new_token)
+    #   final_logprobs    [2, 4] (raw, sampled) of the step that sampled EOS -- its ids are not part of ids[b] -- or None for a sequence that ended by its limit
+    logprobs: Optional[List[torch.Tensor]] = None
+    sampled_logprobs: Optional[List[torch.Tensor]] = None
+    final_logprobs: Optional[List[Optional[torch.Tensor]]] = None
 
 
 @dataclass(repr=False, eq=False)
@@ -599,8 +606,10 @@ class GPT:
                  min_new_token=0, logits_warpers=[], logits_processors=[], infer_text=False, return_attn=False,
                  return_hidden=False, stream=False, show_tqdm=True, ensure_non_empty=True, stream_batch=24,
                  context=None, noise="auto", seed: Optional[int] = None, max_restarts: int = 64, utt_ids=None, max_new_tokens_per_row=None,
-                 sampling_per_row=None):
-        """`noise`: "torch" draws q = empty(B*4,V).exponential_() per step from torch's CPU generator -- the very numbers
+                 sampling_per_row=None, return_logprobs=False):
+        """`return_logprobs`: every yielded GenerationOutputs (the partial ones of stream=True too) carries `logprobs`, `sampled_logprobs` and
+        `final_logprobs` for the tokens so far, written by the sampler as it draws them (ctts_gpt_set_logprob_out; code mode only).
+        `noise`: "torch" draws q = empty(B*4,V).exponential_() per step from torch's CPU generator -- the very numbers
         torch.multinomial consumes in the reference, so TorchSeedContext(seed) reproduces the CPU path's tokens (costs
         ~21 ns of host time per element: hidden behind the GPU up to batch ~8, 3x the step time at batch 32); "device"
         uses the on-device Philox generator keyed by `seed` (None: one draw from torch's CPU generator, so manual_seed
@@ -616,6 +625,8 @@ class GPT:
             raise _lib.HipBackendError("return_attn=True is unsupported (the reference's eager attention path is broken, SURVEY F2)")
         if not self._finalized:
             raise _lib.HipBackendError("weights not loaded")
+        if return_logprobs and infer_text:
+            raise _lib.HipBackendError("return_logprobs: the refine-text pass (infer_text=True) returns no log-probs; code mode only")
         if self._busy_token.owner is not None:
             # engine state (batch, step counters, noise staging ring) and the KV cache -- shared with LoRA-merged sibling engines -- belong
             # to ONE generate() at a time
@@ -625,7 +636,7 @@ class GPT:
         try:
             yield from self._generate(emb, inputs_ids, temperature, eos_token, attention_mask, max_new_token, min_new_token, logits_warpers,
                                       logits_processors, infer_text, return_hidden, stream, ensure_non_empty, stream_batch, context, noise, seed,
-                                      max_restarts, utt_ids, max_new_tokens_per_row, sampling_per_row)
+                                      max_restarts, utt_ids, max_new_tokens_per_row, sampling_per_row, bool(return_logprobs))
         finally:
             if sampling_per_row is not None:
                 self._lib.ctts_gpt_set_row_sampling(self._h, None, 0)      # a later plain call takes its own values
@@ -633,7 +644,7 @@ class GPT:
 
     def _generate(self, emb, inputs_ids, temperature, eos_token, attention_mask, max_new_token, min_new_token, logits_warpers, logits_processors,
                   infer_text, return_hidden, stream, ensure_non_empty, stream_batch, context, noise, seed, max_restarts, utt_ids=None,
-                  row_limits=None, sampling_per_row=None):
+                  row_limits=None, sampling_per_row=None, return_logprobs=False):
         context = context or Context()
         lib, h = self._lib, self._h
         B, T = int(inputs_ids.shape[0]), int(inputs_ids.shape[1])
@@ -656,6 +667,7 @@ class GPT:
         # default max_new_token = 2048 made this a 201 MB zero-fill per call at batch 32)
         ids = torch.empty(B, max_new_token, NVQ, dtype=torch.int32, device=dev)
         hid = torch.empty(B, max_new_token, H, dtype=torch.float32, device=dev) if return_hidden else None
+        lps = torch.empty(2, B, max_new_token, NVQ, dtype=torch.float32, device=dev) if return_logprobs else None      # (raw, sampled), laid out like ids
         finish = torch.zeros(B, dtype=torch.int32, device=dev)
         end_idx = torch.zeros(B, dtype=torch.int32, device=dev)
         n_draws = max_new_token + max_restarts
@@ -726,6 +738,8 @@ class GPT:
             if knobs is not None:
                 _lib.check(lib.ctts_gpt_set_row_sampling(h, knobs, B), "set_row_sampling")
             _lib.check(lib.ctts_gpt_begin(h, B, T, mask.data_ptr(), C.byref(sc), C.byref(io), st), "begin")
+            if lps is not None:
+                _lib.check(lib.ctts_gpt_set_logprob_out(h, lps[0].data_ptr(), lps[1].data_ptr(), st), "set_logprob_out")
             _lib.check(lib.ctts_gpt_prefill(h, emb.data_ptr(), st), "prefill")
             tick("begin+prefill")
             steps, alld = C.c_int32(0), C.c_int32(0)
@@ -759,7 +773,7 @@ class GPT:
                     if steps.value == prev and not alld.value:
                         raise _lib.HipBackendError("decode made no progress (device state inconsistent)")
                     if steps.value % chunk == 0 and steps.value > prev:
-                        yield self._outputs(ids, hid, end_idx, infer_text)
+                        yield self._outputs(ids, hid, end_idx, infer_text, lps, finish)
             else:
                 # one chunk stays in flight while the previous chunk's progress words are inspected (no GPU bubble at the
                 # poll); steps launched after every sequence finished exit at their first instruction on the device
@@ -820,7 +834,7 @@ class GPT:
                 tick("final_progress")
             self._restore_rng(rng_states, used_draws)
             self.saturations = self._report_saturations(h, st, "generate()")
-            out = self._outputs(ids, hid, end_idx, infer_text)
+            out = self._outputs(ids, hid, end_idx, infer_text, lps, finish)
             tick("outputs")
             yield out
 
@@ -830,7 +844,7 @@ class GPT:
                       attention_mask: Optional[torch.Tensor] = None, max_new_token=2048, min_new_token=0, logits_warpers=[],
                       logits_processors=[], return_hidden=False, ensure_non_empty=True, context=None, seed: Optional[int] = None,
                       max_restarts: int = 64, utt_ids=None, max_new_tokens_per_row=None, rows: Optional[int] = None, admit_min: Optional[int] = None,
-                      on_done=None, infer_text: bool = False, adapter_slots=None, sampling_per_row=None) -> GenerationOutputs:
+                      on_done=None, infer_text: bool = False, adapter_slots=None, sampling_per_row=None, return_logprobs=False) -> GenerationOutputs:
         """N utterances (left-padded prompts emb[N,T,H], like generate()) through `rows` <= max_batch decode rows: whenever utterances
         finish, queued ones take over their rows (ctts_gpt_admit) instead of the whole slice waiting for its slowest row as the reference's
         slices of 4 do (pipeline:391-397, gpt.py:527-546); once the queue is empty finished rows are compacted away (ctts_gpt_compact).
@@ -840,18 +854,19 @@ class GPT:
         `on_done(list_of_indices)` is called (on the host, while decoding continues) as utterances complete.
         `adapter_slots` = the resident adapter slot (load_adapter) of every utterance or -1 / None: per-utterance LoRA under row re-use (an admitted
         utterance brings its own adapter, ctts_gpt_admit_adapters).  `sampling_per_row` = one dict of sampling knobs or None per utterance (as in
-        generate()): an admitted utterance brings its own knobs (ctts_gpt_admit_sampling).
+        generate()): an admitted utterance brings its own knobs (ctts_gpt_admit_sampling).  `return_logprobs`: as in generate() -- the log-prob arrays are
+        indexed by utterance like the ids, so admission, compaction and ensure_non_empty re-admission need nothing extra.
         Returns one GenerationOutputs for all N utterances, in input order."""
         gen = self.generate_many_iter(emb, inputs_ids, temperature, eos_token, attention_mask=attention_mask, max_new_token=max_new_token,
                                       min_new_token=min_new_token, logits_warpers=logits_warpers, logits_processors=logits_processors,
                                       return_hidden=return_hidden, ensure_non_empty=ensure_non_empty, context=context, seed=seed, max_restarts=max_restarts,
                                       utt_ids=utt_ids, max_new_tokens_per_row=max_new_tokens_per_row, rows=rows, admit_min=admit_min, infer_text=infer_text,
-                                      adapter_slots=adapter_slots, sampling_per_row=sampling_per_row)
+                                      adapter_slots=adapter_slots, sampling_per_row=sampling_per_row, return_logprobs=return_logprobs)
         try:
             while True:
                 ev = next(gen)
                 if on_done is not None:
-                    on_done([u for u, _, _ in ev])
+                    on_done([e[0] for e in ev])
         except StopIteration as stop:
             return stop.value
 
@@ -859,15 +874,19 @@ class GPT:
     def generate_many_iter(self, emb, inputs_ids, temperature, eos_token, attention_mask=None, max_new_token=2048, min_new_token=0, logits_warpers=[],
                            logits_processors=[], return_hidden=False, ensure_non_empty=True, context=None, seed=None, max_restarts: int = 64,
                            utt_ids=None, max_new_tokens_per_row=None, rows=None, admit_min=None, infer_text: bool = False, progress: bool = False,
-                           adapter_slots=None, sampling_per_row=None):
+                           adapter_slots=None, sampling_per_row=None, return_logprobs=False):
         """generate_many as a generator: yields [(utterance index, ids [n,4] long, hiddens [n,768] or None)] for the utterances that completed
         since the last yield -- while the rest keeps decoding (what was yielded is final: its rows were written before the report that showed
         the utterance finished) -- and returns (StopIteration.value) the GenerationOutputs of all N utterances.
         `infer_text=True`: the refine-text pass (gpt.py infer_text: the 21178-way text head, one id per step) through the same row re-use; ids are [n].
         `progress=True` (streaming): between the completion lists the generator also yields ("progress", [(utterance index, tokens so far n, ids[:n],
-        hiddens[:n] or None)]) for the utterances still decoding -- the first n tokens of an utterance are final once reported."""
+        hiddens[:n] or None)]) for the utterances still decoding -- the first n tokens of an utterance are final once reported.
+        `return_logprobs=True`: every tuple of either kind gains a last element, a GenerationOutputs of that one utterance's tokens so far (ids, hiddens,
+        logprobs, sampled_logprobs, final_logprobs: lists of one), and the returned GenerationOutputs carries the three fields for all N."""
         if not self._finalized:
             raise _lib.HipBackendError("weights not loaded")
+        if return_logprobs and infer_text:
+            raise _lib.HipBackendError("return_logprobs: the refine-text pass (infer_text=True) returns no log-probs; code mode only")
         if self._busy_token.owner is not None:
             raise _lib.HipBackendError("GPT.generate is already running on this engine (or on an engine sharing its KV cache)")
         self._busy_token.owner = self
@@ -875,7 +894,7 @@ class GPT:
             return (yield from self._generate_many(emb, inputs_ids, temperature, eos_token, attention_mask, int(max_new_token), min_new_token, logits_warpers,
                                                    logits_processors, return_hidden, ensure_non_empty, context or Context(), seed, max_restarts, utt_ids,
                                                    max_new_tokens_per_row, rows, admit_min, bool(infer_text), bool(progress), adapter_slots,
-                                                   sampling_per_row))
+                                                   sampling_per_row, bool(return_logprobs)))
         finally:
             if adapter_slots is not None:
                 self.set_row_adapters(None)
@@ -885,7 +904,7 @@ class GPT:
 
     def _generate_many(self, emb, inputs_ids, temperature, eos_token, attention_mask, max_new_token, min_new_token, logits_warpers, logits_processors,
                        return_hidden, ensure_non_empty, context, seed, max_restarts, utt_ids, row_limits, rows, admit_min, infer_text=False, progress=False,
-                       adapter_slots=None, sampling_per_row=None):
+                       adapter_slots=None, sampling_per_row=None, return_logprobs=False):
         lib, h, dev = self._lib, self._h, self.device
         N, T = int(inputs_ids.shape[0]), int(inputs_ids.shape[1])
         H, NVQ = self.model_dim, self.num_vq
@@ -910,6 +929,7 @@ class GPT:
                 raise _lib.HipBackendError(f"adapter_slots: {len(slots)} entries for {N} utterances (code mode only)")
         ids = torch.empty(N, max_new_token, NVQ, dtype=torch.int32, device=dev)
         hid = torch.empty(N, max_new_token, H, dtype=torch.float32, device=dev) if return_hidden else None
+        lps = torch.empty(2, N, max_new_token, NVQ, dtype=torch.float32, device=dev) if return_logprobs else None       # (raw, sampled), indexed like ids
         finish = torch.zeros(N, dtype=torch.int32, device=dev)
         end_idx = torch.zeros(N, dtype=torch.int32, device=dev)
         admit_min = max(1, int(admit_min) if admit_min else R // 8)
@@ -956,6 +976,8 @@ class GPT:
             if knobs is not None:
                 _lib.check(lib.ctts_gpt_set_row_sampling(h, (_lib.RowSampling * R)(*[knobs[u] for u in first]), R), "set_row_sampling")
             _lib.check(lib.ctts_gpt_begin(h, R, Ta, mask_a.data_ptr(), C.byref(sc), C.byref(io), st), "begin")
+            if lps is not None:
+                _lib.check(lib.ctts_gpt_set_logprob_out(h, lps[0].data_ptr(), lps[1].data_ptr(), st), "set_logprob_out")
             _lib.check(lib.ctts_gpt_prefill(h, emb_a.data_ptr(), st), "prefill")
             _lib.check(lib.ctts_gpt_sample(h, st), "sample")
             queue = [(u, 0) for u in order[R:]]                    # (utterance, regenerate attempt)
@@ -967,6 +989,13 @@ class GPT:
             evs = [torch.cuda.Event() for _ in range(2)]
             layouts = [None, None]
             pending, n_chunks, launched = [], 0, 1
+
+            def one(u, n, eos):
+                """GenerationOutputs of utterance (buffer position) u alone: its first n tokens; `eos`: the step after them sampled EOS"""
+                fl = lps[:, u, n].clone() if (eos and n < max_new_token) else None
+                return GenerationOutputs(ids=[ids[u, :n].to(torch.long)], attentions=[], hiddens=[hid[u, :n]] if hid is not None else [],
+                                         logprobs=[lps[0, u, :n]], sampled_logprobs=[lps[1, u, :n]], final_logprobs=[fl])
+
             while n_done < N and not context.get():
                 while len(pending) < 2:
                     _lib.check(lib.ctts_gpt_decode(h, chunk, 1 if self.use_graph else 0, st), "decode")
@@ -985,12 +1014,15 @@ class GPT:
                     live = [(book.tickets[tk][0], int(end)) for tk, (fin, end) in zip(lay, states) if tk is not None and tk in book.tickets and not fin and end > 0]
                     if live:
                         yield ("progress", [(back[u], n, ids[u, :n, 0].to(torch.long) if infer_text else ids[u, :n].to(torch.long), hid[u, :n] if hid is not None else None)
-                                            for u, n in live])
+                                            + ((one(u, n, False),) if lps is not None else ()) for u, n in live])
+                # (which of the rows that finished did so by EOS: read before report() retires their tickets)
+                eos_of = {book.tickets[tk][0]: bool(fin & 2) for tk, (fin, end) in zip(lay, states) if fin and tk in book.tickets} if lps is not None else {}
                 finished_now, again = book.report(lay, states, ensure_non_empty, max_restarts)
                 queue = again + queue                              # first token was EOS (gpt.py:496-525): next noise attempt, ahead of the queue
                 n_done += len(finished_now)
                 if finished_now:
-                    yield [(back[u], ids[u, :n, 0].to(torch.long) if infer_text else ids[u, :n].to(torch.long), hid[u, :n] if hid is not None else None) for u, n in finished_now]
+                    yield [(back[u], ids[u, :n, 0].to(torch.long) if infer_text else ids[u, :n].to(torch.long), hid[u, :n] if hid is not None else None)
+                           + ((one(u, n, eos_of.get(u, False)),) if lps is not None else ()) for u, n in finished_now]
                 free = book.free_rows()
                 since_free = since_free + 1 if free else 0
                 if queue and free and (len(free) >= min(admit_min, len(queue)) or since_free >= 4 or len(free) == len(book.row_tk)):
@@ -1035,7 +1067,9 @@ class GPT:
                 inv = torch.as_tensor(np.argsort(np.asarray(back)), dtype=torch.long, device=dev)
                 ids, end_idx = ids.index_select(0, inv), end_idx.index_select(0, inv)
                 hid = hid.index_select(0, inv) if hid is not None else None
-            return self._outputs(ids, hid, end_idx, infer_text)
+                lps = lps.index_select(1, inv) if lps is not None else None
+                finish = finish.index_select(0, inv)
+            return self._outputs(ids, hid, end_idx, infer_text, lps, finish)
 
     # -- teacher-forced scoring (train_lora.py:430-469; ctts_gpt_score) ----------------------------------------------------------
     @torch.no_grad()
@@ -1103,13 +1137,20 @@ class GPT:
         if states and used < len(states):
             torch.random.set_rng_state(states[used])
 
-    def _outputs(self, ids, hid, end_idx, infer_text=False) -> GenerationOutputs:
+    def _outputs(self, ids, hid, end_idx, infer_text=False, lps=None, finish=None) -> GenerationOutputs:
         n = end_idx.cpu().tolist()
         out_ids = [ids[b, :n[b]].to(torch.long) for b in range(len(n))]                # gpt.py:295-297
         if infer_text:
             out_ids = [i[:, 0] for i in out_ids]                                        # gpt.py:298-299
         out_h = [hid[b, :n[b]] for b in range(len(n))] if hid is not None else []     # gpt.py:301-305
-        return GenerationOutputs(ids=out_ids, attentions=[], hiddens=out_h)
+        if lps is None:
+            return GenerationOutputs(ids=out_ids, attentions=[], hiddens=out_h)
+        # the step that sampled EOS wrote its log-probs at index end_idx (its ids are not part of the sequence); a sequence that ended by its limit has none
+        eos = finish.cpu().tolist()
+        cap = int(lps.shape[2])
+        return GenerationOutputs(ids=out_ids, attentions=[], hiddens=out_h, logprobs=[lps[0, b, :n[b]] for b in range(len(n))],
+                                 sampled_logprobs=[lps[1, b, :n[b]] for b in range(len(n))],
+                                 final_logprobs=[lps[:, b, n[b]].clone() if (eos[b] and n[b] < cap) else None for b in range(len(n))])
 
     # -- test hooks ------------------------------------------------------------------------------
     def last_logits(self, B: int) -> torch.Tensor:

@@ -114,6 +114,79 @@ def per_utterance_overrides(base, entries) -> List[dict]:
     return out
 
 
+# -- log-probs of a generation and N-candidate ranking (infer(return_details=..., num_candidates=...); no counterpart in the reference) -----------------
+CANDIDATE_SHIFT = 48        # candidate k of utterance id u draws the device noise of key u | (k << 48): candidate 0 is the plain generation
+
+
+@dataclass(repr=False, eq=False)
+class CandidateDetails:
+    """One generated candidate of one utterance: `ids` [n, 4], `logprobs` / `sampled_logprobs` [n, 4] (GenerationOutputs), `final_logprobs` [2, 4] or None,
+    `hiddens` [n, 768] or None, `mean_logprob` = the mean of `logprobs` over tokens and codebooks (-inf for a candidate with no tokens)."""
+    ids: torch.Tensor
+    logprobs: torch.Tensor
+    sampled_logprobs: torch.Tensor
+    mean_logprob: float
+    final_logprobs: Optional[torch.Tensor] = None
+    hiddens: Optional[torch.Tensor] = None
+
+
+@dataclass(repr=False, eq=False)
+class InferDetails:
+    """What infer(return_details=True) yields instead of the bare list of waveforms.  Per utterance (lists in input order): `wavs`, `ids`, `logprobs`,
+    `sampled_logprobs`, `mean_logprob` (the length-normalised raw score: the negative of ScoreOutputs.nll for the same tokens).  With num_candidates:
+    `candidate` (the chosen index), `candidate_scores` ([N] mean log-probs) and `candidates` (the N CandidateDetails, hiddens dropped)."""
+    wavs: list
+    ids: List[torch.Tensor]
+    logprobs: List[torch.Tensor]
+    sampled_logprobs: List[torch.Tensor]
+    mean_logprob: List[float]
+    candidate: Optional[List[int]] = None
+    candidate_scores: Optional[List[torch.Tensor]] = None
+    candidates: Optional[List[List[CandidateDetails]]] = None
+
+
+def candidate_utt_id(utt_id: int, k: int) -> int:
+    """Noise key of candidate k of utterance id `utt_id`."""
+    return int(utt_id) | (int(k) << CANDIDATE_SHIFT)
+
+
+def check_candidate_request(num_candidates, utt_ids, stream: bool, noise_mode) -> int:
+    """Validates infer(num_candidates=N); returns N.  Each refusal is a HipBackendError that says what is refused."""
+    try:
+        n = int(num_candidates)
+    except (TypeError, ValueError):
+        n = 0
+    if n < 1 or n != num_candidates:
+        raise _lib.HipBackendError(f"num_candidates must be an integer >= 1 (got {num_candidates!r})")
+    if n > 1:
+        if stream:
+            raise _lib.HipBackendError("num_candidates > 1 needs stream=False: the candidates are ranked once all of them are complete")
+        if not (isinstance(noise_mode, str) and noise_mode in ("auto", "device")):
+            raise _lib.HipBackendError('num_candidates > 1 needs device noise (noise="device" or "auto"): host noise is indexed by batch row, not keyed by utterance id')
+        if n >= (1 << (64 - CANDIDATE_SHIFT)):
+            raise _lib.HipBackendError(f"num_candidates must be below {1 << (64 - CANDIDATE_SHIFT)}")
+        big = [int(u) for u in utt_ids if int(u) >= (1 << CANDIDATE_SHIFT) or int(u) < 0]
+        if big:
+            raise _lib.HipBackendError(f"num_candidates > 1: utterance id {big[0]} is not below 2^{CANDIDATE_SHIFT} (the candidate index takes the bits above)")
+    return n
+
+
+def mean_logprob(logprobs: torch.Tensor) -> float:
+    """Mean of [n, 4] log-probs over tokens and codebooks; -inf when there is no token."""
+    return float(logprobs.double().mean()) if logprobs.numel() else float("-inf")
+
+
+def select_candidate(scores) -> int:
+    """The default rule: the highest mean log-prob; ties go to the lowest index; a candidate with no tokens (-inf) or a NaN score ranks last."""
+    best, best_s = 0, None
+    for k, v in enumerate(scores):
+        v = float(v)
+        v = float("-inf") if v != v else v
+        if best_s is None or v > best_s:
+            best, best_s = k, v
+    return best
+
+
 def _get(cfg, key, default=None):
     try:
         return cfg[key]
@@ -571,6 +644,15 @@ class ChatTTSPlusPipeline:
                 utt_prompts = [d.get("prompt", params_infer_code.prompt) or "" for d in diffs]
             if any("spk_emb" in d for d in diffs):
                 params_infer_code = dataclasses.replace(params_infer_code, spk_emb=self._speaker_rows(params_infer_code.spk_emb, diffs))
+        # return_details / num_candidates (no counterpart in the reference): log-probs written by the sampler, N candidates per utterance ranked by them
+        n_cand = check_candidate_request(kwargs.get("num_candidates", 1), utt_ids, stream, noise_mode)
+        if (n_cand > 1 or kwargs.get("return_details")) and not refine_text_only:
+            if stream:
+                raise _lib.HipBackendError("return_details=True needs stream=False")
+            yield from self._infer_details(text_in, n_cand, bool(kwargs.get("return_details")), kwargs.get("select"), skip_refine_text, use_decoder,
+                                           params_refine_text, params_infer_code, gpt, slice_size, noise_mode, noise_seed, utt_ids, utt_limits, utt_sampling,
+                                           utt_prompts, lora_paths, kwargs.get("continuous"), kwargs.get("_ids_sink"))
+            return
         # `continuous=True` (no counterpart in the reference): the request's utterances are NOT cut into slices that each wait for their slowest
         # row (pipeline:391-397); slice_size decode rows are kept busy -- queued utterances take over the rows of finished ones
         # (GPT.generate_many_iter, ctts_gpt_admit).  Device noise keyed by utterance id: every utterance gets the waveform the sliced path gives it.
@@ -770,6 +852,117 @@ class ChatTTSPlusPipeline:
                 if total > length:
                     yield self._window(last, length, total, use_decoder)
 
+    def _infer_details(self, text_in, n_cand, return_details, select, skip_refine_text, use_decoder, params_refine_text, params_infer_code, gpt, slice_size,
+                       noise_mode, noise_seed, utt_ids, utt_limits, utt_sampling, utt_prompts, lora_paths, continuous, ids_sink):
+        """infer(return_details=True) / infer(num_candidates=N): the code pass with return_logprobs, every utterance served N times as ordinary decode rows
+        (candidate k under noise key candidate_utt_id(u, k), so candidate 0 is the plain generation), the winner picked by `select` or select_candidate,
+        only winners vocoded.  Sliced: max(1, slice_size // N) utterances per slice, one yield per slice; continuous (more rows than slice_size): the
+        whole request through GPT.generate_many, one yield.  The refine-text pass runs once per utterance, before the candidates are laid out."""
+        tok = self.models_dict["tokenizer"]
+        n_utt = len(text_in)
+        if n_cand > slice_size:
+            raise _lib.HipBackendError(f"num_candidates={n_cand} exceeds slice_size={slice_size}: the candidates of an utterance share one decode batch")
+        device_noise = n_cand > 1 or noise_mode == "device"
+        cont = bool(continuous) and n_utt * n_cand > slice_size
+        if cont and noise_mode not in ("auto", "device"):
+            raise _lib.HipBackendError("continuous=True works with device noise")
+        per_slice = max(1, slice_size // n_cand)
+        if noise_seed is None and noise_mode in ("auto", "device") and (device_noise or cont or min(per_slice, n_utt) * n_cand > 4):
+            noise_seed = int(torch.randint(0, 2 ** 62, (1,)).item())       # ONE draw per request (torch.manual_seed reproduces it)
+        texts = list(text_in)
+        if not skip_refine_text:                 # once per utterance, in the batches the plain call refines in
+            if cont:
+                refined = self._refine_text(texts, params_refine_text, continuous_rows=slice_size, seed=noise_seed, utt_ids=utt_ids)
+                texts = tok.decode([i[i.less(tok.break_0_ids)] for i in refined.ids])
+            else:
+                out = []
+                for ii in range(0, n_utt, slice_size):
+                    refined = self._refine_text(texts[ii:ii + slice_size], params_refine_text)
+                    out += tok.decode([i[i.less(tok.break_0_ids)] for i in refined.ids])
+                texts = out
+        texts = [t if t.strip().endswith("[uv_break]") else t + " [uv_break]" for t in texts]   # pipeline:414-416
+        per_utt_spk = torch.is_tensor(params_infer_code.spk_emb) and params_infer_code.spk_emb.dim() == 2 and params_infer_code.spk_emb.shape[0] == n_utt and n_utt > 1
+
+        def run(us):
+            """utterances `us` x n_cand candidates as one list of rows (utterance-major) -> one CandidateDetails per row"""
+            rows = [(u, k) for u in us for k in range(n_cand)]
+            pic = params_infer_code
+            if per_utt_spk or (torch.is_tensor(pic.spk_emb) and pic.spk_emb.dim() == 2 and pic.spk_emb.shape[0] == n_utt and len(rows) != n_utt):
+                pic = dataclasses.replace(pic, spk_emb=pic.spk_emb[torch.as_tensor([u for u, _ in rows], device=pic.spk_emb.device)])
+            gen_kw = dict(return_logprobs=True)
+            many = cont and len(rows) > slice_size
+            if device_noise or many or len(rows) > 4:      # (the plain call's rule: slices of <= 4 keep the reference-compatible torch noise under "auto")
+                gen_kw.update(seed=noise_seed, utt_ids=[candidate_utt_id(utt_ids[u], k) for u, k in rows])
+                if not many:
+                    gen_kw["noise"] = "device" if noise_mode == "auto" else noise_mode
+            elif noise_mode != "auto":
+                gen_kw["noise"] = noise_mode
+            if utt_limits is not None:
+                gen_kw["max_new_tokens_per_row"] = [utt_limits[u] for u, _ in rows]
+            if utt_sampling is not None:
+                gen_kw["sampling_per_row"] = [utt_sampling[u] for u, _ in rows]
+            if utt_prompts is not None:
+                gen_kw["prompts"] = [utt_prompts[u] for u, _ in rows]
+            slots = self._adapter_slots(gpt, [lora_paths[u] for u, _ in rows]) if lora_paths is not None else None
+            try:
+                if many:
+                    if slots is not None:
+                        gen_kw["adapter_slots"] = slots
+                    events = self._infer_code([texts[u] for u, _ in rows], False, use_decoder, pic, gpt=gpt, continuous=True, rows=slice_size, **gen_kw)
+                    try:
+                        while True:
+                            next(events)
+                    except StopIteration as stop:
+                        res = stop.value
+                else:
+                    if slots is not None:
+                        gpt.set_row_adapters(slots)
+                    res = None
+                    for res in self._infer_code([texts[u] for u, _ in rows], False, use_decoder, pic, gpt=gpt, **gen_kw):
+                        pass
+            finally:
+                if slots is not None and not many:
+                    gpt.set_row_adapters(None)
+            if res is None:           # (ensure_non_empty gave up: the reference's bare return, gpt.py:525)
+                return None
+            return [CandidateDetails(ids=res.ids[r], logprobs=res.logprobs[r].cpu(), sampled_logprobs=res.sampled_logprobs[r].cpu(),
+                                     mean_logprob=mean_logprob(res.logprobs[r]), final_logprobs=res.final_logprobs[r],
+                                     hiddens=res.hiddens[r] if use_decoder else None) for r in range(len(rows))]
+
+        def finish(us, cands):
+            chosen, scores = [], []
+            for j in range(len(us)):
+                group = cands[j * n_cand:(j + 1) * n_cand]
+                sc = torch.tensor([c.mean_logprob for c in group], dtype=torch.float64)
+                k = int(select(list(group))) if select is not None else select_candidate(sc.tolist())
+                if not 0 <= k < n_cand:
+                    raise _lib.HipBackendError(f"select returned {k}: not a candidate index (0..{n_cand - 1})")
+                chosen.append(k)
+                scores.append(sc)
+            win = [cands[j * n_cand + k] for j, k in enumerate(chosen)]
+            if ids_sink is not None:
+                ids_sink.extend((utt_ids[u], w.ids) for u, w in zip(us, win))
+            wavs = self._decode_to_wavs([w.hiddens if use_decoder else w.ids for w in win], use_decoder)      # pipeline:435-439; winners only
+            if not return_details:
+                return wavs
+            det = InferDetails(wavs=wavs, ids=[w.ids for w in win], logprobs=[w.logprobs for w in win], sampled_logprobs=[w.sampled_logprobs for w in win],
+                               mean_logprob=[w.mean_logprob for w in win])
+            if n_cand > 1:
+                det.candidate, det.candidate_scores = chosen, scores
+                det.candidates = [[dataclasses.replace(c, hiddens=None) for c in cands[j * n_cand:(j + 1) * n_cand]] for j in range(len(us))]
+            return det
+
+        if cont:
+            cands = run(list(range(n_utt)))
+            if cands is not None:
+                yield finish(list(range(n_utt)), cands)
+            return
+        for ii in range(0, n_utt, per_slice):
+            us = list(range(ii, min(ii + per_slice, n_utt)))
+            cands = run(us)
+            if cands is not None:
+                yield finish(us, cands)
+
     def _window(self, hiddens, s0: int, s1: int, use_decoder: bool = True) -> torch.Tensor:
         """[B, s1-s0] samples s0..s1 of the padded batch of prefix waveforms."""
         syn = self.synth if use_decoder else self._codes_synth()
@@ -828,6 +1021,10 @@ class ChatTTSPlusPipeline:
         Note SURVEY F8: the reference's repetition penalty skips rows >= 625 of the flattened [B*4] batch; a rank never holds
         more than max_batch <= 128 sequences (512 rows) per call, so the quirk cannot trigger on any rank."""
         from . import dist as cdist
+        if kwargs.get("num_candidates", 1) != 1 or kwargs.get("return_details"):
+            raise _lib.HipBackendError("infer_sharded serves one generation per utterance and returns waveforms: num_candidates > 1 and return_details are "
+                                       "refused (rank the candidates with infer() on one rank)")
+        kwargs.pop("num_candidates", None); kwargs.pop("return_details", None)
         if not isinstance(texts, list):
             texts = [texts]
         params = dataclasses.replace(params_infer_code)

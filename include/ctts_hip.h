@@ -338,6 +338,27 @@ int ctts_gpt_admit_adapters(ctts_gpt* h, int n, const int32_t* rows, const int32
 int ctts_gpt_set_row_sampling(ctts_gpt* h, const ctts_row_sampling* per_seq, int B);
 int ctts_gpt_admit_sampling(ctts_gpt* h, int n, const int32_t* rows, const ctts_row_sampling* p, void* stream);
 
+/* Log-probs of the sampled ids, written by the sampler as it draws them (no counterpart in the reference; ctts_gpt_score re-scores finished codes with a
+ * prompt pass, and knows the raw heads only).  Per (utterance, step, codebook), for the id the sampler returned:
+ *   lp_raw      log_softmax(raw logits)[id] -- the row as the code head wrote it, BEFORE the division by the temperature: the quantity ctts_gpt_score
+ *               returns for the same token
+ *   lp_sampled  log p(id) under the distribution the sampler drew from: the raw row after temperature, repetition penalty, top-P, top-K and the
+ *               min_new_token rule, i.e. the log of the final softmax over the kept set at the chosen element.  When every ratio of the exponential race is
+ *               0 or NaN, element 0 stands in for the draw and may lie outside the kept set: then lp_sampled is -inf
+ * Both buffers are fp32 [n_out][max_new_token][4] device memory laid out like ctts_gen_io.ids (n_out = the extent of the ids array: indexed by the
+ * utterance's output index, so ctts_gpt_compact and ctts_gpt_admit need nothing extra).  Either may be NULL (not wanted).  The values are stored next to
+ * the id, under the id's condition (the row had not finished before the step):
+ *   - the step that samples EOS IS written, at index end_idx (its ids are not part of the sequence, its log-probs are the probability of stopping there);
+ *   - a finished row writes nothing; entries of steps a row never sampled keep the caller's fill (the call clears nothing);
+ *   - an ensure_non_empty restart (ctts_gpt_restart, or re-admission with attempt + 1) overwrites from step 0.
+ * Valid after ctts_gpt_begin and before the first ctts_gpt_sample / ctts_gpt_decode of the call.  Every ctts_gpt_begin resets both to NULL: callers that
+ * never call this see no change -- the sampler then runs no extra reduction, and ids, hiddens, finish and end_idx are bit-identical with and without
+ * log-probs (the values feed nothing back into the sampling arithmetic).  The two pointers live in the per-call device block the sampler reads, so captured
+ * decode graphs are shared between calls with and without log-probs.  Under "batch_invariant" both values are part of the CONTRACT above: bit-identical
+ * whatever the schedule.  Errors: no generate state (no begin, or ended by ctts_gpt_score), infer_text (the refine-text pass returns none), called after the
+ * first sample. */
+int ctts_gpt_set_logprob_out(ctts_gpt* h, float* lp_raw_dev, float* lp_sampled_dev, void* stream);
+
 /* Non-blocking variant: enqueues a copy of {steps_done, draws, all_finished, -} into 4 int32 of PINNED host memory; the
  * caller records an event after it and reads the words once the event has completed -- lets the host keep one chunk of
  * decode steps in flight while it inspects the previous one. */
@@ -361,6 +382,11 @@ int ctts_sampler_run(const ctts_sampler_cfg* sc, const float* logits_dev, const 
  * max_input_ids and max_new_token still come from `sc`.  The per-row path of the generate-mode sampler, stand-alone (a test hook). */
 int ctts_sampler_run_rows(const ctts_sampler_cfg* sc, const ctts_row_sampling* per_seq, const float* logits_dev, const int32_t* history_dev,
                           int hist_len, const float* q_dev, int rows, int vocab, int step, int32_t* idx_dev, void* stream);
+
+/* ... plus the log-probs of idx (ctts_gpt_set_logprob_out's definitions): lp_raw_out / lp_sampled_out fp32 [rows] device, either may be NULL. */
+int ctts_sampler_run_rows_lp(const ctts_sampler_cfg* sc, const ctts_row_sampling* per_seq, const float* logits_dev, const int32_t* history_dev,
+                             int hist_len, const float* q_dev, int rows, int vocab, int step, int32_t* idx_dev, float* lp_raw_out, float* lp_sampled_out,
+                             void* stream);
 
 /* last measured average duration (ms) of one captured decode step, measured with hipEvents on the launch
  * stream around `n` graph replays; used by bench.py for the roofline object. */
