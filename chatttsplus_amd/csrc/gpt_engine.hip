@@ -156,7 +156,7 @@ struct ctts_gpt {
     int persist_share_keys = 384;                //   "persistent_share_keys": keys per key share at 1..5 rows; one share serves up to this + 128 keys (384 in registers, the rest -- up to 256 -- waits in LDS
                                                  //   since round 6 instead of streaming behind the query), more keys open a second share.  Re-swept with the LDS tail: 384 stays the best or ties
                                                  //   from 400 to 1000 keys (one share of 640: context 630 0.279 vs 0.263 ms/step with two shares; profiles/r06_ab_pair_lds_tail.jsonl)
-    int persist_lora = 1;                        //   "persistent_lora": rows with per-utterance adapters stay on the persistent launch (round 6; 0 = they take the launch chain, as until round 5)
+    int persist_lora = 1;                        //   "persistent_lora": rows with per-utterance adapters stay on the persistent launch (round 6; 0 = they take the launch chain, as until round 5).  q/k/v/o terms only: rows whose adapter names an MLP target take the chain (lora_mlp)
     int persist_heads = 1;                       //   the final RMSNorm + heads ("persistent_heads"; code mode, paced schedule): one launch fewer per step
     unsigned long long* pl_g = nullptr;          //   granule buffers g_qkv | g_att | g_x1 | g_act
     unsigned* pl_epoch = nullptr;                //   launch counter = granule tag
@@ -208,6 +208,15 @@ struct ctts_gpt {
     unsigned long long* lora_g = nullptr;        //   decode steps: the same terms as tagged granules from worker workgroups inside the QKV / o_proj launches (lora_worker.h)
     int lora_fold = 1;                           //   "lora_fold" option: 0 = the two extra launches per layer at decode too
     int lora_rows = 0;                           // 1: the current / next generate() calls carry per-sequence adapters
+    // ... on the MLP projections (gate_proj / up_proj / down_proj): tables of their own, allocated when the first such target is loaded (737 KB per layer and slot;
+    // engines that serve q/k/v/o adapters keep their footprint): A_gu [layer][slot][gate | up][16][768], B_gu [layer][slot][gate | up][16][3072],
+    // A_d [layer][slot][16][3072], B_d [layer][slot][16][768] (rank-major, zero padded to r = 16), scale [layer][slot][4] = gate, up, down, -
+    float *lora_mA_gu = nullptr, *lora_mB_gu = nullptr, *lora_mA_d = nullptr, *lora_mB_d = nullptr, *lora_mscale = nullptr, *ln2 = nullptr;
+    float* lora_dgu = nullptr;                   //   gate / up terms of the rows being processed [rows][gate | up][3072] (the down term shares lora_do: o_proj has consumed it by then)
+    std::vector<signed char> lora_mrank;         //   [layer][slot][gate, up, down] rank as loaded (0 = empty; sized last: non-empty = the tables above are all there)
+    std::vector<float> ln2_host;                 //   post_attention_layernorm weights [layer][768], kept from finalize (61 KB): engines without MLP adapters allocate what they always did
+    int lora_mlp = 0;                            // 1: a LIVE row's slot holds an MLP target (recomputed wherever lora_rows is): two more launches per layer, and decode steps take the
+                                                 //    launch chain at every row count (the persistent launch carries q/k/v/o terms only)
     int pass_rows = PASS_ROWS_MAX;               // prompt rows per pass of this engine (env CTTS_PASS_ROWS, read once at finalize, lowers it: the
                                                  // one capacity knob of the product library; the multi-pass tests use it)
     void* xh = nullptr;                          // fp16 decode, > split_rows rows: residual stream as packed fp16 B operand (EPI_RESID_XH -> PRO_XH)
@@ -414,6 +423,7 @@ extern "C" int ctts_gpt_get_option(ctts_gpt* h, const char* name, int* value) {
     else if (n == "graph_steps_persistent") *value = h->graph_steps_persist;
     else if (n == "decode_splits") *value = h->force_splits;
     else if (n == "lora_fold") *value = h->lora_fold;
+    else if (n == "lora_mlp_live") *value = h->lora_mlp;      // read only: 1 while a live row's adapter names gate / up / down (the two MLP launches per layer run, decode on the launch chain)
     else if (n == "down_splitk_rows") *value = h->down_sk_rows;
     else { ctts_set_error("get_option: unknown option '%s'", name); return 1; }
     return 0;
@@ -527,7 +537,7 @@ extern "C" void ctts_gpt_destroy(ctts_gpt* h) {
     void* bufs[] = {h->sk_scratch, h->dyn, h->wblob, h->wsplit, h->whead_sp, h->sp_x_hi, h->sp_x_lo, h->sp_act_hi, h->sp_act_lo, h->whead_text, h->lnf, h->emb_code, h->emb_text, h->rope, h->x_dec, h->x_last, h->x_pre, h->q_buf, h->part_ml, h->part_o, h->logits,
                     h->act, h->attn_packed, h->norm_packed, h->dpart, h->rope_pre, h->rope_dec, h->meta_pre, h->meta_dec, h->meta_dec0, h->st, h->last_rows,
                     h->hist_ring, h->sat, h->finend, h->xh, h->ssq, h->scale_o, h->scale_d, h->cx, h->crope, h->cmeta, h->cring, h->cfin, h->keep_dev,
-                    h->lora_A, h->lora_B, h->lora_Af, h->lora_scale, h->ln1, h->lora_slot_of_seq, h->lora_dqkv, h->lora_do, h->lora_g, h->pimg, h->pimg_head, h->pl_g, h->pl_epoch, h->pl_error, h->pl_ts, h->sk_slab, h->sk_cnt, h->rope_dec0, h->cknobs,
+                    h->lora_A, h->lora_B, h->lora_Af, h->lora_scale, h->ln1, h->lora_slot_of_seq, h->lora_dqkv, h->lora_do, h->lora_g, h->lora_mA_gu, h->lora_mB_gu, h->lora_mA_d, h->lora_mB_d, h->lora_mscale, h->ln2, h->lora_dgu, h->pimg, h->pimg_head, h->pl_g, h->pl_epoch, h->pl_error, h->pl_ts, h->sk_slab, h->sk_cnt, h->rope_dec0, h->cknobs,
                     h->score_x, h->score_logits, h->score_oidx};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (h->host_pin) (void)hipHostFree(h->host_pin);
@@ -573,13 +583,20 @@ extern "C" int ctts_gpt_set_weight(ctts_gpt* h, const char* name, const float* d
     return 0;
 }
 
+static int lora_target_index(const char* t);
+static inline int lora_target_out(const ctts_gpt* h, int t) { return (t == 4 || t == 5) ? h->I : h->H; }      // (out, in) of target t: gate / up I x H, down H x I, q/k/v/o H x H
+static inline int lora_target_in(const ctts_gpt* h, int t) { return t == 6 ? h->I : h->H; }
 extern "C" int ctts_gpt_merge_lora(ctts_gpt* h, int layer, const char* target, const float* A, const float* B, int r, float scale) {
     if (!h || h->finalized) { ctts_set_error("merge_lora must precede finalize"); return 1; }
+    if (!target || !A || !B || r < 1) { ctts_set_error("merge_lora: null argument or r %d < 1", r); return 1; }
+    const int t = lora_target_index(target);
+    if (t < 0) { ctts_set_error("merge_lora: unknown target '%s' (q_proj k_proj v_proj o_proj gate_proj up_proj down_proj)", target); return 1; }
     char key[128];
-    snprintf(key, sizeof(key), "gpt.layers.%d.self_attn.%s.weight", layer, target);
+    snprintf(key, sizeof(key), "gpt.layers.%d.%s.%s.weight", layer, t < 4 ? "self_attn" : "mlp", target);
     auto it = h->host.find(key);
     if (it == h->host.end()) { ctts_set_error("merge_lora: %s not loaded", key); return 1; }
-    const int out = h->H, in = h->H;
+    const int out = lora_target_out(h, t), in = lora_target_in(h, t);      // A [r][in], B [out][r] (llama.py:214,737-739: gate / up 3072 x 768, down 768 x 3072)
+    if (it->second.size() != (size_t)out * in) { ctts_set_error("merge_lora: %s holds %zu values, not %d x %d", key, it->second.size(), out, in); return 1; }
     std::vector<float>& W = it->second;
     // peft merge_and_unload: W' = W + scale * B @ A   (pipeline:420-432; scale = lora_alpha / r)
     for (int o = 0; o < out; ++o)
@@ -593,8 +610,8 @@ extern "C" int ctts_gpt_merge_lora(ctts_gpt* h, int layer, const char* target, c
 
 // ---- per-utterance LoRA (lora.hip) ---------------------------------------------------------------
 static int lora_target_index(const char* t) {
-    static const char* names[4] = {"q_proj", "k_proj", "v_proj", "o_proj"};
-    for (int i = 0; i < 4; ++i) if (t && !strcmp(t, names[i])) return i;
+    static const char* names[7] = {"q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj"};
+    for (int i = 0; i < 7; ++i) if (t && !strcmp(t, names[i])) return i;
     return -1;
 }
 static int lora_ensure_storage(ctts_gpt* h) {
@@ -612,6 +629,52 @@ static int lora_ensure_storage(ctts_gpt* h) {
     if (!h->pl_error) { if (dev_alloc((void**)&h->pl_error, 4)) return 1; CTTS_HIP_CHECK(hipMemset(h->pl_error, 0, 4)); }
     return 0;
 }
+static int lora_ensure_mlp_storage(ctts_gpt* h) {
+    if (!h->lora_mrank.empty()) return 0;           // (set last: a failed allocation leaves it empty, and the next call takes up where this one stopped)
+    const size_t slots = (size_t)h->L * CTTS_MAX_ADAPTERS, H = h->H, I = h->I;
+    struct { float** p; size_t n; } tabs[] = {{&h->lora_mA_gu, slots * 2 * 16 * H}, {&h->lora_mB_gu, slots * 2 * 16 * I}, {&h->lora_mA_d, slots * 16 * I},
+                                              {&h->lora_mB_d, slots * 16 * H}, {&h->lora_mscale, slots * 4}};
+    for (auto& t : tabs) {
+        if (*t.p == nullptr && dev_alloc((void**)t.p, t.n * 4)) return 1;
+        CTTS_HIP_CHECK(hipMemset(*t.p, 0, t.n * 4));
+    }
+    if (h->ln2_host.size() != (size_t)h->L * H) { ctts_set_error("set_adapter: the post-attention RMSNorm weights were not kept at finalize"); return 1; }
+    if (h->ln2 == nullptr && dev_alloc((void**)&h->ln2, h->ln2_host.size() * 4)) return 1;
+    CTTS_HIP_CHECK(hipMemcpy(h->ln2, h->ln2_host.data(), h->ln2_host.size() * 4, hipMemcpyHostToDevice));
+    h->lora_mrank.assign(slots * 3, 0);
+    return 0;
+}
+// The rows' gate / up terms [rows of a pass][gate | up][3072] fp32 -- 24 KB per prompt row, 402 MB on an engine sized for 16384-row passes: allocated when a LIVE row first
+// selects a slot that holds an MLP target (an MLP adapter that is resident but unused costs its tables only).  Called wherever lora_mlp can rise, outside graph capture.
+static int lora_ensure_mlp_terms(ctts_gpt* h) {
+    if (!h->lora_mlp || h->lora_dgu) return 0;
+    return dev_alloc((void**)&h->lora_dgu, (size_t)h->pass_rows * 2 * h->I * 4);
+}
+// does `slot` hold an MLP target in any layer?
+static bool lora_slot_has_mlp(const ctts_gpt* h, int slot) {
+    if (slot < 0 || h->lora_mrank.empty()) return false;
+    for (int l = 0; l < h->L; ++l)
+        for (int t = 0; t < 3; ++t) if (h->lora_mrank[((size_t)l * CTTS_MAX_ADAPTERS + slot) * 3 + t]) return true;
+    return false;
+}
+// gate_proj / up_proj / down_proj (t = 4 / 5 / 6) of one layer into the slot's MLP tables
+static int lora_set_mlp_target(ctts_gpt* h, int slot, int layer, int t, const float* A, const float* B, int r, float scale) {
+    if (h->H != 768 || h->I != 3072) { ctts_set_error("set_adapter: MLP targets need hidden 768 / intermediate 3072 (engine: %d / %d)", h->H, h->I); return 1; }
+    if (lora_ensure_storage(h) || lora_ensure_mlp_storage(h)) return 1;
+    const int out = lora_target_out(h, t), in = lora_target_in(h, t), m = t - 4;
+    std::vector<float> a16((size_t)16 * in, 0.f), b16((size_t)16 * out, 0.f);
+    memcpy(a16.data(), A, (size_t)r * in * 4);
+    for (int n = 0; n < out; ++n) for (int k = 0; k < r; ++k) b16[(size_t)k * out + n] = B[(size_t)n * r + k];       // rank-major like A
+    const size_t ls = (size_t)layer * CTTS_MAX_ADAPTERS + slot;
+    float* dA = m < 2 ? h->lora_mA_gu + (ls * 2 + m) * 16 * in : h->lora_mA_d + ls * 16 * in;
+    float* dB = m < 2 ? h->lora_mB_gu + (ls * 2 + m) * 16 * out : h->lora_mB_d + ls * 16 * out;
+    CTTS_HIP_CHECK(hipMemcpy(dA, a16.data(), a16.size() * 4, hipMemcpyHostToDevice));
+    CTTS_HIP_CHECK(hipMemcpy(dB, b16.data(), b16.size() * 4, hipMemcpyHostToDevice));
+    CTTS_HIP_CHECK(hipMemcpy(h->lora_mscale + ls * 4 + m, &scale, 4, hipMemcpyHostToDevice));
+    h->lora_mrank[ls * 3 + m] = (signed char)r;
+    h->opt_gen++;                                   // which launches a step takes depends on the slots' targets: captured graphs are stale
+    return 0;
+}
 extern "C" int ctts_gpt_set_adapter(ctts_gpt* h, int slot, int layer, const char* target, const float* A, const float* B, int r, float scale) {
     if (!h || !h->finalized || !A || !B) { ctts_set_error("set_adapter: handle not finalized or null argument"); return 1; }
     const int t = lora_target_index(target);
@@ -619,6 +682,7 @@ extern "C" int ctts_gpt_set_adapter(ctts_gpt* h, int slot, int layer, const char
         ctts_set_error("set_adapter: slot %d / layer %d / target %s / r %d out of range", slot, layer, target ? target : "(null)", r);
         return 1;
     }
+    if (t >= 4) return lora_set_mlp_target(h, slot, layer, t, A, B, r, scale);
     if (lora_ensure_storage(h)) return 1;
     const int H = h->H;
     std::vector<float> a16((size_t)16 * H, 0.f), b16((size_t)H * 16, 0.f);
@@ -651,6 +715,15 @@ extern "C" int ctts_gpt_clear_adapter(ctts_gpt* h, int slot) {
         CTTS_HIP_CHECK(hipMemset(h->lora_B + off, 0, per * 4));
         CTTS_HIP_CHECK(hipMemset(h->lora_scale + ((size_t)l * CTTS_MAX_ADAPTERS + slot) * 4, 0, 16));
         if (!h->lora_rank.empty()) for (int t = 0; t < 4; ++t) h->lora_rank[((size_t)l * CTTS_MAX_ADAPTERS + slot) * 4 + t] = 0;
+        if (h->lora_mA_gu) {
+            const size_t ls = (size_t)l * CTTS_MAX_ADAPTERS + slot, H = h->H, I = h->I;
+            CTTS_HIP_CHECK(hipMemset(h->lora_mA_gu + ls * 2 * 16 * H, 0, 2 * 16 * H * 4));
+            CTTS_HIP_CHECK(hipMemset(h->lora_mB_gu + ls * 2 * 16 * I, 0, 2 * 16 * I * 4));
+            CTTS_HIP_CHECK(hipMemset(h->lora_mA_d + ls * 16 * I, 0, 16 * I * 4));
+            CTTS_HIP_CHECK(hipMemset(h->lora_mB_d + ls * 16 * H, 0, 16 * H * 4));
+            CTTS_HIP_CHECK(hipMemset(h->lora_mscale + ls * 4, 0, 16));
+            for (int t = 0; t < 3; ++t) h->lora_mrank[ls * 3 + t] = 0;
+        }
     }
     h->opt_gen++;
     return 0;
@@ -658,7 +731,7 @@ extern "C" int ctts_gpt_clear_adapter(ctts_gpt* h, int slot) {
 extern "C" int ctts_gpt_set_row_adapters(ctts_gpt* h, const int32_t* slots, int B) {
     if (!h || !h->finalized) { ctts_set_error("set_row_adapters: handle not finalized"); return 1; }
     auto clear_rows = [h]() -> int {              // no row carries an adapter: also forget what an earlier request's rows carried (ctts_gpt_admit_adapters builds on these)
-        h->lora_rows = 0;
+        h->lora_rows = 0; h->lora_mlp = 0;
         h->lora_req_host.clear();
         if (!h->lora_slot_host.empty()) h->lora_slot_host.assign(CTTS_MAX_B, -1);
         for (int b = 0; b < CTTS_MAX_B; ++b) h->lora_row_slots[b] = -1;
@@ -681,7 +754,9 @@ extern "C" int ctts_gpt_set_row_adapters(ctts_gpt* h, const int32_t* slots, int 
     h->lora_req_host = tab;
     for (int b = 0; b < CTTS_MAX_B; ++b) h->lora_row_slots[b] = (signed char)tab[b];      // rows == sequences until a compaction
     h->lora_rows = 1;
-    return 0;
+    h->lora_mlp = 0;
+    for (int b = 0; b < B; ++b) if (lora_slot_has_mlp(h, tab[b])) h->lora_mlp = 1;
+    return lora_ensure_mlp_terms(h);
 }
 
 // ---- per-utterance sampling knobs (RowSampling, common.h) ----------------------------------------
@@ -832,6 +907,7 @@ static int finalize_t(ctts_gpt* h) {
         t.l2 = need(h, p + "post_attention_layernorm.weight", H);
         if (!t.q || !t.k || !t.v || !t.o || !t.g || !t.u || !t.d || !t.l1 || !t.l2) return 1;
         CTTS_HIP_CHECK(hipMemcpy(h->ln1 + (size_t)l * H, t.l1->data(), (size_t)H * 4, hipMemcpyHostToDevice));
+        h->ln2_host.insert(h->ln2_host.end(), t.l2->begin(), t.l2->end());      // post_attention_layernorm weights, unfolded: uploaded with the first MLP target (lora_ensure_mlp_storage)
     }
     // host-side packing of the 20 layers on a few threads (pure CPU work on disjoint slices of the blobs)
     std::atomic<bool> split_in_range(true);
@@ -1071,6 +1147,7 @@ struct StreamForm { bool parts; bool xh; bool logits; bool split; };     // x = 
 static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* rope_rows, int R, int S, const DevState* st, hipStream_t s, StreamForm* form = nullptr) {
     const int dt = h->cfg.dtype;
     const bool lora = h->lora_rows != 0;                   // per-utterance adapters: the residual stream must be materialised in x (no split-K partials)
+    const bool lmlp = lora && h->lora_mlp != 0;      // ... on gate / up / down too: their terms come from two more lora.hip launches per layer, decode and prompt pass alike
     const bool inv = h->batch_inv != 0;                    // "batch_invariant": every choice below that depends on R is pinned (ctts_gpt_begin refuses adapters then)
     // fp32 engines, decode batches of >= split_decode_rows rows: head / tail fp16 operands (the predicate is completed below; it needs the packed-residual path)
     const bool spd_ok = st != nullptr && dt == CTTS_DTYPE_F32 && h->xh_mode && h->split_ok && h->wsplit != nullptr && !lora && S == 1 &&
@@ -1091,6 +1168,7 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
     // prompt pass over >= 384 rows, fp32 engine: the same tiling on the fp16 pipes with head / tail operands -- 3 MFMAs per product instead of 16,
     // fp32-level accuracy (prefill_split.hip); the attention stays the fp32 row kernel
     // (round 5: also with per-utterance adapters -- their low-rank terms come from the two lora.hip launches per layer and are added in the split GEMMs' epilogues)
+    // (... and with adapters on gate / up / down: two more launches; the gate / up term rides in a SwiGLU epilogue of its own, the down term is read from the act images)
     // (invariant: every pass height, 1 row included -- the block shapes give bit-identical rows, tools/prefill_fuzz.py -- and the down projection's K never sliced)
     const bool pfs = (dt == CTTS_DTYPE_F32) && h->wsplit != nullptr &&
                      (inv ? (st == nullptr && h->split_ok) : (prepack && h->split_rows_min > 0 && (R >= h->split_rows_min)));
@@ -1148,6 +1226,7 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
         nb = nb < 8 ? 8 : (nb > 256 ? 256 : nb);
         g.pf.ptr = w; g.pf.unit_bytes = (unsigned)tile; g.pf.n_units = (unsigned)n_tiles; g.pf_blocks = (int)nb;
     };
+    if (lmlp && (h->lora_dgu == nullptr || h->lora_mrank.empty())) { ctts_set_error("per-utterance LoRA: the MLP targets' buffers are missing"); return 1; }
     for (int l = 0; l < h->L; ++l) {
         GemmArgs a = {};
         a.st = st; a.R = R; a.eps = 1e-6f; a.meta = meta; a.Lmax = h->cfg.max_seq; a.sat = h->sat;
@@ -1220,6 +1299,12 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
         // RMSNorm + gate|up + SiLU*up
         GemmArgs g3 = a;
         g3.W = h->lw[l].gu; g3.n_row_tiles = 2 * h->I / 16; g3.K = h->H; g3.x = x; g3.act_out = h->act;
+        const size_t mlp_l = (size_t)l * CTTS_MAX_ADAPTERS;
+        if (lmlp) {       // gate / up terms of every row from the residual stream o_proj just completed; the SwiGLU epilogues add them before the activation
+            if (launch_lora_delta_gu(x, h->ln2 + (size_t)l * h->H, a.eps, meta, h->lora_slot_of_seq, h->lora_mA_gu + mlp_l * 2 * 16 * h->H, h->lora_mB_gu + mlp_l * 2 * 16 * h->I,
+                                     h->lora_mscale + mlp_l * 4, h->lora_dgu, R, h->H, h->I, s)) return 1;
+            g3.lora_delta = h->lora_dgu; g3.lora_gu = 1;
+        }
         if (pfs) {
             if (launch_norm_pack_split(x, h->sp_x_hi, h->sp_x_lo, R, a.eps, s)) return 1;
             if (launch_prefill_split_gemm(EPI_SWIGLU, g3, h->lw[l].gu_sp, h->sp_x_hi, h->sp_x_lo, h->sp_act_hi, h->sp_act_lo, sp_scale, sp_pol, s)) return 1;
@@ -1235,6 +1320,13 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
         // down + residual
         GemmArgs g4 = a;
         g4.W = h->lw[l].d; g4.n_row_tiles = h->H / 16; g4.K = h->I; g4.xpacked = h->act; g4.x_out = x;
+        if (lmlp) {       // down term from the operand the down projection itself reads (the packed SwiGLU output, or the split pass's head / tail images); added with the residual
+            if (pfs ? launch_lora_delta_down_split(h->sp_act_hi, h->sp_act_lo, meta, h->lora_slot_of_seq, h->lora_mA_d + mlp_l * 16 * h->I, h->lora_mB_d + mlp_l * 16 * h->H,
+                                                   h->lora_mscale + mlp_l * 4, h->lora_do, R, h->H, h->I, s)
+                    : launch_lora_delta_down(dt, h->act, nbg, meta, h->lora_slot_of_seq, h->lora_mA_d + mlp_l * 16 * h->I, h->lora_mB_d + mlp_l * 16 * h->H,
+                                             h->lora_mscale + mlp_l * 4, h->lora_do, R, h->H, h->I, s)) return 1;
+            g4.lora_delta = h->lora_do;
+        }
         if (pfs) {      // the SwiGLU images hold silu(g) * u / 16
             if (launch_prefill_split_gemm(EPI_RESID, g4, h->lw[l].d_sp, h->sp_act_hi, h->sp_act_lo, nullptr, nullptr, sp_scale * 16.0f, sp_pol, s)) return 1;
         } else if (pfg) {
@@ -1317,8 +1409,11 @@ static int seat_row_adapters(ctts_gpt* h, int B, const char* who, hipStream_t s)
     bool any = false;
     for (int b = 0; b < CTTS_MAX_B; ++b) { h->lora_row_slots[b] = (signed char)h->lora_slot_host[b]; any = any || (b < B && h->lora_slot_host[b] >= 0); }
     h->lora_rows = any ? 1 : 0;
+    h->lora_mlp = 0;
+    for (int b = 0; b < B; ++b) if (lora_slot_has_mlp(h, h->lora_slot_host[b])) h->lora_mlp = 1;
+    if (lora_ensure_mlp_terms(h)) { h->lora_rows = 0; h->lora_mlp = 0; h->B = 0; return 1; }
     if (h->lora_rows && h->batch_inv) {
-        h->lora_rows = 0; h->B = 0;
+        h->lora_rows = 0; h->lora_mlp = 0; h->B = 0;
         ctts_set_error("%s: per-utterance adapters (ctts_gpt_set_row_adapters) are outside the batch_invariant contract; set the option to 0 or merge the adapter", who);
         return 1;
     }
@@ -1579,6 +1674,7 @@ static int advance_rows(ctts_gpt* h, int n_steps) {
 // Asked once per step (plan_decode): L is that step's longest context, so a step's share count does not depend on how its decode call was chunked.
 static inline int decode_persist(const ctts_gpt* h, int B, int L) {
     if (!(h->persist_rows > 0 && h->pimg != nullptr && B <= h->persist_rows && B <= PL_MAXR)) return 0;
+    if (h->lora_rows && h->lora_mlp) return 0;             // ... on the MLP projections: the launch carries q/k/v/o terms only (ctts_hip.h "persistent_lora")
     if (h->lora_rows && !(h->persist_lora && h->persist_sched == 3 && h->lora_Af != nullptr && h->H == PL_H)) return 0;      // per-utterance adapters ride inside the launch (round 6, paced schedule)
     int cap = PL_ATT_BLOCKS / (PL_NH * B);
     cap = cap > PL_SMAX ? PL_SMAX : (cap < 1 ? 1 : cap);
@@ -1663,7 +1759,7 @@ static int graph_span(const ctts_gpt* h, int left) {
 
 static int ensure_graph(ctts_gpt* h, int n_steps) {
     char sig[160];
-    snprintf(sig, sizeof(sig), "%d|%d|%p|%d|%d|%d|%d|%d", h->B, h->text_mode, (void*)h->kv, h->cur_splits, h->lora_rows, h->opt_gen, h->cur_persist, n_steps);      // (diagnostic switches are fixed at create)
+    snprintf(sig, sizeof(sig), "%d|%d|%p|%d|%d|%d|%d|%d", h->B, h->text_mode, (void*)h->kv, h->cur_splits, h->lora_rows + 2 * h->lora_mlp, h->opt_gen, h->cur_persist, n_steps);      // (diagnostic switches are fixed at create)
     std::string key(sig);
     if (h->lora_rows) key.append((const char*)h->lora_row_slots, (size_t)h->B);      // the rows' adapter slots are kernel arguments of the folded launches (LoraFold)
     if (h->graph_gen != h->opt_gen || h->graphs.size() >= 96) {
@@ -1784,8 +1880,10 @@ extern "C" int ctts_gpt_rows_enqueue(ctts_gpt* h, int32_t* host_pinned_2B, void*
 // per-utterance adapters: the engine keeps the LoRA launches only while a live row carries an adapter
 static void lora_refresh(ctts_gpt* h) {
     bool any = false;
-    for (int r = 0; r < h->B; ++r) any = any || h->lora_row_slots[r] >= 0;
+    bool mlp = false;
+    for (int r = 0; r < h->B; ++r) { any = any || h->lora_row_slots[r] >= 0; mlp = mlp || lora_slot_has_mlp(h, h->lora_row_slots[r]); }
     h->lora_rows = any ? 1 : 0;
+    h->lora_mlp = mlp ? 1 : 0;
 }
 extern "C" int ctts_gpt_compact(ctts_gpt* h, const int32_t* keep_rows, int n_keep, void* stream) {
     if (!h || !keep_rows || h->B == 0) { ctts_set_error("compact: call begin first"); return 1; }
@@ -1830,7 +1928,7 @@ extern "C" int ctts_gpt_admit_adapters(ctts_gpt* h, int n, const int32_t* rows, 
     if (h->lora_slot_of_seq)        // (pageable source: staged before the call returns)
         CTTS_HIP_CHECK(hipMemcpyAsync(h->lora_slot_of_seq, h->lora_slot_host.data(), CTTS_MAX_B * 4, hipMemcpyHostToDevice, (hipStream_t)stream));
     lora_refresh(h);
-    return 0;
+    return lora_ensure_mlp_terms(h);
 }
 
 // Continuous batching (no counterpart in the reference, whose slices run to their slowest row, pipeline:391-397 / gpt.py:527-546): `n` new

@@ -82,6 +82,7 @@ struct GemmArgs {
     float* scale_out;       // [rows] PRO_XH / PRO_NORM (block 0): 2^floor(log2(rs)) of this normalisation = the scale of the NEXT xh rows
     // per-utterance LoRA (lora.hip): low-rank term of every row, added in the epilogue.  EPI_QKV: [rows][3][768]; EPI_RESID*: [rows][768]
     const float* lora_delta;
+    int lora_gu;            // EPI_SWIGLU: lora_delta holds the gate / up terms [rows][2][N / 2], added before the activation (selects the LORA instantiation, skinny_gemm.hip)
     LoraFold lf;            // decode steps: the same term from worker workgroups inside the launch, as tagged granules (lora_worker.h); lora_w workers per chunk
     int lora_w;             //   EPI_QKV: 3 * 16 * NBG, EPI_RESID*: 16 * NBG, 0 = off (lora_delta then holds the term, or null)
     int* sat;               // fp16 engines: counter of saturated / NaN fp16 stores (common.h sat_half); null = do not count
@@ -182,6 +183,13 @@ int launch_lora_delta_o(int dtype, const void* attn_packed, int nbg, const RowMe
                         const float* scale_l, float* delta, int rows, int H, hipStream_t s);
 int launch_lora_delta_o_split(const void* hi, const void* lo, const RowMeta* meta, const int* slot_of_seq, const float* A_l, const float* B_l,
                               const float* scale_l, float* delta, int rows, int H, hipStream_t s);
+// MLP targets: gate / up term [rows][2][3072] (added before the activation by the SwiGLU epilogues), down term [rows][768] from the down projection's own operand
+int launch_lora_delta_gu(const float* x, const float* lnw, float eps, const RowMeta* meta, const int* slot_of_seq, const float* A_l, const float* B_l,
+                         const float* scale_l, float* delta, int rows, int H, int I, hipStream_t s);
+int launch_lora_delta_down(int dtype, const void* act_packed, int nbg, const RowMeta* meta, const int* slot_of_seq, const float* A_l, const float* B_l,
+                           const float* scale_l, float* delta, int rows, int H, int I, hipStream_t s);
+int launch_lora_delta_down_split(const void* hi, const void* lo, const RowMeta* meta, const int* slot_of_seq, const float* A_l, const float* B_l,
+                                 const float* scale_l, float* delta, int rows, int H, int I, hipStream_t s);
 int launch_prefill_gemm(int epi, const GemmArgs& a, hipStream_t s);      // prefill_gemm.hip: fp16 prompt-pass GEMM (QKV / RESID / SWIGLU epilogues)
 int launch_norm_pack_split(const float* x, void* hi, void* lo, int R, float eps, hipStream_t s);                    // prefill_split.hip (fp32 engine, >= 1536 prompt rows)
 int launch_split_pack(const float* src, void* hi, void* lo, int R, hipStream_t s);

@@ -90,6 +90,9 @@ struct SplitGemm {
 // Epilogue of a wave tile of NT n tiles x NG 16-row groups (both split GEMM kernels).  C tile layout: lane = (iq = lane >> 4, n = lane & 15): activation row n of
 // the group, weight rows 4 * iq + j (j = register).  rt0 = the wave's first n tile (q / k / v: 4 consecutive tiles = one head, tile t of it = dims 8t.. | 8t + 32..;
 // gate|up: a tile = 8 outputs), G0 = its first row group.
+// EPI_SWIGLU whose rows carry per-utterance LoRA terms of gate_proj / up_proj (a.lora_delta [rows][gate | up][N / 2], lora.hip): an epilogue of its own, so that the
+// adapter-free SwiGLU kernels keep their registers (a value outside kernels.h's EPI_* range: only this file's kernels know it)
+#define SP_EPI_SWIGLU_LORA 8
 template <int EPI, int NG, int NT>
 __device__ __forceinline__ void sp_epilogue(f32x4 (&acc)[NT][NG], const SplitGemm& p, const GemmArgs& a, const int lane, const int rt0, const int G0) {
     int nsat = 0;                                          // EPI_SWIGLU: this lane's clamped outputs (one atomic per wave at the end)
@@ -121,7 +124,7 @@ __device__ __forceinline__ void sp_epilogue(f32x4 (&acc)[NT][NG], const SplitGem
                 const f32x4 c = acc[t][g];
                 *(f32x4*)(a.part_out + (size_t)blockIdx.z * p.part_stride + (size_t)row * N + (rt0 + t) * 16 + 4 * iq) = (f32x4){c[0] * sc, c[1] * sc, c[2] * sc, c[3] * sc};
             }
-        } else if (EPI == EPI_SWIGLU) {
+        } else if (EPI == EPI_SWIGLU || EPI == SP_EPI_SWIGLU_LORA) {
             // tile rows [8 gate | 8 up]: lanes iq 0,1 hold gate rows 4 iq + j, lanes iq 2,3 the matching up rows.  Every lane finishes TWO outputs (round 6; the gate
             // lanes used to finish all four while the up lanes idled through the expf + division: half the epilogue's VALU time): a gate lane keeps j = 0, 1 and
             // receives the up values, its partner (lane ^ 32) keeps j = 2, 3 and receives the gate values -- two exchanges instead of four, the same arithmetic per output.
@@ -137,6 +140,11 @@ __device__ __forceinline__ void sp_epilogue(f32x4 (&acc)[NT][NG], const SplitGem
                     uv[jj] = (lowh ? got : c[2 + jj]) * sc;
                 }
                 if (rv) {
+                    if constexpr (EPI == SP_EPI_SWIGLU_LORA) {       // the terms are part of the projections, so before the activation (llama.py:214)
+                        const float* dl = a.lora_delta + (size_t)row * (a.n_row_tiles * 16) + (rt0 + t) * 8 + 4 * (iq & 1) + (lowh ? 0 : 2);      // this lane's two outputs
+                        const float2 dg = *(const float2*)dl, du = *(const float2*)(dl + a.n_row_tiles * 8);
+                        gv[0] += dg.x; gv[1] += dg.y; uv[0] += du.x; uv[1] += du.y;
+                    }
                     half2v h, l;
 #pragma unroll
                     for (int jj = 0; jj < 2; ++jj) {
@@ -188,7 +196,7 @@ __device__ __forceinline__ void sp_epilogue(f32x4 (&acc)[NT][NG], const SplitGem
             }
         }
     }
-    if (EPI == EPI_SWIGLU && a.sat != nullptr && nsat != 0) atomicAdd(a.sat, nsat);
+    if ((EPI == EPI_SWIGLU || EPI == SP_EPI_SWIGLU_LORA) && a.sat != nullptr && nsat != 0) atomicAdd(a.sat, nsat);
 }
 
 // RING = LDS stages of 32 KB.  2: two blocks per CU, the second block's MFMAs fill the first one's barrier / landing bubbles (long passes).  4: one block per CU with three
@@ -662,7 +670,8 @@ static int sp_launch(SplitGemm& p, const GemmArgs& a, const SplitGemmPolicy& pol
     }
     // Short passes of the down projection (K = 3072: 96 k-tiles in a row, 6 blocks per 128 rows -- 24 blocks on 256 CUs at 448 rows, 75 of the layer's 170 us): K sliced
     // four ways over grid.z, the slices' shares parked in `pol.sk_scratch`, resid_combine_kernel adds them in slice order and the residual.  Another summation order
-    // than the unsliced kernel's (the usual 1e-7); a.lora_delta never rides here (the o_proj products have K = 768).
+    // than the unsliced kernel's (the usual 1e-7); a.lora_delta stands aside from it (the o_proj products have K = 768; a down_proj term
+    // takes the unsliced kernel, whose epilogue adds it).
     const size_t rows_pad = (size_t)((p.R + 127) / 128) * 128;
     const bool sliced = EPI == EPI_RESID && shape == 0 && pol.sk_rows > 0 && p.R <= pol.sk_rows && p.ktiles >= 64 && (p.ktiles & 3) == 0 && a.lora_delta == nullptr &&
                         pol.sk_scratch != nullptr && 4 * rows_pad * (size_t)(nt * 16) <= pol.sk_cap_floats;
@@ -700,7 +709,7 @@ int launch_prefill_split_gemm(int epi, const GemmArgs& a, const void* Wsplit, co
     p.ktiles = a.K / 32; p.kt_per = p.ktiles; p.part_stride = 0; p.R = a.R; p.scale = scale; p.act_hi = (half_t*)act_hi; p.act_lo = (half_t*)act_lo;
     if ((a.n_row_tiles % 8) != 0 || p.ktiles < 2) { ctts_set_error("prefill_split_gemm: %d n tiles / K = %d not supported", a.n_row_tiles, a.K); return 1; }
     if (epi == EPI_QKV) return sp_launch<EPI_QKV>(p, a, pol, s);
-    if (epi == EPI_SWIGLU) return sp_launch<EPI_SWIGLU>(p, a, pol, s);
+    if (epi == EPI_SWIGLU) return a.lora_delta != nullptr ? sp_launch<SP_EPI_SWIGLU_LORA>(p, a, pol, s) : sp_launch<EPI_SWIGLU>(p, a, pol, s);
     if (epi == EPI_RESID) return sp_launch<EPI_RESID>(p, a, pol, s);
     ctts_set_error("prefill_split_gemm: unsupported epilogue %d", epi);
     return 1;

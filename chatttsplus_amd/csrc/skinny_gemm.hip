@@ -180,7 +180,10 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const int* done
     // (LORA is a template argument: compiled into every capable launch, the worker branch and the look-ahead cost the adapter-less step 0.5 % in fp32 and 2 % in fp16)
     constexpr bool LORA_QKV = LORA && (EPI == EPI_QKV) && (K == 768) && (VR == 0) && (PRO == PRO_NORM || PRO == PRO_XH);
     constexpr bool LORA_O = LORA && (EPI == EPI_RESID || EPI == EPI_RESID_XH) && (K == 768) && (VR == 0) && (PRO == PRO_PACKED);
-    static_assert(!LORA || LORA_QKV || LORA_O, "LoRA workers: the q/k/v and o_proj launches of a decode step");
+    // ... and on the gate|up launch LORA selects the epilogue that adds the rows' gate / up terms (lora.hip lora_delta_gu_kernel) before the activation: no workers, the
+    // terms come from a launch of their own (decode steps and prompt passes alike).  A template flag for the same reason: the adapter-free SwiGLU kernels keep their registers.
+    constexpr bool LORA_GU = LORA && (EPI == EPI_SWIGLU) && (VR == 0);
+    static_assert(!LORA || LORA_QKV || LORA_O || LORA_GU, "LoRA: the q/k/v and o_proj launches of a decode step (workers), the gate|up launch (epilogue term)");
     const int lw = (LORA_QKV || LORA_O) ? ((misc >> 15) & 0x7F) : 0;
     int lora_draw = 0;
     // (the layer index is read where the tag is formed: an unconditional read of the argument struct at entry cost the adapter-less launches 0.2 us)
@@ -246,6 +249,18 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const int* done
                 }
             }
             resid_pf[u] = v;
+        }
+    }
+    float gu_pf[LORA_GU ? RT : 1][2];                      // this thread's gate / up terms [rows][gate | up][N / 2] of every row tile (zero for rows without an adapter)
+    if constexpr (LORA_GU) {
+        const int r = row0 + (tid >> 3), half_n = a.n_row_tiles * 8;
+#pragma unroll
+        for (int t = 0; t < RT; ++t) {
+            gu_pf[t][0] = 0.f; gu_pf[t][1] = 0.f;
+            if (tid < 8 * NB && r < R) {
+                const float* dl = a.lora_delta + (size_t)r * 2 * half_n + (rt0 + t) * 8 + (tid & 7);
+                gu_pf[t][0] = dl[0]; gu_pf[t][1] = dl[half_n];
+            }
         }
     }
     RowMeta meta_pf = {0, 0, 0, 0};
@@ -658,6 +673,10 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const int* done
         if (EPI == EPI_SWIGLU) {
             // packed rows: [8 gate | 8 up] per tile -> act[rt*8+p] = silu(g) * u
             float y = 0.f;
+            if constexpr (LORA_GU) {          // per-utterance LoRA on gate_proj / up_proj: part of the projections, so before the activation (llama.py:214)
+                const float gl = va + gu_pf[ti][0], ul = vb + gu_pf[ti][1];
+                if (r < R) y = (gl / (1.0f + expf(-gl))) * ul;
+            } else
             if (r < R) y = (va / (1.0f + expf(-va))) * vb;
             const int ktiles_out = (a.n_row_tiles * 8) / KT;
             if (SPLIT) y *= 1.0f / CTTS_SPLIT_ACT_SCALE;
@@ -816,6 +835,10 @@ static int dispatch(int pro, int epi, const GemmArgs& a, int chunks, hipStream_t
         rc |= launch_one<WT, NBG, W768, P768, PRO_XH, EPI_QKV, RT_XH, 0, true>(a, chunks, s, true);
         rc |= launch_one<WT, NBG, W768, P768, PRO_PACKED, EPI_RESID, 1, 0, true>(a, chunks, s, true);
         rc |= launch_one<WT, NBG, W768, P768, PRO_PACKED, EPI_RESID_XH, 1, 0, true>(a, chunks, s, true);
+        // the gate|up launches whose epilogue adds the rows' gate / up terms (per-utterance adapters on the MLP projections)
+        rc |= launch_one<WT, NBG, W768, P768, PRO_NORM, EPI_SWIGLU, RT_NORM_C, 0, true>(a, chunks, s, true);
+        rc |= launch_one<WT, NBG, W768, P768, PRO_XH, EPI_SWIGLU, RT_XH, 0, true>(a, chunks, s, true);
+        if constexpr (NBG == 2) rc |= launch_one<WT, 2, W768, P768, PRO_PACKED, EPI_SWIGLU, 4, 0, true>(a, chunks, s, true);
         if constexpr (!F16 && NBG == 1) {
 #define CTTS_VALU_CFG(VRN) rc |= launch_one<float, 1, W768, P768, PRO_NORM_P, EPI_QKV, 1, VRN>(a, chunks, s, true); rc |= launch_one<float, 1, W768, P768, PRO_NORM, EPI_QKV, 1, VRN>(a, chunks, s, true); \
             rc |= launch_one<float, 1, W768, P768, PRO_ATTN, EPI_RESID_P, 1, VRN>(a, chunks, s, true); rc |= launch_one<float, 1, W768, P768, PRO_NORM, EPI_SWIGLU, 1, VRN>(a, chunks, s, true); \
@@ -857,6 +880,14 @@ static int dispatch(int pro, int epi, const GemmArgs& a, int chunks, hipStream_t
         if (pro == PRO_PACKED && epi == EPI_RESID && a.K == 768) return launch_one<WT, NBG, W768, P768, PRO_PACKED, EPI_RESID, 1, 0, true>(a, chunks, s, false);
         if (pro == PRO_PACKED && epi == EPI_RESID_XH && a.K == 768) return launch_one<WT, NBG, W768, P768, PRO_PACKED, EPI_RESID_XH, 1, 0, true>(a, chunks, s, false);
         ctts_set_error("skinny_gemm: prologue/epilogue %d/%d cannot carry LoRA workers", pro, epi);
+        return 1;
+    }
+    if (a.lora_gu != 0) {         // per-utterance adapters on gate_proj / up_proj: a.lora_delta = [rows][gate | up][N / 2]
+        if (epi != EPI_SWIGLU || a.lora_delta == nullptr) { ctts_set_error("skinny_gemm: gate / up LoRA terms ride on the SwiGLU epilogue only (epi %d)", epi); return 1; }
+        if (pro == PRO_NORM) return launch_one<WT, NBG, W768, P768, PRO_NORM, EPI_SWIGLU, RT_NORM, 0, true>(a, chunks, s, false);
+        if (pro == PRO_XH) return launch_one<WT, NBG, W768, P768, PRO_XH, EPI_SWIGLU, RT_XH, 0, true>(a, chunks, s, false);
+        if constexpr (NBG == 2) { if (pro == PRO_PACKED) return launch_one<WT, 2, W768, P768, PRO_PACKED, EPI_SWIGLU, 4, 0, true>(a, chunks, s, false); }
+        ctts_set_error("skinny_gemm: prologue %d cannot carry the gate / up LoRA terms", pro);
         return 1;
     }
     if (pro == PRO_NORM && epi == EPI_QKV) return launch_one<WT, NBG, W768, P768, PRO_NORM, EPI_QKV, RT_NORM>(a, chunks, s, false);
@@ -907,7 +938,7 @@ static int dispatch_split(int pro, int epi, const GemmArgs& a, int chunks, hipSt
         rc |= launch_one<split_t, NBG, W768, P768, PRO_PACKED, EPI_RESID_XH_SK>(a, chunks, s, true);
         return rc;
     }
-    if (a.lora_w != 0 || a.lora_delta != nullptr) { ctts_set_error("skinny_gemm: the split decode kernels carry no per-utterance adapters"); return 1; }
+    if (a.lora_w != 0 || a.lora_delta != nullptr || a.lora_gu != 0) { ctts_set_error("skinny_gemm: the split decode kernels carry no per-utterance adapters"); return 1; }
     if (pro == PRO_XH && epi == EPI_QKV) return launch_one<split_t, NBG, W768, P768, PRO_XH, EPI_QKV>(a, chunks, s, false);
     if (pro == PRO_XH && epi == EPI_SWIGLU) return launch_one<split_t, NBG, W768, P768, PRO_XH, EPI_SWIGLU>(a, chunks, s, false);
     if (pro == PRO_XH && epi == EPI_LOGITS) return launch_one<split_t, NBG, W768, P768, PRO_XH, EPI_LOGITS>(a, chunks, s, false);

@@ -70,6 +70,22 @@ def score_reduce(logprob: List[torch.Tensor], argmax: List[torch.Tensor], target
     return nll, acc, loss, accuracy
 
 
+LORA_TARGETS = {"q_proj": "self_attn", "k_proj": "self_attn", "v_proj": "self_attn", "o_proj": "self_attn", "gate_proj": "mlp", "up_proj": "mlp", "down_proj": "mlp"}
+
+
+def check_lora_shapes(layer, target, A, B, hidden_size: int = 768, intermediate_size: int = 3072, where: str = "") -> None:
+    """A must be [r, in] and B [out, r] for the (out, in) of the nn.Linear `target` names (llama.py:214,737-739: gate / up intermediate x hidden, down hidden x
+    intermediate, q/k/v/o hidden x hidden): the engine reads both by these sizes.  ValueError naming layer, target and the shapes."""
+    if target not in LORA_TARGETS:
+        raise ValueError(f"LoRA{where}: layer {layer}: unknown target '{target}' (one of {' '.join(LORA_TARGETS)})")
+    out, inn = {"gate_proj": (intermediate_size, hidden_size), "up_proj": (intermediate_size, hidden_size),
+                "down_proj": (hidden_size, intermediate_size)}.get(target, (hidden_size, hidden_size))
+    a, b = tuple(np.shape(A)), tuple(np.shape(B))
+    r = a[0] if len(a) == 2 else -1
+    if len(a) != 2 or len(b) != 2 or r < 1 or a != (r, inn) or b != (out, r):
+        raise ValueError(f"LoRA{where}: layer {layer} {target}: A {a} / B {b}, expected (r, {inn}) / ({out}, r)")
+
+
 def score_inputs(input_ids: torch.Tensor, attention_mask: torch.Tensor, text_mask: torch.Tensor, codes, eos_token: int, append_eos: bool = True):
     """Host helper of GPT.score (CPU): utterance i's codes [n_i, 4] follow its left-padded prompt (input_ids [B, T, 4], attention_mask / text_mask [B, T], as
     Tokenizer.encode gives them); the joined sequences are left padded again.  Returns dict(ids [B, T', 4], mask [B, T'] int32, text_mask [B, T'] bool,
@@ -445,8 +461,23 @@ class GPT:
         self.load_state_dict(torch.load(file_path, weights_only=True, mmap=True))      # gpt.py:84-85
 
     def add_lora(self, layer: int, target: str, A, B, scale: float):
-        """peft merge rule W += scale * B @ A (pipeline:420-432) applied before finalize."""
+        """peft merge rule W += scale * B @ A (pipeline:420-432) applied before finalize.  `target`: q_proj k_proj v_proj o_proj (768 x 768), gate_proj up_proj
+        (3072 x 768) or down_proj (768 x 3072); A is [r, in], B [out, r] for the target's own (out, in), checked here (the engine reads both by these sizes)."""
+        self._check_lora(layer, target, A, B)
         self._lora.append((layer, target, np.ascontiguousarray(A, dtype=np.float32), np.ascontiguousarray(B, dtype=np.float32), float(scale)))
+
+    def _check_lora(self, layer, target, A, B, r_max=None) -> None:
+        """Layer, target and A / B shapes of one adapter matrix pair against this engine's widths; errors name layer and target."""
+        H, I, L = int(self.gpt_config["hidden_size"]), int(self.gpt_config["intermediate_size"]), int(self.gpt_config["num_hidden_layers"])
+        try:
+            check_lora_shapes(layer, target, A, B, H, I)
+        except ValueError as e:
+            raise _lib.HipBackendError(str(e)) from None
+        if not 0 <= int(layer) < L:
+            raise _lib.HipBackendError(f"LoRA: layer {layer} ({target}) out of range: the engine has {L} layers")
+        r = np.shape(A)[0]
+        if r_max is not None and r > r_max:
+            raise _lib.HipBackendError(f"LoRA: layer {layer} {target}: r = {r} > {r_max} (per-utterance adapters; a merged adapter, with_lora(), takes any rank)")
 
     @staticmethod
     def _known_key(k: str, layers: int, num_vq: int) -> bool:
@@ -499,8 +530,9 @@ class GPT:
         return self
 
     def with_lora(self, adapters) -> "GPT":
-        """A sibling engine whose q/k/v/o weights carry W += scale * B @ A (peft merge_and_unload, pipeline:420-432);
-        the base engine stays untouched, like the reference's gpt_org swap (pipeline:424,465-470)."""
+        """A sibling engine whose weights carry W += scale * B @ A on every projection the adapter names -- q/k/v/o and gate / up / down, like peft's
+        merge_and_unload (pipeline:420-432); the base engine stays untouched, like the reference's gpt_org swap (pipeline:424,465-470).  A merged adapter is
+        just weights: every engine mode (fp16, the persistent launch, batch_invariant) serves it."""
         g = GPT(**self._ctor)
         for (layer, target, A, B, scale) in adapters:
             g.add_lora(layer, target, A, B, scale)
@@ -509,9 +541,13 @@ class GPT:
 
     # -- per-utterance LoRA: adapters resident beside the packed weights, one slot (or none) per sequence -------------
     def load_adapter(self, slot: int, adapters) -> None:
-        """`adapters` = [(layer, target, A[r,in], B[out,r], scale)] as returned by pipeline.load_lora_adapter; replaces whatever the slot held."""
+        """`adapters` = [(layer, target, A[r,in], B[out,r], scale)] as returned by pipeline.load_lora_adapter; replaces whatever the slot held.  Targets: q/k/v/o_proj
+        and gate / up / down_proj, r <= 16, shapes checked against the target's (out, in).  The tables of the three MLP targets (737 KB per layer and slot) are
+        allocated when the first of them is loaded."""
         if not self._finalized:
             raise _lib.HipBackendError("weights not loaded")
+        for (layer, target, A, B, scale) in adapters:
+            self._check_lora(layer, target, A, B, r_max=16)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.ctts_gpt_clear_adapter(self._h, int(slot)), "clear_adapter")
             for (layer, target, A, B, scale) in adapters:
@@ -521,7 +557,9 @@ class GPT:
 
     def set_row_adapters(self, slots) -> None:
         """Adapter slot (or -1 / None) per sequence for the following generate() calls; None switches the per-row path off.  With it
-        every q/k/v/o projection evaluates W x + scale * B (A x) per row (decode: inside the projection launches, lora_worker.h; prompt pass: two more launches per layer).
+        every projection the row's adapter names evaluates W x + scale * B (A x) per row (q/k/v/o -- decode: inside the projection launches, lora_worker.h; prompt pass: two
+        more launches per layer.  gate / up / down: two more launches per layer, decode and prompt pass, while a live row's slot holds such a target; decode steps then take the
+        launch chain at every row count).
         Not under options={"batch_invariant": 1}: per-utterance adapters are outside its contract (a merged adapter, with_lora(), is covered)."""
         with torch.cuda.device(self.device):
             if slots is None:

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import dataclasses
 import json
+import math
 import logging
 import os
 from collections import OrderedDict
@@ -67,7 +68,7 @@ class TorchSeedContext:                        # reference commons/utils.py:48-5
 
 # gen_logits and its scalar carriers live beside the sampler configuration they feed (hip_models/gpt.py): one conversion for a call's knobs and for an
 # utterance's (sampling_per_row)
-from .hip_models.gpt import _RepPenalty, _TopK, _TopP, gen_logits  # noqa: E402,F401
+from .hip_models.gpt import LORA_TARGETS, _RepPenalty, _TopK, _TopP, check_lora_shapes, gen_logits  # noqa: E402,F401
 
 
 # params_per_utterance (ChatTTSPlusPipeline.infer / infer_sharded): the InferCodeParams fields one utterance may set for itself.  The sampling knobs
@@ -200,24 +201,54 @@ def load_config(path: str) -> dict:
         return yaml.safe_load(f)
 
 
-def load_lora_adapter(path: str):
+def load_lora_adapter(path: str, hidden_size: int = 768, intermediate_size: int = 3072):
     """peft adapter directory -> [(layer, target, A[r,in], B[out,r], scale)] (pipeline:420-432; train config
-    configs/train/train_voice_clone_lora.yaml:72-80: r=8, alpha=16 on q/k/v/o).  Reads adapter_config.json +
-    adapter_model.safetensors directly; peft is not needed."""
+    configs/train/train_voice_clone_lora.yaml:72-83: r=8, alpha=16 on q/k/v/o, with gate / up / down as the commented-out candidates).  Reads
+    adapter_config.json + adapter_model.safetensors directly; peft is not needed.  The seven targets of the decoder layers are served (`self_attn.{q,k,v,o}_proj`,
+    `mlp.{gate,up,down}_proj`); any other tensor in the file (`lora_embedding_A` / `_B`, `modules_to_save` copies, heads) is an error that names the key and the file, and so is an A / B pair
+    whose shapes do not fit its target.  Config: `r` and `lora_alpha` default to 8 as in peft's LoraConfig; `use_rslora` gives scale = alpha / sqrt(r);
+    `use_dora` is refused (its merge rule is not W + scale * B A).  The file layout itself is not pinned against peft (not available offline): pinned algebraically only."""
     from safetensors.numpy import load_file
-    with open(os.path.join(path, "adapter_config.json")) as f:
+    cfg_path = os.path.join(path, "adapter_config.json")
+    with open(cfg_path) as f:
         ac = json.load(f)
-    scale = float(ac["lora_alpha"]) / float(ac["r"])
-    sd = load_file(os.path.join(path, "adapter_model.safetensors"))
+    if ac.get("use_dora", False):
+        raise ValueError(f"{cfg_path}: use_dora adapters are not supported (DoRA's merge is not W + scale * B A; merging it as LoRA would be silently wrong)")
+    r = int(ac.get("r", 8))
+    alpha = float(ac.get("lora_alpha", 8))
+    scale = alpha / math.sqrt(r) if ac.get("use_rslora", False) else alpha / float(r)
+    st_path = os.path.join(path, "adapter_model.safetensors")
+    sd = load_file(st_path)
     out = []
-    for k, A in sd.items():
-        if ".lora_A" not in k:
-            continue
+
+    def parse(k):
+        """(layer, target, 'lora_A' | 'lora_B') of `...layers.N.{self_attn,mlp}.TARGET.lora_{A,B}[.adapter_name].weight`, else None."""
         parts = k.split(".")
+        if "layers" not in parts:
+            return None
         li = parts.index("layers")
-        layer, target = int(parts[li + 1]), parts[li + 3]
+        if len(parts) < li + 6 or not parts[li + 1].isdigit() or LORA_TARGETS.get(parts[li + 3]) != parts[li + 2]:
+            return None
+        if parts[li + 4] not in ("lora_A", "lora_B") or parts[-1] != "weight" or len(parts) > li + 7:
+            return None
+        return int(parts[li + 1]), parts[li + 3], parts[li + 4]
+    for k in sd:        # every tensor of the file must be one this backend applies: anything else (lora_embedding_A / _B, modules_to_save copies, heads, DoRA magnitudes) would be dropped silently
+        if parse(k) is None:
+            raise ValueError(f"{st_path}: key '{k}' is not a lora_A / lora_B matrix of a decoder layer's {' '.join(LORA_TARGETS)} (embeddings, heads and modules_to_save are not served)")
+    for k, A in sd.items():
+        layer, target, which = parse(k)
+        if which != "lora_A":
+            if k.replace("lora_B", "lora_A") not in sd:
+                raise ValueError(f"{st_path}: key '{k}' has no '{k.replace('lora_B', 'lora_A')}'")
+            continue
         Bk = k.replace("lora_A", "lora_B")
-        out.append((layer, target, np.asarray(A, dtype=np.float32), np.asarray(sd[Bk], dtype=np.float32), scale))
+        if Bk not in sd:
+            raise ValueError(f"{st_path}: key '{k}' has no '{Bk}'")
+        A = np.asarray(A, dtype=np.float32); Bm = np.asarray(sd[Bk], dtype=np.float32)
+        check_lora_shapes(layer, target, A, Bm, hidden_size, intermediate_size, where=f" {st_path} (key '{k}')")
+        if A.shape[0] != r and "r" in ac:
+            raise ValueError(f"{st_path}: key '{k}' has rank {A.shape[0]}, adapter_config.json says r = {r} (rank_pattern is not supported)")
+        out.append((layer, target, A, Bm, scale))
     return out
 
 

@@ -80,7 +80,11 @@ void ctts_gpt_destroy(ctts_gpt* h);
  *                         concurrently on different streams would have to share the CUs; every wait is bounded and ctts_gpt_progress reports a give-up)
  *   "persistent_share_keys"  1..5 rows: one key share per (row, head) serves up to this + 128 cached keys (384 in registers, the rest in LDS), longer contexts open more shares (default 384)
  *   "persistent_lora"     1 (default): rows that carry a per-utterance adapter stay on the persistent launch -- its otherwise idle compute waves evaluate A h, the edge lanes add
- *                         B (A h) to their q / k / v / o_proj rows (paced schedule; 0 = such batches take the launch chain's worker workgroups, "lora_fold")
+ *                         B (A h) to their q / k / v / o_proj rows (paced schedule; 0 = such batches take the launch chain's worker workgroups, "lora_fold").
+ *                         The launch carries the q/k/v/o terms only: while a live row's adapter names gate_proj / up_proj / down_proj the step takes the launch
+ *                         chain at every row count, whatever this option says.  Teaching the persistent launch the MLP terms is out of scope so far; its price,
+ *                         fp32, 1 row, ~300 keys: 0.897 ms/step with an all-seven-target adapter (launch chain) against 0.304 with a q/k/v/o adapter (persistent
+ *                         launch; this library -- the parent commit's measured 0.316 in the same call; profiles/mlp_lora_probe.jsonl)
  *   "persistent_delay_lora"  poll delay of that hand-off (-1 = 14 + 2 rows, the default)
  *   "persistent_layers_per_launch"  0 = the whole stack in one launch (default), n = n layers per launch
  *   "persistent_schedule" weight request schedule of the persistent launch (1 / 2 / 3, default 3 = paced requests)    "persistent_pace"  its pacing interval (-1 = by row count, the default)
@@ -102,8 +106,11 @@ void ctts_gpt_destroy(ctts_gpt* h);
  *   "nbg2_rows"           decode batches of >= this many rows use 32-row blocks instead of 16-row chunks (default 81 fp32 / 57 fp16)
  *   "graph_steps"         decode steps captured per hipGraph (default 4)
  *   "graph_steps_persistent"  ... per hipGraph of the persistent paths, whose step is 2 launches (default 16; shorter remainders use "graph_steps")
+ *   "lora_mlp_live"       read only (get_option): 1 while a live row's adapter names gate_proj / up_proj / down_proj
  *   "lora_fold"           per-utterance adapters at decode: 1 (default) = the rows' low-rank terms come from worker workgroups inside the QKV / o_proj launches
- *                         (lora_worker.h), 0 = two more launches per layer (lora.hip; the prompt pass always uses those)
+ *                         (lora_worker.h), 0 = two more launches per layer (lora.hip; the prompt pass always uses those).  The q/k/v/o terms only: gate / up / down
+ *                         terms always come from two launches of their own per layer, beside either form (measured with all seven targets on every row, fp32,
+ *                         ms/step 1 / 0: 1 row 0.90 / 1.06, 8 rows 1.04 / 1.24, 32 rows 1.19 / 1.39 -- the workers stay)
  *   "persistent_fault"    test hook: one workgroup withholds a hand-off in layer value - 1 (the bounded waits must end the step with an error)
  *   "batch_invariant"     fp32 (parity) engines, default 0 (fp16 engines: setting it is an error).  1 = the batch-invariance contract below.  Before or after
  *                         finalize (after: the engine must hold the head / tail weight images).
@@ -146,14 +153,23 @@ int ctts_gpt_debug_read(ctts_gpt* h, const char* name, void* out, size_t max_byt
  * (the last two + emb_text enable the refine-text pass, infer_text=1). */
 int ctts_gpt_set_weight(ctts_gpt* h, const char* name, const float* data, size_t numel);
 
-/* LoRA merge rule of peft merge_and_unload (pipeline:420-432): W += scale * B @ A for one target
- * ("q_proj","k_proj","v_proj","o_proj") of one layer; A [r, in], B [out, r], host fp32.  Call before finalize. */
+/* LoRA merge rule of peft merge_and_unload (pipeline:420-432): W += scale * B @ A for one target of one layer -- "q_proj", "k_proj", "v_proj", "o_proj"
+ * (out x in = hidden x hidden), "gate_proj", "up_proj" (intermediate x hidden) or "down_proj" (hidden x intermediate; llama.py:214,737-739).  A [r][in], B [out][r], host
+ * fp32, both sized by the TARGET's own (out, in): the caller checks the shapes (hip_models.GPT.add_lora does).  An unknown target or a layer whose matrix is not loaded is
+ * an error naming it.  Call before finalize: a merged adapter is just weights, every engine mode serves it. */
 int ctts_gpt_merge_lora(ctts_gpt* h, int layer, const char* target, const float* A, const float* B, int r, float scale);
 
 /* Per-utterance LoRA (no counterpart in the reference, which merges ONE adapter for a whole batch, pipeline:420-432):
  * up to CTTS_MAX_ADAPTERS adapters stay resident beside the packed weights; every sequence of a batch selects one slot or none and
  * the projections evaluate  W x + scale * B (A x)  per row.  Call after ctts_gpt_finalize.
- *   set_adapter      one (layer, target in "q_proj","k_proj","v_proj","o_proj") of adapter `slot`: A [r][hidden], B [hidden][r], host fp32, r <= 16
+ *   set_adapter      one (layer, target) of adapter `slot`; targets and shapes as for ctts_gpt_merge_lora (A [r][in], B [out][r], host fp32), r <= 16.
+ *                    The tables of gate_proj / up_proj / down_proj (737 KB per layer and slot in fp32, 118 MB for 20 layers x 8 slots) are allocated when the
+ *                    first such target is loaded; the rows' gate / up terms (24 KB per prompt row of a pass: 402 MB on an engine sized for 16384-row passes)
+ *                    when a live row first selects a slot that holds one.  While a LIVE row's slot holds one of them, every layer runs two more launches (lora.hip:
+ *                    the gate / up term from the post-attention RMSNorm output, added before the activation in the SwiGLU epilogues; the down term from the
+ *                    down projection's own packed operand, added with the residual) -- decode steps and prompt passes -- and decode steps take the launch chain
+ *                    at every row count ("persistent_lora").  A batch whose live rows use q/k/v/o adapters only, or none, launches exactly what it would
+ *                    with no MLP adapter resident.
  *   clear_adapter    zeroes a slot (all layers / targets)
  *   set_row_adapters slot (or -1) per sequence for the following ctts_gpt_begin calls; slots == NULL or B == 0 switches the path off */
 #define CTTS_MAX_ADAPTERS 8
