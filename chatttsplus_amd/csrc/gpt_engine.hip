@@ -49,6 +49,7 @@ extern "C" int ctts_version(void) { return 1; }
 #define SMAX 8        // == ATT_SMAX in skinny_gemm.hip
 #define CTTS_PERSIST_MAX_ROWS PL_MAXR
 
+struct DecodePath { int splits, persist; };      // how a decode step runs: key splits of the decode attention (decode_splits) / key shares of the persistent launch, 0 = the launch chain (decode_persist)
 struct LayerW {
     void *qkv, *o, *gu, *d;      // RMSNorm weights are folded into qkv / gu columns
     // fp32 engines: head / tail fp16 images of 64 * W, [tile][k tile][head | tail][lane][16 B] in the fp16 tile order (common.h split_t): the prompt pass's split
@@ -113,7 +114,6 @@ struct ctts_gpt {
                                                  // ms/step launch slices / packed + combine: batch 8 0.599 / 0.613, 9 0.632 / 0.623, 10 0.641 / 0.627, 12 0.664 / 0.637,
                                                  // 14 0.687 / 0.648, 16 0.709 / 0.661; launch slices beyond 16 rows lose (17 0.765 -> 0.812, 32 0.860 -> 0.939)
     float* dpart = nullptr;                      // [rows<=32][4][768]
-    int cur_splits = 1;                          // key splits of the decode attention for the steps being launched (decode_splits)
     int launched = 0;                            // decode steps enqueued since begin / restart: host-side bound on the context length
     int nbg2_rows = 33;                          // decode batches of at least this many rows use 32-row blocks instead of 16-row chunks.
                                                  // Measured: two 16-row chunks beat one 32-row block at batch 24 / 32 (598 vs 624,
@@ -162,7 +162,6 @@ struct ctts_gpt {
     unsigned* pl_epoch = nullptr;                //   launch counter = granule tag
     int* pl_error = nullptr;                     //   first give-up code (0 = none); reported by ctts_gpt_progress
     unsigned long long* pl_ts = nullptr;         //   diagnostics: per-workgroup phase marks of the last launch ("persistent_timestamps")
-    int cur_persist = 0;                         //   the steps being launched use the persistent layer
     int pl_ts_on = 0;
     int persist_fault = 0;                       //   test hook ("persistent_fault"): see PersistArgs.fault
     int persist_pair_keys = 704;                 //   6..8 rows: contexts beyond this many keys (minus 128 per row above 6) go back to the launch chain; "persistent_pair_keys"
@@ -259,19 +258,28 @@ struct ctts_gpt {
     int graph_steps_persist = 16;                // ... and per graph of the persistent paths (2 nodes per step: 32 nodes): the replay gap is 8.1 us whatever the graph
                                                  // holds (profiles/r05_trace_gaps_b1.json), 2.0 us per step at 4 steps, 0.5 us at 16
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct DecodeSeg { int n, splits, persist; };
+    struct DecodeSeg { int n; DecodePath path; };
     std::vector<DecodeSeg> segs;                 // plan_decode: the steps of one decode call as runs of equal decode paths
     // ctts_gpt_score: the gathered scored rows [SCORE_ROWS][H], their head logits [SCORE_ROWS][4 * V] and output entries [SCORE_ROWS] --
     // allocated by the first score call (engines that never score keep their footprint)
     float *score_x = nullptr, *score_logits = nullptr; int* score_oidx = nullptr;
     size_t score_bytes = 0;
+    std::vector<void*> owned;                    // every device buffer of the engine (dev_alloc)
 };
 #define SCORE_ROWS 2048       // scored rows per heads launch: bounds the logits scratch (2048 x 2504 fp32 = 20.5 MB)
 
-static int dev_alloc(void** p, size_t bytes) {
+// Device buffers belong to the engine: every allocation is recorded, ctts_gpt_destroy frees what is on the record
+static int dev_alloc(ctts_gpt* h, void** p, size_t bytes) {
     CTTS_HIP_CHECK(hipMalloc(p, bytes));
+    h->owned.push_back(*p);
     CTTS_HIP_CHECK(hipMemset(*p, 0, bytes));
     return 0;
+}
+// ... and one released early leaves the record
+static void dev_free(ctts_gpt* h, void* p) {
+    if (!p) return;
+    for (size_t i = 0; i < h->owned.size(); ++i) if (h->owned[i] == p) { h->owned.erase(h->owned.begin() + i); break; }
+    (void)hipFree(p);
 }
 
 extern "C" int ctts_gpt_create(const ctts_gpt_cfg* c, ctts_gpt** out) {
@@ -361,8 +369,8 @@ static int ensure_persist(ctts_gpt* h, bool required) {
         return 0;
     }
     if (persist_configure()) return 1;
-    if (dev_alloc((void**)&h->pl_g, (size_t)PL_G_TOTAL * 8) || dev_alloc((void**)&h->pl_epoch, 4)) return 1;
-    if (!h->pl_error && dev_alloc((void**)&h->pl_error, 4)) return 1;
+    if (dev_alloc(h, (void**)&h->pl_g, (size_t)PL_G_TOTAL * 8) || dev_alloc(h, (void**)&h->pl_epoch, 4)) return 1;
+    if (!h->pl_error && dev_alloc(h, (void**)&h->pl_error, 4)) return 1;
     const unsigned one = 1;
     CTTS_HIP_CHECK(hipMemcpy(h->pl_epoch, &one, 4, hipMemcpyHostToDevice));
     h->persist_ok = true;
@@ -375,16 +383,15 @@ static int persist_images(ctts_gpt* h) {
     // built into locals and published only when complete: a failed allocation or repack (an engine beside others on a full device) leaves the engine on the launch
     // chain -- the mode is an optimisation -- instead of failing the decode call that happened to need the images first, or leaving half-built ones behind
     char* img = nullptr; char* img_head = nullptr;
-    bool ok = dev_alloc((void**)&img, layer_bytes * h->L) == 0;
+    bool ok = dev_alloc(h, (void**)&img, layer_bytes * h->L) == 0;
     for (int l = 0; ok && l < h->L; ++l)
         ok = launch_persist_repack(h->esz == 2, h->lw[l].qkv, h->lw[l].o, h->lw[l].gu, h->lw[l].d, img + layer_bytes * l, nullptr) == 0;
-    ok = ok && dev_alloc((void**)&img_head, (size_t)PL_GEMV_BLOCKS * PL_HEAD_FRAGS * 4 * h->esz) == 0;
+    ok = ok && dev_alloc(h, (void**)&img_head, (size_t)PL_GEMV_BLOCKS * PL_HEAD_FRAGS * 4 * h->esz) == 0;
     ok = ok && launch_persist_repack_heads(h->esz == 2, h->whead, (h->NVQ * h->V + 15) / 16, img_head, nullptr) == 0;
     ok = ok && hipDeviceSynchronize() == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
-        if (img) (void)hipFree(img);
-        if (img_head) (void)hipFree(img_head);
+        dev_free(h, img); dev_free(h, img_head);
         h->persist_rows = 0;                                     // (ctts_gpt_get_option reports it; "persistent_rows" can be set again)
         return 0;
     }
@@ -392,141 +399,98 @@ static int persist_images(ctts_gpt* h) {
     return 0;
 }
 
+// Named engine options: explicit calls of the host side (hip_models.GPT(options=...)), never the environment.  One row per option: its field, how a value is clamped
+// (v < lo -> below, v > hi -> above; OPT_FLAG: v != 0), whether it can be set / read, and what ctts_gpt_get_option reports while "batch_invariant" pins it (OPT_PIN: the
+// stored value is kept for when the option is switched off; what the launches use meanwhile is stated at tuning()).  Options that do more than store an integer name a hook.
+enum { OPT_W = 1, OPT_R = 2, OPT_RW = 3, OPT_FLAG = 4, OPT_PIN = 8 };
+enum OptHook { HOOK_NONE, HOOK_BATCH_INV, HOOK_PREFILL_SPLIT, HOOK_SPLIT_DECODE, HOOK_PERSIST_ROWS, HOOK_TIMESTAMPS, HOOK_DECODE_SPLITS, HOOK_POLL };
+struct OptRow { const char* name; int ctts_gpt::*field; int lo, below, hi, above; int flags; int pin; OptHook hook; };
+#define OPT_MAX 0x7FFFFFFF
+#define OPT_MIN(lo) lo, lo, OPT_MAX, OPT_MAX             // below lo -> lo
+#define OPT_RANGE(lo, hi) lo, lo, hi, hi                 // clamped to lo..hi
+#define OPT_ANY 0, 0, 0, 0                               // OPT_FLAG rows and hooks that do not clamp
+static const OptRow g_options[] = {
+    {"batch_invariant", &ctts_gpt::batch_inv, OPT_ANY, OPT_RW | OPT_FLAG, 0, HOOK_BATCH_INV},      // fp32 engines: bit-identical rows whatever the batch / schedule (see batch_inv); before or after finalize
+    // prompt passes of >= this many rows use the head / tail fp16 split GEMMs (fp32 engines); 0 = never.  Before finalize: also decides whether the images are built; afterwards the
+    // pass can be switched off (0: a checkpoint that leaves the fp16 range, see ctts_gpt_saturations) or moved while the images exist
+    {"prefill_split_rows", &ctts_gpt::split_rows_min, OPT_MIN(0), OPT_RW | OPT_PIN, 1, HOOK_PREFILL_SPLIT},
+    // fp32 engines: decode batches of >= this many rows multiply on the fp16 pipes with head / tail operands (0 = never; see split_dec_rows).  Before finalize: also decides whether the images are built
+    {"split_decode_rows", &ctts_gpt::split_dec_rows, OPT_MIN(0), OPT_RW | OPT_PIN, 1, HOOK_SPLIT_DECODE},
+    {"split_nbg2_rows", &ctts_gpt::split_nbg2_rows, OPT_MIN(17), OPT_RW | OPT_PIN, 0, HOOK_NONE},
+    {"weight_prefetch_kb", &ctts_gpt::prefetch_kb, OPT_RANGE(0, 4096), OPT_RW, 0, HOOK_NONE},      // launch chain: KiB of the next launch's weights per prefetch workgroup (0 = no prefetch workgroups; see prefetch_kb)
+    {"valu_rows", &ctts_gpt::valu_rows, OPT_RANGE(0, 4), OPT_RW | OPT_PIN, 0, HOOK_NONE},          // fp32 engines: decode batches of <= this many rows run their projections on the VALU instead of exact-f32 MFMA (0..4)
+    // decode batches of <= this many rows run each layer as ONE persistent launch (0 = off); reads the EFFECTIVE value (0 when the mode is unavailable)
+    {"persistent_rows", &ctts_gpt::persist_rows, OPT_RANGE(0, CTTS_PERSIST_MAX_ROWS), OPT_RW | OPT_PIN, 0, HOOK_PERSIST_ROWS},
+    {"persistent_delay_lora", &ctts_gpt::persist_delay_u, 0, -1, 256, 256, OPT_RW, 0, HOOK_NONE},
+    {"prefill_small_blocks", &ctts_gpt::prefill_small_blocks, OPT_MIN(0), OPT_RW, 0, HOOK_NONE},
+    {"prefill_ring4_blocks", &ctts_gpt::prefill_ring4_blocks, OPT_MIN(0), OPT_RW, 0, HOOK_NONE},
+    {"prefill_splitk_rows", &ctts_gpt::prefill_sk_rows, OPT_MIN(0), OPT_RW | OPT_PIN, 0, HOOK_NONE},
+    {"prefill_pp_blocks", &ctts_gpt::prefill_pp_blocks, -4, 0, OPT_MAX, OPT_MAX, OPT_RW, 0, HOOK_NONE},      // -3 / -4: always the counter-phased kernel with that many n tiles per wave (tests, A/B)
+    {"attn_wide_blocks", &ctts_gpt::attn_wide_blocks, OPT_MIN(0), OPT_RW | OPT_PIN, OPT_MAX, HOOK_NONE},
+    {"persistent_share_keys", &ctts_gpt::persist_share_keys, 64, 384, OPT_MAX, OPT_MAX, OPT_RW, 0, HOOK_NONE},
+    {"persistent_lora", &ctts_gpt::persist_lora, OPT_ANY, OPT_RW | OPT_FLAG, 0, HOOK_NONE},        // 1 (default): rows with per-utterance adapters stay on the persistent launch; 0 = they take the launch chain
+    {"persistent_heads", &ctts_gpt::persist_heads, OPT_ANY, OPT_RW | OPT_FLAG, 0, HOOK_NONE},      // 1 (default): the persistent launch that ends the stack also runs the final norm + heads; 0 = the separate heads launch
+    {"persistent_layers_per_launch", &ctts_gpt::persist_lpl, OPT_MIN(0), OPT_RW, 0, HOOK_NONE},    // 0 = the whole stack in one launch (default); 1 = one launch per layer
+    {"persistent_schedule", &ctts_gpt::persist_sched, 1, 1, 3, 1, OPT_RW, 0, HOOK_NONE},           // 1 / 2: see persist_layer.hip
+    {"lora_fold", &ctts_gpt::lora_fold, 0, 1, 3, 1, OPT_RW, 0, HOOK_NONE},                         // per-utterance adapters at decode: 1 = workers inside the QKV / o_proj launches, 0 = two more launches per layer
+    {"persistent_fault", &ctts_gpt::persist_fault, OPT_MIN(0), OPT_RW, 0, HOOK_NONE},              // test hook: a withheld hand-off; every wait is bounded, ctts_gpt_progress reports the edge
+    {"persistent_pair_keys", &ctts_gpt::persist_pair_keys, OPT_MIN(0), OPT_RW, 0, HOOK_NONE},
+    {"persistent_max_keys", &ctts_gpt::persist_max_keys, OPT_MIN(0), OPT_RW, 0, HOOK_NONE},
+    {"persistent_splits", &ctts_gpt::persist_splits, OPT_RANGE(0, PL_SMAX), OPT_RW, 0, HOOK_NONE},
+    {"persistent_pace", &ctts_gpt::persist_pace, 0, -1, 64, 64, OPT_RW, 0, HOOK_NONE},             // SCHED 3: ~128-cycle units between two paced weight requests of a wave (< 0: by row count)
+    {"persistent_delay_att", &ctts_gpt::persist_delay_att, OPT_RANGE(0, 256), OPT_RW, 0, HOOK_NONE},
+    {"persistent_delay", &ctts_gpt::persist_delay, OPT_RANGE(0, 256), OPT_RW, 0, HOOK_NONE},
+    {"persistent_delay_act", &ctts_gpt::persist_delay_act, OPT_RANGE(0, 256), OPT_RW, 0, HOOK_NONE},
+    {"persistent_delay_x", &ctts_gpt::persist_delay_x, OPT_RANGE(0, 256), OPT_RW, 0, HOOK_NONE},
+    {"persistent_nap_qkv", &ctts_gpt::persist_nap_qkv, OPT_RANGE(0, 256), OPT_RW, 0, HOOK_NONE},
+    {"persistent_nap", &ctts_gpt::persist_nap, OPT_RANGE(0, 256), OPT_RW, 0, HOOK_NONE},
+    {"persistent_poll", &ctts_gpt::persist_poll, OPT_ANY, OPT_RW, 0, HOOK_POLL},                   // bit 0: sentinel granules before the full sweeps (< 0: by row count)
+    {"persistent_timestamps", &ctts_gpt::pl_ts_on, OPT_ANY, OPT_RW | OPT_FLAG, 0, HOOK_TIMESTAMPS},      // diagnostics: every workgroup of a persistent launch records wall_clock64 marks (ctts_gpt_debug_read "pl_ts")
+    {"decode_splits", &ctts_gpt::force_splits, OPT_ANY, OPT_RW | OPT_PIN, 1, HOOK_DECODE_SPLITS},  // key splits of the decode attention (0 = the decode_splits policy); out-of-range values are refused
+    {"split_rows", &ctts_gpt::split_rows, OPT_RANGE(0, 32), OPT_RW | OPT_PIN, 0, HOOK_NONE},       // decode batches up to this size run the down projection as split-K launch slices
+    {"nbg2_rows", &ctts_gpt::nbg2_rows, OPT_MIN(17), OPT_RW | OPT_PIN, 0, HOOK_NONE},              // decode batches of >= this many rows use 32-row blocks (see nbg2_rows)
+    {"down_splitk_rows", &ctts_gpt::down_sk_rows, OPT_MIN(0), OPT_RW | OPT_PIN, 1, HOOK_NONE},     // see down_sk_rows
+    {"graph_steps", &ctts_gpt::graph_steps, OPT_RANGE(1, 64), OPT_RW, 0, HOOK_NONE},
+    {"graph_steps_persistent", &ctts_gpt::graph_steps_persist, OPT_RANGE(1, 64), OPT_RW, 0, HOOK_NONE},
+    {"lora_mlp_live", &ctts_gpt::lora_mlp, OPT_ANY, OPT_R, 0, HOOK_NONE},      // read only: 1 while a live row's adapter names gate / up / down (the two MLP launches per layer run, decode on the launch chain)
+};
+static const OptRow* find_option(const char* name, int access) {
+    for (const OptRow& o : g_options) if (!strcmp(name, o.name)) return (o.flags & access) ? &o : nullptr;
+    return nullptr;
+}
+
 extern "C" int ctts_gpt_get_option(ctts_gpt* h, const char* name, int* value) {
     if (!h || !name || !value) { ctts_set_error("get_option: null argument"); return 1; }
-    const std::string n(name);
-    if (n == "batch_invariant") { *value = h->batch_inv; return 0; }
-    if (h->batch_inv) {          // what the launches use while the option is on (the tuning values set meanwhile are kept for when it is switched off)
-        static const struct { const char* name; int value; } eff[] = {
-            {"persistent_rows", 0}, {"valu_rows", 0}, {"split_decode_rows", 1}, {"split_rows", 0}, {"down_splitk_rows", 1}, {"nbg2_rows", 0},
-            {"split_nbg2_rows", 0}, {"decode_splits", 1}, {"attn_wide_blocks", 0x7FFFFFFF}, {"prefill_split_rows", 1}, {"prefill_splitk_rows", 0}};
-        for (const auto& e : eff) if (n == e.name) { *value = e.value; return 0; }
-    }
-    if (n == "persistent_rows") *value = (h->persist_ok || !h->finalized) ? h->persist_rows : 0;      // the EFFECTIVE value (0 when the mode is unavailable)
-    else if (n == "persistent_heads") *value = h->persist_heads;
-    else if (n == "persistent_lora") *value = h->persist_lora;
-    else if (n == "persistent_share_keys") *value = h->persist_share_keys;
-    else if (n == "attn_wide_blocks") *value = h->attn_wide_blocks;
-    else if (n == "prefill_pp_blocks") *value = h->prefill_pp_blocks;
-    else if (n == "prefill_splitk_rows") *value = h->prefill_sk_rows;
-    else if (n == "prefill_ring4_blocks") *value = h->prefill_ring4_blocks;
-    else if (n == "prefill_small_blocks") *value = h->prefill_small_blocks;
-    else if (n == "persistent_delay_lora") *value = h->persist_delay_u;
-    else if (n == "valu_rows") *value = h->valu_rows;
-    else if (n == "prefill_split_rows") *value = h->split_rows_min;
-    else if (n == "split_decode_rows") *value = h->split_dec_rows;
-    else if (n == "weight_prefetch_kb") *value = h->prefetch_kb;
-    else if (n == "nbg2_rows") *value = h->nbg2_rows;
-    else if (n == "split_nbg2_rows") *value = h->split_nbg2_rows;
-    else if (n == "split_rows") *value = h->split_rows;
-    else if (n == "graph_steps") *value = h->graph_steps;
-    else if (n == "graph_steps_persistent") *value = h->graph_steps_persist;
-    else if (n == "decode_splits") *value = h->force_splits;
-    else if (n == "lora_fold") *value = h->lora_fold;
-    else if (n == "lora_mlp_live") *value = h->lora_mlp;      // read only: 1 while a live row's adapter names gate / up / down (the two MLP launches per layer run, decode on the launch chain)
-    else if (n == "down_splitk_rows") *value = h->down_sk_rows;
-    else { ctts_set_error("get_option: unknown option '%s'", name); return 1; }
+    const OptRow* o = find_option(name, OPT_R);
+    if (!o) { ctts_set_error("get_option: unknown option '%s'", name); return 1; }
+    if (h->batch_inv && (o->flags & OPT_PIN)) *value = o->pin;          // what the launches use while the option is on (the tuning values set meanwhile are kept for when it is switched off)
+    else if (o->hook == HOOK_PERSIST_ROWS) *value = (h->persist_ok || !h->finalized) ? h->persist_rows : 0;
+    else *value = h->*o->field;
     return 0;
 }
 
-// Named engine options: explicit calls of the host side (hip_models.GPT(options=...)), never the environment.  Options that shape the launches bump
-// `opt_gen`, which is part of the decode-graph key, so graphs captured under other settings are not replayed.
+// Options that shape the launches bump `opt_gen`, which is part of the decode-graph key, so graphs captured under other settings are not replayed.
 extern "C" int ctts_gpt_set_option(ctts_gpt* h, const char* name, int value) {
     if (!h || !name) { ctts_set_error("set_option: null argument"); return 1; }
-    const std::string n(name);
-    if (n == "batch_invariant") {                // fp32 engines: bit-identical rows whatever the batch / schedule (see batch_inv); before or after finalize
+    const OptRow* o = find_option(name, OPT_W);
+    if (!o) { ctts_set_error("set_option: unknown option '%s'", name); return 1; }
+    const bool images = h->split_ok && h->wsplit;      // (refusals first: a refused value changes nothing)
+    if (o->hook == HOOK_BATCH_INV) {
         if (h->cfg.dtype != CTTS_DTYPE_F32) { ctts_set_error("set_option(batch_invariant): fp32 (parity) engines only"); return 1; }
-        if (value && h->finalized && !(h->split_ok && h->wsplit && h->whead_sp)) {
+        if (value && h->finalized && !(images && h->whead_sp)) {
             ctts_set_error("set_option(batch_invariant): this engine holds no head / tail weight images (a weight beyond the fp16 range, or split_decode_rows and prefill_split_rows were 0 at finalize)");
             return 1;
         }
-        h->batch_inv = value ? 1 : 0;
-    } else if (n == "prefill_split_rows") {             // prompt passes of >= this many rows use the head / tail fp16 split GEMMs (fp32 engines); 0 = never.  Before finalize.
-        // before finalize: also decides whether the images are built; afterwards the pass can be switched off (0: a checkpoint that leaves the fp16 range, see
-        // ctts_gpt_saturations) or moved while the images exist
-        if (h->finalized && value > 0 && !(h->split_ok && h->wsplit)) { ctts_set_error("set_option(prefill_split_rows): this engine holds no head / tail weight images (fp16 engine, a weight beyond the fp16 range, or the option was 0 at finalize)"); return 1; }
-        h->split_rows_min = value < 0 ? 0 : value;
-    } else if (n == "split_decode_rows") {       // fp32 engines: decode batches of >= this many rows multiply on the fp16 pipes with head / tail operands (0 = never; see split_dec_rows)
-        if (!h->finalized) h->split_dec_rows = value < 0 ? 0 : value;      // before finalize: also decides whether the images are built
-        else if (value > 0 && !(h->split_ok && h->wsplit)) { ctts_set_error("set_option(split_decode_rows): this engine holds no head / tail weight images (fp16 engine, a weight beyond the fp16 range, or the option was 0 at finalize)"); return 1; }
-        else h->split_dec_rows = value < 0 ? 0 : value;
-    } else if (n == "split_nbg2_rows") {
-        h->split_nbg2_rows = value < 17 ? 17 : value;
-    } else if (n == "weight_prefetch_kb") {      // launch chain: KiB of the next launch's weights per prefetch workgroup (0 = no prefetch workgroups; see prefetch_kb)
-        h->prefetch_kb = value < 0 ? 0 : (value > 4096 ? 4096 : value);
-    } else if (n == "valu_rows") {               // fp32 engines: decode batches of <= this many rows run their projections on the VALU instead of exact-f32 MFMA (0..4)
-        h->valu_rows = value < 0 ? 0 : (value > 4 ? 4 : value);
-    } else if (n == "persistent_rows") {         // fp32 engines: decode batches of <= this many rows run each layer as ONE persistent launch (0 = off)
-        h->persist_rows = value < 0 ? 0 : (value > CTTS_PERSIST_MAX_ROWS ? CTTS_PERSIST_MAX_ROWS : value);
-        if (h->persist_rows > 0 && ensure_persist(h, true)) { h->persist_rows = 0; return 1; }
-    } else if (n == "persistent_delay_lora") {
-        h->persist_delay_u = value < 0 ? -1 : (value > 256 ? 256 : value);
-    } else if (n == "prefill_small_blocks") {
-        h->prefill_small_blocks = value < 0 ? 0 : value;
-    } else if (n == "prefill_ring4_blocks") {
-        h->prefill_ring4_blocks = value < 0 ? 0 : value;
-    } else if (n == "prefill_splitk_rows") {
-        h->prefill_sk_rows = value < 0 ? 0 : value;
-    } else if (n == "prefill_pp_blocks") {
-        h->prefill_pp_blocks = value < -4 ? 0 : value;      // -3 / -4: always the counter-phased kernel with that many n tiles per wave (tests, A/B)
-    } else if (n == "attn_wide_blocks") {
-        h->attn_wide_blocks = value < 0 ? 0 : value;
-    } else if (n == "persistent_share_keys") {
-        h->persist_share_keys = value < 64 ? 384 : value;
-    } else if (n == "persistent_lora") {         // 1 (default): rows with per-utterance adapters stay on the persistent launch; 0 = they take the launch chain
-        h->persist_lora = value ? 1 : 0;
-    } else if (n == "persistent_heads") {        // 1 (default): the persistent launch that ends the stack also runs the final norm + heads; 0 = the separate heads launch
-        h->persist_heads = value ? 1 : 0;
-    } else if (n == "persistent_layers_per_launch") {      // 0 = the whole stack in one launch (default); 1 = one launch per layer
-        h->persist_lpl = value < 0 ? 0 : value;
-    } else if (n == "persistent_schedule") {               // 1 / 2: see persist_layer.hip
-        h->persist_sched = (value >= 1 && value <= 3) ? value : 1;
-    } else if (n == "lora_fold") {                         // per-utterance adapters at decode: 1 = workers inside the QKV / o_proj launches, 0 = two more launches per layer
-        h->lora_fold = (value < 0 || value > 3) ? 1 : value;
-    } else if (n == "persistent_fault") {                  // test hook: a withheld hand-off; every wait is bounded, ctts_gpt_progress reports the edge
-        h->persist_fault = value < 0 ? 0 : value;
-    } else if (n == "persistent_pair_keys") {
-        h->persist_pair_keys = value < 0 ? 0 : value;
-    } else if (n == "persistent_max_keys") {
-        h->persist_max_keys = value < 0 ? 0 : value;
-    } else if (n == "persistent_splits") {
-        h->persist_splits = value < 0 ? 0 : (value > PL_SMAX ? PL_SMAX : value);
-    } else if (n == "persistent_pace") {                   // SCHED 3: ~128-cycle units between two paced weight requests of a wave
-        h->persist_pace = value < 0 ? -1 : (value > 64 ? 64 : value);          // (< 0: by row count)
-    } else if (n == "persistent_delay_att") {
-        h->persist_delay_att = value < 0 ? 0 : (value > 256 ? 256 : value);
-    } else if (n == "persistent_delay") {
-        h->persist_delay = value < 0 ? 0 : (value > 256 ? 256 : value);
-    } else if (n == "persistent_delay_act") {
-        h->persist_delay_act = value < 0 ? 0 : (value > 256 ? 256 : value);
-    } else if (n == "persistent_delay_x") {
-        h->persist_delay_x = value < 0 ? 0 : (value > 256 ? 256 : value);
-    } else if (n == "persistent_nap_qkv") {
-        h->persist_nap_qkv = value < 0 ? 0 : (value > 256 ? 256 : value);
-    } else if (n == "persistent_nap") {
-        h->persist_nap = value < 0 ? 0 : (value > 256 ? 256 : value);
-    } else if (n == "persistent_poll") {                   // bit 0: sentinel granules before the full sweeps
-        h->persist_poll = value < 0 ? -1 : (value & 1);
-    } else if (n == "persistent_timestamps") {   // diagnostics: every workgroup of a persistent launch records wall_clock64 marks (ctts_gpt_debug_read "pl_ts")
-        if (value && !h->pl_ts && dev_alloc((void**)&h->pl_ts, (size_t)PL_BLOCKS * 10 * 8)) return 1;
-        h->pl_ts_on = value ? 1 : 0;
-    } else if (n == "decode_splits") {           // key splits of the decode attention (0 = the decode_splits policy)
+    } else if (o->hook == HOOK_PREFILL_SPLIT || o->hook == HOOK_SPLIT_DECODE) {
+        if (h->finalized && value > 0 && !images) { ctts_set_error("set_option(%s): this engine holds no head / tail weight images (fp16 engine, a weight beyond the fp16 range, or the option was 0 at finalize)", name); return 1; }
+    } else if (o->hook == HOOK_DECODE_SPLITS) {
         if (value < 0 || value > SMAX) { ctts_set_error("set_option(decode_splits): 0..%d", SMAX); return 1; }
-        h->force_splits = value;
-    } else if (n == "split_rows") {              // decode batches up to this size run the down projection as split-K launch slices
-        h->split_rows = value < 0 ? 0 : (value > 32 ? 32 : value);
-    } else if (n == "nbg2_rows") {               // decode batches of >= this many rows use 32-row blocks (see nbg2_rows)
-        h->nbg2_rows = value < 17 ? 17 : value;
-    } else if (n == "down_splitk_rows") {        // see down_sk_rows
-        h->down_sk_rows = value < 0 ? 0 : value;
-    } else if (n == "graph_steps") {
-        h->graph_steps = value < 1 ? 1 : (value > 64 ? 64 : value);
-    } else if (n == "graph_steps_persistent") {
-        h->graph_steps_persist = value < 1 ? 1 : (value > 64 ? 64 : value);
-    } else {
-        ctts_set_error("set_option: unknown option '%s'", name);
-        return 1;
-    }
+    } else if (o->hook == HOOK_TIMESTAMPS && value && !h->pl_ts && dev_alloc(h, (void**)&h->pl_ts, (size_t)PL_BLOCKS * 10 * 8)) return 1;
+    if (o->flags & OPT_FLAG) value = value ? 1 : 0;
+    else if (o->hook == HOOK_POLL) value = value < 0 ? -1 : (value & 1);
+    else if (o->hook != HOOK_DECODE_SPLITS) value = value < o->lo ? o->below : (value > o->hi ? o->above : value);
+    h->*o->field = value;
+    if (o->hook == HOOK_PERSIST_ROWS && value > 0 && ensure_persist(h, true)) { h->persist_rows = 0; return 1; }
     h->opt_gen++;
     return 0;
 }
@@ -534,12 +498,7 @@ extern "C" int ctts_gpt_set_option(ctts_gpt* h, const char* name, int value) {
 extern "C" void ctts_gpt_destroy(ctts_gpt* h) {
     if (!h) return;
     for (auto& kv : h->graphs) { (void)hipGraphExecDestroy(kv.second.exec); (void)hipGraphDestroy(kv.second.graph); }
-    void* bufs[] = {h->sk_scratch, h->dyn, h->wblob, h->wsplit, h->whead_sp, h->sp_x_hi, h->sp_x_lo, h->sp_act_hi, h->sp_act_lo, h->whead_text, h->lnf, h->emb_code, h->emb_text, h->rope, h->x_dec, h->x_last, h->x_pre, h->q_buf, h->part_ml, h->part_o, h->logits,
-                    h->act, h->attn_packed, h->norm_packed, h->dpart, h->rope_pre, h->rope_dec, h->meta_pre, h->meta_dec, h->meta_dec0, h->st, h->last_rows,
-                    h->hist_ring, h->sat, h->finend, h->xh, h->ssq, h->scale_o, h->scale_d, h->cx, h->crope, h->cmeta, h->cring, h->cfin, h->keep_dev,
-                    h->lora_A, h->lora_B, h->lora_Af, h->lora_scale, h->ln1, h->lora_slot_of_seq, h->lora_dqkv, h->lora_do, h->lora_g, h->lora_mA_gu, h->lora_mB_gu, h->lora_mA_d, h->lora_mB_d, h->lora_mscale, h->ln2, h->lora_dgu, h->pimg, h->pimg_head, h->pl_g, h->pl_epoch, h->pl_error, h->pl_ts, h->sk_slab, h->sk_cnt, h->rope_dec0, h->cknobs,
-                    h->score_x, h->score_logits, h->score_oidx};
-    for (void* b : bufs) if (b) (void)hipFree(b);
+    for (void* b : h->owned) (void)hipFree(b);
     if (h->host_pin) (void)hipHostFree(h->host_pin);
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -617,16 +576,16 @@ static int lora_target_index(const char* t) {
 static int lora_ensure_storage(ctts_gpt* h) {
     if (h->lora_A) return 0;
     const size_t per = (size_t)h->L * CTTS_MAX_ADAPTERS * 4 * 16 * h->H;
-    if (dev_alloc((void**)&h->lora_Af, per / 4 * 3 * 4)) return 1;
+    if (dev_alloc(h, (void**)&h->lora_Af, per / 4 * 3 * 4)) return 1;
     CTTS_HIP_CHECK(hipMemset(h->lora_Af, 0, per / 4 * 3 * 4));
-    if (dev_alloc((void**)&h->lora_A, per * 4) || dev_alloc((void**)&h->lora_B, per * 4) ||
-        dev_alloc((void**)&h->lora_scale, (size_t)h->L * CTTS_MAX_ADAPTERS * 4 * 4) || dev_alloc((void**)&h->lora_slot_of_seq, CTTS_MAX_B * 4) ||
-        dev_alloc((void**)&h->lora_dqkv, (size_t)h->pass_rows * 3 * h->H * 4) || dev_alloc((void**)&h->lora_do, (size_t)h->pass_rows * h->H * 4))
+    if (dev_alloc(h, (void**)&h->lora_A, per * 4) || dev_alloc(h, (void**)&h->lora_B, per * 4) ||
+        dev_alloc(h, (void**)&h->lora_scale, (size_t)h->L * CTTS_MAX_ADAPTERS * 4 * 4) || dev_alloc(h, (void**)&h->lora_slot_of_seq, CTTS_MAX_B * 4) ||
+        dev_alloc(h, (void**)&h->lora_dqkv, (size_t)h->pass_rows * 3 * h->H * 4) || dev_alloc(h, (void**)&h->lora_do, (size_t)h->pass_rows * h->H * 4))
         return 1;
     CTTS_HIP_CHECK(hipMemset(h->lora_slot_of_seq, 0xFF, CTTS_MAX_B * 4));
-    if (dev_alloc((void**)&h->lora_g, (size_t)CTTS_MAX_B * 4 * h->H * 8)) return 1;           // [rows][3][768] q/k/v | [rows][768] o_proj
+    if (dev_alloc(h, (void**)&h->lora_g, (size_t)CTTS_MAX_B * 4 * h->H * 8)) return 1;           // [rows][3][768] q/k/v | [rows][768] o_proj
     CTTS_HIP_CHECK(hipMemset(h->lora_g, 0, (size_t)CTTS_MAX_B * 4 * h->H * 8));                 // tag 0 never matches (tags start at 64)
-    if (!h->pl_error) { if (dev_alloc((void**)&h->pl_error, 4)) return 1; CTTS_HIP_CHECK(hipMemset(h->pl_error, 0, 4)); }
+    if (!h->pl_error) { if (dev_alloc(h, (void**)&h->pl_error, 4)) return 1; CTTS_HIP_CHECK(hipMemset(h->pl_error, 0, 4)); }
     return 0;
 }
 static int lora_ensure_mlp_storage(ctts_gpt* h) {
@@ -635,11 +594,11 @@ static int lora_ensure_mlp_storage(ctts_gpt* h) {
     struct { float** p; size_t n; } tabs[] = {{&h->lora_mA_gu, slots * 2 * 16 * H}, {&h->lora_mB_gu, slots * 2 * 16 * I}, {&h->lora_mA_d, slots * 16 * I},
                                               {&h->lora_mB_d, slots * 16 * H}, {&h->lora_mscale, slots * 4}};
     for (auto& t : tabs) {
-        if (*t.p == nullptr && dev_alloc((void**)t.p, t.n * 4)) return 1;
+        if (*t.p == nullptr && dev_alloc(h, (void**)t.p, t.n * 4)) return 1;
         CTTS_HIP_CHECK(hipMemset(*t.p, 0, t.n * 4));
     }
     if (h->ln2_host.size() != (size_t)h->L * H) { ctts_set_error("set_adapter: the post-attention RMSNorm weights were not kept at finalize"); return 1; }
-    if (h->ln2 == nullptr && dev_alloc((void**)&h->ln2, h->ln2_host.size() * 4)) return 1;
+    if (h->ln2 == nullptr && dev_alloc(h, (void**)&h->ln2, h->ln2_host.size() * 4)) return 1;
     CTTS_HIP_CHECK(hipMemcpy(h->ln2, h->ln2_host.data(), h->ln2_host.size() * 4, hipMemcpyHostToDevice));
     h->lora_mrank.assign(slots * 3, 0);
     return 0;
@@ -648,7 +607,7 @@ static int lora_ensure_mlp_storage(ctts_gpt* h) {
 // selects a slot that holds an MLP target (an MLP adapter that is resident but unused costs its tables only).  Called wherever lora_mlp can rise, outside graph capture.
 static int lora_ensure_mlp_terms(ctts_gpt* h) {
     if (!h->lora_mlp || h->lora_dgu) return 0;
-    return dev_alloc((void**)&h->lora_dgu, (size_t)h->pass_rows * 2 * h->I * 4);
+    return dev_alloc(h, (void**)&h->lora_dgu, (size_t)h->pass_rows * 2 * h->I * 4);
 }
 // does `slot` hold an MLP target in any layer?
 static bool lora_slot_has_mlp(const ctts_gpt* h, int slot) {
@@ -885,16 +844,16 @@ static int finalize_t(ctts_gpt* h) {
     const size_t total = per_layer * L + n_head;
     std::vector<WT> blob(total);
     h->lw.resize(L);
-    if (dev_alloc((void**)&h->wblob, total * sizeof(WT))) return 1;
+    if (dev_alloc(h, (void**)&h->wblob, total * sizeof(WT))) return 1;
     // fp32 engine whose prompt passes can reach the split-GEMM threshold, or whose decode batches can reach split_decode_rows: head / tail fp16 images of the layer matrices too
     const bool want_split = (sizeof(WT) == 4) && (h->batch_inv || (h->split_rows_min > 0 && (long)h->cfg.max_batch * h->cfg.max_seq >= h->split_rows_min) ||
                                                    (h->split_dec_rows > 0 && h->cfg.max_batch >= h->split_dec_rows));
     std::vector<half_t> sblob;
     if (want_split) {
         sblob.resize(per_layer * 2 * L);
-        if (dev_alloc((void**)&h->wsplit, per_layer * L * 2 * sizeof(half_t))) return 1;
+        if (dev_alloc(h, (void**)&h->wsplit, per_layer * L * 2 * sizeof(half_t))) return 1;
     }
-    if (dev_alloc((void**)&h->ln1, (size_t)L * H * 4)) return 1;       // input_layernorm weights, unfolded: the LoRA path needs w * x_hat itself
+    if (dev_alloc(h, (void**)&h->ln1, (size_t)L * H * 4)) return 1;       // input_layernorm weights, unfolded: the LoRA path needs w * x_hat itself
     struct LayerSrc { const std::vector<float>*q, *k, *v, *o, *g, *u, *d, *l1, *l2; };
     std::vector<LayerSrc> ls(L);
     for (int l = 0; l < L; ++l) {
@@ -992,7 +951,7 @@ static int finalize_t(ctts_gpt* h) {
         std::vector<half_t> hs((size_t)head_tiles * 16 * H * 2);
         const bool ok = pack_tiles_split(hs.data(), head_tiles, H, [&](int pr) -> const float* { return pr < nvalid ? folded.data() + (size_t)pr * H : nullptr; }, nf->data());
         if (ok) {
-            if (dev_alloc(&h->whead_sp, hs.size() * sizeof(half_t))) return 1;
+            if (dev_alloc(h, &h->whead_sp, hs.size() * sizeof(half_t))) return 1;
             CTTS_HIP_CHECK(hipMemcpy(h->whead_sp, hs.data(), hs.size() * sizeof(half_t), hipMemcpyHostToDevice));
         }
     }
@@ -1011,15 +970,15 @@ static int finalize_t(ctts_gpt* h) {
             }
             std::vector<WT> packed((size_t)tiles * 16 * H);
             pack_tiles<WT>(packed.data(), tiles, H, [&](int pr) -> const float* { return pr < Vt ? ft.data() + (size_t)pr * H : nullptr; }, nf->data());
-            if (dev_alloc(&h->whead_text, packed.size() * sizeof(WT))) return 1;
+            if (dev_alloc(h, &h->whead_text, packed.size() * sizeof(WT))) return 1;
             CTTS_HIP_CHECK(hipMemcpy(h->whead_text, packed.data(), packed.size() * sizeof(WT), hipMemcpyHostToDevice));
             h->vocab_text_head = Vt;
         }
     }
     CTTS_HIP_CHECK(hipMemcpy(h->wblob, blob.data(), total * sizeof(WT), hipMemcpyHostToDevice));
-    if (dev_alloc((void**)&h->lnf, H * 4)) return 1;
+    if (dev_alloc(h, (void**)&h->lnf, H * 4)) return 1;
     CTTS_HIP_CHECK(hipMemcpy(h->lnf, nf->data(), H * 4, hipMemcpyHostToDevice));
-    if (dev_alloc((void**)&h->emb_code, (size_t)h->NVQ * V * H * 4)) return 1;
+    if (dev_alloc(h, (void**)&h->emb_code, (size_t)h->NVQ * V * H * 4)) return 1;
     for (int i = 0; i < h->NVQ; ++i) {
         const std::vector<float>* e = need(h, "emb_code." + std::to_string(i) + ".weight", (size_t)V * H);
         if (!e) return 1;
@@ -1042,34 +1001,34 @@ extern "C" int ctts_gpt_finalize(ctts_gpt* h) {
     }
     const int PASS_ROWS = h->pass_rows;
     const size_t act_bytes = (size_t)((PASS_ROWS + PASS_PAD) / 16) * (h->I / (h->esz == 2 ? 32 : 16)) * 1024;
-    if (dev_alloc((void**)&h->x_dec, (size_t)CTTS_MAX_B * H * 4) || dev_alloc((void**)&h->x_last, (size_t)CTTS_MAX_B * H * 4) ||
-        dev_alloc((void**)&h->x_pre, (size_t)PASS_ROWS * H * 4) ||
-        dev_alloc((void**)&h->q_buf, (size_t)PASS_ROWS * H * 4) ||
-        dev_alloc((void**)&h->part_ml, (size_t)(CTTS_MAX_B + 32) * NH * SMAX * 2 * 4) ||          // flash-decoding partials: decode rows only (the prompt pass never splits keys)
-        dev_alloc((void**)&h->part_o, (size_t)(CTTS_MAX_B + 32) * NH * SMAX * CTTS_HEAD_DIM * 4) ||
-        dev_alloc((void**)&h->logits, (size_t)CTTS_MAX_B * (h->NVQ * h->V > h->vocab_text_head ? h->NVQ * h->V : h->vocab_text_head) * 4) || dev_alloc(&h->act, act_bytes) || dev_alloc((void**)&h->rope_pre, (size_t)MB * h->cfg.max_seq * 64 * 4) ||
-        dev_alloc((void**)&h->rope_dec, (size_t)CTTS_MAX_B * 64 * 4) || dev_alloc((void**)&h->dpart, (size_t)32 * 4 * H * 4) || dev_alloc(&h->attn_packed, (size_t)((PASS_ROWS + PASS_PAD) / 16) * (H / (h->esz == 2 ? 32 : 16)) * 1024) ||
-        dev_alloc(&h->norm_packed, (size_t)((PASS_ROWS + PASS_PAD) / 16) * (H / (h->esz == 2 ? 32 : 16)) * 1024) ||
-        dev_alloc((void**)&h->meta_pre, (size_t)MB * h->cfg.max_seq * sizeof(RowMeta)) ||
-        dev_alloc((void**)&h->meta_dec, CTTS_MAX_B * sizeof(RowMeta)) || dev_alloc((void**)&h->meta_dec0, CTTS_MAX_B * sizeof(RowMeta)) ||
-        dev_alloc((void**)&h->st, sizeof(DevState)) || dev_alloc((void**)&h->last_rows, CTTS_MAX_B * 4) ||
-        dev_alloc((void**)&h->dyn, sizeof(SamplerDyn)) || dev_alloc((void**)&h->hist_ring, (size_t)CTTS_MAX_B * CTTS_NUM_VQ * 16 * 4) ||
-        dev_alloc((void**)&h->finend, (size_t)CTTS_MAX_B * (sizeof(RowState) + sizeof(RowSampling))) || dev_alloc((void**)&h->sat, 4) ||
-        dev_alloc((void**)&h->cknobs, (size_t)CTTS_MAX_B * sizeof(RowSampling)) ||
-        dev_alloc((void**)&h->sk_slab, (size_t)(H / 16) * (CTTS_MAX_B / 16) * 4 * 256 * 4) || dev_alloc((void**)&h->sk_cnt, (size_t)(H / 16) * (CTTS_MAX_B / 16) * 4) ||
-        dev_alloc((void**)&h->cx, (size_t)CTTS_MAX_B * H * 4) || dev_alloc((void**)&h->crope, (size_t)CTTS_MAX_B * 64 * 4) ||
-        dev_alloc((void**)&h->cmeta, CTTS_MAX_B * sizeof(RowMeta)) || dev_alloc((void**)&h->cring, (size_t)CTTS_MAX_B * CTTS_NUM_VQ * 16 * 4) ||
-        dev_alloc((void**)&h->cfin, (size_t)CTTS_MAX_B * sizeof(RowState)) || dev_alloc((void**)&h->keep_dev, CTTS_MAX_B * 4) ||
-        dev_alloc(&h->xh, (size_t)((CTTS_MAX_B + 32) / 16) * (H / (h->esz == 2 ? 32 : 16)) * 1024) || dev_alloc((void**)&h->ssq, (size_t)(CTTS_MAX_B + 32) * (H / 16) * 4) ||
-        dev_alloc((void**)&h->scale_o, (size_t)(CTTS_MAX_B + 32) * 4) || dev_alloc((void**)&h->scale_d, (size_t)(CTTS_MAX_B + 32) * 4) ||
-        dev_alloc((void**)&h->rope_dec0, (size_t)CTTS_MAX_B * 64 * 4))
+    if (dev_alloc(h, (void**)&h->x_dec, (size_t)CTTS_MAX_B * H * 4) || dev_alloc(h, (void**)&h->x_last, (size_t)CTTS_MAX_B * H * 4) ||
+        dev_alloc(h, (void**)&h->x_pre, (size_t)PASS_ROWS * H * 4) ||
+        dev_alloc(h, (void**)&h->q_buf, (size_t)PASS_ROWS * H * 4) ||
+        dev_alloc(h, (void**)&h->part_ml, (size_t)(CTTS_MAX_B + 32) * NH * SMAX * 2 * 4) ||          // flash-decoding partials: decode rows only (the prompt pass never splits keys)
+        dev_alloc(h, (void**)&h->part_o, (size_t)(CTTS_MAX_B + 32) * NH * SMAX * CTTS_HEAD_DIM * 4) ||
+        dev_alloc(h, (void**)&h->logits, (size_t)CTTS_MAX_B * (h->NVQ * h->V > h->vocab_text_head ? h->NVQ * h->V : h->vocab_text_head) * 4) || dev_alloc(h, &h->act, act_bytes) || dev_alloc(h, (void**)&h->rope_pre, (size_t)MB * h->cfg.max_seq * 64 * 4) ||
+        dev_alloc(h, (void**)&h->rope_dec, (size_t)CTTS_MAX_B * 64 * 4) || dev_alloc(h, (void**)&h->dpart, (size_t)32 * 4 * H * 4) || dev_alloc(h, &h->attn_packed, (size_t)((PASS_ROWS + PASS_PAD) / 16) * (H / (h->esz == 2 ? 32 : 16)) * 1024) ||
+        dev_alloc(h, &h->norm_packed, (size_t)((PASS_ROWS + PASS_PAD) / 16) * (H / (h->esz == 2 ? 32 : 16)) * 1024) ||
+        dev_alloc(h, (void**)&h->meta_pre, (size_t)MB * h->cfg.max_seq * sizeof(RowMeta)) ||
+        dev_alloc(h, (void**)&h->meta_dec, CTTS_MAX_B * sizeof(RowMeta)) || dev_alloc(h, (void**)&h->meta_dec0, CTTS_MAX_B * sizeof(RowMeta)) ||
+        dev_alloc(h, (void**)&h->st, sizeof(DevState)) || dev_alloc(h, (void**)&h->last_rows, CTTS_MAX_B * 4) ||
+        dev_alloc(h, (void**)&h->dyn, sizeof(SamplerDyn)) || dev_alloc(h, (void**)&h->hist_ring, (size_t)CTTS_MAX_B * CTTS_NUM_VQ * 16 * 4) ||
+        dev_alloc(h, (void**)&h->finend, (size_t)CTTS_MAX_B * (sizeof(RowState) + sizeof(RowSampling))) || dev_alloc(h, (void**)&h->sat, 4) ||
+        dev_alloc(h, (void**)&h->cknobs, (size_t)CTTS_MAX_B * sizeof(RowSampling)) ||
+        dev_alloc(h, (void**)&h->sk_slab, (size_t)(H / 16) * (CTTS_MAX_B / 16) * 4 * 256 * 4) || dev_alloc(h, (void**)&h->sk_cnt, (size_t)(H / 16) * (CTTS_MAX_B / 16) * 4) ||
+        dev_alloc(h, (void**)&h->cx, (size_t)CTTS_MAX_B * H * 4) || dev_alloc(h, (void**)&h->crope, (size_t)CTTS_MAX_B * 64 * 4) ||
+        dev_alloc(h, (void**)&h->cmeta, CTTS_MAX_B * sizeof(RowMeta)) || dev_alloc(h, (void**)&h->cring, (size_t)CTTS_MAX_B * CTTS_NUM_VQ * 16 * 4) ||
+        dev_alloc(h, (void**)&h->cfin, (size_t)CTTS_MAX_B * sizeof(RowState)) || dev_alloc(h, (void**)&h->keep_dev, CTTS_MAX_B * 4) ||
+        dev_alloc(h, &h->xh, (size_t)((CTTS_MAX_B + 32) / 16) * (H / (h->esz == 2 ? 32 : 16)) * 1024) || dev_alloc(h, (void**)&h->ssq, (size_t)(CTTS_MAX_B + 32) * (H / 16) * 4) ||
+        dev_alloc(h, (void**)&h->scale_o, (size_t)(CTTS_MAX_B + 32) * 4) || dev_alloc(h, (void**)&h->scale_d, (size_t)(CTTS_MAX_B + 32) * 4) ||
+        dev_alloc(h, (void**)&h->rope_dec0, (size_t)CTTS_MAX_B * 64 * 4))
         return 1;
     if (h->wsplit) {     // operand images of the prompt rows for the split GEMMs: heads / tails of the normalised rows | attention outputs (K = 768) and of the SwiGLU outputs (K = 3072)
         const size_t rows = (size_t)PASS_ROWS + PASS_PAD;
-        if (dev_alloc(&h->sp_x_hi, rows * H * 2) || dev_alloc(&h->sp_x_lo, rows * H * 2) || dev_alloc(&h->sp_act_hi, rows * h->I * 2) || dev_alloc(&h->sp_act_lo, rows * h->I * 2)) return 1;
+        if (dev_alloc(h, &h->sp_x_hi, rows * H * 2) || dev_alloc(h, &h->sp_x_lo, rows * H * 2) || dev_alloc(h, &h->sp_act_hi, rows * h->I * 2) || dev_alloc(h, &h->sp_act_lo, rows * h->I * 2)) return 1;
         // short passes slice the down projection's K four ways (prefill_split.hip sp_launch): the slices' partial outputs [4][rows <= 2048, padded to 128][H] fp32 (<= 25 MB)
         h->sk_cap_floats = (size_t)4 * (size_t)(((PASS_ROWS < 2048 ? PASS_ROWS : 2048) + 127) / 128 * 128) * H;
-        if (dev_alloc((void**)&h->sk_scratch, h->sk_cap_floats * 4)) return 1;
+        if (dev_alloc(h, (void**)&h->sk_scratch, h->sk_cap_floats * 4)) return 1;
     }
     h->knobs = (RowSampling*)(h->finend + CTTS_MAX_B);      // (the sampler derives this address from its finend argument)
     CTTS_HIP_CHECK(hipHostMalloc((void**)&h->host_pin, 64));
@@ -1077,7 +1036,7 @@ extern "C" int ctts_gpt_finalize(ctts_gpt* h) {
         auto it = h->host.find("emb_text.weight");
         if (it != h->host.end() && it->second.size() % H == 0) {
             h->vocab_text = (int)(it->second.size() / H);
-            if (dev_alloc((void**)&h->emb_text, it->second.size() * 4)) return 1;
+            if (dev_alloc(h, (void**)&h->emb_text, it->second.size() * 4)) return 1;
             CTTS_HIP_CHECK(hipMemcpy(h->emb_text, it->second.data(), it->second.size() * 4, hipMemcpyHostToDevice));
         }
     }
@@ -1109,8 +1068,8 @@ extern "C" int ctts_gpt_bind_kv(ctts_gpt* h, void* kv, size_t bytes) {
 }
 extern "C" int ctts_gpt_set_rope(ctts_gpt* h, const float* rope_host, int n_pos) {
     if (!h || !rope_host || n_pos < h->cfg.max_seq) { ctts_set_error("set_rope: need at least max_seq=%d positions", h ? h->cfg.max_seq : 0); return 1; }
-    if (h->rope) (void)hipFree(h->rope);
-    if (dev_alloc((void**)&h->rope, (size_t)(n_pos + 1) * 64 * 4)) return 1;   // +1: the sampler prefetches the row of the position after the last one
+    dev_free(h, h->rope); h->rope = nullptr;
+    if (dev_alloc(h, (void**)&h->rope, (size_t)(n_pos + 1) * 64 * 4)) return 1;   // +1: the sampler prefetches the row of the position after the last one
     CTTS_HIP_CHECK(hipMemcpy(h->rope, rope_host, (size_t)n_pos * 64 * 4, hipMemcpyHostToDevice));
     h->rope_n = n_pos;
     return 0;
@@ -1121,6 +1080,20 @@ static inline void* kv_layer(ctts_gpt* h, int l, int which) {
     const size_t per = (size_t)h->cfg.max_batch * h->NH * h->cfg.max_seq * CTTS_HEAD_DIM * h->esz;
     return h->kv + ((size_t)l * 2 + which) * per;
 }
+// The row-count thresholds the launches use.  "batch_invariant" pins every choice that depends on the row count, the pass height or the padding, and THIS is where: no
+// persistent launch, no VALU rows, the split projections from 1 row on (one padded 16-row chunk), the down projection's K sliced inside the launch and never by launch slices,
+// never 32-row blocks at decode, unsplit attention on 8-wave blocks, the prompt's K never sliced (ctts_gpt_begin refuses adapters then).  plan_layers adds the two choices that are no threshold.
+struct Tuning { bool inv; int persist_rows, valu_rows, split_dec_rows, split_rows, down_sk_rows, nbg2_rows, split_nbg2_rows, force_splits, attn_wide_blocks, prefill_sk_rows; };
+static inline Tuning tuning(const ctts_gpt* h) {
+    if (h->batch_inv) return {true, 0, 0, 1, 0, 1, OPT_MAX, OPT_MAX, 1, OPT_MAX, 0};
+    return {false, h->persist_rows, h->valu_rows, h->split_dec_rows, h->split_rows, h->down_sk_rows, h->nbg2_rows, h->split_nbg2_rows, h->force_splits, h->attn_wide_blocks, h->prefill_sk_rows};
+}
+// the persistent weight images, built lazily before the first step that could use them is planned (outside capture: see persist_images)
+static int ensure_persist_images(ctts_gpt* h) {
+    const int rows = tuning(h).persist_rows;
+    return (h->persist_ok && h->pimg == nullptr && rows > 0 && h->B <= rows && (!h->lora_rows || h->persist_lora)) ? persist_images(h) : 0;
+}
+
 // Key splits of the decode attention for a batch of B rows whose longest context in the coming steps is L keys.
 // Cap: enough (row, head, split) blocks to cover the chip.  Measured (us/step, 256 steps from a 48-token prompt unless noted):
 //   B=1: S=1 412, 2 400, 4 392, 8 392;  L~1900: S=1 628, 2 589, 8 438        -> one row: always the cap
@@ -1128,9 +1101,9 @@ static inline void* kv_layer(ctts_gpt* h, int l, int which) {
 // in o_proj (S = 1 lets the attention write o_proj's packed operand directly): from 4 rows on, split only when one
 // 8-wave block would otherwise loop over more than ~768 keys.
 static inline int decode_splits(const ctts_gpt* h, int B, int L) {
-    if (h->batch_inv) return 1;                            // a function of neither the batch nor the longest row
+    const int forced = tuning(h).force_splits;             // (batch_invariant: 1 -- a function of neither the batch nor the longest row)
     if (h->lora_rows) return 1;                            // per-utterance LoRA reads the attention output from o_proj's packed operand (S = 1 path)
-    if (h->force_splits) return h->force_splits;
+    if (forced) return forced;
     int cap = 256 / (B * h->NH);
     cap = cap < 1 ? 1 : (cap > SMAX ? SMAX : cap);
     if (B <= 2) return cap;
@@ -1139,72 +1112,108 @@ static inline int decode_splits(const ctts_gpt* h, int B, int L) {
     return want < 1 ? 1 : (want > cap ? cap : want);
 }
 
-// What run_layers decided about the hand-off of the residual stream to whatever reads it next (the heads): one place computes the
-// predicates, the consumer uses what was actually launched.
-struct StreamForm { bool parts; bool xh; bool logits; bool split; };     // x = x_dec + dpart[0..3] (split-K down projection) / packed copy + sums of squares exist / the logits (and hidden rows) exist already / the packed copy is a head / tail fp16 pair (split_t)
+// How run_layers leaves the residual stream to whatever reads it next (the heads), and the heads' launch shape: one place computes the predicates, the consumer
+// uses what was actually launched.  parts: x = x_dec + dpart[0..3] (split-K down projection) / xh: packed copy + sums of squares exist / logits: the logits (and
+// hidden rows) exist already / split: the packed copy is a head / tail fp16 pair (split_t) / nbg, valu: the heads' block height (16 * nbg rows) and VALU form
+struct StreamForm { bool parts, xh, logits, split; int nbg, valu; };
+// decode rows per block / 16: see nbg2_rows / split_nbg2_rows (`split`: the projections read head / tail images)
+static inline int decode_nbg(const Tuning& t, int R, bool split) { return (R <= 16 || R < (split ? t.split_nbg2_rows : t.nbg2_rows)) ? 1 : 2; }
+// the heads' block height is a function of B and of whether the packed copy is a head / tail pair (the packed rows' layout does not depend on the producer's block height)
+static StreamForm stream_form(const ctts_gpt* h, bool parts, bool xh, bool logits, bool split) {
+    const Tuning t = tuning(h);
+    return {parts, xh, logits, split, decode_nbg(t, h->B, split), (h->cfg.dtype == CTTS_DTYPE_F32 && h->B <= t.valu_rows) ? 1 : 0};
+}
+static inline StreamForm plain_form(const ctts_gpt* h) { return stream_form(h, false, false, false, false); }      // after a prompt pass / a restart: fp32 rows in x_dec
 
-// 20 decoder layers on R rows of residual stream x (llama.py:719-749 per layer)
-static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* rope_rows, int R, int S, const DevState* st, hipStream_t s, StreamForm* form = nullptr) {
+// Everything run_layers decides before its layer loop, for R rows of a decode step (`decode`, on path `path`) or of a prompt pass: computed once per call by
+// plan_layers, which has no other effect; run_layers then only fills argument structs and launches.
+struct LayerPlan {
+    bool lora, lmlp;                  // per-utterance adapters: the residual stream must be materialised in x (no split-K partials) / ... on gate / up / down too: their terms come from two more lora.hip launches per layer, decode and prompt pass alike
+    int S, nbg, chunks, dts, pf_kb, valu, wide_blocks, anchor, prefill_sk_rows;      // key splits; 16 * nbg rows per block, blocks; launch_gemm's operand format; see plan_layers for the rest
+    bool splitd, prepack, pfg, pfs, xhm, spd, down_sk, fuse_heads;
+    int persist, per, pace, poll, delay_act, delay_u;      // persistent launch: key shares (0 = the launch chain), layers per launch, and its row-count defaults resolved
+    StreamForm form;
+};
+static LayerPlan plan_layers(const ctts_gpt* h, int R, bool decode, DecodePath path) {
+    LayerPlan p = {};
+    const Tuning t = tuning(h);
     const int dt = h->cfg.dtype;
-    const bool lora = h->lora_rows != 0;                   // per-utterance adapters: the residual stream must be materialised in x (no split-K partials)
-    const bool lmlp = lora && h->lora_mlp != 0;      // ... on gate / up / down too: their terms come from two more lora.hip launches per layer, decode and prompt pass alike
-    const bool inv = h->batch_inv != 0;                    // "batch_invariant": every choice below that depends on R is pinned (ctts_gpt_begin refuses adapters then)
+    p.S = path.splits; p.lora = h->lora_rows != 0; p.lmlp = p.lora && h->lora_mlp != 0;
     // fp32 engines, decode batches of >= split_decode_rows rows: head / tail fp16 operands (the predicate is completed below; it needs the packed-residual path)
-    const bool spd_ok = st != nullptr && dt == CTTS_DTYPE_F32 && h->xh_mode && h->split_ok && h->wsplit != nullptr && !lora && S == 1 &&
-                        (inv || (h->split_dec_rows > 0 && R >= h->split_dec_rows && R > h->split_rows));      // (invariant: 1..8 rows too, one padded 16-row chunk)
-    const int nbg = (R <= 16 || (st != nullptr && (inv || R < (spd_ok ? h->split_nbg2_rows : h->nbg2_rows)))) ? 1 : 2;     // decode rows: see nbg2_rows / split_nbg2_rows
-    const int NB = 16 * nbg;
-    const int chunks = (R + NB - 1) / NB;
+    const bool spd_ok = decode && dt == CTTS_DTYPE_F32 && h->xh_mode && h->split_ok && h->wsplit != nullptr && !p.lora && p.S == 1 &&
+                        t.split_dec_rows > 0 && R >= t.split_dec_rows && R > t.split_rows;
+    p.nbg = decode ? decode_nbg(t, R, spd_ok) : (R <= 16 ? 1 : 2);      // (the prompt pass keeps 32-row blocks)
+    p.chunks = (R + 16 * p.nbg - 1) / (16 * p.nbg);
     // small decode batches: the down projection is launched as 4 split-K slices (192 blocks instead of 48 x 1024 threads);
     // its partial sums dp[0..3] are added, in order, by the next consumers of the residual stream (QKV RMSNorm, o_proj
     // residual, final heads) -- deterministic, no atomics.  x itself is re-materialised by every o_proj.
-    const bool splitd = (st != nullptr) && (R <= h->split_rows) && (nbg == 1) && !lora && !inv;
+    p.splitd = decode && (R <= t.split_rows) && (p.nbg == 1) && !p.lora;
     // prompt pass over more than a few chunks: normalise every row once (norm_pack_kernel) instead of in every GEMM block
-    const bool prepack = (st == nullptr) && (nbg == 2) && (R > 64) && !h->no_prepack;
+    p.prepack = !decode && (p.nbg == 2) && (R > 64) && !h->no_prepack;
     // prompt pass over >= 1536 rows, fp16: LDS-staged 256/128 x 128 MFMA GEMM (prefill_gemm.hip) instead of one weight tile per 32-row block
     // (measured with 128 x 128 blocks, prompt pass ms with / without it: 512 rows 2.31 / 1.48, 1024 rows 2.47 / 2.29, 1536 rows 2.70 / 3.12,
     //  2048 rows 2.81 / 3.9, 3072 rows 3.6 / 5.3, 16384 rows 10.3 / 29)
-    const bool pfg = prepack && (dt == CTTS_DTYPE_F16) && h->prefill_gemm_rows > 0 && (R >= h->prefill_gemm_rows) && !lora;
+    p.pfg = p.prepack && (dt == CTTS_DTYPE_F16) && h->prefill_gemm_rows > 0 && (R >= h->prefill_gemm_rows) && !p.lora;
     // prompt pass over >= 384 rows, fp32 engine: the same tiling on the fp16 pipes with head / tail operands -- 3 MFMAs per product instead of 16,
     // fp32-level accuracy (prefill_split.hip); the attention stays the fp32 row kernel
     // (round 5: also with per-utterance adapters -- their low-rank terms come from the two lora.hip launches per layer and are added in the split GEMMs' epilogues)
     // (... and with adapters on gate / up / down: two more launches; the gate / up term rides in a SwiGLU epilogue of its own, the down term is read from the act images)
     // (invariant: every pass height, 1 row included -- the block shapes give bit-identical rows, tools/prefill_fuzz.py -- and the down projection's K never sliced)
-    const bool pfs = (dt == CTTS_DTYPE_F32) && h->wsplit != nullptr &&
-                     (inv ? (st == nullptr && h->split_ok) : (prepack && h->split_rows_min > 0 && (R >= h->split_rows_min)));
-    const float sp_scale = 1.0f / 64.0f;
-    const SplitGemmPolicy sp_pol = {h->prefill_pp_blocks, inv ? 0 : h->prefill_sk_rows, h->sk_scratch, h->sk_cap_floats, h->prefill_small_blocks, h->prefill_ring4_blocks};
+    p.pfs = (dt == CTTS_DTYPE_F32) && h->wsplit != nullptr &&
+            (t.inv ? (!decode && h->split_ok) : (p.prepack && h->split_rows_min > 0 && (R >= h->split_rows_min)));
     // decode above the split-K batch sizes: the residual stream travels between kernels as a packed B operand in the engine dtype + per-tile
     // sums of squares (EPI_RESID_XH -> PRO_XH, kernels.h); layer 0 still normalises the sampler's fp32 rows itself.  (Handing gate|up
     // the packed copy at batches <= 4 too was measured slower in fp16: batch 1 393 vs 381 us/step, 2 415 vs 403, 4 450 vs 443.)
     // fp32: the RMSNorm factor then multiplies the C tile instead of the operand -- (sum w x) rs instead of sum w (x rs), one rounding
     // apart; token ids stay bit-exact on every golden (tests/test_gpu_gpt.py)
-    const bool xhm = (st != nullptr) && h->xh_mode && !splitd;
+    p.xhm = decode && h->xh_mode && !p.splitd;
     // ... and from split_decode_rows rows on (fp32 engines) the projections read head / tail fp16 images of weights and operands: 3 fp16 MFMAs per product instead of 8
     // exact-f32 ones (common.h split_t; the prompt pass's arithmetic, prefill_split.hip).  Layer 0's q|k|v projection normalises the sampler's fp32 rows and stays exact.
-    const bool spd = xhm && spd_ok;
-    const int dts = spd ? 2 : dt;                              // launch_gemm's operand format
-    if (st != nullptr && h->cur_persist && h->pimg != nullptr && R <= PL_MAXR && !inv) {
-        // one persistent launch per layer (persist_layer.hip): the residual stream stays in x, nothing is left in partial or packed form
+    p.spd = p.xhm && spd_ok;
+    p.dts = p.spd ? 2 : dt;
+    // weight prefetch across a launch boundary of a decode step (kernels.h WPrefetch): the o_proj launch carries workgroups that pull the gate|up launch's weight image into L2
+    // (packed-residual path: every consumer workgroup column is one row tile; per-utterance adapters shift the consumers' block indices by their workers: off)
+    p.pf_kb = (p.xhm && !p.lora && (p.spd || (dt == CTTS_DTYPE_F16 && R >= 17))) ? h->prefetch_kb : 0;      // (the exact-f32 kernels lose with it: batch 32 0.845 -> 0.897)
+    p.valu = (decode && dt == CTTS_DTYPE_F32 && R <= t.valu_rows && !p.lora) ? 1 : 0;
+    // the packed-residual down projection with its K sliced 4 ways inside the launch, last arriver combines (EPI_RESID_XH_SK, kernels.h): see down_sk_rows
+    p.down_sk = (p.nbg == 1 || p.spd) && R >= t.down_sk_rows && t.down_sk_rows > 0;
+    p.wide_blocks = t.attn_wide_blocks; p.anchor = t.inv ? 1 : 0; p.prefill_sk_rows = t.prefill_sk_rows;
+    p.form = stream_form(h, p.splitd, p.xhm, false, p.spd);
+    // one persistent launch per layer (persist_layer.hip): the residual stream stays in x, nothing is left in partial or packed form
+    p.persist = (decode && h->pimg != nullptr && R <= PL_MAXR) ? path.persist : 0;
+    if (p.persist) {
         // the launch that ends the stack also runs the final norm + the 4 code heads (persist_layer.hip phase H): code mode, paced schedule, images built
         // (ms/step separate heads launch / fused, tools/ab_options.py: fp32 batch 1 0.2798 / 0.2786, 2 0.3396 / 0.3384, 4 0.4711 / 0.4721; fp16 batch 3 0.3793 / 0.3800 -> up to 2 rows)
-        const bool fuse_heads = h->persist_heads && R <= 2 && !h->text_mode && h->persist_sched == 3 && h->pimg_head != nullptr && h->dyn != nullptr;
-        if (form) { form->parts = false; form->xh = false; form->logits = fuse_heads; form->split = false; }
+        p.fuse_heads = h->persist_heads && R <= 2 && !h->text_mode && h->persist_sched == 3 && h->pimg_head != nullptr && h->dyn != nullptr;
+        p.form = stream_form(h, false, false, p.fuse_heads, false);
         // (persistent_layers_per_launch, default all: the whole stack is ONE launch; 1 = a launch per layer, the first version of the structure)
-        const int per = (h->persist_lpl > 0 && h->persist_lpl < h->L) ? h->persist_lpl : h->L;
-        for (int l = 0; l < h->L; l += per) {
+        p.per = (h->persist_lpl > 0 && h->persist_lpl < h->L) ? h->persist_lpl : h->L;
+        p.pace = h->persist_pace < 0 ? (R <= 2 ? 3 : 2) : h->persist_pace; p.poll = (h->persist_poll < 0) ? 0 : h->persist_poll;
+        p.delay_act = h->persist_delay_act + 2 * (R - 1); p.delay_u = h->persist_delay_u < 0 ? 14 + 2 * R : h->persist_delay_u;
+    }
+    return p;
+}
+
+// 20 decoder layers on R rows of residual stream x (llama.py:719-749 per layer); st != nullptr: a decode step on `path`, else a prompt pass ({1, 0})
+static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* rope_rows, int R, DecodePath path, const DevState* st, hipStream_t s, StreamForm* form = nullptr) {
+    const LayerPlan p = plan_layers(h, R, st != nullptr, path);
+    const int dt = h->cfg.dtype, S = p.S, nbg = p.nbg, NB = 16 * nbg, chunks = p.chunks, dts = p.dts;
+    const bool lora = p.lora, lmlp = p.lmlp, splitd = p.splitd, prepack = p.prepack, pfg = p.pfg, pfs = p.pfs, xhm = p.xhm, spd = p.spd;
+    if (form) *form = p.form;
+    if (p.persist) {
+        for (int l = 0; l < h->L; l += p.per) {
             PersistArgs pa = {};
-            if (fuse_heads && l + per >= h->L) {
+            if (p.fuse_heads && l + p.per >= h->L) {
                 pa.heads = 1; pa.hw = h->pimg_head; pa.logits = h->logits; pa.n_valid = h->NVQ * h->V; pa.lnf = h->lnf; pa.dyn = h->dyn; pa.rows = h->finend;
             }
-            pa.w = h->pimg + PL_LAYER_BYTES / 4 * h->esz * l; pa.half_w = h->esz == 2 ? 1 : 0; pa.n_layers = (h->L - l < per) ? h->L - l : per;
+            pa.w = h->pimg + PL_LAYER_BYTES / 4 * h->esz * l; pa.half_w = h->esz == 2 ? 1 : 0; pa.n_layers = (h->L - l < p.per) ? h->L - l : p.per;
             pa.x = x; pa.meta = meta; pa.rope_rows = rope_rows;
             pa.kv = kv_layer(h, l, 0); pa.kv_per = (size_t)h->cfg.max_batch * h->NH * h->cfg.max_seq * CTTS_HEAD_DIM; pa.Lmax = h->cfg.max_seq;
-            pa.g_qkv = h->pl_g; pa.g_att = pa.g_qkv + PL_G_QKV; pa.g_x1 = pa.g_att + PL_G_ATT; pa.g_act = pa.g_x1 + PL_G_X1; pa.g_x = pa.g_act + PL_G_ACT; pa.g_part = pa.g_x + PL_G_X; pa.S = h->cur_persist;
-            pa.epoch = h->pl_epoch; pa.error = h->pl_error; pa.done = &st->all_done; pa.ts = h->pl_ts_on ? h->pl_ts : nullptr; pa.eps = 1e-6f; pa.sched = h->persist_sched; pa.pace = h->persist_pace < 0 ? (R <= 2 ? 3 : 2) : h->persist_pace; pa.fault = h->persist_fault; pa.delay_att = h->persist_delay_att; pa.delay = h->persist_delay; pa.delay_act = h->persist_delay_act + 2 * (R - 1); pa.delay_x = h->persist_delay_x; pa.nap = h->persist_nap; pa.nap_qkv = h->persist_nap_qkv; pa.poll = (h->persist_poll < 0) ? 0 : h->persist_poll;
+            pa.g_qkv = h->pl_g; pa.g_att = pa.g_qkv + PL_G_QKV; pa.g_x1 = pa.g_att + PL_G_ATT; pa.g_act = pa.g_x1 + PL_G_X1; pa.g_x = pa.g_act + PL_G_ACT; pa.g_part = pa.g_x + PL_G_X; pa.S = p.persist;
+            pa.epoch = h->pl_epoch; pa.error = h->pl_error; pa.done = &st->all_done; pa.ts = h->pl_ts_on ? h->pl_ts : nullptr; pa.eps = 1e-6f; pa.sched = h->persist_sched; pa.pace = p.pace; pa.fault = h->persist_fault; pa.delay_att = h->persist_delay_att; pa.delay = h->persist_delay; pa.delay_act = p.delay_act; pa.delay_x = h->persist_delay_x; pa.nap = h->persist_nap; pa.nap_qkv = h->persist_nap_qkv; pa.poll = p.poll;
             if (lora) {
                 // per-utterance adapters: the rows' slots travel in the arguments (part of the decode-graph key), the operands are read from the resident tables
-                pa.lora = 1; pa.lslots = 0; pa.delay_u = h->persist_delay_u < 0 ? 14 + 2 * R : h->persist_delay_u;
+                pa.lora = 1; pa.lslots = 0; pa.delay_u = p.delay_u;
                 for (int r = 0; r < PL_MAXR; ++r) pa.lslots |= (unsigned long long)(unsigned char)(r < R ? h->lora_row_slots[r] : -1) << (8 * r);
                 pa.la_qkv_stride = (size_t)CTTS_MAX_ADAPTERS * 3 * 16 * h->H; pa.la_stride = (size_t)CTTS_MAX_ADAPTERS * 4 * 16 * h->H;
                 pa.la_qkv = h->lora_Af + pa.la_qkv_stride * l; pa.la = h->lora_A + pa.la_stride * l; pa.lb = h->lora_B + pa.la_stride * l;
@@ -1214,14 +1223,12 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
         }
         return 0;
     }
-    if (form) { form->parts = splitd; form->xh = xhm; form->logits = false; form->split = spd; }
-    // weight prefetch across a launch boundary of a decode step (kernels.h WPrefetch): the o_proj launch carries workgroups that pull the gate|up launch's weight image into L2
-    // (packed-residual path: every consumer workgroup column is one row tile; per-utterance adapters shift the consumers' block indices by their workers: off)
-    const int pf_kb = (st != nullptr && xhm && !lora && (spd || (dt == CTTS_DTYPE_F16 && R >= 17))) ? h->prefetch_kb : 0;      // (the exact-f32 kernels lose with it: batch 32 0.845 -> 0.897)
+    const float sp_scale = 1.0f / 64.0f;
+    const SplitGemmPolicy sp_pol = {h->prefill_pp_blocks, p.prefill_sk_rows, h->sk_scratch, h->sk_cap_floats, h->prefill_small_blocks, h->prefill_ring4_blocks};
     auto set_pf = [&](GemmArgs& g, const void* w, int n_tiles, int K, int fmt) {          // fmt: 0 fp32 tiles, 1 fp16 tiles, 2 head / tail pairs
-        if (pf_kb <= 0 || w == nullptr) return;
+        if (p.pf_kb <= 0 || w == nullptr) return;
         const size_t tile = (size_t)16 * K * (fmt == 1 ? 2 : 4);
-        size_t nb = (tile * n_tiles + (size_t)pf_kb * 1024 - 1) / ((size_t)pf_kb * 1024);
+        size_t nb = (tile * n_tiles + (size_t)p.pf_kb * 1024 - 1) / ((size_t)p.pf_kb * 1024);
         nb = (nb + 7) & ~(size_t)7;
         nb = nb < 8 ? 8 : (nb > 256 ? 256 : nb);
         g.pf.ptr = w; g.pf.unit_bytes = (unsigned)tile; g.pf.n_units = (unsigned)n_tiles; g.pf_blocks = (int)nb;
@@ -1230,7 +1237,7 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
     for (int l = 0; l < h->L; ++l) {
         GemmArgs a = {};
         a.st = st; a.R = R; a.eps = 1e-6f; a.meta = meta; a.Lmax = h->cfg.max_seq; a.sat = h->sat;
-        a.valu = (st != nullptr && dt == CTTS_DTYPE_F32 && R <= h->valu_rows && !lora && !inv) ? 1 : 0;
+        a.valu = p.valu;
         // RMSNorm + QKV + RoPE + KV append
         GemmArgs g1 = a;
         g1.W = h->lw[l].qkv; g1.n_row_tiles = 3 * h->H / 16; g1.K = h->H; g1.x = x;
@@ -1266,8 +1273,7 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
         } else if (launch_gemm(dt, nbg, splitd ? PRO_NORM_P : PRO_NORM, EPI_QKV, g1, chunks, s)) return 1;
         AttnArgs at = {};
         at.q = h->q_buf; at.k_cache = g1.k_cache; at.v_cache = g1.v_cache; at.Lmax = h->cfg.max_seq; at.NH = h->NH; at.R = R; at.S = S;
-        at.meta = meta; at.st = st; at.part_ml = h->part_ml; at.part_o = h->part_o; at.wide_blocks = inv ? 0x7FFFFFFF : h->attn_wide_blocks;
-        at.anchor = inv ? 1 : 0;
+        at.meta = meta; at.st = st; at.part_ml = h->part_ml; at.part_o = h->part_o; at.wide_blocks = p.wide_blocks; at.anchor = p.anchor;
         if (st == nullptr) { at.T = h->pre_T; at.row0 = (int)(meta - h->meta_pre); }       // prompt pass: position of this pass in the flattened [B][T] prompt
         at.packed_out = (S == 1) ? h->attn_packed : nullptr; at.nbg = nbg; at.packed_split = spd ? 1 : 0;
         if (pfs && S == 1) { if (launch_attention_split(at, h->sp_x_hi, h->sp_x_lo, s)) return 1; }      // writes o_proj's head / tail operand images directly
@@ -1337,8 +1343,7 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
         } else if (xhm) {                          // (the last layer's copy is for the heads: run_heads)
             g4.xh = h->xh; g4.ssq = h->ssq; g4.scale_in = h->scale_d;
             if (spd) g4.W = h->lw[l].d_sp;
-            if (inv || ((nbg == 1 || spd) && R >= h->down_sk_rows && h->down_sk_rows > 0)) {
-                // K sliced 4 ways inside the launch, last arriver combines (EPI_RESID_XH_SK, kernels.h)
+            if (p.down_sk) {
                 g4.ktiles_total = h->I / ((h->esz == 2 || spd) ? 32 : 16); g4.sk_slab = h->sk_slab; g4.sk_cnt = h->sk_cnt;
                 if (launch_gemm(dts, nbg, PRO_PACKED, EPI_RESID_XH_SK, g4, chunks, s)) return 1;
             } else if (launch_gemm(dts, nbg, PRO_PACKED, EPI_RESID_XH, g4, chunks, s)) return 1;
@@ -1346,14 +1351,12 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
     }
     return 0;
 }
-
-// final RMSNorm + heads on the h->B decode rows; `form` = how the last run_layers left them (all false after a prompt pass / restart)
+// final RMSNorm + heads on the h->B decode rows; `form` = how the last run_layers left them (plain_form after a prompt pass / restart)
 static int run_heads(ctts_gpt* h, bool write_hidden, StreamForm form, hipStream_t s) {
-    const int nbg = (h->B <= 16 || h->batch_inv || h->B < (form.split ? h->split_nbg2_rows : h->nbg2_rows)) ? 1 : 2;      // (the packed rows' layout does not depend on the producer's block height)
-    const int chunks = (h->B + 16 * nbg - 1) / (16 * nbg);
+    const int nbg = form.nbg, chunks = (h->B + 16 * nbg - 1) / (16 * nbg);
     GemmArgs a = {};
     a.st = h->st; a.R = h->B; a.eps = 1e-6f; a.meta = h->meta_dec;
-    a.valu = (h->cfg.dtype == CTTS_DTYPE_F32 && h->B <= h->valu_rows && !h->batch_inv) ? 1 : 0;
+    a.valu = form.valu;
     const int nv = h->text_mode ? h->vocab_text_head : h->NVQ * h->V;
     a.W = h->text_mode ? h->whead_text : h->whead; a.n_row_tiles = (nv + 15) / 16; a.K = h->H; a.x = h->x_dec; a.lnw = h->lnf;
     a.logits = h->logits; a.n_valid = nv;
@@ -1522,7 +1525,7 @@ static int prefill_invariant(ctts_gpt* h, const float* emb, hipStream_t s) {
                 r += len;
             }
         }
-        if (run_layers(h, h->x_pre, h->meta_pre + r0, h->rope_pre + (size_t)r0 * 64, n, 1, nullptr, s)) return 1;
+        if (run_layers(h, h->x_pre, h->meta_pre + r0, h->rope_pre + (size_t)r0 * 64, n, DecodePath{1, 0}, nullptr, s)) return 1;
     }
     CTTS_HIP_CHECK(hipMemcpy2DAsync(h->x_dec, (size_t)H * 4, emb + (size_t)Tm * H, (size_t)T * H * 4, (size_t)H * 4, B, hipMemcpyDeviceToDevice, s));
     CTTS_HIP_CHECK(hipMemcpyAsync(h->x_last, h->x_dec, (size_t)B * H * 4, hipMemcpyDeviceToDevice, s));       // (ensure_non_empty restarts replay from here)
@@ -1539,7 +1542,7 @@ extern "C" int ctts_gpt_prefill(ctts_gpt* h, const float* emb, void* stream) {
     for (int r0 = 0; r0 < R; r0 += PASS_ROWS) {
         const int n = (R - r0 < PASS_ROWS) ? R - r0 : PASS_ROWS;
         CTTS_HIP_CHECK(hipMemcpyAsync(h->x_pre, emb + (size_t)r0 * h->H, (size_t)n * h->H * 4, hipMemcpyDeviceToDevice, s));
-        if (run_layers(h, h->x_pre, h->meta_pre + r0, h->rope_pre + (size_t)r0 * 64, n, 1, nullptr, s)) return 1;
+        if (run_layers(h, h->x_pre, h->meta_pre + r0, h->rope_pre + (size_t)r0 * 64, n, DecodePath{1, 0}, nullptr, s)) return 1;
         // rows (b, T-1) that live in this pass -> x_dec[b]  (indices computed on the device: the call stays asynchronous)
         if (launch_gather_last_rows(h->x_pre, h->x_dec, h->B, h->T, r0, n, h->H, s)) return 1;
     }
@@ -1575,10 +1578,10 @@ extern "C" int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* mask, co
     h->text_mode = 0;
     if (seat_row_adapters(h, B, "score", s)) return 1;
     const int NV = h->NVQ * h->V;
-    if (h->score_oidx == nullptr) {                // (every byte is written before it is read: no fill)
-        if (!h->score_x) CTTS_HIP_CHECK(hipMalloc((void**)&h->score_x, (size_t)SCORE_ROWS * h->H * 4));
-        if (!h->score_logits) CTTS_HIP_CHECK(hipMalloc((void**)&h->score_logits, (size_t)SCORE_ROWS * NV * 4));
-        CTTS_HIP_CHECK(hipMalloc((void**)&h->score_oidx, (size_t)SCORE_ROWS * 4));
+    if (h->score_oidx == nullptr) {
+        if (!h->score_x && dev_alloc(h, (void**)&h->score_x, (size_t)SCORE_ROWS * h->H * 4)) return 1;
+        if (!h->score_logits && dev_alloc(h, (void**)&h->score_logits, (size_t)SCORE_ROWS * NV * 4)) return 1;
+        if (dev_alloc(h, (void**)&h->score_oidx, (size_t)SCORE_ROWS * 4)) return 1;
         h->score_bytes = (size_t)SCORE_ROWS * (h->H + NV + 1) * 4;
     }
     // entries j >= n_b: logprob 0, argmax -1
@@ -1594,7 +1597,7 @@ extern "C" int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* mask, co
     for (long r0 = 0; r0 < R; r0 += h->pass_rows) {
         const int n = (int)(R - r0 < h->pass_rows ? R - r0 : h->pass_rows);
         CTTS_HIP_CHECK(hipMemcpyAsync(h->x_pre, emb + (size_t)r0 * h->H, (size_t)n * h->H * 4, hipMemcpyDeviceToDevice, s));
-        if (run_layers(h, h->x_pre, h->meta_pre + r0, h->rope_pre + (size_t)r0 * 64, n, 1, nullptr, s)) return 1;
+        if (run_layers(h, h->x_pre, h->meta_pre + r0, h->rope_pre + (size_t)r0 * 64, n, DecodePath{1, 0}, nullptr, s)) return 1;
         // the scored rows of this pass: sequence b's rows [b T + T - n_b, b T + T) clipped to [r0, r0 + n)
         sr.cum[0] = 0;
         for (int b = 0; b < B; ++b) {
@@ -1618,8 +1621,8 @@ extern "C" int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* mask, co
     return 0;
 }
 
-static inline int pick_decode_path(ctts_gpt* h, int longest);
-static int run_decode_step(ctts_gpt* h, hipStream_t s);
+static int run_decode_step(ctts_gpt* h, DecodePath path, hipStream_t s);
+static inline DecodePath pick_decode_path(const ctts_gpt* h, int longest);
 
 // Log-probs of the sampled ids (include/ctts_hip.h): the two destinations are the last words of the per-call block the sampler reads (SamplerDyn), so a
 // captured decode graph serves calls with and without them; begin's rewrite of the block leaves both null.
@@ -1638,10 +1641,10 @@ extern "C" int ctts_gpt_sample(ctts_gpt* h, void* stream) {
     CTTS_RANGE("ctts_gpt_sample");
     h->sampled = true;
     if (h->batch_inv) {          // the last prompt token's layer pass first (see prefill_invariant): a decode step
-        if (pick_decode_path(h, 0)) return 1;
-        return run_decode_step(h, (hipStream_t)stream);
+        if (ensure_persist_images(h)) return 1;
+        return run_decode_step(h, pick_decode_path(h, 0), (hipStream_t)stream);
     }
-    return run_sample_phase(h, StreamForm{false, false, false, false}, (hipStream_t)stream);
+    return run_sample_phase(h, plain_form(h), (hipStream_t)stream);
 }
 
 extern "C" int ctts_gpt_restart(ctts_gpt* h, void* stream) {
@@ -1673,7 +1676,8 @@ static int advance_rows(ctts_gpt* h, int n_steps) {
 // PL_SMAX; a context beyond twice that many prefetchable keys goes back to the launch chain (its attention spreads the keys over up to 96 workgroups).
 // Asked once per step (plan_decode): L is that step's longest context, so a step's share count does not depend on how its decode call was chunked.
 static inline int decode_persist(const ctts_gpt* h, int B, int L) {
-    if (!(h->persist_rows > 0 && h->pimg != nullptr && B <= h->persist_rows && B <= PL_MAXR)) return 0;
+    const int rows = tuning(h).persist_rows;               // (batch_invariant: 0 -- the launch chain at every row count)
+    if (!(rows > 0 && h->pimg != nullptr && B <= rows && B <= PL_MAXR)) return 0;
     if (h->lora_rows && h->lora_mlp) return 0;             // ... on the MLP projections: the launch carries q/k/v/o terms only (ctts_hip.h "persistent_lora")
     if (h->lora_rows && !(h->persist_lora && h->persist_sched == 3 && h->lora_Af != nullptr && h->H == PL_H)) return 0;      // per-utterance adapters ride inside the launch (round 6, paced schedule)
     int cap = PL_ATT_BLOCKS / (PL_NH * B);
@@ -1697,13 +1701,7 @@ static inline int decode_persist(const ctts_gpt* h, int B, int L) {
     return want > cap ? cap : want;
 }
 
-static inline int pick_decode_path(ctts_gpt* h, int longest) {
-    h->cur_splits = decode_splits(h, h->B, longest);
-    if (h->batch_inv) { h->cur_persist = 0; return 0; }      // the launch chain at every row count
-    if (h->persist_ok && h->pimg == nullptr && h->persist_rows > 0 && h->B <= h->persist_rows && (!h->lora_rows || h->persist_lora) && persist_images(h)) return 1;
-    h->cur_persist = decode_persist(h, h->B, longest);
-    return 0;
-}
+static inline DecodePath pick_decode_path(const ctts_gpt* h, int longest) { return {decode_splits(h, h->B, longest), decode_persist(h, h->B, longest)}; }
 
 // Persistent launches of ONE process on one device take turns.  Each needs all 256 workgroups resident; two of them enqueued on different streams (two engines, two
 // threads: a base engine and a LoRA-merged sibling, two pipelines) could each be given a share of the CUs and wait for the other's until both give up.  The
@@ -1746,20 +1744,20 @@ struct PersistTurnGuard {
     }
 };
 
-static int run_decode_step(ctts_gpt* h, hipStream_t s) {
-    StreamForm form = {false, false, false, false};
-    if (run_layers(h, h->x_dec, h->meta_dec, h->rope_dec, h->B, h->cur_splits, h->st, s, &form)) return 1;
+static int run_decode_step(ctts_gpt* h, DecodePath path, hipStream_t s) {
+    StreamForm form = {};
+    if (run_layers(h, h->x_dec, h->meta_dec, h->rope_dec, h->B, path, h->st, s, &form)) return 1;
     return run_sample_phase(h, form, s);            // the heads add dpart[0..3] / read the packed copy; the sampler then re-materialises x_dec
 }
 
-// steps per replay of the current decode path, given `left` steps to launch: the long graph of the persistent paths while it fits, else the short one
-static int graph_span(const ctts_gpt* h, int left) {
-    return (h->cur_persist && h->graph_steps_persist > h->graph_steps && left >= h->graph_steps_persist) ? h->graph_steps_persist : h->graph_steps;
+// steps per replay of a decode path, given `left` steps to launch: the long graph of the persistent paths while it fits, else the short one
+static int graph_span(const ctts_gpt* h, DecodePath path, int left) {
+    return (path.persist && h->graph_steps_persist > h->graph_steps && left >= h->graph_steps_persist) ? h->graph_steps_persist : h->graph_steps;
 }
 
-static int ensure_graph(ctts_gpt* h, int n_steps) {
+static int ensure_graph(ctts_gpt* h, DecodePath path, int n_steps) {
     char sig[160];
-    snprintf(sig, sizeof(sig), "%d|%d|%p|%d|%d|%d|%d|%d", h->B, h->text_mode, (void*)h->kv, h->cur_splits, h->lora_rows + 2 * h->lora_mlp, h->opt_gen, h->cur_persist, n_steps);      // (diagnostic switches are fixed at create)
+    snprintf(sig, sizeof(sig), "%d|%d|%p|%d|%d|%d|%d|%d", h->B, h->text_mode, (void*)h->kv, path.splits, h->lora_rows + 2 * h->lora_mlp, h->opt_gen, path.persist, n_steps);      // (diagnostic switches are fixed at create)
     std::string key(sig);
     if (h->lora_rows) key.append((const char*)h->lora_row_slots, (size_t)h->B);      // the rows' adapter slots are kernel arguments of the folded launches (LoraFold)
     if (h->graph_gen != h->opt_gen || h->graphs.size() >= 96) {
@@ -1777,7 +1775,7 @@ static int ensure_graph(ctts_gpt* h, int n_steps) {
     ctts_gpt::GraphEntry ge = {nullptr, nullptr};
     CTTS_HIP_CHECK(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
     int rc = 0;
-    for (int i = 0; i < n_steps && !rc; ++i) rc = run_decode_step(h, h->cap_stream);
+    for (int i = 0; i < n_steps && !rc; ++i) rc = run_decode_step(h, path, h->cap_stream);
     hipError_t e = hipStreamEndCapture(h->cap_stream, &ge.graph);
     if (rc) { if (ge.graph) (void)hipGraphDestroy(ge.graph); return 1; }
     if (e != hipSuccess) { ctts_set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); return 1; }
@@ -1791,31 +1789,28 @@ static int ensure_graph(ctts_gpt* h, int n_steps) {
 // The decode path of every coming step (key splits, persistent share count) from THAT step's context alone: step i of the next n_steps sees the longest
 // row after i steps (what a call of i steps would pick).  A generation then runs the same kernels at every step however its caller chunks the calls (one
 // 512-step call used to run all its steps with the share count of its LAST context).  Consecutive steps with equal paths form one segment.
-static int plan_decode(ctts_gpt* h, int n_steps) {
+static void plan_decode(ctts_gpt* h, int n_steps) {
     h->segs.clear();
     for (int i = 1; i <= n_steps; ++i) {
         int longest = 1;
         for (int r = 0; r < h->B; ++r) { const int c = std::min(h->row_ctx[r] + i, h->row_cap[r]); if (c > longest) longest = c; }
-        if (pick_decode_path(h, longest + 1)) return 1;
-        if (!h->segs.empty() && h->segs.back().splits == h->cur_splits && h->segs.back().persist == h->cur_persist) ++h->segs.back().n;
-        else h->segs.push_back({1, h->cur_splits, h->cur_persist});
+        const DecodePath path = pick_decode_path(h, longest + 1);
+        if (!h->segs.empty() && h->segs.back().path.splits == path.splits && h->segs.back().path.persist == path.persist) ++h->segs.back().n;
+        else h->segs.push_back({1, path});
     }
-    return 0;
 }
 
 // one segment's steps: whole graph spans as replays, the rest (at most graph_steps - 1 steps) eagerly; launch = false: only capture the graphs
 static int run_segment(ctts_gpt* h, const ctts_gpt::DecodeSeg& sg, bool graphs, bool launch, hipStream_t s) {
-    h->cur_splits = sg.splits;
-    h->cur_persist = sg.persist;
     int left = sg.n;
     if (graphs) {
         while (left >= h->graph_steps) {
-            const int span = graph_span(h, left);
-            if (ensure_graph(h, span)) return 1;
+            const int span = graph_span(h, sg.path, left);
+            if (ensure_graph(h, sg.path, span)) return 1;
             for (; left >= span; left -= span) if (launch) CTTS_HIP_CHECK(hipGraphLaunch(h->gexec, s));
         }
     }
-    if (launch) for (; left > 0; --left) if (run_decode_step(h, s)) return 1;
+    if (launch) for (; left > 0; --left) if (run_decode_step(h, sg.path, s)) return 1;
     return 0;
 }
 
@@ -1824,12 +1819,13 @@ extern "C" int ctts_gpt_decode(ctts_gpt* h, int n_steps, int use_graph, void* st
     CTTS_RANGE("ctts_gpt_decode");              // reference: nvtx "forward" per decode step + "execute" (trt_models/predictor.py:164)
     hipStream_t s = (hipStream_t)stream;
     h->sampled = true;
-    if (n_steps < 1) { h->launched += n_steps; return pick_decode_path(h, advance_rows(h, n_steps) + 1); }
-    if (plan_decode(h, n_steps)) return 1;
+    if (ensure_persist_images(h)) return 1;
+    if (n_steps < 1) { h->launched += n_steps; (void)advance_rows(h, n_steps); return 0; }
+    plan_decode(h, n_steps);
     (void)advance_rows(h, n_steps);
     h->launched += n_steps;
     bool persistent = false;
-    for (const auto& sg : h->segs) persistent = persistent || sg.persist != 0;
+    for (const auto& sg : h->segs) persistent = persistent || sg.path.persist != 0;
     PersistTurnGuard turn(persistent, s);
     if (turn.rc) { ctts_set_error("decode: hipStreamWaitEvent failed"); return 1; }
     for (const auto& sg : h->segs) if (run_segment(h, sg, use_graph != 0, true, s)) return 1;
@@ -1990,7 +1986,7 @@ extern "C" int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, co
         CTTS_HIP_CHECK(hipMemcpy2DAsync(h->x_pre, (size_t)(T - 1) * h->H * 4, emb, (size_t)T * h->H * 4, (size_t)(T - 1) * h->H * 4, n, hipMemcpyDeviceToDevice, s));
         const int keepT = h->pre_T;
         h->pre_T = T - 1;
-        const int rc = run_layers(h, h->x_pre, h->meta_pre, h->rope_pre, R, 1, nullptr, s);
+        const int rc = run_layers(h, h->x_pre, h->meta_pre, h->rope_pre, R, DecodePath{1, 0}, nullptr, s);
         h->pre_T = keepT;
         if (rc) return 1;
     }
@@ -2103,7 +2099,8 @@ extern "C" int ctts_gpt_time_decode(ctts_gpt* h, int n_steps, float* ms_per_step
     // before the clock starts
     n_steps = (n_steps + h->graph_steps - 1) / h->graph_steps * h->graph_steps;
     h->sampled = true;
-    if (plan_decode(h, n_steps)) return 1;
+    if (ensure_persist_images(h)) return 1;
+    plan_decode(h, n_steps);
     for (const auto& sg : h->segs) if (run_segment(h, sg, true, false, s)) return 1;
     CTTS_HIP_CHECK(hipEventRecord(h->ev0, s));
     for (const auto& sg : h->segs) if (run_segment(h, sg, true, true, s)) return 1;

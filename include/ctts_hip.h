@@ -139,7 +139,7 @@ void ctts_gpt_destroy(ctts_gpt* h);
  *       sequences' padding and the pass boundaries (the prompt pass pinned as above, the code heads on 16-row chunks at every row count).
  * Unknown names are an error. */
 int ctts_gpt_set_option(ctts_gpt* h, const char* name, int value);
-int ctts_gpt_get_option(ctts_gpt* h, const char* name, int* value);      /* the EFFECTIVE value ("persistent_rows" reads 0 where the mode is unavailable) */
+int ctts_gpt_get_option(ctts_gpt* h, const char* name, int* value);      /* every option that can be set can be read; the EFFECTIVE value ("persistent_rows" reads 0 where the mode is unavailable) */
 
 /* Diagnostics (tools/persist_probe.py): copies a named internal buffer to HOST memory -- "x_dec", "q_buf", "logits", "pl_g" (the persistent
  * layer's granule buffers), "pl_ts" (its per-workgroup phase marks, option "persistent_timestamps"), "pl_state" ({epoch, error}), "xh" / "ssq" (the packed residual copy and its per-tile sums of squares).  Synchronises. */
