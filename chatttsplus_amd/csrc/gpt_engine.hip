@@ -264,6 +264,13 @@ struct ctts_gpt {
     // allocated by the first score call (engines that never score keep their footprint)
     float *score_x = nullptr, *score_logits = nullptr; int* score_oidx = nullptr;
     size_t score_bytes = 0;
+    // shared prompt passes (ctts_gpt_share_prompts; kv_share.hip)
+    std::vector<int> share_req;                  //   the pending request: prompt of every sequence of the NEXT begin / admit (empty = none); consumed by that call
+    int share_req_P = 0;                         //   ... and its number of prompts
+    std::vector<int> share_tab;                  //   host image of share_dev for the call that consumed it (kernels.h SH_*)
+    int* share_dev = nullptr;                    //   device table [SH_INTS], allocated by the first ctts_gpt_share_prompts
+    int share_P = 0;                             //   prompts of the current ctts_gpt_begin (0 = every sequence runs its own prompt); read by ctts_gpt_prefill
+    int share_groups = 0;                        //   prompts with at least one follower
     std::vector<void*> owned;                    // every device buffer of the engine (dev_alloc)
 };
 #define SCORE_ROWS 2048       // scored rows per heads launch: bounds the logits scratch (2048 x 2504 fp32 = 20.5 MB)
@@ -1428,13 +1435,81 @@ static int seat_row_adapters(ctts_gpt* h, int B, const char* who, hipStream_t s)
     return 0;
 }
 
+// Shared prompt passes: sequences that name one prompt run it through the prompt pass once, in the lane of the first of them; kv_share.hip hands the others a copy.
+extern "C" int ctts_gpt_share_prompts(ctts_gpt* h, int n, const int32_t* prompt_of, int n_prompts) {
+    if (!h) { ctts_set_error("share_prompts: null handle"); return 1; }
+    h->share_req.clear(); h->share_req_P = 0;
+    if (!prompt_of || n == 0) return 0;
+    if (n < 1 || n > h->cfg.max_batch || n_prompts < 1 || n_prompts > n) {
+        ctts_set_error("share_prompts: n=%d sequences (max_batch %d) on n_prompts=%d prompts: need 1 <= n_prompts <= n <= max_batch", n, h->cfg.max_batch, n_prompts);
+        return 1;
+    }
+    std::vector<char> named(n_prompts, 0);
+    for (int i = 0; i < n; ++i) {
+        if (prompt_of[i] < 0 || prompt_of[i] >= n_prompts) { ctts_set_error("share_prompts: prompt_of[%d]=%d outside 0..%d", i, prompt_of[i], n_prompts - 1); return 1; }
+        named[prompt_of[i]] = 1;
+    }
+    for (int p = 0; p < n_prompts; ++p) if (!named[p]) { ctts_set_error("share_prompts: prompt %d is named by no sequence", p); return 1; }
+    if (!h->share_dev && dev_alloc(h, (void**)&h->share_dev, (size_t)SH_INTS * 4)) return 1;
+    h->share_req.assign(prompt_of, prompt_of + n);
+    h->share_req_P = n_prompts;
+    return 0;
+}
+// the table of one call (kernels.h SH_*): `lanes[i]` = KV lane of the call's i-th sequence.  The prompt pass runs under the leader's adapter slot, so a group shares one slot or none.
+static int share_plan(ctts_gpt* h, const std::vector<int>& prompt_of, int P, const int* lanes, const char* who, hipStream_t s) {
+    const int n = (int)prompt_of.size();
+    std::vector<int>& t = h->share_tab;
+    t.assign(SH_INTS, 0);
+    for (int p = 0; p < P; ++p) t[SH_LEADER + p] = -1;
+    for (int i = 0; i < n; ++i) {
+        const int p = prompt_of[i];
+        t[SH_PROMPT + i] = p;
+        if (t[SH_LEADER + p] < 0) t[SH_LEADER + p] = i;
+        const int ld = t[SH_LEADER + p];
+        t[SH_LEAD_OF + i] = ld;
+        if (!h->lora_slot_host.empty() && h->lora_slot_host[lanes[i]] != h->lora_slot_host[lanes[ld]]) {
+            ctts_set_error("%s: sequences %d and %d share prompt %d (ctts_gpt_share_prompts) but carry different adapter slots (%d, %d); the prompt pass depends on the adapter: "
+                           "a group shares one slot or none", who, ld, i, p, h->lora_slot_host[lanes[ld]], h->lora_slot_host[lanes[i]]);
+            return 1;
+        }
+    }
+    int G = 0, nf = 0;
+    for (int p = 0; p < P; ++p) {
+        const int ld = t[SH_LEADER + p], first = nf;
+        for (int i = 0; i < n; ++i) if (prompt_of[i] == p && i != ld) t[SH_FOLLOWERS + nf++] = lanes[i];
+        if (nf == first) continue;
+        t[SH_GROUPS + 3 * G] = lanes[ld]; t[SH_GROUPS + 3 * G + 1] = first; t[SH_GROUPS + 3 * G + 2] = nf - first;
+        ++G;
+    }
+    h->share_groups = G;
+    CTTS_HIP_CHECK(hipMemcpyAsync(h->share_dev, t.data(), (size_t)SH_INTS * 4, hipMemcpyHostToDevice, s));      // pageable source: staged before the call returns
+    return 0;
+}
+// the leaders' prompt span [0, span) of the cache -> their followers' lanes, after the last prompt pass of the call, in stream order
+static int share_kv(ctts_gpt* h, int span, hipStream_t s) {
+    if (h->share_groups == 0 || span <= 0) return 0;
+    KvShareArgs a = {};
+    a.kv = h->kv; a.run_bytes = (size_t)h->cfg.max_seq * CTTS_HEAD_DIM * h->esz; a.lane_bytes = a.run_bytes * h->NH; a.plane_bytes = a.lane_bytes * h->cfg.max_batch;
+    a.groups = h->share_dev + SH_GROUPS; a.followers = h->share_dev + SH_FOLLOWERS; a.n_groups = h->share_groups; a.NH = h->NH;
+    a.units = (unsigned)((size_t)span * CTTS_HEAD_DIM * h->esz / 16);
+    return launch_kv_share(a, h->L * 2 * h->NH, s);
+}
+
 extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, const ctts_sampler_cfg* sc, const ctts_gen_io* io, void* stream) {
+    // what ctts_gpt_share_prompts named is for THIS call only, whether it goes through or fails below
+    std::vector<int> share;
+    int share_P = 0;
+    if (h) { share.swap(h->share_req); share_P = h->share_req_P; h->share_req_P = 0; }
     if (!h || !h->finalized || !h->kv || !h->rope) { ctts_set_error("begin: handle not ready (finalize / bind_kv / set_rope)"); return 1; }
     if (!mask || !sc || !io || !io->ids || !io->finish || !io->end_idx) { ctts_set_error("begin: null argument"); return 1; }
     CTTS_RANGE("ctts_gpt_begin");               // reference: nvtx "adjust_buffer" / "set_tensors" (trt_models/predictor.py:142,159)
     if (B < 1 || B > h->cfg.max_batch || T < 1 || T + sc->max_new_token > h->cfg.max_seq) {
         ctts_set_error("begin: B=%d T=%d max_new=%d exceed max_batch=%d / max_seq=%d", B, T, sc->max_new_token, h->cfg.max_batch, h->cfg.max_seq);
         return 1;
+    }
+    if (!share.empty()) {
+        if ((int)share.size() != B) { ctts_set_error("begin: ctts_gpt_share_prompts named the prompts of %d sequences, this call has B=%d", (int)share.size(), B); return 1; }
+        if (sc->infer_text) { ctts_set_error("begin: shared prompt passes (ctts_gpt_share_prompts) are code mode only; the refine-text pass (infer_text) runs every prompt"); return 1; }
     }
     h->text_mode = sc->infer_text ? 1 : 0;
     if (h->text_mode) {
@@ -1470,6 +1545,12 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
     h->row_seq.resize(B); h->row_ctx.assign(B, T); h->row_cap.resize(B);
     for (int b = 0; b < B; ++b) { h->row_seq[b] = b; h->row_cap[b] = T + h->rows_host[b].limit; }
     if (seat_row_adapters(h, B, "begin", s)) return 1;
+    h->share_P = 0; h->share_groups = 0;
+    if (!share.empty()) {       // sequence b sits in row b and KV lane b
+        if (share_plan(h, share, share_P, h->row_seq.data(), "begin", s)) { h->B = 0; return 1; }
+        h->share_P = share_P;
+    }
+    const int* share_dev = h->share_P ? h->share_dev : nullptr;
     h->pre_T = T;
     h->io.utt_ids = nullptr; h->io.row_limits = nullptr;      // host arrays are consumed here, not kept
     h->sc = cfg_of_abi(*sc);
@@ -1483,7 +1564,7 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
     for (int b = 0; b < B && b < (int)h->knobs_req.size(); ++b) h->knobs_host[b] = h->knobs_req[b];
     h->knobs_admit.clear();
     CTTS_HIP_CHECK(hipMemcpyAsync(h->knobs, h->knobs_host.data(), (size_t)B * sizeof(RowSampling), hipMemcpyHostToDevice, s));
-    if (launch_fill_meta(h->meta_pre, h->meta_dec0, h->st, mask, B, T, h->rope, h->rope_pre, s)) return 1;
+    if (launch_fill_meta(h->meta_pre, h->meta_dec0, h->st, mask, B, T, h->rope, h->rope_pre, share_dev, h->share_P ? h->share_P : B, s)) return 1;
     if (h->batch_inv) {
         // the prompt is laid out like an admission of every row (ctts_gpt_admit): T - 1 prompt rows per sequence for the prompt pass, the decode rows at the last
         // token (slot T - 1: the same RowMeta as meta_dec0) with its RoPE row -- ctts_gpt_prefill fills x_dec with the last tokens' embeddings
@@ -1495,7 +1576,7 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
         AdmitArgs a = {};
         a.mask = mask; a.emb = nullptr; a.rows = h->keep_dev; a.seqs = h->keep_dev; a.fresh = h->cfin; a.n = B; a.T = T; a.H = h->H;
         a.pm = h->meta_pre; a.rope_pre = h->rope_pre; a.dm = h->meta_dec; a.rope_dec = h->rope_dec; a.x_dec = h->x_dec; a.ring = h->hist_ring; a.finend = h->finend;
-        a.rope = h->rope; a.st = h->st; a.finish = io->finish; a.end_idx = io->end_idx; a.begin = 1;
+        a.rope = h->rope; a.st = h->st; a.finish = io->finish; a.end_idx = io->end_idx; a.begin = 1; a.share = share_dev;
         if (launch_admit_rows(a, s)) return 1;
         CTTS_HIP_CHECK(hipMemcpyAsync(h->rope_dec0, h->rope_dec, (size_t)B * 64 * 4, hipMemcpyDeviceToDevice, s));
     }
@@ -1506,10 +1587,11 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
 
 // batch_invariant prompt pass: the first T - 1 tokens of every sequence, laid out [B][T - 1] (ctts_gpt_begin), in passes of at most pass_rows rows; the last
 // token's embedding becomes the decode row's input, which ctts_gpt_sample runs through the first layer pass -- the admission path (ctts_gpt_admit), so a begun
-// utterance and an admitted one take the same arithmetic
+// utterance and an admitted one take the same arithmetic.  Shared prompt passes: emb and the layout are per PROMPT ([P][T - 1] rows in the leaders' lanes); every
+// sequence takes its prompt's last embedding, the followers a copy of the span [0, T - 1)
 static int prefill_invariant(ctts_gpt* h, const float* emb, hipStream_t s) {
-    const int B = h->B, T = h->T, Tm = T - 1, H = h->H;
-    const long R = (long)B * Tm;
+    const int B = h->B, T = h->T, Tm = T - 1, H = h->H, P = h->share_P ? h->share_P : B;
+    const long R = (long)P * Tm;
     for (long r0 = 0; r0 < R; r0 += h->pass_rows) {
         const int n = (int)(R - r0 < h->pass_rows ? R - r0 : h->pass_rows);
         for (long r = r0; r < r0 + n;) {             // x_pre[0, n) <- prompt rows r0 .. r0 + n - 1 of the [B][T - 1] layout (emb is [B][T])
@@ -1527,7 +1609,10 @@ static int prefill_invariant(ctts_gpt* h, const float* emb, hipStream_t s) {
         }
         if (run_layers(h, h->x_pre, h->meta_pre + r0, h->rope_pre + (size_t)r0 * 64, n, DecodePath{1, 0}, nullptr, s)) return 1;
     }
-    CTTS_HIP_CHECK(hipMemcpy2DAsync(h->x_dec, (size_t)H * 4, emb + (size_t)Tm * H, (size_t)T * H * 4, (size_t)H * 4, B, hipMemcpyDeviceToDevice, s));
+    if (h->share_P) {
+        if (launch_share_rows(emb + (size_t)Tm * H, (size_t)T * H, h->share_dev + SH_PROMPT, h->x_dec, B, H, s) || share_kv(h, Tm, s)) return 1;
+    } else
+        CTTS_HIP_CHECK(hipMemcpy2DAsync(h->x_dec, (size_t)H * 4, emb + (size_t)Tm * H, (size_t)T * H * 4, (size_t)H * 4, B, hipMemcpyDeviceToDevice, s));
     CTTS_HIP_CHECK(hipMemcpyAsync(h->x_last, h->x_dec, (size_t)B * H * 4, hipMemcpyDeviceToDevice, s));       // (ensure_non_empty restarts replay from here)
     return 0;
 }
@@ -1537,15 +1622,18 @@ extern "C" int ctts_gpt_prefill(ctts_gpt* h, const float* emb, void* stream) {
     CTTS_RANGE("ctts_gpt_prefill");             // reference: nvtx "forward" (trt_models/llama_trt_model.py:44,74), q_len > 1
     hipStream_t s = (hipStream_t)stream;
     if (h->batch_inv) return prefill_invariant(h, emb, s);
-    const int R = h->B * h->T;
+    // shared prompt passes: P prompts in the leaders' lanes; their last residual rows land in the leaders' decode rows, the followers get a copy of both
+    const int P = h->share_P ? h->share_P : h->B;
+    const int R = P * h->T;
     const int PASS_ROWS = h->pass_rows;
     for (int r0 = 0; r0 < R; r0 += PASS_ROWS) {
         const int n = (R - r0 < PASS_ROWS) ? R - r0 : PASS_ROWS;
         CTTS_HIP_CHECK(hipMemcpyAsync(h->x_pre, emb + (size_t)r0 * h->H, (size_t)n * h->H * 4, hipMemcpyDeviceToDevice, s));
         if (run_layers(h, h->x_pre, h->meta_pre + r0, h->rope_pre + (size_t)r0 * 64, n, DecodePath{1, 0}, nullptr, s)) return 1;
         // rows (b, T-1) that live in this pass -> x_dec[b]  (indices computed on the device: the call stays asynchronous)
-        if (launch_gather_last_rows(h->x_pre, h->x_dec, h->B, h->T, r0, n, h->H, s)) return 1;
+        if (launch_gather_last_rows(h->x_pre, h->x_dec, P, h->T, r0, n, h->H, h->share_P ? h->share_dev + SH_LEADER : nullptr, s)) return 1;
     }
+    if (h->share_P && (launch_share_rows(h->x_dec, (size_t)h->H, h->share_dev + SH_LEAD_OF, h->x_dec, h->B, h->H, s) || share_kv(h, h->T, s))) return 1;
     // keep a copy of the prompt's last residual rows for ensure_non_empty restarts
     CTTS_HIP_CHECK(hipMemcpyAsync(h->x_last, h->x_dec, (size_t)h->B * h->H * 4, hipMemcpyDeviceToDevice, s));
     return 0;
@@ -1574,7 +1662,7 @@ extern "C" int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* mask, co
     }
     CTTS_RANGE("ctts_gpt_score");
     hipStream_t s = (hipStream_t)stream;
-    h->B = 0; h->admitted = false;                 // the KV lanes and the prompt workspaces are overwritten: any generate() state ends here
+    h->B = 0; h->admitted = false; h->share_P = 0;      // the KV lanes and the prompt workspaces are overwritten: any generate() state ends here
     h->text_mode = 0;
     if (seat_row_adapters(h, B, "score", s)) return 1;
     const int NV = h->NVQ * h->V;
@@ -1588,7 +1676,7 @@ extern "C" int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* mask, co
     CTTS_HIP_CHECK(hipMemsetAsync(logprob, 0, (size_t)B * max_targets * CTTS_NUM_VQ * 4, s));
     CTTS_HIP_CHECK(hipMemsetAsync(argmax, 0xFF, (size_t)B * max_targets * CTTS_NUM_VQ * 4, s));
     h->pre_T = T;
-    if (launch_fill_meta(h->meta_pre, h->meta_dec0, h->st, mask, B, T, h->rope, h->rope_pre, s)) return 1;
+    if (launch_fill_meta(h->meta_pre, h->meta_dec0, h->st, mask, B, T, h->rope, h->rope_pre, nullptr, B, s)) return 1;
     const long R = (long)B * T;
     // batch_invariant: the heads on 16-row chunks whatever the block holds (as run_heads pins nbg = 1); the chunk of SCORE_ROWS rows only bounds the scratch
     const int nbg = h->batch_inv ? 1 : 2;
@@ -1938,11 +2026,18 @@ extern "C" int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, co
     // what ctts_gpt_admit_sampling named is for THIS admission only, whether it goes through or fails below: a later admit never picks up a stale entry
     std::vector<std::pair<int, RowSampling>> named;
     named.swap(h->knobs_admit);
+    std::vector<int> share;                      // ... and so is what ctts_gpt_share_prompts named
+    share.swap(h->share_req);
+    const int share_P = h->share_req_P;
+    h->share_req_P = 0;
+    if (!share.empty() && (int)share.size() != n) { ctts_set_error("admit: ctts_gpt_share_prompts named the prompts of %d sequences, this call seats n=%d", (int)share.size(), n); return 1; }
+    if (!share.empty() && h->text_mode) { ctts_set_error("admit: shared prompt passes (ctts_gpt_share_prompts) are code mode only"); return 1; }
+    const int P = share.empty() ? n : share_P;   // prompts: mask [P][T], emb [P][T][H]
     if (!rows || !mask || !emb || !utt_ids || !out_index) { ctts_set_error("admit: null argument"); return 1; }
     if (h->io.noise != nullptr) { ctts_set_error("admit: device noise only (caller-supplied noise is indexed by the batch's draw counter)"); return 1; }
     if (h->batch_inv && h->lora_rows) { ctts_set_error("admit: per-utterance adapters are outside the batch_invariant contract; set the option to 0 or merge the adapter"); return 1; }
-    if (n < 1 || n > h->B || T < 1 || T + h->sc.max_new > h->cfg.max_seq || (long long)n * (T - 1) > h->pass_rows) {
-        ctts_set_error("admit: n=%d of %d rows, T=%d (max_seq %d, %d prompt rows per pass)", n, h->B, T, h->cfg.max_seq, h->pass_rows);
+    if (n < 1 || n > h->B || T < 1 || T + h->sc.max_new > h->cfg.max_seq || (long long)P * (T - 1) > h->pass_rows) {
+        ctts_set_error("admit: n=%d of %d rows on %d prompts, T=%d (max_seq %d; %d x %d prompt rows for %d per pass)", n, h->B, P, T, h->cfg.max_seq, P, T - 1, h->pass_rows);
         return 1;
     }
     CTTS_RANGE("ctts_gpt_admit");
@@ -1967,6 +2062,7 @@ extern "C" int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, co
     h->knobs_host.assign(n, knobs_of_cfg(h->sc));
     for (int i = 0; i < n; ++i)
         for (const auto& e : named) if (e.first == rows[i]) h->knobs_host[i] = e.second;
+    if (!share.empty() && share_plan(h, share, P, seqs.data(), "admit", s)) return 1;
     int* rows_dev = h->keep_dev;
     int* seqs_dev = h->cring;                    // (compaction scratch: consumed in stream order)
     RowState* fresh_dev = h->cfin;
@@ -1978,17 +2074,18 @@ extern "C" int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, co
     a.mask = mask; a.emb = emb; a.rows = rows_dev; a.seqs = seqs_dev; a.fresh = fresh_dev; a.n = n; a.T = T; a.H = h->H;
     a.fresh_knobs = h->cknobs; a.knobs = h->knobs;
     a.pm = h->meta_pre; a.rope_pre = h->rope_pre; a.dm = h->meta_dec; a.rope_dec = h->rope_dec; a.x_dec = h->x_dec; a.ring = h->hist_ring; a.finend = h->finend;
-    a.rope = h->rope; a.st = h->st; a.finish = h->io.finish; a.end_idx = h->io.end_idx;
+    a.rope = h->rope; a.st = h->st; a.finish = h->io.finish; a.end_idx = h->io.end_idx; a.share = share.empty() ? nullptr : h->share_dev;
     if (launch_admit_rows(a, s)) return 1;
-    const int R = n * (T - 1);
+    const int R = P * (T - 1);
     if (R > 0) {
         // prompt rows [n][T-1] <- emb[i][0 .. T-2]
-        CTTS_HIP_CHECK(hipMemcpy2DAsync(h->x_pre, (size_t)(T - 1) * h->H * 4, emb, (size_t)T * h->H * 4, (size_t)(T - 1) * h->H * 4, n, hipMemcpyDeviceToDevice, s));
+        CTTS_HIP_CHECK(hipMemcpy2DAsync(h->x_pre, (size_t)(T - 1) * h->H * 4, emb, (size_t)T * h->H * 4, (size_t)(T - 1) * h->H * 4, P, hipMemcpyDeviceToDevice, s));
         const int keepT = h->pre_T;
         h->pre_T = T - 1;
         const int rc = run_layers(h, h->x_pre, h->meta_pre, h->rope_pre, R, DecodePath{1, 0}, nullptr, s);
         h->pre_T = keepT;
         if (rc) return 1;
+        if (!share.empty() && share_kv(h, T - 1, s)) return 1;      // the followers' lanes <- the leaders' span [0, T - 1)
     }
     for (int i = 0; i < n; ++i) { h->row_ctx[rows[i]] = T; h->row_cap[rows[i]] = T + h->fresh_host[i].limit; }
     h->admitted = true;

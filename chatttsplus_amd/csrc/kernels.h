@@ -208,9 +208,35 @@ int launch_prefill_split_gemm(int epi, const GemmArgs& a, const void* Wsplit, co
 int launch_norm_pack(int dtype, const float* x, void* out_packed, int R, int nbg, float eps, hipStream_t s);
 int launch_attention(int dtype, const AttnArgs& a, hipStream_t s);
 int launch_sampler(const SamplerArgs& a, int blocks, hipStream_t s);
-int launch_gather_last_rows(const float* src, float* dst, int B, int T, int r0, int n, int H, hipStream_t s);
+// Shared prompt passes (ctts_gpt_share_prompts): the device table of one begin / admit call that seats n sequences on P prompts, CTTS_MAX_B ints per section.
+// Sequences are counted 0..n-1 in the call's order (begin: the sequence is its row and its KV lane; admit: the i-th row named).
+enum {
+    SH_PROMPT = 0,                          // [n] prompt of sequence i
+    SH_LEADER = CTTS_MAX_B,                 // [P] the first sequence naming prompt p: it runs the prompt pass into its own KV lane
+    SH_LEAD_OF = 2 * CTTS_MAX_B,            // [n] the leader of sequence i's prompt (i itself for a leader)
+    SH_GROUPS = 3 * CTTS_MAX_B,             // [groups][3] = {leader's KV lane, first entry in SH_FOLLOWERS, followers}: the prompts with at least one follower
+    SH_FOLLOWERS = 6 * CTTS_MAX_B,          // the followers' KV lanes, group after group
+    SH_INTS = 7 * CTTS_MAX_B
+};
+// kv_share.hip: the leaders' prompt span of the KV cache -> their followers' lanes, one launch for every group of the call
+struct KvShareArgs {
+    char* kv;                   // the cache [layer][k | v][lane][head][slot][64]
+    size_t run_bytes;           // one (lane, head): max_seq x 64 elements
+    size_t lane_bytes;          // one lane: heads x run_bytes
+    size_t plane_bytes;         // one (layer, k | v): max_batch x lane_bytes
+    const int* groups;          // device: SH_GROUPS
+    const int* followers;       // device: SH_FOLLOWERS
+    int n_groups, NH;
+    unsigned units;             // 16-byte units of the span [0, span) of one run: span x 64 elements
+};
+int launch_kv_share(const KvShareArgs& a, int runs, hipStream_t s);
+int launch_share_rows(const float* src, size_t src_stride, const int* src_idx, float* dst, int n, int H, hipStream_t s);
+// dst_row (device, or null = b): where prompt b's last row goes (shared prompt passes: the leader's decode row)
+int launch_gather_last_rows(const float* src, float* dst, int B, int T, int r0, int n, int H, const int* dst_row, hipStream_t s);
 int launch_embed_ids(const int* ids, const float* emb_code, float* x, int B, int V, int H, hipStream_t s);
-int launch_fill_meta(RowMeta* prefill_meta, RowMeta* decode_meta, DevState* st, const int* mask, int B, int T, const float* rope, float* rope_pre, hipStream_t s);
+// share (device table above, or null: every sequence has its own prompt, P == B): mask is [P][T], the prompt rows [P][T] name the leaders' lanes
+int launch_fill_meta(RowMeta* prefill_meta, RowMeta* decode_meta, DevState* st, const int* mask, int B, int T, const float* rope, float* rope_pre, const int* share, int P,
+                     hipStream_t s);
 int launch_embed_prompt(const int* ids, const int* text_mask, const float* emb_text, const float* emb_code, const float* spk, int spk_id,
                         float* out, int rows, int T, int V, int H, hipStream_t s);
 int launch_restart_rows(RowState* rows, int B, hipStream_t s);
@@ -229,6 +255,7 @@ struct AdmitArgs {
                             //    finished-row count is left alone -- no finished row is being replaced)
     const RowSampling* fresh_knobs;   // [n] device: the new rows' sampling knobs (null: the table is left alone -- begin uploads it itself)
     RowSampling* knobs;               // the decode rows' knob table (common.h RowSampling)
+    const int* share;                 // shared prompt passes (table above, or null): mask / emb are indexed by prompt, the prompt rows [P][T-1] are written by the leaders
 };
 int launch_admit_rows(const AdmitArgs& a, hipStream_t s);
 // ctts_gpt_score (score.hip): the scored rows of one prompt pass, sequence by sequence, as a contiguous block (computed on the host from the targets' counts,

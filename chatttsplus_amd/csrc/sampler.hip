@@ -799,11 +799,14 @@ int launch_compact_rows(const int* keep, int n_keep, int H, float* x, float* rop
 __global__ __launch_bounds__(64) void admit_rows_kernel(const AdmitArgs a) {
     const int i = blockIdx.x, lane = threadIdx.x, T = a.T;
     const int row = a.rows[i], seq = a.seqs[i];
+    // shared prompt passes: sequence i reads prompt p's mask / embedding; the prompt rows are the leader's (written once, into its lane)
+    const int p = a.share != nullptr ? a.share[SH_PROMPT + i] : i;
+    const bool lead = a.share == nullptr || a.share[SH_LEADER + p] == i;
     int cum = 0, pad = 0;
     bool seen = false;
     for (int t0 = 0; t0 < T; t0 += 64) {
         const int t = t0 + lane;
-        const int mk = (t < T) ? (a.mask[i * T + t] != 0) : 0;
+        const int mk = (t < T) ? (a.mask[p * T + t] != 0) : 0;
         const unsigned long long bal = __builtin_amdgcn_ballot_w64(mk != 0);
         if (!seen) {
             if (bal != 0ull) { pad = t0 + (int)__builtin_ctzll(bal); seen = true; }
@@ -815,10 +818,10 @@ __global__ __launch_bounds__(64) void admit_rows_kernel(const AdmitArgs a) {
         m.pos = mk ? incl - 1 : 1;             // gpt.py:238-245
         m.slot = t;
         m.kv_start = mk ? pad : t;
-        if (t < T - 1) a.pm[i * (T - 1) + t] = m;
-        for (int j = 0; j < 64 && t0 + j < T - 1; ++j) {          // the prompt rows' RoPE table rows, one coalesced 256-byte copy each
+        if (t < T - 1 && lead) a.pm[p * (T - 1) + t] = m;
+        for (int j = 0; lead && j < 64 && t0 + j < T - 1; ++j) {          // the prompt rows' RoPE table rows, one coalesced 256-byte copy each
             const int pj = __shfl(m.pos, j);
-            a.rope_pre[((size_t)i * (T - 1) + t0 + j) * 64 + lane] = a.rope[(size_t)pj * 64 + lane];
+            a.rope_pre[((size_t)p * (T - 1) + t0 + j) * 64 + lane] = a.rope[(size_t)pj * 64 + lane];
         }
         cum += __builtin_popcountll(bal);
     }
@@ -827,7 +830,7 @@ __global__ __launch_bounds__(64) void admit_rows_kernel(const AdmitArgs a) {
     a.ring[(size_t)row * 64 + lane] = -1;
     if (a.fresh_knobs != nullptr && lane < 7) ((int4*)(a.knobs + row))[lane] = ((const int4*)(a.fresh_knobs + i))[lane];      // the utterance's own knobs
     if (a.emb != nullptr)
-        for (int k = lane; k < a.H; k += 64) a.x_dec[(size_t)row * a.H + k] = a.emb[((size_t)i * T + T - 1) * a.H + k];
+        for (int k = lane; k < a.H; k += 64) a.x_dec[(size_t)row * a.H + k] = a.emb[((size_t)p * T + T - 1) * a.H + k];
     if (lane == 0) {
         RowMeta d;
         d.seq = seq; d.pos = pos_last; d.slot = T - 1; d.kv_start = pad;
@@ -846,14 +849,15 @@ int launch_admit_rows(const AdmitArgs& a, hipStream_t s) {
 
 // rows (b, T-1) of the prompt that live in the pass [r0, r0 + n) -> dst[b]: the row indices are computed on the device, so the
 // prompt pass needs no host-side index table (and no stream synchronisation between passes)
-__global__ void gather_last_rows_kernel(const float* src, float* dst, int T, int r0, int n, int H) {
+__global__ void gather_last_rows_kernel(const float* src, float* dst, int T, int r0, int n, int H, const int* dst_row) {
     const int b = blockIdx.x;
     const int sr = b * T + T - 1 - r0;
     if (sr < 0 || sr >= n) return;             // row not part of this prefill pass
-    for (int k = threadIdx.x; k < H; k += blockDim.x) dst[(size_t)b * H + k] = src[(size_t)sr * H + k];
+    const int d = dst_row != nullptr ? dst_row[b] : b;
+    for (int k = threadIdx.x; k < H; k += blockDim.x) dst[(size_t)d * H + k] = src[(size_t)sr * H + k];
 }
-int launch_gather_last_rows(const float* src, float* dst, int B, int T, int r0, int n, int H, hipStream_t s) {
-    hipLaunchKernelGGL(gather_last_rows_kernel, dim3(B), dim3(256), 0, s, src, dst, T, r0, n, H);
+int launch_gather_last_rows(const float* src, float* dst, int B, int T, int r0, int n, int H, const int* dst_row, hipStream_t s) {
+    hipLaunchKernelGGL(gather_last_rows_kernel, dim3(B), dim3(256), 0, s, src, dst, T, r0, n, H, dst_row);
     CTTS_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -875,15 +879,18 @@ int launch_embed_ids(const int* ids, const float* emb_code, float* x, int B, int
 
 // position ids / cache slots from the left-padded attention mask (gpt.py:238-245):
 //   pos = cumsum(mask) - 1, pad -> 1;   decode rows start at slot T with pos = (#valid tokens)
-__global__ __launch_bounds__(64) void fill_meta_kernel(RowMeta* pm, RowMeta* dm, DevState* st, const int* mask, int B, int T, const float* rope, float* rope_pre) {
+__global__ __launch_bounds__(64) void fill_meta_kernel(RowMeta* pm, RowMeta* dm, DevState* st, const int* mask, int B, int T, const float* rope, float* rope_pre, const int* share) {
     // one wavefront per sequence: 64 positions per round, cumsum(mask) from ballots (the former single-thread loop over T took
     // 0.29 ms at T = 512 -- 2 % of a 32 x 512-token prompt pass)
     const int b = blockIdx.x, lane = threadIdx.x;
+    // shared prompt passes: sequence b reads prompt p's mask row; the prompt rows [p][T] are the leader's (its lane), the decode row is every sequence's own
+    const int p = share != nullptr ? share[SH_PROMPT + b] : b;
+    const bool lead = share == nullptr || share[SH_LEADER + p] == b;
     int cum = 0, pad = 0;                      // uniform: valid tokens before this round; leading zeros (left padding)
     bool seen = false;
     for (int t0 = 0; t0 < T; t0 += 64) {
         const int t = t0 + lane;
-        const int mk = (t < T) ? (mask[b * T + t] != 0) : 0;
+        const int mk = (t < T) ? (mask[p * T + t] != 0) : 0;
         const unsigned long long bal = __builtin_amdgcn_ballot_w64(mk != 0);
         if (!seen) {                           // first attended position so far
             if (bal != 0ull) { pad = t0 + (int)__builtin_ctzll(bal); seen = true; }
@@ -895,7 +902,7 @@ __global__ __launch_bounds__(64) void fill_meta_kernel(RowMeta* pm, RowMeta* dm,
         m.pos = mk ? incl - 1 : 1;             // gpt.py:238-245: cumsum - 1, pad -> 1
         m.slot = t;
         m.kv_start = mk ? pad : t;             // pad query rows attend to themselves only (their output is never used)
-        if (t < T) pm[b * T + t] = m;
+        if (t < T && lead) pm[p * T + t] = m;
         cum += __builtin_popcountll(bal);
     }
     if (lane == 0) {
@@ -911,9 +918,9 @@ __global__ __launch_bounds__(256) void rope_rows_kernel(const RowMeta* pm, const
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (r < n) rope_pre[(size_t)r * 64 + lane] = rope[(size_t)pm[r].pos * 64 + lane];
 }
-int launch_fill_meta(RowMeta* pm, RowMeta* dm, DevState* st, const int* mask, int B, int T, const float* rope, float* rope_pre, hipStream_t s) {
-    hipLaunchKernelGGL(fill_meta_kernel, dim3(B), dim3(64), 0, s, pm, dm, st, mask, B, T, rope, rope_pre);
-    hipLaunchKernelGGL(rope_rows_kernel, dim3((B * T + 3) / 4), dim3(256), 0, s, (const RowMeta*)pm, rope, rope_pre, B * T);
+int launch_fill_meta(RowMeta* pm, RowMeta* dm, DevState* st, const int* mask, int B, int T, const float* rope, float* rope_pre, const int* share, int P, hipStream_t s) {
+    hipLaunchKernelGGL(fill_meta_kernel, dim3(B), dim3(64), 0, s, pm, dm, st, mask, B, T, rope, rope_pre, share);
+    hipLaunchKernelGGL(rope_rows_kernel, dim3((P * T + 3) / 4), dim3(256), 0, s, (const RowMeta*)pm, rope, rope_pre, P * T);
     CTTS_HIP_CHECK(hipGetLastError());
     return 0;
 }

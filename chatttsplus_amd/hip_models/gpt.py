@@ -297,6 +297,46 @@ def row_sampling_array(base: _lib.SamplerCfg, entries, n: int, num_vq: int = 4, 
     return (_lib.RowSampling * n)(*[row_sampling_from_values(base, e, num_vq) for e in entries])
 
 
+def prompt_groups(prompt_of, n_prompts: int, slots=None, subset=None, n=None, infer_text: bool = False):
+    """Index bookkeeping of shared prompt passes (ctts_gpt_share_prompts): `prompt_of[i]` in [0, n_prompts) names the prompt of sequence i.  For the sequences
+    `subset` (indices into prompt_of, in seating order; None = all of them) that one begin / admit call seats, returns (prompts, local, leaders):
+      prompts   the prompts the subset names, in order of first use -- the rows of emb / mask the call passes
+      local     the subset's prompt_of re-indexed into `prompts` (what ctts_gpt_share_prompts takes)
+      leaders   per entry of `prompts` the position in the subset of the first sequence naming it: it runs the prompt pass, the others receive a copy.
+    Raises HipBackendError on what the engine refuses: a length that differs from the call's `n`, an index out of range, a prompt named by no sequence (checked on
+    the whole list), infer_text, and sequences of one group with different adapter `slots` (one per sequence; -1 / None = none)."""
+    prompt_of = [int(p) for p in prompt_of]
+    n_prompts = int(n_prompts)
+    if n is not None and len(prompt_of) != int(n):
+        raise _lib.HipBackendError(f"prompt_of: {len(prompt_of)} entries for {int(n)} sequences")
+    if infer_text:
+        raise _lib.HipBackendError("prompt_of: shared prompt passes are code mode only; the refine-text pass (infer_text=True) runs every prompt")
+    for i, p in enumerate(prompt_of):
+        if not 0 <= p < n_prompts:
+            raise _lib.HipBackendError(f"prompt_of[{i}]={p} is out of range: the call has {n_prompts} prompts")
+    missing = sorted(set(range(n_prompts)) - set(prompt_of))
+    if missing:
+        raise _lib.HipBackendError(f"prompt_of: prompt {missing[0]} is named by no sequence")
+    if slots is not None and len(slots) != len(prompt_of):
+        raise _lib.HipBackendError(f"prompt_of: {len(slots)} adapter slots for {len(prompt_of)} sequences")
+    sub = list(range(len(prompt_of))) if subset is None else [int(i) for i in subset]
+    prompts, local, leaders, where = [], [], [], {}
+    for j, i in enumerate(sub):
+        p = prompt_of[i]
+        if p not in where:
+            where[p] = len(prompts)
+            prompts.append(p)
+            leaders.append(j)
+        elif slots is not None:
+            a, b = slots[sub[leaders[where[p]]]], slots[i]
+            a, b = (-1 if a is None or int(a) < 0 else int(a)), (-1 if b is None or int(b) < 0 else int(b))
+            if a != b:
+                raise _lib.HipBackendError(f"prompt_of: sequences {sub[leaders[where[p]]]} and {i} share prompt {p} but carry different adapter slots ({a}, {b}); "
+                                           "the prompt pass depends on the adapter: a group shares one slot or none")
+        local.append(where[p])
+    return prompts, local, leaders
+
+
 def compact_size(n_live: int) -> int:
     """Decode-batch size used for `n_live` unfinished sequences (finished-row compaction, ctts_gpt_compact): every size up to 16, then
     multiples of 2 up to 32, of 4 up to 64, of 8 beyond -- a captured decode graph exists per batch size, so the sizes are quantised;
@@ -411,6 +451,7 @@ class GPT:
             self.set_option(k, v)
         self.compact = bool(kwargs.get("compact", True))      # finished-row compaction at chunk boundaries (batches of >= 8 sequences)
         self.compact_chunk = int(kwargs.get("compact_chunk", 8))   # ... whose chunks are this short: a finished row leaves the batch 1-2 chunks later
+        self.shared_prompts = []          # (rows, prompts) per begin / admit of the last generate(prompt_of=...) / generate_many(prompt_of=...) call
         self.model_path = kwargs.get("model_path", None)
         if self.model_path:
             self.from_pretrained(self.model_path)
@@ -644,8 +685,11 @@ class GPT:
                  min_new_token=0, logits_warpers=[], logits_processors=[], infer_text=False, return_attn=False,
                  return_hidden=False, stream=False, show_tqdm=True, ensure_non_empty=True, stream_batch=24,
                  context=None, noise="auto", seed: Optional[int] = None, max_restarts: int = 64, utt_ids=None, max_new_tokens_per_row=None,
-                 sampling_per_row=None, return_logprobs=False):
-        """`return_logprobs`: every yielded GenerationOutputs (the partial ones of stream=True too) carries `logprobs`, `sampled_logprobs` and
+                 sampling_per_row=None, return_logprobs=False, prompt_of=None):
+        """`prompt_of` (shared prompt passes, ctts_gpt_share_prompts; code mode): a list of length B naming each sequence's prompt; `emb` / `inputs_ids` /
+        `attention_mask` then have one row per PROMPT, every per-row argument (`utt_ids`, `max_new_tokens_per_row`, `sampling_per_row`) and every output has length
+        B.  The first sequence of a prompt runs the prompt pass, the others receive a copy of its KV lane; `shared_prompts` records (rows, prompts) of the call.
+        `return_logprobs`: every yielded GenerationOutputs (the partial ones of stream=True too) carries `logprobs`, `sampled_logprobs` and
         `final_logprobs` for the tokens so far, written by the sampler as it draws them (ctts_gpt_set_logprob_out; code mode only).
         `noise`: "torch" draws q = empty(B*4,V).exponential_() per step from torch's CPU generator -- the very numbers
         torch.multinomial consumes in the reference, so TorchSeedContext(seed) reproduces the CPU path's tokens (costs
@@ -674,18 +718,27 @@ class GPT:
         try:
             yield from self._generate(emb, inputs_ids, temperature, eos_token, attention_mask, max_new_token, min_new_token, logits_warpers,
                                       logits_processors, infer_text, return_hidden, stream, ensure_non_empty, stream_batch, context, noise, seed,
-                                      max_restarts, utt_ids, max_new_tokens_per_row, sampling_per_row, bool(return_logprobs))
+                                      max_restarts, utt_ids, max_new_tokens_per_row, sampling_per_row, bool(return_logprobs), prompt_of)
         finally:
+            if prompt_of is not None:
+                self._lib.ctts_gpt_share_prompts(self._h, 0, None, 0)         # (a call that failed before its begin leaves nothing pending)
             if sampling_per_row is not None:
                 self._lib.ctts_gpt_set_row_sampling(self._h, None, 0)      # a later plain call takes its own values
             self._busy_token.owner = None
 
     def _generate(self, emb, inputs_ids, temperature, eos_token, attention_mask, max_new_token, min_new_token, logits_warpers, logits_processors,
                   infer_text, return_hidden, stream, ensure_non_empty, stream_batch, context, noise, seed, max_restarts, utt_ids=None,
-                  row_limits=None, sampling_per_row=None, return_logprobs=False):
+                  row_limits=None, sampling_per_row=None, return_logprobs=False, prompt_of=None):
         context = context or Context()
         lib, h = self._lib, self._h
         B, T = int(inputs_ids.shape[0]), int(inputs_ids.shape[1])
+        share = None
+        if prompt_of is not None:             # B sequences on inputs_ids.shape[0] prompts
+            prompt_groups(prompt_of, B, infer_text=infer_text)                # (refusals; emb / mask keep the caller's prompt order)
+            share = np.ascontiguousarray([int(p) for p in prompt_of], dtype=np.int32)
+            n_prompts, B = B, int(share.size)
+            if B > self.max_batch:
+                raise _lib.HipBackendError(f"prompt_of: {B} sequences exceed max_batch={self.max_batch}")
         V, H, NVQ = (self.num_text_tokens if infer_text else self.num_audio_tokens), self.model_dim, self.num_vq
         rows_per_seq = 1 if infer_text else NVQ          # multinomial rows per sequence: [B, V_text] vs [B*4, 626] (gpt.py:444-467)
         dev = self.device
@@ -699,7 +752,7 @@ class GPT:
             noise = "torch" if (B <= 4 and B * rows_per_seq * V <= 16384) else "device"
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (isinstance(noise, str) and noise == "device") else 0
-        mask = torch.ones(B, T, dtype=torch.int32, device=dev) if attention_mask is None else attention_mask.to(dev).to(torch.int32).contiguous()
+        mask = torch.ones(int(inputs_ids.shape[0]), T, dtype=torch.int32, device=dev) if attention_mask is None else attention_mask.to(dev).to(torch.int32).contiguous()
         emb = emb.to(dev, dtype=torch.float32).contiguous()
         # uninitialised: only [b, :end_idx[b]] is ever read, and every one of those rows was written by the step that produced it (the
         # default max_new_token = 2048 made this a 201 MB zero-fill per call at batch 32)
@@ -775,6 +828,10 @@ class GPT:
             tick("setup")
             if knobs is not None:
                 _lib.check(lib.ctts_gpt_set_row_sampling(h, knobs, B), "set_row_sampling")
+            self.shared_prompts = []
+            if share is not None:
+                _lib.check(lib.ctts_gpt_share_prompts(h, B, share.ctypes.data_as(C.c_void_p), n_prompts), "share_prompts")
+                self.shared_prompts.append((B, n_prompts))
             _lib.check(lib.ctts_gpt_begin(h, B, T, mask.data_ptr(), C.byref(sc), C.byref(io), st), "begin")
             if lps is not None:
                 _lib.check(lib.ctts_gpt_set_logprob_out(h, lps[0].data_ptr(), lps[1].data_ptr(), st), "set_logprob_out")
@@ -882,7 +939,7 @@ class GPT:
                       attention_mask: Optional[torch.Tensor] = None, max_new_token=2048, min_new_token=0, logits_warpers=[],
                       logits_processors=[], return_hidden=False, ensure_non_empty=True, context=None, seed: Optional[int] = None,
                       max_restarts: int = 64, utt_ids=None, max_new_tokens_per_row=None, rows: Optional[int] = None, admit_min: Optional[int] = None,
-                      on_done=None, infer_text: bool = False, adapter_slots=None, sampling_per_row=None, return_logprobs=False) -> GenerationOutputs:
+                      on_done=None, infer_text: bool = False, adapter_slots=None, sampling_per_row=None, return_logprobs=False, prompt_of=None) -> GenerationOutputs:
         """N utterances (left-padded prompts emb[N,T,H], like generate()) through `rows` <= max_batch decode rows: whenever utterances
         finish, queued ones take over their rows (ctts_gpt_admit) instead of the whole slice waiting for its slowest row as the reference's
         slices of 4 do (pipeline:391-397, gpt.py:527-546); once the queue is empty finished rows are compacted away (ctts_gpt_compact).
@@ -894,12 +951,16 @@ class GPT:
         utterance brings its own adapter, ctts_gpt_admit_adapters).  `sampling_per_row` = one dict of sampling knobs or None per utterance (as in
         generate()): an admitted utterance brings its own knobs (ctts_gpt_admit_sampling).  `return_logprobs`: as in generate() -- the log-prob arrays are
         indexed by utterance like the ids, so admission, compaction and ensure_non_empty re-admission need nothing extra.
+        `prompt_of` (as in generate(): N = len(prompt_of) utterances on emb.shape[0] prompts): the utterances each begin / admit call seats are grouped by prompt,
+        whatever their number, and each group pays one prompt pass (a group split across two admissions pays two); `shared_prompts` lists (rows, prompts) per call.
+        With `adapter_slots`, the utterances of one prompt must carry one slot or none over the WHOLE request (refused up front) -- stricter than the engine, which
+        compares only the sequences one call seats: give utterances that differ in their adapter their own prompt rows.
         Returns one GenerationOutputs for all N utterances, in input order."""
         gen = self.generate_many_iter(emb, inputs_ids, temperature, eos_token, attention_mask=attention_mask, max_new_token=max_new_token,
                                       min_new_token=min_new_token, logits_warpers=logits_warpers, logits_processors=logits_processors,
                                       return_hidden=return_hidden, ensure_non_empty=ensure_non_empty, context=context, seed=seed, max_restarts=max_restarts,
                                       utt_ids=utt_ids, max_new_tokens_per_row=max_new_tokens_per_row, rows=rows, admit_min=admit_min, infer_text=infer_text,
-                                      adapter_slots=adapter_slots, sampling_per_row=sampling_per_row, return_logprobs=return_logprobs)
+                                      adapter_slots=adapter_slots, sampling_per_row=sampling_per_row, return_logprobs=return_logprobs, prompt_of=prompt_of)
         try:
             while True:
                 ev = next(gen)
@@ -912,7 +973,7 @@ class GPT:
     def generate_many_iter(self, emb, inputs_ids, temperature, eos_token, attention_mask=None, max_new_token=2048, min_new_token=0, logits_warpers=[],
                            logits_processors=[], return_hidden=False, ensure_non_empty=True, context=None, seed=None, max_restarts: int = 64,
                            utt_ids=None, max_new_tokens_per_row=None, rows=None, admit_min=None, infer_text: bool = False, progress: bool = False,
-                           adapter_slots=None, sampling_per_row=None, return_logprobs=False):
+                           adapter_slots=None, sampling_per_row=None, return_logprobs=False, prompt_of=None):
         """generate_many as a generator: yields [(utterance index, ids [n,4] long, hiddens [n,768] or None)] for the utterances that completed
         since the last yield -- while the rest keeps decoding (what was yielded is final: its rows were written before the report that showed
         the utterance finished) -- and returns (StopIteration.value) the GenerationOutputs of all N utterances.
@@ -932,8 +993,10 @@ class GPT:
             return (yield from self._generate_many(emb, inputs_ids, temperature, eos_token, attention_mask, int(max_new_token), min_new_token, logits_warpers,
                                                    logits_processors, return_hidden, ensure_non_empty, context or Context(), seed, max_restarts, utt_ids,
                                                    max_new_tokens_per_row, rows, admit_min, bool(infer_text), bool(progress), adapter_slots,
-                                                   sampling_per_row, bool(return_logprobs)))
+                                                   sampling_per_row, bool(return_logprobs), prompt_of))
         finally:
+            if prompt_of is not None:
+                self._lib.ctts_gpt_share_prompts(self._h, 0, None, 0)
             if adapter_slots is not None:
                 self.set_row_adapters(None)
             if sampling_per_row is not None:
@@ -942,18 +1005,25 @@ class GPT:
 
     def _generate_many(self, emb, inputs_ids, temperature, eos_token, attention_mask, max_new_token, min_new_token, logits_warpers, logits_processors,
                        return_hidden, ensure_non_empty, context, seed, max_restarts, utt_ids, row_limits, rows, admit_min, infer_text=False, progress=False,
-                       adapter_slots=None, sampling_per_row=None, return_logprobs=False):
+                       adapter_slots=None, sampling_per_row=None, return_logprobs=False, prompt_of=None):
         lib, h, dev = self._lib, self._h, self.device
         N, T = int(inputs_ids.shape[0]), int(inputs_ids.shape[1])
+        pof = None                                # shared prompt passes: utterance -> row of emb / mask
+        if prompt_of is not None:
+            prompt_groups(prompt_of, N, adapter_slots, infer_text=infer_text)      # (refusals)
+            pof = [int(p) for p in prompt_of]
+            n_prompts, N = N, len(pof)
         H, NVQ = self.model_dim, self.num_vq
         R = min(N, int(rows) if rows else self.max_batch, self.max_batch)
         sc = sampler_cfg_from_objects(temperature, int(eos_token), max_new_token, min_new_token, logits_warpers, logits_processors, NVQ, infer_text=infer_text)
         knobs = list(row_sampling_array(sc, sampling_per_row, N, NVQ, infer_text)) if sampling_per_row is not None else None
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        mask = torch.ones(N, T, dtype=torch.int32, device=dev) if attention_mask is None else attention_mask.to(dev).to(torch.int32).contiguous()
+        mask = torch.ones(int(inputs_ids.shape[0]), T, dtype=torch.int32, device=dev) if attention_mask is None else attention_mask.to(dev).to(torch.int32).contiguous()
         emb = emb.to(dev, dtype=torch.float32).contiguous()
         lens = mask.sum(1).cpu().tolist()
+        if pof is not None:
+            lens = [lens[p] for p in pof]
         if max(lens) + max_new_token > self.max_seq:
             # (every utterance is admitted with its own prompt, trimmed of padding: the longest one decides)
             raise _lib.HipBackendError(f"generate_many: prompt of {max(lens)} tokens + max_new_token={max_new_token} exceed max_seq_len={self.max_seq}")
@@ -972,12 +1042,20 @@ class GPT:
         end_idx = torch.zeros(N, dtype=torch.int32, device=dev)
         admit_min = max(1, int(admit_min) if admit_min else R // 8)
         chunk = max(4, min(self.chunk_steps, self.compact_chunk))
-        self.compactions, self.admissions = [], []
+        self.compactions, self.admissions, self.shared_prompts = [], [], []
 
         def prompts_of(idx):
-            """left-padded prompts of the utterances `idx`, trimmed to the longest of them"""
+            """left-padded prompts of the utterances `idx`, trimmed to the longest of them.  Shared prompt passes: one row per prompt the utterances name, and the
+            engine is told which of them each utterance has (for the begin / admit call that follows)"""
             Ta = max(1, max(lens[u] for u in idx))
-            ii = torch.as_tensor(idx, dtype=torch.long, device=dev)
+            sel = idx
+            if pof is not None:
+                sel, local, _ = prompt_groups(pof, n_prompts, slots, subset=idx)
+                if len(sel) < len(idx):
+                    arr = np.ascontiguousarray(local, dtype=np.int32)
+                    _lib.check(lib.ctts_gpt_share_prompts(h, len(idx), arr.ctypes.data_as(C.c_void_p), len(sel)), "share_prompts")
+                self.shared_prompts.append((len(idx), len(sel)))
+            ii = torch.as_tensor(sel, dtype=torch.long, device=dev)
             return Ta, emb.index_select(0, ii)[:, T - Ta:].contiguous(), mask.index_select(0, ii)[:, T - Ta:].contiguous()
 
         with torch.cuda.device(dev):
@@ -994,8 +1072,11 @@ class GPT:
             if order != back:
                 # ctts_gpt_begin writes row r's outputs at index r: the request is served permuted (position j holds utterance order[j]) and every index
                 # handed back is mapped through `back` -- seating utterance order[r] in row r had them written at r and read at order[r]
-                pt = torch.as_tensor(order, dtype=torch.long, device=dev)
-                emb, mask = emb.index_select(0, pt), mask.index_select(0, pt)
+                if pof is None:
+                    pt = torch.as_tensor(order, dtype=torch.long, device=dev)
+                    emb, mask = emb.index_select(0, pt), mask.index_select(0, pt)
+                else:                                              # (emb / mask stay indexed by prompt)
+                    pof = [pof[u] for u in order]
                 lens, uids, lims = [lens[u] for u in order], [uids[u] for u in order], [lims[u] for u in order]
                 if slots is not None:
                     slots = [slots[u] for u in order]

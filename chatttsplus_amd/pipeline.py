@@ -172,6 +172,20 @@ def check_candidate_request(num_candidates, utt_ids, stream: bool, noise_mode) -
     return n
 
 
+def resolve_share_prompt(share_prompt, num_candidates, batch_invariant) -> bool:
+    """infer(num_candidates=N, share_prompt=...): do the N candidates of an utterance share one prompt pass (GPT.generate(prompt_of=...))?  None: exactly when the
+    engine's batch_invariant option reads 1 -- there a copied KV lane is bit for bit what the candidate's own prompt pass writes, so the result is the unshared
+    call's; True: in any mode (default-mode engines: same distribution, tokens may differ from the unshared schedule's); False: never.  One candidate per
+    utterance has nothing to share."""
+    if num_candidates is None or int(num_candidates) <= 1:
+        return False
+    if share_prompt is None:
+        return bool(batch_invariant)
+    if not isinstance(share_prompt, bool):
+        raise _lib.HipBackendError(f"share_prompt must be None, True or False (got {share_prompt!r})")
+    return bool(share_prompt)
+
+
 def mean_logprob(logprobs: torch.Tensor) -> float:
     """Mean of [n, 4] log-probs over tokens and codebooks; -inf when there is no token."""
     return float(logprobs.double().mean()) if logprobs.numel() else float("-inf")
@@ -682,7 +696,7 @@ class ChatTTSPlusPipeline:
                 raise _lib.HipBackendError("return_details=True needs stream=False")
             yield from self._infer_details(text_in, n_cand, bool(kwargs.get("return_details")), kwargs.get("select"), skip_refine_text, use_decoder,
                                            params_refine_text, params_infer_code, gpt, slice_size, noise_mode, noise_seed, utt_ids, utt_limits, utt_sampling,
-                                           utt_prompts, lora_paths, kwargs.get("continuous"), kwargs.get("_ids_sink"))
+                                           utt_prompts, lora_paths, kwargs.get("continuous"), kwargs.get("_ids_sink"), kwargs.get("share_prompt"))
             return
         # `continuous=True` (no counterpart in the reference): the request's utterances are NOT cut into slices that each wait for their slowest
         # row (pipeline:391-397); slice_size decode rows are kept busy -- queued utterances take over the rows of finished ones
@@ -884,11 +898,13 @@ class ChatTTSPlusPipeline:
                     yield self._window(last, length, total, use_decoder)
 
     def _infer_details(self, text_in, n_cand, return_details, select, skip_refine_text, use_decoder, params_refine_text, params_infer_code, gpt, slice_size,
-                       noise_mode, noise_seed, utt_ids, utt_limits, utt_sampling, utt_prompts, lora_paths, continuous, ids_sink):
+                       noise_mode, noise_seed, utt_ids, utt_limits, utt_sampling, utt_prompts, lora_paths, continuous, ids_sink, share_prompt=None):
         """infer(return_details=True) / infer(num_candidates=N): the code pass with return_logprobs, every utterance served N times as ordinary decode rows
         (candidate k under noise key candidate_utt_id(u, k), so candidate 0 is the plain generation), the winner picked by `select` or select_candidate,
         only winners vocoded.  Sliced: max(1, slice_size // N) utterances per slice, one yield per slice; continuous (more rows than slice_size): the
-        whole request through GPT.generate_many, one yield.  The refine-text pass runs once per utterance, before the candidates are laid out."""
+        whole request through GPT.generate_many, one yield.  The refine-text pass runs once per utterance, before the candidates are laid out.
+        `share_prompt` (resolve_share_prompt): the candidates of an utterance share its prompt pass -- each utterance is tokenised and embedded once and the
+        rows name their prompt (GPT prompt_of); speaker rows, prompts and adapters go per prompt, limits / sampling / noise keys per row."""
         tok = self.models_dict["tokenizer"]
         n_utt = len(text_in)
         if n_cand > slice_size:
@@ -913,14 +929,19 @@ class ChatTTSPlusPipeline:
                 texts = out
         texts = [t if t.strip().endswith("[uv_break]") else t + " [uv_break]" for t in texts]   # pipeline:414-416
         per_utt_spk = torch.is_tensor(params_infer_code.spk_emb) and params_infer_code.spk_emb.dim() == 2 and params_infer_code.spk_emb.shape[0] == n_utt and n_utt > 1
+        read_option = getattr(gpt, "get_option", None)           # (an engine object without options shares only when asked to)
+        share = resolve_share_prompt(share_prompt, n_cand, n_cand > 1 and read_option is not None and read_option("batch_invariant"))
 
         def run(us):
             """utterances `us` x n_cand candidates as one list of rows (utterance-major) -> one CandidateDetails per row"""
             rows = [(u, k) for u in us for k in range(n_cand)]
+            src = [(u, 0) for u in us] if share else rows          # what is tokenised and embedded: every utterance once, or every row
             pic = params_infer_code
-            if per_utt_spk or (torch.is_tensor(pic.spk_emb) and pic.spk_emb.dim() == 2 and pic.spk_emb.shape[0] == n_utt and len(rows) != n_utt):
-                pic = dataclasses.replace(pic, spk_emb=pic.spk_emb[torch.as_tensor([u for u, _ in rows], device=pic.spk_emb.device)])
+            if per_utt_spk or (torch.is_tensor(pic.spk_emb) and pic.spk_emb.dim() == 2 and pic.spk_emb.shape[0] == n_utt and len(src) != n_utt):
+                pic = dataclasses.replace(pic, spk_emb=pic.spk_emb[torch.as_tensor([u for u, _ in src], device=pic.spk_emb.device)])
             gen_kw = dict(return_logprobs=True)
+            if share:
+                gen_kw["prompt_of"] = [j for j in range(len(us)) for _ in range(n_cand)]
             many = cont and len(rows) > slice_size
             if device_noise or many or len(rows) > 4:      # (the plain call's rule: slices of <= 4 keep the reference-compatible torch noise under "auto")
                 gen_kw.update(seed=noise_seed, utt_ids=[candidate_utt_id(utt_ids[u], k) for u, k in rows])
@@ -933,13 +954,13 @@ class ChatTTSPlusPipeline:
             if utt_sampling is not None:
                 gen_kw["sampling_per_row"] = [utt_sampling[u] for u, _ in rows]
             if utt_prompts is not None:
-                gen_kw["prompts"] = [utt_prompts[u] for u, _ in rows]
+                gen_kw["prompts"] = [utt_prompts[u] for u, _ in src]
             slots = self._adapter_slots(gpt, [lora_paths[u] for u, _ in rows]) if lora_paths is not None else None
             try:
                 if many:
                     if slots is not None:
                         gen_kw["adapter_slots"] = slots
-                    events = self._infer_code([texts[u] for u, _ in rows], False, use_decoder, pic, gpt=gpt, continuous=True, rows=slice_size, **gen_kw)
+                    events = self._infer_code([texts[u] for u, _ in src], False, use_decoder, pic, gpt=gpt, continuous=True, rows=slice_size, **gen_kw)
                     try:
                         while True:
                             next(events)
@@ -949,7 +970,7 @@ class ChatTTSPlusPipeline:
                     if slots is not None:
                         gpt.set_row_adapters(slots)
                     res = None
-                    for res in self._infer_code([texts[u] for u, _ in rows], False, use_decoder, pic, gpt=gpt, **gen_kw):
+                    for res in self._infer_code([texts[u] for u, _ in src], False, use_decoder, pic, gpt=gpt, **gen_kw):
                         pass
             finally:
                 if slots is not None and not many:

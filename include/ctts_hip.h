@@ -130,6 +130,8 @@ void ctts_gpt_destroy(ctts_gpt* h);
  *       decode_splits 1, attn_wide_blocks INT_MAX, prefill_split_rows 1, prefill_splitk_rows 0.  Block-shape options (prefill_pp_blocks, prefill_small_blocks,
  *       prefill_ring4_blocks, weight_prefetch_kb) stay live: they do not change the arithmetic.
  *       An utterance's sampling knobs (ctts_gpt_set_row_sampling / ctts_gpt_admit_sampling) count as its own inputs: they are covered like its token limit.
+ *       Sharing a prompt pass (ctts_gpt_share_prompts) is one more thing an utterance's outputs do not depend on: a prompt row's K / V is a function of the
+ *       utterance's own inputs, so the lane a follower receives is bit for bit what its own prompt pass would have written.
  *       OUTSIDE the contract: caller-supplied noise (indexed by the batch's draw counter); per-utterance adapters (ctts_gpt_set_row_adapters /
  *       ctts_gpt_admit_adapters: begin / admit with a live adapter row return an error naming the option; a merged adapter, ctts_gpt_merge_lora, is just
  *       weights and is covered); ensure_non_empty restarts of a whole generate() batch (ctts_gpt_restart: the reference regenerates the slice, so an
@@ -353,6 +355,20 @@ int ctts_gpt_admit_adapters(ctts_gpt* h, int n, const int32_t* rows, const int32
  * engine address, so captured decode graphs stay valid. */
 int ctts_gpt_set_row_sampling(ctts_gpt* h, const ctts_row_sampling* per_seq, int B);
 int ctts_gpt_admit_sampling(ctts_gpt* h, int n, const int32_t* rows, const ctts_row_sampling* p, void* stream);
+
+/* Shared prompt passes (no counterpart in the reference): sequences with ONE prompt -- the N candidates of an utterance, one text at several temperatures or
+ * noise keys -- run it through the prompt pass once.  One-shot, like ctts_gpt_admit_sampling: names, for the NEXT ctts_gpt_begin (B == n) or ctts_gpt_admit
+ * (its n == n), which prompt each sequence has.  prompt_of HOST [n], values in [0, n_prompts); every prompt named at least once.  While pending, the call's mask
+ * is [n_prompts][T] and its emb (ctts_gpt_prefill / ctts_gpt_admit) is [n_prompts][T][hidden]: indexed by PROMPT, not by sequence; the prompt pass is
+ * n_prompts x T rows high (n_prompts x (T - 1) under "batch_invariant" and in ctts_gpt_admit, whose fit check counts prompts).  The first sequence naming a
+ * prompt (the leader) runs it through the prompt pass into its own KV lane; the others receive a copy of the prompt span of the lane and of the leader's pending
+ * decode input (one launch after the last pass, kv_share.hip; never host-synchronised).  Every sequence keeps its own decode-row state: lane, utterance id,
+ * limit, output index, sampling knobs; ctts_gpt_restart, ctts_gpt_compact and later admissions work as without the call.  Caller-supplied noise is allowed.
+ * NULL / n == 0 clears.  Refused here: an index out of range, a prompt named by no sequence.  Refused by the begin / admit call that consumes the request (it is
+ * consumed whether that call succeeds or fails): n differs from the call's; infer_text (code mode only); sequences of one group that carry different adapter
+ * slots (ctts_gpt_set_row_adapters / ctts_gpt_admit_adapters) -- the prompt pass depends on the adapter, so a group shares one slot or none.
+ * Without the call nothing changes: the same launches, bit-identical results. */
+int ctts_gpt_share_prompts(ctts_gpt* h, int n, const int32_t* prompt_of_host, int n_prompts);
 
 /* Log-probs of the sampled ids, written by the sampler as it draws them (no counterpart in the reference; ctts_gpt_score re-scores finished codes with a
  * prompt pass, and knows the raw heads only).  Per (utterance, step, codebook), for the id the sampler returned:
