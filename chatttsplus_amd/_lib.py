@@ -110,6 +110,8 @@ SYMBOLS = [
     ("ctts_gpt_compact", C.c_int, [_P, _P, C.c_int, _P]),
     ("ctts_sampler_noise", C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     ("ctts_gpt_admit", C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    ("ctts_gpt_grow", C.c_int, [_P, C.c_int, _P]),
+    ("ctts_gpt_cancel", C.c_int, [_P, C.c_int, _P, _P]),
     ("ctts_gpt_admit_adapters", C.c_int, [_P, C.c_int, _P, _P, _P]),
     ("ctts_gpt_set_row_sampling", C.c_int, [_P, _P, C.c_int]),
     ("ctts_gpt_admit_sampling", C.c_int, [_P, C.c_int, _P, _P, _P]),

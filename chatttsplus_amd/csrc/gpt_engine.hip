@@ -2092,6 +2092,61 @@ extern "C" int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, co
     return 0;
 }
 
+// Elastic batch (no counterpart in the reference): n dead rows behind the decode batch, for the ctts_gpt_admit that follows.  A dead row runs through the layers
+// and appends K / V at slot 0 of its lane, so it gets a lane no row of the batch holds: the lowest free ones (after a compaction those are not B ..).  h->B changes
+// exactly as in ctts_gpt_compact: the next ctts_gpt_decode plans, picks its graphs and its persistent launches by the new row count.
+extern "C" int ctts_gpt_grow(ctts_gpt* h, int n, void* stream) {
+    if (!h || h->B == 0) { ctts_set_error("grow: no generate state (call ctts_gpt_begin first)"); return 1; }
+    if (h->io.noise != nullptr) { ctts_set_error("grow: device noise only (caller-supplied noise is indexed by the batch's draw counter and sized for the rows of begin)"); return 1; }
+    if (n < 1) { ctts_set_error("grow: n=%d (at least one row)", n); return 1; }
+    if (h->B + n > h->cfg.max_batch) { ctts_set_error("grow: %d + %d rows exceed max_batch=%d", h->B, n, h->cfg.max_batch); return 1; }
+    CTTS_RANGE("ctts_gpt_grow");
+    hipStream_t s = (hipStream_t)stream;
+    const int B = h->B;
+    bool used[CTTS_MAX_B] = {};
+    for (int r = 0; r < B; ++r) used[h->row_seq[r]] = true;
+    h->row_seq.resize(B + n); h->row_ctx.resize(B + n); h->row_cap.resize(B + n);
+    h->seq_host.assign(n, 0);
+    for (int i = 0, lane = 0; i < n; ++i, ++lane) {
+        while (used[lane]) ++lane;               // (B + n <= max_batch and the rows' lanes are distinct: n free lanes exist below max_batch)
+        h->seq_host[i] = lane;
+        h->row_seq[B + i] = lane; h->row_ctx[B + i] = 1; h->row_cap[B + i] = 1;      // parked on slot 0
+        h->lora_row_slots[B + i] = -1;
+        if (!h->lora_slot_host.empty()) h->lora_slot_host[lane] = -1;
+    }
+    if (!h->lora_slot_host.empty() && h->lora_slot_of_seq)
+        CTTS_HIP_CHECK(hipMemcpyAsync(h->lora_slot_of_seq, h->lora_slot_host.data(), CTTS_MAX_B * 4, hipMemcpyHostToDevice, s));
+    h->knobs_host.assign(1, knobs_of_cfg(h->sc));
+    CTTS_HIP_CHECK(hipMemcpyAsync(h->keep_dev, h->seq_host.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));      // (compaction scratch: consumed in stream order)
+    CTTS_HIP_CHECK(hipMemcpyAsync(h->cknobs, h->knobs_host.data(), sizeof(RowSampling), hipMemcpyHostToDevice, s));
+    GrowArgs a = {};
+    a.B0 = B; a.n = n; a.H = h->H; a.seqs = h->keep_dev;
+    a.dm = h->meta_dec; a.rope_dec = h->rope_dec; a.x_dec = h->x_dec; a.ring = h->hist_ring; a.finend = h->finend;
+    a.knobs = h->knobs; a.call_knobs = h->cknobs; a.rope = h->rope; a.st = h->st;
+    if (launch_grow_rows(a, s)) return 1;
+    h->B = B + n;
+    h->admitted = true;                          // x_last / meta_dec0 no longer describe the rows: no ctts_gpt_restart
+    return 0;
+}
+
+// Ends the utterances in `rows` where they stand (a client went away): the rows become ordinary finished rows -- they write nothing more, rows_enqueue reports
+// them, admit may take them, compact may drop them.  The row count does not change, so the other rows' launches are those of the same schedule without the call.
+extern "C" int ctts_gpt_cancel(ctts_gpt* h, int n, const int32_t* rows, void* stream) {
+    if (!h || h->B == 0) { ctts_set_error("cancel: no generate state (call ctts_gpt_begin first)"); return 1; }
+    if (n < 1 || !rows) { ctts_set_error("cancel: n=%d rows / null argument", n); return 1; }
+    bool named[CTTS_MAX_B] = {};
+    for (int i = 0; i < n; ++i) {
+        if (rows[i] < 0 || rows[i] >= h->B) { ctts_set_error("cancel: row %d of %d", rows[i], h->B); return 1; }
+        if (named[rows[i]]) { ctts_set_error("cancel: row %d named twice", rows[i]); return 1; }
+        named[rows[i]] = true;
+    }
+    CTTS_RANGE("ctts_gpt_cancel");
+    hipStream_t s = (hipStream_t)stream;
+    h->keep_host.assign(rows, rows + n);
+    CTTS_HIP_CHECK(hipMemcpyAsync(h->keep_dev, h->keep_host.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    return launch_cancel_rows(h->keep_dev, n, h->finend, h->st, s);
+}
+
 // Diagnostics: copies a named internal buffer to HOST memory (tools/persist_probe.py compares the persistent layer's intermediates with the
 // launch path's).  Synchronises the stream.  Returns the number of bytes copied through *bytes.
 extern "C" int ctts_gpt_debug_read(ctts_gpt* h, const char* name, void* out, size_t max_bytes, size_t* bytes, void* stream) {
@@ -2100,6 +2155,7 @@ extern "C" int ctts_gpt_debug_read(ctts_gpt* h, const char* name, void* out, siz
     const void* src = nullptr; size_t nb = 0;
     if (n == "x_dec") { src = h->x_dec; nb = (size_t)CTTS_MAX_B * h->H * 4; }
     else if (n == "q_buf") { src = h->q_buf; nb = (size_t)32 * h->H * 4; }
+    else if (n == "meta_dec") { src = h->meta_dec; nb = (size_t)CTTS_MAX_B * sizeof(RowMeta); }      // {KV lane, pos, slot, kv_start} per decode row
     else if (n == "logits") { src = h->logits; nb = (size_t)CTTS_MAX_B * h->NVQ * h->V * 4; }
     else if (n == "pl_g" && h->pl_g) { src = h->pl_g; nb = (size_t)PL_G_TOTAL * 8; }
     else if (n == "pl_ts" && h->pl_ts) { src = h->pl_ts; nb = (size_t)PL_BLOCKS * 10 * 8; }

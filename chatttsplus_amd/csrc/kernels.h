@@ -258,6 +258,17 @@ struct AdmitArgs {
     const int* share;                 // shared prompt passes (table above, or null): mask / emb are indexed by prompt, the prompt rows [P][T-1] are written by the leaders
 };
 int launch_admit_rows(const AdmitArgs& a, hipStream_t s);
+// ctts_gpt_grow: n dead rows B0 .. B0 + n - 1 (KV lanes `seqs[i]`, device) behind the decode batch; every row gets the call's knobs (`call_knobs`, one device entry)
+struct GrowArgs {
+    int B0, n, H;
+    const int* seqs;
+    RowMeta* dm; float* rope_dec; float* x_dec; int* ring; RowState* finend;      // decode-row arrays
+    RowSampling* knobs; const RowSampling* call_knobs;
+    const float* rope; DevState* st;
+};
+int launch_grow_rows(const GrowArgs& a, hipStream_t s);
+// ctts_gpt_cancel: the live rows among rows[0..n) (device, distinct, < the batch's row count) become finished rows where they stand
+int launch_cancel_rows(const int* rows, int n, RowState* finend, DevState* st, hipStream_t s);
 // ctts_gpt_score (score.hip): the scored rows of one prompt pass, sequence by sequence, as a contiguous block (computed on the host from the targets' counts,
 // passed by value: the call needs no index upload and stays asynchronous)
 struct ScoreRows {

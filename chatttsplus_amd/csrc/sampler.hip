@@ -847,6 +847,58 @@ int launch_admit_rows(const AdmitArgs& a, hipStream_t s) {
     return 0;
 }
 
+// ctts_gpt_grow: one wavefront per new row.  The row is a finished one that never was live (fin = 1 without the EOS bit, no tokens, limit 1, output index 0:
+// every store keyed by `out` is under the row-is-live test), parked on slot 0 of a KV lane of its own, where it keeps appending its K / V like any finished
+// row until ctts_gpt_admit seats an utterance in it.  The batch's row count and its finished-row count go up by n together.
+__global__ __launch_bounds__(64) void grow_rows_kernel(const GrowArgs a) {
+    const int i = blockIdx.x, lane = threadIdx.x;
+    const int row = a.B0 + i;
+    a.rope_dec[(size_t)row * 64 + lane] = a.rope[lane];                  // position 0
+    a.ring[(size_t)row * 64 + lane] = -1;
+    if (lane < 7) ((int4*)(a.knobs + row))[lane] = ((const int4*)a.call_knobs)[lane];
+    for (int k = lane; k < a.H; k += 64) a.x_dec[(size_t)row * a.H + k] = 0.f;
+    if (lane == 0) {
+        RowMeta d;
+        d.seq = a.seqs[i]; d.pos = 0; d.slot = 0; d.kv_start = 0;
+        a.dm[row] = d;
+        RowState r = {};
+        r.fin = 1; r.limit = 1;
+        a.finend[row] = r;
+        if (i == 0) { a.st->B = a.B0 + a.n; a.st->ticket += a.n << 16; }
+    }
+}
+int launch_grow_rows(const GrowArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(grow_rows_kernel, dim3(a.n), dim3(64), 0, s, a);
+    CTTS_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ctts_gpt_cancel: one wavefront.  Which of the named rows are still live is known on the device only: each lane tests its row, the ballot counts the rows
+// that changed, lane 0 moves the batch's finished-row count (high half of the ticket) by that many.  finish / end_idx of the utterance stay as the sampler left
+// them: EOS not seen, end_idx = tokens written.
+__global__ __launch_bounds__(64) void cancel_rows_kernel(const int* rows, int n, RowState* finend, DevState* st) {
+    const int lane = threadIdx.x;
+    int changed = 0;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        bool hit = false;
+        if (i < n) {
+            RowState* r = finend + rows[i];
+            if (r->fin == 0) { r->fin = 1; hit = true; }
+        }
+        changed += __builtin_popcountll(__builtin_amdgcn_ballot_w64(hit));
+    }
+    if (lane == 0 && changed > 0) {
+        const int tot = __hip_atomic_fetch_add(&st->ticket, changed << 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + (changed << 16);
+        if ((tot >> 16) == st->B) st->all_done = 1;
+    }
+}
+int launch_cancel_rows(const int* rows, int n, RowState* finend, DevState* st, hipStream_t s) {
+    hipLaunchKernelGGL(cancel_rows_kernel, dim3(1), dim3(64), 0, s, rows, n, finend, st);
+    CTTS_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // rows (b, T-1) of the prompt that live in the pass [r0, r0 + n) -> dst[b]: the row indices are computed on the device, so the
 // prompt pass needs no host-side index table (and no stream synchronisation between passes)
 __global__ void gather_last_rows_kernel(const float* src, float* dst, int T, int r0, int n, int H, const int* dst_row) {

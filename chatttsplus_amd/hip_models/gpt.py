@@ -402,6 +402,426 @@ class RowBook:
                 self.tickets[tk][2] = nr
 
 
+class SessionPlan:
+    """What DecodeSession.step does to the decode batch next (SessionBook.plan): `begin` / `admit` = [(row, ticket)], `grow` = rows to append first
+    (ctts_gpt_grow), `lanes` = the KV lanes those rows get (the engine picks the same ones), `compact` = rows to keep (ctts_gpt_compact) or None."""
+
+    def __init__(self, begin=(), grow=0, lanes=(), admit=(), compact=None):
+        self.begin, self.grow, self.lanes, self.admit, self.compact = list(begin), int(grow), list(lanes), list(admit), compact
+
+    def __bool__(self):
+        return bool(self.begin or self.grow or self.admit or self.compact is not None)
+
+
+class SessionBook:
+    """Bookkeeping of a serving session (GPT.open_session), pure Python: tickets, the queue, which output slot an utterance writes to and when the slot is
+    free again, the mirror of the decode rows' KV lanes, and the decision what to do with the batch next -- seat queued utterances in free rows, then in rows
+    obtained by growing the batch up to `rows`, else (nothing queued) shrink it by the compact_size rule.  Row reports are interpreted by a RowBook, whose
+    "utterance" is the session ticket."""
+
+    def __init__(self, rows: int, out_slots: int, max_batch: int, max_seq: int, max_new_token: int, ensure_non_empty: bool = True, max_restarts: int = 64,
+                 compact: bool = True):
+        if not (1 <= int(rows) <= int(max_batch)):
+            raise ValueError(f"session: rows={rows} outside 1..max_batch={max_batch}")
+        if int(out_slots) < 1:
+            raise ValueError(f"session: out_slots={out_slots} (at least one)")
+        self.rows, self.max_batch, self.max_seq, self.max_new = int(rows), int(max_batch), int(max_seq), int(max_new_token)
+        self.ensure_non_empty, self.max_restarts, self.compact = bool(ensure_non_empty), int(max_restarts), bool(compact)
+        self.book = RowBook()
+        self.lanes: List[int] = []                 # KV lane of every current decode row (the engine's row_seq)
+        self.free_slots = list(range(int(out_slots)))
+        self.queue: List[int] = []                 # tickets waiting for a row (and an output slot), in order of service
+        self.utts = {}                             # ticket -> dict(utt_id, T, limit, attempt, slot, row_tk, cancelled)
+        self.begun = False
+        self._next = 0
+        self._to_cancel: List[int] = []            # seated tickets whose cancel the device has not seen yet
+        self._dropped: List[int] = []              # tickets cancelled while queued: delivered by the next step
+
+    # -- requests ---------------------------------------------------------------------------------
+    def submit(self, T: int, utt_id: int, limit: Optional[int] = None) -> int:
+        T = int(T)
+        if T < 1 or T + self.max_new > self.max_seq:
+            raise ValueError(f"submit: prompt of {T} tokens + max_new_token={self.max_new} exceed max_seq_len={self.max_seq}")
+        lim = self.max_new if limit is None else min(max(int(limit), 1), self.max_new)
+        tk = self._next
+        self._next += 1
+        self.utts[tk] = dict(utt_id=int(utt_id), T=T, limit=lim, attempt=0, slot=None, row_tk=None, cancelled=False)
+        self.queue.append(tk)
+        return tk
+
+    def cancel(self, tk: int) -> Optional[str]:
+        """"queued": dropped at once (the next step delivers an empty result); "seated": the device cancels it at the next step boundary; None: unknown, already
+        delivered or already cancelled"""
+        u = self.utts.get(tk)
+        if u is None or u["cancelled"]:
+            return None
+        u["cancelled"] = True
+        if tk in self.queue:
+            self.queue.remove(tk)
+            self._dropped.append(tk)
+            return "queued"
+        self._to_cancel.append(tk)
+        return "seated"
+
+    def cancel_rows(self) -> List[int]:
+        """current rows of the seated tickets cancelled since the last call (for ctts_gpt_cancel)"""
+        rows = sorted(self.book.tickets[self.utts[tk]["row_tk"]][2] for tk in self._to_cancel
+                      if tk in self.utts and self.utts[tk]["row_tk"] in self.book.tickets)
+        self._to_cancel = []
+        return rows
+
+    def take_dropped(self) -> List[int]:
+        out, self._dropped = self._dropped, []
+        return out
+
+    def n_live(self) -> int:
+        return len(self.book.tickets)
+
+    def idle(self) -> bool:
+        return not self.queue and not self.book.tickets and not self._dropped
+
+    # -- the batch -----------------------------------------------------------------------------------
+    def free_lanes(self) -> List[int]:
+        used = set(self.lanes)
+        return [l for l in range(self.max_batch) if l not in used]
+
+    def _seat(self, row: int, tk: int) -> None:
+        u = self.utts[tk]
+        u["slot"] = self.free_slots.pop(0)
+        u["row_tk"] = self.book.seat(row, tk, u["attempt"])
+
+    def plan(self) -> SessionPlan:
+        """Decides and books the next change of the batch; the caller carries it out in the order begin | grow, admit | compact."""
+        k = min(len(self.queue), len(self.free_slots))
+        if not self.begun:
+            k = min(k, self.rows)
+            if k == 0:
+                return SessionPlan()
+            take, self.queue = self.queue[:k], self.queue[k:]
+            for r, tk in enumerate(take):
+                self._seat(r, tk)
+                assert self.utts[tk]["slot"] == r      # ctts_gpt_begin writes row r's outputs at index r
+            self.lanes = list(range(k))
+            self.begun = True
+            return SessionPlan(begin=list(enumerate(take)))
+        B = len(self.book.row_tk)
+        free = self.book.free_rows()
+        if k > 0:
+            grow = max(0, min(k - len(free), self.rows - B))
+            k = min(k, len(free) + grow)
+            if k == 0:
+                return SessionPlan()
+            lanes = self.free_lanes()[:grow]           # lowest first: after a compaction these are not B ..
+            self.lanes += lanes
+            rows = free[:k - grow] + list(range(B, B + grow))
+            take, self.queue = self.queue[:k], self.queue[k:]
+            for r, tk in zip(rows, take):
+                self._seat(r, tk)
+            return SessionPlan(grow=grow, lanes=lanes, admit=list(zip(rows, take)))
+        if not self.queue and self.compact and B >= 2:
+            live = self.book.live_rows()
+            target = compact_size(len(live))
+            if live and target < B:
+                keep = sorted(live + free[:target - len(live)])
+                self.book.compact(keep)
+                self.lanes = [self.lanes[r] for r in keep]
+                return SessionPlan(compact=keep)
+        return SessionPlan()
+
+    def report(self, layout, states):
+        """One row report ([(fin, end)] per row of `layout`, RowBook.report).  Returns [(ticket, tokens, fin bits, cancelled)] of the utterances that ended; those
+        whose first token was EOS go back to the head of the queue with their next attempt (a cancelled one ends instead).  The caller clones the results out
+        of slot utts[ticket]["slot"] and then calls release(ticket)."""
+        fin_of = {self.book.tickets[t][0]: int(fin) for t, (fin, end) in zip(layout, states) if t is not None and fin and t in self.book.tickets}
+        done, again = self.book.report(layout, states, self.ensure_non_empty, self.max_restarts)
+        out, back = [], []
+        for tk, att in again:
+            u = self.utts[tk]
+            if u["cancelled"]:
+                out.append((tk, 0, 1, True))
+                continue
+            u["attempt"], u["row_tk"] = att, None
+            self.free_slots.append(u["slot"])
+            self.free_slots.sort()
+            u["slot"] = None
+            back.append(tk)
+        self.queue = back + self.queue
+        for tk, n in done:
+            u = self.utts[tk]
+            fin = fin_of.get(tk, 1)
+            out.append((tk, n, fin, bool(u["cancelled"] and not (fin & 2) and n < u["limit"])))
+        return out
+
+    def release(self, tk: int) -> None:
+        """the utterance's result has been cloned out: its output slot may be written again"""
+        u = self.utts.pop(tk)
+        if u["slot"] is not None:
+            self.free_slots.append(u["slot"])
+            self.free_slots.sort()
+
+
+# arguments of generate() / generate_many() / infer() that a session refuses by name (GPT.open_session, ChatTTSPlusPipeline.open_session)
+SESSION_OUT_OF_SCOPE = {"prompt_of": "shared prompt passes", "share_prompt": "shared prompt passes", "num_candidates": "num_candidates / shared prompt passes",
+                        "noise": "caller-supplied noise", "stream": "per-utterance streaming windows", "stream_batch": "per-utterance streaming windows",
+                        "sharded": "infer_sharded", "infer_text": "the refine-text pass inside a code session",
+                        "refine_text_only": "the refine-text pass inside a code session", "params_refine_text": "the refine-text pass inside a code session"}
+
+
+def refuse_out_of_scope(kw: dict, instead: str) -> None:
+    """open_session(**kw): a name outside SESSION_OUT_OF_SCOPE is a TypeError as for any function; a named one that asks for the feature (not None / False, not
+    the values that mean "off": noise="device", num_candidates=1) is refused with the reason"""
+    for name, value in kw.items():
+        if name not in SESSION_OUT_OF_SCOPE:
+            raise TypeError(f"open_session() got an unexpected keyword argument {name!r}")
+        off = value is None or value is False or (name == "noise" and isinstance(value, str) and value == "device") or \
+            (name == "num_candidates" and isinstance(value, int) and value == 1)
+        if not off:
+            raise _lib.HipBackendError(f"open_session: {SESSION_OUT_OF_SCOPE[name]} ({name}=) is not offered inside a session; {instead}")
+
+
+@dataclass(repr=False, eq=False)
+class SessionResult:
+    """One utterance a DecodeSession delivered: clones, independent of the session's output buffers."""
+    ticket: int
+    utt_id: int
+    ids: torch.Tensor
+    hiddens: Optional[torch.Tensor] = None
+    logprobs: Optional[torch.Tensor] = None
+    sampled_logprobs: Optional[torch.Tensor] = None
+    final_logprobs: Optional[torch.Tensor] = None
+    finished_by_eos: bool = False
+    cancelled: bool = False
+    attempt: int = 0              # first-token-EOS regenerations before this result (ensure_non_empty)
+
+
+class DecodeSession:
+    """A generate state kept open (GPT.open_session): utterances are submitted and cancelled while others decode.  The decode batch is as wide as the utterances
+    in flight need -- it grows (ctts_gpt_grow + ctts_gpt_admit) when texts arrive and shrinks (ctts_gpt_compact) when they end -- instead of being opened at its
+    peak width.  Holds the engine's busy token until close(); a context manager.  Code mode, device noise."""
+
+    def __init__(self, gpt: "GPT", sc, seed: int, rows: int, out_slots: int, return_hidden: bool, return_logprobs: bool, ensure_non_empty: bool, max_restarts: int = 64):
+        self.gpt, self.sc, self.seed = gpt, sc, int(seed)
+        self.max_new = int(sc.max_new_token)
+        self.book = SessionBook(rows, out_slots, gpt.max_batch, gpt.max_seq, self.max_new, ensure_non_empty, max_restarts, gpt.compact)
+        dev, H, NVQ = gpt.device, gpt.model_dim, gpt.num_vq
+        self.ids = torch.empty(out_slots, self.max_new, NVQ, dtype=torch.int32, device=dev)
+        self.hid = torch.empty(out_slots, self.max_new, H, dtype=torch.float32, device=dev) if return_hidden else None
+        self.lps = torch.empty(2, out_slots, self.max_new, NVQ, dtype=torch.float32, device=dev) if return_logprobs else None
+        self.finish = torch.zeros(out_slots, dtype=torch.int32, device=dev)
+        self.end_idx = torch.zeros(out_slots, dtype=torch.int32, device=dev)
+        self.chunk = max(4, min(gpt.chunk_steps, gpt.compact_chunk))
+        self.batch_trace: List[tuple] = []         # (steps launched, rows) at every change of the row count
+        self.launched = 0
+        self._req = {}                             # ticket -> (emb [T,H] device, knobs or None, adapter slot)
+        self._pins = [torch.zeros(2 * int(rows), dtype=torch.int32).pin_memory() for _ in range(2)]
+        self._evs = [torch.cuda.Event() for _ in range(2)]
+        self._layouts = [None, None]
+        self._pending: List[int] = []
+        self._adapters = False                     # an utterance of this session named an adapter slot: every admission names its rows' slots from then on
+        self._open = True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _check_open(self):
+        if not self._open:
+            raise _lib.HipBackendError("DecodeSession: the session is closed")
+
+    # -- requests ---------------------------------------------------------------------------------
+    def submit(self, emb: torch.Tensor, mask: torch.Tensor, utt_id: int, limit: Optional[int] = None, sampling=None, adapter_slot: Optional[int] = None) -> int:
+        """Queues one utterance: emb [T, H] (GPT.__call__), mask [T] left padded.  `limit` <= max_new_token, `sampling` a dict as in sampling_per_row,
+        `adapter_slot` a resident adapter (load_adapter).  Returns its ticket."""
+        self._check_open()
+        g = self.gpt
+        emb = torch.as_tensor(emb)
+        mask = torch.as_tensor(mask).flatten()
+        if emb.dim() != 2 or emb.shape[1] != g.model_dim or mask.numel() != emb.shape[0]:
+            raise ValueError(f"submit: emb must be [T, {g.model_dim}] and mask [T] (got {tuple(emb.shape)}, {tuple(mask.shape)})")
+        _check_left_padded(mask.reshape(1, -1))
+        n = int((mask != 0).sum())
+        if n < 1:
+            raise ValueError("submit: the prompt has no attended token")
+        knobs = row_sampling_from_values(self.sc, sampling, g.num_vq) if sampling is not None else None
+        slot = -1 if adapter_slot is None or int(adapter_slot) < 0 else int(adapter_slot)
+        if slot >= 0 and g.options.get("batch_invariant", 0):
+            raise _lib.HipBackendError("submit: per-utterance adapters are outside the batch_invariant contract; merge the adapter (with_lora) or set the option to 0")
+        try:
+            tk = self.book.submit(n, utt_id, limit)
+        except ValueError as e:
+            raise _lib.HipBackendError(str(e)) from None
+        self._req[tk] = (emb[emb.shape[0] - n:].to(g.device, dtype=torch.float32).contiguous(), knobs, slot)
+        self._adapters = self._adapters or slot >= 0
+        return tk
+
+    def cancel(self, ticket: int) -> bool:
+        """A queued utterance is dropped at once, a seated one is cancelled on the device at the next step boundary; either is delivered by a later step() with
+        cancelled=True and the tokens written so far.  False: unknown ticket, already delivered or already cancelled."""
+        self._check_open()
+        return self.book.cancel(int(ticket)) is not None
+
+    # -- engine calls -------------------------------------------------------------------------------
+    def _prompts(self, tks):
+        """left-padded prompts [k, Ta, H] / [k, Ta] of the tickets, Ta = the longest of them"""
+        g = self.gpt
+        Ta = max(int(self._req[tk][0].shape[0]) for tk in tks)
+        emb = torch.zeros(len(tks), Ta, g.model_dim, dtype=torch.float32, device=g.device)
+        mask = torch.zeros(len(tks), Ta, dtype=torch.int32, device=g.device)
+        for i, tk in enumerate(tks):
+            e = self._req[tk][0]
+            emb[i, Ta - e.shape[0]:] = e
+            mask[i, Ta - e.shape[0]:] = 1
+        return Ta, emb, mask
+
+    def _arrays(self, tks):
+        u = self.book.utts
+        return (np.ascontiguousarray([u[tk]["utt_id"] for tk in tks], dtype=np.uint64), np.ascontiguousarray([u[tk]["limit"] for tk in tks], dtype=np.int32),
+                np.ascontiguousarray([u[tk]["slot"] for tk in tks], dtype=np.int32), np.ascontiguousarray([u[tk]["attempt"] for tk in tks], dtype=np.int32))
+
+    def _begin(self, seats, st):
+        g, lib, h = self.gpt, self.gpt._lib, self.gpt._h
+        tks = [tk for _, tk in seats]
+        R = len(tks)
+        Ta, emb, mask = self._prompts(tks)
+        uid_arr, lim_arr, _, _ = self._arrays(tks)
+        io = _lib.GenIO(ids=self.ids.data_ptr(), hiddens=self.hid.data_ptr() if self.hid is not None else None, finish=self.finish.data_ptr(),
+                        end_idx=self.end_idx.data_ptr(), noise=None, n_draws=self.max_new, seed=self.seed, utt_ids=uid_arr.ctypes.data, row_limits=lim_arr.ctypes.data)
+        if self._adapters:
+            g.set_row_adapters([self._req[tk][2] for tk in tks])
+        knobs = any(self._req[tk][1] is not None for tk in tks)
+        if knobs:
+            base = row_sampling_from_values(self.sc, None, g.num_vq)
+            _lib.check(lib.ctts_gpt_set_row_sampling(h, (_lib.RowSampling * R)(*[self._req[tk][1] or base for tk in tks]), R), "set_row_sampling")
+        try:
+            _lib.check(lib.ctts_gpt_begin(h, R, Ta, mask.data_ptr(), C.byref(self.sc), C.byref(io), st), "begin")
+        finally:
+            if knobs:
+                lib.ctts_gpt_set_row_sampling(h, None, 0)
+        if self.lps is not None:
+            _lib.check(lib.ctts_gpt_set_logprob_out(h, self.lps[0].data_ptr(), self.lps[1].data_ptr(), st), "set_logprob_out")
+        _lib.check(lib.ctts_gpt_prefill(h, emb.data_ptr(), st), "prefill")
+        _lib.check(lib.ctts_gpt_sample(h, st), "sample")
+        self.launched = 1
+        self.batch_trace.append((self.launched, R))
+
+    def _admit(self, seats, st):
+        g, lib, h = self.gpt, self.gpt._lib, self.gpt._h
+        rows, tks = [r for r, _ in seats], [tk for _, tk in seats]
+        k = len(tks)
+        Ta, emb, mask = self._prompts(tks)
+        uid_arr, lim_arr, out_arr, att_arr = self._arrays(tks)
+        rows_arr = np.ascontiguousarray(rows, dtype=np.int32)
+        if self._adapters:
+            sl_arr = np.ascontiguousarray([self._req[tk][2] for tk in tks], dtype=np.int32)
+            _lib.check(lib.ctts_gpt_admit_adapters(h, k, rows_arr.ctypes.data_as(C.c_void_p), sl_arr.ctypes.data_as(C.c_void_p), st), "admit_adapters")
+        if any(self._req[tk][1] is not None for tk in tks):
+            base = row_sampling_from_values(self.sc, None, g.num_vq)
+            _lib.check(lib.ctts_gpt_admit_sampling(h, k, rows_arr.ctypes.data_as(C.c_void_p), (_lib.RowSampling * k)(*[self._req[tk][1] or base for tk in tks]), st),
+                       "admit_sampling")
+        _lib.check(lib.ctts_gpt_admit(h, k, rows_arr.ctypes.data_as(C.c_void_p), Ta, mask.data_ptr(), emb.data_ptr(), uid_arr.ctypes.data_as(C.c_void_p),
+                                      lim_arr.ctypes.data_as(C.c_void_p), out_arr.ctypes.data_as(C.c_void_p), att_arr.ctypes.data_as(C.c_void_p), st), "admit")
+
+    def _result(self, tk: int, n: int, fin: int, cancelled: bool) -> SessionResult:
+        u = self.book.utts[tk]
+        s = u["slot"]
+        eos = bool(fin & 2)
+        if s is None or n == 0:
+            e = torch.empty(0, self.gpt.num_vq, dtype=torch.long, device=self.gpt.device)
+            res = SessionResult(ticket=tk, utt_id=u["utt_id"], ids=e, hiddens=self.hid[0, :0].clone() if self.hid is not None else None,
+                                logprobs=self.lps[0, 0, :0].clone() if self.lps is not None else None,
+                                sampled_logprobs=self.lps[1, 0, :0].clone() if self.lps is not None else None, finished_by_eos=eos, cancelled=cancelled,
+                                attempt=u["attempt"])
+            if s is not None and self.lps is not None and eos:
+                res.final_logprobs = self.lps[:, s, 0].clone()
+        else:
+            res = SessionResult(ticket=tk, utt_id=u["utt_id"], ids=self.ids[s, :n].to(torch.long), hiddens=self.hid[s, :n].clone() if self.hid is not None else None,
+                                logprobs=self.lps[0, s, :n].clone() if self.lps is not None else None,
+                                sampled_logprobs=self.lps[1, s, :n].clone() if self.lps is not None else None,
+                                final_logprobs=self.lps[:, s, n].clone() if (self.lps is not None and eos and n < self.max_new) else None,
+                                finished_by_eos=eos, cancelled=cancelled, attempt=u["attempt"])
+        self.book.release(tk)
+        self._req.pop(tk, None)
+        return res
+
+    # -- the loop ---------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self) -> List[SessionResult]:
+        """One chunk of decode steps is launched, the previous chunk's row report is read (two chunks stay enqueued, as in generate_many): finished utterances
+        are delivered, first-token-EOS ones queued again with their next attempt, and the batch is rebalanced -- queued utterances into free rows, then into
+        rows the batch grows by, else a compaction.  With nothing live and nothing queued nothing is launched."""
+        self._check_open()
+        g, lib, h, book = self.gpt, self.gpt._lib, self.gpt._h, self.book
+        out = [self._result(tk, 0, 1, True) for tk in book.take_dropped()]
+        if book.idle():
+            return out
+        with torch.cuda.device(g.device):
+            st = g._stream()
+            if not book.begun:
+                plan = book.plan()
+                if plan.begin:
+                    self._begin(plan.begin, st)
+                return out
+            rows = book.cancel_rows()
+            if rows:
+                arr = np.ascontiguousarray(rows, dtype=np.int32)
+                _lib.check(lib.ctts_gpt_cancel(h, len(rows), arr.ctypes.data_as(C.c_void_p), st), "cancel")
+            if book.n_live() > 0:
+                _lib.check(lib.ctts_gpt_decode(h, self.chunk, 1 if g.use_graph else 0, st), "decode")
+                self.launched += self.chunk
+                slot = 1 - self._pending[-1] if self._pending else 0
+                _lib.check(lib.ctts_gpt_rows_enqueue(h, self._pins[slot].data_ptr(), st), "rows_enqueue")
+                self._layouts[slot] = book.book.layout()
+                self._evs[slot].record(torch.cuda.current_stream(g.device))
+                self._pending.append(slot)
+                if len(self._pending) == 2:
+                    slot = self._pending.pop(0)
+                    self._evs[slot].synchronize()
+                    lay = self._layouts[slot]
+                    states = self._pins[slot][:2 * len(lay)].view(-1, 2).tolist()
+                    out += [self._result(*r) for r in book.report(lay, states)]
+            plan = book.plan()
+            if plan.grow:
+                _lib.check(lib.ctts_gpt_grow(h, plan.grow, st), "grow")
+            if plan.admit:
+                self._admit(plan.admit, st)
+            if plan.compact is not None:
+                karr = np.ascontiguousarray(plan.compact, dtype=np.int32)
+                _lib.check(lib.ctts_gpt_compact(h, karr.ctypes.data_as(C.c_void_p), int(karr.size), st), "compact")
+            if plan.grow or plan.compact is not None:
+                self.batch_trace.append((self.launched, len(book.book.row_tk)))
+        return out
+
+    def drain(self) -> List[SessionResult]:
+        """steps until nothing is queued or live; everything delivered on the way"""
+        out = []
+        while not self.book.idle():
+            out += self.step()
+        return out
+
+    def close(self) -> None:
+        """Ends the session (utterances still queued or decoding are abandoned) and releases the engine."""
+        if not self._open:
+            return
+        self._open = False
+        g = self.gpt
+        try:
+            if self.book.begun and getattr(g, "_h", None) and g._h.value:
+                with torch.cuda.device(g.device):
+                    st = g._stream()
+                    torch.cuda.current_stream(g.device).synchronize()
+                    steps, alld = C.c_int32(0), C.c_int32(0)
+                    _lib.check(g._lib.ctts_gpt_progress(g._h, C.byref(steps), C.byref(alld), st), "progress")
+                    g.saturations = g._report_saturations(g._h, st, "session")
+                    if self._adapters:
+                        g.set_row_adapters(None)
+        finally:
+            if g._busy_token.owner is self:
+                g._busy_token.owner = None
+
+
 class _BusyToken:
     """One generate() at a time per KV cache: shared by every engine bound to the same KV tensor (LoRA-merged siblings, with_lora)."""
     def __init__(self):
@@ -484,8 +904,9 @@ class GPT:
         """Destroys the engine handle (packed weights, workspaces, graphs) now instead of at garbage collection; the KV
         tensor is released with the last engine that shares it.  Refused while a generate() generator of THIS engine is live (its
         native handle is in use): exhaust or close the generator first."""
-        if not _force and getattr(self, "_busy_token", None) is not None and self._busy_token.owner is self:
-            raise _lib.HipBackendError("GPT.close(): a generate() generator is still live on this engine; exhaust or close it first")
+        owner = getattr(getattr(self, "_busy_token", None), "owner", None)
+        if not _force and owner is not None and (owner is self or getattr(owner, "gpt", None) is self):
+            raise _lib.HipBackendError("GPT.close(): a generate() generator or a session (open_session) is still live on this engine; exhaust or close it first")
         if getattr(self, "_h", None) and self._h.value:
             self._lib.ctts_gpt_destroy(self._h)
             self._h = C.c_void_p()
@@ -1189,6 +1610,36 @@ class GPT:
                 lps = lps.index_select(1, inv) if lps is not None else None
                 finish = finish.index_select(0, inv)
             return self._outputs(ids, hid, end_idx, infer_text, lps, finish)
+
+    # -- serving session (ctts_gpt_grow / ctts_gpt_cancel) ------------------------------------------------------------------------
+    def open_session(self, temperature, eos_token, max_new_token, min_new_token=0, logits_warpers=[], logits_processors=[], return_hidden=False,
+                     return_logprobs=False, seed: Optional[int] = None, rows: Optional[int] = None, out_slots: Optional[int] = None, ensure_non_empty=True,
+                     **out_of_scope) -> DecodeSession:
+        """Opens a DecodeSession: a generate state that stays open while utterances are submitted (submit), cancelled (cancel) and delivered (step / drain).  The
+        sampling arguments are the call's values, as in generate_many; an utterance may bring its own (submit(sampling=...)).  `rows` <= max_batch bounds the
+        decode batch (default max_batch), `out_slots` the utterances whose results are held at once (default 2 * rows; slots are recycled once a result has been
+        cloned out).  Holds the engine until close(): generate* and score raise meanwhile.  Not offered inside a session, each refused with a message:
+        shared prompt passes / num_candidates, caller-supplied noise, per-utterance streaming windows, infer_sharded, the refine-text pass (the engine runs
+        one mode at a time: refine first, submit the refined text)."""
+        if not self._finalized:
+            raise _lib.HipBackendError("weights not loaded")
+        refuse_out_of_scope(out_of_scope, "use generate() / generate_many() / infer() for it")
+        rows = self.max_batch if rows is None else int(rows)
+        if not (1 <= rows <= self.max_batch):
+            raise _lib.HipBackendError(f"open_session: rows={rows} outside 1..max_batch={self.max_batch}")
+        out_slots = 2 * rows if out_slots is None else int(out_slots)
+        if out_slots < 1:
+            raise _lib.HipBackendError(f"open_session: out_slots={out_slots} (at least one)")
+        if self._busy_token.owner is not None:
+            raise _lib.HipBackendError("GPT.open_session: GPT.generate is already running on this engine (or on an engine sharing its KV cache): exhaust or close "
+                                       "the previous generator / session first")
+        sc = sampler_cfg_from_objects(temperature, int(eos_token), int(max_new_token), min_new_token, logits_warpers, logits_processors, self.num_vq)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        with torch.cuda.device(self.device):
+            ses = DecodeSession(self, sc, seed, rows, out_slots, bool(return_hidden), bool(return_logprobs), bool(ensure_non_empty))
+        self._busy_token.owner = ses
+        return ses
 
     # -- teacher-forced scoring (train_lora.py:430-469; ctts_gpt_score) ----------------------------------------------------------
     @torch.no_grad()

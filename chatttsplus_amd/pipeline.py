@@ -68,7 +68,7 @@ class TorchSeedContext:                        # reference commons/utils.py:48-5
 
 # gen_logits and its scalar carriers live beside the sampler configuration they feed (hip_models/gpt.py): one conversion for a call's knobs and for an
 # utterance's (sampling_per_row)
-from .hip_models.gpt import LORA_TARGETS, _RepPenalty, _TopK, _TopP, check_lora_shapes, gen_logits  # noqa: E402,F401
+from .hip_models.gpt import LORA_TARGETS, _RepPenalty, _TopK, _TopP, check_lora_shapes, gen_logits, refuse_out_of_scope  # noqa: E402,F401
 
 
 # params_per_utterance (ChatTTSPlusPipeline.infer / infer_sharded): the InferCodeParams fields one utterance may set for itself.  The sampling knobs
@@ -200,6 +200,108 @@ def select_candidate(scores) -> int:
         if best_s is None or v > best_s:
             best, best_s = k, v
     return best
+
+
+@dataclass(repr=False, eq=False)
+class SessionDetails:
+    """What SynthSession.poll returns per utterance instead of the bare waveform under open_session(return_details=True): one utterance's entry of InferDetails."""
+    wav: torch.Tensor
+    ids: torch.Tensor
+    logprobs: torch.Tensor
+    sampled_logprobs: torch.Tensor
+    mean_logprob: float
+    finished_by_eos: bool = False
+
+
+class SynthSession:
+    """A serving session of the pipeline (ChatTTSPlusPipeline.open_session): texts are submitted and cancelled while others are being spoken.  A
+    GPT.DecodeSession (elastic decode batch, ctts_gpt_grow / ctts_gpt_cancel) under the prompt building of infer() and the batched vocoder.  Texts are
+    already refined (the engine runs one mode at a time: refine first with infer(refine_text_only=True), submit the refined text)."""
+
+    def __init__(self, pipe, gpt, params: InferCodeParams, use_decoder: bool, rows, seed, return_details: bool):
+        self.pipe, self.gpt, self.params, self.use_decoder, self.return_details = pipe, gpt, params, bool(use_decoder), bool(return_details)
+        num_code = int(gpt.emb_code[0].num_embeddings - 1)
+        warpers, processors = gen_logits(num_code=num_code, top_P=params.top_P, top_K=params.top_K, repetition_penalty=params.repetition_penalty)
+        temperature = params.temperature if isinstance(params.temperature, list) else [params.temperature] * gpt.num_vq
+        self.session = gpt.open_session(torch.tensor(temperature), num_code, params.max_new_token, min_new_token=params.min_new_token, logits_warpers=warpers,
+                                        logits_processors=processors, return_hidden=self.use_decoder, return_logprobs=self.return_details, seed=seed, rows=rows,
+                                        ensure_non_empty=params.ensure_non_empty)
+        self._paths = []                           # adapters utterances of this session named: all stay resident (at most _lib.MAX_ADAPTERS)
+        self._auto_id = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    @property
+    def batch_trace(self):
+        return self.session.batch_trace
+
+    def submit(self, text: str, params=None, lora_path: Optional[str] = None, utt_id: Optional[int] = None, max_new_token: Optional[int] = None) -> int:
+        """Queues one already-refined text.  `params`: this utterance's overrides (an InferCodeParams or a dict, checked by per_utterance_overrides:
+        sampling knobs, max_new_token, prompt, spk_emb); `lora_path`: its own adapter; `utt_id`: its noise key (default: a counter).  Returns its ticket."""
+        if not isinstance(text, str):
+            raise _lib.HipBackendError("SynthSession.submit takes one text (a str) per call")
+        pipe, gpt, base = self.pipe, self.gpt, self.params
+        diff = per_utterance_overrides(base, [params])[0] if params is not None else {}
+        if max_new_token is not None:
+            if "max_new_token" in diff:
+                raise _lib.HipBackendError("submit: max_new_token and a per-utterance params.max_new_token are exclusive")
+            diff["max_new_token"] = int(max_new_token)
+        if int(diff.get("max_new_token", base.max_new_token)) > base.max_new_token:
+            raise _lib.HipBackendError(f"submit: max_new_token={diff['max_new_token']} exceeds the session's {base.max_new_token}")
+        slot = None
+        if lora_path:
+            paths = list(dict.fromkeys(self._paths + [lora_path]))
+            if len(paths) > _lib.MAX_ADAPTERS:
+                raise _lib.HipBackendError(f"submit: {len(paths)} distinct adapters in this session; the engine holds {_lib.MAX_ADAPTERS}")
+            slot = pipe._adapter_slots(gpt, paths)[paths.index(lora_path)]
+            self._paths = paths
+        t = pipe.normalizer(text, True, True, None)                      # infer()'s defaults
+        t = t if t.strip().endswith("[uv_break]") else t + " [uv_break]"      # pipeline:414-416
+        pic = dataclasses.replace(base, spk_emb=diff["spk_emb"]) if "spk_emb" in diff else base
+        input_ids, attention_mask, text_mask = pipe._code_prompt([t], pic, gpt, [diff["prompt"] or ""] if "prompt" in diff else None)
+        emb = gpt(input_ids, text_mask, spk_emb=pic.spk_emb, spk_emb_ids=pipe.models_dict["tokenizer"].spk_emb_ids)
+        if utt_id is None:
+            utt_id, self._auto_id = self._auto_id, self._auto_id + 1
+        sampling = {k: diff[k] for k in PER_UTTERANCE_SAMPLING if k in diff} or None
+        return self.session.submit(emb[0], attention_mask[0], int(utt_id), limit=diff.get("max_new_token"), sampling=sampling, adapter_slot=slot)
+
+    def cancel(self, ticket: int) -> bool:
+        return self.session.cancel(ticket)
+
+    def _deliver(self, results):
+        spoken = [r for r in results if r.ids.shape[0] > 0]
+        wavs = self.pipe._decode_to_wavs([(r.hiddens if self.use_decoder else r.ids) for r in spoken], self.use_decoder) if spoken else []
+        wav_of = {r.ticket: w for r, w in zip(spoken, wavs)}
+        out = []
+        for r in results:
+            w = wav_of.get(r.ticket)
+            if w is None:
+                w = torch.zeros(0, device=self.pipe.device)
+            if self.return_details:
+                w = SessionDetails(wav=w, ids=r.ids, logprobs=r.logprobs.cpu(), sampled_logprobs=r.sampled_logprobs.cpu(), mean_logprob=mean_logprob(r.logprobs.cpu()),
+                                   finished_by_eos=r.finished_by_eos)
+            out.append((r.ticket, w, r.cancelled))
+        return out
+
+    @torch.no_grad()
+    def poll(self):
+        """One DecodeSession.step(); what finished is vocoded in one batch.  Returns [(ticket, wav or SessionDetails, cancelled)]: a cancelled utterance with at
+        least one token is vocoded, one with none yields an empty waveform."""
+        return self._deliver(self.session.step())
+
+    def drain(self):
+        out = []
+        while not self.session.book.idle():
+            out += self.poll()
+        return out
+
+    def close(self) -> None:
+        self.session.close()
 
 
 def _get(cfg, key, default=None):
@@ -1057,6 +1159,20 @@ class ChatTTSPlusPipeline:
             params_infer_code.spk_emb = self.sample_random_speaker()
         return self._infer(text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                            do_text_optimization, do_homophone_replacement, params_refine_text, params_infer_code, **kwargs)
+
+    # -- serving session (no counterpart in the reference) ------------------------------------------------------------------------
+    def open_session(self, params_infer_code: Optional[InferCodeParams] = None, use_decoder: bool = True, lora_path: Optional[str] = None, rows: Optional[int] = None,
+                     seed: Optional[int] = None, return_details: bool = False, **out_of_scope) -> SynthSession:
+        """A SynthSession: submit(text) / cancel(ticket) / poll() / drain() / close() while the engine keeps decoding -- the decode batch grows when texts arrive
+        and shrinks when they end.  `params_infer_code` are the session's values (speaker included; a random one is sampled if it names none), `lora_path` one
+        merged adapter for the whole session (an utterance may name its own at submit), `rows` bounds the decode batch, `seed` keys the device noise.
+        Not offered inside a session (refused): num_candidates / shared prompt passes, caller-supplied noise, stream=True windows, infer_sharded, the
+        refine-text pass."""
+        refuse_out_of_scope(out_of_scope, "use infer() for it (refine first with infer(refine_text_only=True) and submit the refined text)")
+        params = dataclasses.replace(params_infer_code if params_infer_code is not None else InferCodeParams())
+        if params.spk_emb is None and params.spk_smp is None:
+            params.spk_emb = self.sample_random_speaker()
+        return SynthSession(self, self._gpt_for_lora(lora_path), params, use_decoder, rows, seed, return_details)
 
     # -- multi-GPU: utterance sharding (SURVEY 8e; BASELINE configs[3]: batch 256 over 8 GPUs) --------------------------------
     @torch.no_grad()

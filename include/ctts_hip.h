@@ -143,7 +143,7 @@ void ctts_gpt_destroy(ctts_gpt* h);
 int ctts_gpt_set_option(ctts_gpt* h, const char* name, int value);
 int ctts_gpt_get_option(ctts_gpt* h, const char* name, int* value);      /* every option that can be set can be read; the EFFECTIVE value ("persistent_rows" reads 0 where the mode is unavailable) */
 
-/* Diagnostics (tools/persist_probe.py): copies a named internal buffer to HOST memory -- "x_dec", "q_buf", "logits", "pl_g" (the persistent
+/* Diagnostics (tools/persist_probe.py): copies a named internal buffer to HOST memory -- "x_dec", "q_buf", "logits", "meta_dec" ({KV lane, pos, slot, kv_start} per decode row), "pl_g" (the persistent
  * layer's granule buffers), "pl_ts" (its per-workgroup phase marks, option "persistent_timestamps"), "pl_state" ({epoch, error}), "xh" / "ssq" (the packed residual copy and its per-tile sums of squares).  Synchronises. */
 int ctts_gpt_debug_read(ctts_gpt* h, const char* name, void* out, size_t max_bytes, size_t* bytes, void* stream);
 
@@ -341,6 +341,26 @@ int ctts_gpt_compact(ctts_gpt* h, const int32_t* keep_rows, int n_keep, void* st
  * ctts_gpt_admit_adapters first.  Asynchronous. */
 int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, const int32_t* mask, const float* emb, const uint64_t* utt_ids,
                    const int32_t* row_limits, const int32_t* out_index, const int32_t* attempts, void* stream);
+
+/* Elastic batch and cancellation (no counterpart in the reference): what a serving session needs between two ctts_gpt_decode calls, next to compact and admit.
+ * Both are asynchronous, never synchronise, and work in code mode and text mode alike.
+ *   grow    appends `n` dead rows B .. B+n-1 to the decode batch (B + n <= max_batch).  A dead row is a finished row that holds no utterance: it counts as
+ *           finished (ctts_gpt_progress, rows_enqueue report {1, 0}), writes nothing into the output arrays, carries the call's sampling knobs and no adapter,
+ *           and is parked on slot 0 of a KV lane no row of the batch uses (the lowest free lanes of [0, max_batch): after a compaction these are not B ..).
+ *           Seat utterances in the new rows with ctts_gpt_admit (+ admit_adapters / admit_sampling).  The next ctts_gpt_decode plans its launches, picks its
+ *           graphs and its persistent-launch limit by the new row count, exactly as after ctts_gpt_compact; "batch_invariant" engines accept the call (the
+ *           option pins every choice that depends on the row count).  Device noise only, as ctts_gpt_admit.  No ctts_gpt_restart afterwards.
+ *   cancel  rows = HOST [n] current row indices, distinct.  Every named row that is still live becomes a finished row where it stands: finish[out] stays 0
+ *           (EOS not seen), end_idx[out] keeps the number of tokens written, nothing more is written for it.  Rows that had already finished are left alone
+ *           (decided on the device: the host cannot know).  The row count does not change, so the other rows' launches -- and results -- are those of the
+ *           same schedule without the call.  When the last live row is cancelled the batch reports all-finished.
+ * Both act on the generate state of the last ctts_gpt_begin, which outlives the call that began it: the output arrays handed to that begin (ids, hiddens, log-probs,
+ * finish, end_idx) must still be alive when rows are grown and admitted, as for ctts_gpt_admit -- the engine keeps the pointers, not the memory.
+ * Not offered inside one generate state: caller-supplied noise with grow; a session on top of these (GPT.open_session) additionally refuses shared prompt
+ * passes / num_candidates, per-utterance streaming windows, infer_sharded and the refine-text pass inside a code session (the engine runs one mode at a time:
+ * refine first, submit the refined text). */
+int ctts_gpt_grow(ctts_gpt* h, int n, void* stream);
+int ctts_gpt_cancel(ctts_gpt* h, int n, const int32_t* rows_host, void* stream);
 
 /* Adapter slots (ctts_gpt_set_adapter; -1 = none) of the utterances the NEXT ctts_gpt_admit call seats in `rows`; rows not named keep theirs.  When no
  * live row carries an adapter any more the engine drops back to the plain launches. */
