@@ -115,6 +115,9 @@ SYMBOLS = [
     ("ctts_gpt_admit_adapters", C.c_int, [_P, C.c_int, _P, _P, _P]),
     ("ctts_gpt_set_row_sampling", C.c_int, [_P, _P, C.c_int]),
     ("ctts_gpt_admit_sampling", C.c_int, [_P, C.c_int, _P, _P, _P]),
+    ("ctts_gpt_enable_text_rows", C.c_int, [_P, C.POINTER(SamplerCfg), _P, _P]),
+    ("ctts_gpt_set_row_modes", C.c_int, [_P, _P, C.c_int]),
+    ("ctts_gpt_admit_modes", C.c_int, [_P, C.c_int, _P, _P, _P]),
     ("ctts_gpt_share_prompts", C.c_int, [_P, C.c_int, _P, C.c_int]),
     ("ctts_gpt_set_logprob_out", C.c_int, [_P, _P, _P, _P]),
     ("ctts_gpt_logits", C.c_int, [_P, _P, _P]),

@@ -46,7 +46,8 @@ struct RowState {
     int limit;           // the row stops after this many tokens
     unsigned uid_lo, uid_hi;   // global utterance id
     int out;             // index of the utterance in ids / hiddens / finish / end_idx (and in the caller-supplied noise rows)
-    int pad1;
+    int mode;            // 0 = code row (4 codebook rows, code heads, sampler_generate_kernel), 1 = text row (refine-text: one row under the text head, sampler_text_kernel;
+                         //   ctts_gpt_enable_text_rows).  Travels with the record: admit seats it, grow's dead rows are code rows, compact / cancel / restart keep it
 };
 
 // Per decode ROW sampling knobs (ctts_row_sampling of the header, same layout): what one utterance may choose for itself.  The table lives right

@@ -88,6 +88,16 @@ struct ctts_gpt {
     void* whead = nullptr;
     void* whead_text = nullptr;                  // refine-text head (21178 x H), packed like whead; optional
     int text_mode = 0;                           // current generate() call: infer_text=True
+    // text rows beside code rows in one decode batch (ctts_gpt_enable_text_rows; RowState.mode): the mode is a property of the ROW, the call stays a code-mode call
+    int text_rows_on = 0;                        //   the current generate state has its text block (begin switches it off again)
+    int text_live = 0;                           //   rows of the batch whose mode is 1, finished ones included ("text_rows_live"): > 0 = the step is MIXED -- two more launches
+                                                 //   (text head, text sampler); decided from the host mirror below, as lora_mlp is
+    std::vector<int> row_mode;                   //   host mirror: mode of every current decode row (moves with row_seq)
+    std::vector<int> modes_req;                  //   what ctts_gpt_set_row_modes asked for, per sequence ("the following begin calls")
+    std::vector<std::pair<int, int>> modes_admit;   // ctts_gpt_admit_modes: (row, mode) of the utterances the next ctts_gpt_admit seats
+    SamplerCfgDev sc_text = {};                  //   the text rows' sampling parameters (the refine pass's ctts_sampler_cfg)
+    SamplerDyn* dyn_text = nullptr;              //   device: the text block -- sc_text, the text ids array, and the code block's finish / end_idx / seed
+    float* logits_text = nullptr;                //   [max_batch][vocab_text_head]; both allocated by the first ctts_gpt_enable_text_rows
     float* lnf = nullptr;
     float* emb_code = nullptr;
     float* emb_text = nullptr;                   // [V_text][H] prompt embedding table (optional)
@@ -459,6 +469,7 @@ static const OptRow g_options[] = {
     {"down_splitk_rows", &ctts_gpt::down_sk_rows, OPT_MIN(0), OPT_RW | OPT_PIN, 1, HOOK_NONE},     // see down_sk_rows
     {"graph_steps", &ctts_gpt::graph_steps, OPT_RANGE(1, 64), OPT_RW, 0, HOOK_NONE},
     {"graph_steps_persistent", &ctts_gpt::graph_steps_persist, OPT_RANGE(1, 64), OPT_RW, 0, HOOK_NONE},
+    {"text_rows_live", &ctts_gpt::text_live, OPT_ANY, OPT_R, 0, HOOK_NONE},    // read only: rows of the decode batch whose mode is 1 (ctts_gpt_enable_text_rows); > 0 = every step runs the text head and the text sampler too
     {"lora_mlp_live", &ctts_gpt::lora_mlp, OPT_ANY, OPT_R, 0, HOOK_NONE},      // read only: 1 while a live row's adapter names gate / up / down (the two MLP launches per layer run, decode on the launch chain)
 };
 static const OptRow* find_option(const char* name, int access) {
@@ -750,6 +761,13 @@ static RowSampling knobs_of_abi(const ctts_row_sampling& p) {
     memcpy(&r, &p, sizeof(r));
     r.pad = 0;
     return r;
+}
+// field by field (not the bytes: nothing may hang on two builders' padding)
+static bool same_knobs(const RowSampling& a, const RowSampling& b) {
+    for (int v = 0; v < CTTS_NUM_VQ; ++v) if (a.temperature[v] != b.temperature[v]) return false;
+    for (int i = 0; i < 17; ++i) if (a.penalty_table[i] != b.penalty_table[i]) return false;
+    return a.top_p_threshold == b.top_p_threshold && a.top_k == b.top_k && a.min_keep == b.min_keep && a.use_penalty == b.use_penalty &&
+           a.past_window == b.past_window && a.min_new == b.min_new;
 }
 static int check_knobs(const ctts_row_sampling& p, int max_new, const char* who, int i) {
     for (int v = 0; v < CTTS_NUM_VQ; ++v)
@@ -1191,7 +1209,9 @@ static LayerPlan plan_layers(const ctts_gpt* h, int R, bool decode, DecodePath p
     if (p.persist) {
         // the launch that ends the stack also runs the final norm + the 4 code heads (persist_layer.hip phase H): code mode, paced schedule, images built
         // (ms/step separate heads launch / fused, tools/ab_options.py: fp32 batch 1 0.2798 / 0.2786, 2 0.3396 / 0.3384, 4 0.4711 / 0.4721; fp16 batch 3 0.3793 / 0.3800 -> up to 2 rows)
-        p.fuse_heads = h->persist_heads && R <= 2 && !h->text_mode && h->persist_sched == 3 && h->pimg_head != nullptr && h->dyn != nullptr;
+        // (not in a mixed step, text rows beside code rows: the fused heads read the stack's output from the launch's granules and leave x_dec at the stack's INPUT --
+        //  the text head of a mixed step reads x_dec, so such a step ends with the separate heads launches)
+        p.fuse_heads = h->persist_heads && R <= 2 && !h->text_mode && h->text_live == 0 && h->persist_sched == 3 && h->pimg_head != nullptr && h->dyn != nullptr;
         p.form = stream_form(h, false, false, p.fuse_heads, false);
         // (persistent_layers_per_launch, default all: the whole stack is ONE launch; 1 = a launch per layer, the first version of the structure)
         p.per = (h->persist_lpl > 0 && h->persist_lpl < h->L) ? h->persist_lpl : h->L;
@@ -1359,20 +1379,22 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
     return 0;
 }
 // final RMSNorm + heads on the h->B decode rows; `form` = how the last run_layers left them (plain_form after a prompt pass / restart)
-static int run_heads(ctts_gpt* h, bool write_hidden, StreamForm form, hipStream_t s) {
+// `mixed_text`: the text head of a mixed step (text rows beside code rows) -- the text-mode launch over all rows into the text logits, no hidden rows
+static int run_heads(ctts_gpt* h, bool write_hidden, StreamForm form, hipStream_t s, bool mixed_text = false) {
     const int nbg = form.nbg, chunks = (h->B + 16 * nbg - 1) / (16 * nbg);
+    const bool text = h->text_mode || mixed_text;
     GemmArgs a = {};
     a.st = h->st; a.R = h->B; a.eps = 1e-6f; a.meta = h->meta_dec;
     a.valu = form.valu;
-    const int nv = h->text_mode ? h->vocab_text_head : h->NVQ * h->V;
-    a.W = h->text_mode ? h->whead_text : h->whead; a.n_row_tiles = (nv + 15) / 16; a.K = h->H; a.x = h->x_dec; a.lnw = h->lnf;
-    a.logits = h->logits; a.n_valid = nv;
-    a.dyn = write_hidden ? h->dyn : nullptr;       // the kernel tests dyn->hidden_out itself
+    const int nv = text ? h->vocab_text_head : h->NVQ * h->V;
+    a.W = text ? h->whead_text : h->whead; a.n_row_tiles = (nv + 15) / 16; a.K = h->H; a.x = h->x_dec; a.lnw = h->lnf;
+    a.logits = mixed_text ? h->logits_text : h->logits; a.n_valid = nv;
+    a.dyn = (write_hidden && !mixed_text) ? h->dyn : nullptr;       // the kernel tests dyn->hidden_out itself
     a.rows = h->finend;
     a.opart = h->dpart; a.np = form.parts ? 4 : 0;
     // the last down projection left the rows as packed fp16 + sums of squares (PRO_XH): no fp32 re-normalisation per block.  The text head is a
     // different launch shape (not measured): it keeps the fp32 prologue
-    if (form.xh && !h->text_mode && h->xh_heads && (!form.split || h->whead_sp != nullptr)) {
+    if (form.xh && !text && h->xh_heads && (!form.split || h->whead_sp != nullptr)) {
         a.xh = h->xh; a.ssq = h->ssq; a.scale_in = h->scale_d;
         if (form.split) a.W = h->whead_sp;
         return launch_gemm(form.split ? 2 : h->cfg.dtype, nbg, PRO_XH, EPI_LOGITS, a, chunks, s);
@@ -1382,11 +1404,29 @@ static int run_heads(ctts_gpt* h, bool write_hidden, StreamForm form, hipStream_
 
 static int run_sample_phase(ctts_gpt* h, StreamForm form, hipStream_t s) {
     if (!form.logits && run_heads(h, true, form, s)) return 1;      // (the persistent launch that ended the stack wrote the logits and the hidden rows itself)
+    // Mixed step (a row of the batch is a text row, host mirror text_live): the code heads ran over ALL rows as in any step -- as a launch of their own: the persistent
+    // launch drops its fused heads in mixed steps (plan_layers), a text row's code logits are simply not read -- then the text head over all rows into the text logits,
+    // the code sampler (its text rows' blocks return) and the text sampler on the text block (its code rows' blocks return).  Every row takes its ticket once, in the kernel of its mode; the last
+    // arriver, whichever kernel it runs in, advances the step state.  Both samplers read x_dec-independent inputs (logits, row records) and each writes only its
+    // own rows' x_dec / meta / RoPE rows, so the text head must read x_dec BEFORE either of them runs: it is launched first.
+    const bool mixed = !h->text_mode && h->text_live > 0;
+    if (mixed) {
+        if (!h->text_rows_on || !h->dyn_text || !h->logits_text) {
+            ctts_set_error("sample / decode: a row of the batch is a text row (mode 1) but ctts_gpt_enable_text_rows has not been called for this generate state");
+            return 1;
+        }
+        StreamForm tf = form;
+        tf.logits = false;
+        if (run_heads(h, false, tf, s, true)) return 1;
+    }
     SamplerArgs sa = {};
     sa.dyn = h->dyn; sa.logits = h->logits; sa.V = h->text_mode ? h->vocab_text_head : h->V; sa.B = h->B; sa.st = h->st;
-    sa.text_mode = h->text_mode;
+    sa.text_mode = h->text_mode; sa.mixed = mixed ? 1 : 0;
     sa.emb_code = h->text_mode ? h->emb_text : h->emb_code; sa.H = h->H; sa.x_next = h->x_dec; sa.meta = h->meta_dec; sa.rope = h->rope; sa.rope_rows = h->rope_dec;
     sa.hist_ring = h->hist_ring; sa.finend = h->finend;
+    if (launch_sampler(sa, h->B, s)) return 1;
+    if (!mixed) return 0;
+    sa.dyn = h->dyn_text; sa.logits = h->logits_text; sa.V = h->vocab_text_head; sa.text_mode = 1; sa.emb_code = h->emb_text;
     return launch_sampler(sa, h->B, s);
 }
 
@@ -1511,7 +1551,23 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
         if ((int)share.size() != B) { ctts_set_error("begin: ctts_gpt_share_prompts named the prompts of %d sequences, this call has B=%d", (int)share.size(), B); return 1; }
         if (sc->infer_text) { ctts_set_error("begin: shared prompt passes (ctts_gpt_share_prompts) are code mode only; the refine-text pass (infer_text) runs every prompt"); return 1; }
     }
+    // row modes of this call (ctts_gpt_set_row_modes): checked before anything changes
+    bool any_text = false;
+    for (int b = 0; b < B && b < (int)h->modes_req.size(); ++b) any_text = any_text || h->modes_req[b] == 1;
+    if (any_text) {
+        if (sc->infer_text) { ctts_set_error("begin: text rows (ctts_gpt_set_row_modes) live in a code-mode call; this call's own infer_text is 1 -- every row of it is a text row already"); return 1; }
+        if (!h->whead_text || !h->emb_text) { ctts_set_error("begin: a text row (ctts_gpt_set_row_modes) needs head_text.* and emb_text.weight"); return 1; }
+        if (io->noise != nullptr) { ctts_set_error("begin: text rows (ctts_gpt_set_row_modes) need device noise (caller-supplied noise is laid out for one mode's rows)"); return 1; }
+        if (!share.empty()) { ctts_set_error("begin: shared prompt passes (ctts_gpt_share_prompts) are for code rows; this call seats a text row (ctts_gpt_set_row_modes)"); return 1; }
+        const RowSampling call_knobs = knobs_of_cfg(cfg_of_abi(*sc));      // (set_row_sampling names every sequence: an entry equal to the call's values is no knob of its own)
+        for (int b = 0; b < B && b < (int)h->knobs_req.size() && b < (int)h->modes_req.size(); ++b)
+            if (h->modes_req[b] == 1 && !same_knobs(h->knobs_req[b], call_knobs)) {
+                ctts_set_error("begin: sequence %d is a text row (ctts_gpt_set_row_modes) and carries per-row sampling knobs (ctts_gpt_set_row_sampling); text rows keep the values of ctts_gpt_enable_text_rows", b);
+                return 1;
+            }
+    }
     h->text_mode = sc->infer_text ? 1 : 0;
+    h->text_rows_on = 0; h->text_live = 0; h->modes_admit.clear();      // every begin switches text rows off again: ctts_gpt_enable_text_rows follows it
     if (h->text_mode) {
         if (!h->whead_text || !h->emb_text) { ctts_set_error("begin: infer_text needs head_text.* and emb_text.weight"); return 1; }
         if (sc->use_penalty) { ctts_set_error("begin: infer_text supports repetition_penalty == 1 only (the reference's processor mis-broadcasts the [B,n,1] history in this mode)"); return 1; }
@@ -1541,7 +1597,10 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
         r.limit = lim < 1 ? 1 : (lim > sc->max_new_token ? sc->max_new_token : lim);
         r.uid_lo = (unsigned)uid; r.uid_hi = (unsigned)(uid >> 32);
         r.out = b;
+        r.mode = (any_text && b < (int)h->modes_req.size() && h->modes_req[b] == 1) ? 1 : 0;
     }
+    h->row_mode.assign(B, 0);
+    for (int b = 0; b < B; ++b) { h->row_mode[b] = h->rows_host[b].mode; h->text_live += h->rows_host[b].mode; }
     h->row_seq.resize(B); h->row_ctx.assign(B, T); h->row_cap.resize(B);
     for (int b = 0; b < B; ++b) { h->row_seq[b] = b; h->row_cap[b] = T + h->rows_host[b].limit; }
     if (seat_row_adapters(h, B, "begin", s)) return 1;
@@ -1663,7 +1722,7 @@ extern "C" int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* mask, co
     CTTS_RANGE("ctts_gpt_score");
     hipStream_t s = (hipStream_t)stream;
     h->B = 0; h->admitted = false; h->share_P = 0;      // the KV lanes and the prompt workspaces are overwritten: any generate() state ends here
-    h->text_mode = 0;
+    h->text_mode = 0; h->text_rows_on = 0; h->text_live = 0;
     if (seat_row_adapters(h, B, "score", s)) return 1;
     const int NV = h->NVQ * h->V;
     if (h->score_oidx == nullptr) {
@@ -1724,8 +1783,72 @@ extern "C" int ctts_gpt_set_logprob_out(ctts_gpt* h, float* lp_raw, float* lp_sa
     return 0;
 }
 
+// ---- text rows beside code rows (include/ctts_hip.h; RowState.mode) --------------------------------------------------------------------------------------------
+extern "C" int ctts_gpt_set_row_modes(ctts_gpt* h, const int32_t* modes, int B) {
+    if (!h) { ctts_set_error("set_row_modes: null handle"); return 1; }
+    if (!modes || B <= 0) { h->modes_req.clear(); return 0; }
+    if (B > CTTS_MAX_B) { ctts_set_error("set_row_modes: B=%d > %d", B, CTTS_MAX_B); return 1; }
+    for (int b = 0; b < B; ++b) if (modes[b] != 0 && modes[b] != 1) { ctts_set_error("set_row_modes: sequence %d: mode %d (0 = code, 1 = text)", b, modes[b]); return 1; }
+    h->modes_req.assign(modes, modes + B);
+    return 0;
+}
+extern "C" int ctts_gpt_admit_modes(ctts_gpt* h, int n, const int32_t* rows, const int32_t* modes, void* stream) {
+    (void)stream;        // host-side request: the next ctts_gpt_admit seats the modes
+    if (!h || h->B == 0 || !rows || !modes || n < 0) { ctts_set_error("admit_modes: call begin first / null argument"); return 1; }
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        if (rows[i] < 0 || rows[i] >= h->B) { ctts_set_error("admit_modes: row %d of %d", rows[i], h->B); return 1; }
+        if (modes[i] != 0 && modes[i] != 1) { ctts_set_error("admit_modes: entry %d: mode %d (0 = code, 1 = text)", i, modes[i]); return 1; }
+        any = any || modes[i] == 1;
+    }
+    if (any && h->text_mode) { ctts_set_error("admit_modes: this call's own infer_text is 1: every row of it is a text row already; text rows beside code rows live in a code-mode call"); return 1; }
+    if (any && !h->text_rows_on) { ctts_set_error("admit_modes: a mode-1 row needs ctts_gpt_enable_text_rows first (after ctts_gpt_begin, before the row is seated)"); return 1; }
+    for (int i = 0; i < n; ++i) {
+        bool found = false;
+        for (auto& e : h->modes_admit) if (e.first == rows[i]) { e.second = modes[i]; found = true; }
+        if (!found) h->modes_admit.emplace_back(rows[i], modes[i]);
+    }
+    return 0;
+}
+extern "C" int ctts_gpt_enable_text_rows(ctts_gpt* h, const ctts_sampler_cfg* tsc, int32_t* text_ids_dev, void* stream) {
+    if (!h || h->B == 0) { ctts_set_error("enable_text_rows: no generate state (call ctts_gpt_begin first)"); return 1; }
+    if (!tsc || !text_ids_dev) { ctts_set_error("enable_text_rows: null argument"); return 1; }
+    if (h->text_mode) { ctts_set_error("enable_text_rows: this call's own infer_text is 1: every row of it is a text row already; text rows beside code rows live in a code-mode call"); return 1; }
+    if (!tsc->infer_text) { ctts_set_error("enable_text_rows: text_sc must be the refine-text pass's parameters (infer_text = 1)"); return 1; }
+    if (!h->whead_text || !h->emb_text) { ctts_set_error("enable_text_rows: text rows need head_text.* and emb_text.weight"); return 1; }
+    if (tsc->use_penalty) { ctts_set_error("enable_text_rows: text rows support repetition_penalty == 1 only (use_penalty must be 0, as for infer_text)"); return 1; }
+    if (h->io.noise != nullptr) { ctts_set_error("enable_text_rows: device noise only (caller-supplied noise is laid out for one mode's rows)"); return 1; }
+    if (tsc->eos_token < 0 || tsc->eos_token >= h->vocab_text_head) { ctts_set_error("enable_text_rows: eos out of range"); return 1; }
+    if (!std::isfinite(tsc->temperature[0]) || !(tsc->temperature[0] > 0.f)) { ctts_set_error("enable_text_rows: temperature[0] = %g (must be finite and > 0)", (double)tsc->temperature[0]); return 1; }
+    if (tsc->max_new_token < 1 || tsc->max_new_token > h->sc.max_new) {
+        // the stores keyed by the row's output slot and its own step that are not the samplers' (the heads' hidden rows [slot][step < max_new_token]) stay inside the
+        // utterance's own slot only while a text row's step stays below the code call's max_new_token
+        ctts_set_error("enable_text_rows: the text rows' max_new_token = %d must be 1..%d, the code call's max_new_token (a text row's step indexes the call's per-slot arrays)", tsc->max_new_token, h->sc.max_new);
+        return 1;
+    }
+    if (tsc->min_new_token > tsc->max_new_token) { ctts_set_error("enable_text_rows: min_new_token = %d > max_new_token = %d", tsc->min_new_token, tsc->max_new_token); return 1; }
+    if (h->sampled && h->text_live > 0) { ctts_set_error("enable_text_rows: a text row seated by ctts_gpt_begin needs the call before the first ctts_gpt_sample / ctts_gpt_decode"); return 1; }
+    hipStream_t s = (hipStream_t)stream;
+    if (!h->dyn_text && dev_alloc(h, (void**)&h->dyn_text, sizeof(SamplerDyn))) return 1;
+    if (!h->logits_text && dev_alloc(h, (void**)&h->logits_text, (size_t)CTTS_MAX_B * h->vocab_text_head * 4)) return 1;
+    h->sc_text = cfg_of_abi(*tsc);
+    SamplerDyn d = {};
+    d.cfg = h->sc_text; d.n_draws = 1; d.ids = text_ids_dev; d.finish = h->io.finish; d.end_idx = h->io.end_idx; d.noise = nullptr;
+    d.seed = h->io.seed; d.hidden_out = nullptr; d.hidden_stride = 0; d.rows0 = h->B0;
+    CTTS_HIP_CHECK(hipMemcpyAsync(h->dyn_text, &d, sizeof(d), hipMemcpyHostToDevice, s));       // pageable source: staged before the call returns
+    // text rows that begin seated (ctts_gpt_set_row_modes): their limit is the text rows' own (begin clamped it to the code call's)
+    if (h->text_live > 0) {
+        for (int b = 0; b < h->B; ++b)
+            if (h->rows_host[b].mode == 1 && h->rows_host[b].limit > h->sc_text.max_new) { h->rows_host[b].limit = h->sc_text.max_new; h->row_cap[b] = h->T + h->sc_text.max_new; }
+        CTTS_HIP_CHECK(hipMemcpyAsync(h->finend, h->rows_host.data(), (size_t)h->B * sizeof(RowState), hipMemcpyHostToDevice, s));
+    }
+    h->text_rows_on = 1;
+    return 0;
+}
+
 extern "C" int ctts_gpt_sample(ctts_gpt* h, void* stream) {
     if (!h || h->B == 0) { ctts_set_error("sample: call begin first"); return 1; }
+    if (h->text_live > 0 && !h->text_rows_on) { ctts_set_error("sample: a row of the batch is a text row (ctts_gpt_set_row_modes) but ctts_gpt_enable_text_rows has not been called for this generate state"); return 1; }
     CTTS_RANGE("ctts_gpt_sample");
     h->sampled = true;
     if (h->batch_inv) {          // the last prompt token's layer pass first (see prefill_invariant): a decode step
@@ -1739,6 +1862,7 @@ extern "C" int ctts_gpt_restart(ctts_gpt* h, void* stream) {
     if (!h || h->B == 0) { ctts_set_error("restart: call begin first"); return 1; }
     if (h->B != h->B0) { ctts_set_error("restart: rows were compacted away (a regenerate restarts the whole batch at step 0, gpt.py:496-525)"); return 1; }
     if (h->admitted) { ctts_set_error("restart: rows of this batch were handed to other utterances (ctts_gpt_admit); re-admit the utterance with attempt + 1 instead"); return 1; }
+    if (h->text_rows_on || h->text_live > 0) { ctts_set_error("restart: text rows are enabled (ctts_gpt_enable_text_rows): a regenerate restarts the whole batch in one mode; re-admit the utterance with attempt + 1 instead"); return 1; }
     hipStream_t s = (hipStream_t)stream;
     CTTS_HIP_CHECK(hipMemcpyAsync(h->x_dec, h->x_last, (size_t)h->B * h->H * 4, hipMemcpyDeviceToDevice, s));
     if (h->batch_inv) CTTS_HIP_CHECK(hipMemcpyAsync(h->rope_dec, h->rope_dec0, (size_t)h->B * 64 * 4, hipMemcpyDeviceToDevice, s));      // the first layer pass again
@@ -1845,7 +1969,7 @@ static int graph_span(const ctts_gpt* h, DecodePath path, int left) {
 
 static int ensure_graph(ctts_gpt* h, DecodePath path, int n_steps) {
     char sig[160];
-    snprintf(sig, sizeof(sig), "%d|%d|%p|%d|%d|%d|%d|%d", h->B, h->text_mode, (void*)h->kv, path.splits, h->lora_rows + 2 * h->lora_mlp, h->opt_gen, path.persist, n_steps);      // (diagnostic switches are fixed at create)
+    snprintf(sig, sizeof(sig), "%d|%d|%p|%d|%d|%d|%d|%d", h->B, h->text_mode + 2 * (h->text_live > 0 ? 1 : 0), (void*)h->kv, path.splits, h->lora_rows + 2 * h->lora_mlp, h->opt_gen, path.persist, n_steps);      // (+ 2: a mixed step, two more launches)      // (diagnostic switches are fixed at create)
     std::string key(sig);
     if (h->lora_rows) key.append((const char*)h->lora_row_slots, (size_t)h->B);      // the rows' adapter slots are kernel arguments of the folded launches (LoraFold)
     if (h->graph_gen != h->opt_gen || h->graphs.size() >= 96) {
@@ -1904,6 +2028,7 @@ static int run_segment(ctts_gpt* h, const ctts_gpt::DecodeSeg& sg, bool graphs, 
 
 extern "C" int ctts_gpt_decode(ctts_gpt* h, int n_steps, int use_graph, void* stream) {
     if (!h || h->B == 0) { ctts_set_error("decode: call begin first"); return 1; }
+    if (h->text_live > 0 && !h->text_rows_on) { ctts_set_error("decode: a row of the batch is a text row (ctts_gpt_set_row_modes) but ctts_gpt_enable_text_rows has not been called for this generate state"); return 1; }
     CTTS_RANGE("ctts_gpt_decode");              // reference: nvtx "forward" per decode step + "execute" (trt_models/predictor.py:164)
     hipStream_t s = (hipStream_t)stream;
     h->sampled = true;
@@ -1981,6 +2106,11 @@ extern "C" int ctts_gpt_compact(ctts_gpt* h, const int32_t* keep_rows, int n_kee
     if (launch_compact_rows(h->keep_dev, n_keep, h->H, h->x_dec, h->rope_dec, h->meta_dec, h->hist_ring, h->finend, h->knobs, h->cx, h->crope, h->cmeta, h->cring, h->cfin,
                             h->cknobs, h->st, s)) return 1;
     for (int i = 0; i < n_keep; ++i) { h->row_seq[i] = h->row_seq[keep_rows[i]]; h->row_ctx[i] = h->row_ctx[keep_rows[i]]; h->row_cap[i] = h->row_cap[keep_rows[i]]; }
+    if (!h->row_mode.empty()) {      // the rows' modes move with them; a batch that dropped its last text row is an ordinary code batch again
+        h->text_live = 0;
+        for (int i = 0; i < n_keep; ++i) { h->row_mode[i] = h->row_mode[keep_rows[i]]; h->text_live += h->row_mode[i]; }
+        h->row_mode.resize(n_keep);
+    }
     if (!h->lora_slot_host.empty()) for (int i = 0; i < n_keep; ++i) h->lora_row_slots[i] = (signed char)h->lora_slot_host[h->row_seq[i]];
     h->B = n_keep;
     if (h->lora_rows) lora_refresh(h);
@@ -2026,6 +2156,8 @@ extern "C" int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, co
     // what ctts_gpt_admit_sampling named is for THIS admission only, whether it goes through or fails below: a later admit never picks up a stale entry
     std::vector<std::pair<int, RowSampling>> named;
     named.swap(h->knobs_admit);
+    std::vector<std::pair<int, int>> modes;      // ... and what ctts_gpt_admit_modes named
+    modes.swap(h->modes_admit);
     std::vector<int> share;                      // ... and so is what ctts_gpt_share_prompts named
     share.swap(h->share_req);
     const int share_P = h->share_req_P;
@@ -2057,6 +2189,16 @@ extern "C" int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, co
         r.attempt = attempts ? attempts[i] : 0;
         r.out = out_index[i];
         if (r.out < 0) { ctts_set_error("admit: negative output index"); return 1; }
+        for (const auto& e : modes) if (e.first == rows[i]) r.mode = e.second;
+        if (r.mode == 1) {
+            if (!h->text_rows_on) { ctts_set_error("admit: row %d is to hold a text utterance (ctts_gpt_admit_modes) but ctts_gpt_enable_text_rows has not been called for this generate state", rows[i]); return 1; }
+            if (!share.empty()) { ctts_set_error("admit: shared prompt passes (ctts_gpt_share_prompts) are for code rows; row %d is to hold a text utterance (ctts_gpt_admit_modes)", rows[i]); return 1; }
+            for (const auto& e : named) if (e.first == rows[i]) {
+                ctts_set_error("admit: row %d is to hold a text utterance (ctts_gpt_admit_modes) and carries per-row sampling knobs (ctts_gpt_admit_sampling); text rows keep the values of ctts_gpt_enable_text_rows", rows[i]);
+                return 1;
+            }
+            if (r.limit > h->sc_text.max_new) r.limit = h->sc_text.max_new;      // the text ids array is [n_out][max_new_text][4]
+        }
     }
     // the new rows' sampling knobs: what ctts_gpt_admit_sampling named for the row, else the call's values (never the finished utterance's)
     h->knobs_host.assign(n, knobs_of_cfg(h->sc));
@@ -2088,6 +2230,10 @@ extern "C" int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, co
         if (!share.empty() && share_kv(h, T - 1, s)) return 1;      // the followers' lanes <- the leaders' span [0, T - 1)
     }
     for (int i = 0; i < n; ++i) { h->row_ctx[rows[i]] = T; h->row_cap[rows[i]] = T + h->fresh_host[i].limit; }
+    h->row_mode.resize(h->B, 0);
+    for (int i = 0; i < n; ++i) h->row_mode[rows[i]] = h->fresh_host[i].mode;      // (a row handed to a code utterance stops counting as a text row here)
+    h->text_live = 0;
+    for (int r = 0; r < h->B; ++r) h->text_live += h->row_mode[r];
     h->admitted = true;
     return 0;
 }
@@ -2106,6 +2252,7 @@ extern "C" int ctts_gpt_grow(ctts_gpt* h, int n, void* stream) {
     bool used[CTTS_MAX_B] = {};
     for (int r = 0; r < B; ++r) used[h->row_seq[r]] = true;
     h->row_seq.resize(B + n); h->row_ctx.resize(B + n); h->row_cap.resize(B + n);
+    h->row_mode.resize(B); h->row_mode.resize(B + n, 0);      // dead rows are code rows
     h->seq_host.assign(n, 0);
     for (int i = 0, lane = 0; i < n; ++i, ++lane) {
         while (used[lane]) ++lane;               // (B + n <= max_batch and the rows' lanes are distinct: n free lanes exist below max_batch)

@@ -158,6 +158,8 @@ struct SamplerArgs {
     DevState* st;           // null in stand-alone mode
     // generate mode
     int text_mode;          // refine-text pass: one V_text-wide row per sequence, emb_code points at emb_text [V_text][H]
+    int mixed;              // the batch holds text rows beside code rows (RowState.mode): each of the two generate-mode kernels serves the rows of its mode, the others' blocks
+                            //   return after their first loads; 0 = every row is this launch's (the kernels as they were)
     const float* emb_code;  // [4][V][H] fp32
     int H;
     float* x_next;          // [B][H]

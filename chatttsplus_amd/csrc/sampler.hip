@@ -285,6 +285,10 @@ __device__ int sample_row(const SampleKnobs& c, const float* tab, const RowIn& i
 // generate mode: grid = B blocks, block = 4 waves (one per codebook)
 // The leading scalars are preloaded into SGPRs (see skinny_gemm.hip): state header, logits and bookkeeping rows are all
 // requested before the first wait of the kernel.
+// MIXED (SamplerArgs.mixed): the batch also holds text rows (RowState.mode 1), which sampler_text_kernel serves in a launch of its own: a block whose row is one
+// returns once its first batch of loads is back -- it stores nothing and takes no ticket (the row arrives through the text kernel).  The mode is the last word of
+// the record's second int4, which the kernel loads anyway.  MIXED = false is the kernel as it was: the test is compiled out.
+template <bool MIXED>
 __global__ __launch_bounds__(256) void sampler_generate_kernel(const int* st_words, const float* logits_p, const SamplerDyn* dyn_p, const RowMeta* meta_p,
                                                                const int V_p, const int* ring_p, const RowState* finend_p, const SamplerArgs a) {
     __shared__ float tab[17];
@@ -309,7 +313,7 @@ __global__ __launch_bounds__(256) void sampler_generate_kernel(const int* st_wor
     // the finish / end_idx bookkeeping is mirrored in engine memory (the caller's arrays are write-only here).
     const int ring_v = ring_p[(size_t)(b * CTTS_NUM_VQ + vq) * 16 + (lane & 15)];
     const int4 fe = ((const int4*)(finend_p + b))[0];              // {fin, end, attempt, limit}
-    const int4 uid = ((const int4*)(finend_p + b))[1];             // {uid_lo, uid_hi, out, -}
+    const int4 uid = ((const int4*)(finend_p + b))[1];             // {uid_lo, uid_hi, out, mode}
     // the row's sampling knobs (common.h RowSampling): indexed by the ROW b, in the table behind the RowState table -- an address known at launch as
     // well (indexing by the utterance, uid.z, would put a dependent round trip in front of them).  Read through the constant address space, as d->cfg
     // was: scalar loads off a preloaded argument.  eos / max_input_ids / max_new stay per call (d->cfg)
@@ -317,6 +321,7 @@ __global__ __launch_bounds__(256) void sampler_generate_kernel(const int* st_wor
     if (tid < 17) tab[tid] = knob->penalty_table[tid];
     const RowMeta meta_in = meta_p[b];
     if (__builtin_amdgcn_readfirstlane(hdr.z)) return;            // every sequence finished (gpt.py:545)
+    if (MIXED && __builtin_amdgcn_readfirstlane(uid.w) != 0) return;      // a text row: sampler_text_kernel's
     const int gstep = __builtin_amdgcn_readfirstlane(hdr.x), draw = __builtin_amdgcn_readfirstlane(hdr.y);
     const int fin_in = fe.x, end_in = fe.y;
     // the row's OWN step (i of gpt.py:389 for this utterance) = tokens it has sampled so far: equal to the batch's step counter while the
@@ -476,6 +481,7 @@ __global__ __launch_bounds__(1024) void sampler_text_kernel(const SamplerArgs a)
     const int b = blockIdx.x, V = a.V;
     const int gstep = st->step, draw = st->draw;
     const RowState rs_in = a.finend[b];
+    if (a.mixed && rs_in.mode == 0) return;                          // text rows beside code rows: a code row is sampler_generate_kernel's (no store, no ticket here)
     // per-row bookkeeping like the code sampler's (RowState, common.h): the row's OWN step, its utterance's place in the output arrays, its own limit --
     // so text rows can be compacted away and re-used by queued utterances (ctts_gpt_admit) exactly like code rows
     const int step = rs_in.end, seq = rs_in.out;
@@ -727,7 +733,8 @@ int launch_sampler(const SamplerArgs& a, int blocks, hipStream_t s) {
     if (a.st != nullptr && a.text_mode) {
         if (a.V > 1024 * TVPT) { ctts_set_error("text sampler: vocab %d > %d", a.V, 1024 * TVPT); return 1; }
         hipLaunchKernelGGL(sampler_text_kernel, dim3(a.B), dim3(1024), 0, s, a);
-    } else if (a.st != nullptr) hipLaunchKernelGGL(sampler_generate_kernel, dim3(a.B), dim3(256), 0, s, (const int*)a.st, a.logits, a.dyn, (const RowMeta*)a.meta, a.V, (const int*)a.hist_ring, (const RowState*)a.finend, a);
+    } else if (a.st != nullptr && a.mixed) hipLaunchKernelGGL(sampler_generate_kernel<true>, dim3(a.B), dim3(256), 0, s, (const int*)a.st, a.logits, a.dyn, (const RowMeta*)a.meta, a.V, (const int*)a.hist_ring, (const RowState*)a.finend, a);
+    else if (a.st != nullptr) hipLaunchKernelGGL(sampler_generate_kernel<false>, dim3(a.B), dim3(256), 0, s, (const int*)a.st, a.logits, a.dyn, (const RowMeta*)a.meta, a.V, (const int*)a.hist_ring, (const RowState*)a.finend, a);
     else hipLaunchKernelGGL(sampler_rows_kernel, dim3(blocks), dim3(256), 0, s, a);
     CTTS_HIP_CHECK(hipGetLastError());
     return 0;

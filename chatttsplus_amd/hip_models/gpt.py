@@ -420,32 +420,43 @@ class SessionBook:
     "utterance" is the session ticket."""
 
     def __init__(self, rows: int, out_slots: int, max_batch: int, max_seq: int, max_new_token: int, ensure_non_empty: bool = True, max_restarts: int = 64,
-                 compact: bool = True):
+                 compact: bool = True, max_new_text: Optional[int] = None):
         if not (1 <= int(rows) <= int(max_batch)):
             raise ValueError(f"session: rows={rows} outside 1..max_batch={max_batch}")
         if int(out_slots) < 1:
             raise ValueError(f"session: out_slots={out_slots} (at least one)")
         self.rows, self.max_batch, self.max_seq, self.max_new = int(rows), int(max_batch), int(max_seq), int(max_new_token)
         self.ensure_non_empty, self.max_restarts, self.compact = bool(ensure_non_empty), int(max_restarts), bool(compact)
+        # text utterances (mode "text": refine-text rows beside the code rows) have a token limit of their own, at most the code rows'; None = the session serves none
+        if max_new_text is not None and not (1 <= int(max_new_text) <= self.max_new):
+            raise ValueError(f"session: the text rows' max_new_token={max_new_text} must be 1..max_new_token={self.max_new} of the code rows")
+        self.max_new_text = None if max_new_text is None else int(max_new_text)
         self.book = RowBook()
         self.lanes: List[int] = []                 # KV lane of every current decode row (the engine's row_seq)
         self.free_slots = list(range(int(out_slots)))
         self.queue: List[int] = []                 # tickets waiting for a row (and an output slot), in order of service
-        self.utts = {}                             # ticket -> dict(utt_id, T, limit, attempt, slot, row_tk, cancelled)
+        self.utts = {}                             # ticket -> dict(utt_id, T, limit, attempt, slot, row_tk, cancelled, mode)
         self.begun = False
         self._next = 0
         self._to_cancel: List[int] = []            # seated tickets whose cancel the device has not seen yet
         self._dropped: List[int] = []              # tickets cancelled while queued: delivered by the next step
 
     # -- requests ---------------------------------------------------------------------------------
-    def submit(self, T: int, utt_id: int, limit: Optional[int] = None) -> int:
+    def submit(self, T: int, utt_id: int, limit: Optional[int] = None, mode: str = "code") -> int:
+        """`mode` "code" or "text": a text utterance takes a row, a KV lane and an output slot like a code utterance (one index space: a slot is held by one
+        utterance of either kind); only its token limit is the text rows' own"""
         T = int(T)
+        if mode not in ("code", "text"):
+            raise ValueError(f"submit: mode={mode!r} (\"code\" or \"text\")")
+        if mode == "text" and self.max_new_text is None:
+            raise ValueError("submit: mode=\"text\" needs a session opened with text_rows=...")
         if T < 1 or T + self.max_new > self.max_seq:
             raise ValueError(f"submit: prompt of {T} tokens + max_new_token={self.max_new} exceed max_seq_len={self.max_seq}")
-        lim = self.max_new if limit is None else min(max(int(limit), 1), self.max_new)
+        cap = self.max_new_text if mode == "text" else self.max_new
+        lim = cap if limit is None else min(max(int(limit), 1), cap)
         tk = self._next
         self._next += 1
-        self.utts[tk] = dict(utt_id=int(utt_id), T=T, limit=lim, attempt=0, slot=None, row_tk=None, cancelled=False)
+        self.utts[tk] = dict(utt_id=int(utt_id), T=T, limit=lim, attempt=0, slot=None, row_tk=None, cancelled=False, mode=mode)
         self.queue.append(tk)
         return tk
 
@@ -579,6 +590,27 @@ def refuse_out_of_scope(kw: dict, instead: str) -> None:
             raise _lib.HipBackendError(f"open_session: {SESSION_OUT_OF_SCOPE[name]} ({name}=) is not offered inside a session; {instead}")
 
 
+TEXT_ROWS_KEYS = ("temperature", "top_P", "top_K", "eos_token", "max_new_token", "min_new_token")
+
+
+def text_rows_cfg(text_rows, num_vq: int = 4) -> _lib.SamplerCfg:
+    """open_session(text_rows=...): the refine pass's sampler configuration (infer_text = 1) from a dict or an object carrying TEXT_ROWS_KEYS -- built the way
+    generate(infer_text=True) builds its own: gen_logits for top_P / top_K (no repetition penalty in this mode), sampler_cfg_from_objects for the rest"""
+    if isinstance(text_rows, dict):
+        bad = sorted(set(text_rows) - set(TEXT_ROWS_KEYS))
+        if bad:
+            raise _lib.HipBackendError(f"open_session: text_rows: unknown key(s) {bad}; the keys are {list(TEXT_ROWS_KEYS)}")
+        get = text_rows.get
+    else:
+        def get(k, d=None):
+            return getattr(text_rows, k, d)
+    if get("eos_token") is None or get("max_new_token") is None:
+        raise _lib.HipBackendError("open_session: text_rows needs eos_token ([Ebreak]) and max_new_token")
+    w, p = gen_logits(0, top_P=get("top_P", 0.7), top_K=get("top_K", 20), repetition_penalty=None)
+    t = get("temperature", 0.7)
+    return sampler_cfg_from_objects(0.7 if t is None else t, int(get("eos_token")), int(get("max_new_token")), int(get("min_new_token", 0) or 0), w, p, num_vq, infer_text=True)
+
+
 @dataclass(repr=False, eq=False)
 class SessionResult:
     """One utterance a DecodeSession delivered: clones, independent of the session's output buffers."""
@@ -592,18 +624,28 @@ class SessionResult:
     finished_by_eos: bool = False
     cancelled: bool = False
     attempt: int = 0              # first-token-EOS regenerations before this result (ensure_non_empty)
+    mode: str = "code"            # "text": a refine-text utterance -- ids is [n] (as generate(infer_text=True) returns them), no hiddens, no log-probs
 
 
 class DecodeSession:
     """A generate state kept open (GPT.open_session): utterances are submitted and cancelled while others decode.  The decode batch is as wide as the utterances
     in flight need -- it grows (ctts_gpt_grow + ctts_gpt_admit) when texts arrive and shrinks (ctts_gpt_compact) when they end -- instead of being opened at its
-    peak width.  Holds the engine's busy token until close(); a context manager.  Code mode, device noise."""
+    peak width.  Holds the engine's busy token until close(); a context manager.  A code-mode generate state, device noise; opened with `text_sc` (the refine
+    pass's sampler configuration) it also serves refine-text utterances as text rows beside the code rows (submit(mode="text"); ctts_gpt_enable_text_rows)."""
 
-    def __init__(self, gpt: "GPT", sc, seed: int, rows: int, out_slots: int, return_hidden: bool, return_logprobs: bool, ensure_non_empty: bool, max_restarts: int = 64):
+    def __init__(self, gpt: "GPT", sc, seed: int, rows: int, out_slots: int, return_hidden: bool, return_logprobs: bool, ensure_non_empty: bool, max_restarts: int = 64,
+                 text_sc=None):
         self.gpt, self.sc, self.seed = gpt, sc, int(seed)
         self.max_new = int(sc.max_new_token)
-        self.book = SessionBook(rows, out_slots, gpt.max_batch, gpt.max_seq, self.max_new, ensure_non_empty, max_restarts, gpt.compact)
+        self.text_sc = text_sc
+        try:
+            self.book = SessionBook(rows, out_slots, gpt.max_batch, gpt.max_seq, self.max_new, ensure_non_empty, max_restarts, gpt.compact,
+                                    max_new_text=None if text_sc is None else int(text_sc.max_new_token))
+        except ValueError as e:
+            raise _lib.HipBackendError(f"open_session: {e}") from None
         dev, H, NVQ = gpt.device, gpt.model_dim, gpt.num_vq
+        # the text rows' ids [slot][text max_new_token][4]: the same slots as `ids` (a slot is held by one utterance of either kind)
+        self.tids = torch.empty(out_slots, int(text_sc.max_new_token), NVQ, dtype=torch.int32, device=dev) if text_sc is not None else None
         self.ids = torch.empty(out_slots, self.max_new, NVQ, dtype=torch.int32, device=dev)
         self.hid = torch.empty(out_slots, self.max_new, H, dtype=torch.float32, device=dev) if return_hidden else None
         self.lps = torch.empty(2, out_slots, self.max_new, NVQ, dtype=torch.float32, device=dev) if return_logprobs else None
@@ -612,7 +654,7 @@ class DecodeSession:
         self.chunk = max(4, min(gpt.chunk_steps, gpt.compact_chunk))
         self.batch_trace: List[tuple] = []         # (steps launched, rows) at every change of the row count
         self.launched = 0
-        self._req = {}                             # ticket -> (emb [T,H] device, knobs or None, adapter slot)
+        self._req = {}                             # ticket -> (emb [T,H] device, knobs or None, adapter slot, mode 0 / 1)
         self._pins = [torch.zeros(2 * int(rows), dtype=torch.int32).pin_memory() for _ in range(2)]
         self._evs = [torch.cuda.Event() for _ in range(2)]
         self._layouts = [None, None]
@@ -632,11 +674,19 @@ class DecodeSession:
             raise _lib.HipBackendError("DecodeSession: the session is closed")
 
     # -- requests ---------------------------------------------------------------------------------
-    def submit(self, emb: torch.Tensor, mask: torch.Tensor, utt_id: int, limit: Optional[int] = None, sampling=None, adapter_slot: Optional[int] = None) -> int:
+    def submit(self, emb: torch.Tensor, mask: torch.Tensor, utt_id: int, limit: Optional[int] = None, sampling=None, adapter_slot: Optional[int] = None,
+               mode: str = "code") -> int:
         """Queues one utterance: emb [T, H] (GPT.__call__), mask [T] left padded.  `limit` <= max_new_token, `sampling` a dict as in sampling_per_row,
-        `adapter_slot` a resident adapter (load_adapter).  Returns its ticket."""
+        `adapter_slot` a resident adapter (load_adapter).  `mode` "text" (sessions opened with text_rows=): a refine-text utterance -- its prompt is the refine
+        prompt, it samples under the text head with the session's text parameters (no per-utterance `sampling`), and its result's ids are [n].  Returns its ticket."""
         self._check_open()
         g = self.gpt
+        if mode not in ("code", "text"):
+            raise _lib.HipBackendError(f"submit: mode={mode!r} (\"code\" or \"text\")")
+        if mode == "text" and self.text_sc is None:
+            raise _lib.HipBackendError("submit: mode=\"text\" needs a session opened with text_rows=... (GPT.open_session)")
+        if mode == "text" and sampling is not None:
+            raise _lib.HipBackendError("submit: per-utterance sampling parameters are for code utterances; a text utterance keeps the session's text_rows values")
         emb = torch.as_tensor(emb)
         mask = torch.as_tensor(mask).flatten()
         if emb.dim() != 2 or emb.shape[1] != g.model_dim or mask.numel() != emb.shape[0]:
@@ -650,10 +700,10 @@ class DecodeSession:
         if slot >= 0 and g.options.get("batch_invariant", 0):
             raise _lib.HipBackendError("submit: per-utterance adapters are outside the batch_invariant contract; merge the adapter (with_lora) or set the option to 0")
         try:
-            tk = self.book.submit(n, utt_id, limit)
+            tk = self.book.submit(n, utt_id, limit, mode)
         except ValueError as e:
             raise _lib.HipBackendError(str(e)) from None
-        self._req[tk] = (emb[emb.shape[0] - n:].to(g.device, dtype=torch.float32).contiguous(), knobs, slot)
+        self._req[tk] = (emb[emb.shape[0] - n:].to(g.device, dtype=torch.float32).contiguous(), knobs, slot, 1 if mode == "text" else 0)
         self._adapters = self._adapters or slot >= 0
         return tk
 
@@ -695,11 +745,18 @@ class DecodeSession:
         if knobs:
             base = row_sampling_from_values(self.sc, None, g.num_vq)
             _lib.check(lib.ctts_gpt_set_row_sampling(h, (_lib.RowSampling * R)(*[self._req[tk][1] or base for tk in tks]), R), "set_row_sampling")
+        modes = np.ascontiguousarray([self._req[tk][3] for tk in tks], dtype=np.int32)
+        if modes.any():
+            _lib.check(lib.ctts_gpt_set_row_modes(h, modes.ctypes.data_as(C.c_void_p), R), "set_row_modes")
         try:
             _lib.check(lib.ctts_gpt_begin(h, R, Ta, mask.data_ptr(), C.byref(self.sc), C.byref(io), st), "begin")
         finally:
             if knobs:
                 lib.ctts_gpt_set_row_sampling(h, None, 0)
+            if modes.any():
+                lib.ctts_gpt_set_row_modes(h, None, 0)
+        if self.text_sc is not None:               # (after begin, which creates the state; before the first sample, which a begun text row needs it for)
+            _lib.check(lib.ctts_gpt_enable_text_rows(h, C.byref(self.text_sc), self.tids.data_ptr(), st), "enable_text_rows")
         if self.lps is not None:
             _lib.check(lib.ctts_gpt_set_logprob_out(h, self.lps[0].data_ptr(), self.lps[1].data_ptr(), st), "set_logprob_out")
         _lib.check(lib.ctts_gpt_prefill(h, emb.data_ptr(), st), "prefill")
@@ -721,6 +778,9 @@ class DecodeSession:
             base = row_sampling_from_values(self.sc, None, g.num_vq)
             _lib.check(lib.ctts_gpt_admit_sampling(h, k, rows_arr.ctypes.data_as(C.c_void_p), (_lib.RowSampling * k)(*[self._req[tk][1] or base for tk in tks]), st),
                        "admit_sampling")
+        if self.text_sc is not None:
+            md_arr = np.ascontiguousarray([self._req[tk][3] for tk in tks], dtype=np.int32)
+            _lib.check(lib.ctts_gpt_admit_modes(h, k, rows_arr.ctypes.data_as(C.c_void_p), md_arr.ctypes.data_as(C.c_void_p), st), "admit_modes")
         _lib.check(lib.ctts_gpt_admit(h, k, rows_arr.ctypes.data_as(C.c_void_p), Ta, mask.data_ptr(), emb.data_ptr(), uid_arr.ctypes.data_as(C.c_void_p),
                                       lim_arr.ctypes.data_as(C.c_void_p), out_arr.ctypes.data_as(C.c_void_p), att_arr.ctypes.data_as(C.c_void_p), st), "admit")
 
@@ -728,6 +788,12 @@ class DecodeSession:
         u = self.book.utts[tk]
         s = u["slot"]
         eos = bool(fin & 2)
+        if u.get("mode", "code") == "text":      # ids [n] as generate(infer_text=True) returns them (gpt.py:298-299); no hiddens, no log-probs
+            ids = self.tids[s, :n, 0].to(torch.long) if (s is not None and n > 0) else torch.empty(0, dtype=torch.long, device=self.gpt.device)
+            res = SessionResult(ticket=tk, utt_id=u["utt_id"], ids=ids, finished_by_eos=eos, cancelled=cancelled, attempt=u["attempt"], mode="text")
+            self.book.release(tk)
+            self._req.pop(tk, None)
+            return res
         if s is None or n == 0:
             e = torch.empty(0, self.gpt.num_vq, dtype=torch.long, device=self.gpt.device)
             res = SessionResult(ticket=tk, utt_id=u["utt_id"], ids=e, hiddens=self.hid[0, :0].clone() if self.hid is not None else None,
@@ -1614,13 +1680,15 @@ class GPT:
     # -- serving session (ctts_gpt_grow / ctts_gpt_cancel) ------------------------------------------------------------------------
     def open_session(self, temperature, eos_token, max_new_token, min_new_token=0, logits_warpers=[], logits_processors=[], return_hidden=False,
                      return_logprobs=False, seed: Optional[int] = None, rows: Optional[int] = None, out_slots: Optional[int] = None, ensure_non_empty=True,
-                     **out_of_scope) -> DecodeSession:
+                     text_rows=None, **out_of_scope) -> DecodeSession:
         """Opens a DecodeSession: a generate state that stays open while utterances are submitted (submit), cancelled (cancel) and delivered (step / drain).  The
         sampling arguments are the call's values, as in generate_many; an utterance may bring its own (submit(sampling=...)).  `rows` <= max_batch bounds the
         decode batch (default max_batch), `out_slots` the utterances whose results are held at once (default 2 * rows; slots are recycled once a result has been
         cloned out).  Holds the engine until close(): generate* and score raise meanwhile.  Not offered inside a session, each refused with a message:
-        shared prompt passes / num_candidates, caller-supplied noise, per-utterance streaming windows, infer_sharded, the refine-text pass (the engine runs
-        one mode at a time: refine first, submit the refined text)."""
+        shared prompt passes / num_candidates, caller-supplied noise, per-utterance streaming windows, infer_sharded, and the call-level names of the refine-text
+        pass (infer_text, refine_text_only, params_refine_text).  The refine-text pass itself is served INSIDE the session: `text_rows` = a dict (or an object with
+        these attributes) of temperature, top_P, top_K, eos_token ([Ebreak]), max_new_token (<= the code rows'), min_new_token makes submit(mode="text") seat
+        refine-text utterances as text rows beside the code rows of the one decode batch (ctts_gpt_enable_text_rows); their results carry ids [n]."""
         if not self._finalized:
             raise _lib.HipBackendError("weights not loaded")
         refuse_out_of_scope(out_of_scope, "use generate() / generate_many() / infer() for it")
@@ -1634,10 +1702,11 @@ class GPT:
             raise _lib.HipBackendError("GPT.open_session: GPT.generate is already running on this engine (or on an engine sharing its KV cache): exhaust or close "
                                        "the previous generator / session first")
         sc = sampler_cfg_from_objects(temperature, int(eos_token), int(max_new_token), min_new_token, logits_warpers, logits_processors, self.num_vq)
+        text_sc = text_rows_cfg(text_rows, self.num_vq) if text_rows is not None else None
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         with torch.cuda.device(self.device):
-            ses = DecodeSession(self, sc, seed, rows, out_slots, bool(return_hidden), bool(return_logprobs), bool(ensure_non_empty))
+            ses = DecodeSession(self, sc, seed, rows, out_slots, bool(return_hidden), bool(return_logprobs), bool(ensure_non_empty), text_sc=text_sc)
         self._busy_token.owner = ses
         return ses
 

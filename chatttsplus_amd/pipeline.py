@@ -211,23 +211,38 @@ class SessionDetails:
     sampled_logprobs: torch.Tensor
     mean_logprob: float
     finished_by_eos: bool = False
+    refined_text: Optional[str] = None         # sessions opened with refine=: the text the refine stage produced (what the code stage spoke); None otherwise
 
 
 class SynthSession:
     """A serving session of the pipeline (ChatTTSPlusPipeline.open_session): texts are submitted and cancelled while others are being spoken.  A
-    GPT.DecodeSession (elastic decode batch, ctts_gpt_grow / ctts_gpt_cancel) under the prompt building of infer() and the batched vocoder.  Texts are
-    already refined (the engine runs one mode at a time: refine first with infer(refine_text_only=True), submit the refined text)."""
+    GPT.DecodeSession (elastic decode batch, ctts_gpt_grow / ctts_gpt_cancel) under the prompt building of infer() and the batched vocoder.  Opened with
+    `refine` (a RefineTextParams) a text is refined first, INSIDE the session: its refine prompt is seated as a text row beside the code rows of the one decode
+    batch (DecodeSession.submit(mode="text")); when the row delivers, its ids are filtered and decoded as infer() does and the code utterance is submitted --
+    both stages under the ticket submit() returned and under one utterance id (noise stream 4 for the text row, 0-3 for the code row)."""
 
-    def __init__(self, pipe, gpt, params: InferCodeParams, use_decoder: bool, rows, seed, return_details: bool):
+    def __init__(self, pipe, gpt, params: InferCodeParams, use_decoder: bool, rows, seed, return_details: bool, refine: Optional[RefineTextParams] = None):
         self.pipe, self.gpt, self.params, self.use_decoder, self.return_details = pipe, gpt, params, bool(use_decoder), bool(return_details)
+        self.refine = refine
         num_code = int(gpt.emb_code[0].num_embeddings - 1)
         warpers, processors = gen_logits(num_code=num_code, top_P=params.top_P, top_K=params.top_K, repetition_penalty=params.repetition_penalty)
         temperature = params.temperature if isinstance(params.temperature, list) else [params.temperature] * gpt.num_vq
+        text_rows = None
+        if refine is not None:
+            if refine.repetition_penalty is not None and float(refine.repetition_penalty) != 1.0:
+                raise _lib.HipBackendError("open_session: refine.repetition_penalty must be 1 (the refine-text pass supports no repetition penalty)")
+            text_rows = dict(temperature=refine.temperature, top_P=refine.top_P, top_K=refine.top_K, eos_token=pipe.models_dict["tokenizer"].eos_token,
+                             max_new_token=refine.max_new_token, min_new_token=refine.min_new_token)
         self.session = gpt.open_session(torch.tensor(temperature), num_code, params.max_new_token, min_new_token=params.min_new_token, logits_warpers=warpers,
                                         logits_processors=processors, return_hidden=self.use_decoder, return_logprobs=self.return_details, seed=seed, rows=rows,
-                                        ensure_non_empty=params.ensure_non_empty)
+                                        ensure_non_empty=params.ensure_non_empty, text_rows=text_rows)
         self._paths = []                           # adapters utterances of this session named: all stay resident (at most _lib.MAX_ADAPTERS)
         self._auto_id = 0
+        self._refining = {}                        # public ticket (= the refine stage's) -> what the code stage needs: dict(diff, slot, utt_id)
+        self._public = {}                          # code-stage ticket of a refined utterance -> its public ticket
+        self._code_tk = {}                         # ... and back
+        self._refined = {}                         # public ticket -> refined text
+        self.failed = {}                           # public ticket -> why its code stage could not be submitted (delivered empty, cancelled=True)
 
     def __enter__(self):
         return self
@@ -240,11 +255,16 @@ class SynthSession:
     def batch_trace(self):
         return self.session.batch_trace
 
-    def submit(self, text: str, params=None, lora_path: Optional[str] = None, utt_id: Optional[int] = None, max_new_token: Optional[int] = None) -> int:
-        """Queues one already-refined text.  `params`: this utterance's overrides (an InferCodeParams or a dict, checked by per_utterance_overrides:
-        sampling knobs, max_new_token, prompt, spk_emb); `lora_path`: its own adapter; `utt_id`: its noise key (default: a counter).  Returns its ticket."""
+    def submit(self, text: str, params=None, lora_path: Optional[str] = None, utt_id: Optional[int] = None, max_new_token: Optional[int] = None,
+               refine: Optional[bool] = None) -> int:
+        """Queues one text.  `params`: this utterance's overrides (an InferCodeParams or a dict, checked by per_utterance_overrides: sampling knobs,
+        max_new_token, prompt, spk_emb); `lora_path`: its own adapter; `utt_id`: its noise key (default: a counter).  `refine`: refine the text first (default:
+        iff the session was opened with refine=); False = the text is already refined.  Returns its ticket."""
         if not isinstance(text, str):
             raise _lib.HipBackendError("SynthSession.submit takes one text (a str) per call")
+        refine = (self.refine is not None) if refine is None else bool(refine)
+        if refine and self.refine is None:
+            raise _lib.HipBackendError("submit: refine=True needs a session opened with refine=RefineTextParams(...)")
         pipe, gpt, base = self.pipe, self.gpt, self.params
         diff = per_utterance_overrides(base, [params])[0] if params is not None else {}
         if max_new_token is not None:
@@ -261,37 +281,91 @@ class SynthSession:
             slot = pipe._adapter_slots(gpt, paths)[paths.index(lora_path)]
             self._paths = paths
         t = pipe.normalizer(text, True, True, None)                      # infer()'s defaults
+        if utt_id is None:
+            utt_id, self._auto_id = self._auto_id, self._auto_id + 1
+        if refine:
+            # stage 1: the refine prompt as a text row (pipeline:237-277).  No per-utterance adapter: infer() refines on the base weights (_refine_text); a session
+            # opened with lora_path runs on the merged engine in both stages
+            input_ids, attention_mask, text_mask = pipe._refine_prompt([t], self.refine)
+            emb = gpt(input_ids, text_mask)
+            tk = self.session.submit(emb[0], attention_mask[0], int(utt_id), mode="text")
+            self._refining[tk] = dict(diff=diff, slot=slot, utt_id=int(utt_id))
+            return tk
+        return self._submit_code(t, diff, slot, int(utt_id))
+
+    def _submit_code(self, t: str, diff: dict, slot, utt_id: int) -> int:
+        """the code utterance of one (refined) text: infer()'s prompt building, then DecodeSession.submit"""
+        pipe, gpt, base = self.pipe, self.gpt, self.params
         t = t if t.strip().endswith("[uv_break]") else t + " [uv_break]"      # pipeline:414-416
         pic = dataclasses.replace(base, spk_emb=diff["spk_emb"]) if "spk_emb" in diff else base
         input_ids, attention_mask, text_mask = pipe._code_prompt([t], pic, gpt, [diff["prompt"] or ""] if "prompt" in diff else None)
         emb = gpt(input_ids, text_mask, spk_emb=pic.spk_emb, spk_emb_ids=pipe.models_dict["tokenizer"].spk_emb_ids)
-        if utt_id is None:
-            utt_id, self._auto_id = self._auto_id, self._auto_id + 1
         sampling = {k: diff[k] for k in PER_UTTERANCE_SAMPLING if k in diff} or None
-        return self.session.submit(emb[0], attention_mask[0], int(utt_id), limit=diff.get("max_new_token"), sampling=sampling, adapter_slot=slot)
+        return self.session.submit(emb[0], attention_mask[0], utt_id, limit=diff.get("max_new_token"), sampling=sampling, adapter_slot=slot)
 
     def cancel(self, ticket: int) -> bool:
-        return self.session.cancel(ticket)
+        """Works in either stage of a refined utterance: during the refine stage the text row is cancelled and the utterance is delivered with an empty waveform
+        and cancelled=True (no code stage follows); during the code stage as for any utterance.  A refine-stage cancel answers True for every first call, also
+        when the text row had already finished on the device and only its report was still on the way: the utterance is delivered empty with cancelled=True then
+        too (the host decides it; no code stage is started)."""
+        if ticket in self._refining:
+            if self._refining[ticket].get("cancelled"):
+                return False
+            self._refining[ticket]["cancelled"] = True
+            self.session.cancel(ticket)
+            return True
+        return self.session.cancel(self._code_tk.get(ticket, ticket))
+
+    def _empty(self, cancelled: bool, refined_text=None):
+        w = torch.zeros(0, device=self.pipe.device)
+        if not self.return_details:
+            return w
+        e = torch.empty(0, self.gpt.num_vq)
+        return SessionDetails(wav=w, ids=torch.empty(0, self.gpt.num_vq, dtype=torch.long, device=self.pipe.device), logprobs=e, sampled_logprobs=e.clone(),
+                              mean_logprob=mean_logprob(e), finished_by_eos=False, refined_text=refined_text)
 
     def _deliver(self, results):
-        spoken = [r for r in results if r.ids.shape[0] > 0]
+        tok = self.pipe.models_dict["tokenizer"]
+        out, code = [], []
+        for r in results:
+            if getattr(r, "mode", "code") != "text":
+                code.append(r)
+                continue
+            # a refine stage ended: cancelled -> the utterance ends here; else filter and decode its ids exactly as infer() does and start the code stage
+            info = self._refining.pop(r.ticket)
+            if r.cancelled or info.get("cancelled"):
+                out.append((r.ticket, self._empty(True), True))
+                continue
+            text = tok.decode([r.ids[r.ids.less(tok.break_0_ids)]])[0]
+            try:
+                tk2 = self._submit_code(text, info["diff"], info["slot"], info["utt_id"])
+            except _lib.HipBackendError as e:
+                # the code stage was refused (a refined text whose prompt no longer fits max_seq_len, ...): this utterance ends here, delivered like a cancelled
+                # one with the reason on record; the other results of the step are not lost
+                self.failed[r.ticket] = str(e)
+                out.append((r.ticket, self._empty(True, refined_text=text), True))
+                continue
+            self._public[tk2], self._code_tk[r.ticket], self._refined[r.ticket] = r.ticket, tk2, text
+        spoken = [r for r in code if r.ids.shape[0] > 0]
         wavs = self.pipe._decode_to_wavs([(r.hiddens if self.use_decoder else r.ids) for r in spoken], self.use_decoder) if spoken else []
         wav_of = {r.ticket: w for r, w in zip(spoken, wavs)}
-        out = []
-        for r in results:
+        for r in code:
+            pub = self._public.pop(r.ticket, r.ticket)
+            self._code_tk.pop(pub, None)
+            refined = self._refined.pop(pub, None)
             w = wav_of.get(r.ticket)
             if w is None:
                 w = torch.zeros(0, device=self.pipe.device)
             if self.return_details:
                 w = SessionDetails(wav=w, ids=r.ids, logprobs=r.logprobs.cpu(), sampled_logprobs=r.sampled_logprobs.cpu(), mean_logprob=mean_logprob(r.logprobs.cpu()),
-                                   finished_by_eos=r.finished_by_eos)
-            out.append((r.ticket, w, r.cancelled))
+                                   finished_by_eos=r.finished_by_eos, refined_text=refined)
+            out.append((pub, w, r.cancelled))
         return out
 
     @torch.no_grad()
     def poll(self):
         """One DecodeSession.step(); what finished is vocoded in one batch.  Returns [(ticket, wav or SessionDetails, cancelled)]: a cancelled utterance with at
-        least one token is vocoded, one with none yields an empty waveform."""
+        least one token is vocoded, one with none yields an empty waveform.  A refine stage that ended is not returned: its code stage is submitted instead."""
         return self._deliver(self.session.step())
 
     def drain(self):
@@ -617,14 +691,19 @@ class ChatTTSPlusPipeline:
                             logits_processors=processors, infer_text=False, return_hidden=return_hidden, stream=stream,
                             show_tqdm=params.show_tqdm, ensure_non_empty=params.ensure_non_empty, stream_batch=params.stream_batch, **gen_kwargs)
 
+    def _refine_prompt(self, text, params: RefineTextParams):
+        """The refine-text prompt of pipeline:237-277 (shared by _refine_text and SynthSession): "[Sbreak]{text}[Pbreak]{prompt}", tokenised.  Returns input_ids
+        [B, T, 4], attention_mask, text_mask (left padded)."""
+        gpt, tok = self.models_dict["gpt"], self.models_dict["tokenizer"]
+        return tok.encode([f"[Sbreak]{i}[Pbreak]{params.prompt}" for i in text], gpt.num_vq, device=self.device)
+
     @torch.no_grad()
     def _refine_text(self, text, params: RefineTextParams, continuous_rows: int = 0, seed=None, utt_ids=None):
         """pipeline:237-277: "[Sbreak]{text}[Pbreak]{prompt}" -> GPT.generate(infer_text=True) on the 21178-way text head.
         `continuous_rows` > 0 (no counterpart in the reference, which refines slice by slice): all sentences of the request through that many decode
         rows with row re-use (GPT.generate_many, device noise keyed by utterance id: a sentence's refined text does not depend on its neighbours)."""
         gpt, tok = self.models_dict["gpt"], self.models_dict["tokenizer"]
-        text = [f"[Sbreak]{i}[Pbreak]{params.prompt}" for i in text]
-        input_ids, attention_mask, text_mask = tok.encode(text, gpt.num_vq, device=self.device)
+        input_ids, attention_mask, text_mask = self._refine_prompt(text, params)
         warpers, processors = gen_logits(num_code=tok.len, top_P=params.top_P, top_K=params.top_K, repetition_penalty=params.repetition_penalty)
         emb = gpt(input_ids, text_mask)
         if continuous_rows > 0:
@@ -1162,17 +1241,21 @@ class ChatTTSPlusPipeline:
 
     # -- serving session (no counterpart in the reference) ------------------------------------------------------------------------
     def open_session(self, params_infer_code: Optional[InferCodeParams] = None, use_decoder: bool = True, lora_path: Optional[str] = None, rows: Optional[int] = None,
-                     seed: Optional[int] = None, return_details: bool = False, **out_of_scope) -> SynthSession:
+                     seed: Optional[int] = None, return_details: bool = False, refine: Optional[RefineTextParams] = None, **out_of_scope) -> SynthSession:
         """A SynthSession: submit(text) / cancel(ticket) / poll() / drain() / close() while the engine keeps decoding -- the decode batch grows when texts arrive
         and shrinks when they end.  `params_infer_code` are the session's values (speaker included; a random one is sampled if it names none), `lora_path` one
         merged adapter for the whole session (an utterance may name its own at submit), `rows` bounds the decode batch, `seed` keys the device noise.
-        Not offered inside a session (refused): num_candidates / shared prompt passes, caller-supplied noise, stream=True windows, infer_sharded, the
-        refine-text pass."""
-        refuse_out_of_scope(out_of_scope, "use infer() for it (refine first with infer(refine_text_only=True) and submit the refined text)")
+        `refine` (a RefineTextParams; max_new_token <= the code parameters', repetition_penalty 1): submit() refines every text first, inside the session -- as
+        a text row beside the code rows (SynthSession); SessionDetails.refined_text carries the result.
+        Not offered inside a session (refused): num_candidates / shared prompt passes, caller-supplied noise, stream=True windows, infer_sharded, and infer()'s
+        call-level names of the refine-text pass (refine_text_only, params_refine_text: use refine=)."""
+        refuse_out_of_scope(out_of_scope, "use infer() for it (the refine-text pass is served inside a session through open_session(refine=RefineTextParams(...)))")
+        if refine is not None and not isinstance(refine, RefineTextParams):
+            raise _lib.HipBackendError("open_session: refine must be a RefineTextParams")
         params = dataclasses.replace(params_infer_code if params_infer_code is not None else InferCodeParams())
         if params.spk_emb is None and params.spk_smp is None:
             params.spk_emb = self.sample_random_speaker()
-        return SynthSession(self, self._gpt_for_lora(lora_path), params, use_decoder, rows, seed, return_details)
+        return SynthSession(self, self._gpt_for_lora(lora_path), params, use_decoder, rows, seed, return_details, refine=refine)
 
     # -- multi-GPU: utterance sharding (SURVEY 8e; BASELINE configs[3]: batch 256 over 8 GPUs) --------------------------------
     @torch.no_grad()

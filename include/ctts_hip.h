@@ -357,8 +357,8 @@ int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, const int32_t
  * Both act on the generate state of the last ctts_gpt_begin, which outlives the call that began it: the output arrays handed to that begin (ids, hiddens, log-probs,
  * finish, end_idx) must still be alive when rows are grown and admitted, as for ctts_gpt_admit -- the engine keeps the pointers, not the memory.
  * Not offered inside one generate state: caller-supplied noise with grow; a session on top of these (GPT.open_session) additionally refuses shared prompt
- * passes / num_candidates, per-utterance streaming windows, infer_sharded and the refine-text pass inside a code session (the engine runs one mode at a time:
- * refine first, submit the refined text). */
+ * passes / num_candidates, per-utterance streaming windows and infer_sharded.  The refine-text pass runs INSIDE such a session as text rows beside the code rows
+ * (ctts_gpt_enable_text_rows below; GPT.open_session(text_rows=...), submit(mode="text")). */
 int ctts_gpt_grow(ctts_gpt* h, int n, void* stream);
 int ctts_gpt_cancel(ctts_gpt* h, int n, const int32_t* rows_host, void* stream);
 
@@ -375,6 +375,41 @@ int ctts_gpt_admit_adapters(ctts_gpt* h, int n, const int32_t* rows, const int32
  * engine address, so captured decode graphs stay valid. */
 int ctts_gpt_set_row_sampling(ctts_gpt* h, const ctts_row_sampling* per_seq, int B);
 int ctts_gpt_admit_sampling(ctts_gpt* h, int n, const int32_t* rows, const ctts_row_sampling* p, void* stream);
+
+/* Text rows beside code rows in one decode batch (no counterpart in the reference, which runs the refine-text pass as a call of its own, pipeline:237-277): the
+ * mode is a property of the decode ROW (0 = code: four codebook rows, the code heads, the code sampler; 1 = text: one row under head_text, the refine-text
+ * sampler, next input = emb_text[id]).  The 20-layer stack, the row record (own step, output slot, limit, utterance id, attempt), compact, grow, admit and cancel
+ * are the same for both; only the sample phase differs.  The call itself is a CODE-mode call (its ctts_sampler_cfg has infer_text = 0), device noise.
+ *   enable_text_rows  gives the generate state its text block: text_sc = the refine pass's parameters (infer_text = 1: temperature[0], top-P, top-K,
+ *                     eos_token = [Ebreak], min_new_token, max_new_token = the text rows' limit) and text_ids_dev int32 [n_out][text max_new_token][4], the text
+ *                     rows' ids (laid out as an infer_text call writes them: the id repeated over the 4 columns), n_out = the extent of the call's ids array.
+ *                     Text utterances take their output slot from the SAME index space as code utterances -- a slot is held by one utterance of either kind --
+ *                     and write finish / end_idx of the call at it.  The text rows' max_new_token must not exceed the code call's: a text row's own step
+ *                     indexes the call's per-slot arrays (the heads write its hidden row at [slot][step] when hiddens are asked for; nobody reads it).
+ *                     The first call allocates the text logits [max_batch][vocab_text] and the block; engines that never call it allocate what they did.
+ *   set_row_modes     HOST modes [B]: modes of sequences 0..B-1 for the following ctts_gpt_begin calls (a persisting request, like set_row_sampling); NULL / 0
+ *                     clears.  ORDER when begin itself seats a text row: set_row_modes, ctts_gpt_begin, ctts_gpt_enable_text_rows, (set_logprob_out,)
+ *                     ctts_gpt_prefill, ctts_gpt_sample -- enable_text_rows needs the state begin creates and clamps the begun text rows' limits to the
+ *                     text max_new_token; sample / decode refuse a batch that holds a text row without it.
+ *   admit_modes       one-shot, like admit_sampling: modes of the utterances the NEXT ctts_gpt_admit seats in `rows`; rows not named become code rows (never the
+ *                     mode of the finished utterance whose row they take).  A mode-1 entry needs enable_text_rows first.
+ * A step is MIXED while a row of the batch has mode 1 (option "text_rows_live", read only: the number of such rows; a finished text row counts until it is
+ * compacted away or its row is handed to a code utterance).  A mixed step runs two more launches: after the code heads, which run over all rows as in any step
+ * (a text row's code logits are not read), the text head over all rows into the text logits; then the code sampler -- the blocks of text rows return after their
+ * first loads -- and the text sampler on the text block -- the blocks of code rows return.  The persistent launch drops its fused heads in mixed steps (they leave
+ * the stack's output in the launch's granules, not in the residual rows the text head reads), so at <= 2 rows the code heads are a third extra launch.  Every row takes
+ * its arrival ticket once per step, in the kernel of its mode; the last arriver advances the step.  Unmixed steps launch exactly what they did.  Device noise:
+ * stream 4 of (seed, utterance id) for a text row, streams 0-3 for a code row, so one utterance id may serve a refine stage and a code stage.
+ * Log-probs (ctts_gpt_set_logprob_out) stay code-only: a text row writes none.  A text row's adapter slot is an argument like any row's (admit_adapters).
+ * Every ctts_gpt_begin switches the feature off again.  Under "batch_invariant" a text row's ids equal those of its batch-1 infer_text call bit for bit, and the
+ * code rows' results do not depend on the text rows beside them.
+ * Refused, each with a message: a mode-1 row without enable_text_rows; an engine without head_text / emb_text; use_penalty in text_sc; caller-supplied noise;
+ * ctts_gpt_share_prompts groups of a call that seats a text row; ctts_gpt_restart while text rows are enabled (re-admit with attempt + 1); per-row sampling
+ * knobs on a text row (set_row_sampling entries that differ from the call's values, admit_sampling entries); a call whose own infer_text is 1; text
+ * max_new_token beyond the code call's. */
+int ctts_gpt_enable_text_rows(ctts_gpt* h, const ctts_sampler_cfg* text_sc, int32_t* text_ids_dev, void* stream);
+int ctts_gpt_set_row_modes(ctts_gpt* h, const int32_t* modes, int B);
+int ctts_gpt_admit_modes(ctts_gpt* h, int n, const int32_t* rows, const int32_t* modes, void* stream);
 
 /* Shared prompt passes (no counterpart in the reference): sequences with ONE prompt -- the N candidates of an utterance, one text at several temperatures or
  * noise keys -- run it through the prompt pass once.  One-shot, like ctts_gpt_admit_sampling: names, for the NEXT ctts_gpt_begin (B == n) or ctts_gpt_admit
