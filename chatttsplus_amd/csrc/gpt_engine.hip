@@ -1589,6 +1589,7 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
     h->B = B; h->B0 = B; h->T = T; h->io = *io;
     h->admitted = false;
     h->sampled = false;
+    h->segs.clear();                  // (debug_read "decode_plan": nothing planned yet for this batch)
     h->rows_host.assign(B, RowState{});
     for (int b = 0; b < B; ++b) {
         RowState& r = h->rows_host[b];
@@ -2315,6 +2316,18 @@ extern "C" int ctts_gpt_debug_read(ctts_gpt* h, const char* name, void* out, siz
         CTTS_HIP_CHECK(hipMemcpy(o, h->pl_epoch, 4, hipMemcpyDeviceToHost));
         CTTS_HIP_CHECK(hipMemcpy(o + 1, h->pl_error, 4, hipMemcpyDeviceToHost));
         if (bytes) *bytes = 8;
+        return 0;
+    }
+    else if (n == "decode_plan") {
+        // host only: what plan_layers decides for the current batch on the path of the last planned decode step (no device work, nothing synchronised)
+        if (h->B == 0 || h->segs.empty()) { ctts_set_error("debug_read: decode_plan: no decode call has been planned for this batch"); return 1; }
+        const DecodePath path = h->segs.back().path;
+        const LayerPlan p = plan_layers(h, h->B, true, path);
+        const int32_t v[] = {h->B, path.splits, path.persist, p.S, p.nbg, p.chunks, p.dts, p.pf_kb, p.valu, p.wide_blocks, p.splitd, p.prepack, p.xhm, p.spd, p.down_sk,
+                             p.fuse_heads, p.lora, p.form.parts, p.form.xh, p.form.logits, p.form.split, p.form.nbg, p.form.valu};
+        if (max_bytes < sizeof(v)) { ctts_set_error("debug_read: buffer too small"); return 1; }
+        memcpy(out, v, sizeof(v));
+        if (bytes) *bytes = sizeof(v);
         return 0;
     }
     if (!src) { ctts_set_error("debug_read: unknown or unallocated buffer '%s'", name); return 1; }

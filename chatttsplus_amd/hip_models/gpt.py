@@ -1797,5 +1797,18 @@ class GPT:
         _lib.check(self._lib.ctts_gpt_logits(self._h, out.data_ptr(), self._stream()), "logits")
         return out
 
+    DECODE_PLAN_FIELDS = ("B", "splits", "persist", "S", "nbg", "chunks", "dts", "pf_kb", "valu", "wide_blocks", "splitd", "prepack", "xhm", "spd", "down_sk",
+                          "fuse_heads", "lora", "form_parts", "form_xh", "form_logits", "form_split", "form_nbg", "form_valu")
+
+    def decode_plan(self) -> dict:
+        """The launch plan of a decode step of the current batch on the path of the last planned step (ctts_gpt_debug_read "decode_plan"): host arithmetic only,
+        no device work.  `splits` / `persist` are the decode path, `S` .. `lora` the layer plan, `form_*` the residual stream's form for the heads."""
+        buf = (C.c_int32 * len(self.DECODE_PLAN_FIELDS))()
+        nb = C.c_size_t(0)
+        _lib.check(self._lib.ctts_gpt_debug_read(self._h, b"decode_plan", buf, C.sizeof(buf), C.byref(nb), None), "debug_read(decode_plan)")
+        if nb.value != C.sizeof(buf):
+            raise _lib.HipBackendError(f"decode_plan: the library returned {nb.value} bytes, this wrapper knows {len(self.DECODE_PLAN_FIELDS)} fields")
+        return dict(zip(self.DECODE_PLAN_FIELDS, (int(v) for v in buf)))
+
     def step_bytes(self, B: int, mean_ctx: float) -> float:
         return float(self._lib.ctts_gpt_step_bytes(self._h, B, float(mean_ctx)))

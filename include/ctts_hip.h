@@ -144,7 +144,11 @@ int ctts_gpt_set_option(ctts_gpt* h, const char* name, int value);
 int ctts_gpt_get_option(ctts_gpt* h, const char* name, int* value);      /* every option that can be set can be read; the EFFECTIVE value ("persistent_rows" reads 0 where the mode is unavailable) */
 
 /* Diagnostics (tools/persist_probe.py): copies a named internal buffer to HOST memory -- "x_dec", "q_buf", "logits", "meta_dec" ({KV lane, pos, slot, kv_start} per decode row), "pl_g" (the persistent
- * layer's granule buffers), "pl_ts" (its per-workgroup phase marks, option "persistent_timestamps"), "pl_state" ({epoch, error}), "xh" / "ssq" (the packed residual copy and its per-tile sums of squares).  Synchronises. */
+ * layer's granule buffers), "pl_ts" (its per-workgroup phase marks, option "persistent_timestamps"), "pl_state" ({epoch, error}), "xh" / "ssq" (the packed residual copy and its per-tile sums of squares).  Synchronises.
+ * "decode_plan" is computed on the host (no device work, no synchronisation, no effect on any launch): the launch plan of a decode step of the current batch on the path
+ * of the last step the last ctts_gpt_decode call planned, as 23 int32 in this order -- B, path.splits, path.persist, then the layer plan S, nbg, chunks, dts, pf_kb, valu,
+ * wide_blocks, splitd, prepack, xhm, spd, down_sk, fuse_heads, lora, then the residual stream's form for the heads parts, xh, logits, split, nbg, valu.  An error before the
+ * first decode call of a batch. */
 int ctts_gpt_debug_read(ctts_gpt* h, const char* name, void* out, size_t max_bytes, size_t* bytes, void* stream);
 
 /* replaces GPT.from_pretrained -> load_state_dict (gpt.py:84-85).  `name` is the reference
