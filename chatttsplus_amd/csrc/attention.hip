@@ -286,11 +286,19 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_g8_kernel(const int* done
 // launch at 8192 rows -- the extra 32 VGPRs cost more occupancy than the exposed load latency.)  Output: normalised rows in the o_proj kernel's fragment-major B operand, like the other kernels.
 #define FA_PITCH 68        // halfs per V^T row in LDS (64 keys + pad; rows stay 8-byte aligned)
 #define FA_KPITCH 72       // halfs per K row in LDS (64 dims + pad; rows stay 16-byte aligned)
+// ANCHOR ("schedule_invariant", AttnArgs.anchor): the 64-key chunk boundaries sit at the sequence's first real key + 64 j (all live queries of a block belong to one sequence; its
+// real queries share one kv_start, a pad query's kv_start is its own slot, before it -- so the first real key is the block's LARGEST kv_start, as in prefill_split.hip) instead
+// of at multiples of 64: a real query's chunk boundaries, and with them the order of its online-softmax rescales, no longer move with the left padding.  Which other queries
+// share the block (that does move with the padding and the pass boundaries) only decides how many chunks the block walks outside a query's [kv_start, slot], and such a chunk
+// leaves the query's state bit for bit as it was: every score is masked, so every p = 0 and the MFMAs add zeros (the staged V rows are rows of the sequence this or an
+// earlier pass wrote).  BEFORE the query's first key: mrun = -inf, sc = 0, lpart and oacc stay +0.  BEYOND its last key: mloc = -inf, mn = mrun, sc = exp(0) = 1 exactly.
+// A template argument: the default instantiation keeps its code and registers.
+template <bool ANCHOR>
 __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(const RowMeta* meta_p, const float* q_p, const half_t* k_p, const half_t* v_p, const int NHp,
                                                               const int R, const AttnArgs a) {
     __shared__ __attribute__((aligned(16))) half_t vt[2][CTTS_HEAD_DIM][FA_PITCH];
     __shared__ __attribute__((aligned(16))) half_t ks[2][64][FA_KPITCH];          // the chunk's K rows as they lie in the cache (+ pad)
-    __shared__ int range_s[4][3];
+    __shared__ int range_s[4][4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int qn = lane & 15, iq = lane >> 4;
     const int b = blockIdx.z, h = blockIdx.y, T = a.T;
@@ -305,6 +313,12 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(const RowMeta* m
 #pragma unroll
     for (int off = 1; off < 16; off <<= 1) { wlo = min(wlo, __shfl_xor(wlo, off)); whi = max(whi, __shfl_xor(whi, off)); wsq = max(wsq, __shfl_xor(wsq, off)); }
     if (lane == 0) { range_s[wave][0] = wlo; range_s[wave][1] = whi; range_s[wave][2] = wsq; }
+    if constexpr (ANCHOR) {
+        int wan = live ? m.kv_start : -1;                                 // the sequence's first real key: the largest kv_start of the block
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1) wan = max(wan, __shfl_xor(wan, off));
+        if (lane == 0) range_s[wave][3] = wan;
+    }
     __syncthreads();
     const int blo = min(min(range_s[0][0], range_s[1][0]), min(range_s[2][0], range_s[3][0]));
     const int bhi = max(max(range_s[0][1], range_s[1][1]), max(range_s[2][1], range_s[3][1]));
@@ -334,7 +348,8 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(const RowMeta* m
     const int skey = tid >> 2, sdim = 16 * (tid & 3);
     half8 vst[2], kst[2];
     auto vload = [&](int c) {
-        const int key = min(c + skey, bhi);                               // clamp: a valid slot of this sequence (masked later)
+        int key = min(c + skey, bhi);                                     // clamp: a valid slot of this sequence (masked later)
+        if constexpr (ANCHOR) key = max(key, blo);                        //   (an anchored first chunk may start below the block's first key, and below slot 0)
         const half8* vp = (const half8*)(vb + (size_t)key * CTTS_HEAD_DIM + sdim);
         const half8* kp = (const half8*)(kb + (size_t)key * CTTS_HEAD_DIM + sdim);
         vst[0] = vp[0]; vst[1] = vp[1];
@@ -346,7 +361,11 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(const RowMeta* m
         *(half8*)&ks[buf][skey][sdim] = kst[0];
         *(half8*)&ks[buf][skey][sdim + 8] = kst[1];
     };
-    const int c0 = blo & ~63;
+    int c0 = blo & ~63;
+    if constexpr (ANCHOR) {
+        const int ban = max(max(range_s[0][3], range_s[1][3]), max(range_s[2][3], range_s[3][3]));
+        c0 = ban - 64 * ((ban - blo + 63) / 64);                          // boundaries at ban + 64 j, extended downwards over the pad queries' keys
+    }
     vload(c0);
     vstore(0);
     __syncthreads();
@@ -426,11 +445,12 @@ int launch_attention(int dtype, const AttnArgs& a, hipStream_t s) {
     static const int wide_env = diag_env("CTTS_ATTN_WIDE") ? atoi(diag_env("CTTS_ATTN_WIDE")) : -1;     // diagnostic builds: force 8-wave (1) / 4-wave (0) blocks
     const bool wide = (a.S == 1) && (a.st != nullptr) && (wide_env < 0 ? (a.R * a.NH < (a.wide_blocks > 0 ? a.wide_blocks : 256)) : wide_env != 0);
     static const int tiled_env = diag_env("CTTS_PREFILL_ATTN") ? atoi(diag_env("CTTS_PREFILL_ATTN")) : 1;    // diagnostic builds: 0 = prompt attention row by row
-    if (a.st == nullptr && a.S == 1 && a.packed_out != nullptr && a.R >= 64 && dtype == 1 && a.T > 0 && tiled_env >= 1) {
-        // prompt pass, fp16: MFMA flash attention, block = (64 queries, head, sequence)
+    if (a.st == nullptr && a.S == 1 && a.packed_out != nullptr && (a.R >= 64 || a.anchor) && dtype == 1 && a.T > 0 && (tiled_env >= 1 || a.anchor)) {
+        // prompt pass, fp16: MFMA flash attention, block = (64 queries, head, sequence); anchored ("schedule_invariant"): at every pass height, 1 row included
         const int B = (a.row0 + a.R + a.T - 1) / a.T;                     // sequences 0 .. B-1 may have rows in this pass
         dim3 g3((a.T + 63) / 64, a.NH, B);
-        hipLaunchKernelGGL(attn_prefill_mfma_kernel, g3, dim3(256), 0, s, a.meta, a.q, (const half_t*)a.k_cache, (const half_t*)a.v_cache, a.NH, a.R, a);
+        if (a.anchor) hipLaunchKernelGGL(attn_prefill_mfma_kernel<true>, g3, dim3(256), 0, s, a.meta, a.q, (const half_t*)a.k_cache, (const half_t*)a.v_cache, a.NH, a.R, a);
+        else hipLaunchKernelGGL(attn_prefill_mfma_kernel<false>, g3, dim3(256), 0, s, a.meta, a.q, (const half_t*)a.k_cache, (const half_t*)a.v_cache, a.NH, a.R, a);
     } else if (wide) {
         if (dtype == 1) hipLaunchKernelGGL((attn_decode_kernel<half_t, 8>), grid, dim3(512), 0, s, done_p, a.meta, a.q, a.k_cache, a.v_cache, a.NH, a.S, a);
         else hipLaunchKernelGGL((attn_decode_kernel<float, 8>), grid, dim3(512), 0, s, done_p, a.meta, a.q, a.k_cache, a.v_cache, a.NH, a.S, a);

@@ -197,6 +197,9 @@ struct ctts_gpt {
                                                  //   projections on 16-row chunks at every row count, the down projection's K always sliced in the launch, layer 0 and the heads in one form, unsplit
                                                  //   8-wave attention, no persistent launch, no VALU rows.  Prompt: the split GEMMs at every pass height, K never sliced, attention chunks anchored
                                                  //   at the first real key.  begin: the last prompt token runs through the first decode step's layer pass, as after ctts_gpt_admit
+                                                 //   fp16 engines take the same contract as "schedule_invariant" (this field under its dtype-independent name; on fp32 engines a synonym): the launch chain on the
+                                                 //   packed fp16 residual stream in 16-row chunks at every row count with the same pins, and ONE prompt arithmetic -- norm_pack + the prefill_gemm.hip GEMM on
+                                                 //   128 x 128 blocks at every pass height, the MFMA flash attention anchored at the first real key -- instead of the split GEMMs (plan_layers, inv16)
     float* rope_dec0 = nullptr;                  //   ... the decode rows' RoPE rows at begin (ctts_gpt_restart replays the first layer pass)
     RowMeta *meta_pre = nullptr, *meta_dec = nullptr, *meta_dec0 = nullptr;
     DevState* st = nullptr;
@@ -428,6 +431,7 @@ struct OptRow { const char* name; int ctts_gpt::*field; int lo, below, hi, above
 #define OPT_ANY 0, 0, 0, 0                               // OPT_FLAG rows and hooks that do not clamp
 static const OptRow g_options[] = {
     {"batch_invariant", &ctts_gpt::batch_inv, OPT_ANY, OPT_RW | OPT_FLAG, 0, HOOK_BATCH_INV},      // fp32 engines: bit-identical rows whatever the batch / schedule (see batch_inv); before or after finalize
+    {"schedule_invariant", &ctts_gpt::batch_inv, OPT_ANY, OPT_RW | OPT_FLAG, 0, HOOK_BATCH_INV},   // the same field under its dtype-independent name: a synonym on fp32 engines, the only accepted setter on fp16 engines
     // prompt passes of >= this many rows use the head / tail fp16 split GEMMs (fp32 engines); 0 = never.  Before finalize: also decides whether the images are built; afterwards the
     // pass can be switched off (0: a checkpoint that leaves the fp16 range, see ctts_gpt_saturations) or moved while the images exist
     {"prefill_split_rows", &ctts_gpt::split_rows_min, OPT_MIN(0), OPT_RW | OPT_PIN, 1, HOOK_PREFILL_SPLIT},
@@ -472,6 +476,8 @@ static const OptRow g_options[] = {
     {"text_rows_live", &ctts_gpt::text_live, OPT_ANY, OPT_R, 0, HOOK_NONE},    // read only: rows of the decode batch whose mode is 1 (ctts_gpt_enable_text_rows); > 0 = every step runs the text head and the text sampler too
     {"lora_mlp_live", &ctts_gpt::lora_mlp, OPT_ANY, OPT_R, 0, HOOK_NONE},      // read only: 1 while a live row's adapter names gate / up / down (the two MLP launches per layer run, decode on the launch chain)
 };
+// the name under which this engine's dtype takes the contract (error messages)
+static inline const char* inv_name(const ctts_gpt* h) { return h->cfg.dtype == CTTS_DTYPE_F16 ? "schedule_invariant" : "batch_invariant"; }
 static const OptRow* find_option(const char* name, int access) {
     for (const OptRow& o : g_options) if (!strcmp(name, o.name)) return (o.flags & access) ? &o : nullptr;
     return nullptr;
@@ -481,7 +487,8 @@ extern "C" int ctts_gpt_get_option(ctts_gpt* h, const char* name, int* value) {
     if (!h || !name || !value) { ctts_set_error("get_option: null argument"); return 1; }
     const OptRow* o = find_option(name, OPT_R);
     if (!o) { ctts_set_error("get_option: unknown option '%s'", name); return 1; }
-    if (h->batch_inv && (o->flags & OPT_PIN)) *value = o->pin;          // what the launches use while the option is on (the tuning values set meanwhile are kept for when it is switched off)
+    if (h->batch_inv && (o->flags & OPT_PIN))          // what the launches use while the option is on (the tuning values set meanwhile are kept for when it is switched off)
+        *value = (h->cfg.dtype == CTTS_DTYPE_F16 && (o->hook == HOOK_PREFILL_SPLIT || o->hook == HOOK_SPLIT_DECODE)) ? 0 : o->pin;      // (fp16 engines hold no head / tail images: both mechanisms read "never")
     else if (o->hook == HOOK_PERSIST_ROWS) *value = (h->persist_ok || !h->finalized) ? h->persist_rows : 0;
     else *value = h->*o->field;
     return 0;
@@ -494,9 +501,10 @@ extern "C" int ctts_gpt_set_option(ctts_gpt* h, const char* name, int value) {
     if (!o) { ctts_set_error("set_option: unknown option '%s'", name); return 1; }
     const bool images = h->split_ok && h->wsplit;      // (refusals first: a refused value changes nothing)
     if (o->hook == HOOK_BATCH_INV) {
-        if (h->cfg.dtype != CTTS_DTYPE_F32) { ctts_set_error("set_option(batch_invariant): fp32 (parity) engines only"); return 1; }
-        if (value && h->finalized && !(images && h->whead_sp)) {
-            ctts_set_error("set_option(batch_invariant): this engine holds no head / tail weight images (a weight beyond the fp16 range, or split_decode_rows and prefill_split_rows were 0 at finalize)");
+        // fp16 engines take the contract under its dtype-independent name only (their pinned stack needs no head / tail images)
+        if (h->cfg.dtype != CTTS_DTYPE_F32 && strcmp(name, "schedule_invariant")) { ctts_set_error("set_option(batch_invariant): fp32 (parity) engines only; an fp16 engine takes the contract as \"schedule_invariant\""); return 1; }
+        if (value && h->cfg.dtype == CTTS_DTYPE_F32 && h->finalized && !(images && h->whead_sp)) {
+            ctts_set_error("set_option(%s): this engine holds no head / tail weight images (a weight beyond the fp16 range, or split_decode_rows and prefill_split_rows were 0 at finalize)", name);
             return 1;
         }
     } else if (o->hook == HOOK_PREFILL_SPLIT || o->hook == HOOK_SPLIT_DECODE) {
@@ -1108,6 +1116,8 @@ static inline void* kv_layer(ctts_gpt* h, int l, int which) {
 // The row-count thresholds the launches use.  "batch_invariant" pins every choice that depends on the row count, the pass height or the padding, and THIS is where: no
 // persistent launch, no VALU rows, the split projections from 1 row on (one padded 16-row chunk), the down projection's K sliced inside the launch and never by launch slices,
 // never 32-row blocks at decode, unsplit attention on 8-wave blocks, the prompt's K never sliced (ctts_gpt_begin refuses adapters then).  plan_layers adds the two choices that are no threshold.
+// The same pins serve fp16 engines ("schedule_invariant"): split_dec_rows / valu_rows / split_nbg2_rows name fp32 mechanisms and are simply never consulted there, the rest puts every row
+// count on the packed-residual chain (xhm) in 16-row chunks with EPI_RESID_XH_SK; the weight-prefetch workgroups keep their own threshold (17 rows): they do no arithmetic.
 struct Tuning { bool inv; int persist_rows, valu_rows, split_dec_rows, split_rows, down_sk_rows, nbg2_rows, split_nbg2_rows, force_splits, attn_wide_blocks, prefill_sk_rows; };
 static inline Tuning tuning(const ctts_gpt* h) {
     if (h->batch_inv) return {true, 0, 0, 1, 0, 1, OPT_MAX, OPT_MAX, 1, OPT_MAX, 0};
@@ -1155,6 +1165,7 @@ static inline StreamForm plain_form(const ctts_gpt* h) { return stream_form(h, f
 struct LayerPlan {
     bool lora, lmlp;                  // per-utterance adapters: the residual stream must be materialised in x (no split-K partials) / ... on gate / up / down too: their terms come from two more lora.hip launches per layer, decode and prompt pass alike
     int S, nbg, chunks, dts, pf_kb, valu, wide_blocks, anchor, prefill_sk_rows;      // key splits; 16 * nbg rows per block, blocks; launch_gemm's operand format; see plan_layers for the rest
+    int pfg_shape;                    // block shape of prefill_gemm.hip (-1 = by pass height)
     bool splitd, prepack, pfg, pfs, xhm, spd, down_sk, fuse_heads;
     int persist, per, pace, poll, delay_act, delay_u;      // persistent launch: key shares (0 = the launch chain), layers per launch, and its row-count defaults resolved
     StreamForm form;
@@ -1167,18 +1178,22 @@ static LayerPlan plan_layers(const ctts_gpt* h, int R, bool decode, DecodePath p
     // fp32 engines, decode batches of >= split_decode_rows rows: head / tail fp16 operands (the predicate is completed below; it needs the packed-residual path)
     const bool spd_ok = decode && dt == CTTS_DTYPE_F32 && h->xh_mode && h->split_ok && h->wsplit != nullptr && !p.lora && p.S == 1 &&
                         t.split_dec_rows > 0 && R >= t.split_dec_rows && R > t.split_rows;
-    p.nbg = decode ? decode_nbg(t, R, spd_ok) : (R <= 16 ? 1 : 2);      // (the prompt pass keeps 32-row blocks)
+    // invariant fp16 engines ("schedule_invariant"): ONE prompt arithmetic at every pass height, 1 row included -- norm_pack, then the LDS-staged GEMM of prefill_gemm.hip
+    // (every output accumulated by one wave in k order, rows past the end clamped, operand buffers sized for whole blocks) on its 128 x 128 blocks
+    const bool inv16 = t.inv && dt == CTTS_DTYPE_F16 && !decode;
+    p.nbg = decode ? decode_nbg(t, R, spd_ok) : ((R <= 16 && !inv16) ? 1 : 2);      // (the prompt pass keeps 32-row blocks)
     p.chunks = (R + 16 * p.nbg - 1) / (16 * p.nbg);
     // small decode batches: the down projection is launched as 4 split-K slices (192 blocks instead of 48 x 1024 threads);
     // its partial sums dp[0..3] are added, in order, by the next consumers of the residual stream (QKV RMSNorm, o_proj
     // residual, final heads) -- deterministic, no atomics.  x itself is re-materialised by every o_proj.
     p.splitd = decode && (R <= t.split_rows) && (p.nbg == 1) && !p.lora;
     // prompt pass over more than a few chunks: normalise every row once (norm_pack_kernel) instead of in every GEMM block
-    p.prepack = !decode && (p.nbg == 2) && (R > 64) && !h->no_prepack;
+    p.prepack = inv16 || (!decode && (p.nbg == 2) && (R > 64) && !h->no_prepack);
     // prompt pass over >= 1536 rows, fp16: LDS-staged 256/128 x 128 MFMA GEMM (prefill_gemm.hip) instead of one weight tile per 32-row block
     // (measured with 128 x 128 blocks, prompt pass ms with / without it: 512 rows 2.31 / 1.48, 1024 rows 2.47 / 2.29, 1536 rows 2.70 / 3.12,
     //  2048 rows 2.81 / 3.9, 3072 rows 3.6 / 5.3, 16384 rows 10.3 / 29)
-    p.pfg = p.prepack && (dt == CTTS_DTYPE_F16) && h->prefill_gemm_rows > 0 && (R >= h->prefill_gemm_rows) && !p.lora;
+    p.pfg = inv16 || (p.prepack && (dt == CTTS_DTYPE_F16) && h->prefill_gemm_rows > 0 && (R >= h->prefill_gemm_rows) && !p.lora);
+    p.pfg_shape = inv16 ? 0 : -1;
     // prompt pass over >= 384 rows, fp32 engine: the same tiling on the fp16 pipes with head / tail operands -- 3 MFMAs per product instead of 16,
     // fp32-level accuracy (prefill_split.hip); the attention stays the fp32 row kernel
     // (round 5: also with per-utterance adapters -- their low-rank terms come from the two lora.hip launches per layer and are added in the split GEMMs' epilogues)
@@ -1291,7 +1306,7 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
         } else if (prepack) {
             g1.xpacked = h->norm_packed;
             if (launch_norm_pack(dt, x, h->norm_packed, R, nbg, a.eps, s)) return 1;
-            if (pfg ? launch_prefill_gemm(EPI_QKV, g1, s) : launch_gemm(dt, nbg, PRO_PACKED, EPI_QKV, g1, chunks, s)) return 1;
+            if (pfg ? launch_prefill_gemm(EPI_QKV, g1, s, p.pfg_shape) : launch_gemm(dt, nbg, PRO_PACKED, EPI_QKV, g1, chunks, s)) return 1;
         } else if (xhm) {
             g1.scale_out = h->scale_o;
             if (l > 0) { g1.xh = h->xh; g1.ssq = h->ssq; g1.scale_in = h->scale_d; }
@@ -1323,7 +1338,7 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
         }
         if (pfs && S == 1) {
             if (launch_prefill_split_gemm(EPI_RESID, g2, h->lw[l].o_sp, h->sp_x_hi, h->sp_x_lo, nullptr, nullptr, sp_scale, sp_pol, s)) return 1;
-        } else if (pfg && S == 1) { if (launch_prefill_gemm(EPI_RESID, g2, s)) return 1; }
+        } else if (pfg && S == 1) { if (launch_prefill_gemm(EPI_RESID, g2, s, p.pfg_shape)) return 1; }
         else {
             if (spd) g2.W = h->lw[l].o_sp;
             set_pf(g2, spd ? h->lw[l].gu_sp : h->lw[l].gu, 2 * h->I / 16, h->H, dts);
@@ -1344,7 +1359,7 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
         } else if (prepack) {
             g3.xpacked = h->norm_packed;
             if (launch_norm_pack(dt, x, h->norm_packed, R, nbg, a.eps, s)) return 1;
-            if (pfg ? launch_prefill_gemm(EPI_SWIGLU, g3, s) : launch_gemm(dt, nbg, PRO_PACKED, EPI_SWIGLU, g3, chunks, s)) return 1;
+            if (pfg ? launch_prefill_gemm(EPI_SWIGLU, g3, s, p.pfg_shape) : launch_gemm(dt, nbg, PRO_PACKED, EPI_SWIGLU, g3, chunks, s)) return 1;
         } else if (xhm) {
             g3.xh = h->xh; g3.ssq = h->ssq; g3.scale_in = h->scale_o; g3.scale_out = h->scale_d;
             if (spd) g3.W = h->lw[l].gu_sp;
@@ -1363,7 +1378,7 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
         if (pfs) {      // the SwiGLU images hold silu(g) * u / 16
             if (launch_prefill_split_gemm(EPI_RESID, g4, h->lw[l].d_sp, h->sp_act_hi, h->sp_act_lo, nullptr, nullptr, sp_scale * 16.0f, sp_pol, s)) return 1;
         } else if (pfg) {
-            if (launch_prefill_gemm(EPI_RESID, g4, s)) return 1;
+            if (launch_prefill_gemm(EPI_RESID, g4, s, p.pfg_shape)) return 1;
         } else if (splitd) {
             g4.part_out = h->dpart; g4.ktiles_total = h->I / (h->esz == 2 ? 32 : 16);
             if (launch_gemm(dt, nbg, PRO_PACKED, EPI_PART, g4, chunks, s)) return 1;
@@ -1464,7 +1479,7 @@ static int seat_row_adapters(ctts_gpt* h, int B, const char* who, hipStream_t s)
     if (lora_ensure_mlp_terms(h)) { h->lora_rows = 0; h->lora_mlp = 0; h->B = 0; return 1; }
     if (h->lora_rows && h->batch_inv) {
         h->lora_rows = 0; h->lora_mlp = 0; h->B = 0;
-        ctts_set_error("%s: per-utterance adapters (ctts_gpt_set_row_adapters) are outside the batch_invariant contract; set the option to 0 or merge the adapter", who);
+        ctts_set_error("%s: per-utterance adapters (ctts_gpt_set_row_adapters) are outside the %s contract; set the option to 0 or merge the adapter", who, inv_name(h));
         return 1;
     }
     if (h->lora_slot_of_seq)        // (pageable source: staged before the call returns)
@@ -1573,7 +1588,12 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
         if (sc->use_penalty) { ctts_set_error("begin: infer_text supports repetition_penalty == 1 only (the reference's processor mis-broadcasts the [B,n,1] history in this mode)"); return 1; }
         if (sc->eos_token >= h->vocab_text_head) { ctts_set_error("begin: eos out of range"); return 1; }
     } else if (sc->past_window > 16 || sc->eos_token >= h->V) { ctts_set_error("begin: past_window>16 or eos out of range"); return 1; }
-    if (h->batch_inv && !(h->split_ok && h->wsplit && h->whead_sp)) {
+    if (h->batch_inv && h->cfg.dtype == CTTS_DTYPE_F16 && io->noise != nullptr) {
+        // (fp32 engines keep accepting it -- the reference goldens replay torch's draws under the option -- though it is outside the contract there too)
+        ctts_set_error("begin: caller-supplied noise is indexed by the batch's draw counter and is outside the schedule_invariant contract; use device noise or set the option to 0");
+        return 1;
+    }
+    if (h->batch_inv && h->cfg.dtype == CTTS_DTYPE_F32 && !(h->split_ok && h->wsplit && h->whead_sp)) {
         ctts_set_error("begin: batch_invariant needs the head / tail weight images, and a weight of this checkpoint is beyond the fp16 range (x 64)");
         return 1;
     }
@@ -1716,7 +1736,7 @@ extern "C" int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* mask, co
             return 1;
         }
     }
-    if (h->batch_inv && !(h->split_ok && h->wsplit)) {
+    if (h->batch_inv && h->cfg.dtype == CTTS_DTYPE_F32 && !(h->split_ok && h->wsplit)) {
         ctts_set_error("score: batch_invariant needs the head / tail weight images, and a weight of this checkpoint is beyond the fp16 range (x 64)");
         return 1;
     }
@@ -2133,7 +2153,7 @@ extern "C" int ctts_gpt_admit_adapters(ctts_gpt* h, int n, const int32_t* rows, 
         if (rows[i] < 0 || rows[i] >= h->B || slots[i] >= CTTS_MAX_ADAPTERS) { ctts_set_error("admit_adapters: row %d / slot %d out of range", rows[i], slots[i]); return 1; }
         any = any || slots[i] >= 0;
     }
-    if (any && h->batch_inv) { ctts_set_error("admit_adapters: per-utterance adapters are outside the batch_invariant contract; set the option to 0 or merge the adapter"); return 1; }
+    if (any && h->batch_inv) { ctts_set_error("admit_adapters: per-utterance adapters are outside the %s contract; set the option to 0 or merge the adapter", inv_name(h)); return 1; }
     if (any && lora_ensure_storage(h)) return 1;
     for (int i = 0; i < n; ++i) {
         const int sl = slots[i] < 0 ? -1 : slots[i];
@@ -2168,7 +2188,7 @@ extern "C" int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, co
     const int P = share.empty() ? n : share_P;   // prompts: mask [P][T], emb [P][T][H]
     if (!rows || !mask || !emb || !utt_ids || !out_index) { ctts_set_error("admit: null argument"); return 1; }
     if (h->io.noise != nullptr) { ctts_set_error("admit: device noise only (caller-supplied noise is indexed by the batch's draw counter)"); return 1; }
-    if (h->batch_inv && h->lora_rows) { ctts_set_error("admit: per-utterance adapters are outside the batch_invariant contract; set the option to 0 or merge the adapter"); return 1; }
+    if (h->batch_inv && h->lora_rows) { ctts_set_error("admit: per-utterance adapters are outside the %s contract; set the option to 0 or merge the adapter", inv_name(h)); return 1; }
     if (n < 1 || n > h->B || T < 1 || T + h->sc.max_new > h->cfg.max_seq || (long long)P * (T - 1) > h->pass_rows) {
         ctts_set_error("admit: n=%d of %d rows on %d prompts, T=%d (max_seq %d; %d x %d prompt rows for %d per pass)", n, h->B, P, T, h->cfg.max_seq, P, T - 1, h->pass_rows);
         return 1;

@@ -111,8 +111,8 @@ struct AttnArgs {
     int packed_split;       //   fp32 engine: packed_out is the head / tail fp16 image pair of the split decode kernels (common.h split_t), not fp32 fragments
     int T, row0;            // prompt pass (MFMA flash kernel): prompt length and the flattened index b*T + t of the pass's first row
     int wide_blocks;        // decode, unsplit: 8-wave blocks while rows x heads < this (0 = 256: fewer blocks than CUs; option "attn_wide_blocks")
-    int anchor;             // prompt pass, fp32 engine (option "batch_invariant"): 64-key chunks start at the sequence's first real key instead of at multiples of 64,
-                            //   so that the left padding of a batch cannot regroup a query's online-softmax sum
+    int anchor;             // prompt pass (options "batch_invariant" / "schedule_invariant"): 64-key chunks start at the sequence's first real key instead of at multiples of 64,
+                            //   so that the left padding of a batch cannot regroup a query's online-softmax sum; fp16 engines then take the MFMA flash kernel at every pass height
 };
 
 struct SamplerCfgDev {      // mirrors ctts_sampler_cfg
@@ -192,7 +192,7 @@ int launch_lora_delta_down(int dtype, const void* act_packed, int nbg, const Row
                            const float* scale_l, float* delta, int rows, int H, int I, hipStream_t s);
 int launch_lora_delta_down_split(const void* hi, const void* lo, const RowMeta* meta, const int* slot_of_seq, const float* A_l, const float* B_l,
                                  const float* scale_l, float* delta, int rows, int H, int I, hipStream_t s);
-int launch_prefill_gemm(int epi, const GemmArgs& a, hipStream_t s);      // prefill_gemm.hip: fp16 prompt-pass GEMM (QKV / RESID / SWIGLU epilogues)
+int launch_prefill_gemm(int epi, const GemmArgs& a, hipStream_t s, int shape_pin = -1);      // prefill_gemm.hip: fp16 prompt-pass GEMM (QKV / RESID / SWIGLU epilogues); shape_pin >= 0: that block shape whatever the pass height
 int launch_norm_pack_split(const float* x, void* hi, void* lo, int R, float eps, hipStream_t s);                    // prefill_split.hip (fp32 engine, >= 1536 prompt rows)
 int launch_split_pack(const float* src, void* hi, void* lo, int R, hipStream_t s);
 int launch_attention_split(const AttnArgs& a, void* out_hi, void* out_lo, hipStream_t s);

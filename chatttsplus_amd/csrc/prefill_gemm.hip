@@ -286,7 +286,7 @@ static int pf_shape(int shape, const GemmArgs& a, const void* X, int ktiles, hip
 
 // fp16 only.  X = packed activations (norm_packed / attn_packed / act); the operand buffers must cover whole blocks of rows
 // (gpt_engine.hip allocates them for PASS_ROWS + 256 rows).
-int launch_prefill_gemm(int epi, const GemmArgs& a, hipStream_t s) {
+int launch_prefill_gemm(int epi, const GemmArgs& a, hipStream_t s, int shape_pin) {
     const void* X = a.xpacked;
     const int ktiles = a.K / 32;
     // block shape per projection: 0 = 128 x 128, 1 = 256 x 128, 2 = 256 x 256.  CTTS_PF_SHAPE = "qkv,gateup,resid" overrides (diagnostic).
@@ -301,7 +301,8 @@ int launch_prefill_gemm(int epi, const GemmArgs& a, hipStream_t s) {
     int shape = shape_env[which];
     // measured (32 x 512 / 8 x 2000 tokens per pass): all 128 x 128 9.99 / 13.50 ms; gate|up on 256 x 128 9.70 / 13.37; gate|up + QKV on 256 x 128
     // 9.79 / 13.64; everything on 256 x 256 10.10 / 14.08.  Below 8192 rows the 128 x 128 grid fills the chip better (4 x 512: 2.51 vs 2.57 ms).
-    if (shape < 0) shape = (epi == EPI_SWIGLU && a.R >= 8192) ? 1 : 0;
+    if (shape_pin >= 0) shape = shape_pin;                 // "schedule_invariant": no choice may follow the pass height (the shapes share one k order per output; pinned all the same)
+    else if (shape < 0) shape = (epi == EPI_SWIGLU && a.R >= 8192) ? 1 : 0;
     if (epi == EPI_QKV) return pf_shape<EPI_QKV>(shape, a, X, ktiles, s);
     if (epi == EPI_SWIGLU) return pf_shape<EPI_SWIGLU>(shape, a, X, ktiles, s);
     if (epi == EPI_RESID) return pf_shape<EPI_RESID>(shape, a, X, ktiles, s);

@@ -697,8 +697,8 @@ class DecodeSession:
             raise ValueError("submit: the prompt has no attended token")
         knobs = row_sampling_from_values(self.sc, sampling, g.num_vq) if sampling is not None else None
         slot = -1 if adapter_slot is None or int(adapter_slot) < 0 else int(adapter_slot)
-        if slot >= 0 and g.options.get("batch_invariant", 0):
-            raise _lib.HipBackendError("submit: per-utterance adapters are outside the batch_invariant contract; merge the adapter (with_lora) or set the option to 0")
+        if slot >= 0 and g.invariant_option():
+            raise _lib.HipBackendError(f"submit: per-utterance adapters are outside the {g.invariant_option()} contract; merge the adapter (with_lora) or set the option to 0")
         try:
             tk = self.book.submit(n, utt_id, limit, mode)
         except ValueError as e:
@@ -948,6 +948,14 @@ class GPT:
             _lib.check(self._lib.ctts_gpt_set_option(self._h, str(name).encode(), int(value)), f"set_option({name})")
         self.options[str(name)] = int(value)
 
+    def invariant_option(self) -> Optional[str]:
+        """The name under which this engine keeps the batch-invariance contract -- "batch_invariant" (fp32 engines) or its dtype-independent name
+        "schedule_invariant" (either dtype; the only setter on fp16 engines) -- or None while neither is on."""
+        for name in ("batch_invariant", "schedule_invariant"):
+            if self.options.get(name, 0):
+                return name
+        return None
+
     def get_option(self, name: str) -> int:
         """The effective value of an engine option (ctts_gpt_get_option)."""
         v = C.c_int(0)
@@ -1088,14 +1096,15 @@ class GPT:
         every projection the row's adapter names evaluates W x + scale * B (A x) per row (q/k/v/o -- decode: inside the projection launches, lora_worker.h; prompt pass: two
         more launches per layer.  gate / up / down: two more launches per layer, decode and prompt pass, while a live row's slot holds such a target; decode steps then take the
         launch chain at every row count).
-        Not under options={"batch_invariant": 1}: per-utterance adapters are outside its contract (a merged adapter, with_lora(), is covered)."""
+        Not under options={"batch_invariant": 1} / {"schedule_invariant": 1}: per-utterance adapters are outside the contract (a merged adapter, with_lora(), is covered)."""
         with torch.cuda.device(self.device):
             if slots is None:
                 _lib.check(self._lib.ctts_gpt_set_row_adapters(self._h, None, 0), "set_row_adapters")
                 return
-            if self.options.get("batch_invariant", 0) and any(s is not None and int(s) >= 0 for s in slots):
-                raise _lib.HipBackendError("set_row_adapters: per-utterance adapters are outside the batch_invariant contract; construct the GPT with "
-                                           "options={'batch_invariant': 0}, or merge the adapter into a sibling engine (with_lora)")
+            inv = self.invariant_option()
+            if inv and any(s is not None and int(s) >= 0 for s in slots):
+                raise _lib.HipBackendError(f"set_row_adapters: per-utterance adapters are outside the {inv} contract; construct the GPT with "
+                                           f"options={{'{inv}': 0}}, or merge the adapter into a sibling engine (with_lora)")
             arr = np.ascontiguousarray([(-1 if s is None else int(s)) for s in slots], dtype=np.int32)
             _lib.check(self._lib.ctts_gpt_set_row_adapters(self._h, arr.ctypes.data_as(C.c_void_p), int(arr.size)), "set_row_adapters")
 
@@ -1148,7 +1157,7 @@ class GPT:
             import warnings
             if self.dtype_code == _lib.DTYPE_F16:
                 msg = f"use weight_dtype='fp32' for this checkpoint"
-            elif self.options.get("batch_invariant", 0):
+            elif self.invariant_option():
                 # the option's contract is one arithmetic per row: switching kernels between calls would break it, so they stay
                 msg = ("the fp32 engine keeps silu(gate) * up / 16 and the scaled residual rows as fp16 head / tail images; THIS call's values were clipped there.  "
                        "batch_invariant is on, so the engine keeps these kernels (results stay schedule-independent, and clipped); construct the GPT with "
@@ -1236,7 +1245,8 @@ class GPT:
         if isinstance(noise, str) and noise == "auto":
             # host draws cost ~21 ns per element and step: 10k elements (4 sequences x 4 x 626) hide behind the GPU step, one
             # 21178-wide refine-text row already does not (measured: 502 vs 423 us/step at batch 1, 1.2 vs 0.5 ms at batch 4)
-            noise = "torch" if (B <= 4 and B * rows_per_seq * V <= 16384) else "device"
+            # (an fp16 engine under "schedule_invariant" takes device noise only: ctts_gpt_begin refuses a caller's draws there)
+            noise = "torch" if (B <= 4 and B * rows_per_seq * V <= 16384 and not (self.dtype_code == _lib.DTYPE_F16 and self.invariant_option())) else "device"
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (isinstance(noise, str) and noise == "device") else 0
         mask = torch.ones(int(inputs_ids.shape[0]), T, dtype=torch.int32, device=dev) if attention_mask is None else attention_mask.to(dev).to(torch.int32).contiguous()

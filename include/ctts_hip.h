@@ -143,6 +143,38 @@ void ctts_gpt_destroy(ctts_gpt* h);
 int ctts_gpt_set_option(ctts_gpt* h, const char* name, int value);
 int ctts_gpt_get_option(ctts_gpt* h, const char* name, int* value);      /* every option that can be set can be read; the EFFECTIVE value ("persistent_rows" reads 0 where the mode is unavailable) */
 
+/* One more option, the dtype-independent name of the contract above: "schedule_invariant" (flag, default 0, read / write, before or after finalize; part of the
+ * decode-graph key like every option).
+ *   fp32 engines: a synonym of "batch_invariant" -- the same field, the same hook, the same refusals; either name reads what the other set.
+ *   fp16 engines: the ONLY accepted setter (setting "batch_invariant" there stays an error, whose message names this option).  While it is on,
+ *       get_option("batch_invariant") reads 1 too -- reading was never refused -- so hosts that ask "does this engine keep the contract?" under the older
+ *       name (share_prompt=None of infer(num_candidates=N), the sessions, generate_many) need no change.
+ * With the option at 0 every engine launches exactly what it launched without it.
+ * The CONTRACT on fp16 engines is the one stated above, word for word: under device noise an utterance's hidden rows, token ids, end_idx and log-probs are bit
+ * for bit a function of its own inputs only -- not of the batch size, max_batch, its row or KV lane; the other utterances and their padding; compaction, begin
+ * versus admit, grow, or the cancel of other rows; the service order, slice size or rank count; the pass boundaries of the prompt pass; shared prompt passes.
+ * Scoring (ctts_gpt_score: logprob, argmax), the refine-text pass and text rows beside code rows are covered as on fp32 engines.  Values are fp16-mode values:
+ * the option changes which fp16 kernels run, not their precision (mel / waveform against the CPU oracle stay within the fp16 mode's 2e-3).
+ * How, on fp16 engines -- no head / tail weight images are involved, and no message that demands them fires:
+ *   decode  the launch chain at every row count on the packed fp16 residual stream (EPI_RESID_XH -> PRO_XH) in 16-row chunks (1..8 rows: one padded chunk; never
+ *       32-row blocks), the down projection's K always sliced four ways inside the launch with the fixed-order last-arriver combine (EPI_RESID_XH_SK), never
+ *       split-K launch slices, layer 0's q|k|v (PRO_NORM) and the code heads (PRO_XH) / text head (PRO_NORM_P) on 16-row chunks in one prologue form each,
+ *       decode attention unsplit (S = 1) on 8-wave blocks, no persistent launch (its weight images are never built).  The weight-prefetch workgroups stay
+ *       live ("weight_prefetch_kb", from 17 rows): they do no arithmetic.  No pin beyond this list turned out to be needed.
+ *   prompt  ONE projection arithmetic at every pass height, the 1-row pass included: norm_pack, then the LDS-staged GEMM of prefill_gemm.hip -- every output is
+ *       accumulated by one wave in k order, rows past the end are clamped, K is never sliced -- pinned to its 128 x 128 blocks (the taller shapes share the
+ *       k order; the choice by pass height is switched off all the same).  The MFMA flash attention at every pass height too, its 64-key chunks anchored at
+ *       the sequence's first real key; a chunk outside a query's own [first real key, slot] leaves that query's state bit-unchanged, so the queries that happen
+ *       to share its 64-query block do not matter.  ctts_gpt_prefill passes T - 1 prompt tokens, the last one runs through the first decode step's layer pass
+ *       (ctts_gpt_sample), exactly as after ctts_gpt_admit; ctts_gpt_restart replays that pass; ctts_gpt_score runs its heads on 16-row chunks.
+ *   fp16 saturating stores and ctts_gpt_saturations behave as without the option.
+ * ctts_gpt_get_option while the option is on, fp16 engines: persistent_rows 0, split_rows 0, down_splitk_rows 1, nbg2_rows 0 (never), decode_splits 1,
+ * attn_wide_blocks INT_MAX, prefill_splitk_rows 0; the fp32-only mechanisms read what "never used" reads: split_decode_rows 0, prefill_split_rows 0 (fp32 engines:
+ * 1 and 1), split_nbg2_rows 0, valu_rows 0.  Stored values return when the option is switched off.
+ * OUTSIDE the contract, and refused with a message naming the option: per-utterance adapters (ctts_gpt_set_row_adapters / ctts_gpt_admit_adapters, begin / admit
+ * with a live adapter row), as on fp32 engines; caller-supplied noise -- fp16 engines refuse it at ctts_gpt_begin (fp32 engines keep accepting it: their
+ * reference goldens replay torch's draws under the option; it is outside the contract there as well). */
+
 /* Diagnostics (tools/persist_probe.py): copies a named internal buffer to HOST memory -- "x_dec", "q_buf", "logits", "meta_dec" ({KV lane, pos, slot, kv_start} per decode row), "pl_g" (the persistent
  * layer's granule buffers), "pl_ts" (its per-workgroup phase marks, option "persistent_timestamps"), "pl_state" ({epoch, error}), "xh" / "ssq" (the packed residual copy and its per-tile sums of squares).  Synchronises.
  * "decode_plan" is computed on the host (no device work, no synchronisation, no effect on any launch): the launch plan of a decode step of the current batch on the path

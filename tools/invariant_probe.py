@@ -3,7 +3,9 @@
   prompt    the prompt pass (begin + prefill) at 32 x 512, 8 x 56 and 1 x 96 tokens
   request   the 256-utterance request of bench._request_256 through infer_sharded(continuous=True) at 32 / 16 / 8 rows x longest-first / arrival
             order: useful tok/s and how many utterances keep the token ids of the 32-row longest-first run
-usage: python tools/invariant_probe.py [out.jsonl] [--skip-request]"""
+usage: python tools/invariant_probe.py [out.jsonl] [--skip-request] [--dtype fp16]
+--dtype fp16: the same three probes on fp16 engines, default mode against option "schedule_invariant" (out.jsonl defaults to profiles/invariant_fp16_probe.jsonl).
+The two engines live side by side in one process and alternate, three rounds: step and prompt lines carry the median and the spread (min, max) of the three."""
 import ctypes as C
 import json
 import os
@@ -22,7 +24,10 @@ from chatttsplus_amd.hip_models.gpt import GPT, sampler_cfg_from_objects  # noqa
 LW = [type("P", (), dict(top_p=0.7, min_tokens_to_keep=3))(), type("K", (), dict(top_k=20))()]
 LP = [type("R", (), dict(penalty=1.05, past_window=16, max_input_ids=625))()]
 dev = torch.device("cuda:0")
-out_path = next((a for a in sys.argv[1:] if not a.startswith("--")), None)
+DTYPE = sys.argv[sys.argv.index("--dtype") + 1] if "--dtype" in sys.argv else "fp32"
+out_path = next((a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] != "--dtype"), None)
+if out_path is None and DTYPE == "fp16":
+    out_path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "invariant_fp16_probe.jsonl")
 
 
 def emit(rec):
@@ -45,9 +50,9 @@ def begin(g, B, T, N):
     return emb, sc, io, st, msk, bufs
 
 
-def step_times(g, mode):
+def step_times(g, mode, rows=(1, 2, 4, 8, 9, 16, 17, 24, 32, 33, 64), collect=None):
     lib, h = g._lib, g._h
-    for B in (1, 2, 4, 8, 9, 16, 17, 24, 32, 33, 64):
+    for B in rows:
         P, N = 48, 600
         emb, sc, io, st, msk, bufs = begin(g, B, P, N)
         _lib.check(lib.ctts_gpt_begin(h, B, P, msk.data_ptr(), C.byref(sc), C.byref(io), st), "begin")
@@ -56,10 +61,13 @@ def step_times(g, mode):
         _lib.check(lib.ctts_gpt_decode(h, 160, 1, st), "warm")
         ms = C.c_float(0)
         _lib.check(lib.ctts_gpt_time_decode(h, 200, C.byref(ms), st), "time")          # steps 161 .. 360: mean context 48 + 261
+        if collect is not None:
+            collect.setdefault(("step", mode, B), []).append(ms.value)
+            continue
         emit({"probe": "step", "mode": mode, "rows": B, "mean_ctx": 48 + 261, "ms_per_step": round(ms.value, 4)})
 
 
-def prompt_times(g, mode):
+def prompt_times(g, mode, collect=None):
     lib, h = g._lib, g._h
     for B, T in ((32, 512), (8, 56), (1, 96)):
         emb, sc, io, st, msk, bufs = begin(g, B, T, 16)
@@ -73,6 +81,9 @@ def prompt_times(g, mode):
             torch.cuda.synchronize(dev)
             if rep:
                 best = e0.elapsed_time(e1) if best is None else min(best, e0.elapsed_time(e1))
+        if collect is not None:
+            collect.setdefault(("prompt", mode, (B, T)), []).append(best)
+            continue
         emit({"probe": "prompt", "mode": mode, "B": B, "T": T, "ms": round(best, 3)})
 
 
@@ -86,7 +97,7 @@ def request(mode, options):
     syn.load("dvae.", synth.dvae_state_dict(synth.DVAE_REAL, 1234)); syn.load("vocos.", synth.vocos_state_dict(synth.VOCOS_REAL, 1234))
     runs = {}
     for rows in (32, 16, 8):
-        g = GPT(bench.LLAMA, max_batch=rows, max_seq_len=48 + 96 + 512 + 32, weight_dtype="fp32", device=str(dev), options=dict(options))
+        g = GPT(bench.LLAMA, max_batch=rows, max_seq_len=48 + 96 + 512 + 32, weight_dtype=DTYPE, device=str(dev), options=dict(options))
         g.load_state_dict(synth.gpt_state_dict(synth.GPT_REAL, 1234))
         with tempfile.TemporaryDirectory() as td:
             pipe = ChatTTSPlusPipeline.from_components(g, syn, synth.toy_tokenizer(td), dev)
@@ -106,11 +117,40 @@ def request(mode, options):
     ref = runs[(32, "longest_first")][0]
     for (rows, order), (ids, wall) in runs.items():
         same = sum(bool(torch.equal(a, b)) for a, b in zip(ref, ids))
-        emit({"probe": "request", "mode": mode, "rows": rows, "order": order, "utterances": len(ids), "useful_tok_per_s": round(sum(limits) / wall, 1),
+        emit({"probe": "request", "dtype": DTYPE, "mode": mode, "rows": rows, "order": order, "utterances": len(ids), "useful_tok_per_s": round(sum(limits) / wall, 1),
               "wall_s": round(wall, 3), "identical_to_32_rows_longest_first": same})
 
 
+FP16_ROWS = (1, 2, 4, 5, 6, 8, 9, 16, 17, 32, 33, 56, 57, 64, 128)
+
+
+def main_fp16():
+    modes = (("default", {}), ("schedule_invariant", {"schedule_invariant": 1}))
+    engines = {}
+    for mode, options in modes:
+        engines[mode] = GPT(bench.LLAMA, max_batch=128, max_seq_len=1024, weight_dtype="fp16", device=str(dev), options=dict(options))
+        engines[mode].load_state_dict(synth.gpt_state_dict(synth.GPT_REAL, 1234))
+    got = {}
+    for rnd in range(3):
+        for mode, _ in modes:
+            step_times(engines[mode], mode, FP16_ROWS, got)
+            prompt_times(engines[mode], mode, got)
+    for g in engines.values():
+        g.close()
+    for (probe, mode, what), v in got.items():
+        v = sorted(v)
+        rec = {"probe": probe, "dtype": "fp16", "mode": mode}
+        rec.update({"rows": what, "mean_ctx": 48 + 261} if probe == "step" else {"B": what[0], "T": what[1]})
+        rec.update({("ms_per_step" if probe == "step" else "ms"): round(v[1], 4), "min": round(v[0], 4), "max": round(v[2], 4), "rounds": 3})
+        emit(rec)
+    if "--skip-request" not in sys.argv:
+        for mode, options in modes:
+            request(mode, options)
+
+
 def main():
+    if DTYPE == "fp16":
+        return main_fp16()
     for mode, options in (("default", {}), ("batch_invariant", {"batch_invariant": 1})):
         g = GPT(bench.LLAMA, max_batch=64, max_seq_len=1024, weight_dtype="fp32", device=str(dev), options=dict(options))
         g.load_state_dict(synth.gpt_state_dict(synth.GPT_REAL, 1234))
