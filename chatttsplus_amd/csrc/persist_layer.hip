@@ -14,7 +14,8 @@
 //   * the activations travel between workgroups as 8-byte {tag, value} granules (one sc1 store each, cdna_hip_programming.md Guideline 16 R2):
 //     the data is the flag, a consumer wave re-reads its granules until every tag equals (launch counter, layer) -- no fences, no counters,
 //     placement-independent.  Four "edge" waves per workgroup (two until round 5) do all gathering, epilogues and publishing, so the compute waves never poll
-//     (a poll's result would queue behind their in-flight weight loads: vmcnt retires in order);
+//     (a poll's result would queue behind their in-flight weight loads: vmcnt retires in order); a gather is handed to the compute waves through the hardware
+//     barrier, and at one row the edge waves reduce the rows' norm sums while the compute waves multiply ("phase trim" below);
 //   * five edges per layer: q|k|v -> attention, attention -> o_proj, (x + attention) -> gate|up, silu(gate) * up -> down, layer output -> next layer;
 //     the residual stream enters the launch and leaves it through plain global memory (the sampler wrote it, the heads read it: launch boundaries).
 // Every spin is bounded; a give-up sets a device error word that makes this and every later launch return at once (ctts_gpt_progress
@@ -244,6 +245,39 @@ template <int CTRL, int C> __device__ inline void pl_rs_step(float* v, bool f) {
         }
     } else v[0] += dpp_f<CTRL>(v[0]);
 }
+// ---- phase trim (SCHED 3): links of a phase's serial chain that the result needs but the path "gather complete -> granule published" does not.  Each has its own
+// switch for A/B builds (tools/build_variant.sh NAME -DPL_...=0); none changes an operand or the order of an addition.
+//   PL_EARLY_ARRIVE: an edge wave announces its gather (xs written) BEFORE it reduces the rows' sums of squares: the compute waves need xs, only the epilogue needs ssq
+//                    (R wave_sums of ~45 dependent instructions each leave the path in front of q|k|v, gate|up and the heads).
+//   PL_RS_EARLY:     the epilogue lanes compute the norm factor 1 / sqrtf(ssq / 768 + eps) while the compute waves multiply instead of behind B2: the edge waves count
+//                    their finished ssq rows in a second LDS counter (abort_s[2]) and the waves that own epilogue lanes wait for it (bounded, honours the give-up flag).
+//   PL_BAR_WAKE:     B1 ends in the hardware barrier for all waves of the workgroup (edge waves right behind their arrive, compute waves once their paced requests
+//                    are out) instead of a sleep-and-poll of the counter by every compute wave; the counter stays as the pacing loop's early exit.
+//   PL_A16_DPP:      the two neighbours a 16-byte act granule collects come through DPP row shifts (a decode row's 16 lanes are one DPP row) instead of ds_bpermute.
+// The LORA kernels keep the old order for the first two: their compute waves 6 / 7 read ssq in phase A (the normalised input of u = A h), i.e. ssq is on THEIR path.
+// The first two apply to the ONE-row kernels only (PL_TRIM_NORM_MAXR).  The rows' sums of squares are written `ssp += v * v`, which hipcc contracts to FMAs; in
+// `v0 * v0 + v1 * v1` either product may become the FMA's addend, and which one hipcc picks per row and gather changed as soon as the code around the gather moved:
+// with both items on, the 2-, 5-, 6- and 8-row kernels (fp32 and fp16) produced hiddens an ulp-level rounding away from the previous build's (token ids
+// unchanged; tests/test_gpu_persist_phase_trim.py), and six of them reserved a 36-byte private segment for a spill slot nothing uses.  The one-row kernels compile to
+// the same sums.  (Pinning the association with __fmul_rn / fmaf would end the dependence, but not on the bits every instantiation produces today.)
+#ifndef PL_EARLY_ARRIVE
+#define PL_EARLY_ARRIVE 1
+#endif
+#ifndef PL_RS_EARLY
+#define PL_RS_EARLY 0                        // OFF: measured beside PL_EARLY_ARRIVE it costs what that one gains (profiles/persist_phase_trim_marks.jsonl): wave 8 then
+#endif                                       //   reduces its sums, waits for the three other waves' and divides in a row -- longer than the one-row q|k|v products it hides behind
+#ifndef PL_TRIM_NORM_MAXR
+#define PL_TRIM_NORM_MAXR 1                  // rows up to which the first two apply (above: from 2 rows on they do not leave the outputs bit-identical)
+#endif
+#ifndef PL_BAR_WAKE
+#define PL_BAR_WAKE 1
+#endif
+#ifndef PL_A16_DPP
+#define PL_A16_DPP 1
+#endif
+#define PL_DPP_ROW_SHL(n_) (0x100 + (n_))    // lane i of a 16-lane row reads lane i + n; lanes past the row read 0 (bound_ctrl)
+__device__ inline float pl_row_shl1(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), PL_DPP_ROW_SHL(1), 0xF, 0xF, true)); }
+__device__ inline float pl_row_shl2(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), PL_DPP_ROW_SHL(2), 0xF, 0xF, true)); }
 #define PL_FRONT_BYTES 4096                 // 16 + (384 + 512 + 16 + 16) * 4 = 3728, rounded
 #ifndef PL_TAIL_ALL
 #define PL_TAIL_ALL 1
@@ -336,6 +370,9 @@ __device__ inline bool sweep_masked(const u64* base, unsigned lane_elem, bool va
 template <int R, int SCHED, typename WT, bool LORA = false>
 __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs a) {
     static_assert(!LORA || SCHED == 3, "per-utterance adapters: the paced schedule only");
+    constexpr bool EARLY = PL_EARLY_ARRIVE != 0 && SCHED == 3 && !LORA && R <= PL_TRIM_NORM_MAXR;      // (phase trim, above)
+    constexpr bool RSE = PL_RS_EARLY != 0 && SCHED == 3 && !LORA && R <= PL_TRIM_NORM_MAXR;
+    constexpr bool BARW = PL_BAR_WAKE != 0 && SCHED == 3;
     typedef typename PlW<WT>::frag wfrag;
     // Edge waves per workgroup: 2 at one row, 4 at 2..4 rows (round 5).  A gather is 768 R (3072 R for the act rows) granules over the edge lanes; with two waves the
     // per-lane share grew with the rows (6 R and 24 R loads per lane, the act rows one sweep after the other) -- +4.3 us of the +9.2 us per layer between 1 and 4 rows.
@@ -344,7 +381,7 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
     constexpr size_t BLOCK_BYTES = (size_t)PL_BLOCK_BYTES / 4 * sizeof(WT), LAYER_BYTES = PL_LAYER_BYTES / 4 * sizeof(WT);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // LDS: [front block: give-up flag + the attention workgroups' scratch][GEMV workgroups: xs | red | ssq | xres   /   attention workgroups of the 6..8-row kernels: the K / V tail]
-    int* const abort_s = (int*)smem;                      // [4]: [0] give-up flag, [1] SCHED 3: gathers completed by the edge waves (2 per phase)
+    int* const abort_s = (int*)smem;                      // [4]: [0] give-up flag, [1] SCHED 3: gathers completed by the edge waves (EW per phase), [2] PL_RS_EARLY: ssq rows complete (EW per norm)
     float* const att_s = (float*)(abort_s + 4);           // attention workgroups: q[2][64] | k_new[2][64] | v_new[2][64] | the waves' outputs [8][64], maxima [8], sums [8]
     float* const xs = (float*)(smem + PL_FRONT_BYTES);    // activations of the current phase [R][768] ([R][3072] for the down projection)
     float* const red = xs + R * PL_I;                     // compute waves' results [8 waves][16 values][4 rows of 16 lanes] (pl_reduce_store / pl_red)
@@ -361,7 +398,7 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
     unsigned long long t_mark[10];
 #define PL_MARK(i) do { if (a.ts != nullptr) t_mark[i] = wall_clock64(); } while (0)
     PL_MARK(0);
-    if (tid == 0) { abort_s[0] = 0; abort_s[1] = 0; }
+    if (tid == 0) { abort_s[0] = 0; abort_s[1] = 0; abort_s[2] = 0; }
 
     if (b < PL_GEMV_BLOCKS) {
         const char* wb = a.w + (size_t)b * BLOCK_BYTES;
@@ -429,7 +466,10 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                 const int pace = a.pace;                      // x 128 cycles between two requests of a wave
 #define PL_PACE_BEGIN() const int tgt_ = EW * (++phase); bool ready_ = __hip_atomic_load(arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= tgt_
 #define PL_PIECE(stmt_) do { stmt_; if (!ready_) { for (int z_ = 0; z_ < pace; ++z_) __builtin_amdgcn_s_sleep(2); ready_ = __hip_atomic_load(arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= tgt_; } } while (0)
-#define PL_PACE_END() do { while (!ready_) { __builtin_amdgcn_s_sleep(1); ready_ = __hip_atomic_load(arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= tgt_; } asm volatile("" ::: "memory"); } while (0)
+                // B1: (PL_BAR_WAKE) the hardware barrier of all waves -- the edge waves join it right behind their arrive, so a phase starts when the last edge wave is
+                // done, not when the last of eight pollers notices; only LDS is waited for (the weight requests stay in flight: no vmcnt)
+#define PL_PACE_END() do { if constexpr (BARW) { (void)ready_; asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); } \
+        else { while (!ready_) { __builtin_amdgcn_s_sleep(1); ready_ = __hip_atomic_load(arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= tgt_; } asm volatile("" ::: "memory"); } } while (0)
                 for (int l = 0; l < NL; ++l) {
                     const char* const wn = wb + LAYER_BYTES;
                     const bool more = l + 1 < NL;
@@ -727,8 +767,21 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
         } else {
             // ------------------------------------------------ edge wave: gathers, epilogues, publishing
 #define PL_B1() do { if (SCHED == 3) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-        if (lane == 0) __hip_atomic_fetch_add((__attribute__((address_space(3))) int*)(abort_s + 1), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); } \
+        if (lane == 0) __hip_atomic_fetch_add((__attribute__((address_space(3))) int*)(abort_s + 1), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
+        if constexpr (BARW) asm volatile("s_barrier" ::: "memory"); } \
         else __syncthreads(); } while (0)
+            // the norm sums of a gathered [R][768]: this wave's share of every row's sum of squares -> ssq[ew][r]; PL_RS_EARLY: counted, so that the epilogue lanes
+            // can form the norm factor before B2 (PL_SSQ_WAIT: bounded; a give-up elsewhere in the workgroup ends it)
+            typedef __attribute__((address_space(3))) int pl_lds_cnt;
+#define PL_SSQ_COUNT() do { if constexpr (RSE) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
+        if (lane == 0) __hip_atomic_fetch_add((pl_lds_cnt*)(abort_s + 2), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); } } while (0)
+#define PL_SSQ_STORE() do { _Pragma("unroll") for (int r = 0; r < R; ++r) { const float s_ = wave_sum(ssp[r]); if (lane == 0) ssq[ew * R + r] = s_; } PL_SSQ_COUNT(); } while (0)
+#define PL_SSQ_WAIT(code_, norms_) do { const int t2_ = EW * (norms_);      /* norms gathered so far: two per layer (x, x + attention) + the heads' */ \
+        for (unsigned sp_ = 0; __hip_atomic_load((pl_lds_cnt*)(abort_s + 2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < t2_; ++sp_) { \
+            if (sp_ >= PL_SPIN_LIMIT || PL_ABORT_GET(abort_s) != 0) { if (lane == 0) { atomicCAS(a.error, 0, code_); PL_ABORT_SET(abort_s); } break; } \
+            __builtin_amdgcn_s_sleep(1); } \
+        asm volatile("" ::: "memory"); } while (0)
+#define PL_RS(r_) (1.0f / sqrtf((EW == 2 ? ssq[r_] + ssq[R + (r_)] : (ssq[r_] + ssq[R + (r_)]) + (ssq[2 * R + (r_)] + ssq[3 * R + (r_)])) / (float)PL_H + a.eps))
 
             const int ew = wave - 8, e = ew * 64 + lane;      // 0..127
             const int hh = b >> 4, jj = b & 15;               // q | k | v rows of this workgroup: head hh, dims (2jj, 2jj+1, +32) / v dims 4jj..4jj+3
@@ -769,12 +822,15 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
 #pragma unroll
                 for (int r = 0; r < R; ++r) ssp[r] += (idx / 192 == r) ? d : 0.f;
             }
+            if constexpr (!EARLY) {
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const float s = wave_sum(ssp[r]);
-                if (lane == 0) ssq[ew * R + r] = s;
+                for (int r = 0; r < R; ++r) {
+                    const float s = wave_sum(ssp[r]);
+                    if (lane == 0) ssq[ew * R + r] = s;
+                }
             }
             __syncthreads();                                  // S0
+            if constexpr (!EARLY) PL_SSQ_COUNT();             // (counted behind S0: thread 0 zeroes the counter in front of it)
             PL_MARK(1);
             const size_t kv_per = a.kv_per;                   // floats between K and V of a layer (and half the distance between layers)
             for (int l = 0; l < NL; ++l) {
@@ -795,14 +851,25 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                         xs[(k / GX) * PL_H + NE * (k % GX) + e] = v[k];
                         ssp[k / GX] += v[k] * v[k];
                     }
-#pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        const float s = wave_sum(ssp[r]);
-                        if (lane == 0) ssq[ew * R + r] = s;
+                    if constexpr (EARLY) {
+                        if (last) PL_MARK(2);
+                        PL_B1();                              // B1(A): the gather is in LDS -- announced before the rows' wave sums, which run beside the compute waves' products
                     }
+                    PL_SSQ_STORE();
+                } else if constexpr (EARLY) {
+                    if (last) PL_MARK(2);
+                    PL_B1();                                  // B1(A) of the launch's first layer: xs came from global memory in front of S0; its norm sums follow here
+                    PL_SSQ_STORE();
                 }
-                if (last) PL_MARK(2);
-                PL_B1();                                      // B1(A): the gather is in LDS
+                if constexpr (!EARLY) {
+                    if (last) PL_MARK(2);
+                    PL_B1();                                  // B1(A): the gather is in LDS
+                }
+                float rsA = 0.f;                              // PL_RS_EARLY: the norm factor, formed while the compute waves multiply
+                if constexpr (RSE) if (ew * 64 < 6 * R) {
+                    PL_SSQ_WAIT(1, 2 * l + 1);
+                    if (doA) rsA = PL_RS(rA);
+                }
                 float lda = 0.f, ldb = 0.f;                   // LORA: this lane's two rows' scale * B (A h) (pipeline:420-432, per row)
                 float uq[LORA ? 16 : 1];
                 const int slA = (LORA && doA) ? pl_slot(a.lslots, rA) : -1;
@@ -820,7 +887,7 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                     }
                 }
                 if (doA) {
-                    const float rs = 1.0f / sqrtf((EW == 2 ? ssq[rA] + ssq[R + rA] : (ssq[rA] + ssq[R + rA]) + (ssq[2 * R + rA] + ssq[3 * R + rA])) / (float)PL_H + a.eps);          // llama.py:82-87 (the weight is folded into W's columns)
+                    const float rs = RSE ? rsA : PL_RS(rA);          // llama.py:82-87 (the weight is folded into W's columns)
                     const float va = pl_red(red, pwA, rA) * rs + lda, vb = pl_red(red, pwA, R + rA) * rs + ldb;
                     float ya = va, yb = vb;
                     int which, dA, dB;
@@ -891,32 +958,39 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                         xs[(k / GX) * PL_H + NE * (k % GX) + e] = v[k];
                         ssp[k / GX] += v[k] * v[k];
                     }
-#pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        const float s = wave_sum(ssp[r]);
-                        if (lane == 0) ssq[ew * R + r] = s;
+                    if constexpr (EARLY) {
+                        if (last) PL_MARK(6);
+                        PL_B1();                              // B1(D): the gather is in LDS -- announced before the rows' wave sums
                     }
+                    PL_SSQ_STORE();
                 }
-                if (last) PL_MARK(6);
-                PL_B1();                                      // B1(D): the gather is in LDS
+                if constexpr (!EARLY) {
+                    if (last) PL_MARK(6);
+                    PL_B1();                                  // B1(D): the gather is in LDS
+                }
+                float rsD = 0.f;
+                if constexpr (RSE) if (ew * 64 < 16 * R) {
+                    PL_SSQ_WAIT(4, 2 * l + 2);
+                    if (e < 16 * R) rsD = PL_RS(e >> 4);
+                }
                 __syncthreads();                              // B2(D)
                 if constexpr (A16) {
                     float av = 0.f;
                     const int pi = e & 15, r = e >> 4;
                     if (e < 16 * R) {
                         const int w = pi >> 1, p = pi & 1;
-                        const float rs = 1.0f / sqrtf((EW == 2 ? ssq[r] + ssq[R + r] : (ssq[r] + ssq[R + r]) + (ssq[2 * R + r] + ssq[3 * R + r])) / (float)PL_H + a.eps);
+                        const float rs = RSE ? rsD : PL_RS(r);
                         const float gv = pl_red(red, w, 16 * p + r) * rs, uv = pl_red(red, w, 16 * p + R + r) * rs;
                         av = (gv / (1.0f + expf(-gv))) * uv;                                                                    // llama.py:214
                     }
                     // the 16 lanes of a decode row: lane pi = 3 s collects (pi, pi + 1, pi + 2) and stores granule s
-                    const float a1 = __shfl_down(av, 1), a2 = __shfl_down(av, 2);
+                    const float a1 = PL_A16_DPP ? pl_row_shl1(av) : __shfl_down(av, 1), a2 = PL_A16_DPP ? pl_row_shl2(av) : __shfl_down(av, 2);
                     if (e < 16 * R && pi % 3 == 0)
                         store_granule16(a.g_act, PL_GEMV_BLOCKS * PL_A16_SLOTS * R, (unsigned)pl_opq<(R > PL_MAXR_ONE)>((r * PL_GEMV_BLOCKS + b) * PL_A16_SLOTS + pi / 3), tag,
                                         av, (pi + 1 < 16) ? a1 : 0.f, (pi + 2 < 16) ? a2 : 0.f);
                 } else if (e < 16 * R) {
                     const int pi = e & 15, r = e >> 4, w = pi >> 1, p = pi & 1;
-                    const float rs = 1.0f / sqrtf((EW == 2 ? ssq[r] + ssq[R + r] : (ssq[r] + ssq[R + r]) + (ssq[2 * R + r] + ssq[3 * R + r])) / (float)PL_H + a.eps);
+                    const float rs = RSE ? rsD : PL_RS(r);
                     const float gv = pl_red(red, w, 16 * p + r) * rs, uv = pl_red(red, w, 16 * p + R + r) * rs;
                     store_granule(a.g_act + (size_t)pl_opq<(R > PL_MAXR_ONE)>(r * PL_I + 16 * b + pi), tag, (gv / (1.0f + expf(-gv))) * uv);       // llama.py:214
                 }
@@ -1016,16 +1090,18 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                     xs[(k / GX) * PL_H + NE * (k % GX) + e] = v[k];
                     ssp[k / GX] += v[k] * v[k];
                 }
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const float s = wave_sum(ssp[r]);
-                    if (lane == 0) ssq[ew * R + r] = s;
+                if constexpr (EARLY) PL_B1();                 // B1(H): announced before the rows' wave sums
+                PL_SSQ_STORE();
+                if constexpr (!EARLY) PL_B1();                // B1(H)
+                float rsH = 0.f;
+                if constexpr (RSE) if (ew * 64 < PL_HEAD_ROWS * R) {
+                    PL_SSQ_WAIT(1, 2 * NL + 1);
+                    if (e < PL_HEAD_ROWS * R) rsH = PL_RS(e / PL_HEAD_ROWS);
                 }
-                PL_B1();                                      // B1(H)
                 __syncthreads();                              // B2(H)
                 if (e < PL_HEAD_ROWS * R) {
                     const int rr = e % PL_HEAD_ROWS, r = e / PL_HEAD_ROWS, col = PL_HEAD_ROWS * b + rr;
-                    const float rs = 1.0f / sqrtf((EW == 2 ? ssq[r] + ssq[R + r] : (ssq[r] + ssq[R + r]) + (ssq[2 * R + r] + ssq[3 * R + r])) / (float)PL_H + a.eps);          // llama.py:1002 (the weight is folded into the heads' columns)
+                    const float rs = RSE ? rsH : PL_RS(r);          // llama.py:1002 (the weight is folded into the heads' columns)
                     if (col < a.n_valid) a.logits[(size_t)r * a.n_valid + col] = pl_red(red, rr >> 1, (rr & 1) * R + r) * rs;
                 }
                 if (e < 4 * R) {
