@@ -136,6 +136,8 @@ SYMBOLS = [
     ("ctts_synth_batch", C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
     ("ctts_dvae_decode_codes", C.c_int, [_P, _P, C.c_int, _P, _P]),
     ("ctts_synth_batch_codes", C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
+    ("ctts_synth_window_range", C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    ("ctts_synth_windows", C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P]),
     ("ctts_enc_create", C.c_int, [C.POINTER(EncCfg), C.POINTER(_P)]),
     ("ctts_enc_destroy", None, [_P]),
     ("ctts_enc_set_weight", C.c_int, [_P, C.c_char_p, _P, C.c_size_t]),

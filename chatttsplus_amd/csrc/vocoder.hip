@@ -122,6 +122,31 @@ __global__ void overlap_add_kernel(const float* frames, const float* win, float*
     wavs[u][s] = acc / env;
 }
 
+// The same sum for samples [skip[u], skip[u] + count[u]) of utterance u only, stored back to back at out + out_off[u] (ctts_synth_windows): float32, or
+// int16 PCM when fmt == 1.  Term for term overlap_add_kernel's arithmetic, so the float result is the slice of its output bit for bit.
+__global__ void overlap_add_window_kernel(const float* frames, const float* win, void* out, const int* Fs, const int* skip, const int* count, const int* out_off,
+                                          long sf, int n_fft, int hop, int fmt) {
+    const int u = blockIdx.y, F = Fs[u];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count[u]) return;
+    const int s = skip[u] + i;
+    if (s < 0 || s >= hop * (F - 1)) return;                 // (the host refuses such a window; never store outside it)
+    frames += (size_t)u * sf;
+    const int t = s + n_fft / 2;
+    float acc = 0.f, env = 0.f;
+    const int f_hi = min(F - 1, t / hop);
+    for (int f = f_hi; f >= 0; --f) {
+        const int o = t - f * hop;
+        if (o >= n_fft) break;
+        acc += frames[(size_t)f * n_fft + o];
+        env += win[o] * win[o];
+    }
+    const float v = acc / env;
+    const size_t dst = (size_t)out_off[u] + (size_t)i;
+    if (fmt == 1) ((short*)out)[dst] = (short)rintf(fminf(fmaxf(v, -1.f), 1.f) * 32767.f);
+    else ((float*)out)[dst] = v;
+}
+
 // ------------------------------------------------------------------------------------------------
 struct SplitW { half_t *hi = nullptr, *lo = nullptr; };       // head / tail fp16 images of a GEMM weight (conv_gemm.h gemm_split_kernel)
 struct ConvNext { float *dw_w, *dw_b, *ln_w, *ln_b, *b1, *b2, *gamma; SplitW s1, s2; };      // s1 / s2: head / tail FRAGMENT images of pwconv1 / pwconv2 (cnx_gemm.h)
@@ -146,6 +171,7 @@ struct ctts_voc {
     int mel_ld, spec_ld, head_ld, mid_ld;
     // per-call tables: frames per utterance, hidden / wav / mel pointers (device copy + ring of pinned staging slots)
     void* d_tab = nullptr; void* pin = nullptr;
+    int *d_skip = nullptr, *d_count = nullptr, *d_ooff = nullptr;      // windows (ctts_synth_windows): first sample, samples, offset in the packed output
     int* d_F = nullptr; const float* const* d_hid = nullptr; float* const* d_wav = nullptr; float* const* d_mel = nullptr;      // (d_hid doubles as the table of code-id pointers in the codes mode)
     std::vector<int> frames_host;
     hipEvent_t pin_ev[8]; bool pin_used[8] = {false, false, false, false, false, false, false, false}; int pin_next = 0;
@@ -313,7 +339,7 @@ extern "C" int ctts_voc_finalize(ctts_voc* h) {
         if (valloc(h, &a, MB * Fp * YD / 2) || valloc(h, &b2, MB * Fp * YD / 2) || valloc(h, &c2, MB * Fp * h->mid_ld / 2) || valloc(h, &d2, MB * Fp * h->mid_ld / 2)) return 1;
         h->ln_hi = (half_t*)a; h->ln_lo = (half_t*)b2; h->mid_hi = (half_t*)c2; h->mid_lo = (half_t*)d2;
     }
-    const size_t tab_bytes = MB * 4 + MB * 24;
+    const size_t tab_bytes = MB * 4 + MB * 24 + MB * 12;      // frames, three pointers, three window integers per utterance
     CTTS_HIP_CHECK(hipMalloc(&h->d_tab, tab_bytes));
     CTTS_HIP_CHECK(hipHostMalloc(&h->pin, tab_bytes * 8));
     for (int i = 0; i < 8; ++i) CTTS_HIP_CHECK(hipEventCreateWithFlags(&h->pin_ev[i], hipEventDisableTiming));
@@ -321,6 +347,9 @@ extern "C" int ctts_voc_finalize(ctts_voc* h) {
     h->d_hid = (const float* const*)((char*)h->d_tab + MB * 4);
     h->d_wav = (float* const*)((char*)h->d_tab + MB * 4 + MB * 8);
     h->d_mel = (float* const*)((char*)h->d_tab + MB * 4 + MB * 16);
+    h->d_skip = (int*)((char*)h->d_tab + MB * 28);
+    h->d_count = h->d_skip + MB;
+    h->d_ooff = h->d_count + MB;
     h->frames_host.assign(MB, 0);
     h->host.clear();
     h->finalized = true;
@@ -344,9 +373,11 @@ static int run_convnext(ctts_voc* h, const ConvNext& cb, int nb, int Fmax, int d
 }
 
 // upload the per-call tables (frames, pointers): a ring of pinned staging slots guarded by events, no stream sync
-static int set_tables(ctts_voc* h, const float* const* hidden, const int* frames, float* const* wavs, float* const* mels, int nb, hipStream_t s) {
+// `win3` = {skip, count, out_off} HOST [nb] each: the window integers of ctts_synth_windows; calls without windows upload what they always did
+static int set_tables(ctts_voc* h, const float* const* hidden, const int* frames, float* const* wavs, float* const* mels, int nb, hipStream_t s,
+                      const int32_t* const* win3 = nullptr) {
     const size_t MB = h->cfg.max_batch;
-    const size_t tab_bytes = MB * 4 + MB * 24;
+    const size_t tab_bytes = MB * 4 + MB * 24 + MB * 12;
     const int slot = h->pin_next++ % 8;
     if (h->pin_used[slot]) CTTS_HIP_CHECK(hipEventSynchronize(h->pin_ev[slot]));
     char* p = (char*)h->pin + slot * tab_bytes;
@@ -354,7 +385,8 @@ static int set_tables(ctts_voc* h, const float* const* hidden, const int* frames
     if (hidden) memcpy(p + MB * 4, hidden, nb * sizeof(void*));
     if (wavs) memcpy(p + MB * 4 + MB * 8, wavs, nb * sizeof(void*));
     if (mels) memcpy(p + MB * 4 + MB * 16, mels, nb * sizeof(void*));
-    CTTS_HIP_CHECK(hipMemcpyAsync(h->d_tab, p, tab_bytes, hipMemcpyHostToDevice, s));
+    for (int k = 0; win3 && k < 3; ++k) memcpy(p + MB * 28 + (size_t)k * MB * 4, win3[k], nb * 4);
+    CTTS_HIP_CHECK(hipMemcpyAsync(h->d_tab, p, win3 ? tab_bytes : MB * 28, hipMemcpyHostToDevice, s));
     CTTS_HIP_CHECK(hipEventRecord(h->pin_ev[slot], s));
     h->pin_used[slot] = true;
     return 0;
@@ -406,7 +438,8 @@ static int run_dvae(ctts_voc* h, int nb, int Fmax, bool to_mcl, hipStream_t s) {
     return launch_gemm_f32(EP_SCALE_T, g4, nb, s, 127);                                        //   ... -> [100][F] API layout
 }
 
-static int run_vocos(ctts_voc* h, int nb, int Fmax, hipStream_t s) {
+// `win_out` != nullptr: the last kernel overlap-adds the windows of the tables into that packed buffer (count_max = the longest) instead of whole waveforms
+static int run_vocos(ctts_voc* h, int nb, int Fmax, hipStream_t s, void* win_out = nullptr, int count_max = 0, int fmt = 0) {
     const ctts_voc_cfg& c = h->cfg;
     const int VD = c.vocos_dim, LD = h->mel_ld, NB = c.n_fft / 2 + 1;
     const long Fp = h->Fp;
@@ -432,6 +465,12 @@ static int run_vocos(ctts_voc* h, int nb, int Fmax, hipStream_t s) {
     g3.A = h->spec; g3.lda = h->spec_ld; g3.sA = Fp * h->spec_ld; g3.W = h->basis; g3.ldw = h->spec_ld; g3.C = h->frames; g3.ldc = c.n_fft;
     g3.sC = Fp * c.n_fft; g3.M = Fmax; g3.Ms = h->d_F; g3.N = c.n_fft; g3.K = h->spec_ld; g3.Whi = h->s_basis.hi; g3.Wlo = h->s_basis.lo;
     if (launch_gemm_f32(EP_NONE, g3, nb, s, 127)) return 1;                                    // windowed irfft as GEMM
+    if (win_out) {
+        hipLaunchKernelGGL(overlap_add_window_kernel, dim3((count_max + 255) / 256, nb), dim3(256), 0, s, h->frames, h->win, win_out, h->d_F, h->d_skip, h->d_count,
+                           h->d_ooff, Fp * c.n_fft, c.n_fft, c.hop, fmt);
+        CTTS_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
     const int lenmax = c.hop * (Fmax - 1);
     hipLaunchKernelGGL(overlap_add_kernel, dim3((lenmax + 255) / 256, nb), dim3(256), 0, s, h->frames, h->win, h->d_wav, h->d_F, Fp * c.n_fft, c.n_fft, c.hop);
     CTTS_HIP_CHECK(hipGetLastError());
@@ -511,4 +550,57 @@ extern "C" int ctts_synth_batch(ctts_voc* h, const float* const* hidden_ptrs, co
     if (set_tables(h, hidden_ptrs, h->frames_host.data(), wav_ptrs, nullptr, B, s) || stage(h, true, B, Fmax, s)) return 1;
     if (run_dvae(h, B, Fmax, true, s)) return 1;
     return run_vocos(h, B, Fmax, s);
+}
+
+// ---- windows of the waveform (streaming) ----------------------------------------------------------------------------------------------
+static int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+
+extern "C" int ctts_synth_window_range(int n_tokens, int64_t s0, int64_t s1, int hop, int halo_frames, int clamp_tail, int64_t* out5) {
+    if (!out5 || hop < 1 || halo_frames < 0 || n_tokens < 0) { ctts_set_error("synth_window_range: bad argument"); return 1; }
+    const long halo = (long)halo_frames + 1, n = n_tokens;
+    const long total = n > 0 ? (long)hop * (2 * n - 1) : 0;
+    if (!clamp_tail) {
+        const long settled = n > 0 ? (long)hop * (2 * n - halo - 1 > 0 ? 2 * n - halo - 1 : 0) : 0;
+        if (s1 > settled) { ctts_set_error("synth_window_range: samples up to %lld of a %d-token prefix are not settled (%ld are)", (long long)s1, n_tokens, settled); return 1; }
+    }
+    long a0 = s0 < 0 ? 0 : (s0 > total ? total : (long)s0), a1 = s1 < 0 ? 0 : (s1 > total ? total : (long)s1);
+    for (int i = 0; i < 5; ++i) out5[i] = 0;
+    if (a1 <= a0) return 0;
+    long f0 = a0 / hop - halo; if (f0 < 0) f0 = 0;
+    long f1 = ceil_div(a1, hop) + 1 + halo; if (f1 > 2 * n) f1 = 2 * n;
+    long a = f0 / 2, b = (f1 + 1) / 2;
+    if (clamp_tail && 2 * n - 2 * b < 2 * halo) b = n;
+    out5[0] = a; out5[1] = b; out5[2] = 2 * a * hop; out5[3] = a0; out5[4] = a1;
+    return 0;
+}
+
+extern "C" int ctts_synth_windows(ctts_voc* h, const void* const* src_ptrs, const int32_t* n_tokens, const int32_t* skip, const int32_t* count, int B, void* out,
+                                  const int32_t* out_off, int fmt, int codes, void* stream) {
+    if (codes) { if (codes_ready(h, "synth_windows")) return 1; }
+    else if (!h || !h->finalized) { ctts_set_error("synth_windows: handle not finalized"); return 1; }
+    if (!src_ptrs || !n_tokens || !skip || !count || !out_off) { ctts_set_error("synth_windows: null argument"); return 1; }
+    if (B < 1 || B > h->cfg.max_batch) { ctts_set_error("synth_windows: B=%d exceeds max_batch=%d", B, h->cfg.max_batch); return 1; }
+    if (fmt != 0 && fmt != 1) { ctts_set_error("synth_windows: fmt=%d (0 = float32, 1 = int16 PCM)", fmt); return 1; }
+    CTTS_RANGE("ctts_synth_windows");
+    int Fmax = 0, count_max = 0;
+    for (int u = 0; u < B; ++u) {
+        const int F = 2 * n_tokens[u];
+        if (n_tokens[u] < 1 || F > h->cfg.max_frames) { ctts_set_error("synth_windows: utterance %d has %d frames (max_frames=%d)", u, F, h->cfg.max_frames); return 1; }
+        if (!src_ptrs[u]) { ctts_set_error("synth_windows: utterance %d has no input", u); return 1; }
+        const long len = (long)h->cfg.hop * (F - 1);
+        if (skip[u] < 0 || count[u] < 0 || out_off[u] < 0 || (long)skip[u] + count[u] > len) {
+            ctts_set_error("synth_windows: utterance %d: samples [%d, %d + %d) lie outside its %ld-sample waveform", u, skip[u], skip[u], count[u], len);
+            return 1;
+        }
+        h->frames_host[u] = F;
+        Fmax = F > Fmax ? F : Fmax;
+        count_max = count[u] > count_max ? count[u] : count_max;
+    }
+    if (count_max == 0) return 0;                            // nothing to store
+    if (!out) { ctts_set_error("synth_windows: null output"); return 1; }
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t* win3[3] = {skip, count, out_off};
+    if (set_tables(h, (const float* const*)src_ptrs, h->frames_host.data(), nullptr, nullptr, B, s, win3) || stage(h, true, B, Fmax, s, codes != 0)) return 1;
+    if (run_dvae(h, B, Fmax, true, s)) return 1;
+    return run_vocos(h, B, Fmax, s, out, count_max, fmt);
 }

@@ -417,10 +417,19 @@ class SessionBook:
     """Bookkeeping of a serving session (GPT.open_session), pure Python: tickets, the queue, which output slot an utterance writes to and when the slot is
     free again, the mirror of the decode rows' KV lanes, and the decision what to do with the batch next -- seat queued utterances in free rows, then in rows
     obtained by growing the batch up to `rows`, else (nothing queued) shrink it by the compact_size rule.  Row reports are interpreted by a RowBook, whose
-    "utterance" is the session ticket."""
+    "utterance" is the session ticket.
+
+    Streaming (submit(stream="exact" | "eager")): every row report carries the live rows' token counts, and from them the book derives the sample windows
+    that are due (take_windows): (ticket, slot, tokens seen, s0, s1, final).  The windows of a ticket are consecutive and disjoint; the final one comes with
+    the utterance's completion or cancel and carries everything not yet emitted (it may be empty).
+      exact   s1 = settled_samples(tokens seen): the samples no later token can change, so the concatenation IS the finished utterance's waveform; a window
+              is due once `stream_batch` tokens' worth (2 hop samples a token) of newly settled samples exist
+      eager   the rule of infer(stream=True, continuous=True): once `stream_batch` new tokens exist, the window runs to the end of the PREFIX waveform, at
+              most `stream_speed` samples -- the reference's semantics: a window's tail is computed against the zero padding behind the prefix"""
 
     def __init__(self, rows: int, out_slots: int, max_batch: int, max_seq: int, max_new_token: int, ensure_non_empty: bool = True, max_restarts: int = 64,
-                 compact: bool = True, max_new_text: Optional[int] = None):
+                 compact: bool = True, max_new_text: Optional[int] = None, stream_batch: int = 24, stream_speed: int = 12000, hop: int = 256,
+                 halo_frames: int = 105):
         if not (1 <= int(rows) <= int(max_batch)):
             raise ValueError(f"session: rows={rows} outside 1..max_batch={max_batch}")
         if int(out_slots) < 1:
@@ -440,14 +449,25 @@ class SessionBook:
         self._next = 0
         self._to_cancel: List[int] = []            # seated tickets whose cancel the device has not seen yet
         self._dropped: List[int] = []              # tickets cancelled while queued: delivered by the next step
+        if int(stream_batch) < 1 or int(stream_speed) < 1:
+            raise ValueError(f"session: stream_batch={stream_batch} / stream_speed={stream_speed} (at least 1)")
+        self.stream_batch, self.stream_speed, self.hop, self.halo_frames = int(stream_batch), int(stream_speed), int(hop), int(halo_frames)
+        self._windows: List[tuple] = []            # windows the reports made due since the last take_windows()
 
     # -- requests ---------------------------------------------------------------------------------
-    def submit(self, T: int, utt_id: int, limit: Optional[int] = None, mode: str = "code") -> int:
+    def submit(self, T: int, utt_id: int, limit: Optional[int] = None, mode: str = "code", stream: Optional[str] = None, stream_batch: Optional[int] = None) -> int:
         """`mode` "code" or "text": a text utterance takes a row, a KV lane and an output slot like a code utterance (one index space: a slot is held by one
-        utterance of either kind); only its token limit is the text rows' own"""
+        utterance of either kind); only its token limit is the text rows' own.  `stream` None, "exact" or "eager" (code utterances): sample windows become due
+        while it decodes; `stream_batch` defaults to the session's"""
         T = int(T)
         if mode not in ("code", "text"):
             raise ValueError(f"submit: mode={mode!r} (\"code\" or \"text\")")
+        if stream not in (None, "exact", "eager"):
+            raise ValueError(f"submit: stream={stream!r} (None, \"exact\" or \"eager\")")
+        if stream is not None and mode == "text":
+            raise ValueError("submit: stream= is for code utterances; a text row produces no audio")
+        if stream_batch is not None and (stream is None or int(stream_batch) < 1):
+            raise ValueError(f"submit: stream_batch={stream_batch} needs stream= and a value of at least 1")
         if mode == "text" and self.max_new_text is None:
             raise ValueError("submit: mode=\"text\" needs a session opened with text_rows=...")
         if T < 1 or T + self.max_new > self.max_seq:
@@ -456,7 +476,8 @@ class SessionBook:
         lim = cap if limit is None else min(max(int(limit), 1), cap)
         tk = self._next
         self._next += 1
-        self.utts[tk] = dict(utt_id=int(utt_id), T=T, limit=lim, attempt=0, slot=None, row_tk=None, cancelled=False, mode=mode)
+        self.utts[tk] = dict(utt_id=int(utt_id), T=T, limit=lim, attempt=0, slot=None, row_tk=None, cancelled=False, mode=mode, stream=stream,
+                             stream_batch=self.stream_batch if stream_batch is None else int(stream_batch), emitted=0, last_n=0)
         self.queue.append(tk)
         return tk
 
@@ -483,7 +504,39 @@ class SessionBook:
 
     def take_dropped(self) -> List[int]:
         out, self._dropped = self._dropped, []
+        for tk in out:                             # a streaming ticket cancelled while queued ends with an empty final window
+            if self.utts[tk].get("stream"):
+                self._windows.append((tk, None, 0, 0, 0, True))
         return out
+
+    def take_windows(self) -> List[tuple]:
+        """[(ticket, slot, tokens seen, s0, s1, final)] made due since the last call, in report order"""
+        out, self._windows = self._windows, []
+        return out
+
+    def _progress(self, tk: int, n: int) -> None:
+        """a live streaming utterance was reported with n tokens written: book the window that is due, if any"""
+        from .vocoder import settled_samples
+        u = self.utts[tk]
+        n, s0 = int(n), u["emitted"]
+        if u["stream"] == "exact":
+            s1 = settled_samples(n, self.hop, self.halo_frames)
+            if s1 - s0 < u["stream_batch"] * 2 * self.hop:
+                return
+        else:
+            total = self.hop * (2 * n - 1) if n > 0 else 0
+            if total <= s0 or n - u["last_n"] < u["stream_batch"]:
+                return
+            s1 = min(s0 + self.stream_speed, total)
+        self._windows.append((tk, u["slot"], n, s0, s1, False))
+        u["emitted"], u["last_n"] = s1, n
+
+    def _final(self, tk: int, n: int) -> None:
+        u = self.utts[tk]
+        if u.get("stream"):
+            total = self.hop * (2 * int(n) - 1) if n > 0 else 0
+            self._windows.append((tk, u["slot"], int(n), min(u["emitted"], total), total, True))
+            u["emitted"] = total
 
     def n_live(self) -> int:
         return len(self.book.tickets)
@@ -544,14 +597,19 @@ class SessionBook:
         whose first token was EOS go back to the head of the queue with their next attempt (a cancelled one ends instead).  The caller clones the results out
         of slot utts[ticket]["slot"] and then calls release(ticket)."""
         fin_of = {self.book.tickets[t][0]: int(fin) for t, (fin, end) in zip(layout, states) if t is not None and fin and t in self.book.tickets}
+        for t, (fin, end) in zip(layout, states):  # live rows of streaming utterances: the windows their token counts make due
+            if t is not None and not fin and t in self.book.tickets and self.utts[self.book.tickets[t][0]].get("stream"):
+                self._progress(self.book.tickets[t][0], end)
         done, again = self.book.report(layout, states, self.ensure_non_empty, self.max_restarts)
         out, back = [], []
         for tk, att in again:
             u = self.utts[tk]
             if u["cancelled"]:
+                self._final(tk, 0)
                 out.append((tk, 0, 1, True))
                 continue
             u["attempt"], u["row_tk"] = att, None
+            u["emitted"], u["last_n"] = 0, 0           # (its first token was EOS: nothing was emitted; the next attempt starts over)
             self.free_slots.append(u["slot"])
             self.free_slots.sort()
             u["slot"] = None
@@ -560,6 +618,7 @@ class SessionBook:
         for tk, n in done:
             u = self.utts[tk]
             fin = fin_of.get(tk, 1)
+            self._final(tk, n)
             out.append((tk, n, fin, bool(u["cancelled"] and not (fin & 2) and n < u["limit"])))
         return out
 
@@ -573,7 +632,7 @@ class SessionBook:
 
 # arguments of generate() / generate_many() / infer() that a session refuses by name (GPT.open_session, ChatTTSPlusPipeline.open_session)
 SESSION_OUT_OF_SCOPE = {"prompt_of": "shared prompt passes", "share_prompt": "shared prompt passes", "num_candidates": "num_candidates / shared prompt passes",
-                        "noise": "caller-supplied noise", "stream": "per-utterance streaming windows", "stream_batch": "per-utterance streaming windows",
+                        "noise": "caller-supplied noise", "stream": "session-wide streaming windows", "stream_batch": "session-wide streaming windows",
                         "sharded": "infer_sharded", "infer_text": "the refine-text pass inside a code session",
                         "refine_text_only": "the refine-text pass inside a code session", "params_refine_text": "the refine-text pass inside a code session"}
 
@@ -587,7 +646,8 @@ def refuse_out_of_scope(kw: dict, instead: str) -> None:
         off = value is None or value is False or (name == "noise" and isinstance(value, str) and value == "device") or \
             (name == "num_candidates" and isinstance(value, int) and value == 1)
         if not off:
-            raise _lib.HipBackendError(f"open_session: {SESSION_OUT_OF_SCOPE[name]} ({name}=) is not offered inside a session; {instead}")
+            per_utt = "; streaming is asked per utterance at submit(stream=\"exact\" | \"eager\")" if name in ("stream", "stream_batch") else ""
+            raise _lib.HipBackendError(f"open_session: {SESSION_OUT_OF_SCOPE[name]} ({name}=) is not offered inside a session; {instead}{per_utt}")
 
 
 TEXT_ROWS_KEYS = ("temperature", "top_P", "top_K", "eos_token", "max_new_token", "min_new_token")
@@ -627,6 +687,24 @@ class SessionResult:
     mode: str = "code"            # "text": a refine-text utterance -- ids is [n] (as generate(infer_text=True) returns them), no hiddens, no log-probs
 
 
+@dataclass(repr=False, eq=False)
+class SessionWindow:
+    """One sample window of a streaming utterance that a DecodeSession.step made due (take_windows): samples [s0, s1) of the waveform, to be vocoded from tokens
+    tok0 .. tok0 + len(ids) -- the receptive field of the window and no more.  `hiddens` / `ids` are VIEWS of the session's output slot while the utterance is
+    live (it holds the slot, and rows below n_tokens are written once; use them on the session's stream, behind the decode launches, before the next step) and
+    the delivered result's clones for the final window."""
+    ticket: int
+    n_tokens: int                 # tokens the row report showed (eager: the prefix whose waveform the window is a slice of)
+    s0: int
+    s1: int
+    final: bool
+    tok0: int
+    ids: torch.Tensor             # int32 [k, 4]
+    hiddens: Optional[torch.Tensor] = None
+    cancelled: bool = False       # (final windows) the utterance was cancelled
+    mode: str = "exact"
+
+
 class DecodeSession:
     """A generate state kept open (GPT.open_session): utterances are submitted and cancelled while others decode.  The decode batch is as wide as the utterances
     in flight need -- it grows (ctts_gpt_grow + ctts_gpt_admit) when texts arrive and shrinks (ctts_gpt_compact) when they end -- instead of being opened at its
@@ -660,6 +738,8 @@ class DecodeSession:
         self._layouts = [None, None]
         self._pending: List[int] = []
         self._adapters = False                     # an utterance of this session named an adapter slot: every admission names its rows' slots from then on
+        self._stream_mode = {}                     # streaming ticket -> "exact" / "eager"
+        self._wins: List[SessionWindow] = []       # windows the last step made due
         self._open = True
 
     def __enter__(self):
@@ -675,8 +755,10 @@ class DecodeSession:
 
     # -- requests ---------------------------------------------------------------------------------
     def submit(self, emb: torch.Tensor, mask: torch.Tensor, utt_id: int, limit: Optional[int] = None, sampling=None, adapter_slot: Optional[int] = None,
-               mode: str = "code") -> int:
-        """Queues one utterance: emb [T, H] (GPT.__call__), mask [T] left padded.  `limit` <= max_new_token, `sampling` a dict as in sampling_per_row,
+               mode: str = "code", stream: Optional[str] = None, stream_batch: Optional[int] = None, stream_hidden: bool = True) -> int:
+        """`stream` "exact" / "eager" (SessionBook): sample windows of this utterance become due while it decodes, see take_windows(); `stream_batch` tokens between
+        windows (default: the session's); `stream_hidden` = the windows are vocoded from hidden rows (needs return_hidden), False = from the ids.
+        Queues one utterance: emb [T, H] (GPT.__call__), mask [T] left padded.  `limit` <= max_new_token, `sampling` a dict as in sampling_per_row,
         `adapter_slot` a resident adapter (load_adapter).  `mode` "text" (sessions opened with text_rows=): a refine-text utterance -- its prompt is the refine
         prompt, it samples under the text head with the session's text parameters (no per-utterance `sampling`), and its result's ids are [n].  Returns its ticket."""
         self._check_open()
@@ -687,6 +769,10 @@ class DecodeSession:
             raise _lib.HipBackendError("submit: mode=\"text\" needs a session opened with text_rows=... (GPT.open_session)")
         if mode == "text" and sampling is not None:
             raise _lib.HipBackendError("submit: per-utterance sampling parameters are for code utterances; a text utterance keeps the session's text_rows values")
+        if stream is not None and mode == "text":
+            raise _lib.HipBackendError("submit: stream= is for code utterances; a text row produces no audio")
+        if stream is not None and stream_hidden and self.hid is None:
+            raise _lib.HipBackendError("submit: stream= vocodes hidden rows: open the session with return_hidden=True (or pass stream_hidden=False to stream from the ids)")
         emb = torch.as_tensor(emb)
         mask = torch.as_tensor(mask).flatten()
         if emb.dim() != 2 or emb.shape[1] != g.model_dim or mask.numel() != emb.shape[0]:
@@ -700,11 +786,13 @@ class DecodeSession:
         if slot >= 0 and g.invariant_option():
             raise _lib.HipBackendError(f"submit: per-utterance adapters are outside the {g.invariant_option()} contract; merge the adapter (with_lora) or set the option to 0")
         try:
-            tk = self.book.submit(n, utt_id, limit, mode)
+            tk = self.book.submit(n, utt_id, limit, mode, stream=stream, stream_batch=stream_batch)
         except ValueError as e:
             raise _lib.HipBackendError(str(e)) from None
         self._req[tk] = (emb[emb.shape[0] - n:].to(g.device, dtype=torch.float32).contiguous(), knobs, slot, 1 if mode == "text" else 0)
         self._adapters = self._adapters or slot >= 0
+        if stream is not None:
+            self._stream_mode[tk] = stream
         return tk
 
     def cancel(self, ticket: int) -> bool:
@@ -813,8 +901,36 @@ class DecodeSession:
         return res
 
     # -- the loop ---------------------------------------------------------------------------------------
+    def _build_windows(self, due, results) -> List[SessionWindow]:
+        from .vocoder import window_token_range
+        book, by_tk, out = self.book, {r.ticket: r for r in results}, []
+        dev = self.gpt.device
+        for tk, slot, n, s0, s1, final in due:
+            mode = self._stream_mode.get(tk, "exact")
+            if final:
+                # the finished (or cancelled) utterance IS the prefix: settled to its end; built from the delivered clones, the slot is already released
+                self._stream_mode.pop(tk, None)
+                r = by_tk[tk]
+                a, b, _, s0, s1 = window_token_range(n, s0, s1, book.hop, book.halo_frames)
+                out.append(SessionWindow(tk, n, s0, s1, True, a, r.ids[a:b].to(torch.int32), r.hiddens[a:b] if r.hiddens is not None else None, bool(r.cancelled), mode))
+                continue
+            a, b, _, s0, s1 = window_token_range(n, s0, s1, book.hop, book.halo_frames, clamp_tail=(mode != "exact"))
+            out.append(SessionWindow(tk, n, s0, s1, False, a, self.ids[slot, a:b], self.hid[slot, a:b] if self.hid is not None else None, False, mode))
+        return out
+
+    def take_windows(self) -> List[SessionWindow]:
+        """The SessionWindows the last step() made due, in report order (a ticket's final window comes with its SessionResult)."""
+        out, self._wins = self._wins, []
+        return out
+
     @torch.no_grad()
     def step(self) -> List[SessionResult]:
+        """One _step(); the sample windows it made due for streaming utterances wait in take_windows() (replaced by the next step)."""
+        out = self._step()
+        self._wins = self._build_windows(self.book.take_windows(), out)
+        return out
+
+    def _step(self) -> List[SessionResult]:
         """One chunk of decode steps is launched, the previous chunk's row report is read (two chunks stay enqueued, as in generate_many): finished utterances
         are delivered, first-token-EOS ones queued again with their next attempt, and the batch is rebalanced -- queued utterances into free rows, then into
         rows the batch grows by, else a compaction.  With nothing live and nothing queued nothing is launched."""
@@ -1695,7 +1811,8 @@ class GPT:
         sampling arguments are the call's values, as in generate_many; an utterance may bring its own (submit(sampling=...)).  `rows` <= max_batch bounds the
         decode batch (default max_batch), `out_slots` the utterances whose results are held at once (default 2 * rows; slots are recycled once a result has been
         cloned out).  Holds the engine until close(): generate* and score raise meanwhile.  Not offered inside a session, each refused with a message:
-        shared prompt passes / num_candidates, caller-supplied noise, per-utterance streaming windows, infer_sharded, and the call-level names of the refine-text
+        shared prompt passes / num_candidates, caller-supplied noise, session-wide streaming windows (stream= / stream_batch= here: streaming is asked per utterance at
+        submit(stream=...), see take_windows), infer_sharded, and the call-level names of the refine-text
         pass (infer_text, refine_text_only, params_refine_text).  The refine-text pass itself is served INSIDE the session: `text_rows` = a dict (or an object with
         these attributes) of temperature, top_P, top_K, eos_token ([Ebreak]), max_new_token (<= the code rows'), min_new_token makes submit(mode="text") seat
         refine-text utterances as text rows beside the code rows of the one decode batch (ctts_gpt_enable_text_rows); their results carry ids [n]."""

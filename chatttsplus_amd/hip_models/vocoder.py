@@ -147,35 +147,92 @@ class Synth:
     # overlapping ISTFT frames (+-3).  LayerNorms are per frame.
     HALO_FRAMES = 75 + 27 + 3
 
+    def synth_windows(self, srcs, skips, counts, pcm16: bool = False):
+        """Samples [skips[u], skips[u] + counts[u]) of the waveform `decode_batch` would return for srcs[u] (hidden rows, or code ids for the
+        decode-codes model), for every u in ONE packed device buffer (ctts_synth_windows: the last kernel overlap-adds the window only).  Returns views of
+        that buffer, float32 or -- `pcm16` -- int16 PCM (rintf(clamp(x, -1, 1) * 32767)).  A count of 0 yields an empty view."""
+        if not self._finalized:
+            raise _lib.HipBackendError("DVAE / Vocos weights not loaded")
+        codes = self.vq is not None
+        counts = [max(0, int(c)) for c in counts]
+        offs = [0]
+        for c in counts:
+            offs.append(offs[-1] + c)
+        out = torch.empty(offs[-1], dtype=torch.int16 if pcm16 else torch.float32, device=self.device)
+        todo = [u for u, c in enumerate(counts) if c > 0]
+        with torch.cuda.device(self.device):
+            for c0 in range(0, len(todo), self.max_batch):
+                idx = todo[c0:c0 + self.max_batch]
+                hs = [srcs[u].to(self.device, dtype=torch.int32 if codes else torch.float32).contiguous() for u in idx]
+                k = len(idx)
+                hp = (C.c_void_p * k)(*[h.data_ptr() for h in hs])
+                nt = (C.c_int32 * k)(*[int(h.shape[0]) for h in hs])
+                sk = (C.c_int32 * k)(*[int(skips[u]) for u in idx])
+                ct = (C.c_int32 * k)(*[counts[u] for u in idx])
+                oo = (C.c_int32 * k)(*[offs[u] for u in idx])
+                _lib.check(self._lib.ctts_synth_windows(self._h, hp, nt, sk, ct, k, out.data_ptr(), oo, 1 if pcm16 else 0, 1 if codes else 0, self._stream()),
+                           "synth_windows")
+        return [out[offs[u]:offs[u + 1]] for u in range(len(counts))]
+
     def decode_window(self, hiddens, starts, stops):
         """Samples [starts[u], stops[u]) of the waveform `decode_batch` would return for hiddens[u] (the prefix generated so
         far), computed from the tokens inside the receptive field of that window only.  Bit-identical to slicing the
         full-prefix waveform: every output element runs the same K-order arithmetic whatever rows surround it.  The
-        reference's stream branch re-vocodes the whole prefix for every chunk it yields (pipeline:436-461)."""
-        subs, offs, meta = [], [], []
+        reference's stream branch re-vocodes the whole prefix for every chunk it yields (pipeline:436-461).  One output
+        allocation for the call; views of it are returned (synth_windows)."""
+        subs, skips, counts = [], [], []
         for h, s0, s1 in zip(hiddens, starts, stops):
             a, b, off, s0, s1 = window_token_range(int(h.shape[0]), s0, s1, self.cfg.hop, self.HALO_FRAMES)
-            subs.append(h[a:b]); offs.append(off); meta.append((s0, s1))
-        wavs = self.decode_batch(subs)
-        return [w[s0 - o:s1 - o] if s1 > s0 else w[:0] for w, o, (s0, s1) in zip(wavs, offs, meta)]
+            subs.append(h[a:b]); skips.append(s0 - off); counts.append(s1 - s0)
+        return self.synth_windows(subs, skips, counts)
+
+    def decode_settled(self, srcs, tok0s, starts, stops, pcm16: bool = False):
+        """Settled windows (settled_samples): srcs[u] holds tokens tok0s[u] .. of an utterance -- the range settled_token_range names for samples
+        [starts[u], stops[u]) -- and the samples come out as the finished utterance will have them, whatever tokens follow."""
+        hop = self.cfg.hop
+        return self.synth_windows(srcs, [int(s0) - 2 * int(a) * hop for s0, a in zip(starts, tok0s)], [int(s1) - int(s0) for s0, s1 in zip(starts, stops)], pcm16)
 
 
-def window_token_range(n_tokens: int, s0: int, s1: int, hop: int = 256, halo_frames: int = 105):
+def settled_samples(n_tokens: int, hop: int = 256, halo_frames: int = Synth.HALO_FRAMES, finished: bool = False) -> int:
+    """Leading samples of the n_tokens-long prefix waveform that no later token can change.  The dependency model is window_token_range's: a
+    window ending at sample s1 needs mel frames below ceil(s1 / hop) + 1 + (halo_frames + 1); while all of them exist among the 2 n_tokens frames of
+    the prefix -- ceil(s1 / hop) + 1 + (halo_frames + 1) <= 2 n_tokens -- the zero padding behind the prefix is outside the window's receptive field,
+    and so is whatever replaces it.  The largest such s1 is a multiple of hop: hop * (2 n_tokens - halo_frames - 2).  A finished utterance has no
+    later token: it is settled to its end."""
+    n = int(n_tokens)
+    if n <= 0:
+        return 0
+    if finished:
+        return hop * (2 * n - 1)
+    return hop * max(0, 2 * n - (halo_frames + 1) - 1)
+
+
+def window_token_range(n_tokens: int, s0: int, s1: int, hop: int = 256, halo_frames: int = 105, clamp_tail: bool = True):
     """Tokens [a, b) whose vocoding contains samples [s0, s1) of the n_tokens-long prefix waveform exactly, the sample offset of
     that sub-waveform, and the clamped window.  A sample s depends on ISTFT frames s/hop - 1 .. s/hop + 2, each of which depends
     on `halo_frames - 3` mel frames either side (conv receptive fields); a token is two frames.  A right edge that would fall
-    inside the halo of the true end is moved to the true end (the zero padding there is part of the reference's result)."""
+    inside the halo of the true end is moved to the true end (the zero padding there is part of the reference's result).
+    `clamp_tail=False` is the rule for SETTLED windows (s1 <= settled_samples(n_tokens), else ValueError): the right edge stays the
+    unclamped ceil(f1 / 2) -- the tokens the window can depend on and no more -- so the range is the same for every longer prefix."""
     halo = halo_frames + 1
     total = hop * (2 * n_tokens - 1) if n_tokens > 0 else 0
+    if not clamp_tail and int(s1) > settled_samples(n_tokens, hop, halo_frames):
+        raise ValueError(f"window_token_range: samples up to {int(s1)} of a {n_tokens}-token prefix are not settled "
+                         f"(settled_samples = {settled_samples(n_tokens, hop, halo_frames)})")
     s0, s1 = max(0, min(int(s0), total)), max(0, min(int(s1), total))
     if s1 <= s0:
         return 0, 0, 0, 0, 0
     f0 = max(0, s0 // hop - halo)
     f1 = min(2 * n_tokens, (s1 + hop - 1) // hop + 1 + halo)
     a, b = f0 // 2, (f1 + 1) // 2
-    if 2 * n_tokens - 2 * b < 2 * halo:
+    if clamp_tail and 2 * n_tokens - 2 * b < 2 * halo:
         b = n_tokens
     return a, b, 2 * a * hop, s0, s1
+
+
+def settled_token_range(n_tokens: int, s0: int, s1: int, hop: int = 256, halo_frames: int = 105):
+    """window_token_range for a settled window: independent of n_tokens (which only has to be large enough to settle s1)."""
+    return window_token_range(n_tokens, s0, s1, hop, halo_frames, clamp_tail=False)
 
 
 class DVAE:

@@ -214,12 +214,29 @@ class SessionDetails:
     refined_text: Optional[str] = None         # sessions opened with refine=: the text the refine stage produced (what the code stage spoke); None otherwise
 
 
+@dataclass(repr=False, eq=False)
+class SessionChunk:
+    """What SynthSession.poll returns for a streaming ticket (submit(stream=...)), zero or more times, the last one with final=True: samples
+    [start, start + len(wav)) of the utterance's waveform -- float32, or int16 PCM under pcm16=True.  The chunks of a ticket are consecutive.  `details`: only on
+    the final chunk of a return_details session (its `wav` is this final chunk's, not the whole utterance's)."""
+    wav: torch.Tensor
+    start: int
+    final: bool = False
+    details: Optional[SessionDetails] = None
+    n_tokens: int = 0             # tokens the utterance had when the chunk was cut ("eager": the chunk is a slice of THAT prefix's waveform)
+
+
 class SynthSession:
     """A serving session of the pipeline (ChatTTSPlusPipeline.open_session): texts are submitted and cancelled while others are being spoken.  A
     GPT.DecodeSession (elastic decode batch, ctts_gpt_grow / ctts_gpt_cancel) under the prompt building of infer() and the batched vocoder.  Opened with
     `refine` (a RefineTextParams) a text is refined first, INSIDE the session: its refine prompt is seated as a text row beside the code rows of the one decode
     batch (DecodeSession.submit(mode="text")); when the row delivers, its ids are filtered and decoded as infer() does and the code utterance is submitted --
-    both stages under the ticket submit() returned and under one utterance id (noise stream 4 for the text row, 0-3 for the code row)."""
+    both stages under the ticket submit() returned and under one utterance id (noise stream 4 for the text row, 0-3 for the code row).
+    submit(stream="exact" | "eager") streams an utterance's audio while it decodes: poll() vocodes the sample windows the step made due (SessionBook) in one
+    ctts_synth_windows call and returns them as SessionChunks.  "exact" emits only samples no later token can change (vocoder.settled_samples: it holds back the
+    last 53 tokens' worth until the utterance ends), so the chunks concatenate to the waveform a non-streaming poll returns, bit for bit; "eager" keeps
+    infer(stream=True)'s and the reference's semantics -- each chunk is a slice of the PREFIX waveform, whose last 1.1 s is computed against zero padding, so the
+    concatenation is not the offline waveform and chunk boundaries carry seams."""
 
     def __init__(self, pipe, gpt, params: InferCodeParams, use_decoder: bool, rows, seed, return_details: bool, refine: Optional[RefineTextParams] = None):
         self.pipe, self.gpt, self.params, self.use_decoder, self.return_details = pipe, gpt, params, bool(use_decoder), bool(return_details)
@@ -236,6 +253,8 @@ class SynthSession:
         self.session = gpt.open_session(torch.tensor(temperature), num_code, params.max_new_token, min_new_token=params.min_new_token, logits_warpers=warpers,
                                         logits_processors=processors, return_hidden=self.use_decoder, return_logprobs=self.return_details, seed=seed, rows=rows,
                                         ensure_non_empty=params.ensure_non_empty, text_rows=text_rows)
+        self.session.book.stream_batch, self.session.book.stream_speed = max(1, int(params.stream_batch)), max(1, int(params.stream_speed))
+        self._streams = {}                         # code-stage ticket of a streaming utterance -> pcm16
         self._paths = []                           # adapters utterances of this session named: all stay resident (at most _lib.MAX_ADAPTERS)
         self._auto_id = 0
         self._refining = {}                        # public ticket (= the refine stage's) -> what the code stage needs: dict(diff, slot, utt_id)
@@ -256,12 +275,21 @@ class SynthSession:
         return self.session.batch_trace
 
     def submit(self, text: str, params=None, lora_path: Optional[str] = None, utt_id: Optional[int] = None, max_new_token: Optional[int] = None,
-               refine: Optional[bool] = None) -> int:
-        """Queues one text.  `params`: this utterance's overrides (an InferCodeParams or a dict, checked by per_utterance_overrides: sampling knobs,
+               refine: Optional[bool] = None, stream: Optional[str] = None, stream_batch: Optional[int] = None, pcm16: bool = False) -> int:
+        """`stream` "exact" or "eager": poll() returns this ticket's audio as SessionChunks while it decodes (class docstring; "exact" is the one to use unless the
+        reference's windows are wanted); `stream_batch`: tokens between chunks (default: the session's params.stream_batch); `pcm16`: its chunks are int16 PCM.
+        Queues one text.  `params`: this utterance's overrides (an InferCodeParams or a dict, checked by per_utterance_overrides: sampling knobs,
         max_new_token, prompt, spk_emb); `lora_path`: its own adapter; `utt_id`: its noise key (default: a counter).  `refine`: refine the text first (default:
         iff the session was opened with refine=); False = the text is already refined.  Returns its ticket."""
         if not isinstance(text, str):
             raise _lib.HipBackendError("SynthSession.submit takes one text (a str) per call")
+        if stream not in (None, "exact", "eager"):
+            raise _lib.HipBackendError(f"submit: stream={stream!r} (None, \"exact\" or \"eager\")")
+        if stream is None and (stream_batch is not None or pcm16):
+            raise _lib.HipBackendError("submit: stream_batch= and pcm16= belong to a streaming utterance (stream=\"exact\" | \"eager\")")
+        if stream_batch is not None and int(stream_batch) < 1:
+            raise _lib.HipBackendError(f"submit: stream_batch={stream_batch} (at least 1)")
+        streaming = None if stream is None else (stream, None if stream_batch is None else int(stream_batch), bool(pcm16))
         refine = (self.refine is not None) if refine is None else bool(refine)
         if refine and self.refine is None:
             raise _lib.HipBackendError("submit: refine=True needs a session opened with refine=RefineTextParams(...)")
@@ -289,11 +317,11 @@ class SynthSession:
             input_ids, attention_mask, text_mask = pipe._refine_prompt([t], self.refine)
             emb = gpt(input_ids, text_mask)
             tk = self.session.submit(emb[0], attention_mask[0], int(utt_id), mode="text")
-            self._refining[tk] = dict(diff=diff, slot=slot, utt_id=int(utt_id))
+            self._refining[tk] = dict(diff=diff, slot=slot, utt_id=int(utt_id), streaming=streaming)      # (the refine stage streams nothing)
             return tk
-        return self._submit_code(t, diff, slot, int(utt_id))
+        return self._submit_code(t, diff, slot, int(utt_id), streaming)
 
-    def _submit_code(self, t: str, diff: dict, slot, utt_id: int) -> int:
+    def _submit_code(self, t: str, diff: dict, slot, utt_id: int, streaming=None) -> int:
         """the code utterance of one (refined) text: infer()'s prompt building, then DecodeSession.submit"""
         pipe, gpt, base = self.pipe, self.gpt, self.params
         t = t if t.strip().endswith("[uv_break]") else t + " [uv_break]"      # pipeline:414-416
@@ -301,7 +329,12 @@ class SynthSession:
         input_ids, attention_mask, text_mask = pipe._code_prompt([t], pic, gpt, [diff["prompt"] or ""] if "prompt" in diff else None)
         emb = gpt(input_ids, text_mask, spk_emb=pic.spk_emb, spk_emb_ids=pipe.models_dict["tokenizer"].spk_emb_ids)
         sampling = {k: diff[k] for k in PER_UTTERANCE_SAMPLING if k in diff} or None
-        return self.session.submit(emb[0], attention_mask[0], utt_id, limit=diff.get("max_new_token"), sampling=sampling, adapter_slot=slot)
+        if streaming is None:
+            return self.session.submit(emb[0], attention_mask[0], utt_id, limit=diff.get("max_new_token"), sampling=sampling, adapter_slot=slot)
+        tk = self.session.submit(emb[0], attention_mask[0], utt_id, limit=diff.get("max_new_token"), sampling=sampling, adapter_slot=slot, stream=streaming[0],
+                                 stream_batch=streaming[1], stream_hidden=self.use_decoder)
+        self._streams[tk] = streaming[2]
+        return tk
 
     def cancel(self, ticket: int) -> bool:
         """Works in either stage of a refined utterance: during the refine stage the text row is cancelled and the utterance is delivered with an empty waveform
@@ -324,9 +357,28 @@ class SynthSession:
         return SessionDetails(wav=w, ids=torch.empty(0, self.gpt.num_vq, dtype=torch.long, device=self.pipe.device), logprobs=e, sampled_logprobs=e.clone(),
                               mean_logprob=mean_logprob(e), finished_by_eos=False, refined_text=refined_text)
 
-    def _deliver(self, results):
+    def _vocode_windows(self, wins):
+        """every due window of the step through ctts_synth_windows: one call (one per sample format when float and int16 tickets are mixed); window -> wav"""
+        syn = self.pipe.synth if self.use_decoder else self.pipe._codes_synth()
+        hop, wav_of = syn.cfg.hop, {}
+        for pcm in (False, True):
+            sel = [w for w in wins if self._streams.get(w.ticket, False) == pcm]
+            if not sel:
+                continue
+            wavs = syn.synth_windows([(w.hiddens if self.use_decoder else w.ids) for w in sel], [w.s0 - 2 * w.tok0 * hop for w in sel], [w.s1 - w.s0 for w in sel], pcm)
+            wav_of.update({id(w): v for w, v in zip(sel, wavs)})
+        return wav_of
+
+    def _deliver(self, results, wins=()):
         tok = self.pipe.models_dict["tokenizer"]
         out, code = [], []
+        wav_of_win = self._vocode_windows(wins) if wins else {}
+        final_of = {}
+        for w in wins:
+            if w.final:
+                final_of[w.ticket] = w
+            else:
+                out.append((self._public.get(w.ticket, w.ticket), SessionChunk(wav=wav_of_win[id(w)], start=w.s0, final=False, n_tokens=w.n_tokens), False))
         for r in results:
             if getattr(r, "mode", "code") != "text":
                 code.append(r)
@@ -334,19 +386,20 @@ class SynthSession:
             # a refine stage ended: cancelled -> the utterance ends here; else filter and decode its ids exactly as infer() does and start the code stage
             info = self._refining.pop(r.ticket)
             if r.cancelled or info.get("cancelled"):
-                out.append((r.ticket, self._empty(True), True))
+                e = self._empty(True)
+                out.append((r.ticket, self._end_chunk(e, info.get("streaming")), True))
                 continue
             text = tok.decode([r.ids[r.ids.less(tok.break_0_ids)]])[0]
             try:
-                tk2 = self._submit_code(text, info["diff"], info["slot"], info["utt_id"])
+                tk2 = self._submit_code(text, info["diff"], info["slot"], info["utt_id"], info.get("streaming"))
             except _lib.HipBackendError as e:
                 # the code stage was refused (a refined text whose prompt no longer fits max_seq_len, ...): this utterance ends here, delivered like a cancelled
                 # one with the reason on record; the other results of the step are not lost
                 self.failed[r.ticket] = str(e)
-                out.append((r.ticket, self._empty(True, refined_text=text), True))
+                out.append((r.ticket, self._end_chunk(self._empty(True, refined_text=text), info.get("streaming")), True))
                 continue
             self._public[tk2], self._code_tk[r.ticket], self._refined[r.ticket] = r.ticket, tk2, text
-        spoken = [r for r in code if r.ids.shape[0] > 0]
+        spoken = [r for r in code if r.ids.shape[0] > 0 and r.ticket not in self._streams]      # (a streaming ticket's audio left as windows)
         wavs = self.pipe._decode_to_wavs([(r.hiddens if self.use_decoder else r.ids) for r in spoken], self.use_decoder) if spoken else []
         wav_of = {r.ticket: w for r, w in zip(spoken, wavs)}
         for r in code:
@@ -354,19 +407,35 @@ class SynthSession:
             self._code_tk.pop(pub, None)
             refined = self._refined.pop(pub, None)
             w = wav_of.get(r.ticket)
+            fw = final_of.get(r.ticket)
+            if fw is not None:
+                w = wav_of_win[id(fw)]
             if w is None:
                 w = torch.zeros(0, device=self.pipe.device)
             if self.return_details:
                 w = SessionDetails(wav=w, ids=r.ids, logprobs=r.logprobs.cpu(), sampled_logprobs=r.sampled_logprobs.cpu(), mean_logprob=mean_logprob(r.logprobs.cpu()),
                                    finished_by_eos=r.finished_by_eos, refined_text=refined)
+            if fw is not None:
+                self._streams.pop(r.ticket, None)
+                w = SessionChunk(wav=w.wav if self.return_details else w, start=fw.s0, final=True, details=w if self.return_details else None, n_tokens=fw.n_tokens)
             out.append((pub, w, r.cancelled))
         return out
+
+    def _end_chunk(self, empty, streaming):
+        """how an utterance that ends in its refine stage is delivered: a streaming ticket gets its (empty) final chunk"""
+        if streaming is None:
+            return empty
+        wav = torch.zeros(0, dtype=torch.int16 if streaming[2] else torch.float32, device=self.pipe.device)
+        return SessionChunk(wav=wav, start=0, final=True, details=empty if self.return_details else None)
 
     @torch.no_grad()
     def poll(self):
         """One DecodeSession.step(); what finished is vocoded in one batch.  Returns [(ticket, wav or SessionDetails, cancelled)]: a cancelled utterance with at
-        least one token is vocoded, one with none yields an empty waveform.  A refine stage that ended is not returned: its code stage is submitted instead."""
-        return self._deliver(self.session.step())
+        least one token is vocoded, one with none yields an empty waveform.  A refine stage that ended is not returned: its code stage is submitted instead.
+        A streaming ticket (submit(stream=...)) appears as (ticket, SessionChunk, cancelled) zero or more times, the last one with final=True; every window
+        the step made due is vocoded in one ctts_synth_windows call, right behind the step's decode launches on the same stream."""
+        results = self.session.step()
+        return self._deliver(results, self.session.take_windows() if self._streams else ())      # (no streaming ticket in flight: nothing can be due)
 
     def drain(self):
         out = []
@@ -1247,8 +1316,9 @@ class ChatTTSPlusPipeline:
         merged adapter for the whole session (an utterance may name its own at submit), `rows` bounds the decode batch, `seed` keys the device noise.
         `refine` (a RefineTextParams; max_new_token <= the code parameters', repetition_penalty 1): submit() refines every text first, inside the session -- as
         a text row beside the code rows (SynthSession); SessionDetails.refined_text carries the result.
-        Not offered inside a session (refused): num_candidates / shared prompt passes, caller-supplied noise, stream=True windows, infer_sharded, and infer()'s
-        call-level names of the refine-text pass (refine_text_only, params_refine_text: use refine=)."""
+        Not offered inside a session (refused): num_candidates / shared prompt passes, caller-supplied noise, session-wide streaming windows
+        (stream=True here: streaming is asked per utterance, submit(stream="exact" | "eager")), infer_sharded, and infer()'s call-level names of the refine-text
+        pass (refine_text_only, params_refine_text: use refine=)."""
         refuse_out_of_scope(out_of_scope, "use infer() for it (the refine-text pass is served inside a session through open_session(refine=RefineTextParams(...)))")
         if refine is not None and not isinstance(refine, RefineTextParams):
             raise _lib.HipBackendError("open_session: refine must be a RefineTextParams")

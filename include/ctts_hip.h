@@ -393,7 +393,8 @@ int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, const int32_t
  * Both act on the generate state of the last ctts_gpt_begin, which outlives the call that began it: the output arrays handed to that begin (ids, hiddens, log-probs,
  * finish, end_idx) must still be alive when rows are grown and admitted, as for ctts_gpt_admit -- the engine keeps the pointers, not the memory.
  * Not offered inside one generate state: caller-supplied noise with grow; a session on top of these (GPT.open_session) additionally refuses shared prompt
- * passes / num_candidates, per-utterance streaming windows and infer_sharded.  The refine-text pass runs INSIDE such a session as text rows beside the code rows
+ * passes / num_candidates, session-wide streaming windows (stream= at open_session: streaming is asked per utterance at submit, and vocoded through
+ * ctts_synth_windows from the token counts ctts_gpt_rows_enqueue reports) and infer_sharded.  The refine-text pass runs INSIDE such a session as text rows beside the code rows
  * (ctts_gpt_enable_text_rows below; GPT.open_session(text_rows=...), submit(mode="text")). */
 int ctts_gpt_grow(ctts_gpt* h, int n, void* stream);
 int ctts_gpt_cancel(ctts_gpt* h, int n, const int32_t* rows_host, void* stream);
@@ -570,6 +571,26 @@ int ctts_synth_batch(ctts_voc* h, const float* const* hidden_ptrs, const int32_t
 int ctts_dvae_decode_codes(ctts_voc* h, const int32_t* ids_dev, int n_tokens, float* mel_dev, void* stream);
 /* ... and _decode_to_wavs(result.ids, use_decoder=False) for B utterances in one launch sequence; ids_ptrs[u] int32 [n_tokens[u]][G*R]. */
 int ctts_synth_batch_codes(ctts_voc* h, const int32_t* const* ids_ptrs, const int32_t* n_tokens, int B, float* const* wav_ptrs, void* stream);
+
+/* Windows of the waveform (streaming; no counterpart in the reference, whose stream branch vocodes the whole prefix per chunk, pipeline:436-461).
+ *
+ * ctts_synth_window_range: host only, touches no GPU.  Tokens [a, b) whose vocoding contains samples [s0, s1) of the n_tokens-long prefix waveform exactly:
+ * out5 = {a, b, sample offset of that sub-waveform (2 a hop), s0 clamped, s1 clamped}; an empty window gives five zeros.  A sample s depends on ISTFT frames
+ * s/hop - 1 .. s/hop + 2, each on halo_frames - 3 mel frames either side; a token is two frames (halo_frames = 105 for the DVAE decoder + Vocos stack).
+ *   clamp_tail != 0  a right edge inside the halo of the prefix's end is moved to the end: the zero padding there is part of the PREFIX waveform.  The window is
+ *                    a slice of the n_tokens prefix's waveform, which later tokens change over its last halo.
+ *   clamp_tail == 0  the rule for SETTLED windows: s1 <= hop * max(0, 2 n_tokens - halo_frames - 2), the samples no later token can change (every frame
+ *                    the window needs exists: ceil(s1 / hop) + 1 + halo_frames + 1 <= 2 n_tokens); an unsettled s1 is an error.  b stays the unclamped
+ *                    ceil(f1 / 2): the range does not depend on n_tokens, and the samples are those of the finished utterance.
+ *
+ * ctts_synth_windows: ctts_synth_batch / ctts_synth_batch_codes (codes != 0: src_ptrs[u] are int32 [n_tokens[u]][G*R] code ids, else fp32 [n_tokens[u]][768]
+ * hidden rows) for B token sub-ranges, except that the last kernel overlap-adds only samples [skip[u], skip[u] + count[u]) of sub-waveform u and stores them at
+ * element out_off[u] of ONE packed device buffer `out`: fmt 0 = float32 (bit-identical to the slice of ctts_synth_batch's output), fmt 1 = int16 PCM,
+ * rintf(clamp(x, -1, 1) * 32767).  n_tokens, skip, count and out_off are HOST arrays of length B (<= max_batch); count[u] == 0 stores nothing; a window
+ * outside its sub-waveform is refused.  Nothing else of `out` is written.  Like ctts_synth_batch it never synchronises the stream. */
+int ctts_synth_window_range(int n_tokens, int64_t s0, int64_t s1, int hop, int halo_frames, int clamp_tail, int64_t* out5);
+int ctts_synth_windows(ctts_voc* h, const void* const* src_ptrs, const int32_t* n_tokens, const int32_t* skip, const int32_t* count, int B, void* out,
+                       const int32_t* out_off, int fmt, int codes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Zero-shot speaker prompt: waveform -> audio-prompt codes.
