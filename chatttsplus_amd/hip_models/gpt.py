@@ -349,7 +349,7 @@ def compact_size(n_live: int) -> int:
 
 
 class RowBook:
-    """Continuous batching bookkeeping (GPT.generate_many): which utterance sits in which decode row.  Every seating gets a ticket; the row
+    """Continuous batching bookkeeping (the row level of SessionBook): which utterance sits in which decode row.  Every seating gets a ticket; the row
     states the engine reports ({fin, end} per row, ctts_gpt_rows_enqueue) arrive one or two chunks late and are interpreted through the
     ticket layout that was current when the report was ENQUEUED -- a report taken before an admission or a compaction can neither finish the
     row's new occupant nor be confused by rows having moved."""
@@ -414,10 +414,17 @@ class SessionPlan:
 
 
 class SessionBook:
-    """Bookkeeping of a serving session (GPT.open_session), pure Python: tickets, the queue, which output slot an utterance writes to and when the slot is
-    free again, the mirror of the decode rows' KV lanes, and the decision what to do with the batch next -- seat queued utterances in free rows, then in rows
-    obtained by growing the batch up to `rows`, else (nothing queued) shrink it by the compact_size rule.  Row reports are interpreted by a RowBook, whose
-    "utterance" is the session ticket.
+    """Bookkeeping of continuous batching (DecodeSession: GPT.open_session and GPT.generate_many), pure Python: tickets, the queue, which output slot an
+    utterance writes to and when the slot is free again, the mirror of the decode rows' KV lanes, and the decision what to do with the batch next -- seat queued
+    utterances in free rows, then in rows obtained by growing the batch up to `rows`, else (nothing queued) shrink it by the compact_size rule.  Row reports are
+    interpreted by a RowBook, whose "utterance" is the session ticket.
+
+    The policy of a request that is known in full (generate_many), off by default:
+      own_slots   ticket k writes output slot k, also when ensure_non_empty seats it again: slots are never recycled (release() frees none), the queue alone bounds
+                  plan(), and the batch opens at min(queued, rows) rows and never grows
+      admit_min   free rows are held back until an admission pays for its prompt pass: with `free` the free rows of the B current ones and `since_free` the plans
+                  in a row that saw a free row, queued utterances are seated only if len(free) >= min(admit_min, queued), since_free >= 4 or len(free) == B; a
+                  held-back plan is empty (no compaction while something is queued).  1 = seat at once.
 
     Streaming (submit(stream="exact" | "eager")): every row report carries the live rows' token counts, and from them the book derives the sample windows
     that are due (take_windows): (ticket, slot, tokens seen, s0, s1, final).  The windows of a ticket are consecutive and disjoint; the final one comes with
@@ -429,7 +436,7 @@ class SessionBook:
 
     def __init__(self, rows: int, out_slots: int, max_batch: int, max_seq: int, max_new_token: int, ensure_non_empty: bool = True, max_restarts: int = 64,
                  compact: bool = True, max_new_text: Optional[int] = None, stream_batch: int = 24, stream_speed: int = 12000, hop: int = 256,
-                 halo_frames: int = 105):
+                 halo_frames: int = 105, own_slots: bool = False, admit_min: int = 1):
         if not (1 <= int(rows) <= int(max_batch)):
             raise ValueError(f"session: rows={rows} outside 1..max_batch={max_batch}")
         if int(out_slots) < 1:
@@ -442,7 +449,9 @@ class SessionBook:
         self.max_new_text = None if max_new_text is None else int(max_new_text)
         self.book = RowBook()
         self.lanes: List[int] = []                 # KV lane of every current decode row (the engine's row_seq)
-        self.free_slots = list(range(int(out_slots)))
+        self.own_slots, self.admit_min, self._since_free = bool(own_slots), max(1, int(admit_min)), 0
+        self.free_slots = [] if self.own_slots else list(range(int(out_slots)))
+        self.live: List[tuple] = []                # (ticket, tokens so far) of the rows the last report showed decoding
         self.queue: List[int] = []                 # tickets waiting for a row (and an output slot), in order of service
         self.utts = {}                             # ticket -> dict(utt_id, T, limit, attempt, slot, row_tk, cancelled, mode)
         self.begun = False
@@ -551,12 +560,18 @@ class SessionBook:
 
     def _seat(self, row: int, tk: int) -> None:
         u = self.utts[tk]
-        u["slot"] = self.free_slots.pop(0)
+        u["slot"] = tk if self.own_slots else self.free_slots.pop(0)
         u["row_tk"] = self.book.seat(row, tk, u["attempt"])
+
+    def _unseat(self, u: dict) -> None:
+        if u["slot"] is not None and not self.own_slots:
+            self.free_slots.append(u["slot"])
+            self.free_slots.sort()
+        u["slot"] = None
 
     def plan(self) -> SessionPlan:
         """Decides and books the next change of the batch; the caller carries it out in the order begin | grow, admit | compact."""
-        k = min(len(self.queue), len(self.free_slots))
+        k = len(self.queue) if self.own_slots else min(len(self.queue), len(self.free_slots))
         if not self.begun:
             k = min(k, self.rows)
             if k == 0:
@@ -570,11 +585,13 @@ class SessionBook:
             return SessionPlan(begin=list(enumerate(take)))
         B = len(self.book.row_tk)
         free = self.book.free_rows()
+        self._since_free = self._since_free + 1 if free else 0
         if k > 0:
-            grow = max(0, min(k - len(free), self.rows - B))
+            grow = 0 if self.own_slots else max(0, min(k - len(free), self.rows - B))
             k = min(k, len(free) + grow)
-            if k == 0:
+            if k == 0 or not (grow or len(free) >= min(self.admit_min, len(self.queue)) or self._since_free >= 4 or len(free) == B):
                 return SessionPlan()
+            self._since_free = 0
             lanes = self.free_lanes()[:grow]           # lowest first: after a compaction these are not B ..
             self.lanes += lanes
             rows = free[:k - grow] + list(range(B, B + grow))
@@ -595,11 +612,12 @@ class SessionBook:
     def report(self, layout, states):
         """One row report ([(fin, end)] per row of `layout`, RowBook.report).  Returns [(ticket, tokens, fin bits, cancelled)] of the utterances that ended; those
         whose first token was EOS go back to the head of the queue with their next attempt (a cancelled one ends instead).  The caller clones the results out
-        of slot utts[ticket]["slot"] and then calls release(ticket)."""
+        of slot utts[ticket]["slot"] and then calls release(ticket).  `live` = [(ticket, tokens so far)] of the rows this report showed still decoding."""
         fin_of = {self.book.tickets[t][0]: int(fin) for t, (fin, end) in zip(layout, states) if t is not None and fin and t in self.book.tickets}
-        for t, (fin, end) in zip(layout, states):  # live rows of streaming utterances: the windows their token counts make due
-            if t is not None and not fin and t in self.book.tickets and self.utts[self.book.tickets[t][0]].get("stream"):
-                self._progress(self.book.tickets[t][0], end)
+        self.live = [(self.book.tickets[t][0], int(end)) for t, (fin, end) in zip(layout, states) if t is not None and not fin and t in self.book.tickets]
+        for tk, n in self.live:                    # live rows of streaming utterances: the windows their token counts make due
+            if self.utts[tk].get("stream"):
+                self._progress(tk, n)
         done, again = self.book.report(layout, states, self.ensure_non_empty, self.max_restarts)
         out, back = [], []
         for tk, att in again:
@@ -610,9 +628,7 @@ class SessionBook:
                 continue
             u["attempt"], u["row_tk"] = att, None
             u["emitted"], u["last_n"] = 0, 0           # (its first token was EOS: nothing was emitted; the next attempt starts over)
-            self.free_slots.append(u["slot"])
-            self.free_slots.sort()
-            u["slot"] = None
+            self._unseat(u)
             back.append(tk)
         self.queue = back + self.queue
         for tk, n in done:
@@ -624,10 +640,7 @@ class SessionBook:
 
     def release(self, tk: int) -> None:
         """the utterance's result has been cloned out: its output slot may be written again"""
-        u = self.utts.pop(tk)
-        if u["slot"] is not None:
-            self.free_slots.append(u["slot"])
-            self.free_slots.sort()
+        self._unseat(self.utts.pop(tk))
 
 
 # arguments of generate() / generate_many() / infer() that a session refuses by name (GPT.open_session, ChatTTSPlusPipeline.open_session)
@@ -673,7 +686,8 @@ def text_rows_cfg(text_rows, num_vq: int = 4) -> _lib.SamplerCfg:
 
 @dataclass(repr=False, eq=False)
 class SessionResult:
-    """One utterance a DecodeSession delivered: clones, independent of the session's output buffers."""
+    """One utterance a DecodeSession delivered: clones, independent of the session's output buffers (a request's driver, whose output slots are never rewritten,
+    hands out views)."""
     ticket: int
     utt_id: int
     ids: torch.Tensor
@@ -705,38 +719,74 @@ class SessionWindow:
     mode: str = "exact"
 
 
+class OutBuffers:
+    """The output buffers of a generate state, indexed [output slot][token] -- ids, hiddens, the (raw, sampled) log-probs laid out like ids, the text rows' ids of
+    a session, finish / end_idx per slot -- and the GenIO that names them.  Uninitialised: only [s, :end_idx[s]] is ever read, and every one of those rows was
+    written by the step that produced it (the default max_new_token = 2048 made zero-filling a 201 MB write per call at batch 32)."""
+
+    def __init__(self, n: int, max_new: int, gpt: "GPT", hidden: bool, logprobs: bool, text_new: Optional[int] = None):
+        dev, NVQ = gpt.device, gpt.num_vq
+        self.ids = torch.empty(n, max_new, NVQ, dtype=torch.int32, device=dev)
+        self.hid = torch.empty(n, max_new, gpt.model_dim, dtype=torch.float32, device=dev) if hidden else None
+        self.lps = torch.empty(2, n, max_new, NVQ, dtype=torch.float32, device=dev) if logprobs else None
+        self.tids = torch.empty(n, text_new, NVQ, dtype=torch.int32, device=dev) if text_new else None
+        self.finish = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.end_idx = torch.zeros(n, dtype=torch.int32, device=dev)
+
+    def io(self, n_draws: int, seed: int, utt_ids=None, row_limits=None, noise=None) -> _lib.GenIO:
+        """`utt_ids` / `row_limits`: numpy arrays the caller keeps alive over the begin call"""
+        return _lib.GenIO(ids=self.ids.data_ptr(), hiddens=self.hid.data_ptr() if self.hid is not None else None, finish=self.finish.data_ptr(),
+                          end_idx=self.end_idx.data_ptr(), noise=noise.data_ptr() if noise is not None else None, n_draws=int(n_draws), seed=int(seed),
+                          utt_ids=utt_ids.ctypes.data if utt_ids is not None else None, row_limits=row_limits.ctypes.data if row_limits is not None else None)
+
+    def take(self, s: int, n: int, eos: bool, first_column: bool = False, text_row: bool = False):
+        """(ids, hiddens, logprobs, sampled_logprobs, final_logprobs) of slot s's first n tokens: the ids as long (gpt.py:295-297), the rest views, None what the
+        state does not return.  `first_column`: ids [n] of a refine-text state (gpt.py:298-299); `text_row`: those of a session's text row.  The step that sampled
+        EOS wrote its log-probs at index n (its ids are not part of the sequence): final_logprobs, a clone, where `eos` says so and the row exists."""
+        if text_row:
+            return self.tids[s, :n, 0].to(torch.long), None, None, None, None
+        ids = self.ids[s, :n].to(torch.long)
+        ids = ids[:, 0] if first_column else ids
+        hid = self.hid[s, :n] if self.hid is not None else None
+        if self.lps is None:
+            return ids, hid, None, None, None
+        return ids, hid, self.lps[0, s, :n], self.lps[1, s, :n], self.lps[:, s, n].clone() if (eos and n < self.lps.shape[2]) else None
+
+
 class DecodeSession:
-    """A generate state kept open (GPT.open_session): utterances are submitted and cancelled while others decode.  The decode batch is as wide as the utterances
-    in flight need -- it grows (ctts_gpt_grow + ctts_gpt_admit) when texts arrive and shrinks (ctts_gpt_compact) when they end -- instead of being opened at its
-    peak width.  Holds the engine's busy token until close(); a context manager.  A code-mode generate state, device noise; opened with `text_sc` (the refine
-    pass's sampler configuration) it also serves refine-text utterances as text rows beside the code rows (submit(mode="text"); ctts_gpt_enable_text_rows)."""
+    """The one driver of continuous batching: a generate state kept open while utterances are seated, decoded, delivered and replaced.  GPT.open_session hands it
+    out -- utterances are submitted and cancelled while others decode, the decode batch is as wide as the utterances in flight need (it grows, ctts_gpt_grow +
+    ctts_gpt_admit, when texts arrive and shrinks, ctts_gpt_compact, when they end), and it holds the engine's busy token until close(); a context manager.
+    GPT.generate_many drives one too, with the request policy of SessionBook (`own_slots`, `admit_min`: results are then views of the output slots, which are never
+    rewritten), a call-wide refine-text configuration (`sc.infer_text`: results are ids[:, 0]) and shared prompt passes (`share` = (prompt per ticket, prompts,
+    adapter slot per ticket)); none of the three is offered by open_session.  Device noise.  Opened with `text_sc` (the refine pass's sampler configuration) a
+    code-mode session also serves refine-text utterances as text rows beside the code rows (submit(mode="text"); ctts_gpt_enable_text_rows)."""
 
     def __init__(self, gpt: "GPT", sc, seed: int, rows: int, out_slots: int, return_hidden: bool, return_logprobs: bool, ensure_non_empty: bool, max_restarts: int = 64,
-                 text_sc=None):
+                 text_sc=None, own_slots: bool = False, admit_min: int = 1, share=None, hold=None):
         self.gpt, self.sc, self.seed = gpt, sc, int(seed)
         self.max_new = int(sc.max_new_token)
         self.text_sc = text_sc
         try:
             self.book = SessionBook(rows, out_slots, gpt.max_batch, gpt.max_seq, self.max_new, ensure_non_empty, max_restarts, gpt.compact,
-                                    max_new_text=None if text_sc is None else int(text_sc.max_new_token))
+                                    max_new_text=None if text_sc is None else int(text_sc.max_new_token), own_slots=own_slots, admit_min=admit_min)
         except ValueError as e:
             raise _lib.HipBackendError(f"open_session: {e}") from None
-        dev, H, NVQ = gpt.device, gpt.model_dim, gpt.num_vq
-        # the text rows' ids [slot][text max_new_token][4]: the same slots as `ids` (a slot is held by one utterance of either kind)
-        self.tids = torch.empty(out_slots, int(text_sc.max_new_token), NVQ, dtype=torch.int32, device=dev) if text_sc is not None else None
-        self.ids = torch.empty(out_slots, self.max_new, NVQ, dtype=torch.int32, device=dev)
-        self.hid = torch.empty(out_slots, self.max_new, H, dtype=torch.float32, device=dev) if return_hidden else None
-        self.lps = torch.empty(2, out_slots, self.max_new, NVQ, dtype=torch.float32, device=dev) if return_logprobs else None
-        self.finish = torch.zeros(out_slots, dtype=torch.int32, device=dev)
-        self.end_idx = torch.zeros(out_slots, dtype=torch.int32, device=dev)
+        # (the text rows' ids share the slots of `ids`: a slot is held by one utterance of either kind)
+        self.out = OutBuffers(out_slots, self.max_new, gpt, return_hidden, return_logprobs, None if text_sc is None else int(text_sc.max_new_token))
+        self.ids, self.hid = self.out.ids, self.out.hid
         self.chunk = max(4, min(gpt.chunk_steps, gpt.compact_chunk))
         self.batch_trace: List[tuple] = []         # (steps launched, rows) at every change of the row count
+        self.admissions: List[tuple] = []          # (steps launched, utterances seated) per admission
+        self.compactions: List[tuple] = []         # (steps launched, rows kept) per compaction
+        self.shared_prompts: List[tuple] = []      # (rows, prompts) per begin / admit of a state with shared prompt passes
         self.launched = 0
-        self._req = {}                             # ticket -> (emb [T,H] device, knobs or None, adapter slot, mode 0 / 1)
+        self._req = {}                             # ticket -> (prompt [T, H] on the device, attended length n <= T, knobs or None, adapter slot or None, mode 0 / 1)
         self._pins = [torch.zeros(2 * int(rows), dtype=torch.int32).pin_memory() for _ in range(2)]
         self._evs = [torch.cuda.Event() for _ in range(2)]
         self._layouts = [None, None]
         self._pending: List[int] = []
+        self._share, self._hold = share, hold
         self._adapters = False                     # an utterance of this session named an adapter slot: every admission names its rows' slots from then on
         self._stream_mode = {}                     # streaming ticket -> "exact" / "eager"
         self._wins: List[SessionWindow] = []       # windows the last step made due
@@ -785,14 +835,24 @@ class DecodeSession:
         slot = -1 if adapter_slot is None or int(adapter_slot) < 0 else int(adapter_slot)
         if slot >= 0 and g.invariant_option():
             raise _lib.HipBackendError(f"submit: per-utterance adapters are outside the {g.invariant_option()} contract; merge the adapter (with_lora) or set the option to 0")
-        try:
-            tk = self.book.submit(n, utt_id, limit, mode, stream=stream, stream_batch=stream_batch)
-        except ValueError as e:
-            raise _lib.HipBackendError(str(e)) from None
-        self._req[tk] = (emb[emb.shape[0] - n:].to(g.device, dtype=torch.float32).contiguous(), knobs, slot, 1 if mode == "text" else 0)
-        self._adapters = self._adapters or slot >= 0
+        tk = self._enqueue(emb[emb.shape[0] - n:].to(g.device, dtype=torch.float32).contiguous(), n, utt_id, limit, knobs, slot if slot >= 0 else None, mode,
+                           stream, stream_batch)
         if stream is not None:
             self._stream_mode[tk] = stream
+        return tk
+
+    def _enqueue(self, prompt: torch.Tensor, n: int, utt_id: int, limit, knobs, adapter: Optional[int], mode: str = "code", stream=None, stream_batch=None) -> int:
+        """One ticket: `prompt` [T, H] on the device, of which the last `n` rows are attended (rows before them are the caller's left padding); `adapter` None =
+        the utterance names none (an int, -1 included, makes every later seating name its rows' slots)"""
+        try:
+            tk = self.book.submit(max(int(n), 1), utt_id, limit, mode, stream=stream, stream_batch=stream_batch)
+        except ValueError as e:
+            raise _lib.HipBackendError(str(e)) from None
+        self._req[tk] = (prompt, int(n), knobs, adapter, 1 if mode == "text" else 0)
+        if adapter is not None and not self._adapters:
+            self._adapters = True
+            if self._hold is not None:
+                self._hold.resets.add("adapters")
         return tk
 
     def cancel(self, ticket: int) -> bool:
@@ -803,101 +863,94 @@ class DecodeSession:
 
     # -- engine calls -------------------------------------------------------------------------------
     def _prompts(self, tks):
-        """left-padded prompts [k, Ta, H] / [k, Ta] of the tickets, Ta = the longest of them"""
-        g = self.gpt
-        Ta = max(int(self._req[tk][0].shape[0]) for tk in tks)
-        emb = torch.zeros(len(tks), Ta, g.model_dim, dtype=torch.float32, device=g.device)
-        mask = torch.zeros(len(tks), Ta, dtype=torch.int32, device=g.device)
-        for i, tk in enumerate(tks):
-            e = self._req[tk][0]
-            emb[i, Ta - e.shape[0]:] = e
-            mask[i, Ta - e.shape[0]:] = 1
+        """The prompts [k, Ta, H] / masks [k, Ta] of one seating, Ta = the longest attended length among them: a ticket whose tensor has Ta rows or more gives its
+        last Ta (a request's tickets are rows of the caller's batch and keep the caller's padding rows), a shorter one is zero-padded on the left.  With shared
+        prompt passes: one row per prompt the tickets name, and the engine is told which of them each ticket has (for the begin / admit call that follows)."""
+        g, req = self.gpt, self._req
+        rows = tks
+        if self._share is not None:
+            prompt_of, n_prompts, slots = self._share
+            sel, local, leaders = prompt_groups(prompt_of, n_prompts, slots, subset=tks)
+            if len(sel) < len(tks):
+                arr = np.ascontiguousarray(local, dtype=np.int32)
+                _lib.check(g._lib.ctts_gpt_share_prompts(g._h, len(tks), arr.ctypes.data_as(C.c_void_p), len(sel)), "share_prompts")
+            self.shared_prompts.append((len(tks), len(sel)))
+            rows = [tks[j] for j in leaders]
+        Ta = max(1, max(req[tk][1] for tk in rows))
+        emb = torch.nn.utils.rnn.pad_sequence([req[tk][0][-Ta:] for tk in rows], batch_first=True, padding_side="left")
+        n = torch.as_tensor([req[tk][1] for tk in rows], device=g.device)
+        mask = (torch.arange(Ta, device=g.device)[None, :] >= (Ta - n)[:, None]).to(torch.int32)
         return Ta, emb, mask
 
-    def _arrays(self, tks):
-        u = self.book.utts
-        return (np.ascontiguousarray([u[tk]["utt_id"] for tk in tks], dtype=np.uint64), np.ascontiguousarray([u[tk]["limit"] for tk in tks], dtype=np.int32),
-                np.ascontiguousarray([u[tk]["slot"] for tk in tks], dtype=np.int32), np.ascontiguousarray([u[tk]["attempt"] for tk in tks], dtype=np.int32))
-
-    def _begin(self, seats, st):
-        g, lib, h = self.gpt, self.gpt._lib, self.gpt._h
+    def _seat(self, seats, st, begin: bool = False):
+        """Carries out one seating [(row, ticket)]: ctts_gpt_begin (the state's first: prompt pass and first sample included) or ctts_gpt_admit, after the per-row
+        attributes -- shared prompts, adapter slots, sampling knobs, row modes -- that the call picks up"""
+        g, lib, h, utts, req = self.gpt, self.gpt._lib, self.gpt._h, self.book.utts, self._req
         tks = [tk for _, tk in seats]
-        R = len(tks)
+        k = len(tks)
+
+        def arr(values, dtype=np.int32):
+            return np.ascontiguousarray(values, dtype=dtype)
+
+        def ptr(a):
+            return a.ctypes.data_as(C.c_void_p)
+
+        rows, uids, lims = arr([r for r, _ in seats]), arr([utts[tk]["utt_id"] for tk in tks], np.uint64), arr([utts[tk]["limit"] for tk in tks])
+        outs, atts = arr([utts[tk]["slot"] for tk in tks]), arr([utts[tk]["attempt"] for tk in tks])
         Ta, emb, mask = self._prompts(tks)
-        uid_arr, lim_arr, _, _ = self._arrays(tks)
-        io = _lib.GenIO(ids=self.ids.data_ptr(), hiddens=self.hid.data_ptr() if self.hid is not None else None, finish=self.finish.data_ptr(),
-                        end_idx=self.end_idx.data_ptr(), noise=None, n_draws=self.max_new, seed=self.seed, utt_ids=uid_arr.ctypes.data, row_limits=lim_arr.ctypes.data)
-        if self._adapters:
-            g.set_row_adapters([self._req[tk][2] for tk in tks])
-        knobs = any(self._req[tk][1] is not None for tk in tks)
-        if knobs:
+        slots = arr([-1 if req[tk][3] is None else req[tk][3] for tk in tks]) if self._adapters else None
+        knobs = None
+        if any(req[tk][2] is not None for tk in tks):
             base = row_sampling_from_values(self.sc, None, g.num_vq)
-            _lib.check(lib.ctts_gpt_set_row_sampling(h, (_lib.RowSampling * R)(*[self._req[tk][1] or base for tk in tks]), R), "set_row_sampling")
-        modes = np.ascontiguousarray([self._req[tk][3] for tk in tks], dtype=np.int32)
+            knobs = (_lib.RowSampling * k)(*[req[tk][2] or base for tk in tks])
+        modes = arr([req[tk][4] for tk in tks])
+        if not begin:
+            if slots is not None:
+                _lib.check(lib.ctts_gpt_admit_adapters(h, k, ptr(rows), ptr(slots), st), "admit_adapters")
+            if knobs is not None:         # (re-admissions of ensure_non_empty included: the utterance keeps its own knobs)
+                _lib.check(lib.ctts_gpt_admit_sampling(h, k, ptr(rows), knobs, st), "admit_sampling")
+            if self.text_sc is not None:
+                _lib.check(lib.ctts_gpt_admit_modes(h, k, ptr(rows), ptr(modes), st), "admit_modes")
+            _lib.check(lib.ctts_gpt_admit(h, k, ptr(rows), Ta, mask.data_ptr(), emb.data_ptr(), ptr(uids), ptr(lims), ptr(outs), ptr(atts), st), "admit")
+            self.admissions.append((self.launched, k))
+            return
+        io = self.out.io(self.max_new, self.seed, uids, lims)
+        if slots is not None:
+            g.set_row_adapters(slots.tolist())
+        if knobs is not None:
+            _lib.check(lib.ctts_gpt_set_row_sampling(h, knobs, k), "set_row_sampling")
         if modes.any():
-            _lib.check(lib.ctts_gpt_set_row_modes(h, modes.ctypes.data_as(C.c_void_p), R), "set_row_modes")
+            _lib.check(lib.ctts_gpt_set_row_modes(h, ptr(modes), k), "set_row_modes")
         try:
-            _lib.check(lib.ctts_gpt_begin(h, R, Ta, mask.data_ptr(), C.byref(self.sc), C.byref(io), st), "begin")
+            _lib.check(lib.ctts_gpt_begin(h, k, Ta, mask.data_ptr(), C.byref(self.sc), C.byref(io), st), "begin")
         finally:
-            if knobs:
+            if knobs is not None:
                 lib.ctts_gpt_set_row_sampling(h, None, 0)
             if modes.any():
                 lib.ctts_gpt_set_row_modes(h, None, 0)
         if self.text_sc is not None:               # (after begin, which creates the state; before the first sample, which a begun text row needs it for)
-            _lib.check(lib.ctts_gpt_enable_text_rows(h, C.byref(self.text_sc), self.tids.data_ptr(), st), "enable_text_rows")
-        if self.lps is not None:
-            _lib.check(lib.ctts_gpt_set_logprob_out(h, self.lps[0].data_ptr(), self.lps[1].data_ptr(), st), "set_logprob_out")
+            _lib.check(lib.ctts_gpt_enable_text_rows(h, C.byref(self.text_sc), self.out.tids.data_ptr(), st), "enable_text_rows")
+        if self.out.lps is not None:
+            _lib.check(lib.ctts_gpt_set_logprob_out(h, self.out.lps[0].data_ptr(), self.out.lps[1].data_ptr(), st), "set_logprob_out")
         _lib.check(lib.ctts_gpt_prefill(h, emb.data_ptr(), st), "prefill")
         _lib.check(lib.ctts_gpt_sample(h, st), "sample")
         self.launched = 1
-        self.batch_trace.append((self.launched, R))
+        self.batch_trace.append((self.launched, k))
 
-    def _admit(self, seats, st):
-        g, lib, h = self.gpt, self.gpt._lib, self.gpt._h
-        rows, tks = [r for r, _ in seats], [tk for _, tk in seats]
-        k = len(tks)
-        Ta, emb, mask = self._prompts(tks)
-        uid_arr, lim_arr, out_arr, att_arr = self._arrays(tks)
-        rows_arr = np.ascontiguousarray(rows, dtype=np.int32)
-        if self._adapters:
-            sl_arr = np.ascontiguousarray([self._req[tk][2] for tk in tks], dtype=np.int32)
-            _lib.check(lib.ctts_gpt_admit_adapters(h, k, rows_arr.ctypes.data_as(C.c_void_p), sl_arr.ctypes.data_as(C.c_void_p), st), "admit_adapters")
-        if any(self._req[tk][1] is not None for tk in tks):
-            base = row_sampling_from_values(self.sc, None, g.num_vq)
-            _lib.check(lib.ctts_gpt_admit_sampling(h, k, rows_arr.ctypes.data_as(C.c_void_p), (_lib.RowSampling * k)(*[self._req[tk][1] or base for tk in tks]), st),
-                       "admit_sampling")
-        if self.text_sc is not None:
-            md_arr = np.ascontiguousarray([self._req[tk][3] for tk in tks], dtype=np.int32)
-            _lib.check(lib.ctts_gpt_admit_modes(h, k, rows_arr.ctypes.data_as(C.c_void_p), md_arr.ctypes.data_as(C.c_void_p), st), "admit_modes")
-        _lib.check(lib.ctts_gpt_admit(h, k, rows_arr.ctypes.data_as(C.c_void_p), Ta, mask.data_ptr(), emb.data_ptr(), uid_arr.ctypes.data_as(C.c_void_p),
-                                      lim_arr.ctypes.data_as(C.c_void_p), out_arr.ctypes.data_as(C.c_void_p), att_arr.ctypes.data_as(C.c_void_p), st), "admit")
-
-    def _result(self, tk: int, n: int, fin: int, cancelled: bool) -> SessionResult:
+    def _result(self, tk: int, n: int, fin: int = 0, cancelled: bool = False, final: bool = True) -> SessionResult:
+        """The utterance's first n tokens out of its output slot: clones (views where slots are the tickets' own).  `final`: the utterance ended -- its ticket and
+        slot are released; else a view of a live utterance's tokens so far.  A text row: ids [n] as generate(infer_text=True) returns them (gpt.py:298-299), no
+        hiddens, no log-probs."""
         u = self.book.utts[tk]
-        s = u["slot"]
-        eos = bool(fin & 2)
-        if u.get("mode", "code") == "text":      # ids [n] as generate(infer_text=True) returns them (gpt.py:298-299); no hiddens, no log-probs
-            ids = self.tids[s, :n, 0].to(torch.long) if (s is not None and n > 0) else torch.empty(0, dtype=torch.long, device=self.gpt.device)
-            res = SessionResult(ticket=tk, utt_id=u["utt_id"], ids=ids, finished_by_eos=eos, cancelled=cancelled, attempt=u["attempt"], mode="text")
+        s, eos, text = u["slot"], bool(fin & 2), u.get("mode", "code") == "text"
+        ids, hid, lp, slp, flp = self.out.take(0 if s is None else s, n if s is not None else 0, eos and s is not None, bool(self.sc.infer_text), text)
+        if final and not self.book.own_slots:
+            hid, lp, slp = (x.clone() if x is not None else None for x in (hid, lp, slp))
+        res = SessionResult(ticket=tk, utt_id=u["utt_id"], ids=ids, hiddens=hid, logprobs=lp, sampled_logprobs=slp, final_logprobs=flp, finished_by_eos=eos,
+                            cancelled=cancelled, attempt=u["attempt"], mode="text" if text else "code")
+        if final:
             self.book.release(tk)
             self._req.pop(tk, None)
-            return res
-        if s is None or n == 0:
-            e = torch.empty(0, self.gpt.num_vq, dtype=torch.long, device=self.gpt.device)
-            res = SessionResult(ticket=tk, utt_id=u["utt_id"], ids=e, hiddens=self.hid[0, :0].clone() if self.hid is not None else None,
-                                logprobs=self.lps[0, 0, :0].clone() if self.lps is not None else None,
-                                sampled_logprobs=self.lps[1, 0, :0].clone() if self.lps is not None else None, finished_by_eos=eos, cancelled=cancelled,
-                                attempt=u["attempt"])
-            if s is not None and self.lps is not None and eos:
-                res.final_logprobs = self.lps[:, s, 0].clone()
-        else:
-            res = SessionResult(ticket=tk, utt_id=u["utt_id"], ids=self.ids[s, :n].to(torch.long), hiddens=self.hid[s, :n].clone() if self.hid is not None else None,
-                                logprobs=self.lps[0, s, :n].clone() if self.lps is not None else None,
-                                sampled_logprobs=self.lps[1, s, :n].clone() if self.lps is not None else None,
-                                final_logprobs=self.lps[:, s, n].clone() if (self.lps is not None and eos and n < self.max_new) else None,
-                                finished_by_eos=eos, cancelled=cancelled, attempt=u["attempt"])
-        self.book.release(tk)
-        self._req.pop(tk, None)
         return res
 
     # -- the loop ---------------------------------------------------------------------------------------
@@ -925,27 +978,25 @@ class DecodeSession:
 
     @torch.no_grad()
     def step(self) -> List[SessionResult]:
-        """One _step(); the sample windows it made due for streaming utterances wait in take_windows() (replaced by the next step)."""
-        out = self._step()
+        """One chunk of decode steps is launched and the previous chunk's row report is read (_advance), then the batch is rebalanced (_rebalance).  Returns the
+        utterances that ended; the sample windows the step made due for streaming utterances wait in take_windows() (replaced by the next step)."""
+        out = self._advance()
+        self._rebalance()
         self._wins = self._build_windows(self.book.take_windows(), out)
         return out
 
-    def _step(self) -> List[SessionResult]:
-        """One chunk of decode steps is launched, the previous chunk's row report is read (two chunks stay enqueued, as in generate_many): finished utterances
-        are delivered, first-token-EOS ones queued again with their next attempt, and the batch is rebalanced -- queued utterances into free rows, then into
-        rows the batch grows by, else a compaction.  With nothing live and nothing queued nothing is launched."""
+    def _advance(self) -> List[SessionResult]:
+        """Phase 1 of a step: pending cancels reach the device, one chunk of decode steps is launched with its row report behind it, and the report of the chunk
+        before is read (two chunks stay enqueued): finished utterances are delivered, first-token-EOS ones queued again with their next attempt.  With nothing
+        live nothing is launched.  `live` = [(ticket, tokens so far)] of the rows that report showed decoding (empty: no report was read)."""
         self._check_open()
         g, lib, h, book = self.gpt, self.gpt._lib, self.gpt._h, self.book
         out = [self._result(tk, 0, 1, True) for tk in book.take_dropped()]
-        if book.idle():
+        self.live = []
+        if not book.begun or book.idle():
             return out
         with torch.cuda.device(g.device):
             st = g._stream()
-            if not book.begun:
-                plan = book.plan()
-                if plan.begin:
-                    self._begin(plan.begin, st)
-                return out
             rows = book.cancel_rows()
             if rows:
                 arr = np.ascontiguousarray(rows, dtype=np.int32)
@@ -964,17 +1015,30 @@ class DecodeSession:
                     lay = self._layouts[slot]
                     states = self._pins[slot][:2 * len(lay)].view(-1, 2).tolist()
                     out += [self._result(*r) for r in book.report(lay, states)]
-            plan = book.plan()
+                    self.live = book.live
+        return out
+
+    def _rebalance(self) -> None:
+        """Phase 2 of a step, SessionBook.plan carried out: the state's first seating, or queued utterances into free rows and into rows the batch grows by, else
+        a compaction.  (A request's consumer works between the phases: its vocoder launches stay in front of the admission's prompt pass on the stream.)"""
+        g, lib, h, book = self.gpt, self.gpt._lib, self.gpt._h, self.book
+        plan = book.plan()
+        if not plan:
+            return
+        with torch.cuda.device(g.device):
+            st = g._stream()
+            if plan.begin:
+                self._seat(plan.begin, st, begin=True)
             if plan.grow:
                 _lib.check(lib.ctts_gpt_grow(h, plan.grow, st), "grow")
             if plan.admit:
-                self._admit(plan.admit, st)
+                self._seat(plan.admit, st)
             if plan.compact is not None:
                 karr = np.ascontiguousarray(plan.compact, dtype=np.int32)
                 _lib.check(lib.ctts_gpt_compact(h, karr.ctypes.data_as(C.c_void_p), int(karr.size), st), "compact")
+                self.compactions.append((self.launched, len(plan.compact)))
             if plan.grow or plan.compact is not None:
                 self.batch_trace.append((self.launched, len(book.book.row_tk)))
-        return out
 
     def drain(self) -> List[SessionResult]:
         """steps until nothing is queued or live; everything delivered on the way"""
@@ -997,17 +1061,49 @@ class DecodeSession:
                     steps, alld = C.c_int32(0), C.c_int32(0)
                     _lib.check(g._lib.ctts_gpt_progress(g._h, C.byref(steps), C.byref(alld), st), "progress")
                     g.saturations = g._report_saturations(g._h, st, "session")
-                    if self._adapters:
-                        g.set_row_adapters(None)
         finally:
-            if g._busy_token.owner is self:
-                g._busy_token.owner = None
+            self._hold.release()
 
 
 class _BusyToken:
     """One generate() at a time per KV cache: shared by every engine bound to the same KV tensor (LoRA-merged siblings, with_lora)."""
     def __init__(self):
         self.owner = None
+
+
+class EngineHold:
+    """The busy token of a loaded engine, taken for one call or one session (GPT._hold) -- engine state (batch, step counters, noise staging ring) and the KV cache,
+    shared with LoRA-merged sibling engines, belong to ONE of them at a time.  A context manager; release() hands the token back together with the per-call
+    engine settings named in `resets`: "share" (shared prompt passes: a call that failed before its begin leaves nothing pending), "adapters", "sampling" (a
+    later plain call takes its own values)."""
+
+    def __init__(self, gpt: "GPT", busy: str, resets=()):
+        if not gpt._finalized:
+            raise _lib.HipBackendError("weights not loaded")
+        if gpt._busy_token.owner is not None:
+            raise _lib.HipBackendError(busy)
+        self.gpt, self.resets = gpt, {r for r in resets if r}
+        gpt._busy_token.owner = gpt
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+        return False
+
+    def release(self) -> None:
+        g = self.gpt
+        try:
+            if getattr(g, "_h", None) and g._h.value:
+                if "share" in self.resets:
+                    g._lib.ctts_gpt_share_prompts(g._h, 0, None, 0)
+                if "adapters" in self.resets:
+                    g.set_row_adapters(None)
+                if "sampling" in self.resets:
+                    g._lib.ctts_gpt_set_row_sampling(g._h, None, 0)
+        finally:
+            g._busy_token.owner = None
 
 
 class GPT:
@@ -1261,6 +1357,10 @@ class GPT:
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _hold(self, busy: str, *resets) -> EngineHold:
+        """Takes the engine for one call (`with`) or one session; `busy` is the refusal while another holds it, `resets` see EngineHold"""
+        return EngineHold(self, busy, resets)
+
     @torch.no_grad()
     def _report_saturations(self, h, st, what: str) -> int:
         """fp16 stores of unbounded values saturate instead of overflowing to inf (fp16 engines: SwiGLU outputs, packed residual; fp32 engines:
@@ -1317,26 +1417,13 @@ class GPT:
         top_P, top_K, repetition_penalty, min_new_token (ctts_gpt_set_row_sampling; code mode only).  eos, max_new_token and the F8 threshold stay per call."""
         if return_attn:
             raise _lib.HipBackendError("return_attn=True is unsupported (the reference's eager attention path is broken, SURVEY F2)")
-        if not self._finalized:
-            raise _lib.HipBackendError("weights not loaded")
         if return_logprobs and infer_text:
             raise _lib.HipBackendError("return_logprobs: the refine-text pass (infer_text=True) returns no log-probs; code mode only")
-        if self._busy_token.owner is not None:
-            # engine state (batch, step counters, noise staging ring) and the KV cache -- shared with LoRA-merged sibling engines -- belong
-            # to ONE generate() at a time
-            raise _lib.HipBackendError("GPT.generate is already running on this engine (or on an engine sharing its KV cache): exhaust or close "
-                                       "the previous generator first")
-        self._busy_token.owner = self
-        try:
+        with self._hold("GPT.generate is already running on this engine (or on an engine sharing its KV cache): exhaust or close the previous generator first",
+                        prompt_of is not None and "share", sampling_per_row is not None and "sampling"):
             yield from self._generate(emb, inputs_ids, temperature, eos_token, attention_mask, max_new_token, min_new_token, logits_warpers,
                                       logits_processors, infer_text, return_hidden, stream, ensure_non_empty, stream_batch, context, noise, seed,
                                       max_restarts, utt_ids, max_new_tokens_per_row, sampling_per_row, bool(return_logprobs), prompt_of)
-        finally:
-            if prompt_of is not None:
-                self._lib.ctts_gpt_share_prompts(self._h, 0, None, 0)         # (a call that failed before its begin leaves nothing pending)
-            if sampling_per_row is not None:
-                self._lib.ctts_gpt_set_row_sampling(self._h, None, 0)      # a later plain call takes its own values
-            self._busy_token.owner = None
 
     def _generate(self, emb, inputs_ids, temperature, eos_token, attention_mask, max_new_token, min_new_token, logits_warpers, logits_processors,
                   infer_text, return_hidden, stream, ensure_non_empty, stream_batch, context, noise, seed, max_restarts, utt_ids=None,
@@ -1367,13 +1454,8 @@ class GPT:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (isinstance(noise, str) and noise == "device") else 0
         mask = torch.ones(int(inputs_ids.shape[0]), T, dtype=torch.int32, device=dev) if attention_mask is None else attention_mask.to(dev).to(torch.int32).contiguous()
         emb = emb.to(dev, dtype=torch.float32).contiguous()
-        # uninitialised: only [b, :end_idx[b]] is ever read, and every one of those rows was written by the step that produced it (the
-        # default max_new_token = 2048 made this a 201 MB zero-fill per call at batch 32)
-        ids = torch.empty(B, max_new_token, NVQ, dtype=torch.int32, device=dev)
-        hid = torch.empty(B, max_new_token, H, dtype=torch.float32, device=dev) if return_hidden else None
-        lps = torch.empty(2, B, max_new_token, NVQ, dtype=torch.float32, device=dev) if return_logprobs else None      # (raw, sampled), laid out like ids
-        finish = torch.zeros(B, dtype=torch.int32, device=dev)
-        end_idx = torch.zeros(B, dtype=torch.int32, device=dev)
+        out = OutBuffers(B, max_new_token, self, return_hidden, return_logprobs)
+        finish = out.finish
         n_draws = max_new_token + max_restarts
         qbuf = None
         rng_states = []
@@ -1393,10 +1475,7 @@ class GPT:
         if row_limits is not None:
             lim_arr = np.ascontiguousarray([int(u) for u in row_limits], dtype=np.int32)
             assert lim_arr.size == B, "max_new_tokens_per_row: one limit per sequence"
-        io = _lib.GenIO(ids=ids.data_ptr(), hiddens=hid.data_ptr() if hid is not None else None, finish=finish.data_ptr(),
-                        end_idx=end_idx.data_ptr(), noise=qbuf.data_ptr() if qbuf is not None else None, n_draws=n_draws,
-                        seed=int(seed), utt_ids=uid_arr.ctypes.data if uid_arr is not None else None,
-                        row_limits=lim_arr.ctypes.data if lim_arr is not None else None)
+        io = out.io(n_draws, seed, uid_arr, lim_arr, qbuf)
         drawn = 0
         stage_cap = max(int(self.chunk_steps), int(stream_batch) if stream else 1, 1)
         stage = self._staging(B * rows_per_seq, V, stage_cap) if (isinstance(noise, str) and noise == "torch") else None
@@ -1446,8 +1525,8 @@ class GPT:
                 _lib.check(lib.ctts_gpt_share_prompts(h, B, share.ctypes.data_as(C.c_void_p), n_prompts), "share_prompts")
                 self.shared_prompts.append((B, n_prompts))
             _lib.check(lib.ctts_gpt_begin(h, B, T, mask.data_ptr(), C.byref(sc), C.byref(io), st), "begin")
-            if lps is not None:
-                _lib.check(lib.ctts_gpt_set_logprob_out(h, lps[0].data_ptr(), lps[1].data_ptr(), st), "set_logprob_out")
+            if out.lps is not None:
+                _lib.check(lib.ctts_gpt_set_logprob_out(h, out.lps[0].data_ptr(), out.lps[1].data_ptr(), st), "set_logprob_out")
             _lib.check(lib.ctts_gpt_prefill(h, emb.data_ptr(), st), "prefill")
             tick("begin+prefill")
             steps, alld = C.c_int32(0), C.c_int32(0)
@@ -1481,7 +1560,7 @@ class GPT:
                     if steps.value == prev and not alld.value:
                         raise _lib.HipBackendError("decode made no progress (device state inconsistent)")
                     if steps.value % chunk == 0 and steps.value > prev:
-                        yield self._outputs(ids, hid, end_idx, infer_text, lps, finish)
+                        yield self._outputs(out, infer_text)
             else:
                 # one chunk stays in flight while the previous chunk's progress words are inspected (no GPU bubble at the
                 # poll); steps launched after every sequence finished exit at their first instruction on the device
@@ -1542,9 +1621,9 @@ class GPT:
                 tick("final_progress")
             self._restore_rng(rng_states, used_draws)
             self.saturations = self._report_saturations(h, st, "generate()")
-            out = self._outputs(ids, hid, end_idx, infer_text, lps, finish)
+            res = self._outputs(out, infer_text)
             tick("outputs")
-            yield out
+            yield res
 
     # -- continuous batching: more utterances than decode rows (no counterpart in the reference) ------------------------------------
     @torch.no_grad()
@@ -1595,46 +1674,35 @@ class GPT:
         hiddens[:n] or None)]) for the utterances still decoding -- the first n tokens of an utterance are final once reported.
         `return_logprobs=True`: every tuple of either kind gains a last element, a GenerationOutputs of that one utterance's tokens so far (ids, hiddens,
         logprobs, sampled_logprobs, final_logprobs: lists of one), and the returned GenerationOutputs carries the three fields for all N."""
-        if not self._finalized:
-            raise _lib.HipBackendError("weights not loaded")
         if return_logprobs and infer_text:
             raise _lib.HipBackendError("return_logprobs: the refine-text pass (infer_text=True) returns no log-probs; code mode only")
-        if self._busy_token.owner is not None:
-            raise _lib.HipBackendError("GPT.generate is already running on this engine (or on an engine sharing its KV cache)")
-        self._busy_token.owner = self
-        try:
+        with self._hold("GPT.generate is already running on this engine (or on an engine sharing its KV cache)", prompt_of is not None and "share",
+                        adapter_slots is not None and "adapters", sampling_per_row is not None and "sampling"):
             return (yield from self._generate_many(emb, inputs_ids, temperature, eos_token, attention_mask, int(max_new_token), min_new_token, logits_warpers,
                                                    logits_processors, return_hidden, ensure_non_empty, context or Context(), seed, max_restarts, utt_ids,
                                                    max_new_tokens_per_row, rows, admit_min, bool(infer_text), bool(progress), adapter_slots,
                                                    sampling_per_row, bool(return_logprobs), prompt_of))
-        finally:
-            if prompt_of is not None:
-                self._lib.ctts_gpt_share_prompts(self._h, 0, None, 0)
-            if adapter_slots is not None:
-                self.set_row_adapters(None)
-            if sampling_per_row is not None:
-                self._lib.ctts_gpt_set_row_sampling(self._h, None, 0)
-            self._busy_token.owner = None
 
     def _generate_many(self, emb, inputs_ids, temperature, eos_token, attention_mask, max_new_token, min_new_token, logits_warpers, logits_processors,
                        return_hidden, ensure_non_empty, context, seed, max_restarts, utt_ids, row_limits, rows, admit_min, infer_text=False, progress=False,
                        adapter_slots=None, sampling_per_row=None, return_logprobs=False, prompt_of=None):
-        lib, h, dev = self._lib, self._h, self.device
+        """The request as a client of the DecodeSession driver: prepares the utterances, submits them in their order of service (position j of that order is
+        ticket j and output slot j) and translates what the driver delivers into generate_many_iter's events"""
+        dev = self.device
         N, T = int(inputs_ids.shape[0]), int(inputs_ids.shape[1])
         pof = None                                # shared prompt passes: utterance -> row of emb / mask
         if prompt_of is not None:
             prompt_groups(prompt_of, N, adapter_slots, infer_text=infer_text)      # (refusals)
             pof = [int(p) for p in prompt_of]
             n_prompts, N = N, len(pof)
-        H, NVQ = self.model_dim, self.num_vq
+        NVQ = self.num_vq
         R = min(N, int(rows) if rows else self.max_batch, self.max_batch)
         sc = sampler_cfg_from_objects(temperature, int(eos_token), max_new_token, min_new_token, logits_warpers, logits_processors, NVQ, infer_text=infer_text)
-        knobs = list(row_sampling_array(sc, sampling_per_row, N, NVQ, infer_text)) if sampling_per_row is not None else None
+        knobs = list(row_sampling_array(sc, sampling_per_row, N, NVQ, infer_text)) if sampling_per_row is not None else [None] * N
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        mask = torch.ones(int(inputs_ids.shape[0]), T, dtype=torch.int32, device=dev) if attention_mask is None else attention_mask.to(dev).to(torch.int32).contiguous()
+        lens = [T] * int(inputs_ids.shape[0]) if attention_mask is None else attention_mask.to(torch.int32).sum(1).cpu().tolist()
         emb = emb.to(dev, dtype=torch.float32).contiguous()
-        lens = mask.sum(1).cpu().tolist()
         if pof is not None:
             lens = [lens[p] for p in pof]
         if max(lens) + max_new_token > self.max_seq:
@@ -1643,165 +1711,52 @@ class GPT:
         uids = [int(u) for u in utt_ids] if utt_ids is not None else list(range(N))
         lims = [min(max(int(v), 1), max_new_token) for v in row_limits] if row_limits is not None else [max_new_token] * N
         assert len(uids) == N and len(lims) == N
-        slots = None
+        slots = [None] * N
         if adapter_slots is not None:
             slots = [-1 if a is None or int(a) < 0 else int(a) for a in adapter_slots]
             if len(slots) != N or infer_text:
                 raise _lib.HipBackendError(f"adapter_slots: {len(slots)} entries for {N} utterances (code mode only)")
-        ids = torch.empty(N, max_new_token, NVQ, dtype=torch.int32, device=dev)
-        hid = torch.empty(N, max_new_token, H, dtype=torch.float32, device=dev) if return_hidden else None
-        lps = torch.empty(2, N, max_new_token, NVQ, dtype=torch.float32, device=dev) if return_logprobs else None       # (raw, sampled), indexed like ids
-        finish = torch.zeros(N, dtype=torch.int32, device=dev)
-        end_idx = torch.zeros(N, dtype=torch.int32, device=dev)
         admit_min = max(1, int(admit_min) if admit_min else R // 8)
-        chunk = max(4, min(self.chunk_steps, self.compact_chunk))
-        self.compactions, self.admissions, self.shared_prompts = [], [], []
-
-        def prompts_of(idx):
-            """left-padded prompts of the utterances `idx`, trimmed to the longest of them.  Shared prompt passes: one row per prompt the utterances name, and the
-            engine is told which of them each utterance has (for the begin / admit call that follows)"""
-            Ta = max(1, max(lens[u] for u in idx))
-            sel = idx
-            if pof is not None:
-                sel, local, _ = prompt_groups(pof, n_prompts, slots, subset=idx)
-                if len(sel) < len(idx):
-                    arr = np.ascontiguousarray(local, dtype=np.int32)
-                    _lib.check(lib.ctts_gpt_share_prompts(h, len(idx), arr.ctypes.data_as(C.c_void_p), len(sel)), "share_prompts")
-                self.shared_prompts.append((len(idx), len(sel)))
-            ii = torch.as_tensor(sel, dtype=torch.long, device=dev)
-            return Ta, emb.index_select(0, ii)[:, T - Ta:].contiguous(), mask.index_select(0, ii)[:, T - Ta:].contiguous()
-
+        # Order of service: longest expected utterance first (LPT list scheduling) -- the request ends when its LAST row does, and a long utterance admitted late
+        # decodes alone on a 32-row engine (the 256-utterance request: 2905 steps launched for 2518 ideal ones in arrival order).  The expectation is the row's own
+        # token limit where the caller gave one, else the prompt length (longer text, longer audio).  Results do not depend on the order: every output is indexed
+        # by utterance and the device noise is keyed by the utterance id.  Default: arrival order ("fifo"): a streaming caller wants its first utterance first.
+        if getattr(self, "schedule", "fifo") == "longest_first":      # (ChatTTSPlusPipeline's throughput mode orders the request itself; direct callers opt in)
+            back = sorted(range(N), key=(lambda u: (-lims[u], u)) if row_limits is not None else (lambda u: (-lens[u], u)))
+        else:
+            back = list(range(N))                                  # ticket (= output slot) -> utterance index: every index handed back is mapped through it
         with torch.cuda.device(dev):
-            st = self._stream()
-            # Order of service: longest expected utterance first (LPT list scheduling) -- the request ends when its LAST row does, and a long utterance admitted late
-            # decodes alone on a 32-row engine (the 256-utterance request: 2905 steps launched for 2518 ideal ones in arrival order).  The expectation is the row's own
-            # token limit where the caller gave one, else the prompt length (longer text, longer audio).  Results do not depend on the order: every output is indexed
-            # by utterance and the device noise is keyed by the utterance id.  Default: arrival order ("fifo"): a streaming caller wants its first utterance first.
-            if getattr(self, "schedule", "fifo") == "longest_first":      # (ChatTTSPlusPipeline's throughput mode orders the request itself; direct callers opt in)
-                order = sorted(range(N), key=(lambda u: (-lims[u], u)) if row_limits is not None else (lambda u: (-lens[u], u)))
-            else:
-                order = list(range(N))
-            back = list(range(N))                                  # position in the buffers below -> utterance index
-            if order != back:
-                # ctts_gpt_begin writes row r's outputs at index r: the request is served permuted (position j holds utterance order[j]) and every index
-                # handed back is mapped through `back` -- seating utterance order[r] in row r had them written at r and read at order[r]
-                if pof is None:
-                    pt = torch.as_tensor(order, dtype=torch.long, device=dev)
-                    emb, mask = emb.index_select(0, pt), mask.index_select(0, pt)
-                else:                                              # (emb / mask stay indexed by prompt)
-                    pof = [pof[u] for u in order]
-                lens, uids, lims = [lens[u] for u in order], [uids[u] for u in order], [lims[u] for u in order]
-                if slots is not None:
-                    slots = [slots[u] for u in order]
-                if knobs is not None:
-                    knobs = [knobs[u] for u in order]
-                back, order = order, list(range(N))
-            first = order[:R]
-            Ta, emb_a, mask_a = prompts_of(first)
-            uid_arr = np.ascontiguousarray([uids[u] for u in first], dtype=np.uint64)
-            lim_arr = np.ascontiguousarray([lims[u] for u in first], dtype=np.int32)
-            io = _lib.GenIO(ids=ids.data_ptr(), hiddens=hid.data_ptr() if hid is not None else None, finish=finish.data_ptr(),
-                            end_idx=end_idx.data_ptr(), noise=None, n_draws=max_new_token, seed=int(seed), utt_ids=uid_arr.ctypes.data,
-                            row_limits=lim_arr.ctypes.data)
-            if slots is not None:
-                self.set_row_adapters([slots[u] for u in first])
-            if knobs is not None:
-                _lib.check(lib.ctts_gpt_set_row_sampling(h, (_lib.RowSampling * R)(*[knobs[u] for u in first]), R), "set_row_sampling")
-            _lib.check(lib.ctts_gpt_begin(h, R, Ta, mask_a.data_ptr(), C.byref(sc), C.byref(io), st), "begin")
-            if lps is not None:
-                _lib.check(lib.ctts_gpt_set_logprob_out(h, lps[0].data_ptr(), lps[1].data_ptr(), st), "set_logprob_out")
-            _lib.check(lib.ctts_gpt_prefill(h, emb_a.data_ptr(), st), "prefill")
-            _lib.check(lib.ctts_gpt_sample(h, st), "sample")
-            queue = [(u, 0) for u in order[R:]]                    # (utterance, regenerate attempt)
-            book = RowBook()
-            for r in range(R):
-                book.seat(r, first[r])
-            n_done, since_free = 0, 0
-            pins = [torch.zeros(2 * R, dtype=torch.int32).pin_memory() for _ in range(2)]
-            evs = [torch.cuda.Event() for _ in range(2)]
-            layouts = [None, None]
-            pending, n_chunks, launched = [], 0, 1
+            ses = DecodeSession(self, sc, seed, R, N, return_hidden, return_logprobs, ensure_non_empty, max_restarts, own_slots=True, admit_min=admit_min,
+                                share=None if pof is None else ([pof[u] for u in back], n_prompts, [slots[u] for u in back] if adapter_slots is not None else None))
+            self.admissions, self.compactions, self.shared_prompts = ses.admissions, ses.compactions, ses.shared_prompts
+            for u in back:
+                ses._enqueue(emb[u if pof is None else pof[u]], lens[u], uids[u], lims[u], knobs[u], slots[u])
 
-            def one(u, n, eos):
-                """GenerationOutputs of utterance (buffer position) u alone: its first n tokens; `eos`: the step after them sampled EOS"""
-                fl = lps[:, u, n].clone() if (eos and n < max_new_token) else None
-                return GenerationOutputs(ids=[ids[u, :n].to(torch.long)], attentions=[], hiddens=[hid[u, :n]] if hid is not None else [],
-                                         logprobs=[lps[0, u, :n]], sampled_logprobs=[lps[1, u, :n]], final_logprobs=[fl])
+            def event(r, n=None):
+                """one utterance of a yielded list: (index[, tokens so far], ids, hiddens[, its GenerationOutputs so far])"""
+                one = (GenerationOutputs(ids=[r.ids], attentions=[], hiddens=[r.hiddens] if r.hiddens is not None else [], logprobs=[r.logprobs],
+                                         sampled_logprobs=[r.sampled_logprobs], final_logprobs=[r.final_logprobs]),) if return_logprobs else ()
+                return (back[r.ticket],) + (() if n is None else (n,)) + (r.ids, r.hiddens) + one
 
+            n_done = 0
+            ses._rebalance()                                       # the first R utterances begin
             while n_done < N and not context.get():
-                while len(pending) < 2:
-                    _lib.check(lib.ctts_gpt_decode(h, chunk, 1 if self.use_graph else 0, st), "decode")
-                    launched += chunk
-                    slot = n_chunks % 2
-                    n_chunks += 1
-                    _lib.check(lib.ctts_gpt_rows_enqueue(h, pins[slot].data_ptr(), st), "rows_enqueue")
-                    layouts[slot] = book.layout()
-                    evs[slot].record(torch.cuda.current_stream(dev))
-                    pending.append(slot)
-                slot = pending.pop(0)
-                evs[slot].synchronize()
-                lay = layouts[slot]
-                states = pins[slot][:2 * len(lay)].view(-1, 2).tolist()
-                if progress:
-                    live = [(book.tickets[tk][0], int(end)) for tk, (fin, end) in zip(lay, states) if tk is not None and tk in book.tickets and not fin and end > 0]
-                    if live:
-                        yield ("progress", [(back[u], n, ids[u, :n, 0].to(torch.long) if infer_text else ids[u, :n].to(torch.long), hid[u, :n] if hid is not None else None)
-                                            + ((one(u, n, False),) if lps is not None else ()) for u, n in live])
-                # (which of the rows that finished did so by EOS: read before report() retires their tickets)
-                eos_of = {book.tickets[tk][0]: bool(fin & 2) for tk, (fin, end) in zip(lay, states) if fin and tk in book.tickets} if lps is not None else {}
-                finished_now, again = book.report(lay, states, ensure_non_empty, max_restarts)
-                queue = again + queue                              # first token was EOS (gpt.py:496-525): next noise attempt, ahead of the queue
-                n_done += len(finished_now)
-                if finished_now:
-                    yield [(back[u], ids[u, :n, 0].to(torch.long) if infer_text else ids[u, :n].to(torch.long), hid[u, :n] if hid is not None else None)
-                           + ((one(u, n, eos_of.get(u, False)),) if lps is not None else ()) for u, n in finished_now]
-                free = book.free_rows()
-                since_free = since_free + 1 if free else 0
-                if queue and free and (len(free) >= min(admit_min, len(queue)) or since_free >= 4 or len(free) == len(book.row_tk)):
-                    k = min(len(free), len(queue))
-                    take, queue = queue[:k], queue[k:]
-                    idx = [u for u, _ in take]
-                    Ta, emb_a, mask_a = prompts_of(idx)
-                    rows_arr = np.ascontiguousarray(free[:k], dtype=np.int32)
-                    uid_arr = np.ascontiguousarray([uids[u] for u in idx], dtype=np.uint64)
-                    lim_arr = np.ascontiguousarray([lims[u] for u in idx], dtype=np.int32)
-                    out_arr = np.ascontiguousarray(idx, dtype=np.int32)
-                    att_arr = np.ascontiguousarray([a for _, a in take], dtype=np.int32)
-                    if slots is not None:
-                        sl_arr = np.ascontiguousarray([slots[u] for u in idx], dtype=np.int32)
-                        _lib.check(lib.ctts_gpt_admit_adapters(h, k, rows_arr.ctypes.data_as(C.c_void_p), sl_arr.ctypes.data_as(C.c_void_p), st), "admit_adapters")
-                    if knobs is not None:         # (re-admissions of ensure_non_empty included: the utterance keeps its own knobs)
-                        _lib.check(lib.ctts_gpt_admit_sampling(h, k, rows_arr.ctypes.data_as(C.c_void_p), (_lib.RowSampling * k)(*[knobs[u] for u in idx]), st),
-                                   "admit_sampling")
-                    _lib.check(lib.ctts_gpt_admit(h, k, rows_arr.ctypes.data_as(C.c_void_p), Ta, mask_a.data_ptr(), emb_a.data_ptr(),
-                                                  uid_arr.ctypes.data_as(C.c_void_p), lim_arr.ctypes.data_as(C.c_void_p),
-                                                  out_arr.ctypes.data_as(C.c_void_p), att_arr.ctypes.data_as(C.c_void_p), st), "admit")
-                    for r, (u, a) in zip(free[:k], take):
-                        book.seat(r, u, a)
-                    self.admissions.append((launched, k))
-                    since_free = 0
-                elif not queue and self.compact and len(book.row_tk) >= 2:
-                    live = book.live_rows()
-                    target = compact_size(len(live))
-                    if live and target < len(book.row_tk):
-                        keep = sorted(live + book.free_rows()[:target - len(live)])
-                        karr = np.ascontiguousarray(keep, dtype=np.int32)
-                        _lib.check(lib.ctts_gpt_compact(h, karr.ctypes.data_as(C.c_void_p), int(karr.size), st), "compact")
-                        book.compact(keep)
-                        self.compactions.append((launched, len(book.row_tk)))
+                done = ses._advance()
+                live = [event(ses._result(tk, n, final=False), n) for tk, n in ses.live if n > 0] if progress else []
+                if live:
+                    yield ("progress", live)
+                n_done += len(done)
+                if done:
+                    yield [event(r) for r in done]
+                ses._rebalance()
+            st = self._stream()
             torch.cuda.current_stream(dev).synchronize()
             # the device give-up word (a persistent launch's bounded wait ran out, or a projection tile never got its low-rank term): every later launch of the
             # request was a no-op and the sampler kept drawing from stale rows -- an error, not audio (ctts_gpt_progress raises it, as in generate())
             steps, alld = C.c_int32(0), C.c_int32(0)
-            _lib.check(lib.ctts_gpt_progress(h, C.byref(steps), C.byref(alld), st), "progress")
-            self.saturations = self._report_saturations(h, st, "generate_many()")
-            if back != order:                                      # input order again
-                inv = torch.as_tensor(np.argsort(np.asarray(back)), dtype=torch.long, device=dev)
-                ids, end_idx = ids.index_select(0, inv), end_idx.index_select(0, inv)
-                hid = hid.index_select(0, inv) if hid is not None else None
-                lps = lps.index_select(1, inv) if lps is not None else None
-                finish = finish.index_select(0, inv)
-            return self._outputs(ids, hid, end_idx, infer_text, lps, finish)
+            _lib.check(self._lib.ctts_gpt_progress(self._h, C.byref(steps), C.byref(alld), st), "progress")
+            self.saturations = self._report_saturations(self._h, st, "generate_many()")
+            return self._outputs(ses.out, infer_text, order=np.argsort(np.asarray(back)).tolist())      # input order again
 
     # -- serving session (ctts_gpt_grow / ctts_gpt_cancel) ------------------------------------------------------------------------
     def open_session(self, temperature, eos_token, max_new_token, min_new_token=0, logits_warpers=[], logits_processors=[], return_hidden=False,
@@ -1816,8 +1771,6 @@ class GPT:
         pass (infer_text, refine_text_only, params_refine_text).  The refine-text pass itself is served INSIDE the session: `text_rows` = a dict (or an object with
         these attributes) of temperature, top_P, top_K, eos_token ([Ebreak]), max_new_token (<= the code rows'), min_new_token makes submit(mode="text") seat
         refine-text utterances as text rows beside the code rows of the one decode batch (ctts_gpt_enable_text_rows); their results carry ids [n]."""
-        if not self._finalized:
-            raise _lib.HipBackendError("weights not loaded")
         refuse_out_of_scope(out_of_scope, "use generate() / generate_many() / infer() for it")
         rows = self.max_batch if rows is None else int(rows)
         if not (1 <= rows <= self.max_batch):
@@ -1825,15 +1778,18 @@ class GPT:
         out_slots = 2 * rows if out_slots is None else int(out_slots)
         if out_slots < 1:
             raise _lib.HipBackendError(f"open_session: out_slots={out_slots} (at least one)")
-        if self._busy_token.owner is not None:
-            raise _lib.HipBackendError("GPT.open_session: GPT.generate is already running on this engine (or on an engine sharing its KV cache): exhaust or close "
-                                       "the previous generator / session first")
         sc = sampler_cfg_from_objects(temperature, int(eos_token), int(max_new_token), min_new_token, logits_warpers, logits_processors, self.num_vq)
         text_sc = text_rows_cfg(text_rows, self.num_vq) if text_rows is not None else None
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        with torch.cuda.device(self.device):
-            ses = DecodeSession(self, sc, seed, rows, out_slots, bool(return_hidden), bool(return_logprobs), bool(ensure_non_empty), text_sc=text_sc)
+        hold = self._hold("GPT.open_session: GPT.generate is already running on this engine (or on an engine sharing its KV cache): exhaust or close "
+                          "the previous generator / session first")
+        try:
+            with torch.cuda.device(self.device):
+                ses = DecodeSession(self, sc, seed, rows, out_slots, bool(return_hidden), bool(return_logprobs), bool(ensure_non_empty), text_sc=text_sc, hold=hold)
+        except BaseException:
+            hold.release()
+            raise
         self._busy_token.owner = ses
         return ses
 
@@ -1845,11 +1801,11 @@ class GPT:
         is predicted by row T - n_b + j (score_inputs builds all four from a prompt and codes).  Positions are cumsum(mask) - 1 as in generate(), so a
         sequence scores the same alone as inside a padded batch.  Per-utterance adapters (set_row_adapters) apply per sequence.  Ends nothing a caller
         holds: refused while a generate() generator is live on this engine or on one sharing its KV cache.  Returns ScoreOutputs on the CPU."""
-        if not self._finalized:
-            raise _lib.HipBackendError("weights not loaded")
-        if self._busy_token.owner is not None:
-            raise _lib.HipBackendError("GPT.score: a generate() generator is live on this engine (or on an engine sharing its KV cache), whose KV lanes "
-                                       "scoring would overwrite: exhaust or close it first")
+        with self._hold("GPT.score: a generate() generator is live on this engine (or on an engine sharing its KV cache), whose KV lanes "
+                        "scoring would overwrite: exhaust or close it first"):
+            return self._score(emb, attention_mask, targets, n_targets)
+
+    def _score(self, emb, attention_mask, targets, n_targets) -> ScoreOutputs:
         dev = self.device
         emb = emb.to(dev, dtype=torch.float32).contiguous()
         if emb.dim() != 3 or emb.shape[2] != self.model_dim:
@@ -1903,20 +1859,16 @@ class GPT:
         if states and used < len(states):
             torch.random.set_rng_state(states[used])
 
-    def _outputs(self, ids, hid, end_idx, infer_text=False, lps=None, finish=None) -> GenerationOutputs:
-        n = end_idx.cpu().tolist()
-        out_ids = [ids[b, :n[b]].to(torch.long) for b in range(len(n))]                # gpt.py:295-297
-        if infer_text:
-            out_ids = [i[:, 0] for i in out_ids]                                        # gpt.py:298-299
-        out_h = [hid[b, :n[b]] for b in range(len(n))] if hid is not None else []     # gpt.py:301-305
-        if lps is None:
-            return GenerationOutputs(ids=out_ids, attentions=[], hiddens=out_h)
-        # the step that sampled EOS wrote its log-probs at index end_idx (its ids are not part of the sequence); a sequence that ended by its limit has none
-        eos = finish.cpu().tolist()
-        cap = int(lps.shape[2])
-        return GenerationOutputs(ids=out_ids, attentions=[], hiddens=out_h, logprobs=[lps[0, b, :n[b]] for b in range(len(n))],
-                                 sampled_logprobs=[lps[1, b, :n[b]] for b in range(len(n))],
-                                 final_logprobs=[lps[:, b, n[b]].clone() if (eos[b] and n[b] < cap) else None for b in range(len(n))])
+    @staticmethod
+    def _outputs(out: OutBuffers, infer_text: bool = False, order=None) -> GenerationOutputs:
+        """All sequences of a generate state (gpt.py:295-305); `order[b]` = the output slot of sequence b (default b).  final_logprobs: where the finish flag is set"""
+        n = out.end_idx.cpu().tolist()
+        eos = out.finish.cpu().tolist() if out.lps is not None else [0] * len(n)
+        rows = [out.take(s, n[s], bool(eos[s]), infer_text) for s in (order if order is not None else range(len(n)))]
+        ids, hid, lp, slp, flp = ([r[i] for r in rows] for i in range(5))
+        if out.lps is None:
+            return GenerationOutputs(ids=ids, attentions=[], hiddens=hid if out.hid is not None else [])
+        return GenerationOutputs(ids=ids, attentions=[], hiddens=hid if out.hid is not None else [], logprobs=lp, sampled_logprobs=slp, final_logprobs=flp)
 
     # -- test hooks ------------------------------------------------------------------------------
     def last_logits(self, B: int) -> torch.Tensor:

@@ -161,6 +161,114 @@ def test_prompt_that_does_not_fit_is_refused_at_submit():
         SessionBook(9, 4, 8, 64, 24)
 
 
+# -- the request policy (generate_many drives the same book): own_slots and admit_min.  The expected plans are worked out by hand from the rule in SessionBook's
+#    docstring: queued utterances are seated only if len(free) >= min(admit_min, queued), since_free >= 4 or len(free) == B.
+def _finish(b, rows, n=5):
+    """rows `rows` report their limit after n tokens; the results are released"""
+    done = b.report(*_states(b, {r: (LIMIT, n) for r in rows}))
+    for t, *_ in done:
+        b.release(t)
+    return [t for t, *_ in done]
+
+
+def test_own_slots_10_tickets_on_4_rows_open_at_4_and_never_grow():
+    b = _book(rows=4, out_slots=10, own_slots=True)
+    tk = [b.submit(8, 100 + i) for i in range(10)]
+    p = b.plan()
+    assert p.begin == [(r, tk[r]) for r in range(4)] and b.lanes == [0, 1, 2, 3] and b.queue == tk[4:]
+    assert not b.plan(), "no free row: the queue waits, the batch does not grow"
+    assert _finish(b, [1]) == [tk[1]]
+    p = b.plan()
+    assert p.admit == [(1, tk[4])] and p.grow == 0 and p.compact is None
+    assert sorted(_finish(b, [0, 2, 3])) == [tk[0], tk[2], tk[3]]
+    p = b.plan()
+    assert p.admit == [(0, tk[5]), (2, tk[6]), (3, tk[7])] and p.grow == 0
+    assert sorted(_finish(b, [0, 1, 2, 3])) == tk[4:8]
+    p = b.plan()
+    assert p.admit == [(0, tk[8]), (1, tk[9])] and p.grow == 0 and len(b.book.row_tk) == 4 and b.queue == []
+    # ticket k wrote slot k throughout, no slot was ever recycled, and only the empty queue lets the batch shrink
+    assert [b.utts[t]["slot"] for t in tk[8:]] == tk[8:] and b.free_slots == []
+    assert b.plan().compact == [0, 1] and b.lanes == [0, 1]
+    assert tk == list(range(10))
+
+
+def test_admit_min_holds_one_free_row_for_three_plans():
+    b = _book(rows=4, out_slots=8, own_slots=True, admit_min=2)
+    tk = [b.submit(8, i) for i in range(8)]
+    assert len(b.plan().begin) == 4
+    _finish(b, [2])
+    for held in range(3):                              # since_free = 1, 2, 3: one free row < min(admit_min = 2, 4 queued)
+        p = b.plan()
+        assert not p and p.compact is None and b.queue == tk[4:], f"plan {held + 1} after the row fell free: held back, empty, no compaction"
+    assert b.plan().admit == [(2, tk[4])], "the fourth plan that saw the free row seats it (since_free = 4)"
+    # two free rows reach admit_min: at once
+    _finish(b, [0, 1])
+    assert b.plan().admit == [(0, tk[5]), (1, tk[6])]
+    # one utterance left in the queue: min(admit_min, queued) = 1, one free row is enough
+    _finish(b, [3])
+    assert b.plan().admit == [(3, tk[7])] and b.queue == []
+    # the counter starts over after an admission: a row that falls free now is held for three plans again
+    b2 = _book(rows=2, out_slots=8, own_slots=True, admit_min=2)
+    t2 = [b2.submit(8, i) for i in range(8)]
+    b2.plan()
+    _finish(b2, [0])
+    assert [bool(b2.plan()) for _ in range(4)] == [False, False, False, True]
+    _finish(b2, [1])
+    assert [bool(b2.plan()) for _ in range(4)] == [False, False, False, True] and b2.queue == t2[4:]
+
+
+def test_admit_min_every_row_free_admits_at_once():
+    b = _book(rows=2, out_slots=6, own_slots=True, admit_min=3)
+    tk = [b.submit(8, i) for i in range(6)]
+    b.plan()
+    _finish(b, [0, 1])                                 # 2 free rows < min(3, 4 queued), first plan to see them -- but they are the whole batch
+    assert b.plan().admit == [(0, tk[2]), (1, tk[3])]
+
+
+def test_own_slots_first_token_eos_returns_to_its_own_slot():
+    b = _book(rows=2, out_slots=4, own_slots=True)
+    tk = [b.submit(8, i) for i in range(4)]
+    b.plan()
+    _finish(b, [1])
+    assert b.plan().admit == [(1, tk[2])]
+    _finish(b, [0])
+    assert b.plan().admit == [(0, tk[3])]             # rows now hold tickets (3, 2): row order and slot order differ
+    assert b.report(*_states(b, {0: (EOS_END, 0), 1: (EOS_END, 0)})) == []
+    assert b.queue == [tk[3], tk[2]], "back at the head of the queue, in row order"
+    assert [b.utts[t]["attempt"] for t in (tk[2], tk[3])] == [1, 1] and b.free_slots == []
+    p = b.plan()
+    assert p.admit == [(0, tk[3]), (1, tk[2])]
+    assert b.utts[tk[3]]["slot"] == tk[3] and b.utts[tk[2]]["slot"] == tk[2], "each returns to its own output index"
+    # the session's recycled slots would have handed them out lowest first
+    s = _book(rows=2, out_slots=4)
+    for i in range(4):
+        s.submit(8, i)
+    s.plan()
+    _finish(s, [1]); s.plan(); _finish(s, [0]); s.plan()
+    s.report(*_states(s, {0: (EOS_END, 0), 1: (EOS_END, 0)}))
+    s.plan()
+    assert (s.utts[3]["slot"], s.utts[2]["slot"]) == (0, 1)
+
+
+def test_report_exposes_the_live_rows_token_counts():
+    b = _book(rows=3, own_slots=True, out_slots=3)
+    tk = [b.submit(8, i) for i in range(3)]
+    b.plan()
+    b.report(*_states(b, {0: (LIVE, 7), 1: (LIMIT, 9), 2: (LIVE, 0)}))
+    assert b.live == [(tk[0], 7), (tk[2], 0)]
+
+
+def test_admit_min_1_without_own_slots_reproduces_every_plan_above(monkeypatch):
+    """the session's policy, named explicitly: the tests of the default book pass unchanged"""
+    import functools
+    import sys
+    monkeypatch.setattr(sys.modules[__name__], "_book", functools.partial(_book, admit_min=1, own_slots=False))
+    for test in (test_first_plan_begins_with_what_is_queued_and_rows_equal_slots, test_grow_admit_then_compact_decisions, test_free_lane_mirror_after_compaction,
+                 test_out_slots_are_recycled_only_after_release, test_cancel_of_queued_and_of_seated_tickets, test_first_token_eos_goes_back_to_the_head_of_the_queue,
+                 test_stale_report_cannot_finish_a_rows_new_occupant, test_prompt_that_does_not_fit_is_refused_at_submit):
+        test()
+
+
 def test_symbols_are_declared_bound_and_documented():
     header = open(os.path.join(ROOT, "include", "ctts_hip.h")).read()
     assert re.search(r"int ctts_gpt_grow\(ctts_gpt\* h, int n, void\* stream\);", header)
