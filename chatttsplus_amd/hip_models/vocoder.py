@@ -207,6 +207,18 @@ def settled_samples(n_tokens: int, hop: int = 256, halo_frames: int = Synth.HALO
     return hop * max(0, 2 * n - (halo_frames + 1) - 1)
 
 
+def prefix_samples(n_tokens: int, hop: int = 256) -> int:
+    """Length of the n_tokens-long prefix waveform: two mel frames per token, hop * (2 n_tokens - 1) samples; nothing without a token."""
+    n = int(n_tokens)
+    return hop * (2 * n - 1) if n > 0 else 0
+
+
+def prefix_tokens(n_samples: int, hop: int = 256) -> int:
+    """prefix_samples' inverse: the tokens behind a waveform of n_samples samples."""
+    n = int(n_samples)
+    return (n // hop + 1) // 2 if n else 0
+
+
 def window_token_range(n_tokens: int, s0: int, s1: int, hop: int = 256, halo_frames: int = 105, clamp_tail: bool = True):
     """Tokens [a, b) whose vocoding contains samples [s0, s1) of the n_tokens-long prefix waveform exactly, the sample offset of
     that sub-waveform, and the clamped window.  A sample s depends on ISTFT frames s/hop - 1 .. s/hop + 2, each of which depends

@@ -69,6 +69,7 @@ class TorchSeedContext:                        # reference commons/utils.py:48-5
 # gen_logits and its scalar carriers live beside the sampler configuration they feed (hip_models/gpt.py): one conversion for a call's knobs and for an
 # utterance's (sampling_per_row)
 from .hip_models.gpt import LORA_TARGETS, _RepPenalty, _TopK, _TopP, check_lora_shapes, gen_logits, refuse_out_of_scope  # noqa: E402,F401
+from .hip_models.vocoder import prefix_samples, prefix_tokens  # noqa: E402
 
 
 # params_per_utterance (ChatTTSPlusPipeline.infer / infer_sharded): the InferCodeParams fields one utterance may set for itself.  The sampling knobs
@@ -113,6 +114,70 @@ def per_utterance_overrides(base, entries) -> List[dict]:
                                        f"(per utterance: {', '.join(PER_UTTERANCE_FIELDS)})")
         out.append(diff)
     return out
+
+
+def _with_uv_break(text: str) -> str:
+    """pipeline:414-416: a text that goes to the code pass ends with [uv_break]."""
+    return text if text.strip().endswith("[uv_break]") else text + " [uv_break]"
+
+
+def _decode_refined(tok, ids_list) -> List[str]:
+    """pipeline:406-411: the refine-text pass's ids without the control tokens from [break_0] up, as text."""
+    return tok.decode([i[i.less(tok.break_0_ids)] for i in ids_list])
+
+
+def _draw_request_seed() -> int:
+    """A request's device-noise seed where the caller names none: ONE draw from torch's CPU generator (torch.manual_seed / TorchSeedContext reproduce the request)."""
+    return int(torch.randint(0, 2 ** 62, (1,)).item())
+
+
+def _code_sampler_args(params: InferCodeParams, gpt):
+    """What the code pass's sampler takes from an InferCodeParams: (temperature per codebook, num_code = the EOS id, logits warpers, logits processors)."""
+    num_code = int(gpt.emb_code[0].num_embeddings - 1)
+    warpers, processors = gen_logits(num_code=num_code, top_P=params.top_P, top_K=params.top_K, repetition_penalty=params.repetition_penalty)
+    temperature = params.temperature if isinstance(params.temperature, list) else [params.temperature] * gpt.num_vq
+    return temperature, num_code, warpers, processors
+
+
+def _is_speaker_table(spk, n: int) -> bool:
+    """Is `spk` one speaker row per utterance ([n, 768]: infer_sharded's rows, params_per_utterance's _speaker_rows) and not one speaker for the call?"""
+    return torch.is_tensor(spk) and spk.dim() == 2 and spk.shape[0] == n
+
+
+def _check_entries(name: str, entries, n: int, where: str = "") -> None:
+    """A per-utterance list (None: not given) has one entry per utterance."""
+    if entries is not None and len(entries) != n:
+        raise _lib.HipBackendError(f"{name}: {len(entries)} entries for {n} utterances{where}")
+
+
+@dataclass(repr=False, eq=False)
+class _Request:
+    """One _infer() call, resolved once (ChatTTSPlusPipeline._resolve_request): the normalised texts, the engine, and every per-call and per-utterance value
+    the three paths (_infer_sliced, _infer_continuous, _infer_details) read.  The per-utterance lists are None where the caller set none."""
+    texts: List[str]; gpt: object; slice_size: int
+    params_refine_text: RefineTextParams; params_infer_code: InferCodeParams      # the latter after the max_new_token / spk_emb replacements of params_per_utterance
+    utt_ids: list; utt_limits: Optional[list]; utt_sampling: Optional[list]; utt_prompts: Optional[list]; lora_paths: Optional[list]
+    noise_mode: object; noise_seed: Optional[int]      # "auto" | "device" | what else GPT.generate takes as `noise`; seed None: drawn by the path that runs, when it needs one
+    stream: bool; use_decoder: bool; skip_refine_text: bool; refine_text_only: bool; continuous: object      # continuous: False | True | "throughput"
+    n_cand: int; return_details: bool; select: Optional[Callable]; share_prompt: Optional[bool]; ids_sink: Optional[list]
+    overlap_vocoder: bool; vocoder_chunk: object
+    device_noise = property(lambda self: self.n_cand > 1 or self.noise_mode == "device")      # (details path) device noise whatever the slice's size
+
+    def rows(self, idx, adapters: bool = False, params: bool = True) -> dict:
+        """The generation keywords of utterances `idx` (a range or a list of indices into `texts`, in the order the rows are laid out): `utt_ids`; where the request
+        has them `max_new_tokens_per_row` / `sampling_per_row` / `prompts` / (`adapters`) `lora_paths`; `params`: the InferCodeParams, the rows of a per-utterance
+        speaker table gathered.  An identity `idx` (a slice that is the whole request, the [1, 768] table of one utterance) hands the table on untouched; a range takes a view."""
+        kw = dict(utt_ids=[self.utt_ids[i] for i in idx])
+        for key, per_utt in (("max_new_tokens_per_row", self.utt_limits), ("sampling_per_row", self.utt_sampling), ("prompts", self.utt_prompts),
+                             ("lora_paths", self.lora_paths if adapters else None)):
+            if per_utt is not None:
+                kw[key] = [per_utt[i] for i in idx]
+        if params:
+            kw["params"], spk = self.params_infer_code, self.params_infer_code.spk_emb
+            if _is_speaker_table(spk, len(self.texts)) and list(idx) != list(range(len(self.texts))):
+                rows = spk[idx.start:idx.stop] if isinstance(idx, range) else spk[torch.as_tensor(list(idx), device=spk.device)]
+                kw["params"] = dataclasses.replace(self.params_infer_code, spk_emb=rows)
+        return kw
 
 
 # -- log-probs of a generation and N-candidate ranking (infer(return_details=..., num_candidates=...); no counterpart in the reference) -----------------
@@ -241,9 +306,7 @@ class SynthSession:
     def __init__(self, pipe, gpt, params: InferCodeParams, use_decoder: bool, rows, seed, return_details: bool, refine: Optional[RefineTextParams] = None):
         self.pipe, self.gpt, self.params, self.use_decoder, self.return_details = pipe, gpt, params, bool(use_decoder), bool(return_details)
         self.refine = refine
-        num_code = int(gpt.emb_code[0].num_embeddings - 1)
-        warpers, processors = gen_logits(num_code=num_code, top_P=params.top_P, top_K=params.top_K, repetition_penalty=params.repetition_penalty)
-        temperature = params.temperature if isinstance(params.temperature, list) else [params.temperature] * gpt.num_vq
+        temperature, num_code, warpers, processors = _code_sampler_args(params, gpt)
         text_rows = None
         if refine is not None:
             if refine.repetition_penalty is not None and float(refine.repetition_penalty) != 1.0:
@@ -324,7 +387,7 @@ class SynthSession:
     def _submit_code(self, t: str, diff: dict, slot, utt_id: int, streaming=None) -> int:
         """the code utterance of one (refined) text: infer()'s prompt building, then DecodeSession.submit"""
         pipe, gpt, base = self.pipe, self.gpt, self.params
-        t = t if t.strip().endswith("[uv_break]") else t + " [uv_break]"      # pipeline:414-416
+        t = _with_uv_break(t)
         pic = dataclasses.replace(base, spk_emb=diff["spk_emb"]) if "spk_emb" in diff else base
         input_ids, attention_mask, text_mask = pipe._code_prompt([t], pic, gpt, [diff["prompt"] or ""] if "prompt" in diff else None)
         emb = gpt(input_ids, text_mask, spk_emb=pic.spk_emb, spk_emb_ids=pipe.models_dict["tokenizer"].spk_emb_ids)
@@ -389,7 +452,7 @@ class SynthSession:
                 e = self._empty(True)
                 out.append((r.ticket, self._end_chunk(e, info.get("streaming")), True))
                 continue
-            text = tok.decode([r.ids[r.ids.less(tok.break_0_ids)]])[0]
+            text = _decode_refined(tok, [r.ids])[0]
             try:
                 tk2 = self._submit_code(text, info["diff"], info["slot"], info["utt_id"], info.get("streaming"))
             except _lib.HipBackendError as e:
@@ -742,23 +805,18 @@ class ChatTTSPlusPipeline:
         prompt prefix per text instead of params.prompt (params_per_utterance)."""
         gpt = gpt or self.models_dict["gpt"]
         tok = self.models_dict["tokenizer"]
-        temperature = params.temperature if isinstance(params.temperature, list) else [params.temperature] * gpt.num_vq
         input_ids, attention_mask, text_mask = self._code_prompt(text, params, gpt, prompts)
         emb = gpt(input_ids, text_mask, spk_emb=params.spk_emb, spk_emb_ids=tok.spk_emb_ids)     # get_emb + apply_spk_emb, one launch
-        num_code = int(gpt.emb_code[0].num_embeddings - 1)
-        warpers, processors = gen_logits(num_code=num_code, top_P=params.top_P, top_K=params.top_K,
-                                         repetition_penalty=params.repetition_penalty)
+        temperature, num_code, warpers, processors = _code_sampler_args(params, gpt)
+        gen_kwargs.update(temperature=torch.tensor(temperature), eos_token=num_code, attention_mask=attention_mask, max_new_token=params.max_new_token,
+                          min_new_token=params.min_new_token, logits_warpers=warpers, logits_processors=processors, return_hidden=return_hidden,
+                          ensure_non_empty=params.ensure_non_empty)
         if gen_kwargs.pop("continuous", False):
             # more utterances than decode rows: queued utterances take over rows as they free up (GPT.generate_many_iter: a generator of
             # completion events whose return value is the GenerationOutputs of all utterances)
             gen_kwargs.pop("noise", None)
-            return gpt.generate_many_iter(emb, input_ids, temperature=torch.tensor(temperature), eos_token=num_code, attention_mask=attention_mask,
-                                     max_new_token=params.max_new_token, min_new_token=params.min_new_token, logits_warpers=warpers,
-                                     logits_processors=processors, return_hidden=return_hidden, ensure_non_empty=params.ensure_non_empty, **gen_kwargs)
-        return gpt.generate(emb, input_ids, temperature=torch.tensor(temperature), eos_token=num_code, attention_mask=attention_mask,
-                            max_new_token=params.max_new_token, min_new_token=params.min_new_token, logits_warpers=warpers,
-                            logits_processors=processors, infer_text=False, return_hidden=return_hidden, stream=stream,
-                            show_tqdm=params.show_tqdm, ensure_non_empty=params.ensure_non_empty, stream_batch=params.stream_batch, **gen_kwargs)
+            return gpt.generate_many_iter(emb, input_ids, **gen_kwargs)
+        return gpt.generate(emb, input_ids, infer_text=False, stream=stream, show_tqdm=params.show_tqdm, stream_batch=params.stream_batch, **gen_kwargs)
 
     def _refine_prompt(self, text, params: RefineTextParams):
         """The refine-text prompt of pipeline:237-277 (shared by _refine_text and SynthSession): "[Sbreak]{text}[Pbreak]{prompt}", tokenised.  Returns input_ids
@@ -775,14 +833,11 @@ class ChatTTSPlusPipeline:
         input_ids, attention_mask, text_mask = self._refine_prompt(text, params)
         warpers, processors = gen_logits(num_code=tok.len, top_P=params.top_P, top_K=params.top_K, repetition_penalty=params.repetition_penalty)
         emb = gpt(input_ids, text_mask)
+        kw = dict(temperature=torch.tensor([params.temperature]), eos_token=tok.eos_token, attention_mask=attention_mask, max_new_token=params.max_new_token,
+                  min_new_token=params.min_new_token, logits_warpers=warpers, logits_processors=processors, ensure_non_empty=params.ensure_non_empty, infer_text=True)
         if continuous_rows > 0:
-            return gpt.generate_many(emb, input_ids, temperature=torch.tensor([params.temperature]), eos_token=tok.eos_token, attention_mask=attention_mask,
-                                     max_new_token=params.max_new_token, min_new_token=params.min_new_token, logits_warpers=warpers, logits_processors=processors,
-                                     ensure_non_empty=params.ensure_non_empty, seed=seed, utt_ids=utt_ids, rows=continuous_rows, infer_text=True)
-        return next(gpt.generate(emb, input_ids, temperature=torch.tensor([params.temperature]), eos_token=tok.eos_token,
-                                 attention_mask=attention_mask, max_new_token=params.max_new_token, min_new_token=params.min_new_token,
-                                 logits_warpers=warpers, logits_processors=processors, infer_text=True, stream=False,
-                                 show_tqdm=params.show_tqdm, ensure_non_empty=params.ensure_non_empty))
+            return gpt.generate_many(emb, input_ids, seed=seed, utt_ids=utt_ids, rows=continuous_rows, **kw)
+        return next(gpt.generate(emb, input_ids, stream=False, show_tqdm=params.show_tqdm, **kw))
 
     def _codes_synth(self):
         """The "decode codes" model of use_decoder=False (pipeline:292: decoder = models_dict["dvae_encode"], i.e. the DVAE_full checkpoint
@@ -873,7 +928,7 @@ class ChatTTSPlusPipeline:
 
         def vec(v):
             return codec.speaker_to_vector(v).view(dim) if isinstance(v, str) else torch.as_tensor(v, dtype=torch.float32).cpu().reshape(dim)
-        table = torch.is_tensor(call_spk) and call_spk.dim() == 2 and call_spk.shape[0] == len(diffs)
+        table = _is_speaker_table(call_spk, len(diffs))
         rows = []
         for u, d in enumerate(diffs):
             if "spk_emb" in d:
@@ -887,6 +942,7 @@ class ChatTTSPlusPipeline:
     def _infer(self, text_in, stream=False, lang=None, skip_refine_text=False, refine_text_only=False, use_decoder=True,
                do_text_normalization=True, do_text_optimization=True, do_homophone_replacement=True,
                params_refine_text=RefineTextParams(), params_infer_code=InferCodeParams(), **kwargs):
+        """pipeline:333-470: the text front-end, the request resolved once, the generator of its mode.  A generator itself: no refusal is raised before the first next()."""
         if not isinstance(text_in, list):
             text_in = [text_in]
         if do_text_optimization and self.text_splitter is not None:
@@ -894,31 +950,32 @@ class ChatTTSPlusPipeline:
             lines = [t.strip() for text_ in text_in for t in text_.split("\n") if t.strip()]
             text_in = merge_short_sentences(self.text_splitter(lines))
         text_in = [self.normalizer(t, do_text_normalization, do_homophone_replacement, lang) for t in text_in]
+        req = self._resolve_request(text_in, stream, skip_refine_text, refine_text_only, use_decoder, params_refine_text, params_infer_code, kwargs)
+        if (req.n_cand > 1 or req.return_details) and not req.refine_text_only:
+            yield from self._infer_details(req)
+        elif req.continuous and len(req.texts) > req.slice_size:
+            yield from self._infer_continuous(req)
+        else:
+            yield from self._infer_sliced(req)
+
+    def _resolve_request(self, texts, stream, skip_refine_text, refine_text_only, use_decoder, params_refine_text, params_infer_code, kwargs) -> _Request:
+        """_infer()'s arguments and keywords -> the _Request its paths read, with every refusal that does not depend on the path.  Unknown keywords are ignored."""
+        n, after = len(texts), " (after text splitting)"
         slice_size = int(kwargs.get("slice_size", self.models_dict["gpt"].max_batch))     # reference: 4 (pipeline:391)
         gpt = self._gpt_for_lora(kwargs.get("lora_path"))
-        # per-utterance adapters (the reference can only merge ONE adapter for a whole call): `lora_paths` = one adapter
-        # directory (or None) per input text; adapters stay resident in up to 8 slots of the base engine, each row selects its own
+        # `lora_paths` (SURVEY 8f N3; the reference merges ONE adapter for a whole call): one adapter directory (or None) per text; up to 8 stay resident, each row selects its own
         lora_paths = kwargs.get("lora_paths")
-        if lora_paths is not None:
-            if kwargs.get("lora_path"):
-                raise _lib.HipBackendError("lora_path (one merged adapter) and lora_paths (one adapter per utterance) are exclusive")
-            if len(lora_paths) != len(text_in):
-                raise _lib.HipBackendError(f"lora_paths: {len(lora_paths)} entries for {len(text_in)} utterances (after text splitting)")
-        tok = self.models_dict["tokenizer"]
-        # Device noise is keyed by (request seed, global utterance id): every slice of the request uses the SAME seed and each utterance its
-        # own id, so the result does not depend on slice_size or on which rank serves the utterance (infer_sharded).  `noise="auto"` keeps the
-        # reference-compatible torch-generator noise for slices of <= 4 utterances.
+        if lora_paths is not None and kwargs.get("lora_path"):
+            raise _lib.HipBackendError("lora_path (one merged adapter) and lora_paths (one adapter per utterance) are exclusive")
+        _check_entries("lora_paths", lora_paths, n, after)
+        # Device noise is keyed by (request seed, global utterance id): one seed per request and each utterance its own id, so the result does not depend on slice_size or
+        # on which rank serves the utterance (infer_sharded).  `noise="auto"` keeps the reference-compatible torch-generator noise for slices of <= 4 utterances.
         noise_mode = kwargs.get("noise", "auto")
-        utt_ids = kwargs.get("utt_ids")
-        if utt_ids is None:
-            utt_ids = list(range(len(text_in)))
-        elif len(utt_ids) != len(text_in):
-            raise _lib.HipBackendError(f"utt_ids: {len(utt_ids)} entries for {len(text_in)} utterances (after text splitting)")
-        noise_seed = kwargs.get("noise_seed")      # None: drawn from torch's CPU generator when the first slice that uses device noise starts
+        utt_ids = kwargs.get("utt_ids") if kwargs.get("utt_ids") is not None else list(range(n))
+        _check_entries("utt_ids", utt_ids, n, after)
         # optional per-utterance token limits (<= params_infer_code.max_new_token): ctts_gen_io.row_limits
         utt_limits = kwargs.get("max_new_tokens_per_utterance")
-        if utt_limits is not None and len(utt_limits) != len(text_in):
-            raise _lib.HipBackendError(f"max_new_tokens_per_utterance: {len(utt_limits)} entries for {len(text_in)} utterances (after text splitting)")
+        _check_entries("max_new_tokens_per_utterance", utt_limits, n, after)
         # optional per-utterance parameters (no counterpart in the reference, whose InferCodeParams apply to a whole call): one InferCodeParams or dict of
         # overrides per utterance; the sampling knobs go to the engine's per-row table (GPT sampling_per_row), max_new_token to the per-row limits
         utt_sampling = utt_prompts = None
@@ -926,8 +983,7 @@ class ChatTTSPlusPipeline:
         if diffs is None and kwargs.get("params_per_utterance") is not None:
             diffs = per_utterance_overrides(params_infer_code, kwargs["params_per_utterance"])
         if diffs is not None:
-            if len(diffs) != len(text_in):
-                raise _lib.HipBackendError(f"params_per_utterance: {len(diffs)} entries for {len(text_in)} utterances (after text splitting)")
+            _check_entries("params_per_utterance", diffs, n, after)
             if any(set(d) & set(PER_UTTERANCE_SAMPLING) for d in diffs):
                 utt_sampling = [({k: d[k] for k in PER_UTTERANCE_SAMPLING if k in d} or None) for d in diffs]
             if any("max_new_token" in d for d in diffs):
@@ -941,329 +997,279 @@ class ChatTTSPlusPipeline:
                 params_infer_code = dataclasses.replace(params_infer_code, spk_emb=self._speaker_rows(params_infer_code.spk_emb, diffs))
         # return_details / num_candidates (no counterpart in the reference): log-probs written by the sampler, N candidates per utterance ranked by them
         n_cand = check_candidate_request(kwargs.get("num_candidates", 1), utt_ids, stream, noise_mode)
-        if (n_cand > 1 or kwargs.get("return_details")) and not refine_text_only:
-            if stream:
-                raise _lib.HipBackendError("return_details=True needs stream=False")
-            yield from self._infer_details(text_in, n_cand, bool(kwargs.get("return_details")), kwargs.get("select"), skip_refine_text, use_decoder,
-                                           params_refine_text, params_infer_code, gpt, slice_size, noise_mode, noise_seed, utt_ids, utt_limits, utt_sampling,
-                                           utt_prompts, lora_paths, kwargs.get("continuous"), kwargs.get("_ids_sink"), kwargs.get("share_prompt"))
-            return
-        # `continuous=True` (no counterpart in the reference): the request's utterances are NOT cut into slices that each wait for their slowest
-        # row (pipeline:391-397); slice_size decode rows are kept busy -- queued utterances take over the rows of finished ones
-        # (GPT.generate_many_iter, ctts_gpt_admit).  Device noise keyed by utterance id: every utterance gets the waveform the sliced path gives it.
-        # Lists of waveforms are yielded in input order as prefixes of the request complete.  Not for caller-supplied noise.
-        if kwargs.get("continuous") and len(text_in) > slice_size:
-            if noise_mode not in ("auto", "device"):
-                raise _lib.HipBackendError("continuous=True works with device noise")
-            adapter_slots = None
-            if lora_paths is not None:
-                # per-utterance adapters under row re-use: an admitted utterance brings its own adapter (ctts_gpt_admit_adapters).  All adapters of the request
-                # must be resident at once (the engine holds _lib.MAX_ADAPTERS)
-                if len({p for p in lora_paths if p}) > _lib.MAX_ADAPTERS:
-                    raise _lib.HipBackendError(f"continuous=True: {len({p for p in lora_paths if p})} distinct adapters in the request; the engine holds "
-                                               f"{_lib.MAX_ADAPTERS} (use slices: continuous=False)")
-                adapter_slots = self._adapter_slots(gpt, lora_paths)
-            if noise_seed is None:
-                noise_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-            texts_all = list(text_in)
-            if not skip_refine_text:
-                # pipeline:399-411 for the whole request at once: the refine-text pass keeps `slice_size` rows busy too (its noise is keyed by utterance id on
-                # stream 4, so a sentence is refined to the same text whatever shares the batch with it)
-                refined = self._refine_text(texts_all, params_refine_text, continuous_rows=slice_size, seed=noise_seed, utt_ids=utt_ids)
-                texts_all = tok.decode([i[i.less(tok.break_0_ids)] for i in refined.ids])
-                if refine_text_only:
-                    yield texts_all
-                    return
-            texts_all = [t if t.strip().endswith("[uv_break]") else t + " [uv_break]" for t in texts_all]   # pipeline:414-416
-            # continuous=True: utterances are admitted in input order and their waveforms are yielded IN ORDER as soon as a prefix of the request
-            # is complete (the first list as early as possible, later ones in groups of >= 8 so that the vocoder runs batched) while the rest keeps
-            # decoding.  continuous="throughput": longest texts first (longest-processing-time order: the last rows to finish are short
-            # utterances), one list at the end.  An utterance's result does not depend on the order -- its noise is keyed by its id.
-            ordered = kwargs.get("continuous") != "throughput"
-            n_all = len(texts_all)
-            # (round 6: by the utterance's own token limit where the caller gave one -- the 256-utterance request of bench.py: 2625 decode steps instead of 2905 for
-            #  2518 ideal ones, 30.9 k -> 35.8 k useful tokens/s; `throughput_order = "input"` keeps arrival order)
-            if ordered or getattr(self, "throughput_order", "longest_first") != "longest_first":
-                order = list(range(n_all))
-            elif utt_limits is not None:
-                order = sorted(range(n_all), key=lambda i: (-int(utt_limits[i]), -len(texts_all[i]), i))
-            else:
-                order = sorted(range(n_all), key=lambda i: (-len(texts_all[i]), i))
-            pic = params_infer_code
-            if torch.is_tensor(pic.spk_emb) and pic.spk_emb.dim() == 2 and pic.spk_emb.shape[0] == n_all:      # one speaker row per utterance
-                pic = dataclasses.replace(pic, spk_emb=pic.spk_emb[torch.as_tensor(order, device=pic.spk_emb.device)])
-            events = self._infer_code([texts_all[i] for i in order], False, use_decoder, pic, gpt=gpt, continuous=True, seed=noise_seed,
-                                      utt_ids=[utt_ids[i] for i in order], rows=slice_size,
-                                      max_new_tokens_per_row=[utt_limits[i] for i in order] if utt_limits is not None else None, progress=bool(stream),
-                                      **({"prompts": [utt_prompts[i] for i in order]} if utt_prompts is not None else {}),
-                                      **({"adapter_slots": [adapter_slots[i] for i in order]} if adapter_slots is not None else {}),
-                                      **({"sampling_per_row": [utt_sampling[i] for i in order]} if utt_sampling is not None else {}))
-            if stream:
-                # stream=True with row re-use (no counterpart in the reference, whose stream branch serves one slice, pipeline:440-463): every yield is a list of
-                # (utterance index, sample window) -- the next [emitted, b) samples of that utterance's prefix waveform, vocoded from the tokens inside the window's
-                # receptive field only (Synth.decode_window) -- as soon as `stream_batch` new tokens of it exist; an utterance's last window comes with its completion
-                syn = self.synth if use_decoder else self._codes_synth()
-                emitted, last_n = {}, {}
+        if (n_cand > 1 or kwargs.get("return_details")) and not refine_text_only and stream:
+            raise _lib.HipBackendError("return_details=True needs stream=False")
+        return _Request(texts=texts, gpt=gpt, slice_size=slice_size, params_refine_text=params_refine_text, params_infer_code=params_infer_code, utt_ids=utt_ids,
+                        utt_limits=utt_limits, utt_sampling=utt_sampling, utt_prompts=utt_prompts, lora_paths=lora_paths, noise_mode=noise_mode, stream=stream,
+                        noise_seed=kwargs.get("noise_seed"), use_decoder=use_decoder, skip_refine_text=skip_refine_text, refine_text_only=refine_text_only,
+                        continuous=kwargs.get("continuous"), n_cand=n_cand, return_details=bool(kwargs.get("return_details")), select=kwargs.get("select"),
+                        share_prompt=kwargs.get("share_prompt"), ids_sink=kwargs.get("_ids_sink"), overlap_vocoder=bool(kwargs.get("overlap_vocoder", False)),
+                        vocoder_chunk=kwargs.get("vocoder_chunk", 32))
 
-                def windows(items, final):
-                    out = []
-                    for k, n, ids_k, hid_k in items:
-                        u = order[k]
-                        src = hid_k if use_decoder else ids_k
-                        total = 256 * (2 * int(n) - 1) if n > 0 else 0
-                        s0 = emitted.get(u, 0)
-                        if total > s0 and (final or n - last_n.get(u, 0) >= pic.stream_batch):
-                            b = total if final else min(s0 + pic.stream_speed, total)
-                            out.append((u, syn.decode_window([src], [s0], [b])[0]))
-                            emitted[u], last_n[u] = b, int(n)
-                    return out
-
-                for ev in events:
-                    if isinstance(ev, tuple) and ev[0] == "progress":
-                        got = windows(ev[1], False)
-                    else:
-                        got = windows([(k, int(ids_k.shape[0]), ids_k, hid_k) for k, ids_k, hid_k in ev], True)
-                    if got:
-                        yield got
-                return
-            ready, next_i, first = {}, 0, True
-            ids_sink = kwargs.get("_ids_sink")
-            # continuous="throughput" + overlap_vocoder=True (round 5; OPT-IN since round 6): the vocoder does not wait for the last utterance.  Finished utterances are
-            # vocoded in batches of `vocoder_chunk` on a SIDE stream while the decode rows keep stepping on the caller's stream.  Measured: no gain (256 ragged utterances
-            # 2682 vs 2665-2687 ms: the vocoder's GEMMs fill the chip and the decode chain's small kernels queue behind them), and a <= 5-row tail's persistent launch
-            # -- which needs all 256 workgroups resident -- then shares the chip with vocoder kernels.  Its waits are bounded and the soak test
-            # (tests/test_gpu_pipeline.py::test_vocoder_overlap_soak) drives exactly that overlap, but a default that buys nothing stays off.  One list at the end, in input order.
-            overlap = (not ordered) and self.device.type == "cuda" and bool(kwargs.get("overlap_vocoder", False))
-            voc_chunk = max(1, int(kwargs.get("vocoder_chunk", 32)))
-            side = torch.cuda.Stream(device=self.device) if overlap else None
-            t_req = torch.cuda.Event(enable_timing=True) if overlap else None
-            t_first = None
-            if overlap:
-                t_req.record(torch.cuda.current_stream(self.device))
-            done_wavs, pending = {}, []
-
-            def vocode(batch_idx):
-                nonlocal t_first
-                items = [ready.pop(i) for i in batch_idx]
-                go = torch.cuda.Event()
-                go.record(torch.cuda.current_stream(self.device))      # every token of these utterances was written before this point of the caller's stream
-                side.wait_event(go)
-                with torch.cuda.stream(side):
-                    for it in items:
-                        it.record_stream(side)                           # (views of the generate call's buffers: keep the allocator off them until the side stream is done)
-                    wavs = self._decode_to_wavs(items, use_decoder)
-                    if t_first is None:
-                        t_first = torch.cuda.Event(enable_timing=True)
-                        t_first.record(side)
-                for i, w in zip(batch_idx, wavs):
-                    done_wavs[i] = w
-
-            for ev in events:
-                for k, ids_k, hid_k in ev:
-                    ready[order[k]] = hid_k if use_decoder else ids_k
-                    if ids_sink is not None:
-                        ids_sink.append((utt_ids[order[k]], ids_k))
-                    pending.append(order[k])
-                if not ordered:
-                    while overlap and len(pending) >= voc_chunk:
-                        vocode(pending[:voc_chunk])
-                        pending = pending[voc_chunk:]
-                    continue
-                run = 0
-                while next_i + run in ready:
-                    run += 1
-                if run and (first or run >= 8 or next_i + run == n_all):
-                    yield self._decode_to_wavs([ready.pop(next_i + j) for j in range(run)], use_decoder)
-                    next_i += run
-                    first = False
-            if overlap:
-                if pending:
-                    vocode(pending)
-                torch.cuda.current_stream(self.device).wait_stream(side)      # the caller's stream sees the finished waveforms
-                side.synchronize()
-                self.last_first_audio_ms = t_req.elapsed_time(t_first) if t_first is not None else None
-                rest = sorted(done_wavs)
-                if rest:
-                    yield [done_wavs[i] for i in rest]
-                return
-            rest = [i for i in range(next_i, n_all) if i in ready]      # (everything, in throughput mode without overlap; nothing unless the run was interrupted, otherwise)
-            if rest:
-                yield self._decode_to_wavs([ready[i] for i in rest], use_decoder)
-            return
-        for ii in range(0, len(text_in), slice_size):
-            text = list(text_in[ii:ii + slice_size])
-            if not skip_refine_text:                                                   # pipeline:399-411
-                refined = self._refine_text(text, params_refine_text)
-                text_tokens = [i[i.less(tok.break_0_ids)] for i in refined.ids]
-                text = tok.decode(text_tokens)
-                if refine_text_only:
+    def _infer_sliced(self, req: _Request):
+        """pipeline:391-470: slices of slice_size utterances, each waiting for its slowest row; one list of waveforms per slice (stream=True: [B, samples]
+        windows of the slice's padded prefix waveforms).  The request seed is drawn lazily: inside the first slice that uses device noise, after that slice's
+        refine pass -- slices of <= 4 under noise="auto" keep the reference-compatible torch noise and draw nothing."""
+        gpt, seed = req.gpt, req.noise_seed
+        for ii in range(0, len(req.texts), req.slice_size):
+            idx = range(ii, min(ii + req.slice_size, len(req.texts)))
+            text = [req.texts[i] for i in idx]
+            if not req.skip_refine_text:                                                   # pipeline:399-411
+                text = _decode_refined(self.models_dict["tokenizer"], self._refine_text(text, req.params_refine_text).ids)
+                if req.refine_text_only:
                     yield text
-            if refine_text_only:
+            if req.refine_text_only:
                 continue
-            text = [t if t.strip().endswith("[uv_break]") else t + " [uv_break]" for t in text]   # pipeline:414-416
-            length, pass_batch_count, last = 0, 0, None
-            if lora_paths is not None:
-                gpt.set_row_adapters(self._adapter_slots(gpt, lora_paths[ii:ii + slice_size]))
-            gen_kw = {}
-            if noise_mode != "auto" or len(text) > 4:      # device (or caller-chosen) noise; slices of <= 4 keep the reference-compatible default
-                if noise_seed is None and (noise_mode in ("auto", "device")):
-                    noise_seed = int(torch.randint(0, 2 ** 62, (1,)).item())       # ONE draw per request (torch.manual_seed reproduces it)
-                gen_kw = dict(noise=("device" if noise_mode == "auto" else noise_mode), seed=noise_seed, utt_ids=utt_ids[ii:ii + slice_size])
-            if utt_limits is not None:
-                gen_kw["max_new_tokens_per_row"] = list(utt_limits[ii:ii + slice_size])
-            if utt_sampling is not None:
-                gen_kw["sampling_per_row"] = list(utt_sampling[ii:ii + slice_size])
-            pic = params_infer_code
-            if torch.is_tensor(pic.spk_emb) and pic.spk_emb.dim() == 2 and pic.spk_emb.shape[0] == len(text_in) and len(text_in) > len(text):
-                pic = dataclasses.replace(pic, spk_emb=pic.spk_emb[ii:ii + len(text)])       # one speaker row per utterance: this slice's rows
-            if utt_prompts is not None:
-                gen_kw["prompts"] = list(utt_prompts[ii:ii + slice_size])
-            results = self._infer_code(text, stream, use_decoder, pic, gpt=gpt, **gen_kw)
+            text = [_with_uv_break(t) for t in text]
+            kw = req.rows(idx, adapters=True)
+            pic, utt_ids, paths = kw.pop("params"), kw.pop("utt_ids"), kw.pop("lora_paths", None)
+            if paths is not None:
+                gpt.set_row_adapters(self._adapter_slots(gpt, paths))
+            if req.noise_mode != "auto" or len(text) > 4:      # device (or caller-chosen) noise; slices of <= 4 keep the reference-compatible default
+                if seed is None and (req.noise_mode in ("auto", "device")):
+                    seed = _draw_request_seed()
+                kw.update(noise=("device" if req.noise_mode == "auto" else req.noise_mode), seed=seed, utt_ids=utt_ids)
+            results = self._infer_code(text, req.stream, req.use_decoder, pic, gpt=gpt, **kw)
+            length, passed, last, total = 0, 0, None, 0
             try:
                 for result in results:
-                    if not stream:
-                        if kwargs.get("_ids_sink") is not None:
-                            kwargs["_ids_sink"].extend(zip(utt_ids[ii:ii + slice_size], result.ids))
-                        yield self._decode_to_wavs(result.hiddens if use_decoder else result.ids, use_decoder)      # pipeline:435-439
+                    if not req.stream:
+                        if req.ids_sink is not None:
+                            req.ids_sink.extend(zip(utt_ids, result.ids))
+                        yield self._decode_to_wavs(result.hiddens if req.use_decoder else result.ids, req.use_decoder)      # pipeline:435-439
                         continue
-                    # The reference's stream branch vocodes the whole prefix for every chunk and indexes a python list with
-                    # .shape.  Here every yield is the [length, b) sample window of that same prefix waveform,
-                    # vocoded from the tokens inside the window's receptive field only (Synth.decode_window), zero padded
-                    # like pad_sequence would pad the shorter utterances.
-                    last = result.hiddens if use_decoder else result.ids
-                    pass_batch_count += 1
-                    if pass_batch_count <= params_infer_code.pass_first_n_batches:
-                        continue
-                    total = max((256 * (2 * int(h.shape[0]) - 1) if h.shape[0] > 0 else 0) for h in last)
-                    b = min(length + params_infer_code.stream_speed, total)
-                    if b > length:
-                        yield self._window(last, length, b, use_decoder)
+                    # The reference's stream branch vocodes the whole prefix for every chunk and indexes a python list with .shape (SURVEY F10).  Here every yield is the
+                    # [length, b) sample window of that prefix waveform, vocoded from the tokens in its receptive field only (Synth.decode_window), zero padded like pad_sequence pads
+                    last, passed = (result.hiddens if req.use_decoder else result.ids), passed + 1
+                    total = max(prefix_samples(h.shape[0]) for h in last)
+                    b = min(length + pic.stream_speed, total)
+                    if passed > pic.pass_first_n_batches and b > length:
+                        yield self._window(last, length, b, req.use_decoder)
                         length = b
             finally:
-                if lora_paths is not None:          # the generator stays lazy (streaming works with per-utterance adapters); the row table is
+                if paths is not None:               # the generator stays lazy (streaming works with per-utterance adapters); the row table is
                     gpt.set_row_adapters(None)      # reset when the slice is exhausted, closed or fails
-            if stream and last is not None:
-                total = max((256 * (2 * int(h.shape[0]) - 1) if h.shape[0] > 0 else 0) for h in last)
-                if total > length:
-                    yield self._window(last, length, total, use_decoder)
+            if total > length:                      # streaming: what is left once the slice has ended
+                yield self._window(last, length, total, req.use_decoder)
 
-    def _infer_details(self, text_in, n_cand, return_details, select, skip_refine_text, use_decoder, params_refine_text, params_infer_code, gpt, slice_size,
-                       noise_mode, noise_seed, utt_ids, utt_limits, utt_sampling, utt_prompts, lora_paths, continuous, ids_sink, share_prompt=None):
+    def _infer_continuous(self, req: _Request):
+        """`continuous=True` (no counterpart in the reference): the request's utterances are NOT cut into slices that each wait for their slowest row
+        (pipeline:391-397); slice_size decode rows are kept busy -- queued utterances take over the rows of finished ones (GPT.generate_many_iter,
+        ctts_gpt_admit).  Device noise keyed by utterance id: every utterance gets the waveform the sliced path gives it, whatever the admission order.  Not
+        for caller-supplied noise.  The completion events go to _stream_continuous, to _overlap_vocoder or to the ordered-prefix loop below."""
+        if req.noise_mode not in ("auto", "device"):
+            raise _lib.HipBackendError("continuous=True works with device noise")
+        adapter_slots = None
+        if req.lora_paths is not None:      # an admitted utterance brings its own adapter (ctts_gpt_admit_adapters): all adapters of the request are resident at once
+            distinct = len({p for p in req.lora_paths if p})
+            if distinct > _lib.MAX_ADAPTERS:
+                raise _lib.HipBackendError(f"continuous=True: {distinct} distinct adapters in the request; the engine holds {_lib.MAX_ADAPTERS} (use slices: continuous=False)")
+            adapter_slots = self._adapter_slots(req.gpt, req.lora_paths)
+        seed = req.noise_seed if req.noise_seed is not None else _draw_request_seed()
+        texts = list(req.texts)
+        if not req.skip_refine_text:
+            # pipeline:399-411 for the whole request at once, `slice_size` rows kept busy (noise keyed by utterance id on stream 4: a sentence's refined text does not depend on the batch)
+            refined = self._refine_text(texts, req.params_refine_text, continuous_rows=req.slice_size, seed=seed, utt_ids=req.utt_ids)
+            texts = _decode_refined(self.models_dict["tokenizer"], refined.ids)
+            if req.refine_text_only:
+                yield texts
+                return
+        texts = [_with_uv_break(t) for t in texts]
+        # admission order: input order, or under "throughput" the longest first (the last rows to finish are short utterances) -- by the utterance's own token limit where the
+        # caller gave one (bench.py's 256-utterance request: 2625 decode steps instead of 2905 for 2518 ideal ones); `throughput_order = "input"` keeps arrival order
+        order = list(range(len(texts)))
+        if req.continuous == "throughput" and getattr(self, "throughput_order", "longest_first") == "longest_first":
+            limits = req.utt_limits if req.utt_limits is not None else [0] * len(texts)
+            order.sort(key=lambda i: (-int(limits[i]), -len(texts[i]), i))
+        kw = req.rows(order)
+        if adapter_slots is not None:
+            kw["adapter_slots"] = [adapter_slots[i] for i in order]
+        events = self._infer_code([texts[i] for i in order], False, req.use_decoder, kw.pop("params"), gpt=req.gpt, continuous=True, seed=seed, rows=req.slice_size,
+                                  progress=bool(req.stream), **kw)
+        ordered, n_all = req.continuous != "throughput", len(texts)
+        if req.stream:
+            return (yield from self._stream_continuous(req, events, order))
+        if not ordered and self.device.type == "cuda" and req.overlap_vocoder:
+            return (yield from self._overlap_vocoder(req, events, order))
+        # continuous=True: the waveforms IN ORDER as soon as a prefix of the request is complete (the first list as early as possible, later ones in groups of >= 8 so
+        # that the vocoder runs batched) while the rest keeps decoding.  continuous="throughput": one list at the end, in input order.
+        ready, next_i, first = {}, 0, True
+        for done in self._completions(req, events, order):
+            ready.update(done)
+            run = 0
+            while ordered and next_i + run in ready:
+                run += 1
+            if run and (first or run >= 8 or next_i + run == n_all):
+                yield self._decode_to_wavs([ready.pop(next_i + j) for j in range(run)], req.use_decoder)
+                next_i, first = next_i + run, False
+        rest = [i for i in range(next_i, n_all) if i in ready]      # (everything, in throughput mode; nothing unless the run was interrupted, otherwise)
+        if rest:
+            yield self._decode_to_wavs([ready[i] for i in rest], req.use_decoder)
+
+    def _stream_continuous(self, req: _Request, events, order):
+        """stream=True with row re-use (no counterpart in the reference, whose stream branch serves one slice, pipeline:440-463): every yield is a list of
+        (utterance index, sample window) -- the next [emitted, b) samples of that utterance's prefix waveform, vocoded from the tokens inside the window's
+        receptive field only (Synth.decode_window) -- as soon as `stream_batch` new tokens of it exist; an utterance's last window comes with its completion."""
+        syn = self.synth if req.use_decoder else self._codes_synth()
+        p, emitted, last_n = req.params_infer_code, {}, {}
+        for ev in events:
+            final = not (isinstance(ev, tuple) and ev[0] == "progress")      # a completion list; else ("progress", [(k, tokens so far, ids, hiddens)])
+            got = []
+            for k, n, ids_k, hid_k in ([(k, int(ids_k.shape[0]), ids_k, hid_k) for k, ids_k, hid_k in ev] if final else ev[1]):
+                u = order[k]
+                total, s0 = prefix_samples(n), emitted.get(u, 0)
+                if total > s0 and (final or n - last_n.get(u, 0) >= p.stream_batch):
+                    b = total if final else min(s0 + p.stream_speed, total)
+                    got.append((u, syn.decode_window([hid_k if req.use_decoder else ids_k], [s0], [b])[0]))
+                    emitted[u], last_n[u] = b, int(n)
+            if got:
+                yield got
+
+    def _completions(self, req: _Request, events, order):
+        """generate_many_iter's completion events as lists of (utterance index, what the vocoder takes of it); the ids go to the request's ids_sink"""
+        for ev in events:
+            done = []
+            for k, ids_k, hid_k in ev:
+                if req.ids_sink is not None:
+                    req.ids_sink.append((req.utt_ids[order[k]], ids_k))
+                done.append((order[k], hid_k if req.use_decoder else ids_k))
+            yield done
+
+    def _overlap_vocoder(self, req: _Request, events, order):
+        """continuous="throughput" + overlap_vocoder=True (OPT-IN): finished utterances are vocoded in batches of `vocoder_chunk` on a SIDE stream while the decode
+        rows keep stepping on the caller's stream; one list at the end, in input order.  Measured: no gain (256 ragged utterances 2682 vs 2665-2687 ms: the
+        vocoder's GEMMs fill the chip, the decode chain's small kernels queue behind them, and a <= 5-row tail's persistent launch shares the chip with them), so
+        the default stays off; tests/test_gpu_pipeline.py::test_vocoder_overlap_soak drives exactly this overlap."""
+        voc_chunk = max(1, int(req.vocoder_chunk))
+        side = torch.cuda.Stream(device=self.device)
+        t_req, t_first = torch.cuda.Event(enable_timing=True), None
+        t_req.record(torch.cuda.current_stream(self.device))
+        done_wavs, pending = {}, []
+
+        def vocode(batch):              # [(utterance index, what the vocoder takes of it)]
+            nonlocal t_first
+            items = [it for _, it in batch]
+            go = torch.cuda.Event()
+            go.record(torch.cuda.current_stream(self.device))      # every token of these utterances was written before this point of the caller's stream
+            side.wait_event(go)
+            with torch.cuda.stream(side):
+                for it in items:
+                    it.record_stream(side)                           # (views of the generate call's buffers: keep the allocator off them until the side stream is done)
+                wavs = self._decode_to_wavs(items, req.use_decoder)
+                if t_first is None:
+                    t_first = torch.cuda.Event(enable_timing=True)
+                    t_first.record(side)
+            done_wavs.update((u, w) for (u, _), w in zip(batch, wavs))
+
+        for done in self._completions(req, events, order):
+            pending += done
+            while len(pending) >= voc_chunk:
+                vocode(pending[:voc_chunk])
+                pending = pending[voc_chunk:]
+        if pending:
+            vocode(pending)
+        torch.cuda.current_stream(self.device).wait_stream(side)      # the caller's stream sees the finished waveforms
+        side.synchronize()
+        self.last_first_audio_ms = t_req.elapsed_time(t_first) if t_first is not None else None
+        if done_wavs:
+            yield [done_wavs[i] for i in sorted(done_wavs)]
+
+    def _infer_details(self, req: _Request):
         """infer(return_details=True) / infer(num_candidates=N): the code pass with return_logprobs, every utterance served N times as ordinary decode rows
         (candidate k under noise key candidate_utt_id(u, k), so candidate 0 is the plain generation), the winner picked by `select` or select_candidate,
         only winners vocoded.  Sliced: max(1, slice_size // N) utterances per slice, one yield per slice; continuous (more rows than slice_size): the
         whole request through GPT.generate_many, one yield.  The refine-text pass runs once per utterance, before the candidates are laid out.
         `share_prompt` (resolve_share_prompt): the candidates of an utterance share its prompt pass -- each utterance is tokenised and embedded once and the
         rows name their prompt (GPT prompt_of); speaker rows, prompts and adapters go per prompt, limits / sampling / noise keys per row."""
-        tok = self.models_dict["tokenizer"]
-        n_utt = len(text_in)
+        tok, gpt = self.models_dict["tokenizer"], req.gpt
+        n_utt, n_cand, slice_size = len(req.texts), req.n_cand, req.slice_size
         if n_cand > slice_size:
             raise _lib.HipBackendError(f"num_candidates={n_cand} exceeds slice_size={slice_size}: the candidates of an utterance share one decode batch")
-        device_noise = n_cand > 1 or noise_mode == "device"
-        cont = bool(continuous) and n_utt * n_cand > slice_size
-        if cont and noise_mode not in ("auto", "device"):
+        cont = bool(req.continuous) and n_utt * n_cand > slice_size
+        if cont and req.noise_mode not in ("auto", "device"):
             raise _lib.HipBackendError("continuous=True works with device noise")
         per_slice = max(1, slice_size // n_cand)
-        if noise_seed is None and noise_mode in ("auto", "device") and (device_noise or cont or min(per_slice, n_utt) * n_cand > 4):
-            noise_seed = int(torch.randint(0, 2 ** 62, (1,)).item())       # ONE draw per request (torch.manual_seed reproduces it)
-        texts = list(text_in)
-        if not skip_refine_text:                 # once per utterance, in the batches the plain call refines in
+        seed = req.noise_seed
+        if seed is None and req.noise_mode in ("auto", "device") and (req.device_noise or cont or min(per_slice, n_utt) * n_cand > 4):
+            seed = _draw_request_seed()
+        texts = list(req.texts)
+        if not req.skip_refine_text:                 # once per utterance, in the batches the plain call refines in
             if cont:
-                refined = self._refine_text(texts, params_refine_text, continuous_rows=slice_size, seed=noise_seed, utt_ids=utt_ids)
-                texts = tok.decode([i[i.less(tok.break_0_ids)] for i in refined.ids])
+                texts = _decode_refined(tok, self._refine_text(texts, req.params_refine_text, continuous_rows=slice_size, seed=seed, utt_ids=req.utt_ids).ids)
             else:
-                out = []
-                for ii in range(0, n_utt, slice_size):
-                    refined = self._refine_text(texts[ii:ii + slice_size], params_refine_text)
-                    out += tok.decode([i[i.less(tok.break_0_ids)] for i in refined.ids])
-                texts = out
-        texts = [t if t.strip().endswith("[uv_break]") else t + " [uv_break]" for t in texts]   # pipeline:414-416
-        per_utt_spk = torch.is_tensor(params_infer_code.spk_emb) and params_infer_code.spk_emb.dim() == 2 and params_infer_code.spk_emb.shape[0] == n_utt and n_utt > 1
+                texts = [t for ii in range(0, n_utt, slice_size) for t in _decode_refined(tok, self._refine_text(texts[ii:ii + slice_size], req.params_refine_text).ids)]
+        texts = [_with_uv_break(t) for t in texts]
         read_option = getattr(gpt, "get_option", None)           # (an engine object without options shares only when asked to)
-        share = resolve_share_prompt(share_prompt, n_cand, n_cand > 1 and read_option is not None and read_option("batch_invariant"))
+        share = resolve_share_prompt(req.share_prompt, n_cand, n_cand > 1 and read_option is not None and read_option("batch_invariant"))
+        for us in ([range(n_utt)] if cont else [range(ii, min(ii + per_slice, n_utt)) for ii in range(0, n_utt, per_slice)]):
+            cands = self._run_candidates(req, texts, list(us), seed, cont, share)
+            if cands is not None:
+                yield self._pick_candidates(req, list(us), cands)
 
-        def run(us):
-            """utterances `us` x n_cand candidates as one list of rows (utterance-major) -> one CandidateDetails per row"""
-            rows = [(u, k) for u in us for k in range(n_cand)]
-            src = [(u, 0) for u in us] if share else rows          # what is tokenised and embedded: every utterance once, or every row
-            pic = params_infer_code
-            if per_utt_spk or (torch.is_tensor(pic.spk_emb) and pic.spk_emb.dim() == 2 and pic.spk_emb.shape[0] == n_utt and len(src) != n_utt):
-                pic = dataclasses.replace(pic, spk_emb=pic.spk_emb[torch.as_tensor([u for u, _ in src], device=pic.spk_emb.device)])
-            gen_kw = dict(return_logprobs=True)
-            if share:
-                gen_kw["prompt_of"] = [j for j in range(len(us)) for _ in range(n_cand)]
-            many = cont and len(rows) > slice_size
-            if device_noise or many or len(rows) > 4:      # (the plain call's rule: slices of <= 4 keep the reference-compatible torch noise under "auto")
-                gen_kw.update(seed=noise_seed, utt_ids=[candidate_utt_id(utt_ids[u], k) for u, k in rows])
-                if not many:
-                    gen_kw["noise"] = "device" if noise_mode == "auto" else noise_mode
-            elif noise_mode != "auto":
-                gen_kw["noise"] = noise_mode
-            if utt_limits is not None:
-                gen_kw["max_new_tokens_per_row"] = [utt_limits[u] for u, _ in rows]
-            if utt_sampling is not None:
-                gen_kw["sampling_per_row"] = [utt_sampling[u] for u, _ in rows]
-            if utt_prompts is not None:
-                gen_kw["prompts"] = [utt_prompts[u] for u, _ in src]
-            slots = self._adapter_slots(gpt, [lora_paths[u] for u, _ in rows]) if lora_paths is not None else None
+    def _run_candidates(self, req: _Request, texts, us, seed, cont: bool, share: bool):
+        """utterances `us` x n_cand candidates as one list of rows (utterance-major) -> one CandidateDetails per row; None: ensure_non_empty gave up (gpt.py:525)"""
+        gpt, n_cand, use_decoder = req.gpt, req.n_cand, req.use_decoder
+        rows = [(u, k) for u in us for k in range(n_cand)]
+        src = [(u, 0) for u in us] if share else rows          # what is tokenised and embedded: every utterance once, or every row
+        row_kw = req.rows([u for u, _ in rows], adapters=True, params=not share)
+        src_kw = req.rows([u for u, _ in src]) if share else row_kw           # speaker rows and prompts go per prompt, the rest per row
+        pic, paths = src_kw["params"], row_kw.get("lora_paths")
+        gen_kw = dict(return_logprobs=True)
+        for key, of in (("max_new_tokens_per_row", row_kw), ("sampling_per_row", row_kw), ("prompts", src_kw)):
+            if key in of:
+                gen_kw[key] = of[key]
+        if share:
+            gen_kw["prompt_of"] = [j for j in range(len(us)) for _ in range(n_cand)]
+        if req.device_noise or cont or len(rows) > 4:      # (the plain call's rule: slices of <= 4 keep the reference-compatible torch noise under "auto")
+            gen_kw.update(seed=seed, utt_ids=[candidate_utt_id(i, k) for i, (_, k) in zip(row_kw["utt_ids"], rows)])
+            if not cont:
+                gen_kw["noise"] = "device" if req.noise_mode == "auto" else req.noise_mode
+        elif req.noise_mode != "auto":
+            gen_kw["noise"] = req.noise_mode
+        slots = self._adapter_slots(gpt, paths) if paths is not None else None
+        if cont:            # the whole request at once, more rows than slice_size: row re-use (GPT.generate_many_iter), an admitted row brings its adapter
+            gen_kw.update(continuous=True, rows=req.slice_size, adapter_slots=slots)
+        res = None
+        try:
+            if slots is not None and not cont:
+                gpt.set_row_adapters(slots)
+            results = self._infer_code([texts[u] for u, _ in src], False, use_decoder, pic, gpt=gpt, **gen_kw)
             try:
-                if many:
-                    if slots is not None:
-                        gen_kw["adapter_slots"] = slots
-                    events = self._infer_code([texts[u] for u, _ in src], False, use_decoder, pic, gpt=gpt, continuous=True, rows=slice_size, **gen_kw)
-                    try:
-                        while True:
-                            next(events)
-                    except StopIteration as stop:
-                        res = stop.value
-                else:
-                    if slots is not None:
-                        gpt.set_row_adapters(slots)
-                    res = None
-                    for res in self._infer_code([texts[u] for u, _ in src], False, use_decoder, pic, gpt=gpt, **gen_kw):
-                        pass
-            finally:
-                if slots is not None and not many:
-                    gpt.set_row_adapters(None)
-            if res is None:           # (ensure_non_empty gave up: the reference's bare return, gpt.py:525)
-                return None
-            return [CandidateDetails(ids=res.ids[r], logprobs=res.logprobs[r].cpu(), sampled_logprobs=res.sampled_logprobs[r].cpu(),
-                                     mean_logprob=mean_logprob(res.logprobs[r]), final_logprobs=res.final_logprobs[r],
-                                     hiddens=res.hiddens[r] if use_decoder else None) for r in range(len(rows))]
+                while True:
+                    res = next(results)            # GPT.generate: the last result counts
+            except StopIteration as stop:
+                res = stop.value if cont else res      # GPT.generate_many_iter: the GenerationOutputs of all rows is the generator's return value
+        finally:
+            if slots is not None and not cont:
+                gpt.set_row_adapters(None)
+        return None if res is None else [CandidateDetails(ids=res.ids[r], logprobs=res.logprobs[r].cpu(), sampled_logprobs=res.sampled_logprobs[r].cpu(),
+                                                          mean_logprob=mean_logprob(res.logprobs[r]), final_logprobs=res.final_logprobs[r],
+                                                          hiddens=res.hiddens[r] if use_decoder else None) for r in range(len(rows))]
 
-        def finish(us, cands):
-            chosen, scores = [], []
-            for j in range(len(us)):
-                group = cands[j * n_cand:(j + 1) * n_cand]
-                sc = torch.tensor([c.mean_logprob for c in group], dtype=torch.float64)
-                k = int(select(list(group))) if select is not None else select_candidate(sc.tolist())
-                if not 0 <= k < n_cand:
-                    raise _lib.HipBackendError(f"select returned {k}: not a candidate index (0..{n_cand - 1})")
-                chosen.append(k)
-                scores.append(sc)
-            win = [cands[j * n_cand + k] for j, k in enumerate(chosen)]
-            if ids_sink is not None:
-                ids_sink.extend((utt_ids[u], w.ids) for u, w in zip(us, win))
-            wavs = self._decode_to_wavs([w.hiddens if use_decoder else w.ids for w in win], use_decoder)      # pipeline:435-439; winners only
-            if not return_details:
-                return wavs
-            det = InferDetails(wavs=wavs, ids=[w.ids for w in win], logprobs=[w.logprobs for w in win], sampled_logprobs=[w.sampled_logprobs for w in win],
-                               mean_logprob=[w.mean_logprob for w in win])
-            if n_cand > 1:
-                det.candidate, det.candidate_scores = chosen, scores
-                det.candidates = [[dataclasses.replace(c, hiddens=None) for c in cands[j * n_cand:(j + 1) * n_cand]] for j in range(len(us))]
-            return det
-
-        if cont:
-            cands = run(list(range(n_utt)))
-            if cands is not None:
-                yield finish(list(range(n_utt)), cands)
-            return
-        for ii in range(0, n_utt, per_slice):
-            us = list(range(ii, min(ii + per_slice, n_utt)))
-            cands = run(us)
-            if cands is not None:
-                yield finish(us, cands)
+    def _pick_candidates(self, req: _Request, us, cands):
+        """the winner of every utterance of `us` among its n_cand CandidateDetails (`select` or select_candidate), vocoded: a list of waveforms or InferDetails"""
+        n_cand, use_decoder = req.n_cand, req.use_decoder
+        chosen, scores = [], []
+        for j in range(len(us)):
+            group = cands[j * n_cand:(j + 1) * n_cand]
+            sc = torch.tensor([c.mean_logprob for c in group], dtype=torch.float64)
+            k = int(req.select(list(group))) if req.select is not None else select_candidate(sc.tolist())
+            if not 0 <= k < n_cand:
+                raise _lib.HipBackendError(f"select returned {k}: not a candidate index (0..{n_cand - 1})")
+            chosen.append(k)
+            scores.append(sc)
+        win = [cands[j * n_cand + k] for j, k in enumerate(chosen)]
+        if req.ids_sink is not None:
+            req.ids_sink.extend((req.utt_ids[u], w.ids) for u, w in zip(us, win))
+        wavs = self._decode_to_wavs([w.hiddens if use_decoder else w.ids for w in win], use_decoder)      # pipeline:435-439; winners only
+        if not req.return_details:
+            return wavs
+        det = InferDetails(wavs=wavs, ids=[w.ids for w in win], logprobs=[w.logprobs for w in win], sampled_logprobs=[w.sampled_logprobs for w in win],
+                           mean_logprob=[w.mean_logprob for w in win])
+        if n_cand > 1:
+            det.candidate, det.candidate_scores = chosen, scores
+            det.candidates = [[dataclasses.replace(c, hiddens=None) for c in cands[j * n_cand:(j + 1) * n_cand]] for j in range(len(us))]
+        return det
 
     def _window(self, hiddens, s0: int, s1: int, use_decoder: bool = True) -> torch.Tensor:
         """[B, s1-s0] samples s0..s1 of the padded batch of prefix waveforms."""
@@ -1372,24 +1378,19 @@ class ChatTTSPlusPipeline:
         # TorchSeedContext reproduce a request and two requests differ -- and broadcasts it with the speaker table's process group.
         noise_seed = kwargs.pop("noise_seed", None)
         if noise_seed is None:
-            noise_seed = cdist.broadcast_seed(int(torch.randint(0, 2 ** 62, (1,)).item()), self.device)
+            noise_seed = cdist.broadcast_seed(_draw_request_seed(), self.device)
         noise_seed = int(noise_seed)
         kwargs.pop("noise", None); kwargs.pop("utt_ids", None)
         wavs_local: List[torch.Tensor] = []
         limits_all = kwargs.pop("max_new_tokens_per_utterance", None)          # per GLOBAL utterance; each slice gets its own entries
-        if limits_all is not None and len(limits_all) != len(texts):
-            raise _lib.HipBackendError(f"max_new_tokens_per_utterance: {len(limits_all)} entries for {len(texts)} utterances")
         lora_all = kwargs.pop("lora_paths", None)                              # one adapter directory (or None) per GLOBAL utterance; each slice gets its own entries
-        if lora_all is not None and len(lora_all) != len(texts):
-            raise _lib.HipBackendError(f"lora_paths: {len(lora_all)} entries for {len(texts)} utterances")
         ppu_all = kwargs.pop("params_per_utterance", None)                     # one InferCodeParams / dict of overrides per GLOBAL utterance; each slice gets its own
-        if ppu_all is not None and len(ppu_all) != len(texts):
-            raise _lib.HipBackendError(f"params_per_utterance: {len(ppu_all)} entries for {len(texts)} utterances")
+        for name, entries in (("max_new_tokens_per_utterance", limits_all), ("lora_paths", lora_all), ("params_per_utterance", ppu_all)):
+            _check_entries(name, entries, len(texts))
         # resolved against the caller's params_infer_code: run_local below swaps spk_emb for the rank's speaker rows, which an entry must not be compared with
         over_all = per_utterance_overrides(params_infer_code, ppu_all) if ppu_all is not None else None
         ids_out = kwargs.pop("ids_out", None)                                  # optional list: receives this rank's generated ids, in `mine` order
         sink = [] if ids_out is not None else None
-
         continuous = bool(kwargs.pop("continuous", False))      # each rank keeps slice_size decode rows busy over ALL its utterances (infer(continuous=True))
 
         def run_local(indices, rows):
@@ -1398,20 +1399,15 @@ class ChatTTSPlusPipeline:
             for ii in range(0, len(indices), max(step, 1)):
                 sl = indices[ii:ii + step]
                 p = dataclasses.replace(params, spk_emb=rows[ii:ii + len(sl)])
-                kw_sl = dict(kwargs)
-                if limits_all is not None:
-                    kw_sl["max_new_tokens_per_utterance"] = [int(limits_all[i]) for i in sl]
-                if lora_all is not None:
-                    kw_sl["lora_paths"] = [lora_all[i] for i in sl]
-                if over_all is not None:
-                    kw_sl["_utt_overrides"] = [over_all[i] for i in sl]
-                if sink is not None:
-                    kw_sl["_ids_sink"] = sink
+                kw_sl = dict(kwargs, _ids_sink=sink)
+                for key, per_utt in (("max_new_tokens_per_utterance", limits_all), ("lora_paths", lora_all), ("_utt_overrides", over_all)):
+                    if per_utt is not None:
+                        kw_sl[key] = [per_utt[i] for i in sl]
                 for wavs in self._infer([texts[i] for i in sl], False, None, skip_refine_text, False, True, True, False, True,
                                         params_refine_text, p, slice_size=(slice_size if continuous else len(sl)), utt_ids=list(sl), noise="device",
                                         noise_seed=noise_seed, continuous=("throughput" if continuous else False), **kw_sl):
                     wavs_local.extend(wavs)
-                    lens.extend([(int(w.shape[0]) // 256 + 1) // 2 if w.shape[0] else 0 for w in wavs])
+                    lens.extend([prefix_tokens(w.shape[0]) for w in wavs])
             return lens
 
         mine, all_lens = cdist.sharded_generate([len(t) for t in texts], speaker_index, speaker_table, n_spk, dim, self.device, run_local)
