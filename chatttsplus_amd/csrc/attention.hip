@@ -437,6 +437,15 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(const RowMeta* m
     }
 }
 
+// Which kernel runs the attention of a prompt pass of R rows on prompts of T tokens (kernels.h).  Pure host arithmetic; run_layers (the split kernel) and
+// launch_attention (the rest) call it.  fp16: MFMA flash attention, block = (64 queries, head, sequence), from 64 rows; anchored ("schedule_invariant"): at every
+// pass height, 1 row included.
+int prompt_attention_kind(int dtype, int R, int T, int anchor, bool pfs) {
+    if (pfs) return ATTN_SPLIT;
+    if (dtype == 1 && T > 0 && (R >= 64 || anchor)) return anchor ? ATTN_MFMA_ANCHOR : ATTN_MFMA;
+    return ATTN_ROW;
+}
+
 int launch_attention(int dtype, const AttnArgs& a, hipStream_t s) {
     dim3 grid(a.R * a.NH, a.S), block(256);
     const int* done_p = a.st ? &a.st->all_done : nullptr;
@@ -445,11 +454,11 @@ int launch_attention(int dtype, const AttnArgs& a, hipStream_t s) {
     static const int wide_env = diag_env("CTTS_ATTN_WIDE") ? atoi(diag_env("CTTS_ATTN_WIDE")) : -1;     // diagnostic builds: force 8-wave (1) / 4-wave (0) blocks
     const bool wide = (a.S == 1) && (a.st != nullptr) && (wide_env < 0 ? (a.R * a.NH < (a.wide_blocks > 0 ? a.wide_blocks : 256)) : wide_env != 0);
     static const int tiled_env = diag_env("CTTS_PREFILL_ATTN") ? atoi(diag_env("CTTS_PREFILL_ATTN")) : 1;    // diagnostic builds: 0 = prompt attention row by row
-    if (a.st == nullptr && a.S == 1 && a.packed_out != nullptr && (a.R >= 64 || a.anchor) && dtype == 1 && a.T > 0 && (tiled_env >= 1 || a.anchor)) {
-        // prompt pass, fp16: MFMA flash attention, block = (64 queries, head, sequence); anchored ("schedule_invariant"): at every pass height, 1 row included
+    const int kind = (a.st == nullptr && a.S == 1 && a.packed_out != nullptr && (tiled_env >= 1 || a.anchor)) ? prompt_attention_kind(dtype, a.R, a.T, a.anchor, false) : ATTN_ROW;
+    if (kind != ATTN_ROW) {
         const int B = (a.row0 + a.R + a.T - 1) / a.T;                     // sequences 0 .. B-1 may have rows in this pass
         dim3 g3((a.T + 63) / 64, a.NH, B);
-        if (a.anchor) hipLaunchKernelGGL(attn_prefill_mfma_kernel<true>, g3, dim3(256), 0, s, a.meta, a.q, (const half_t*)a.k_cache, (const half_t*)a.v_cache, a.NH, a.R, a);
+        if (kind == ATTN_MFMA_ANCHOR) hipLaunchKernelGGL(attn_prefill_mfma_kernel<true>, g3, dim3(256), 0, s, a.meta, a.q, (const half_t*)a.k_cache, (const half_t*)a.v_cache, a.NH, a.R, a);
         else hipLaunchKernelGGL(attn_prefill_mfma_kernel<false>, g3, dim3(256), 0, s, a.meta, a.q, (const half_t*)a.k_cache, (const half_t*)a.v_cache, a.NH, a.R, a);
     } else if (wide) {
         if (dtype == 1) hipLaunchKernelGGL((attn_decode_kernel<half_t, 8>), grid, dim3(512), 0, s, done_p, a.meta, a.q, a.k_cache, a.v_cache, a.NH, a.S, a);

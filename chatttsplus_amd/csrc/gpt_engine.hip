@@ -252,6 +252,7 @@ struct ctts_gpt {
     std::vector<RowState> fresh_host;
     std::vector<int> seq_host;
     int pre_T = 0;                               // tokens per sequence of the prompt rows being passed (begin: T; admit: T - 1)
+    long pp_rows = 0; int pp_T = 0;              // the last ctts_gpt_prefill / ctts_gpt_score call: its prompt rows and pre_T (debug_read "prompt_plan", "meta_pre", "x_pre"); 0 rows = none since begin
     int B0 = 0;                                  // sequences the current generate() started with (h->B = rows still in the decode batch)
     bool admitted = false;                       // ctts_gpt_admit handed a row of this generate() to another utterance: x_last / meta_dec0 no longer describe the rows
     // per generate()
@@ -1318,7 +1319,7 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
         at.meta = meta; at.st = st; at.part_ml = h->part_ml; at.part_o = h->part_o; at.wide_blocks = p.wide_blocks; at.anchor = p.anchor;
         if (st == nullptr) { at.T = h->pre_T; at.row0 = (int)(meta - h->meta_pre); }       // prompt pass: position of this pass in the flattened [B][T] prompt
         at.packed_out = (S == 1) ? h->attn_packed : nullptr; at.nbg = nbg; at.packed_split = spd ? 1 : 0;
-        if (pfs && S == 1) { if (launch_attention_split(at, h->sp_x_hi, h->sp_x_lo, s)) return 1; }      // writes o_proj's head / tail operand images directly
+        if (prompt_attention_kind(dt, R, at.T, at.anchor, pfs && S == 1) == ATTN_SPLIT) { if (launch_attention_split(at, h->sp_x_hi, h->sp_x_lo, s)) return 1; }      // writes o_proj's head / tail operand images directly
         else if (launch_attention(dt, at, s)) return 1;
         // softmax combine + o_proj + residual (S == 1: attention already wrote the normalised, packed B operand)
         GemmArgs g2 = a;
@@ -1610,6 +1611,7 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
     h->admitted = false;
     h->sampled = false;
     h->segs.clear();                  // (debug_read "decode_plan": nothing planned yet for this batch)
+    h->pp_rows = 0;                   // (debug_read "prompt_plan": no prompt pass yet)
     h->rows_host.assign(B, RowState{});
     for (int b = 0; b < B; ++b) {
         RowState& r = h->rows_host[b];
@@ -1672,6 +1674,7 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
 static int prefill_invariant(ctts_gpt* h, const float* emb, hipStream_t s) {
     const int B = h->B, T = h->T, Tm = T - 1, H = h->H, P = h->share_P ? h->share_P : B;
     const long R = (long)P * Tm;
+    h->pp_rows = R; h->pp_T = h->pre_T;
     for (long r0 = 0; r0 < R; r0 += h->pass_rows) {
         const int n = (int)(R - r0 < h->pass_rows ? R - r0 : h->pass_rows);
         for (long r = r0; r < r0 + n;) {             // x_pre[0, n) <- prompt rows r0 .. r0 + n - 1 of the [B][T - 1] layout (emb is [B][T])
@@ -1706,6 +1709,7 @@ extern "C" int ctts_gpt_prefill(ctts_gpt* h, const float* emb, void* stream) {
     const int P = h->share_P ? h->share_P : h->B;
     const int R = P * h->T;
     const int PASS_ROWS = h->pass_rows;
+    h->pp_rows = R; h->pp_T = h->pre_T;
     for (int r0 = 0; r0 < R; r0 += PASS_ROWS) {
         const int n = (R - r0 < PASS_ROWS) ? R - r0 : PASS_ROWS;
         CTTS_HIP_CHECK(hipMemcpyAsync(h->x_pre, emb + (size_t)r0 * h->H, (size_t)n * h->H * 4, hipMemcpyDeviceToDevice, s));
@@ -1758,6 +1762,7 @@ extern "C" int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* mask, co
     h->pre_T = T;
     if (launch_fill_meta(h->meta_pre, h->meta_dec0, h->st, mask, B, T, h->rope, h->rope_pre, nullptr, B, s)) return 1;
     const long R = (long)B * T;
+    h->pp_rows = R; h->pp_T = T;
     // batch_invariant: the heads on 16-row chunks whatever the block holds (as run_heads pins nbg = 1); the chunk of SCORE_ROWS rows only bounds the scratch
     const int nbg = h->batch_inv ? 1 : 2;
     ScoreRows sr = {};
@@ -2317,6 +2322,8 @@ extern "C" int ctts_gpt_cancel(ctts_gpt* h, int n, const int32_t* rows, void* st
 
 // Diagnostics: copies a named internal buffer to HOST memory (tools/persist_probe.py compares the persistent layer's intermediates with the
 // launch path's).  Synchronises the stream.  Returns the number of bytes copied through *bytes.
+// GEMM kinds of debug_read "prompt_plan": launch_gemm with the norm in the block / on the packed operand, prefill_gemm.hip shape 0 / 1 / 2, prefill_split.hip SP_SHAPE_*
+enum { PP_TILE_NORM = 0, PP_TILE_PACKED = 1, PP_PFG_0 = 2, PP_SPLIT_64 = 5 };
 extern "C" int ctts_gpt_debug_read(ctts_gpt* h, const char* name, void* out, size_t max_bytes, size_t* bytes, void* stream) {
     if (!h || !name || !out) { ctts_set_error("debug_read: null argument"); return 1; }
     const std::string n(name);
@@ -2349,6 +2356,38 @@ extern "C" int ctts_gpt_debug_read(ctts_gpt* h, const char* name, void* out, siz
         memcpy(out, v, sizeof(v));
         if (bytes) *bytes = sizeof(v);
         return 0;
+    }
+    else if (n == "prompt_plan" || n == "meta_pre" || n == "x_pre") {
+        // the passes of the last ctts_gpt_prefill / ctts_gpt_score call: full passes of pass_rows rows, then the rest
+        if (h->pp_rows <= 0) { ctts_set_error("debug_read: %s: no prompt pass has run since begin", name); return 1; }
+        const int passes = (int)((h->pp_rows + h->pass_rows - 1) / h->pass_rows), n_last = (int)(h->pp_rows - (long)(passes - 1) * h->pass_rows);
+        if (n == "meta_pre") { src = h->meta_pre; nb = (size_t)h->pp_rows * sizeof(RowMeta); }      // {KV lane, pos, slot, kv_start} of every prompt row of the call
+        else if (n == "x_pre") { src = h->x_pre; nb = (size_t)n_last * h->H * 4; }                  // the fp32 residual rows the last pass left
+        else {
+            // host only: what plan_layers and the launchers' own choice functions (kernels.h) decide at the two pass heights (no device work, nothing synchronised)
+            const int n_full = passes > 1 ? h->pass_rows : n_last;
+            int32_t v[4 + 2 * 15], k = 0;
+            v[k++] = passes; v[k++] = n_full; v[k++] = n_last; v[k++] = h->pp_T;
+            for (const int R : {n_full, n_last}) {
+                const LayerPlan p = plan_layers(h, R, false, DecodePath{1, 0});
+                const SplitGemmPolicy pol = {h->prefill_pp_blocks, p.prefill_sk_rows, h->sk_scratch, h->sk_cap_floats, h->prefill_small_blocks, h->prefill_ring4_blocks};
+                const int32_t head[] = {p.nbg, p.prepack, p.pfg, p.pfs, p.anchor, p.lora, prompt_attention_kind(h->cfg.dtype, R, h->pp_T, p.anchor, p.pfs && p.S == 1)};
+                for (const int32_t x : head) v[k++] = x;
+                // the four projections as run_layers launches them: {epilogue, n tiles, k tiles, low-rank term present, reads the normalised residual rows}
+                const struct { int epi, nt, kt; bool lora, norm; } proj[4] = {{EPI_QKV, 3 * h->H / 16, h->H / 32, p.lora, true}, {EPI_RESID, h->H / 16, h->H / 32, p.lora, false},
+                                                                              {EPI_SWIGLU, 2 * h->I / 16, h->H / 32, p.lmlp, true}, {EPI_RESID, h->H / 16, h->I / 32, p.lmlp, false}};
+                for (const auto& j : proj) {
+                    int kind = (j.norm && !p.prepack) ? PP_TILE_NORM : PP_TILE_PACKED, sliced = 0;
+                    if (p.pfs) { const SplitGemmShape c = split_gemm_shape(j.epi, R, j.nt, j.kt, j.lora, pol); kind = PP_SPLIT_64 + c.shape; sliced = c.sliced; }
+                    else if (p.pfg) kind = PP_PFG_0 + prefill_gemm_shape(j.epi, R, p.pfg_shape);
+                    v[k++] = kind; v[k++] = sliced;
+                }
+            }
+            if (max_bytes < sizeof(v)) { ctts_set_error("debug_read: buffer too small"); return 1; }
+            memcpy(out, v, sizeof(v));
+            if (bytes) *bytes = sizeof(v);
+            return 0;
+        }
     }
     if (!src) { ctts_set_error("debug_read: unknown or unallocated buffer '%s'", name); return 1; }
     if (nb > max_bytes) nb = max_bytes;

@@ -207,6 +207,13 @@ struct SplitGemmPolicy {
 };
 int launch_prefill_split_gemm(int epi, const GemmArgs& a, const void* Wsplit, const void* Xhi, const void* Xlo, void* act_hi, void* act_lo,
                               float scale, const SplitGemmPolicy& pol, hipStream_t s);      // Wsplit: [n tile][k tile][head | tail][lane][16 B] (common.h split_t)
+// What the prompt-pass launchers choose, as pure host functions: the launchers call them, and so does ctts_gpt_debug_read "prompt_plan" (one source of truth).
+enum { SP_SHAPE_64 = 0, SP_SHAPE_RING4 = 1, SP_SHAPE_RING2 = 2, SP_SHAPE_PP3 = 3, SP_SHAPE_PP4 = 4 };       // 64 x 64 / 128 x 128 on the 4-stage ring / ... on the 2-stage ring / counter-phased NT 3 / 4
+struct SplitGemmShape { int shape; bool sliced; };
+SplitGemmShape split_gemm_shape(int epi, int R, int n_tiles, int k_tiles, bool lora_term, const SplitGemmPolicy& pol);      // prefill_split.hip (epi: EPI_QKV / EPI_SWIGLU / EPI_RESID)
+int prefill_gemm_shape(int epi, int R, int shape_pin);                                                                        // prefill_gemm.hip: 0 = 128 x 128, 1 = 256 x 128, 2 = 256 x 256
+enum { ATTN_ROW = 0, ATTN_MFMA = 1, ATTN_MFMA_ANCHOR = 2, ATTN_SPLIT = 3 };                                 // row kernel / MFMA flash / ... anchored at the first real key / split kernel (prefill_split.hip)
+int prompt_attention_kind(int dtype, int R, int T, int anchor, bool pfs);                                                    // attention.hip; S == 1 (every prompt pass)
 int launch_norm_pack(int dtype, const float* x, void* out_packed, int R, int nbg, float eps, hipStream_t s);
 int launch_attention(int dtype, const AttnArgs& a, hipStream_t s);
 int launch_sampler(const SamplerArgs& a, int blocks, hipStream_t s);

@@ -284,12 +284,20 @@ static int pf_shape(int shape, const GemmArgs& a, const void* X, int ktiles, hip
     return pf_launch<EPI, 2, 2, 4>(a, X, ktiles, s);
 }
 
+// Block shape of one projection (kernels.h): 0 = 128 x 128, 1 = 256 x 128, 2 = 256 x 256.  Pure host arithmetic; launch_prefill_gemm itself calls it.
+// measured (32 x 512 / 8 x 2000 tokens per pass): all 128 x 128 9.99 / 13.50 ms; gate|up on 256 x 128 9.70 / 13.37; gate|up + QKV on 256 x 128
+// 9.79 / 13.64; everything on 256 x 256 10.10 / 14.08.  Below 8192 rows the 128 x 128 grid fills the chip better (4 x 512: 2.51 vs 2.57 ms).
+int prefill_gemm_shape(int epi, int R, int shape_pin) {
+    if (shape_pin >= 0) return shape_pin;                  // "schedule_invariant": no choice may follow the pass height (the shapes share one k order per output; pinned all the same)
+    return (epi == EPI_SWIGLU && R >= 8192) ? 1 : 0;
+}
+
 // fp16 only.  X = packed activations (norm_packed / attn_packed / act); the operand buffers must cover whole blocks of rows
 // (gpt_engine.hip allocates them for PASS_ROWS + 256 rows).
 int launch_prefill_gemm(int epi, const GemmArgs& a, hipStream_t s, int shape_pin) {
     const void* X = a.xpacked;
     const int ktiles = a.K / 32;
-    // block shape per projection: 0 = 128 x 128, 1 = 256 x 128, 2 = 256 x 256.  CTTS_PF_SHAPE = "qkv,gateup,resid" overrides (diagnostic).
+    // CTTS_PF_SHAPE = "qkv,gateup,resid" overrides the block shape per projection (diagnostic builds).
     static int shape_env[3] = {-1, -1, -1};
     static const bool parsed = [] {
         const char* e = diag_env("CTTS_PF_SHAPE");
@@ -299,10 +307,7 @@ int launch_prefill_gemm(int epi, const GemmArgs& a, hipStream_t s, int shape_pin
     (void)parsed;
     const int which = epi == EPI_QKV ? 0 : epi == EPI_SWIGLU ? 1 : 2;
     int shape = shape_env[which];
-    // measured (32 x 512 / 8 x 2000 tokens per pass): all 128 x 128 9.99 / 13.50 ms; gate|up on 256 x 128 9.70 / 13.37; gate|up + QKV on 256 x 128
-    // 9.79 / 13.64; everything on 256 x 256 10.10 / 14.08.  Below 8192 rows the 128 x 128 grid fills the chip better (4 x 512: 2.51 vs 2.57 ms).
-    if (shape_pin >= 0) shape = shape_pin;                 // "schedule_invariant": no choice may follow the pass height (the shapes share one k order per output; pinned all the same)
-    else if (shape < 0) shape = (epi == EPI_SWIGLU && a.R >= 8192) ? 1 : 0;
+    if (shape_pin >= 0 || shape < 0) shape = prefill_gemm_shape(epi, a.R, shape_pin);
     if (epi == EPI_QKV) return pf_shape<EPI_QKV>(shape, a, X, ktiles, s);
     if (epi == EPI_SWIGLU) return pf_shape<EPI_SWIGLU>(shape, a, X, ktiles, s);
     if (epi == EPI_RESID) return pf_shape<EPI_RESID>(shape, a, X, ktiles, s);

@@ -637,6 +637,37 @@ __global__ __launch_bounds__(256) void resid_combine_kernel(const float* part, c
     ((f32x4*)x)[i] = o;
 }
 
+// What sp_launch launches (kernels.h): block shape and whether the down projection's K is sliced.  Pure host arithmetic; sp_launch itself calls it.
+SplitGemmShape split_gemm_shape(int epi, int R, int n_tiles, int k_tiles, bool lora_term, const SplitGemmPolicy& pol) {
+    // Block shape by a round count (256 CUs; measured per-round times at K = 768, 32 x 512 prompt rows: 128 x 128 blocks, 512 at a time: 36 us; 256 x 256 blocks,
+    // one per CU: 60 us; 256 x 192: 45 us): the 128 x 128 kernel for short passes, the counter-phased kernel once its blocks fill the chip.  pp_min_blocks < 0 forces
+    // the counter-phased kernel with NT = -pp_min_blocks (tests, A/B).
+    const int pp_min_blocks = pol.pp_min_blocks;
+    const int rb = (R + 255) / 256, nt = n_tiles;
+    const int b_old = (nt / 8) * ((R + 127) / 128);
+    const long c_old = (long)((b_old + 511) / 512) * 36;
+    const int b4 = (nt % 16 == 0) ? (nt / 16) * rb : 0, b3 = (nt % 12 == 0) ? (nt / 12) * rb : 0;
+    const long c4 = b4 ? (long)((b4 + 255) / 256) * 60 : (1L << 40), c3 = b3 ? (long)((b3 + 255) / 256) * 45 : (1L << 40);
+    int shape = 0;                                          // 0: 128 x 128; 3 / 4: counter-phased, NT
+    if (pp_min_blocks < 0) shape = (-pp_min_blocks == 3 && b3) ? 3 : (b4 ? 4 : (b3 ? 3 : 0));
+    else if (pp_min_blocks > 0) {
+        if (b4 >= pp_min_blocks && c4 < c_old && c4 <= c3) shape = 4;
+        else if (b3 >= pp_min_blocks && c3 < c_old) shape = 3;
+    }
+    // Short passes of the down projection (K = 3072: 96 k-tiles in a row, 6 blocks per 128 rows -- 24 blocks on 256 CUs at 448 rows, 75 of the layer's 170 us): K sliced
+    // four ways over grid.z, the slices' shares parked in `pol.sk_scratch`, resid_combine_kernel adds them in slice order and the residual.  Another summation order
+    // than the unsliced kernel's (the usual 1e-7); a.lora_delta stands aside from it (the o_proj products have K = 768; a down_proj term
+    // takes the unsliced kernel, whose epilogue adds it).
+    const size_t rows_pad = (size_t)((R + 127) / 128) * 128;
+    const bool sliced = epi == EPI_RESID && shape == 0 && pol.sk_rows > 0 && R <= pol.sk_rows && k_tiles >= 64 && (k_tiles & 3) == 0 && !lora_term &&
+                        pol.sk_scratch != nullptr && 4 * rows_pad * (size_t)(nt * 16) <= pol.sk_cap_floats;
+    // passes so short that even the sliced grids leave most CUs idle: 64 x 64 blocks (four times as many), 4-stage ring of 16 KB stages
+    const bool small = shape == 0 && pol.small_blocks > 0 && (sliced ? 4 : 1) * b_old <= pol.small_blocks;
+    if (shape) return {shape == 4 ? SP_SHAPE_PP4 : SP_SHAPE_PP3, false};
+    if (small) return {SP_SHAPE_64, sliced};
+    return {(sliced ? 4 : 1) * b_old <= pol.ring4_blocks ? SP_SHAPE_RING4 : SP_SHAPE_RING2, sliced};
+}
+
 template <int EPI>
 static int sp_launch(SplitGemm& p, const GemmArgs& a, const SplitGemmPolicy& pol, hipStream_t s) {
     static bool configured = false;
@@ -653,37 +684,17 @@ static int sp_launch(SplitGemm& p, const GemmArgs& a, const SplitGemmPolicy& pol
         }
         configured = true;
     }
-    // Block shape by a round count (256 CUs; measured per-round times at K = 768, 32 x 512 prompt rows: 128 x 128 blocks, 512 at a time: 36 us; 256 x 256 blocks,
-    // one per CU: 60 us; 256 x 192: 45 us): the 128 x 128 kernel for short passes, the counter-phased kernel once its blocks fill the chip.  pp_min_blocks < 0 forces
-    // the counter-phased kernel with NT = -pp_min_blocks (tests, A/B).
-    const int pp_min_blocks = pol.pp_min_blocks;
-    const int rb = (p.R + 255) / 256, nt = a.n_row_tiles;
-    const int b_old = (nt / 8) * ((p.R + 127) / 128);
-    const long c_old = (long)((b_old + 511) / 512) * 36;
-    const int b4 = (nt % 16 == 0) ? (nt / 16) * rb : 0, b3 = (nt % 12 == 0) ? (nt / 12) * rb : 0;
-    const long c4 = b4 ? (long)((b4 + 255) / 256) * 60 : (1L << 40), c3 = b3 ? (long)((b3 + 255) / 256) * 45 : (1L << 40);
-    int shape = 0;                                          // 0: 128 x 128; 3 / 4: counter-phased, NT
-    if (pp_min_blocks < 0) shape = (-pp_min_blocks == 3 && b3) ? 3 : (b4 ? 4 : (b3 ? 3 : 0));
-    else if (pp_min_blocks > 0) {
-        if (b4 >= pp_min_blocks && c4 < c_old && c4 <= c3) shape = 4;
-        else if (b3 >= pp_min_blocks && c3 < c_old) shape = 3;
-    }
-    // Short passes of the down projection (K = 3072: 96 k-tiles in a row, 6 blocks per 128 rows -- 24 blocks on 256 CUs at 448 rows, 75 of the layer's 170 us): K sliced
-    // four ways over grid.z, the slices' shares parked in `pol.sk_scratch`, resid_combine_kernel adds them in slice order and the residual.  Another summation order
-    // than the unsliced kernel's (the usual 1e-7); a.lora_delta stands aside from it (the o_proj products have K = 768; a down_proj term
-    // takes the unsliced kernel, whose epilogue adds it).
+    const SplitGemmShape ch = split_gemm_shape(EPI == SP_EPI_SWIGLU_LORA ? (int)EPI_SWIGLU : (int)EPI, p.R, a.n_row_tiles, p.ktiles, a.lora_delta != nullptr, pol);
+    const int nt = a.n_row_tiles, rb = (p.R + 255) / 256, shape = ch.shape;
+    const bool sliced = ch.sliced;
     const size_t rows_pad = (size_t)((p.R + 127) / 128) * 128;
-    const bool sliced = EPI == EPI_RESID && shape == 0 && pol.sk_rows > 0 && p.R <= pol.sk_rows && p.ktiles >= 64 && (p.ktiles & 3) == 0 && a.lora_delta == nullptr &&
-                        pol.sk_scratch != nullptr && 4 * rows_pad * (size_t)(nt * 16) <= pol.sk_cap_floats;
-    // passes so short that even the sliced grids leave most CUs idle: 64 x 64 blocks (four times as many), 4-stage ring of 16 KB stages
-    const bool small = shape == 0 && pol.small_blocks > 0 && (sliced ? 4 : 1) * b_old <= pol.small_blocks;
     const dim3 g64(nt / 4, (p.R + 63) / 64, sliced ? 4 : 1);
     if (sliced) {
         GemmArgs ap = a;
         ap.part_out = pol.sk_scratch;
         p.kt_per = p.ktiles / 4; p.part_stride = rows_pad * (size_t)(nt * 16);
-        if (small) hipLaunchKernelGGL((prefill_split_gemm_kernel<EPI_PART, 4, 2>), g64, dim3(256), 4 * SP_STAGE / 2, s, p, ap);
-        else if (4 * b_old <= pol.ring4_blocks) hipLaunchKernelGGL((prefill_split_gemm_kernel<EPI_PART, 4>), dim3(nt / 8, (p.R + 127) / 128, 4), dim3(256), 4 * SP_STAGE, s, p, ap);
+        if (shape == SP_SHAPE_64) hipLaunchKernelGGL((prefill_split_gemm_kernel<EPI_PART, 4, 2>), g64, dim3(256), 4 * SP_STAGE / 2, s, p, ap);
+        else if (shape == SP_SHAPE_RING4) hipLaunchKernelGGL((prefill_split_gemm_kernel<EPI_PART, 4>), dim3(nt / 8, (p.R + 127) / 128, 4), dim3(256), 4 * SP_STAGE, s, p, ap);
         else hipLaunchKernelGGL((prefill_split_gemm_kernel<EPI_PART>), dim3(nt / 8, (p.R + 127) / 128, 4), dim3(256), SP_RING * SP_STAGE, s, p, ap);
         CTTS_HIP_CHECK(hipGetLastError());
         const int n4 = p.R * nt * 4;                        // f32x4 elements of [R][N]
@@ -691,10 +702,10 @@ static int sp_launch(SplitGemm& p, const GemmArgs& a, const SplitGemmPolicy& pol
         CTTS_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    if (shape == 4) hipLaunchKernelGGL((prefill_split_gemm_pp_kernel<EPI, 4>), dim3(nt / 16, rb), dim3(512), 2 * SPB_STAGE, s, p, a);
-    else if (shape == 3) hipLaunchKernelGGL((prefill_split_gemm_pp_kernel<EPI, 3>), dim3(nt / 12, rb), dim3(512), 2 * SPB_STAGE, s, p, a);
-    else if (small) hipLaunchKernelGGL((prefill_split_gemm_kernel<EPI, 4, 2>), g64, dim3(256), 4 * SP_STAGE / 2, s, p, a);
-    else if (b_old <= pol.ring4_blocks) hipLaunchKernelGGL((prefill_split_gemm_kernel<EPI, 4>), dim3(nt / 8, (p.R + 127) / 128), dim3(256), 4 * SP_STAGE, s, p, a);      // at most one block per CU anyway
+    if (shape == SP_SHAPE_PP4) hipLaunchKernelGGL((prefill_split_gemm_pp_kernel<EPI, 4>), dim3(nt / 16, rb), dim3(512), 2 * SPB_STAGE, s, p, a);
+    else if (shape == SP_SHAPE_PP3) hipLaunchKernelGGL((prefill_split_gemm_pp_kernel<EPI, 3>), dim3(nt / 12, rb), dim3(512), 2 * SPB_STAGE, s, p, a);
+    else if (shape == SP_SHAPE_64) hipLaunchKernelGGL((prefill_split_gemm_kernel<EPI, 4, 2>), g64, dim3(256), 4 * SP_STAGE / 2, s, p, a);
+    else if (shape == SP_SHAPE_RING4) hipLaunchKernelGGL((prefill_split_gemm_kernel<EPI, 4>), dim3(nt / 8, (p.R + 127) / 128), dim3(256), 4 * SP_STAGE, s, p, a);      // at most one block per CU anyway
     else hipLaunchKernelGGL((prefill_split_gemm_kernel<EPI>), dim3(nt / 8, (p.R + 127) / 128), dim3(256), SP_RING * SP_STAGE, s, p, a);
     CTTS_HIP_CHECK(hipGetLastError());
     return 0;

@@ -1889,5 +1889,22 @@ class GPT:
             raise _lib.HipBackendError(f"decode_plan: the library returned {nb.value} bytes, this wrapper knows {len(self.DECODE_PLAN_FIELDS)} fields")
         return dict(zip(self.DECODE_PLAN_FIELDS, (int(v) for v in buf)))
 
+    # per pass height: the layer plan's prompt fields, the attention kind (PROMPT_ATTN_KINDS) and per projection a GEMM kind (PROMPT_GEMM_KINDS) and `sliced`
+    _PROMPT_HEIGHT_FIELDS = ("nbg", "prepack", "pfg", "pfs", "anchor", "lora", "attn", "qkv", "qkv_sliced", "o", "o_sliced", "gu", "gu_sliced", "down", "down_sliced")
+    PROMPT_PLAN_FIELDS = ("passes", "rows_full", "rows_last", "pre_T") + _PROMPT_HEIGHT_FIELDS + tuple("last_" + f for f in _PROMPT_HEIGHT_FIELDS)
+    PROMPT_ATTN_KINDS = ("row", "mfma", "mfma_anchor", "split")
+    PROMPT_GEMM_KINDS = ("tile_norm", "tile_packed", "pfg0", "pfg1", "pfg2", "split64", "ring4", "ring2", "pp3", "pp4")
+
+    def prompt_plan(self) -> dict:
+        """The launch plans of the prompt passes of the last prefill / score call (ctts_gpt_debug_read "prompt_plan"): host arithmetic only, no device work.
+        `passes` passes, the full ones `rows_full` rows high, the last `rows_last`; the unprefixed fields describe a full pass, `last_*` the last pass (the same
+        plan when the call is one pass).  `attn` indexes PROMPT_ATTN_KINDS, `qkv` / `o` / `gu` / `down` index PROMPT_GEMM_KINDS."""
+        buf = (C.c_int32 * len(self.PROMPT_PLAN_FIELDS))()
+        nb = C.c_size_t(0)
+        _lib.check(self._lib.ctts_gpt_debug_read(self._h, b"prompt_plan", buf, C.sizeof(buf), C.byref(nb), None), "debug_read(prompt_plan)")
+        if nb.value != C.sizeof(buf):
+            raise _lib.HipBackendError(f"prompt_plan: the library returned {nb.value} bytes, this wrapper knows {len(self.PROMPT_PLAN_FIELDS)} fields")
+        return dict(zip(self.PROMPT_PLAN_FIELDS, (int(v) for v in buf)))
+
     def step_bytes(self, B: int, mean_ctx: float) -> float:
         return float(self._lib.ctts_gpt_step_bytes(self._h, B, float(mean_ctx)))

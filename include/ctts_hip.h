@@ -180,7 +180,13 @@ int ctts_gpt_get_option(ctts_gpt* h, const char* name, int* value);      /* ever
  * "decode_plan" is computed on the host (no device work, no synchronisation, no effect on any launch): the launch plan of a decode step of the current batch on the path
  * of the last step the last ctts_gpt_decode call planned, as 23 int32 in this order -- B, path.splits, path.persist, then the layer plan S, nbg, chunks, dts, pf_kb, valu,
  * wide_blocks, splitd, prepack, xhm, spd, down_sk, fuse_heads, lora, then the residual stream's form for the heads parts, xh, logits, split, nbg, valu.  An error before the
- * first decode call of a batch. */
+ * first decode call of a batch.
+ * "prompt_plan" likewise (host only): the launch plans of the prompt passes of the last ctts_gpt_prefill / ctts_gpt_score call, as 34 int32 -- passes, rows of a full pass,
+ * rows of the last pass, tokens per sequence of the prompt rows (T; T - 1 under "batch_invariant" / "schedule_invariant"), then for each of the two pass heights (full, last)
+ * nbg, prepack, pfg, pfs, anchor, lora, the attention kind (0 row kernel, 1 MFMA flash, 2 MFMA flash anchored, 3 split kernel) and for each of qkv, o, gate|up, down a GEMM
+ * kind (0 tile kernel with the norm in the block, 1 tile kernel on the packed operand, 2 / 3 / 4 prefill_gemm shape 0 / 1 / 2, 5 split 64 x 64, 6 split ring4, 7 split ring2,
+ * 8 split pp3, 9 split pp4) and `sliced`.  "meta_pre": the RowMeta {KV lane, pos, slot, kv_start} of every prompt row of that call; "x_pre": the fp32 residual rows its
+ * last pass left, rows x H (both synchronise).  All three are an error while no prompt pass has run since ctts_gpt_begin. */
 int ctts_gpt_debug_read(ctts_gpt* h, const char* name, void* out, size_t max_bytes, size_t* bytes, void* stream);
 
 /* replaces GPT.from_pretrained -> load_state_dict (gpt.py:84-85).  `name` is the reference

@@ -291,6 +291,7 @@ class OracleGPT:
             u = F.linear(h, self.sd[p + "mlp.up_proj.weight"])
             x = res + F.linear(F.silu(g) * u, self.sd[p + "mlp.down_proj.weight"])   # llama.py:214
         self.kv_len = Ltot
+        self.last_residual = x                                          # [B,q,H] the residual stream before the final norm (tests/test_gpu_prompt_plans.py)
         return self._rms(x, self.sd["gpt.norm.weight"])                 # llama.py:1002
 
     def code_logits(self, hidden_last: torch.Tensor) -> torch.Tensor:
