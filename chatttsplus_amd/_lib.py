@@ -143,6 +143,7 @@ SYMBOLS = [
     ("ctts_enc_set_weight", C.c_int, [_P, C.c_char_p, _P, C.c_size_t]),
     ("ctts_enc_finalize", C.c_int, [_P]),
     ("ctts_dvae_encode", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P]),
+    ("ctts_dvae_encode_batch", C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, _P]),
 ]
 
 _lib = None

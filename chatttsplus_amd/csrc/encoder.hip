@@ -20,6 +20,11 @@
 
 struct EncConvNext { float *dw_w, *dw_b, *ln_w, *ln_b, *w1, *b1, *w2, *b2, *gamma; };
 
+// one utterance of a ctts_dvae_encode_batch call; the call's device table is [EncUtt x B][Fs x B][Ts x B], uploaded once
+struct EncUtt { const float* wav; int* ids; float *mel, *feat; int n, F, T, pad; };
+#define ENC_TAB_BYTES ((size_t)CTTS_ENC_MAX_BATCH * (sizeof(EncUtt) + 8))
+#define ENC_BATCH_WS 4
+
 struct ctts_enc {
     ctts_enc_cfg cfg;
     std::map<std::string, std::vector<float>> host;
@@ -30,6 +35,14 @@ struct ctts_enc {
     float *xp, *spec, *mag, *melcl, *d1, *x2, *b128, *y, *ln, *mid, *feat;
     int* d_T;
     int Fmax, spec_ld, mag_ld, mel_ld;
+    // batch path (ctts_dvae_encode_batch): `ws` is the workspace set it chunks a batch into -- the single-clip buffers above until a
+    // call needs more, then a set ENC_BATCH_WS times as large, allocated once; the per-call tables go through a pinned ring
+    struct Ws { float *xp, *spec, *mag, *melcl, *d1, *x2, *b128, *y, *ln, *mid, *feat; size_t n_xp, rowsF, rowsD1, rowsT; } ws = {};
+    bool ws_big = false;
+    char *pin = nullptr, *d_tab = nullptr;
+    hipEvent_t pin_ev[4] = {};
+    bool pin_used[4] = {};
+    int pin_next = 0;
 };
 
 static int ealloc(ctts_enc* h, float** p, size_t n) {
@@ -114,6 +127,96 @@ __global__ __launch_bounds__(64) void gfsq_kernel(const float* feat, const float
     }
 }
 
+// ---- the same kernels keyed by utterance (ctts_dvae_encode_batch): blockIdx.y (gfsq: z) = utterance of the chunk, its sizes and
+// pointers come from the EncUtt table, its workspace region from a batch stride.  Arithmetic term for term that of the kernels above.
+__global__ void reflect_pad_batch_kernel(const EncUtt* U, float* xp, long sxp, int half) {
+    const EncUtt u = U[blockIdx.y];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, n = u.n;
+    if (i >= n + 2 * half) return;
+    int j = i - half;
+    if (j < 0) j = -j;
+    if (j >= n) j = 2 * (n - 1) - j;
+    xp[(size_t)blockIdx.y * sxp + i] = (j >= 0 && j < n) ? u.wav[j] : 0.f;
+}
+
+__global__ void magnitude_batch_kernel(const float* spec, float* mag, const int* Fs, long ss, long sm, int nb, int lds, int ldm) {
+    const int f = blockIdx.x;
+    if (f >= Fs[blockIdx.y]) return;
+    spec += (size_t)blockIdx.y * ss; mag += (size_t)blockIdx.y * sm;
+    for (int k = threadIdx.x; k < ldm; k += blockDim.x) {
+        float v = 0.f;
+        if (k < nb) {
+            const float re = spec[(size_t)f * lds + k], im = spec[(size_t)f * lds + nb + k];
+            v = sqrtf(re * re + im * im);
+        }
+        mag[(size_t)f * ldm + k] = v;
+    }
+}
+
+// zeroes, for every utterance of the chunk, the guard rows the single-clip path clears with its memsets: mel image rows 0 and F + 1,
+// d1 rows 0 and F + 1 .. F + 3, x2 and b128 rows 0 and T + 1 (a longer clip of an earlier call or chunk may have left data there)
+__global__ void guard_rows_batch_kernel(const EncUtt* U, float* melcl, float* d1, float* x2, float* b128, long smel, long sd1, long sx2, long sb,
+                                        int mel_ld, int D, int BN) {
+    const EncUtt u = U[blockIdx.x];
+    const size_t z = blockIdx.x;
+    float *m = melcl + z * smel, *d = d1 + z * sd1, *x = x2 + z * sx2, *b = b128 + z * sb;
+    for (int c = threadIdx.x; c < mel_ld; c += blockDim.x) { m[c] = 0.f; m[(size_t)(u.F + 1) * mel_ld + c] = 0.f; }
+    for (int c = threadIdx.x; c < D; c += blockDim.x) {
+        d[c] = 0.f;
+        for (int r = 1; r <= 3; ++r) d[(size_t)(u.F + r) * D + c] = 0.f;
+        x[c] = 0.f; x[(size_t)(u.T + 1) * D + c] = 0.f;
+    }
+    for (int c = threadIdx.x; c < BN; c += blockDim.x) { b[c] = 0.f; b[(size_t)(u.T + 1) * BN + c] = 0.f; }
+}
+
+// test hooks: mel image -> [n_mels][F_u], encoder output -> [T_u][OD]; an utterance without the hook is skipped
+__global__ void mel_out_batch_kernel(const EncUtt* U, const float* melcl, long smel, int n_mels, int ld) {
+    const EncUtt u = U[blockIdx.y];
+    const int f = blockIdx.x, c = threadIdx.x;
+    if (!u.mel || f >= u.F || c >= n_mels) return;
+    u.mel[(size_t)c * u.F + f] = melcl[(size_t)blockIdx.y * smel + (size_t)(f + 1) * ld + c];
+}
+__global__ void feat_out_batch_kernel(const EncUtt* U, const float* feat, long sf, int OD) {
+    const EncUtt u = U[blockIdx.y];
+    const int t = blockIdx.x;
+    if (!u.feat || t >= u.T) return;
+    for (int c = threadIdx.x; c < OD; c += blockDim.x) u.feat[(size_t)t * OD + c] = feat[(size_t)blockIdx.y * sf + (size_t)t * OD + c];
+}
+
+__global__ __launch_bounds__(64) void gfsq_batch_kernel(const EncUtt* U, const float* feat, long sf, const float* w, const float* b, int per, int ld, int R, int pre_bound) {
+    const EncUtt u = U[blockIdx.z];
+    const int t = blockIdx.x, g = blockIdx.y, lane = threadIdx.x, T = u.T;
+    if (t >= T) return;
+    const float* x = feat + (size_t)blockIdx.z * sf + (size_t)t * ld + (size_t)g * per;
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int c = lane; c < per; c += 64) {
+        const float xv = x[c];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) z[j] += w[((size_t)g * 4 + j) * per + c] * xv;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) z[j] = wave_sum(z[j]) + b[g * 4 + j];
+    if (lane != 0) return;
+    const float half_l = 2.002f;
+    float res[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) res[j] = pre_bound ? tanhf(z[j]) * half_l : z[j];
+    float scale = 1.0f;
+    for (int r = 0; r < R; ++r) {
+        int idx = 0, basis = 1;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float q = rintf(tanhf(res[j] / scale) * half_l);
+            const float code = q / 2.0f;
+            idx += (int)(code * 2.0f + 2.0f) * basis;
+            basis *= 5;
+            res[j] -= code * scale;
+        }
+        u.ids[(size_t)(g * R + r) * T + t] = idx;
+        scale *= 0.25f;
+    }
+}
+
 extern "C" int ctts_enc_create(const ctts_enc_cfg* c, ctts_enc** out) {
     if (!c || !out) { ctts_set_error("null argument"); return 1; }
     if (c->dim != 512 || c->enc_hidden != 256 || c->enc_bn % 64 || c->enc_odim % 64 || c->n_fft != 1024 || c->hop != 256 || c->n_mels > 112 ||
@@ -128,6 +231,8 @@ extern "C" int ctts_enc_create(const ctts_enc_cfg* c, ctts_enc** out) {
 }
 extern "C" void ctts_enc_destroy(ctts_enc* h) {
     if (!h) return;
+    if (h->pin) (void)hipHostFree(h->pin);
+    for (hipEvent_t e : h->pin_ev) if (e) (void)hipEventDestroy(e);
     for (void* p : h->allocs) (void)hipFree(p);
     delete h;
 }
@@ -212,6 +317,11 @@ extern "C" int ctts_enc_finalize(ctts_enc* h) {
         return 1;
     CTTS_HIP_CHECK(hipMalloc((void**)&h->d_T, 16));
     h->allocs.push_back(h->d_T);
+    h->ws = {h->xp, h->spec, h->mag, h->melcl, h->d1, h->x2, h->b128, h->y, h->ln, h->mid, h->feat, (size_t)(r64(Fmax) + 64) * c.hop + N, Fp, Fp + 136, Tp};
+    CTTS_HIP_CHECK(hipMalloc((void**)&h->d_tab, ENC_TAB_BYTES));
+    h->allocs.push_back(h->d_tab);
+    CTTS_HIP_CHECK(hipHostMalloc((void**)&h->pin, 4 * ENC_TAB_BYTES, hipHostMallocDefault));
+    for (hipEvent_t& e : h->pin_ev) CTTS_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     h->host.clear();
     h->finalized = true;
     return 0;
@@ -288,5 +398,149 @@ extern "C" int ctts_dvae_encode(ctts_enc* h, const float* wav, int n_samples, in
     hipLaunchKernelGGL(gfsq_kernel, dim3(T, c.vq_groups), dim3(64), 0, s, h->feat, h->pin_w, h->pin_b, (int*)ids, T, OD / c.vq_groups, OD,
                        c.vq_residuals, c.pre_bound);
     CTTS_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---- batch ----------------------------------------------------------------------------------------------------------------------------
+// Workspace rows one utterance region needs when the longest clip of its chunk has Fc frames: the single-clip formulas of ctts_enc_finalize
+// with Fc in place of Fmax (64-row GEMM tiles stay inside the region, guard rows included).
+struct EncRegion { size_t n_xp, rowsF, rowsD1, rowsT; };
+static EncRegion enc_region(const ctts_enc_cfg& c, int Fc) {
+    const size_t Fp = r64(Fc) + 64 + 8;
+    return {(size_t)(r64(Fc) + 64) * c.hop + c.n_fft, Fp, Fp + 136, (size_t)r64(Fc / 2 + 1) + 64 + 8};
+}
+static bool enc_fits(const ctts_enc::Ws& w, const EncRegion& r, size_t nb) {
+    return nb * r.n_xp <= w.n_xp && nb * r.rowsF <= w.rowsF && nb * r.rowsD1 <= w.rowsD1 && nb * r.rowsT <= w.rowsT;
+}
+
+// one launch sequence for utterances [u0, u0 + nb) of the call's table; Fc / Tc / nmax: the longest of the chunk
+static int encode_chunk(ctts_enc* h, int u0, int nb, int Fc, int Tc, int nmax, bool any_mel, bool any_feat, hipStream_t s) {
+    const ctts_enc_cfg& c = h->cfg;
+    const ctts_enc::Ws& w = h->ws;
+    const int N = c.n_fft, hop = c.hop, NB = N / 2 + 1, D = c.dim, HD = c.enc_hidden, BN = c.enc_bn, OD = c.enc_odim;
+    const EncRegion r = enc_region(c, Fc);
+    const EncUtt* U = (const EncUtt*)h->d_tab + u0;
+    const int* Fs = (const int*)(h->d_tab + (size_t)CTTS_ENC_MAX_BATCH * sizeof(EncUtt)) + u0;
+    const int* Ts = Fs + CTTS_ENC_MAX_BATCH;
+    const long sxp = (long)r.n_xp, sspec = (long)r.rowsF * h->spec_ld, smag = (long)r.rowsF * h->mag_ld, smel = (long)r.rowsF * h->mel_ld,
+               sd1 = (long)r.rowsD1 * D, sx2 = (long)r.rowsT * D, sb = (long)r.rowsT * BN, sy = (long)r.rowsT * HD, smid = (long)r.rowsT * HD * 4,
+               sfeat = (long)r.rowsT * OD;
+    hipLaunchKernelGGL(reflect_pad_batch_kernel, dim3((nmax + N + 255) / 256, nb), dim3(256), 0, s, U, w.xp, sxp, N / 2);
+    CTTS_HIP_CHECK(hipGetLastError());
+    GemmF32Args g = {};
+    g.A = w.xp; g.lda = hop; g.sA = sxp; g.W = h->basis; g.ldw = N; g.C = w.spec; g.ldc = h->spec_ld; g.sC = sspec; g.M = Fc; g.Ms = Fs; g.N = 2 * NB; g.K = N;
+    if (launch_gemm_f32(EP_NONE, g, nb, s)) return 1;                                      // torch.stft (dvae.py:186-193)
+    hipLaunchKernelGGL(magnitude_batch_kernel, dim3(Fc, nb), dim3(256), 0, s, w.spec, w.mag, Fs, sspec, smag, NB, h->spec_ld, h->mag_ld);
+    CTTS_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(guard_rows_batch_kernel, dim3(nb), dim3(256), 0, s, U, w.melcl, w.d1, w.x2, w.b128, smel, sd1, sx2, sb, h->mel_ld, D, BN);
+    CTTS_HIP_CHECK(hipGetLastError());
+    GemmF32Args gm = {};
+    gm.A = w.mag; gm.lda = h->mag_ld; gm.sA = smag; gm.W = h->fbw; gm.ldw = h->mag_ld; gm.C = w.melcl + h->mel_ld; gm.ldc = h->mel_ld; gm.sC = smel;
+    gm.M = Fc; gm.Ms = Fs; gm.N = c.n_mels; gm.K = h->mag_ld; gm.scale = h->coef;
+    if (launch_gemm_f32(EP_LOGCLIP_DIV, gm, nb, s)) return 1;                              // MelScale, log(clip), / coef
+    if (any_mel) {
+        hipLaunchKernelGGL(mel_out_batch_kernel, dim3(Fc, nb), dim3(128), 0, s, U, w.melcl, smel, c.n_mels, h->mel_ld);
+        CTTS_HIP_CHECK(hipGetLastError());
+    }
+    GemmF32Args g1 = {};
+    g1.A = w.melcl; g1.lda = h->mel_ld; g1.sA = smel; g1.W = h->ds0_w; g1.ldw = 3 * h->mel_ld; g1.C = w.d1 + D; g1.ldc = D; g1.sC = sd1;
+    g1.M = Fc; g1.Ms = Fs; g1.N = D; g1.K = 3 * h->mel_ld; g1.bias = h->ds0_b;
+    if (launch_gemm_f32(EP_BIAS_GELU, g1, nb, s)) return 1;                                // downsample_conv.0 k3 p1 + GELU
+    GemmF32Args g2 = {};
+    g2.A = w.d1; g2.lda = 2 * D; g2.sA = sd1; g2.W = h->ds2_w; g2.ldw = 4 * D; g2.C = w.x2 + D; g2.ldc = D; g2.sC = sx2;
+    g2.M = Tc; g2.Ms = Ts; g2.N = D; g2.K = 4 * D; g2.bias = h->ds2_b;
+    if (launch_gemm_f32(EP_BIAS_GELU, g2, nb, s)) return 1;                                // downsample_conv.2 k4 stride 2 p1 + GELU
+    GemmF32Args g3 = {};
+    g3.A = w.x2; g3.lda = D; g3.sA = sx2; g3.W = h->ci0_w; g3.ldw = 3 * D; g3.C = w.b128 + BN; g3.ldc = BN; g3.sC = sb;
+    g3.M = Tc; g3.Ms = Ts; g3.N = BN; g3.K = 3 * D; g3.bias = h->ci0_b;
+    if (launch_gemm_f32(EP_BIAS_GELU, g3, nb, s)) return 1;                                // encoder.conv_in.0 + GELU
+    GemmF32Args g4 = {};
+    g4.A = w.b128; g4.lda = BN; g4.sA = sb; g4.W = h->ci2_w; g4.ldw = 3 * BN; g4.C = w.y; g4.ldc = HD; g4.sC = sy;
+    g4.M = Tc; g4.Ms = Ts; g4.N = HD; g4.K = 3 * BN; g4.bias = h->ci2_b;
+    if (launch_gemm_f32(EP_BIAS, g4, nb, s)) return 1;                                     // encoder.conv_in.2
+    for (int i = 0; i < c.enc_layers; ++i) {                                               // ConvNeXt, dilation 2 (dvae.py:147-158)
+        const EncConvNext& cb = h->blocks[i];
+        hipLaunchKernelGGL(dwconv_ln_kernel<4>, dim3((Tc + 3) / 4, nb), dim3(256), 0, s, w.y, w.ln, cb.dw_w, cb.dw_b, cb.ln_w, cb.ln_b, Ts, sy, sy, HD, 2, 7);
+        CTTS_HIP_CHECK(hipGetLastError());
+        GemmF32Args a1 = {};
+        a1.A = w.ln; a1.lda = HD; a1.sA = sy; a1.W = cb.w1; a1.ldw = HD; a1.C = w.mid; a1.ldc = HD * 4; a1.sC = smid;
+        a1.M = Tc; a1.Ms = Ts; a1.N = HD * 4; a1.K = HD; a1.bias = cb.b1;
+        if (launch_gemm_f32(EP_BIAS_GELU, a1, nb, s)) return 1;
+        GemmF32Args a2 = {};
+        a2.A = w.mid; a2.lda = HD * 4; a2.sA = smid; a2.W = cb.w2; a2.ldw = HD * 4; a2.C = w.y; a2.ldc = HD; a2.sC = sy;
+        a2.M = Tc; a2.Ms = Ts; a2.N = HD; a2.K = HD * 4; a2.bias = cb.b2; a2.gamma = cb.gamma; a2.resid = w.y; a2.ldr = HD; a2.sR = sy;
+        if (launch_gemm_f32(EP_GAMMA_RESID, a2, nb, s)) return 1;
+    }
+    GemmF32Args g5 = {};
+    g5.A = w.y; g5.lda = HD; g5.sA = sy; g5.W = h->co_w; g5.ldw = HD; g5.C = w.feat; g5.ldc = OD; g5.sC = sfeat; g5.M = Tc; g5.Ms = Ts; g5.N = OD; g5.K = HD;
+    if (launch_gemm_f32(EP_NONE, g5, nb, s)) return 1;                                     // encoder.conv_out 1x1
+    if (any_feat) {
+        hipLaunchKernelGGL(feat_out_batch_kernel, dim3(Tc, nb), dim3(256), 0, s, U, w.feat, sfeat, OD);
+        CTTS_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(gfsq_batch_kernel, dim3(Tc, c.vq_groups, nb), dim3(64), 0, s, U, w.feat, sfeat, h->pin_w, h->pin_b, OD / c.vq_groups, OD, c.vq_residuals, c.pre_bound);
+    CTTS_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int ctts_dvae_encode_batch(ctts_enc* h, const float* const* wav_ptrs, const int32_t* n_samples, int B, int32_t* const* ids_ptrs,
+                                      float* const* mel_ptrs, float* const* feat_ptrs, void* stream) {
+    if (!h || !h->finalized || !wav_ptrs || !n_samples || !ids_ptrs) { ctts_set_error("dvae_encode_batch: bad argument"); return 1; }
+    if (B < 1 || B > CTTS_ENC_MAX_BATCH) { ctts_set_error("dvae_encode_batch: B=%d outside [1, %d]", B, CTTS_ENC_MAX_BATCH); return 1; }
+    CTTS_RANGE("ctts_dvae_encode_batch");
+    const ctts_enc_cfg& c = h->cfg;
+    // every check before the first launch: a refused call leaves nothing half-written
+    for (int u = 0; u < B; ++u) {
+        if (n_samples[u] <= c.n_fft / 2 || n_samples[u] > c.max_samples) {
+            ctts_set_error("dvae_encode_batch: utterance %d has %d samples, outside (%d, %d]", u, n_samples[u], c.n_fft / 2, c.max_samples);
+            return 1;
+        }
+        if (!wav_ptrs[u] || !ids_ptrs[u]) { ctts_set_error("dvae_encode_batch: utterance %d has a null %s pointer", u, wav_ptrs[u] ? "ids" : "wav"); return 1; }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    // tables, staged in a pinned ring slot (a slot is reused only after its copy has run)
+    const int slot = h->pin_next++ % 4;
+    if (h->pin_used[slot]) CTTS_HIP_CHECK(hipEventSynchronize(h->pin_ev[slot]));
+    char* p = h->pin + (size_t)slot * ENC_TAB_BYTES;
+    EncUtt* U = (EncUtt*)p;
+    int *Fs = (int*)(p + (size_t)CTTS_ENC_MAX_BATCH * sizeof(EncUtt)), *Ts = Fs + CTTS_ENC_MAX_BATCH;
+    int Fall = 0;
+    for (int u = 0; u < B; ++u) {
+        const int F = 1 + n_samples[u] / c.hop, T = (F - 2) / 2 + 1;
+        U[u] = {wav_ptrs[u], (int*)ids_ptrs[u], mel_ptrs ? mel_ptrs[u] : nullptr, feat_ptrs ? feat_ptrs[u] : nullptr, n_samples[u], F, T, 0};
+        Fs[u] = F; Ts[u] = T;
+        Fall = F > Fall ? F : Fall;
+    }
+    // the single-clip workspace is the minimum budget; a batch that does not fit it in one chunk gets the larger set, once
+    if (!h->ws_big && !enc_fits(h->ws, enc_region(c, Fall), (size_t)B)) {
+        const EncRegion r = enc_region(c, h->Fmax);
+        ctts_enc::Ws w = {};
+        w.n_xp = ENC_BATCH_WS * r.n_xp; w.rowsF = ENC_BATCH_WS * r.rowsF; w.rowsD1 = ENC_BATCH_WS * r.rowsD1; w.rowsT = ENC_BATCH_WS * r.rowsT;
+        if (ealloc(h, &w.xp, w.n_xp) || ealloc(h, &w.spec, w.rowsF * h->spec_ld) || ealloc(h, &w.mag, w.rowsF * h->mag_ld) ||
+            ealloc(h, &w.melcl, w.rowsF * h->mel_ld) || ealloc(h, &w.d1, w.rowsD1 * c.dim) || ealloc(h, &w.x2, w.rowsT * c.dim) ||
+            ealloc(h, &w.b128, w.rowsT * c.enc_bn) || ealloc(h, &w.y, w.rowsT * c.enc_hidden) || ealloc(h, &w.ln, w.rowsT * c.enc_hidden) ||
+            ealloc(h, &w.mid, w.rowsT * c.enc_hidden * 4) || ealloc(h, &w.feat, w.rowsT * c.enc_odim))
+            return 1;
+        h->ws = w;
+        h->ws_big = true;
+    }
+    CTTS_HIP_CHECK(hipMemcpyAsync(h->d_tab, p, ENC_TAB_BYTES, hipMemcpyHostToDevice, s));
+    CTTS_HIP_CHECK(hipEventRecord(h->pin_ev[slot], s));
+    h->pin_used[slot] = true;
+    // greedy chunks in call order: an utterance joins the open chunk while the chunk, strided by its longest clip, still fits
+    int u0 = 0, Fc = 0, Tc = 0, nmax = 0;
+    bool any_mel = false, any_feat = false;
+    for (int u = 0; u <= B; ++u) {
+        if (u < B) {
+            const int Fn = U[u].F > Fc ? U[u].F : Fc;
+            if (u == u0 || enc_fits(h->ws, enc_region(c, Fn), (size_t)(u - u0 + 1))) {
+                Fc = Fn; Tc = U[u].T > Tc ? U[u].T : Tc; nmax = U[u].n > nmax ? U[u].n : nmax;
+                any_mel |= U[u].mel != nullptr; any_feat |= U[u].feat != nullptr;
+                continue;
+            }
+        }
+        if (encode_chunk(h, u0, u - u0, Fc, Tc, nmax, any_mel, any_feat, s)) return 1;
+        if (u < B) { u0 = u; Fc = U[u].F; Tc = U[u].T; nmax = U[u].n; any_mel = U[u].mel != nullptr; any_feat = U[u].feat != nullptr; }
+    }
     return 0;
 }

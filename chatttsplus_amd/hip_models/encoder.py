@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -110,6 +110,28 @@ class DVAEEncoder:
             _lib.check(self._lib.ctts_dvae_encode(self._h, wav.data_ptr(), n, ids.data_ptr(), mel.data_ptr() if mel is not None else None,
                                                   feat.data_ptr() if feat is not None else None, st), "dvae_encode")
         return (ids, mel, feat) if return_debug else ids
+
+    @torch.inference_mode()
+    def encode_batch(self, wavs: List[torch.Tensor], return_debug: bool = False):
+        """One launch sequence for all clips (ctts_dvae_encode_batch): wavs[u] [n_u] fp32 @ 24 kHz -> a list of codes int32 [G*R, T_u] on the device, each
+        bit-identical to encode(wavs[u]); `return_debug`: a list of (ids, mel, feat) as encode returns them."""
+        if not self._finalized:
+            raise _lib.HipBackendError("DVAE encoder weights not loaded")
+        wavs = [torch.as_tensor(w).to(self.device, dtype=torch.float32).contiguous().view(-1) for w in wavs]
+        B = len(wavs)
+        ns = [int(w.shape[0]) for w in wavs]
+        Ts = [max(self.n_codes(n), 0) for n in ns]                  # (a clip that is too short is refused by the library, by index)
+        ids = [torch.empty(self.G * self.R, T, dtype=torch.int32, device=self.device) for T in Ts]
+        mels = [torch.empty(self.cfg.n_mels, 1 + n // 256, dtype=torch.float32, device=self.device) for n in ns] if return_debug else None
+        feats = [torch.empty(T, self.cfg.enc_odim, dtype=torch.float32, device=self.device) for T in Ts] if return_debug else None
+
+        def table(ts):
+            return (C.c_void_p * max(B, 1))(*[t.data_ptr() for t in ts]) if ts is not None else None
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            _lib.check(self._lib.ctts_dvae_encode_batch(self._h, table(wavs), (C.c_int32 * max(B, 1))(*ns), B, table(ids), table(mels), table(feats), st),
+                       "dvae_encode_batch")
+        return list(zip(ids, mels, feats)) if return_debug else ids
 
     @torch.inference_mode()
     def __call__(self, inp: torch.Tensor, mode="encode") -> torch.Tensor:

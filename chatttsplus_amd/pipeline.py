@@ -74,9 +74,44 @@ from .hip_models.vocoder import prefix_samples, prefix_tokens  # noqa: E402
 
 # params_per_utterance (ChatTTSPlusPipeline.infer / infer_sharded): the InferCodeParams fields one utterance may set for itself.  The sampling knobs
 # reach the engine's per-row table (GPT sampling_per_row, ctts_gpt_set_row_sampling); max_new_token becomes the utterance's token limit, prompt its
-# [speed_N] / [oral_N] prefix, spk_emb its speaker row.  Every other field is per call.
+# [speed_N] / [oral_N] prefix, spk_emb its speaker row, spk_smp / txt_smp its cloned voice (the zero-shot audio prompt behind its text and the transcript of
+# that clip in front of it: ClonedVoice.overrides()).  Every other field is per call.
 PER_UTTERANCE_SAMPLING = ("temperature", "top_P", "top_K", "repetition_penalty", "min_new_token")
-PER_UTTERANCE_FIELDS = PER_UTTERANCE_SAMPLING + ("max_new_token", "prompt", "spk_emb")
+PER_UTTERANCE_FIELDS = PER_UTTERANCE_SAMPLING + ("max_new_token", "prompt", "spk_emb", "spk_smp", "txt_smp")
+
+
+@dataclass(eq=False)
+class ClonedVoice:
+    """One cloned voice (ChatTTSPlusPipeline.clone_voices): `spk_smp`, the base16384 audio-prompt string of the clip's codes, and `txt_smp`, the transcript of the
+    clip.  `overrides()` is the params_per_utterance / SynthSession.submit(params=) entry that speaks an utterance in this voice."""
+    spk_smp: str
+    txt_smp: str = ""
+    _codes: Optional[torch.Tensor] = dataclasses.field(default=None, repr=False)
+
+    @property
+    def codes(self) -> torch.Tensor:
+        """the clip's codes [num_vq, T] (decoded once)"""
+        if self._codes is None:
+            self._codes = codec.decode_prompt(self.spk_smp)
+        return self._codes
+
+    def overrides(self) -> dict:
+        """spk_emb None: no speaker vector of the entry's own -- a row that sets spk_smp gets the [empty_spk] tag, whatever the call's speaker"""
+        return {"spk_smp": self.spk_smp, "txt_smp": self.txt_smp, "spk_emb": None}
+
+
+def utterance_voices(base, diffs) -> Optional[list]:
+    """params_per_utterance entries (per_utterance_overrides) -> one (speaker tag, txt_smp, spk_smp) per utterance, None when no entry touches spk_smp / txt_smp.
+    An utterance that sets its own spk_smp speaks without a speaker vector ([empty_spk]; setting both is refused by per_utterance_overrides); every other utterance
+    keeps the call's voice: its speaker row where the call has a speaker, the call's spk_smp / txt_smp where it has those."""
+    if not any(("spk_smp" in d or "txt_smp" in d) for d in diffs):
+        return None
+    out = []
+    for d in diffs:
+        has_vec = "spk_emb" in d or (base.spk_emb is not None and d.get("spk_smp") is None)
+        txt = d.get("txt_smp", base.txt_smp)
+        out.append(("[spk_emb]" if has_vec else "[empty_spk]", "" if txt is None else txt, d.get("spk_smp", base.spk_smp)))
+    return out
 
 
 def _same_value(a, b) -> bool:
@@ -112,6 +147,9 @@ def per_utterance_overrides(base, entries) -> List[dict]:
         if bad:
             raise _lib.HipBackendError(f"params_per_utterance: entry {i}: field {bad[0]!r} differs from params_infer_code but is per call "
                                        f"(per utterance: {', '.join(PER_UTTERANCE_FIELDS)})")
+        if diff.get("spk_smp") is not None and "spk_emb" in diff:
+            raise _lib.HipBackendError(f"params_per_utterance: entry {i} sets both spk_smp (a cloned voice) and spk_emb (a speaker vector): an utterance speaks in one "
+                                       f"of them; leave spk_emb None beside spk_smp")
         out.append(diff)
     return out
 
@@ -157,6 +195,7 @@ class _Request:
     texts: List[str]; gpt: object; slice_size: int
     params_refine_text: RefineTextParams; params_infer_code: InferCodeParams      # the latter after the max_new_token / spk_emb replacements of params_per_utterance
     utt_ids: list; utt_limits: Optional[list]; utt_sampling: Optional[list]; utt_prompts: Optional[list]; lora_paths: Optional[list]
+    utt_voices: Optional[list]                          # per utterance (speaker tag, txt_smp, spk_smp): params_per_utterance entries with spk_smp / txt_smp (utterance_voices)
     noise_mode: object; noise_seed: Optional[int]      # "auto" | "device" | what else GPT.generate takes as `noise`; seed None: drawn by the path that runs, when it needs one
     stream: bool; use_decoder: bool; skip_refine_text: bool; refine_text_only: bool; continuous: object      # continuous: False | True | "throughput"
     n_cand: int; return_details: bool; select: Optional[Callable]; share_prompt: Optional[bool]; ids_sink: Optional[list]
@@ -165,10 +204,10 @@ class _Request:
 
     def rows(self, idx, adapters: bool = False, params: bool = True) -> dict:
         """The generation keywords of utterances `idx` (a range or a list of indices into `texts`, in the order the rows are laid out): `utt_ids`; where the request
-        has them `max_new_tokens_per_row` / `sampling_per_row` / `prompts` / (`adapters`) `lora_paths`; `params`: the InferCodeParams, the rows of a per-utterance
+        has them `max_new_tokens_per_row` / `sampling_per_row` / `prompts` / `voices` / (`adapters`) `lora_paths`; `params`: the InferCodeParams, the rows of a per-utterance
         speaker table gathered.  An identity `idx` (a slice that is the whole request, the [1, 768] table of one utterance) hands the table on untouched; a range takes a view."""
         kw = dict(utt_ids=[self.utt_ids[i] for i in idx])
-        for key, per_utt in (("max_new_tokens_per_row", self.utt_limits), ("sampling_per_row", self.utt_sampling), ("prompts", self.utt_prompts),
+        for key, per_utt in (("max_new_tokens_per_row", self.utt_limits), ("sampling_per_row", self.utt_sampling), ("prompts", self.utt_prompts), ("voices", self.utt_voices),
                              ("lora_paths", self.lora_paths if adapters else None)):
             if per_utt is not None:
                 kw[key] = [per_utt[i] for i in idx]
@@ -342,7 +381,7 @@ class SynthSession:
         """`stream` "exact" or "eager": poll() returns this ticket's audio as SessionChunks while it decodes (class docstring; "exact" is the one to use unless the
         reference's windows are wanted); `stream_batch`: tokens between chunks (default: the session's params.stream_batch); `pcm16`: its chunks are int16 PCM.
         Queues one text.  `params`: this utterance's overrides (an InferCodeParams or a dict, checked by per_utterance_overrides: sampling knobs,
-        max_new_token, prompt, spk_emb); `lora_path`: its own adapter; `utt_id`: its noise key (default: a counter).  `refine`: refine the text first (default:
+        max_new_token, prompt, spk_emb, or a cloned voice: spk_smp / txt_smp, e.g. ClonedVoice.overrides() -- the refine stage does not see the voice); `lora_path`: its own adapter; `utt_id`: its noise key (default: a counter).  `refine`: refine the text first (default:
         iff the session was opened with refine=); False = the text is already refined.  Returns its ticket."""
         if not isinstance(text, str):
             raise _lib.HipBackendError("SynthSession.submit takes one text (a str) per call")
@@ -389,7 +428,12 @@ class SynthSession:
         pipe, gpt, base = self.pipe, self.gpt, self.params
         t = _with_uv_break(t)
         pic = dataclasses.replace(base, spk_emb=diff["spk_emb"]) if "spk_emb" in diff else base
-        input_ids, attention_mask, text_mask = pipe._code_prompt([t], pic, gpt, [diff["prompt"] or ""] if "prompt" in diff else None)
+        voices = utterance_voices(base, [diff])            # its own cloned voice (spk_smp / txt_smp): its own tag, transcript and codes
+        input_ids, attention_mask, text_mask = pipe._code_prompt([t], pic, gpt, [diff["prompt"] or ""] if "prompt" in diff else None, voices)
+        if voices is not None and int(attention_mask.shape[1]) + self.session.book.max_new > self.session.book.max_seq:
+            codes = 0 if voices[0][2] is None else int(codec.decode_prompt(voices[0][2]).shape[1])
+            raise _lib.HipBackendError(f"submit: utterance {utt_id}: prompt of {int(attention_mask.shape[1])} tokens ({codes} of them audio-prompt codes) + "
+                                       f"max_new_token={self.session.book.max_new} exceed max_seq_len={self.session.book.max_seq}")
         emb = gpt(input_ids, text_mask, spk_emb=pic.spk_emb, spk_emb_ids=pipe.models_dict["tokenizer"].spk_emb_ids)
         sampling = {k: diff[k] for k in PER_UTTERANCE_SAMPLING if k in diff} or None
         if streaming is None:
@@ -717,8 +761,46 @@ class ChatTTSPlusPipeline:
         if enc is None:
             raise _lib.HipBackendError("zero-shot speaker needs the dvae_encode checkpoint (DVAE_full.pt) configured with infer_type 'hip'")
         wav = torch.as_tensor(wav, dtype=torch.float32)
-        codes = enc(wav.view(1, -1).to(self.device), "encode")[0]
+        codes = enc.encode_batch([wav.view(-1)])[0]             # the entry clone_voices batches over, with B = 1
         return codec.encode_prompt(codes.cpu())
+
+    @staticmethod
+    def _load_clip(path, wav=None, sample_rate=None) -> torch.Tensor:
+        """A reference clip as infer(speaker_audio_path=) prepares it (pipeline:486-496): read (or taken as [n] / [channels, n] samples at `sample_rate`),
+        resampled to 24 kHz, channels averaged -> [n] fp32."""
+        from . import audio
+        if wav is None:
+            wav, sample_rate = audio.load_audio(path)
+        wav = torch.as_tensor(wav, dtype=torch.float32)
+        wav = wav.view(1, -1) if wav.dim() == 1 else wav
+        return torch.mean(audio.resample(wav, int(sample_rate or 24000), 24000), 0)
+
+    @torch.inference_mode()
+    def clone_voices(self, clips, texts, sample_rates=None) -> List[ClonedVoice]:
+        """One ClonedVoice per reference clip, all clips through ONE encoder call (DVAEEncoder.encode_batch; the reference can clone one voice per infer call,
+        pipeline:486-499).  `clips`: paths, or waveforms ([n] or [channels, n]; `sample_rates`: one rate for all or one per clip, default 24000 -- ignored for
+        paths, whose files name their own); each is resampled and mono-mixed exactly as infer(speaker_audio_path=) does.  `texts`: the transcript of each clip
+        (txt_smp).  Voice i equals ClonedVoice(sample_audio_speaker(clip i), texts[i]), string for string."""
+        enc = self.models_dict.get("dvae_encode")
+        if enc is None:
+            raise _lib.HipBackendError("zero-shot speaker needs the dvae_encode checkpoint (DVAE_full.pt) configured with infer_type 'hip'")
+        clips, texts = list(clips), list(texts)
+        if len(clips) != len(texts):
+            raise _lib.HipBackendError(f"clone_voices: {len(texts)} transcripts for {len(clips)} clips")
+        rates = list(sample_rates) if isinstance(sample_rates, (list, tuple)) else [sample_rates] * len(clips)
+        _check_entries("sample_rates", rates, len(clips))
+        wavs = []
+        for c, r in zip(clips, rates):
+            if isinstance(c, (str, os.PathLike)):
+                if not os.path.exists(c):
+                    raise _lib.HipBackendError(f"clone_voices: clip {os.fspath(c)!r} does not exist")
+                wavs.append(self._load_clip(os.fspath(c)))
+            else:
+                wavs.append(self._load_clip(None, c, r))
+        if not wavs:
+            return []
+        codes = enc.encode_batch(wavs)
+        return [ClonedVoice(spk_smp=codec.encode_prompt(c.cpu()), txt_smp=t or "", _codes=c.cpu().to(torch.int64)) for c, t in zip(codes, texts)]
 
     def sample_random_speaker(self) -> str:
         return self._encode_spk_emb(self._sample_random_speaker())
@@ -734,9 +816,10 @@ class ChatTTSPlusPipeline:
         return torch.randn(dim, device=self.std.device, dtype=self.std.dtype).mul_(self.std).add_(self.mean)
 
     # -- hot path callers --------------------------------------------------------------------------
-    def _code_prompt(self, text, params: InferCodeParams, gpt, prompts=None):
+    def _code_prompt(self, text, params: InferCodeParams, gpt, prompts=None, voices=None):
         """The code-generation prompt of pipeline:157-235 (shared by _infer_code and score): "[Stts]{spk tag}{txt_smp}{prompt}{text}[Ptts]", tokenised
-        with the zero-shot audio prompt (spk_smp) after the text.  Returns input_ids [B, T, 4], attention_mask, text_mask (left padded)."""
+        with the zero-shot audio prompt (spk_smp) after the text.  Returns input_ids [B, T, 4], attention_mask, text_mask (left padded).
+        `voices`: one (spk tag, txt_smp, spk_smp) per text instead of the params' (utterance_voices): every row its own tag, transcript and codes."""
         tok = self.models_dict["tokenizer"]
         if not isinstance(text, list):
             text = [text]
@@ -746,6 +829,9 @@ class ChatTTSPlusPipeline:
             text = [p + i for p, i in zip(prompts, text)]
         elif params.prompt:
             text = [params.prompt + i for i in text]
+        if voices is not None:
+            text = [f"[Stts]{tag}{txt_smp}{i}[Ptts]" for (tag, txt_smp, _), i in zip(voices, text)]
+            return tok.encode(text, gpt.num_vq, prompt_str=[smp for _, _, smp in voices], device=self.device)
         txt_smp = "" if params.txt_smp is None else params.txt_smp
         tag = "[spk_emb]" if params.spk_emb is not None else "[empty_spk]"
         text = [f"[Stts]{tag}{txt_smp}{i}[Ptts]" for i in text]
@@ -772,10 +858,8 @@ class ChatTTSPlusPipeline:
             enc = self.models_dict.get("dvae_encode")
             if enc is None:
                 raise _lib.HipBackendError("score(wavs=...) needs the dvae_encode checkpoint (DVAE_full.pt) configured with infer_type 'hip'")
-            codes = []
-            for w in (wavs if isinstance(wavs, list) else [wavs]):
-                w = torch.as_tensor(w, dtype=torch.float32)
-                codes.append(enc(w.view(1, -1).to(self.device), "encode")[0].t().cpu())      # [4, n] (sample_audio_speaker) -> [n, 4]
+            clips = [torch.as_tensor(w, dtype=torch.float32).view(-1) for w in (wavs if isinstance(wavs, list) else [wavs])]
+            codes = [c.t().cpu() for c in enc.encode_batch(clips)] if clips else []      # one encoder call; [4, n] (sample_audio_speaker) -> [n, 4]
         elif not isinstance(codes, list):
             codes = [codes]
         if len(codes) != len(texts):
@@ -799,13 +883,23 @@ class ChatTTSPlusPipeline:
                 gpt.set_row_adapters(None)
 
     @torch.no_grad()
-    def _infer_code(self, text, stream: bool, return_hidden: bool, params: InferCodeParams, gpt=None, prompts=None, **gen_kwargs):
+    def _infer_code(self, text, stream: bool, return_hidden: bool, params: InferCodeParams, gpt=None, prompts=None, voices=None, **gen_kwargs):
         """pipeline:157-235 -- same argument plumbing; the GPT object is the hip backend.  `gen_kwargs` (noise, seed, utt_ids, sampling_per_row) ride
         through to GPT.generate: the device noise stream of an utterance is keyed by the request seed and its global utterance id.  `prompts`: one
-        prompt prefix per text instead of params.prompt (params_per_utterance)."""
+        prompt prefix per text instead of params.prompt (params_per_utterance); `voices`: one (spk tag, txt_smp, spk_smp) per text (_code_prompt)."""
         gpt = gpt or self.models_dict["gpt"]
         tok = self.models_dict["tokenizer"]
-        input_ids, attention_mask, text_mask = self._code_prompt(text, params, gpt, prompts)
+        input_ids, attention_mask, text_mask = self._code_prompt(text, params, gpt, prompts, voices)
+        if voices is not None:
+            # an audio prompt can be long: text + codes + the utterance's token limit must fit a KV lane -- refused here, before the engine begins, by utterance
+            limits, prompt_of = gen_kwargs.get("max_new_tokens_per_row"), gen_kwargs.get("prompt_of")
+            for r, n in enumerate(attention_mask.sum(1).tolist()):
+                rows_r = [r] if prompt_of is None else [j for j, p in enumerate(prompt_of) if p == r]      # (shared prompt passes: the rows that decode from prompt r)
+                lim = max(int(limits[j]) for j in rows_r) if limits is not None else int(params.max_new_token)
+                if n + lim > gpt.max_seq:
+                    codes = 0 if voices[r][2] is None else int(codec.decode_prompt(voices[r][2]).shape[1])
+                    raise _lib.HipBackendError(f"utterance {r} of this batch: prompt of {int(n)} tokens ({codes} of them audio-prompt codes) + max_new_token={lim} "
+                                               f"exceed max_seq_len={gpt.max_seq}")
         emb = gpt(input_ids, text_mask, spk_emb=params.spk_emb, spk_emb_ids=tok.spk_emb_ids)     # get_emb + apply_spk_emb, one launch
         temperature, num_code, warpers, processors = _code_sampler_args(params, gpt)
         gen_kwargs.update(temperature=torch.tensor(temperature), eos_token=num_code, attention_mask=attention_mask, max_new_token=params.max_new_token,
@@ -933,6 +1027,8 @@ class ChatTTSPlusPipeline:
         for u, d in enumerate(diffs):
             if "spk_emb" in d:
                 rows.append(vec(d["spk_emb"]))
+            elif d.get("spk_smp") is not None:
+                rows.append(torch.zeros(dim))               # a cloned voice: its prompt has no [spk_emb] token, the row is never applied
             elif call_spk is None:
                 raise _lib.HipBackendError("params_per_utterance: an utterance sets spk_emb and the call has no speaker for the others")
             else:
@@ -978,7 +1074,7 @@ class ChatTTSPlusPipeline:
         _check_entries("max_new_tokens_per_utterance", utt_limits, n, after)
         # optional per-utterance parameters (no counterpart in the reference, whose InferCodeParams apply to a whole call): one InferCodeParams or dict of
         # overrides per utterance; the sampling knobs go to the engine's per-row table (GPT sampling_per_row), max_new_token to the per-row limits
-        utt_sampling = utt_prompts = None
+        utt_sampling = utt_prompts = utt_voices = None
         diffs = kwargs.get("_utt_overrides")       # infer / infer_sharded: the entries already resolved against the params their CALLER passed
         if diffs is None and kwargs.get("params_per_utterance") is not None:
             diffs = per_utterance_overrides(params_infer_code, kwargs["params_per_utterance"])
@@ -993,6 +1089,7 @@ class ChatTTSPlusPipeline:
                 params_infer_code = dataclasses.replace(params_infer_code, max_new_token=max(utt_limits))
             if any("prompt" in d for d in diffs):
                 utt_prompts = [d.get("prompt", params_infer_code.prompt) or "" for d in diffs]
+            utt_voices = utterance_voices(params_infer_code, diffs)            # (against the call's speaker, before the table below replaces it)
             if any("spk_emb" in d for d in diffs):
                 params_infer_code = dataclasses.replace(params_infer_code, spk_emb=self._speaker_rows(params_infer_code.spk_emb, diffs))
         # return_details / num_candidates (no counterpart in the reference): log-probs written by the sampler, N candidates per utterance ranked by them
@@ -1000,7 +1097,7 @@ class ChatTTSPlusPipeline:
         if (n_cand > 1 or kwargs.get("return_details")) and not refine_text_only and stream:
             raise _lib.HipBackendError("return_details=True needs stream=False")
         return _Request(texts=texts, gpt=gpt, slice_size=slice_size, params_refine_text=params_refine_text, params_infer_code=params_infer_code, utt_ids=utt_ids,
-                        utt_limits=utt_limits, utt_sampling=utt_sampling, utt_prompts=utt_prompts, lora_paths=lora_paths, noise_mode=noise_mode, stream=stream,
+                        utt_limits=utt_limits, utt_sampling=utt_sampling, utt_prompts=utt_prompts, utt_voices=utt_voices, lora_paths=lora_paths, noise_mode=noise_mode, stream=stream,
                         noise_seed=kwargs.get("noise_seed"), use_decoder=use_decoder, skip_refine_text=skip_refine_text, refine_text_only=refine_text_only,
                         continuous=kwargs.get("continuous"), n_cand=n_cand, return_details=bool(kwargs.get("return_details")), select=kwargs.get("select"),
                         share_prompt=kwargs.get("share_prompt"), ids_sink=kwargs.get("_ids_sink"), overlap_vocoder=bool(kwargs.get("overlap_vocoder", False)),
@@ -1215,7 +1312,7 @@ class ChatTTSPlusPipeline:
         src_kw = req.rows([u for u, _ in src]) if share else row_kw           # speaker rows and prompts go per prompt, the rest per row
         pic, paths = src_kw["params"], row_kw.get("lora_paths")
         gen_kw = dict(return_logprobs=True)
-        for key, of in (("max_new_tokens_per_row", row_kw), ("sampling_per_row", row_kw), ("prompts", src_kw)):
+        for key, of in (("max_new_tokens_per_row", row_kw), ("sampling_per_row", row_kw), ("prompts", src_kw), ("voices", src_kw)):
             if key in of:
                 gen_kw[key] = of[key]
         if share:
@@ -1289,17 +1386,19 @@ class ChatTTSPlusPipeline:
         pipeline:547-556), else a random speaker from spk_stat.  The params object is copied first: the default argument is one shared
         instance, and the reference's in-place writes make a zero-shot prompt or a sampled speaker stick to every later default call.
         `params_per_utterance`: one InferCodeParams or dict per utterance (after text splitting); an entry overrides the fields in which it differs
-        from the params_infer_code passed HERE -- not from the speaker / zero-shot prompt filled in below."""
+        from the params_infer_code passed HERE -- not from the speaker / zero-shot prompt filled in below.  An entry may name a cloned voice
+        (spk_smp / txt_smp: ClonedVoice.overrides(), clone_voices) on every path -- sliced, continuous, stream, num_candidates (the candidates of an
+        utterance share its voice, hence its prompt pass); such a row is tagged [empty_spk], rows with a speaker vector and cloned rows mix freely.
+        No random speaker is sampled for a call that names a cloned voice (params_infer_code.spk_smp) or whose every utterance brings its own voice."""
+        own_voices = False
         if kwargs.get("params_per_utterance") is not None:
             kwargs["_utt_overrides"] = per_utterance_overrides(params_infer_code, kwargs.pop("params_per_utterance"))
+            own_voices = bool(kwargs["_utt_overrides"]) and all(("spk_emb" in d or d.get("spk_smp") is not None) for d in kwargs["_utt_overrides"])
         params_infer_code = dataclasses.replace(params_infer_code)
         if kwargs.get("speaker_audio_path"):                                      # zero shot (pipeline:486-499)
-            from . import audio
             p = kwargs["speaker_audio_path"]
             assert os.path.exists(p), f"speaker_audio_path {p} not exists!"
-            wav, sr = audio.load_audio(p)
-            wav = torch.mean(audio.resample(wav, sr, 24000), 0)
-            params_infer_code.spk_smp = self.sample_audio_speaker(wav)
+            params_infer_code.spk_smp = self.sample_audio_speaker(self._load_clip(p))
             params_infer_code.txt_smp = kwargs.get("speaker_audio_text", "")
             params_infer_code.spk_emb = None
         elif kwargs.get("speaker_emb_path"):
@@ -1309,7 +1408,8 @@ class ChatTTSPlusPipeline:
             if isinstance(obj, dict):
                 obj = next(iter(obj.values()))
             params_infer_code.spk_emb = obj if isinstance(obj, str) else codec.speaker_to_vector(obj)
-        elif params_infer_code.spk_emb is None:
+        elif params_infer_code.spk_emb is None and params_infer_code.spk_smp is None and not own_voices:
+            # (a call that names a cloned voice itself -- spk_smp, as open_session reads it -- or whose every utterance brings its own voice needs no sampled speaker)
             params_infer_code.spk_emb = self.sample_random_speaker()
         return self._infer(text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                            do_text_optimization, do_homophone_replacement, params_refine_text, params_infer_code, **kwargs)
@@ -1344,6 +1444,8 @@ class ChatTTSPlusPipeline:
         exchange: ONE broadcast of the speaker table [n_spk, 768] from rank 0 (RCCL over xGMI) and one all-reduce of the
         generated lengths (disjoint supports).  `speaker_index[i]` selects utterance i's row; without a table every utterance
         uses params_infer_code.spk_emb.
+        `params_per_utterance` (one entry per GLOBAL utterance) is accepted with every per-utterance field, cloned voices (spk_smp / txt_smp) included: the
+        list is an argument every rank holds, like `prompt`, so nothing more is exchanged -- a cloned row ignores its speaker_index row.
         Returns (indices of this rank's utterances, their waveforms in that order, generated token counts of ALL utterances).
         Note SURVEY F8: the reference's repetition penalty skips rows >= 625 of the flattened [B*4] batch; a rank never holds
         more than max_batch <= 128 sequences (512 rows) per call, so the quirk cannot trigger on any rank."""

@@ -630,6 +630,20 @@ int ctts_enc_finalize(ctts_enc* h);
  * row g*R + r like GFSQ.forward's `ind` (dvae.py:108-113,126).  Optional test hooks (device, may be null):
  * mel_out [n_mels][F] = log-mel / coef, feat_out [T][enc_odim] = encoder output. */
 int ctts_dvae_encode(ctts_enc* h, const float* wav, int n_samples, int32_t* ids, float* mel_out, float* feat_out, void* stream);
+/* The same for B clips in one launch sequence (grid.z / grid.y = utterance, per-utterance frame and code counts from device tables uploaded
+ * once per call): per batch it replaces B calls of sample_audio_speaker (pipelines/chattts_plus_pipeline.py:279-284) = B runs of
+ * DVAE.forward(mode="encode") (models/dvae.py:263-270), which the reference can only loop over.  Like ctts_synth_batch the pointer arrays and
+ * n_samples are HOST arrays of length B (1 <= B <= CTTS_ENC_MAX_BATCH) of device pointers: wav_ptrs[u] fp32 [n_samples[u]], ids_ptrs[u] int32
+ * [G*R][T_u].  mel_ptrs / feat_ptrs (the test hooks of the single-clip call) may be null, and so may any entry of them.  Every output is
+ * bit-identical to ctts_dvae_encode of that clip alone, whatever the batch, its order or its chunking.  All arguments are checked on the host
+ * before the first launch: a clip outside (n_fft/2, max_samples] or a null wav / ids entry fails the call, its index in the message, and
+ * nothing is written.  Workspace: a batch that fits the single-clip buffers (one clip of max_samples) uses them; the first batch that does
+ * not allocates, once per handle, a second set 4 times as large (16 KiB per 256-sample frame of max_samples: about 180 MiB at 30 s, 360 MiB at 60 s) and every
+ * batch is then served in as many chunks as fit it, each utterance region strided by its chunk's longest clip.  Never synchronises the stream
+ * (but for that one allocation and, every fifth call in flight, the reuse of a pinned table slot). */
+#define CTTS_ENC_MAX_BATCH 256
+int ctts_dvae_encode_batch(ctts_enc* h, const float* const* wav_ptrs, const int32_t* n_samples, int B, int32_t* const* ids_ptrs,
+                           float* const* mel_ptrs, float* const* feat_ptrs, void* stream);
 
 #ifdef __cplusplus
 }
