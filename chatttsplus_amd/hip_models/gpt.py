@@ -8,7 +8,9 @@ torch is used for device memory, the current stream and the (negligible) embeddi
 from __future__ import annotations
 
 import ctypes as C
+import time
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import List, Optional, Union
 
 import numpy as np
@@ -348,6 +350,16 @@ def compact_size(n_live: int) -> int:
     return (n + q - 1) // q * q
 
 
+def compact_keep(live) -> Optional[List[int]]:
+    """The one compaction rule (generate() and SessionBook.plan; each has its own threshold for asking): `live[r]` = decode row r still decodes.  Returns the rows
+    to keep, ascending -- the live ones and, up to compact_size of their number, the first finished ones as padding -- or None when the batch stays as it is."""
+    rows = [r for r, f in enumerate(live) if f]
+    target = compact_size(len(rows))
+    if not rows or target >= len(live):
+        return None
+    return sorted(rows + [r for r, f in enumerate(live) if not f][:target - len(rows)])
+
+
 class RowBook:
     """Continuous batching bookkeeping (the row level of SessionBook): which utterance sits in which decode row.  Every seating gets a ticket; the row
     states the engine reports ({fin, end} per row, ctts_gpt_rows_enqueue) arrive one or two chunks late and are interpreted through the
@@ -600,10 +612,8 @@ class SessionBook:
                 self._seat(r, tk)
             return SessionPlan(grow=grow, lanes=lanes, admit=list(zip(rows, take)))
         if not self.queue and self.compact and B >= 2:
-            live = self.book.live_rows()
-            target = compact_size(len(live))
-            if live and target < B:
-                keep = sorted(live + free[:target - len(live)])
+            keep = compact_keep([tk is not None for tk in self.book.row_tk])
+            if keep is not None:
                 self.book.compact(keep)
                 self.lanes = [self.lanes[r] for r in keep]
                 return SessionPlan(compact=keep)
@@ -753,6 +763,105 @@ class OutBuffers:
         return ids, hid, self.lps[0, s, :n], self.lps[1, s, :n], self.lps[:, s, n].clone() if (eos and n < self.lps.shape[2]) else None
 
 
+class ReportRing:
+    """Two chunks of decode steps in flight: per slot one pinned int32 buffer for each of `sizes`, an event, and the row layout current at enqueue (see RowBook)."""
+
+    def __init__(self, *sizes: int):
+        self._bufs = [[torch.zeros(n, dtype=torch.int32).pin_memory() for n in sizes] for _ in range(2)]
+        self._evs = [torch.cuda.Event() for _ in range(2)]
+        self.pending: List[tuple] = []             # (slot, layout) of the chunks in flight, oldest first
+        self.free = self._bufs[0]                  # the buffers of the next push: the caller enqueues its report(s) into them behind the chunk just launched
+
+    def push(self, layout) -> None:
+        """the report(s) are enqueued: the layout is remembered and the event recorded on the current stream"""
+        slot = 0 if self.free is self._bufs[0] else 1
+        self._evs[slot].record()
+        self.pending.append((slot, layout))
+        self.free = self._bufs[1 - slot]
+
+    def pop(self):
+        """waits for the oldest chunk in flight: (its layout, its buffers)"""
+        slot, layout = self.pending.pop(0)
+        self._evs[slot].synchronize()
+        return layout, self._bufs[slot]
+
+
+class NoiseFeed:
+    """The sampler's noise of one generate() call (its docstring names the kinds): `buf` [n_draws, rows, V] on the device, None for "device"; a caller's array
+    sets n_draws.  "torch" noise is drawn chunk by chunk ahead of the steps that read it (draw_to) and leaves torch's generator as the reference would (restore)."""
+
+    def __init__(self, gpt: "GPT", noise, n_draws: int, rows: int, V: int, stage_cap: int):
+        self.n_draws, self.buf, self._stage, self._states, self._drawn = int(n_draws), None, None, [], 0
+        if isinstance(noise, str) and noise == "torch":
+            self.buf = torch.empty(self.n_draws, rows, V, dtype=torch.float32, device=gpt.device)
+            # pinned [cap, rows, V] staging slots, kept on the engine across calls (pinning is expensive)
+            if getattr(gpt, "_stage_key", None) != (rows, V, stage_cap):
+                gpt._stage_key, gpt._stage_next = (rows, V, stage_cap), 0
+                gpt._stage_bufs = [[torch.empty(stage_cap, rows, V, dtype=torch.float32).pin_memory(), None] for _ in range(3)]
+            self._gpt, self._cap, self._stage = gpt, stage_cap, gpt._stage_bufs
+        elif not (isinstance(noise, str) and noise == "device"):
+            self.buf = torch.as_tensor(noise, dtype=torch.float32).to(gpt.device).contiguous()
+            self.n_draws = int(self.buf.shape[0])
+
+    def draw_to(self, n: int) -> None:
+        """torch noise: the draws of steps < n are on their way to the device"""
+        if self._stage is None or min(n, self.n_draws) <= self._drawn:
+            return
+        n, g = min(n, self.n_draws), self._gpt
+        while self._drawn < n:
+            # persistent pinned staging ring (3 slots): exponential_ straight into pinned memory, stream-ordered async
+            # upload that lands after the chunk in flight and before the steps that read it; a slot is reused once the
+            # copy that last read it has completed
+            k = min(n - self._drawn, self._cap)
+            slot = g._stage_next % 3
+            g._stage_next += 1
+            buf, ev = self._stage[slot]
+            if ev is not None:
+                ev.synchronize()
+            for i in range(k):
+                self._states.append(torch.random.get_rng_state())
+                buf[i].exponential_(1)
+            self.buf[self._drawn:self._drawn + k].copy_(buf[:k], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(g.device))
+            self._stage[slot][1] = ev
+            self._drawn += k
+
+    def restore(self, used: int) -> None:
+        """Leave torch's CPU generator where the reference would have left it: after `used` multinomial draws."""
+        if self._states and used < len(self._states):
+            torch.random.set_rng_state(self._states[used])
+
+
+def resolve_generate(n_prompts: int, max_batch: int, num_vq: int, vocab_code: int, vocab_text: int, fp16_invariant: bool, *, temperature, eos_token, max_new_token=2048,
+                     min_new_token=0, logits_warpers=(), logits_processors=(), infer_text=False, noise="auto", seed=None, utt_ids=None, row_limits=None,
+                     sampling_per_row=None, prompt_of=None) -> SimpleNamespace:
+    """Everything generate() decides before it touches the device, from its arguments and a few engine facts (`n_prompts` = the rows of inputs_ids;
+    `fp16_invariant` = an fp16 engine under an invariant option).  Pure but for the seed: one draw from torch's CPU generator, only for device noise without one."""
+    B, share = int(n_prompts), None
+    if prompt_of is not None:             # B sequences on n_prompts prompts
+        prompt_groups(prompt_of, n_prompts, infer_text=infer_text)            # (refusals; emb / mask keep the caller's prompt order)
+        share = (np.ascontiguousarray([int(p) for p in prompt_of], dtype=np.int32), int(n_prompts))
+        B = int(share[0].size)
+        if B > max_batch:
+            raise _lib.HipBackendError(f"prompt_of: {B} sequences exceed max_batch={max_batch}")
+    V, rows_per_seq = (vocab_text, 1) if infer_text else (vocab_code, num_vq)      # multinomial rows per sequence: [B, V_text] vs [B*4, 626] (gpt.py:444-467)
+    sc = sampler_cfg_from_objects(temperature, int(eos_token), int(max_new_token), min_new_token, logits_warpers, logits_processors, num_vq, infer_text=infer_text)
+    knobs = row_sampling_array(sc, sampling_per_row, B, num_vq, infer_text) if sampling_per_row is not None else None
+    if isinstance(noise, str) and noise == "auto":
+        # host draws cost ~21 ns per element and step: 10k elements (4 sequences x 4 x 626) hide behind the GPU step, one
+        # 21178-wide refine-text row already does not (measured: 502 vs 423 us/step at batch 1, 1.2 vs 0.5 ms at batch 4)
+        # (an fp16 engine under "schedule_invariant" takes device noise only: ctts_gpt_begin refuses a caller's draws there)
+        noise = "torch" if (B <= 4 and B * rows_per_seq * V <= 16384 and not fp16_invariant) else "device"
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (isinstance(noise, str) and noise == "device") else 0
+    uid_arr = None if utt_ids is None else np.ascontiguousarray([int(u) for u in utt_ids], dtype=np.uint64)
+    assert uid_arr is None or uid_arr.size == B, "utt_ids: one id per sequence"
+    lim_arr = None if row_limits is None else np.ascontiguousarray([int(u) for u in row_limits], dtype=np.int32)
+    assert lim_arr is None or lim_arr.size == B, "max_new_tokens_per_row: one limit per sequence"
+    return SimpleNamespace(B=B, share=share, sc=sc, knobs=knobs, noise=noise, seed=int(seed), utt_ids=uid_arr, row_limits=lim_arr, rows_per_seq=rows_per_seq, V=V)
+
+
 class DecodeSession:
     """The one driver of continuous batching: a generate state kept open while utterances are seated, decoded, delivered and replaced.  GPT.open_session hands it
     out -- utterances are submitted and cancelled while others decode, the decode batch is as wide as the utterances in flight need (it grows, ctts_gpt_grow +
@@ -782,10 +891,7 @@ class DecodeSession:
         self.shared_prompts: List[tuple] = []      # (rows, prompts) per begin / admit of a state with shared prompt passes
         self.launched = 0
         self._req = {}                             # ticket -> (prompt [T, H] on the device, attended length n <= T, knobs or None, adapter slot or None, mode 0 / 1)
-        self._pins = [torch.zeros(2 * int(rows), dtype=torch.int32).pin_memory() for _ in range(2)]
-        self._evs = [torch.cuda.Event() for _ in range(2)]
-        self._layouts = [None, None]
-        self._pending: List[int] = []
+        self._ring = ReportRing(2 * int(rows))      # the row reports of the two chunks in flight
         self._share, self._hold = share, hold
         self._adapters = False                     # an utterance of this session named an adapter slot: every admission names its rows' slots from then on
         self._stream_mode = {}                     # streaming ticket -> "exact" / "eager"
@@ -865,26 +971,25 @@ class DecodeSession:
     def _prompts(self, tks):
         """The prompts [k, Ta, H] / masks [k, Ta] of one seating, Ta = the longest attended length among them: a ticket whose tensor has Ta rows or more gives its
         last Ta (a request's tickets are rows of the caller's batch and keep the caller's padding rows), a shorter one is zero-padded on the left.  With shared
-        prompt passes: one row per prompt the tickets name, and the engine is told which of them each ticket has (for the begin / admit call that follows)."""
+        prompt passes: one row per prompt the tickets name, and `share` = (prompt per ticket, prompts) for the begin / admit call to stage, or None."""
         g, req = self.gpt, self._req
-        rows = tks
+        rows, share = tks, None
         if self._share is not None:
             prompt_of, n_prompts, slots = self._share
             sel, local, leaders = prompt_groups(prompt_of, n_prompts, slots, subset=tks)
             if len(sel) < len(tks):
-                arr = np.ascontiguousarray(local, dtype=np.int32)
-                _lib.check(g._lib.ctts_gpt_share_prompts(g._h, len(tks), arr.ctypes.data_as(C.c_void_p), len(sel)), "share_prompts")
+                share = (np.ascontiguousarray(local, dtype=np.int32), len(sel))
             self.shared_prompts.append((len(tks), len(sel)))
             rows = [tks[j] for j in leaders]
         Ta = max(1, max(req[tk][1] for tk in rows))
         emb = torch.nn.utils.rnn.pad_sequence([req[tk][0][-Ta:] for tk in rows], batch_first=True, padding_side="left")
         n = torch.as_tensor([req[tk][1] for tk in rows], device=g.device)
         mask = (torch.arange(Ta, device=g.device)[None, :] >= (Ta - n)[:, None]).to(torch.int32)
-        return Ta, emb, mask
+        return Ta, emb, mask, share
 
     def _seat(self, seats, st, begin: bool = False):
-        """Carries out one seating [(row, ticket)]: ctts_gpt_begin (the state's first: prompt pass and first sample included) or ctts_gpt_admit, after the per-row
-        attributes -- shared prompts, adapter slots, sampling knobs, row modes -- that the call picks up"""
+        """Carries out one seating [(row, ticket)]: the state's first (GPT._begin_state, then the first sample) or ctts_gpt_admit, with the per-row attributes --
+        adapter slots, sampling knobs, row modes, shared prompts -- that the call picks up"""
         g, lib, h, utts, req = self.gpt, self.gpt._lib, self.gpt._h, self.book.utts, self._req
         tks = [tk for _, tk in seats]
         k = len(tks)
@@ -897,7 +1002,7 @@ class DecodeSession:
 
         rows, uids, lims = arr([r for r, _ in seats]), arr([utts[tk]["utt_id"] for tk in tks], np.uint64), arr([utts[tk]["limit"] for tk in tks])
         outs, atts = arr([utts[tk]["slot"] for tk in tks]), arr([utts[tk]["attempt"] for tk in tks])
-        Ta, emb, mask = self._prompts(tks)
+        Ta, emb, mask, share = self._prompts(tks)
         slots = arr([-1 if req[tk][3] is None else req[tk][3] for tk in tks]) if self._adapters else None
         knobs = None
         if any(req[tk][2] is not None for tk in tks):
@@ -911,28 +1016,16 @@ class DecodeSession:
                 _lib.check(lib.ctts_gpt_admit_sampling(h, k, ptr(rows), knobs, st), "admit_sampling")
             if self.text_sc is not None:
                 _lib.check(lib.ctts_gpt_admit_modes(h, k, ptr(rows), ptr(modes), st), "admit_modes")
-            _lib.check(lib.ctts_gpt_admit(h, k, ptr(rows), Ta, mask.data_ptr(), emb.data_ptr(), ptr(uids), ptr(lims), ptr(outs), ptr(atts), st), "admit")
+            try:                          # (the shared prompt passes are staged next to the admit they are for, and cleared whether or not it took them)
+                if share is not None:
+                    _lib.check(lib.ctts_gpt_share_prompts(h, k, ptr(share[0]), share[1]), "share_prompts")
+                _lib.check(lib.ctts_gpt_admit(h, k, ptr(rows), Ta, mask.data_ptr(), emb.data_ptr(), ptr(uids), ptr(lims), ptr(outs), ptr(atts), st), "admit")
+            finally:
+                lib.ctts_gpt_share_prompts(h, 0, None, 0)
             self.admissions.append((self.launched, k))
             return
-        io = self.out.io(self.max_new, self.seed, uids, lims)
-        if slots is not None:
-            g.set_row_adapters(slots.tolist())
-        if knobs is not None:
-            _lib.check(lib.ctts_gpt_set_row_sampling(h, knobs, k), "set_row_sampling")
-        if modes.any():
-            _lib.check(lib.ctts_gpt_set_row_modes(h, ptr(modes), k), "set_row_modes")
-        try:
-            _lib.check(lib.ctts_gpt_begin(h, k, Ta, mask.data_ptr(), C.byref(self.sc), C.byref(io), st), "begin")
-        finally:
-            if knobs is not None:
-                lib.ctts_gpt_set_row_sampling(h, None, 0)
-            if modes.any():
-                lib.ctts_gpt_set_row_modes(h, None, 0)
-        if self.text_sc is not None:               # (after begin, which creates the state; before the first sample, which a begun text row needs it for)
-            _lib.check(lib.ctts_gpt_enable_text_rows(h, C.byref(self.text_sc), self.out.tids.data_ptr(), st), "enable_text_rows")
-        if self.out.lps is not None:
-            _lib.check(lib.ctts_gpt_set_logprob_out(h, self.out.lps[0].data_ptr(), self.out.lps[1].data_ptr(), st), "set_logprob_out")
-        _lib.check(lib.ctts_gpt_prefill(h, emb.data_ptr(), st), "prefill")
+        g._begin_state(st, k, Ta, mask, emb, self.sc, self.out.io(self.max_new, self.seed, uids, lims), self.out, knobs=knobs, modes=modes if modes.any() else None,
+                       adapters=None if slots is None else slots.tolist(), share=share, text_sc=self.text_sc)
         _lib.check(lib.ctts_gpt_sample(h, st), "sample")
         self.launched = 1
         self.batch_trace.append((self.launched, k))
@@ -1004,16 +1097,11 @@ class DecodeSession:
             if book.n_live() > 0:
                 _lib.check(lib.ctts_gpt_decode(h, self.chunk, 1 if g.use_graph else 0, st), "decode")
                 self.launched += self.chunk
-                slot = 1 - self._pending[-1] if self._pending else 0
-                _lib.check(lib.ctts_gpt_rows_enqueue(h, self._pins[slot].data_ptr(), st), "rows_enqueue")
-                self._layouts[slot] = book.book.layout()
-                self._evs[slot].record(torch.cuda.current_stream(g.device))
-                self._pending.append(slot)
-                if len(self._pending) == 2:
-                    slot = self._pending.pop(0)
-                    self._evs[slot].synchronize()
-                    lay = self._layouts[slot]
-                    states = self._pins[slot][:2 * len(lay)].view(-1, 2).tolist()
+                _lib.check(lib.ctts_gpt_rows_enqueue(h, self._ring.free[0].data_ptr(), st), "rows_enqueue")
+                self._ring.push(book.book.layout())
+                if len(self._ring.pending) == 2:
+                    lay, (words,) = self._ring.pop()
+                    states = words[:2 * len(lay)].view(-1, 2).tolist()
                     out += [self._result(*r) for r in book.report(lay, states)]
                     self.live = book.live
         return out
@@ -1056,11 +1144,8 @@ class DecodeSession:
         try:
             if self.book.begun and getattr(g, "_h", None) and g._h.value:
                 with torch.cuda.device(g.device):
-                    st = g._stream()
-                    torch.cuda.current_stream(g.device).synchronize()
-                    steps, alld = C.c_int32(0), C.c_int32(0)
-                    _lib.check(g._lib.ctts_gpt_progress(g._h, C.byref(steps), C.byref(alld), st), "progress")
-                    g.saturations = g._report_saturations(g._h, st, "session")
+                    g._end_state(g._stream())
+                    g.saturations = g._report_saturations(g._h, g._stream(), "session")
         finally:
             self._hold.release()
 
@@ -1073,9 +1158,9 @@ class _BusyToken:
 
 class EngineHold:
     """The busy token of a loaded engine, taken for one call or one session (GPT._hold) -- engine state (batch, step counters, noise staging ring) and the KV cache,
-    shared with LoRA-merged sibling engines, belong to ONE of them at a time.  A context manager; release() hands the token back together with the per-call
-    engine settings named in `resets`: "share" (shared prompt passes: a call that failed before its begin leaves nothing pending), "adapters", "sampling" (a
-    later plain call takes its own values)."""
+    shared with LoRA-merged sibling engines, belong to ONE of them at a time.  A context manager; release() hands the token back together with the one sticky
+    engine setting a call or session may have made, named in `resets`: "adapters" (set_row_adapters: a later plain call names its own).  Requests that are
+    staged for one begin / admit -- sampling knobs, row modes, shared prompts -- are cleared by whoever staged them (GPT._begin_state, DecodeSession._seat)."""
 
     def __init__(self, gpt: "GPT", busy: str, resets=()):
         if not gpt._finalized:
@@ -1095,13 +1180,8 @@ class EngineHold:
     def release(self) -> None:
         g = self.gpt
         try:
-            if getattr(g, "_h", None) and g._h.value:
-                if "share" in self.resets:
-                    g._lib.ctts_gpt_share_prompts(g._h, 0, None, 0)
-                if "adapters" in self.resets:
-                    g.set_row_adapters(None)
-                if "sampling" in self.resets:
-                    g._lib.ctts_gpt_set_row_sampling(g._h, None, 0)
+            if "adapters" in self.resets and getattr(g, "_h", None) and g._h.value:
+                g.set_row_adapters(None)
         finally:
             g._busy_token.owner = None
 
@@ -1419,211 +1499,152 @@ class GPT:
             raise _lib.HipBackendError("return_attn=True is unsupported (the reference's eager attention path is broken, SURVEY F2)")
         if return_logprobs and infer_text:
             raise _lib.HipBackendError("return_logprobs: the refine-text pass (infer_text=True) returns no log-probs; code mode only")
-        with self._hold("GPT.generate is already running on this engine (or on an engine sharing its KV cache): exhaust or close the previous generator first",
-                        prompt_of is not None and "share", sampling_per_row is not None and "sampling"):
-            yield from self._generate(emb, inputs_ids, temperature, eos_token, attention_mask, max_new_token, min_new_token, logits_warpers,
-                                      logits_processors, infer_text, return_hidden, stream, ensure_non_empty, stream_batch, context, noise, seed,
-                                      max_restarts, utt_ids, max_new_tokens_per_row, sampling_per_row, bool(return_logprobs), prompt_of)
+        with self._hold("GPT.generate is already running on this engine (or on an engine sharing its KV cache): exhaust or close the previous generator first"):
+            call = resolve_generate(int(inputs_ids.shape[0]), self.max_batch, self.num_vq, self.num_audio_tokens, self.num_text_tokens,
+                                    self.dtype_code == _lib.DTYPE_F16 and bool(self.invariant_option()), temperature=temperature, eos_token=eos_token,
+                                    max_new_token=max_new_token, min_new_token=min_new_token, logits_warpers=logits_warpers, logits_processors=logits_processors,
+                                    infer_text=infer_text, noise=noise, seed=seed, utt_ids=utt_ids, row_limits=max_new_tokens_per_row,
+                                    sampling_per_row=sampling_per_row, prompt_of=prompt_of)
+            yield from self._generate(call, emb, inputs_ids, attention_mask, context or Context(), stream, stream_batch, ensure_non_empty, max_restarts,
+                                      return_hidden, bool(return_logprobs))
 
-    def _generate(self, emb, inputs_ids, temperature, eos_token, attention_mask, max_new_token, min_new_token, logits_warpers, logits_processors,
-                  infer_text, return_hidden, stream, ensure_non_empty, stream_batch, context, noise, seed, max_restarts, utt_ids=None,
-                  row_limits=None, sampling_per_row=None, return_logprobs=False, prompt_of=None):
-        context = context or Context()
+    def _begin_state(self, st, k: int, T: int, mask, emb, sc, io, out: OutBuffers, knobs=None, modes=None, adapters=None, share=None, text_sc=None) -> None:
+        """Creates a generate state for k rows (generate() and a session's first seating): stages `adapters` (slot per row; sticky: the caller's EngineHold resets
+        it), `knobs` (ctts_row_sampling [k]), `modes` (int32 [k]) and `share` (prompt per row int32 [k], prompts), then ctts_gpt_begin, the text rows, the log-prob
+        outputs of `out` and the prompt pass.  Nothing staged for a begin outlives it, whether or not begin took it: a later plain call finds nothing pending."""
         lib, h = self._lib, self._h
-        B, T = int(inputs_ids.shape[0]), int(inputs_ids.shape[1])
-        share = None
-        if prompt_of is not None:             # B sequences on inputs_ids.shape[0] prompts
-            prompt_groups(prompt_of, B, infer_text=infer_text)                # (refusals; emb / mask keep the caller's prompt order)
-            share = np.ascontiguousarray([int(p) for p in prompt_of], dtype=np.int32)
-            n_prompts, B = B, int(share.size)
-            if B > self.max_batch:
-                raise _lib.HipBackendError(f"prompt_of: {B} sequences exceed max_batch={self.max_batch}")
-        V, H, NVQ = (self.num_text_tokens if infer_text else self.num_audio_tokens), self.model_dim, self.num_vq
-        rows_per_seq = 1 if infer_text else NVQ          # multinomial rows per sequence: [B, V_text] vs [B*4, 626] (gpt.py:444-467)
-        dev = self.device
-        max_new_token = int(max_new_token)
-        sc = sampler_cfg_from_objects(temperature, int(eos_token), max_new_token, min_new_token, logits_warpers, logits_processors, NVQ,
-                                      infer_text=infer_text)
-        knobs = row_sampling_array(sc, sampling_per_row, B, NVQ, infer_text) if sampling_per_row is not None else None
-        if isinstance(noise, str) and noise == "auto":
-            # host draws cost ~21 ns per element and step: 10k elements (4 sequences x 4 x 626) hide behind the GPU step, one
-            # 21178-wide refine-text row already does not (measured: 502 vs 423 us/step at batch 1, 1.2 vs 0.5 ms at batch 4)
-            # (an fp16 engine under "schedule_invariant" takes device noise only: ctts_gpt_begin refuses a caller's draws there)
-            noise = "torch" if (B <= 4 and B * rows_per_seq * V <= 16384 and not (self.dtype_code == _lib.DTYPE_F16 and self.invariant_option())) else "device"
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (isinstance(noise, str) and noise == "device") else 0
+        try:
+            if adapters is not None:
+                self.set_row_adapters(adapters)
+            if knobs is not None:
+                _lib.check(lib.ctts_gpt_set_row_sampling(h, knobs, k), "set_row_sampling")
+            if modes is not None:
+                _lib.check(lib.ctts_gpt_set_row_modes(h, modes.ctypes.data_as(C.c_void_p), k), "set_row_modes")
+            if share is not None:
+                _lib.check(lib.ctts_gpt_share_prompts(h, k, share[0].ctypes.data_as(C.c_void_p), share[1]), "share_prompts")
+            _lib.check(lib.ctts_gpt_begin(h, k, T, mask.data_ptr(), C.byref(sc), C.byref(io), st), "begin")
+        finally:
+            lib.ctts_gpt_set_row_sampling(h, None, 0)
+            lib.ctts_gpt_set_row_modes(h, None, 0)
+            lib.ctts_gpt_share_prompts(h, 0, None, 0)
+        if text_sc is not None:                    # (after begin, which creates the state; before the first sample, which a begun text row needs it for)
+            _lib.check(lib.ctts_gpt_enable_text_rows(h, C.byref(text_sc), out.tids.data_ptr(), st), "enable_text_rows")
+        if out.lps is not None:
+            _lib.check(lib.ctts_gpt_set_logprob_out(h, out.lps[0].data_ptr(), out.lps[1].data_ptr(), st), "set_logprob_out")
+        _lib.check(lib.ctts_gpt_prefill(h, emb.data_ptr(), st), "prefill")
+
+    def _end_state(self, st) -> int:
+        """The end of a generate state: waits for everything launched and returns the steps taken.  ctts_gpt_progress raises the device give-up word (a persistent
+        launch's bounded wait ran out, or a projection tile never got its low-rank term: later launches were no-ops, the sampler drew from stale rows: no audio)"""
+        torch.cuda.current_stream(self.device).synchronize()
+        steps, alld = C.c_int32(0), C.c_int32(0)
+        _lib.check(self._lib.ctts_gpt_progress(self._h, C.byref(steps), C.byref(alld), st), "progress")
+        return steps.value
+
+    def _generate(self, call, emb, inputs_ids, attention_mask, context, stream, stream_batch, ensure_non_empty, max_restarts, return_hidden, return_logprobs):
+        """generate() on a held engine: setup, step 0 with its restarts, the streamed or the pipelined loop, the end of the state"""
+        lib, h, dev, B, T = self._lib, self._h, self.device, call.B, int(inputs_ids.shape[1])
+        infer_text, max_new = bool(call.sc.infer_text), int(call.sc.max_new_token)
+        self.compactions, self.shared_prompts = [], [] if call.share is None else [(B, call.share[1])]
         mask = torch.ones(int(inputs_ids.shape[0]), T, dtype=torch.int32, device=dev) if attention_mask is None else attention_mask.to(dev).to(torch.int32).contiguous()
         emb = emb.to(dev, dtype=torch.float32).contiguous()
-        out = OutBuffers(B, max_new_token, self, return_hidden, return_logprobs)
-        finish = out.finish
-        n_draws = max_new_token + max_restarts
-        qbuf = None
-        rng_states = []
-        host_q = None
-        if isinstance(noise, str) and noise == "torch":
-            qbuf = torch.empty(n_draws, B * rows_per_seq, V, dtype=torch.float32, device=dev)
-        elif isinstance(noise, str) and noise == "device":
-            qbuf = None
-        else:
-            host_q = torch.as_tensor(noise, dtype=torch.float32)
-            n_draws = int(host_q.shape[0])
-            qbuf = host_q.to(dev).contiguous()
-        uid_arr = lim_arr = None
-        if utt_ids is not None:
-            uid_arr = np.ascontiguousarray([int(u) for u in utt_ids], dtype=np.uint64)
-            assert uid_arr.size == B, "utt_ids: one id per sequence"
-        if row_limits is not None:
-            lim_arr = np.ascontiguousarray([int(u) for u in row_limits], dtype=np.int32)
-            assert lim_arr.size == B, "max_new_tokens_per_row: one limit per sequence"
-        io = out.io(n_draws, seed, uid_arr, lim_arr, qbuf)
-        drawn = 0
-        stage_cap = max(int(self.chunk_steps), int(stream_batch) if stream else 1, 1)
-        stage = self._staging(B * rows_per_seq, V, stage_cap) if (isinstance(noise, str) and noise == "torch") else None
-
-        def draw_to(n):
-            nonlocal drawn
-            if not (isinstance(noise, str) and noise == "torch"):
-                return
-            n = min(n, n_draws)
-            if n <= drawn:
-                return
-            while drawn < n:
-                # persistent pinned staging ring (3 slots): exponential_ straight into pinned memory, stream-ordered async
-                # upload that lands after the chunk in flight and before the steps that read it; a slot is reused once the
-                # copy that last read it has completed
-                k = min(n - drawn, stage_cap)
-                slot = self._stage_next % 3
-                self._stage_next += 1
-                buf, ev = stage[slot]
-                if ev is not None:
-                    ev.synchronize()
-                for i in range(k):
-                    rng_states.append(torch.random.get_rng_state())
-                    buf[i].exponential_(1)
-                qbuf[drawn:drawn + k].copy_(buf[:k], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(dev))
-                stage[slot][1] = ev
-                drawn += k
-
-        import time as _t
+        out = OutBuffers(B, max_new, self, return_hidden, return_logprobs)
+        feed = NoiseFeed(self, call.noise, max_new + max_restarts, B * call.rows_per_seq, call.V, max(int(self.chunk_steps), int(stream_batch) if stream else 1, 1))
+        io = out.io(feed.n_draws, call.seed, call.utt_ids, call.row_limits, feed.buf)
         tm = self.host_timing = {}
-        t_last = [_t.perf_counter()]
+        t_last = [time.perf_counter()]
 
         def tick(name):
-            now = _t.perf_counter()
+            now = time.perf_counter()
             tm[name] = tm.get(name, 0.0) + (now - t_last[0]) * 1e3
             t_last[0] = now
 
         with torch.cuda.device(dev):
             st = self._stream()
             tick("setup")
-            if knobs is not None:
-                _lib.check(lib.ctts_gpt_set_row_sampling(h, knobs, B), "set_row_sampling")
-            self.shared_prompts = []
-            if share is not None:
-                _lib.check(lib.ctts_gpt_share_prompts(h, B, share.ctypes.data_as(C.c_void_p), n_prompts), "share_prompts")
-                self.shared_prompts.append((B, n_prompts))
-            _lib.check(lib.ctts_gpt_begin(h, B, T, mask.data_ptr(), C.byref(sc), C.byref(io), st), "begin")
-            if out.lps is not None:
-                _lib.check(lib.ctts_gpt_set_logprob_out(h, out.lps[0].data_ptr(), out.lps[1].data_ptr(), st), "set_logprob_out")
-            _lib.check(lib.ctts_gpt_prefill(h, emb.data_ptr(), st), "prefill")
+            self._begin_state(st, B, T, mask, emb, call.sc, io, out, knobs=call.knobs, share=call.share)
             tick("begin+prefill")
-            steps, alld = C.c_int32(0), C.c_int32(0)
-            used_draws = 0
-            # step 0 (+ ensure_non_empty regenerate, gpt.py:496-525)
+            # step 0 with the batch-wide ensure_non_empty regenerate (gpt.py:496-525): while a sequence's first token is EOS, every sequence samples again
+            used, steps, alld = 0, C.c_int32(0), C.c_int32(0)
             while True:
-                draw_to(used_draws + 1)
+                feed.draw_to(used + 1)
                 _lib.check(lib.ctts_gpt_sample(h, st), "sample")
-                used_draws += 1
+                used += 1
                 _lib.check(lib.ctts_gpt_progress(h, C.byref(steps), C.byref(alld), st), "progress")
-                if bool(finish.any().item()):
-                    if ensure_non_empty and used_draws < max_restarts:
-                        _lib.check(lib.ctts_gpt_restart(h, st), "restart")
-                        continue
-                    self._restore_rng(rng_states, used_draws)
+                if not bool(out.finish.any().item()):
+                    break
+                if not (ensure_non_empty and used < max_restarts):
+                    feed.restore(used)
                     return                                   # gpt.py:525 bare return
-                break
+                _lib.check(lib.ctts_gpt_restart(h, st), "restart")
             tick("step0")
-            chunk = int(stream_batch) if stream else self.chunk_steps
             if stream:
                 # streaming: synchronous polling; like the reference (gpt.py:531-543) a partial result is yielded whenever the number
                 # of generated tokens is a multiple of stream_batch -- also when that step was the last one, so the final yield
                 # below can repeat it, exactly as the reference does
-                while not alld.value and steps.value < max_new_token and not context.get():
-                    n = min(chunk - steps.value % chunk, max_new_token - steps.value)
-                    draw_to(used_draws + n)
+                chunk = int(stream_batch)
+                while not alld.value and steps.value < max_new and not context.get():
+                    n = min(chunk - steps.value % chunk, max_new - steps.value)
+                    feed.draw_to(used + n)
                     _lib.check(lib.ctts_gpt_decode(h, n, 1 if self.use_graph else 0, st), "decode")
                     prev = steps.value
                     _lib.check(lib.ctts_gpt_progress(h, C.byref(steps), C.byref(alld), st), "progress")
-                    used_draws += steps.value - prev
+                    used += steps.value - prev
                     if steps.value == prev and not alld.value:
                         raise _lib.HipBackendError("decode made no progress (device state inconsistent)")
                     if steps.value % chunk == 0 and steps.value > prev:
                         yield self._outputs(out, infer_text)
             else:
-                # one chunk stays in flight while the previous chunk's progress words are inspected (no GPU bubble at the
-                # poll); steps launched after every sequence finished exit at their first instruction on the device
-                pins = [torch.zeros(4, dtype=torch.int32).pin_memory() for _ in range(2)]
-                evs = [torch.cuda.Event() for _ in range(2)]
-                restarts = used_draws - steps.value            # draws spent on ensure_non_empty regenerations
-                launched, n_chunks, pending = steps.value, 0, []
-                # finished-row compaction (no counterpart in the reference, where finished rows keep computing until the slowest one ends,
-                # gpt.py:527-546): the per-row finish flags travel with the progress words; rows known to have finished are dropped from
-                # the decode batch at the next chunk boundary (ctts_gpt_compact), down to the next size of compact_size()
-                compacting = self.compact and (not infer_text) and B >= 8
-                if compacting:
-                    chunk = max(4, min(chunk, self.compact_chunk))
-                rowpins = [torch.zeros(2 * B, dtype=torch.int32).pin_memory() for _ in range(2)] if compacting else None
-                row_seq = list(range(B))                       # current decode row -> sequence
-                layouts = [None, None]
-                done_seq = set()
-                self.compactions = []
-                while True:
-                    while len(pending) < 2 and launched < max_new_token and not context.get():
-                        n = min(chunk, max_new_token - launched)
-                        tick("loop_other")
-                        draw_to(restarts + launched + n)
-                        tick("draw")
-                        _lib.check(lib.ctts_gpt_decode(h, n, 1 if self.use_graph else 0, st), "decode")
-                        tick("decode_launch")
-                        launched += n
-                        slot = n_chunks % 2
-                        n_chunks += 1
-                        _lib.check(lib.ctts_gpt_progress_enqueue(h, pins[slot].data_ptr(), st), "progress_enqueue")
-                        if compacting:
-                            _lib.check(lib.ctts_gpt_rows_enqueue(h, rowpins[slot].data_ptr(), st), "rows_enqueue")
-                            layouts[slot] = list(row_seq)
-                        evs[slot].record(torch.cuda.current_stream(dev))
-                        pending.append(slot)
-                    if not pending:
-                        break
-                    slot = pending.pop(0)
-                    tick("loop_other")
-                    evs[slot].synchronize()
-                    tick("event_wait")
-                    if int(pins[slot][2]) or int(pins[slot][0]) >= max_new_token or context.get():
-                        break
-                    if compacting:
-                        flags = rowpins[slot][:2 * len(layouts[slot])].view(-1, 2)[:, 0].tolist()
-                        done_seq.update(sq for sq, f in zip(layouts[slot], flags) if f)
-                        live = [r for r, sq in enumerate(row_seq) if sq not in done_seq]
-                        target = compact_size(len(live))
-                        if live and target < len(row_seq):
-                            fill = [r for r, sq in enumerate(row_seq) if sq in done_seq][:target - len(live)]
-                            keep = np.ascontiguousarray(sorted(live + fill), dtype=np.int32)
-                            _lib.check(lib.ctts_gpt_compact(h, keep.ctypes.data_as(C.c_void_p), int(keep.size), st), "compact")
-                            row_seq = [row_seq[r] for r in keep.tolist()]
-                            self.compactions.append((launched, len(row_seq)))
-                prev = steps.value
-                _lib.check(lib.ctts_gpt_progress(h, C.byref(steps), C.byref(alld), st), "progress")
-                used_draws += steps.value - prev
+                self._pipelined_loop(st, call, feed, context, tick, used - steps.value, steps.value)
+                used += self._end_state(st) - steps.value
                 tick("final_progress")
-            self._restore_rng(rng_states, used_draws)
+            feed.restore(used)             # (before the saturation report, which may warn: torch's generator is left right whatever follows)
             self.saturations = self._report_saturations(h, st, "generate()")
             res = self._outputs(out, infer_text)
             tick("outputs")
             yield res
+
+    def _pipelined_loop(self, st, call, feed: NoiseFeed, context, tick, restarts: int, launched: int) -> None:
+        """One chunk stays in flight while the previous chunk's progress words are inspected (no GPU bubble at the poll); steps launched after every sequence
+        finished exit at their first instruction on the device.  `restarts` = draws spent on ensure_non_empty regenerations, `launched` = steps so far."""
+        lib, h, B, max_new, graph, chunk = self._lib, self._h, call.B, int(call.sc.max_new_token), 1 if self.use_graph else 0, self.chunk_steps
+        # finished-row compaction (no counterpart in the reference, where finished rows keep computing until the slowest one ends,
+        # gpt.py:527-546): the per-row finish flags travel with the progress words; rows known to have finished are dropped from
+        # the decode batch at the next chunk boundary (ctts_gpt_compact), down to the next size of compact_size()
+        compacting = self.compact and (not call.sc.infer_text) and B >= 8
+        if compacting:
+            chunk = max(4, min(chunk, self.compact_chunk))
+        ring = ReportRing(4, 2 * B) if compacting else ReportRing(4)
+        row_seq, done_seq = list(range(B)), set()      # current decode row -> sequence; the sequences known to have finished
+        while True:
+            while len(ring.pending) < 2 and launched < max_new and not context.get():
+                n = min(chunk, max_new - launched)
+                tick("loop_other")
+                feed.draw_to(restarts + launched + n)
+                tick("draw")
+                _lib.check(lib.ctts_gpt_decode(h, n, graph, st), "decode")
+                tick("decode_launch")
+                launched += n
+                _lib.check(lib.ctts_gpt_progress_enqueue(h, ring.free[0].data_ptr(), st), "progress_enqueue")
+                if compacting:
+                    _lib.check(lib.ctts_gpt_rows_enqueue(h, ring.free[1].data_ptr(), st), "rows_enqueue")
+                ring.push(list(row_seq) if compacting else None)
+            if not ring.pending:
+                break
+            tick("loop_other")
+            layout, bufs = ring.pop()
+            tick("event_wait")
+            if int(bufs[0][2]) or int(bufs[0][0]) >= max_new or context.get():
+                break
+            if compacting:
+                flags = bufs[1][:2 * len(layout)].view(-1, 2)[:, 0].tolist()
+                done_seq.update(sq for sq, f in zip(layout, flags) if f)
+                keep = compact_keep([sq not in done_seq for sq in row_seq])
+                if keep is not None:
+                    karr = np.ascontiguousarray(keep, dtype=np.int32)
+                    _lib.check(lib.ctts_gpt_compact(h, karr.ctypes.data_as(C.c_void_p), int(karr.size), st), "compact")
+                    row_seq = [row_seq[r] for r in keep]
+                    self.compactions.append((launched, len(row_seq)))
 
     # -- continuous batching: more utterances than decode rows (no counterpart in the reference) ------------------------------------
     @torch.no_grad()
@@ -1676,8 +1697,7 @@ class GPT:
         logprobs, sampled_logprobs, final_logprobs: lists of one), and the returned GenerationOutputs carries the three fields for all N."""
         if return_logprobs and infer_text:
             raise _lib.HipBackendError("return_logprobs: the refine-text pass (infer_text=True) returns no log-probs; code mode only")
-        with self._hold("GPT.generate is already running on this engine (or on an engine sharing its KV cache)", prompt_of is not None and "share",
-                        adapter_slots is not None and "adapters", sampling_per_row is not None and "sampling"):
+        with self._hold("GPT.generate is already running on this engine (or on an engine sharing its KV cache)", adapter_slots is not None and "adapters"):
             return (yield from self._generate_many(emb, inputs_ids, temperature, eos_token, attention_mask, int(max_new_token), min_new_token, logits_warpers,
                                                    logits_processors, return_hidden, ensure_non_empty, context or Context(), seed, max_restarts, utt_ids,
                                                    max_new_tokens_per_row, rows, admit_min, bool(infer_text), bool(progress), adapter_slots,
@@ -1749,13 +1769,8 @@ class GPT:
                 if done:
                     yield [event(r) for r in done]
                 ses._rebalance()
-            st = self._stream()
-            torch.cuda.current_stream(dev).synchronize()
-            # the device give-up word (a persistent launch's bounded wait ran out, or a projection tile never got its low-rank term): every later launch of the
-            # request was a no-op and the sampler kept drawing from stale rows -- an error, not audio (ctts_gpt_progress raises it, as in generate())
-            steps, alld = C.c_int32(0), C.c_int32(0)
-            _lib.check(self._lib.ctts_gpt_progress(self._h, C.byref(steps), C.byref(alld), st), "progress")
-            self.saturations = self._report_saturations(self._h, st, "generate_many()")
+            self._end_state(self._stream())
+            self.saturations = self._report_saturations(self._h, self._stream(), "generate_many()")
             return self._outputs(ses.out, infer_text, order=np.argsort(np.asarray(back)).tolist())      # input order again
 
     # -- serving session (ctts_gpt_grow / ctts_gpt_cancel) ------------------------------------------------------------------------
@@ -1843,21 +1858,6 @@ class GPT:
         ams = [am[b, :n[b]] for b in range(B)]
         nll, acc, loss, accuracy = score_reduce(lps, ams, [tg[b, :n[b]] for b in range(B)])
         return ScoreOutputs(logprob=lps, argmax=ams, nll=nll, seq_accuracy=acc, loss=loss, accuracy=accuracy)
-
-    def _staging(self, rows: int, V: int, cap: int):
-        """Pinned [cap, rows, V] staging slots for the torch-generator noise, kept across calls (pinning is expensive)."""
-        key = (rows, V, cap)
-        if getattr(self, "_stage_key", None) != key:
-            self._stage_key = key
-            self._stage_bufs = [[torch.empty(cap, rows, V, dtype=torch.float32).pin_memory(), None] for _ in range(3)]
-            self._stage_next = 0
-        return self._stage_bufs
-
-    @staticmethod
-    def _restore_rng(states, used):
-        """Leave torch's CPU generator where the reference would have left it: after `used` multinomial draws."""
-        if states and used < len(states):
-            torch.random.set_rng_state(states[used])
 
     @staticmethod
     def _outputs(out: OutBuffers, infer_text: bool = False, order=None) -> GenerationOutputs:
