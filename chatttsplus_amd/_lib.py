@@ -14,6 +14,9 @@ DTYPE_F16 = 1
 MAX_BATCH = 128
 MAX_ADAPTERS = 8
 NUM_VQ = 4
+RESAMPLE_MAX_TAPS = 1024                   # CTTS_RESAMPLE_MAX_TAPS / _TABLE_BYTES / _WINDOWS (include/ctts_hip.h)
+RESAMPLE_MAX_TABLE_BYTES = 4 << 20
+RESAMPLE_MAX_WINDOWS = 1024
 
 
 class GptCfg(C.Structure):
@@ -144,6 +147,13 @@ SYMBOLS = [
     ("ctts_enc_finalize", C.c_int, [_P]),
     ("ctts_dvae_encode", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P]),
     ("ctts_dvae_encode_batch", C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, _P]),
+    ("ctts_resample_out_total", C.c_int64, [C.c_int, C.c_int, C.c_int64]),
+    ("ctts_resample_settled", C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64]),
+    ("ctts_resample_in_range", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    ("ctts_resampler_create", C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
+    ("ctts_resampler_destroy", None, [_P]),
+    ("ctts_resampler_tile_frames", C.c_int, [_P]),
+    ("ctts_resample_windows", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, C.c_int, _P]),
 ]
 
 _lib = None

@@ -29,10 +29,10 @@ def load_audio(path: str) -> Tuple[torch.Tensor, int]:
     return torch.from_numpy(np.ascontiguousarray(x.T)), int(sr)
 
 
-def resample(wav: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> torch.Tensor:
-    """torchaudio.functional.resample(..., resampling_method="sinc_interp_hann") on [..., n]."""
-    if orig_freq == new_freq:
-        return wav
+def resample_kernels(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+    """(orig, new, width, kernels): the rate pair reduced by its gcd, the one-sided filter width in input samples and the polyphase table
+    kernels [new, 2 width + orig] float32 of torchaudio's sinc_interp_hann resampler.  Output sample i new + p of a waveform x is
+    sum_k kernels[p, k] x[i orig - width + k] (x zero outside the waveform).  Shared by `resample` and the device resampler (hip_models.Resampler)."""
     g = math.gcd(int(orig_freq), int(new_freq))
     orig, new = int(orig_freq) // g, int(new_freq) // g
     base = min(orig, new) * rolloff
@@ -44,11 +44,18 @@ def resample(wav: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_wi
     t = t * math.pi
     scale = base / orig
     kernels = torch.where(t == 0, torch.tensor(1.0, dtype=torch.float64), t.sin() / t) * window * scale
-    kernels = kernels.to(torch.float32)                                         # [new, 1, 2 width + orig]
+    return orig, new, width, kernels.to(torch.float32)[:, 0]                    # [new, 2 width + orig]
+
+
+def resample(wav: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> torch.Tensor:
+    """torchaudio.functional.resample(..., resampling_method="sinc_interp_hann") on [..., n]."""
+    if orig_freq == new_freq:
+        return wav
+    orig, new, width, kernels = resample_kernels(orig_freq, new_freq, lowpass_filter_width, rolloff)
     shape = wav.shape
     x = wav.reshape(-1, shape[-1]).float()
     x = torch.nn.functional.pad(x, (width, width + orig))
-    y = torch.nn.functional.conv1d(x[:, None], kernels, stride=orig)            # [b, new, frames]
+    y = torch.nn.functional.conv1d(x[:, None], kernels[:, None], stride=orig)   # [b, new, frames]
     y = y.transpose(1, 2).reshape(x.shape[0], -1)
     target = math.ceil(new * shape[-1] / orig)
     return y[..., :target].reshape(shape[:-1] + (target,))

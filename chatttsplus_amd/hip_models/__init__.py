@@ -4,3 +4,4 @@ chattts_plus/models/__init__.py) so the pipeline's getattr(models, name)(**kwarg
 from .gpt import GPT  # noqa: F401
 from .vocoder import DVAE, Synth, Vocos  # noqa: F401
 from .encoder import DVAEEncoder  # noqa: F401
+from .resampler import Resampler  # noqa: F401

@@ -474,10 +474,14 @@ class SessionBook:
             raise ValueError(f"session: stream_batch={stream_batch} / stream_speed={stream_speed} (at least 1)")
         self.stream_batch, self.stream_speed, self.hop, self.halo_frames = int(stream_batch), int(stream_speed), int(hop), int(halo_frames)
         self._windows: List[tuple] = []            # windows the reports made due since the last take_windows()
+        self._lookback = {}                        # ticket -> stream_lookback (kept until its final window is built: the ticket itself is released first)
 
     # -- requests ---------------------------------------------------------------------------------
-    def submit(self, T: int, utt_id: int, limit: Optional[int] = None, mode: str = "code", stream: Optional[str] = None, stream_batch: Optional[int] = None) -> int:
-        """`mode` "code" or "text": a text utterance takes a row, a KV lane and an output slot like a code utterance (one index space: a slot is held by one
+    def submit(self, T: int, utt_id: int, limit: Optional[int] = None, mode: str = "code", stream: Optional[str] = None, stream_batch: Optional[int] = None,
+               stream_lookback: int = 0) -> int:
+        """`stream_lookback` (stream="exact" only): samples before each window's s0 that its consumer reads again -- a resampler's left taps; the windows stay
+        the same (s0, s1), DecodeSession vocodes them from max(0, s0 - stream_lookback) (SessionWindow.v0).
+        `mode` "code" or "text": a text utterance takes a row, a KV lane and an output slot like a code utterance (one index space: a slot is held by one
         utterance of either kind); only its token limit is the text rows' own.  `stream` None, "exact" or "eager" (code utterances): sample windows become due
         while it decodes; `stream_batch` defaults to the session's"""
         T = int(T)
@@ -489,6 +493,8 @@ class SessionBook:
             raise ValueError("submit: stream= is for code utterances; a text row produces no audio")
         if stream_batch is not None and (stream is None or int(stream_batch) < 1):
             raise ValueError(f"submit: stream_batch={stream_batch} needs stream= and a value of at least 1")
+        if int(stream_lookback) < 0 or (int(stream_lookback) > 0 and stream != "exact"):
+            raise ValueError(f"submit: stream_lookback={stream_lookback} needs stream=\"exact\" and a value of at least 0")
         if mode == "text" and self.max_new_text is None:
             raise ValueError("submit: mode=\"text\" needs a session opened with text_rows=...")
         if T < 1 or T + self.max_new > self.max_seq:
@@ -499,6 +505,8 @@ class SessionBook:
         self._next += 1
         self.utts[tk] = dict(utt_id=int(utt_id), T=T, limit=lim, attempt=0, slot=None, row_tk=None, cancelled=False, mode=mode, stream=stream,
                              stream_batch=self.stream_batch if stream_batch is None else int(stream_batch), emitted=0, last_n=0)
+        if int(stream_lookback) > 0:
+            self._lookback[tk] = int(stream_lookback)
         self.queue.append(tk)
         return tk
 
@@ -529,6 +537,12 @@ class SessionBook:
             if self.utts[tk].get("stream"):
                 self._windows.append((tk, None, 0, 0, 0, True))
         return out
+
+    def window_v0(self, tk: int, s0: int, final: bool = False) -> int:
+        """First sample to vocode for the window of ticket `tk` that starts at s0: max(0, s0 - stream_lookback), s0 itself without a lookback.  `final`: the
+        ticket's last window -- its lookback is forgotten."""
+        back = self._lookback.pop(tk, 0) if final else self._lookback.get(tk, 0)
+        return max(0, int(s0) - back)
 
     def take_windows(self) -> List[tuple]:
         """[(ticket, slot, tokens seen, s0, s1, final)] made due since the last call, in report order"""
@@ -727,6 +741,11 @@ class SessionWindow:
     hiddens: Optional[torch.Tensor] = None
     cancelled: bool = False       # (final windows) the utterance was cancelled
     mode: str = "exact"
+    v0: int = -1                  # first sample to vocode: max(0, s0 - stream_lookback), the tokens cover [v0, s1); s0 without a lookback
+
+    def __post_init__(self):
+        if self.v0 < 0:
+            self.v0 = self.s0
 
 
 class OutBuffers:
@@ -911,8 +930,9 @@ class DecodeSession:
 
     # -- requests ---------------------------------------------------------------------------------
     def submit(self, emb: torch.Tensor, mask: torch.Tensor, utt_id: int, limit: Optional[int] = None, sampling=None, adapter_slot: Optional[int] = None,
-               mode: str = "code", stream: Optional[str] = None, stream_batch: Optional[int] = None, stream_hidden: bool = True) -> int:
-        """`stream` "exact" / "eager" (SessionBook): sample windows of this utterance become due while it decodes, see take_windows(); `stream_batch` tokens between
+               mode: str = "code", stream: Optional[str] = None, stream_batch: Optional[int] = None, stream_hidden: bool = True, stream_lookback: int = 0) -> int:
+        """`stream_lookback` (stream="exact"): each window is vocoded from max(0, s0 - stream_lookback) (SessionWindow.v0), for a consumer that filters across
+        window boundaries (the output resampler).  `stream` "exact" / "eager" (SessionBook): sample windows of this utterance become due while it decodes, see take_windows(); `stream_batch` tokens between
         windows (default: the session's); `stream_hidden` = the windows are vocoded from hidden rows (needs return_hidden), False = from the ids.
         Queues one utterance: emb [T, H] (GPT.__call__), mask [T] left padded.  `limit` <= max_new_token, `sampling` a dict as in sampling_per_row,
         `adapter_slot` a resident adapter (load_adapter).  `mode` "text" (sessions opened with text_rows=): a refine-text utterance -- its prompt is the refine
@@ -942,16 +962,17 @@ class DecodeSession:
         if slot >= 0 and g.invariant_option():
             raise _lib.HipBackendError(f"submit: per-utterance adapters are outside the {g.invariant_option()} contract; merge the adapter (with_lora) or set the option to 0")
         tk = self._enqueue(emb[emb.shape[0] - n:].to(g.device, dtype=torch.float32).contiguous(), n, utt_id, limit, knobs, slot if slot >= 0 else None, mode,
-                           stream, stream_batch)
+                           stream, stream_batch, stream_lookback)
         if stream is not None:
             self._stream_mode[tk] = stream
         return tk
 
-    def _enqueue(self, prompt: torch.Tensor, n: int, utt_id: int, limit, knobs, adapter: Optional[int], mode: str = "code", stream=None, stream_batch=None) -> int:
+    def _enqueue(self, prompt: torch.Tensor, n: int, utt_id: int, limit, knobs, adapter: Optional[int], mode: str = "code", stream=None, stream_batch=None,
+                 stream_lookback: int = 0) -> int:
         """One ticket: `prompt` [T, H] on the device, of which the last `n` rows are attended (rows before them are the caller's left padding); `adapter` None =
         the utterance names none (an int, -1 included, makes every later seating name its rows' slots)"""
         try:
-            tk = self.book.submit(max(int(n), 1), utt_id, limit, mode, stream=stream, stream_batch=stream_batch)
+            tk = self.book.submit(max(int(n), 1), utt_id, limit, mode, stream=stream, stream_batch=stream_batch, stream_lookback=stream_lookback)
         except ValueError as e:
             raise _lib.HipBackendError(str(e)) from None
         self._req[tk] = (prompt, int(n), knobs, adapter, 1 if mode == "text" else 0)
@@ -1053,15 +1074,20 @@ class DecodeSession:
         dev = self.gpt.device
         for tk, slot, n, s0, s1, final in due:
             mode = self._stream_mode.get(tk, "exact")
+            # a lookback widens the request to [v0, s1): the window stays (s0, s1), clamped as without one
+            v0 = book.window_v0(tk, s0, final)
             if final:
                 # the finished (or cancelled) utterance IS the prefix: settled to its end; built from the delivered clones, the slot is already released
                 self._stream_mode.pop(tk, None)
                 r = by_tk[tk]
-                a, b, _, s0, s1 = window_token_range(n, s0, s1, book.hop, book.halo_frames)
-                out.append(SessionWindow(tk, n, s0, s1, True, a, r.ids[a:b].to(torch.int32), r.hiddens[a:b] if r.hiddens is not None else None, bool(r.cancelled), mode))
+                a, b, _, v0, s1 = window_token_range(n, v0, s1, book.hop, book.halo_frames)
+                s0 = max(v0, min(s0, s1))
+                out.append(SessionWindow(tk, n, s0, s1, True, a, r.ids[a:b].to(torch.int32), r.hiddens[a:b] if r.hiddens is not None else None, bool(r.cancelled), mode,
+                                         v0))
                 continue
-            a, b, _, s0, s1 = window_token_range(n, s0, s1, book.hop, book.halo_frames, clamp_tail=(mode != "exact"))
-            out.append(SessionWindow(tk, n, s0, s1, False, a, self.ids[slot, a:b], self.hid[slot, a:b] if self.hid is not None else None, False, mode))
+            a, b, _, v0, s1 = window_token_range(n, v0, s1, book.hop, book.halo_frames, clamp_tail=(mode != "exact"))
+            s0 = max(v0, min(s0, s1))
+            out.append(SessionWindow(tk, n, s0, s1, False, a, self.ids[slot, a:b], self.hid[slot, a:b] if self.hid is not None else None, False, mode, v0))
         return out
 
     def take_windows(self) -> List[SessionWindow]:

@@ -76,6 +76,7 @@ from .hip_models.vocoder import prefix_samples, prefix_tokens  # noqa: E402
 # reach the engine's per-row table (GPT sampling_per_row, ctts_gpt_set_row_sampling); max_new_token becomes the utterance's token limit, prompt its
 # [speed_N] / [oral_N] prefix, spk_emb its speaker row, spk_smp / txt_smp its cloned voice (the zero-shot audio prompt behind its text and the transcript of
 # that clip in front of it: ClonedVoice.overrides()).  Every other field is per call.
+NATIVE_RATE = 24000         # what the vocoder produces; infer(sample_rate=) / submit(sample_rate=) resample it on the device (hip_models.Resampler)
 PER_UTTERANCE_SAMPLING = ("temperature", "top_P", "top_K", "repetition_penalty", "min_new_token")
 PER_UTTERANCE_FIELDS = PER_UTTERANCE_SAMPLING + ("max_new_token", "prompt", "spk_emb", "spk_smp", "txt_smp")
 
@@ -200,6 +201,7 @@ class _Request:
     stream: bool; use_decoder: bool; skip_refine_text: bool; refine_text_only: bool; continuous: object      # continuous: False | True | "throughput"
     n_cand: int; return_details: bool; select: Optional[Callable]; share_prompt: Optional[bool]; ids_sink: Optional[list]
     overlap_vocoder: bool; vocoder_chunk: object
+    sample_rate: Optional[int] = None                   # infer(sample_rate=): the rate the waveforms leave at; None = the vocoder's own 24 kHz
     device_noise = property(lambda self: self.n_cand > 1 or self.noise_mode == "device")      # (details path) device noise whatever the slice's size
 
     def rows(self, idx, adapters: bool = False, params: bool = True) -> dict:
@@ -328,6 +330,7 @@ class SessionChunk:
     final: bool = False
     details: Optional[SessionDetails] = None
     n_tokens: int = 0             # tokens the utterance had when the chunk was cut ("eager": the chunk is a slice of THAT prefix's waveform)
+    sample_rate: int = 24000      # submit(sample_rate=): `start` and len(wav) count samples at THIS rate
 
 
 class SynthSession:
@@ -340,11 +343,20 @@ class SynthSession:
     ctts_synth_windows call and returns them as SessionChunks.  "exact" emits only samples no later token can change (vocoder.settled_samples: it holds back the
     last 53 tokens' worth until the utterance ends), so the chunks concatenate to the waveform a non-streaming poll returns, bit for bit; "eager" keeps
     infer(stream=True)'s and the reference's semantics -- each chunk is a slice of the PREFIX waveform, whose last 1.1 s is computed against zero padding, so the
-    concatenation is not the offline waveform and chunk boundaries carry seams."""
+    concatenation is not the offline waveform and chunk boundaries carry seams.
+    submit(sample_rate=) (default: open_session(sample_rate=)) delivers an utterance at another rate, resampled on the device (hip_models.Resampler): a
+    non-streaming ticket's waveform after the vocoder, one ctts_resample_windows call per distinct rate of the poll; an "exact" ticket's chunks so that they
+    concatenate, bit for bit, to the resampling of the offline waveform -- each settled window is vocoded as float32 from Resampler.lookback samples before
+    its start (SessionWindow.v0), the outputs it settles (Resampler.out_settled) are cut from it, and PCM conversion happens after resampling.  "eager" chunks
+    are slices of different prefix waveforms: no single waveform to resample, refused."""
 
-    def __init__(self, pipe, gpt, params: InferCodeParams, use_decoder: bool, rows, seed, return_details: bool, refine: Optional[RefineTextParams] = None):
+    def __init__(self, pipe, gpt, params: InferCodeParams, use_decoder: bool, rows, seed, return_details: bool, refine: Optional[RefineTextParams] = None,
+                 sample_rate: Optional[int] = None):
         self.pipe, self.gpt, self.params, self.use_decoder, self.return_details = pipe, gpt, params, bool(use_decoder), bool(return_details)
         self.refine = refine
+        self.sample_rate = None if sample_rate is None else pipe.output_rate(sample_rate, "open_session")      # None: the vocoder's own 24 kHz
+        self._rates = {}                           # code-stage ticket -> its output rate (tickets at 24 kHz are not in it)
+        self._emitted = {}                         # code-stage ticket of a resampled "exact" utterance -> J, the output samples emitted so far
         temperature, num_code, warpers, processors = _code_sampler_args(params, gpt)
         text_rows = None
         if refine is not None:
@@ -377,8 +389,10 @@ class SynthSession:
         return self.session.batch_trace
 
     def submit(self, text: str, params=None, lora_path: Optional[str] = None, utt_id: Optional[int] = None, max_new_token: Optional[int] = None,
-               refine: Optional[bool] = None, stream: Optional[str] = None, stream_batch: Optional[int] = None, pcm16: bool = False) -> int:
-        """`stream` "exact" or "eager": poll() returns this ticket's audio as SessionChunks while it decodes (class docstring; "exact" is the one to use unless the
+               refine: Optional[bool] = None, stream: Optional[str] = None, stream_batch: Optional[int] = None, pcm16: bool = False,
+               sample_rate: Optional[int] = None) -> int:
+        """`sample_rate`: this utterance's output rate in Hz (default: the session's; 24000 = the vocoder's own, today's path): with stream=None or "exact".
+        `stream` "exact" or "eager": poll() returns this ticket's audio as SessionChunks while it decodes (class docstring; "exact" is the one to use unless the
         reference's windows are wanted); `stream_batch`: tokens between chunks (default: the session's params.stream_batch); `pcm16`: its chunks are int16 PCM.
         Queues one text.  `params`: this utterance's overrides (an InferCodeParams or a dict, checked by per_utterance_overrides: sampling knobs,
         max_new_token, prompt, spk_emb, or a cloned voice: spk_smp / txt_smp, e.g. ClonedVoice.overrides() -- the refine stage does not see the voice); `lora_path`: its own adapter; `utt_id`: its noise key (default: a counter).  `refine`: refine the text first (default:
@@ -391,6 +405,10 @@ class SynthSession:
             raise _lib.HipBackendError("submit: stream_batch= and pcm16= belong to a streaming utterance (stream=\"exact\" | \"eager\")")
         if stream_batch is not None and int(stream_batch) < 1:
             raise _lib.HipBackendError(f"submit: stream_batch={stream_batch} (at least 1)")
+        rate = self.sample_rate if sample_rate is None else self.pipe.output_rate(sample_rate, "submit")
+        if rate is not None and stream == "eager":
+            raise _lib.HipBackendError(f"submit: stream=\"eager\" with sample_rate={rate} is not offered: eager chunks are slices of different prefix waveforms, so "
+                                       "there is no single waveform to resample (use stream=\"exact\", or resample the 24 kHz chunks yourself)")
         streaming = None if stream is None else (stream, None if stream_batch is None else int(stream_batch), bool(pcm16))
         refine = (self.refine is not None) if refine is None else bool(refine)
         if refine and self.refine is None:
@@ -419,11 +437,11 @@ class SynthSession:
             input_ids, attention_mask, text_mask = pipe._refine_prompt([t], self.refine)
             emb = gpt(input_ids, text_mask)
             tk = self.session.submit(emb[0], attention_mask[0], int(utt_id), mode="text")
-            self._refining[tk] = dict(diff=diff, slot=slot, utt_id=int(utt_id), streaming=streaming)      # (the refine stage streams nothing)
+            self._refining[tk] = dict(diff=diff, slot=slot, utt_id=int(utt_id), streaming=streaming, rate=rate)      # (the refine stage streams nothing)
             return tk
-        return self._submit_code(t, diff, slot, int(utt_id), streaming)
+        return self._submit_code(t, diff, slot, int(utt_id), streaming, rate)
 
-    def _submit_code(self, t: str, diff: dict, slot, utt_id: int, streaming=None) -> int:
+    def _submit_code(self, t: str, diff: dict, slot, utt_id: int, streaming=None, rate: Optional[int] = None) -> int:
         """the code utterance of one (refined) text: infer()'s prompt building, then DecodeSession.submit"""
         pipe, gpt, base = self.pipe, self.gpt, self.params
         t = _with_uv_break(t)
@@ -437,10 +455,16 @@ class SynthSession:
         emb = gpt(input_ids, text_mask, spk_emb=pic.spk_emb, spk_emb_ids=pipe.models_dict["tokenizer"].spk_emb_ids)
         sampling = {k: diff[k] for k in PER_UTTERANCE_SAMPLING if k in diff} or None
         if streaming is None:
-            return self.session.submit(emb[0], attention_mask[0], utt_id, limit=diff.get("max_new_token"), sampling=sampling, adapter_slot=slot)
+            tk = self.session.submit(emb[0], attention_mask[0], utt_id, limit=diff.get("max_new_token"), sampling=sampling, adapter_slot=slot)
+            if rate is not None:
+                self._rates[tk] = rate
+            return tk
         tk = self.session.submit(emb[0], attention_mask[0], utt_id, limit=diff.get("max_new_token"), sampling=sampling, adapter_slot=slot, stream=streaming[0],
-                                 stream_batch=streaming[1], stream_hidden=self.use_decoder)
+                                 stream_batch=streaming[1], stream_hidden=self.use_decoder,
+                                 **({} if rate is None else dict(stream_lookback=self.pipe.resampler(rate).lookback)))
         self._streams[tk] = streaming[2]
+        if rate is not None:
+            self._rates[tk], self._emitted[tk] = rate, 0
         return tk
 
     def cancel(self, ticket: int) -> bool:
@@ -465,16 +489,43 @@ class SynthSession:
                               mean_logprob=mean_logprob(e), finished_by_eos=False, refined_text=refined_text)
 
     def _vocode_windows(self, wins):
-        """every due window of the step through ctts_synth_windows: one call (one per sample format when float and int16 tickets are mixed); window -> wav"""
+        """Every due window of the step through ctts_synth_windows: one call (one per sample format when float and int16 tickets are mixed); window ->
+        (wav, start), or None for a window that yields no chunk.  A resampled ticket's window is vocoded as float32 from its v0 and goes, with the others of its
+        rate (and sample format), through one ctts_resample_windows call: outputs [J, J1), J the ticket's outputs so far, J1 = out_settled(s1, final, total).
+        A non-final window that settles no new output frame (J1 == J) yields nothing and is not vocoded."""
         syn = self.pipe.synth if self.use_decoder else self.pipe._codes_synth()
-        hop, wav_of = syn.cfg.hop, {}
+        hop, out, cut = syn.cfg.hop, {}, {}
+        for w in wins:
+            rate = self._rates.get(w.ticket)
+            if rate is None:
+                continue
+            rs, J = self.pipe.resampler(rate), self._emitted[w.ticket]
+            J1 = rs.out_settled(w.s1, w.final, prefix_samples(w.n_tokens))
+            cut[id(w)] = (rs, J, max(J1, J))
+            if w.final:
+                self._emitted.pop(w.ticket)
+            else:
+                self._emitted[w.ticket] = max(J1, J)
+            if J1 <= J:
+                pcm = self._streams.get(w.ticket, False)
+                out[id(w)] = (torch.zeros(0, dtype=torch.int16 if pcm else torch.float32, device=self.pipe.device), J) if w.final else None
         for pcm in (False, True):
-            sel = [w for w in wins if self._streams.get(w.ticket, False) == pcm]
+            sel = [w for w in wins if id(w) not in out and (id(w) in cut and not pcm or id(w) not in cut and self._streams.get(w.ticket, False) == pcm)]
             if not sel:
                 continue
-            wavs = syn.synth_windows([(w.hiddens if self.use_decoder else w.ids) for w in sel], [w.s0 - 2 * w.tok0 * hop for w in sel], [w.s1 - w.s0 for w in sel], pcm)
-            wav_of.update({id(w): v for w, v in zip(sel, wavs)})
-        return wav_of
+            wavs = syn.synth_windows([(w.hiddens if self.use_decoder else w.ids) for w in sel], [w.v0 - 2 * w.tok0 * hop for w in sel], [w.s1 - w.v0 for w in sel], pcm)
+            for w, v in zip(sel, wavs):
+                if id(w) in cut:
+                    cut[id(w)] += (v,)
+                else:
+                    out[id(w)] = (v, w.s0)
+        todo = [w for w in wins if id(w) in cut and id(w) not in out]
+        for rs, pcm in dict.fromkeys((cut[id(w)][0], self._streams.get(w.ticket, False)) for w in todo):
+            sel = [w for w in todo if cut[id(w)][0] is rs and self._streams.get(w.ticket, False) == pcm]
+            res = rs.resample_windows([cut[id(w)][3] for w in sel], [w.v0 for w in sel], [prefix_samples(w.n_tokens) if w.final else None for w in sel],
+                                      [cut[id(w)][1] for w in sel], [cut[id(w)][2] - cut[id(w)][1] for w in sel], pcm)
+            out.update({id(w): (v, cut[id(w)][1]) for w, v in zip(sel, res)})
+        return out
 
     def _deliver(self, results, wins=()):
         tok = self.pipe.models_dict["tokenizer"]
@@ -484,8 +535,10 @@ class SynthSession:
         for w in wins:
             if w.final:
                 final_of[w.ticket] = w
-            else:
-                out.append((self._public.get(w.ticket, w.ticket), SessionChunk(wav=wav_of_win[id(w)], start=w.s0, final=False, n_tokens=w.n_tokens), False))
+            elif wav_of_win[id(w)] is not None:
+                wav, start = wav_of_win[id(w)]
+                out.append((self._public.get(w.ticket, w.ticket),
+                            SessionChunk(wav=wav, start=start, final=False, n_tokens=w.n_tokens, sample_rate=self._rates.get(w.ticket, NATIVE_RATE)), False))
         for r in results:
             if getattr(r, "mode", "code") != "text":
                 code.append(r)
@@ -494,29 +547,33 @@ class SynthSession:
             info = self._refining.pop(r.ticket)
             if r.cancelled or info.get("cancelled"):
                 e = self._empty(True)
-                out.append((r.ticket, self._end_chunk(e, info.get("streaming")), True))
+                out.append((r.ticket, self._end_chunk(e, info.get("streaming"), info.get("rate")), True))
                 continue
             text = _decode_refined(tok, [r.ids])[0]
             try:
-                tk2 = self._submit_code(text, info["diff"], info["slot"], info["utt_id"], info.get("streaming"))
+                tk2 = self._submit_code(text, info["diff"], info["slot"], info["utt_id"], info.get("streaming"), info.get("rate"))
             except _lib.HipBackendError as e:
                 # the code stage was refused (a refined text whose prompt no longer fits max_seq_len, ...): this utterance ends here, delivered like a cancelled
                 # one with the reason on record; the other results of the step are not lost
                 self.failed[r.ticket] = str(e)
-                out.append((r.ticket, self._end_chunk(self._empty(True, refined_text=text), info.get("streaming")), True))
+                out.append((r.ticket, self._end_chunk(self._empty(True, refined_text=text), info.get("streaming"), info.get("rate")), True))
                 continue
             self._public[tk2], self._code_tk[r.ticket], self._refined[r.ticket] = r.ticket, tk2, text
         spoken = [r for r in code if r.ids.shape[0] > 0 and r.ticket not in self._streams]      # (a streaming ticket's audio left as windows)
         wavs = self.pipe._decode_to_wavs([(r.hiddens if self.use_decoder else r.ids) for r in spoken], self.use_decoder) if spoken else []
         wav_of = {r.ticket: w for r, w in zip(spoken, wavs)}
+        for rate in dict.fromkeys(self._rates[r.ticket] for r in spoken if r.ticket in self._rates):      # one resample call per distinct rate of the poll
+            tks = [r.ticket for r in spoken if self._rates.get(r.ticket) == rate]
+            wav_of.update(zip(tks, self.pipe.resampler(rate).resample([wav_of[tk] for tk in tks])))
         for r in code:
             pub = self._public.pop(r.ticket, r.ticket)
             self._code_tk.pop(pub, None)
             refined = self._refined.pop(pub, None)
             w = wav_of.get(r.ticket)
             fw = final_of.get(r.ticket)
+            rate = self._rates.pop(r.ticket, NATIVE_RATE)
             if fw is not None:
-                w = wav_of_win[id(fw)]
+                w, start = wav_of_win[id(fw)]
             if w is None:
                 w = torch.zeros(0, device=self.pipe.device)
             if self.return_details:
@@ -524,16 +581,17 @@ class SynthSession:
                                    finished_by_eos=r.finished_by_eos, refined_text=refined)
             if fw is not None:
                 self._streams.pop(r.ticket, None)
-                w = SessionChunk(wav=w.wav if self.return_details else w, start=fw.s0, final=True, details=w if self.return_details else None, n_tokens=fw.n_tokens)
+                w = SessionChunk(wav=w.wav if self.return_details else w, start=start, final=True, details=w if self.return_details else None, n_tokens=fw.n_tokens,
+                                 sample_rate=rate)
             out.append((pub, w, r.cancelled))
         return out
 
-    def _end_chunk(self, empty, streaming):
+    def _end_chunk(self, empty, streaming, rate=None):
         """how an utterance that ends in its refine stage is delivered: a streaming ticket gets its (empty) final chunk"""
         if streaming is None:
             return empty
         wav = torch.zeros(0, dtype=torch.int16 if streaming[2] else torch.float32, device=self.pipe.device)
-        return SessionChunk(wav=wav, start=0, final=True, details=empty if self.return_details else None)
+        return SessionChunk(wav=wav, start=0, final=True, details=empty if self.return_details else None, sample_rate=rate or NATIVE_RATE)
 
     @torch.no_grad()
     def poll(self):
@@ -971,6 +1029,33 @@ class ChatTTSPlusPipeline:
             wavs.append(vocos.decode(mel)[0])
         return wavs
 
+    def _request_wavs(self, req: _Request, result_list):
+        """_decode_to_wavs for a request, at the rate it asked for: one ctts_resample_windows launch over the vocoded batch"""
+        wavs = self._decode_to_wavs(result_list, req.use_decoder)
+        return wavs if req.sample_rate is None else self.resampler(req.sample_rate).resample(wavs)
+
+    def resampler(self, rate: int):
+        """The hip_models.Resampler 24 kHz -> `rate`, one per rate, created on first use (an unsupported pair is refused there)."""
+        cache = self.__dict__.setdefault("_resamplers", {})
+        if int(rate) not in cache:
+            cache[int(rate)] = hip_models.Resampler(NATIVE_RATE, int(rate), device=self.device)
+        return cache[int(rate)]
+
+    def output_rate(self, sample_rate, who: str) -> Optional[int]:
+        """sample_rate= of infer / open_session / submit: None for None or 24000 (the vocoder's own rate: nothing is resampled, today's path launch for
+        launch), else the rate as an int with its resampler created -- so a pair the device resampler does not serve is refused by the call that names it."""
+        if sample_rate is None:
+            return None
+        if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, np.integer)) or int(sample_rate) < 1:
+            raise _lib.HipBackendError(f"{who}: sample_rate={sample_rate!r} (a positive integer number of Hz)")
+        if int(sample_rate) == NATIVE_RATE:
+            return None
+        try:
+            self.resampler(int(sample_rate))
+        except _lib.HipBackendError as e:
+            raise _lib.HipBackendError(f"{who}: sample_rate={int(sample_rate)}: {e}") from None
+        return int(sample_rate)
+
     def _adapter_slots(self, gpt, paths) -> List[int]:
         """Slot per utterance for `paths` (adapter directory or None each); adapters are loaded into the engine's resident slots on first
         use and evicted least-recently-used first (at most _lib.MAX_ADAPTERS distinct adapters per slice)."""
@@ -1094,6 +1179,11 @@ class ChatTTSPlusPipeline:
                 params_infer_code = dataclasses.replace(params_infer_code, spk_emb=self._speaker_rows(params_infer_code.spk_emb, diffs))
         # return_details / num_candidates (no counterpart in the reference): log-probs written by the sampler, N candidates per utterance ranked by them
         n_cand = check_candidate_request(kwargs.get("num_candidates", 1), utt_ids, stream, noise_mode)
+        # sample_rate (no counterpart in the reference, which delivers 24 kHz): the finished waveforms resampled on the device; the pair is refused here, before any decoding
+        rate = self.output_rate(kwargs.get("sample_rate"), "infer")
+        if rate is not None and stream:
+            raise _lib.HipBackendError(f"infer(stream=True, sample_rate={rate}) is not offered: its windows are slices of different prefix waveforms, so there is no "
+                                       "single waveform to resample (stream from a session: open_session + submit(stream=\"exact\", sample_rate=...))")
         if (n_cand > 1 or kwargs.get("return_details")) and not refine_text_only and stream:
             raise _lib.HipBackendError("return_details=True needs stream=False")
         return _Request(texts=texts, gpt=gpt, slice_size=slice_size, params_refine_text=params_refine_text, params_infer_code=params_infer_code, utt_ids=utt_ids,
@@ -1101,7 +1191,7 @@ class ChatTTSPlusPipeline:
                         noise_seed=kwargs.get("noise_seed"), use_decoder=use_decoder, skip_refine_text=skip_refine_text, refine_text_only=refine_text_only,
                         continuous=kwargs.get("continuous"), n_cand=n_cand, return_details=bool(kwargs.get("return_details")), select=kwargs.get("select"),
                         share_prompt=kwargs.get("share_prompt"), ids_sink=kwargs.get("_ids_sink"), overlap_vocoder=bool(kwargs.get("overlap_vocoder", False)),
-                        vocoder_chunk=kwargs.get("vocoder_chunk", 32))
+                        vocoder_chunk=kwargs.get("vocoder_chunk", 32), sample_rate=rate)
 
     def _infer_sliced(self, req: _Request):
         """pipeline:391-470: slices of slice_size utterances, each waiting for its slowest row; one list of waveforms per slice (stream=True: [B, samples]
@@ -1133,7 +1223,7 @@ class ChatTTSPlusPipeline:
                     if not req.stream:
                         if req.ids_sink is not None:
                             req.ids_sink.extend(zip(utt_ids, result.ids))
-                        yield self._decode_to_wavs(result.hiddens if req.use_decoder else result.ids, req.use_decoder)      # pipeline:435-439
+                        yield self._request_wavs(req, result.hiddens if req.use_decoder else result.ids)      # pipeline:435-439
                         continue
                     # The reference's stream branch vocodes the whole prefix for every chunk and indexes a python list with .shape.  Here every yield is the
                     # [length, b) sample window of that prefix waveform, vocoded from the tokens in its receptive field only (Synth.decode_window), zero padded like pad_sequence pads
@@ -1197,11 +1287,11 @@ class ChatTTSPlusPipeline:
             while ordered and next_i + run in ready:
                 run += 1
             if run and (first or run >= 8 or next_i + run == n_all):
-                yield self._decode_to_wavs([ready.pop(next_i + j) for j in range(run)], req.use_decoder)
+                yield self._request_wavs(req, [ready.pop(next_i + j) for j in range(run)])
                 next_i, first = next_i + run, False
         rest = [i for i in range(next_i, n_all) if i in ready]      # (everything, in throughput mode; nothing unless the run was interrupted, otherwise)
         if rest:
-            yield self._decode_to_wavs([ready[i] for i in rest], req.use_decoder)
+            yield self._request_wavs(req, [ready[i] for i in rest])
 
     def _stream_continuous(self, req: _Request, events, order):
         """stream=True with row re-use (no counterpart in the reference, whose stream branch serves one slice, pipeline:440-463): every yield is a list of
@@ -1252,7 +1342,7 @@ class ChatTTSPlusPipeline:
             with torch.cuda.stream(side):
                 for it in items:
                     it.record_stream(side)                           # (views of the generate call's buffers: keep the allocator off them until the side stream is done)
-                wavs = self._decode_to_wavs(items, req.use_decoder)
+                wavs = self._request_wavs(req, items)
                 if t_first is None:
                     t_first = torch.cuda.Event(enable_timing=True)
                     t_first.record(side)
@@ -1358,7 +1448,7 @@ class ChatTTSPlusPipeline:
         win = [cands[j * n_cand + k] for j, k in enumerate(chosen)]
         if req.ids_sink is not None:
             req.ids_sink.extend((req.utt_ids[u], w.ids) for u, w in zip(us, win))
-        wavs = self._decode_to_wavs([w.hiddens if use_decoder else w.ids for w in win], use_decoder)      # pipeline:435-439; winners only
+        wavs = self._request_wavs(req, [w.hiddens if use_decoder else w.ids for w in win])      # pipeline:435-439; winners only
         if not req.return_details:
             return wavs
         det = InferDetails(wavs=wavs, ids=[w.ids for w in win], logprobs=[w.logprobs for w in win], sampled_logprobs=[w.sampled_logprobs for w in win],
@@ -1416,12 +1506,14 @@ class ChatTTSPlusPipeline:
 
     # -- serving session (no counterpart in the reference) ------------------------------------------------------------------------
     def open_session(self, params_infer_code: Optional[InferCodeParams] = None, use_decoder: bool = True, lora_path: Optional[str] = None, rows: Optional[int] = None,
-                     seed: Optional[int] = None, return_details: bool = False, refine: Optional[RefineTextParams] = None, **out_of_scope) -> SynthSession:
+                     seed: Optional[int] = None, return_details: bool = False, refine: Optional[RefineTextParams] = None, sample_rate: Optional[int] = None,
+                     **out_of_scope) -> SynthSession:
         """A SynthSession: submit(text) / cancel(ticket) / poll() / drain() / close() while the engine keeps decoding -- the decode batch grows when texts arrive
         and shrinks when they end.  `params_infer_code` are the session's values (speaker included; a random one is sampled if it names none), `lora_path` one
         merged adapter for the whole session (an utterance may name its own at submit), `rows` bounds the decode batch, `seed` keys the device noise.
         `refine` (a RefineTextParams; max_new_token <= the code parameters', repetition_penalty 1): submit() refines every text first, inside the session -- as
-        a text row beside the code rows (SynthSession); SessionDetails.refined_text carries the result.
+        a text row beside the code rows (SynthSession); SessionDetails.refined_text carries the result.  `sample_rate`: the session's output rate in Hz (None or
+        24000: the vocoder's own); a submit may name its own.
         Not offered inside a session (refused): num_candidates / shared prompt passes, caller-supplied noise, session-wide streaming windows
         (stream=True here: streaming is asked per utterance, submit(stream="exact" | "eager")), infer_sharded, and infer()'s call-level names of the refine-text
         pass (refine_text_only, params_refine_text: use refine=)."""
@@ -1431,7 +1523,7 @@ class ChatTTSPlusPipeline:
         params = dataclasses.replace(params_infer_code if params_infer_code is not None else InferCodeParams())
         if params.spk_emb is None and params.spk_smp is None:
             params.spk_emb = self.sample_random_speaker()
-        return SynthSession(self, self._gpt_for_lora(lora_path), params, use_decoder, rows, seed, return_details, refine=refine)
+        return SynthSession(self, self._gpt_for_lora(lora_path), params, use_decoder, rows, seed, return_details, refine=refine, sample_rate=sample_rate)
 
     # -- multi-GPU: utterance sharding (BASELINE configs[3]: batch 256 over 8 GPUs) --------------------------------
     @torch.no_grad()
@@ -1454,6 +1546,10 @@ class ChatTTSPlusPipeline:
             raise _lib.HipBackendError("infer_sharded serves one generation per utterance and returns waveforms: num_candidates > 1 and return_details are "
                                        "refused (rank the candidates with infer() on one rank)")
         kwargs.pop("num_candidates", None); kwargs.pop("return_details", None)
+        if kwargs.get("sample_rate") is not None and int(kwargs["sample_rate"]) != NATIVE_RATE:
+            raise _lib.HipBackendError(f"infer_sharded(sample_rate={kwargs['sample_rate']}) is not offered: the generated lengths every rank exchanges are read off "
+                                       "its 24 kHz waveforms; resample a rank's waveforms with pipe.resampler(rate).resample(wavs)")
+        kwargs.pop("sample_rate", None)
         if not isinstance(texts, list):
             texts = [texts]
         params = dataclasses.replace(params_infer_code)

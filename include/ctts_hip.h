@@ -645,6 +645,41 @@ int ctts_dvae_encode(ctts_enc* h, const float* wav, int n_samples, int32_t* ids,
 int ctts_dvae_encode_batch(ctts_enc* h, const float* const* wav_ptrs, const int32_t* n_samples, int B, int32_t* const* ids_ptrs,
                            float* const* mel_ptrs, float* const* feat_ptrs, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Output sample rate: torchaudio.functional.resample (sinc_interp_hann; the reference uses it on the input side, pipeline:495) as a device kernel for
+ * the waveforms and streaming windows that LEAVE the engine.  A rate pair reduced by its gcd is orig : new_; width and the float32 table
+ * kernels[new_][K], K = 2 width + orig, are audio.resample_kernels' (Python builds the table: libm's sin / cos are not torch's).  Output sample
+ * j = i new_ + p of an n-sample waveform x is sum_k kernels[p][k] x[i orig - width + k], x = 0 outside [0, n); there are ceil(new_ n / orig) of them.
+ *
+ * Host-only geometry (no GPU), the twins of hip_models.resampler's functions:
+ *   ctts_resample_out_total   ceil(new_ n / orig)
+ *   ctts_resample_settled     output samples no later input can change once S input samples are settled: new_ max(0, floor((S - width) / orig)), every
+ *                             output frame whose last tap lies below S; finished != 0: ctts_resample_out_total(n)
+ *   ctts_resample_in_range    out2 = the inputs outputs [j0, j1) can read, before clipping to [0, n):
+ *                             {(j0 / new_) orig - width, ((j1 - 1) / new_) orig + orig + width}; {0, 0} for an empty range
+ *
+ * ctts_resampler_create uploads the table once; a pair with K > CTTS_RESAMPLE_MAX_TAPS or a table above CTTS_RESAMPLE_MAX_TABLE_BYTES is refused.
+ * ctts_resample_windows: ONE launch computes outputs [j0[u], j0[u] + count[u]) of B windows (1 <= B <= CTTS_RESAMPLE_MAX_WINDOWS, ragged, count 0
+ * allowed) and stores them at element out_off[u] of `out`: fmt 0 = float32, fmt 1 = int16 PCM, rintf(clamp(y, -1, 1) * 32767).  src[u] is a device buffer
+ * with input samples [src0[u], src0[u] + src_n[u]) of window u's waveform, total[u] the waveform's length or -1 while it is not known (an utterance still
+ * decoding); the whole waveform is the window src0 = 0, total = src_n, j0 = 0, count = out_total.  All arrays are HOST arrays of length B, uploaded as one
+ * pinned table per call.  Every argument is checked before the launch: in_range(j0, j0 + count) clipped to [0, total) must lie inside
+ * [src0, src0 + src_n) (total = -1: its right edge must lie inside the buffer), else the call fails naming the window and nothing is written.
+ * Each output is one ascending-k fmaf chain in float32 over all K taps, a tap outside [0, total) entering as an exact zero: its bits do not depend on
+ * j0, src0, the tile it falls in or B, and equal the whole-waveform call's.  Never synchronises the stream (but for the reuse of a pinned slot). */
+typedef struct ctts_resampler ctts_resampler;
+#define CTTS_RESAMPLE_MAX_TAPS 1024
+#define CTTS_RESAMPLE_MAX_TABLE_BYTES (4u << 20)
+#define CTTS_RESAMPLE_MAX_WINDOWS 1024
+int64_t ctts_resample_out_total(int orig, int new_, int64_t n);
+int64_t ctts_resample_settled(int orig, int new_, int width, int64_t S, int finished, int64_t n);
+int ctts_resample_in_range(int orig, int new_, int width, int64_t j0, int64_t j1, int64_t* out2);
+int ctts_resampler_create(int orig, int new_, int width, const float* kernels_host, ctts_resampler** out);
+void ctts_resampler_destroy(ctts_resampler* h);
+int ctts_resampler_tile_frames(const ctts_resampler* h);      /* output frames per workgroup tile (tiles are counted from frame 0 of the waveform) */
+int ctts_resample_windows(ctts_resampler* h, const float* const* src, const int64_t* src0, const int32_t* src_n, const int64_t* total,
+                          const int64_t* j0, const int32_t* count, int B, void* out, const int64_t* out_off, int fmt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
