@@ -10,7 +10,10 @@
 //     weights per layer); their 8 compute waves keep the slice in registers and request each array for the NEXT use one wait ahead, paced (SCHED 3: one 1 KB
 //     fragment per wave every ~0.2 us while the edge waves gather), so the weight stream runs AHEAD of the layer's dependency edges
 //     (MI355X_MICROARCH.md price list, row prefetch-credit) and every product is VALU work on registers;
-//   * 64 attention workgroups own one (row, head, key share) each and pull its cached K / V rows into registers before the query exists;
+//   * 64 attention workgroups own one (row, head, key share) each and pull its cached K / V rows into registers before the query exists.  Their barriers, every
+//     wave of the workgroup alike (waves 9..11 only keep them): S0 once, then per layer B1 (wave 8 has q, k_new, v_new in LDS) -> B2 (the compute waves' partial
+//     outputs, maxima and sums are in LDS; wave 8 combines and publishes) -> B3 (in every layer but the last: wave 8 has issued the layer's last hand-off; the
+//     compute waves request the next layer's cached rows behind it, "attention trim" below);
 //   * the activations travel between workgroups as 8-byte {tag, value} granules (one sc1 store each, cdna_hip_programming.md Guideline 16 R2):
 //     the data is the flag, a consumer wave re-reads its granules until every tag equals (launch counter, layer) -- no fences, no counters,
 //     placement-independent.  Four "edge" waves per workgroup (two until round 5) do all gathering, epilogues and publishing, so the compute waves never poll
@@ -274,6 +277,16 @@ template <int CTRL, int C> __device__ inline void pl_rs_step(float* v, bool f) {
 #endif
 #ifndef PL_A16_DPP
 #define PL_A16_DPP 1
+#endif
+// ---- attention trim: the same for the attention workgroups' path "q gathered -> granule published" (switches as above; outputs bit-identical).
+//   PL_KV_AFTER_PUBLISH: the compute waves request the next layer's cached K / V rows behind a third barrier (B3) that wave 8 joins right behind its last hand-off
+//                        of the layer (the g_att store; a split s > 0: its g_part stores; split 0 first finishes its gather of the partials), not at B2: the ~160 KB
+//                        burst no longer sits in the CU's memory queue in front of the publish store and the partials' polls.
+// (Two more links were built, measured and removed, DESIGN section 5: wave 8 forming the rescale factors from early-stored wave maxima beside the exp / PV pass -- an LDS
+//  counter, a bounded wait and a second code path around B2 for no gain alone on any command line --, and the weights' cross-lane sum in front of the PV FMAs -- the
+//  scheduler keeps the 20-instruction sum in one piece in front of the four packed FMAs of an iteration, and its register takes the fp16 6- and 7-row kernels to 129.)
+#ifndef PL_KV_AFTER_PUBLISH
+#define PL_KV_AFTER_PUBLISH 1
 #endif
 #define PL_DPP_ROW_SHL(n_) (0x100 + (n_))    // lane i of a 16-lane row reads lane i + n; lanes past the row read 0 (bound_ctrl)
 __device__ inline float pl_row_shl1(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), PL_DPP_ROW_SHL(1), 0xF, 0xF, true)); }
@@ -1149,6 +1162,8 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
     float* const mm = mo + 512;                               // [8] the waves' maxima
     float* const ml = mm + 8;                                 // [8] the waves' sums
     const size_t kv_per = a.kv_per;
+    // attention trim (above).  B3 exists in every layer but the launch's last, for every wave of the workgroup alike
+    constexpr bool KVP = PL_KV_AFTER_PUBLISH != 0;
     if (wave < 8) {
         // Round 5 layout: the scores come from K rows held 8 dims per lane (key group = lane / 8, a 3-step DPP sum per key), the output from V rows held ONE DIM PER
         // LANE (8 keys x PRE registers): a key's weight reaches all lanes through v_readlane and the wave's output is one register per lane -- no cross-lane sums of
@@ -1316,7 +1331,10 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
             if (lane == 0) { mm[wave] = mrun; ml[wave] = lw; }
             PL_AMARK(6);
             __syncthreads();                                  // B2
-            if (l + 1 < NL) { PL_DMA_KV(l + 1); PL_LOAD_KV(l + 1); }      // the next layer's cached rows: a whole layer ahead of its query (B2: every LDS read of this layer is done)
+            if (l + 1 < NL) {
+                if constexpr (KVP) __syncthreads();           // B3: wave 8 has issued the layer's last hand-off
+                PL_DMA_KV(l + 1); PL_LOAD_KV(l + 1);          // the next layer's cached rows: a whole layer ahead of its query (B2: every LDS read of this layer is done)
+            }
             __builtin_amdgcn_sched_barrier(0);
         }
     } else if (wave == 8 || (PAIR && wave == 9)) {
@@ -1392,6 +1410,7 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                 }
                 store_granule(a.g_att + (size_t)r * PL_H + hh * CTTS_HEAD_DIM + lane, tag, O / L);
             }
+            if constexpr (KVP) { if (l + 1 < NL) __syncthreads(); }      // B3: the layer's last hand-off is issued -- the compute waves request the next layer's cached rows
             if (l + 1 == NL && wave == 8) PL_MARK(2);
         }
         if (a.ts != nullptr && lane == 0 && wave == 8) {
@@ -1403,6 +1422,7 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
         for (int l = 0; l < NL; ++l) {
             __syncthreads();                                  // B1
             __syncthreads();                                  // B2
+            if constexpr (KVP) { if (l + 1 < NL) __syncthreads(); }      // B3
         }
     }
 }
