@@ -57,6 +57,21 @@ struct LayerW {
     void *qkv_sp = nullptr, *o_sp = nullptr, *gu_sp = nullptr, *d_sp = nullptr;
 };
 
+// The host's record of one decode row -- a new per-row property joins this struct: KV lane; context length (an upper bound: advance_rows) and its cap, prompt + token limit;
+// 0 code / 1 text (RowState.mode); adapter slot or -1 as the decode launches carry it (row_slot_bytes; the prompt pass reads the lane table lora_slot_host)
+struct HostRow { int seq, ctx, cap, mode, slot; };
+// What the callers asked for ahead of a call.  RowRequests persist ("the following begin calls", until set again); a NextCall is for the next ctts_gpt_begin / ctts_gpt_admit alone
+struct RowRequests {
+    std::vector<RowSampling> knobs;              // ctts_gpt_set_row_sampling, per sequence (empty = the call's values); checked by begin, against that call's max_new_token
+    std::vector<int> modes;                      // ctts_gpt_set_row_modes, per sequence
+    std::vector<int> slots;                      // ctts_gpt_set_row_adapters, per KV lane [CTTS_MAX_B]: every begin() / score() starts from it again, whatever the previous call did to the live tables
+};
+struct NextCall {
+    std::vector<int> share; int share_P = 0;     // ctts_gpt_share_prompts: prompt of every sequence of the call (empty = none) and the number of prompts
+    std::vector<std::pair<int, RowSampling>> knobs;   // ctts_gpt_admit_sampling: (row, knobs) of the utterances the admission seats
+    std::vector<std::pair<int, int>> modes;      // ctts_gpt_admit_modes: (row, mode) of the same
+};
+
 struct ctts_gpt {
     ctts_gpt_cfg cfg;
     int H, I, NH, L, V, NVQ;
@@ -87,14 +102,7 @@ struct ctts_gpt {
     std::vector<LayerW> lw;
     void* whead = nullptr;
     void* whead_text = nullptr;                  // refine-text head (21178 x H), packed like whead; optional
-    int text_mode = 0;                           // current generate() call: infer_text=True
-    // text rows beside code rows in one decode batch (ctts_gpt_enable_text_rows; RowState.mode): the mode is a property of the ROW, the call stays a code-mode call
-    int text_rows_on = 0;                        //   the current generate state has its text block (begin switches it off again)
-    int text_live = 0;                           //   rows of the batch whose mode is 1, finished ones included ("text_rows_live"): > 0 = the step is MIXED -- two more launches
-                                                 //   (text head, text sampler); decided from the host mirror below, as lora_mlp is
-    std::vector<int> row_mode;                   //   host mirror: mode of every current decode row (moves with row_seq)
-    std::vector<int> modes_req;                  //   what ctts_gpt_set_row_modes asked for, per sequence ("the following begin calls")
-    std::vector<std::pair<int, int>> modes_admit;   // ctts_gpt_admit_modes: (row, mode) of the utterances the next ctts_gpt_admit seats
+    // text rows beside code rows in one decode batch (ctts_gpt_enable_text_rows; RowState.mode): the mode is a property of the ROW (HostRow.mode), the call stays a code-mode call
     SamplerCfgDev sc_text = {};                  //   the text rows' sampling parameters (the refine pass's ctts_sampler_cfg)
     SamplerDyn* dyn_text = nullptr;              //   device: the text block -- sc_text, the text ids array, and the code block's finish / end_idx / seed
     float* logits_text = nullptr;                //   [max_batch][vocab_text_head]; both allocated by the first ctts_gpt_enable_text_rows
@@ -211,15 +219,11 @@ struct ctts_gpt {
     float* lora_Af = nullptr;                    //   A of q | k | v with the input RMSNorm weight folded into the columns [layer][slot][3][16][768]: the persistent launch's waves read it (persist_layer.hip LORA)
     std::vector<float> ln1_host;                 //   host copy of ln1 (fetched at the first ctts_gpt_set_adapter)
     int* lora_slot_of_seq = nullptr;
-    signed char lora_row_slots[CTTS_MAX_B];      //   the same per decode ROW (rows move when finished rows are compacted away): travels in the kernel arguments of the folded launches
     std::vector<signed char> lora_rank;          //   [layer][slot][target] rank as loaded (0 = empty)
-    std::vector<int> lora_slot_host;             //   host copy of lora_slot_of_seq
-    std::vector<int> lora_req_host;              //   what ctts_gpt_set_row_adapters asked for ("the following generate() calls"): every begin() starts from it again, whatever
-                                                 //   compaction (lora_refresh) and ctts_gpt_admit_adapters did to the live tables of the previous call
+    std::vector<int> lora_slot_host;             //   host copy of lora_slot_of_seq, per KV lane (the decode ROWS' slots: HostRow.slot)
     float *lora_dqkv = nullptr, *lora_do = nullptr;
     unsigned long long* lora_g = nullptr;        //   decode steps: the same terms as tagged granules from worker workgroups inside the QKV / o_proj launches (lora_worker.h)
     int lora_fold = 1;                           //   "lora_fold" option: 0 = the two extra launches per layer at decode too
-    int lora_rows = 0;                           // 1: the current / next generate() calls carry per-sequence adapters
     // ... on the MLP projections (gate_proj / up_proj / down_proj): tables of their own, allocated when the first such target is loaded (737 KB per layer and slot;
     // engines that serve q/k/v/o adapters keep their footprint): A_gu [layer][slot][gate | up][16][768], B_gu [layer][slot][gate | up][16][3072],
     // A_d [layer][slot][16][3072], B_d [layer][slot][16][768] (rank-major, zero padded to r = 16), scale [layer][slot][4] = gate, up, down, -
@@ -227,8 +231,6 @@ struct ctts_gpt {
     float* lora_dgu = nullptr;                   //   gate / up terms of the rows being processed [rows][gate | up][3072] (the down term shares lora_do: o_proj has consumed it by then)
     std::vector<signed char> lora_mrank;         //   [layer][slot][gate, up, down] rank as loaded (0 = empty; sized last: non-empty = the tables above are all there)
     std::vector<float> ln2_host;                 //   post_attention_layernorm weights [layer][768], kept from finalize (61 KB): engines without MLP adapters allocate what they always did
-    int lora_mlp = 0;                            // 1: a LIVE row's slot holds an MLP target (recomputed wherever lora_rows is): two more launches per layer, and decode steps take the
-                                                 //    launch chain at every row count (the persistent launch carries q/k/v/o terms only)
     int pass_rows = PASS_ROWS_MAX;               // prompt rows per pass of this engine (env CTTS_PASS_ROWS, read once at finalize, lowers it: the
                                                  // one capacity knob of the product library; the multi-pass tests use it)
     void* xh = nullptr;                          // fp16 decode, > split_rows rows: residual stream as packed fp16 B operand (EPI_RESID_XH -> PRO_XH)
@@ -237,31 +239,18 @@ struct ctts_gpt {
     int* sat = nullptr;                          // fp16 engines: saturated / NaN fp16 stores since begin (common.h sat_half; ctts_gpt_saturations)
     int* hist_ring = nullptr;                    // sampler: repetition-penalty window ring [max_B][4][16] (sampler.hip)
     RowState* finend = nullptr;                  // sampler: per-row state [max_B] (common.h): mirror of {finish, end_idx}, noise key, token limit
-    std::vector<RowState> rows_host;             //   its initial image for the current generate() (uploaded by begin)
+    std::vector<RowState> finend_host;           //   its initial image for the current generate() (uploaded by begin)
     RowSampling* knobs = nullptr;                // sampler: per-row sampling knobs [max_B] (common.h), in the same allocation right behind finend (fixed address: the
                                                  //   captured graphs hold no per-call state)
     RowSampling* cknobs = nullptr;               //   compaction gather target / staging of the knobs an admission seats
     std::vector<RowSampling> knobs_host;         //   begin's image of rows 0..B-1
-    std::vector<RowSampling> knobs_req;          //   what ctts_gpt_set_row_sampling asked for, per sequence ("the following begin calls"; empty = the call's values)
-    std::vector<std::pair<int, RowSampling>> knobs_admit;   //   ctts_gpt_admit_sampling: (row, knobs) of the utterances the next ctts_gpt_admit seats
     // finished-row compaction (ctts_gpt_compact): gather targets + the kept row indices
     float *cx = nullptr, *crope = nullptr; RowMeta* cmeta = nullptr; int* cring = nullptr; RowState* cfin = nullptr; int* keep_dev = nullptr;
     std::vector<int> keep_host;
-    // host mirrors of the decode rows: KV lane, context length (upper bound) and its cap (prompt + limit); see advance_rows / ctts_gpt_admit
-    std::vector<int> row_seq, row_ctx, row_cap;
     std::vector<RowState> fresh_host;
     std::vector<int> seq_host;
-    int pre_T = 0;                               // tokens per sequence of the prompt rows being passed (begin: T; admit: T - 1)
-    long pp_rows = 0; int pp_T = 0;              // the last ctts_gpt_prefill / ctts_gpt_score call: its prompt rows and pre_T (debug_read "prompt_plan", "meta_pre", "x_pre"); 0 rows = none since begin
-    int B0 = 0;                                  // sequences the current generate() started with (h->B = rows still in the decode batch)
-    bool admitted = false;                       // ctts_gpt_admit handed a row of this generate() to another utterance: x_last / meta_dec0 no longer describe the rows
-    // per generate()
-    int B = 0, T = 0;
-    SamplerCfgDev sc;
-    ctts_gen_io io = {};
     hipStream_t cap_stream = nullptr;
     SamplerDyn* dyn = nullptr;                   // device copy of the per-call sampler state (rewritten by begin; read by the heads + sampler nodes)
-    bool sampled = false;                        // a sample phase has been enqueued since begin (ctts_gpt_set_logprob_out is refused from then on)
     // Captured decode graphs, keyed by what shapes the launches (batch, mode, KV binding): caller buffers and sampling
     // parameters are read from `dyn` at run time, so consecutive generate() calls replay the same executable graph.
     struct GraphEntry { hipGraph_t graph; hipGraphExec_t exec; };
@@ -272,20 +261,31 @@ struct ctts_gpt {
     int graph_steps_persist = 16;                // ... and per graph of the persistent paths (2 nodes per step: 32 nodes): the replay gap is 8.1 us whatever the graph
                                                  // holds (profiles/r05_trace_gaps_b1.json), 2.0 us per step at 4 steps, 0.5 us at 16
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct DecodeSeg { int n; DecodePath path; };
-    std::vector<DecodeSeg> segs;                 // plan_decode: the steps of one decode call as runs of equal decode paths
     // ctts_gpt_score: the gathered scored rows [SCORE_ROWS][H], their head logits [SCORE_ROWS][4 * V] and output entries [SCORE_ROWS] --
     // allocated by the first score call (engines that never score keep their footprint)
     float *score_x = nullptr, *score_logits = nullptr; int* score_oidx = nullptr;
     size_t score_bytes = 0;
     // shared prompt passes (ctts_gpt_share_prompts; kv_share.hip)
-    std::vector<int> share_req;                  //   the pending request: prompt of every sequence of the NEXT begin / admit (empty = none); consumed by that call
-    int share_req_P = 0;                         //   ... and its number of prompts
-    std::vector<int> share_tab;                  //   host image of share_dev for the call that consumed it (kernels.h SH_*)
+    std::vector<int> share_tab;                  //   host image of share_dev for the call that consumed the request (kernels.h SH_*)
     int* share_dev = nullptr;                    //   device table [SH_INTS], allocated by the first ctts_gpt_share_prompts
-    int share_P = 0;                             //   prompts of the current ctts_gpt_begin (0 = every sequence runs its own prompt); read by ctts_gpt_prefill
-    int share_groups = 0;                        //   prompts with at least one follower
     std::vector<void*> owned;                    // every device buffer of the engine (dev_alloc)
+    RowRequests req;                             // what the callers asked for: "the following begin calls"
+    NextCall next;                               //   ... and the next ctts_gpt_begin / ctts_gpt_admit alone
+    // ---- the current generate state: what ctts_gpt_begin starts and ctts_gpt_score ends (end_generate_state) ----
+    int B = 0, T = 0, B0 = 0;                    // rows in the decode batch (0 = no generate state), prompt tokens per sequence and sequences at begin
+    std::vector<HostRow> rows;                   // one record per decode row: size == B whenever a generate state exists
+    SamplerCfgDev sc; ctts_gen_io io = {};       // the call's sampling parameters and buffers
+    bool admitted = false;                       // ctts_gpt_admit / ctts_gpt_grow changed the rows of this generate(): x_last / meta_dec0 no longer describe them
+    bool sampled = false;                        // a sample phase has been enqueued since begin (ctts_gpt_set_logprob_out is refused from then on)
+    struct DecodeSeg { int n; DecodePath path; };
+    std::vector<DecodeSeg> segs;                 // plan_decode: the steps of one decode call as runs of equal decode paths
+    int share_P = 0, share_groups = 0;           // prompts of the current ctts_gpt_begin (0 = every sequence runs its own prompt; read by ctts_gpt_prefill), those with at least one follower
+    long pp_rows = 0; int pp_T = 0;              // the last ctts_gpt_prefill / ctts_gpt_score call: its prompt rows and their tokens per sequence (debug_read "prompt_plan", "meta_pre", "x_pre"); 0 rows = none since begin
+    int text_mode = 0, text_rows_on = 0;         // the call's own infer_text; the state has its text block (ctts_gpt_enable_text_rows; begin switches it off again)
+    // ... and what refresh_rows derives from `rows`: which launches a step takes is decided from these
+    int text_live = 0;                           // rows whose mode is 1, finished ones included ("text_rows_live"): > 0 = the step is MIXED -- two more launches (text head, text sampler)
+    int lora_rows = 0;                           // 1: a row carries an adapter slot; before rows exist (ctts_gpt_set_row_adapters, ctts_gpt_score) the sequences of the request do
+    int lora_mlp = 0;                            // 1: such a slot holds an MLP target ("lora_mlp_live"): two more launches per layer, decode on the launch chain at every row count
 };
 #define SCORE_ROWS 2048       // scored rows per heads launch: bounds the logits scratch (2048 x 2504 fp32 = 20.5 MB)
 
@@ -643,6 +643,24 @@ static bool lora_slot_has_mlp(const ctts_gpt* h, int slot) {
         for (int t = 0; t < 3; ++t) if (h->lora_mrank[((size_t)l * CTTS_MAX_ADAPTERS + slot) * 3 + t]) return true;
     return false;
 }
+// lora_rows / lora_mlp of n adapter slots; allocates the MLP terms where lora_mlp rises
+template <class SlotOf>
+static int lora_summary(ctts_gpt* h, int n, SlotOf slot_of) {
+    h->lora_rows = 0; h->lora_mlp = 0;
+    for (int i = 0; i < n; ++i) { h->lora_rows |= slot_of(i) >= 0; h->lora_mlp |= lora_slot_has_mlp(h, slot_of(i)); }
+    return lora_ensure_mlp_terms(h);
+}
+// The summaries of `rows` (text_live, lora_rows, lora_mlp): called wherever the row set or a row's mode / slot changes -- begin, admit, grow, compact, admit_adapters,
+// seat_row_adapters, set_row_adapters, the end of the state
+static int refresh_rows(ctts_gpt* h) {
+    h->text_live = 0;
+    for (const HostRow& r : h->rows) h->text_live += r.mode;
+    return lora_summary(h, (int)h->rows.size(), [h](int r) { return h->rows[r].slot; });
+}
+// The rows' adapter slots as the decode launches and the graph key carry them: one byte per row, -1 (0xFF) past the batch
+static void row_slot_bytes(const ctts_gpt* h, signed char* out, int n) {
+    for (int r = 0; r < n; ++r) out[r] = r < (int)h->rows.size() ? (signed char)h->rows[r].slot : (signed char)-1;
+}
 // gate_proj / up_proj / down_proj (t = 4 / 5 / 6) of one layer into the slot's MLP tables
 static int lora_set_mlp_target(ctts_gpt* h, int slot, int layer, int t, const float* A, const float* B, int r, float scale) {
     if (h->H != 768 || h->I != 3072) { ctts_set_error("set_adapter: MLP targets need hidden 768 / intermediate 3072 (engine: %d / %d)", h->H, h->I); return 1; }
@@ -717,12 +735,11 @@ extern "C" int ctts_gpt_clear_adapter(ctts_gpt* h, int slot) {
 extern "C" int ctts_gpt_set_row_adapters(ctts_gpt* h, const int32_t* slots, int B) {
     if (!h || !h->finalized) { ctts_set_error("set_row_adapters: handle not finalized"); return 1; }
     auto clear_rows = [h]() -> int {              // no row carries an adapter: also forget what an earlier request's rows carried (ctts_gpt_admit_adapters builds on these)
-        h->lora_rows = 0; h->lora_mlp = 0;
-        h->lora_req_host.clear();
+        h->req.slots.clear();
         if (!h->lora_slot_host.empty()) h->lora_slot_host.assign(CTTS_MAX_B, -1);
-        for (int b = 0; b < CTTS_MAX_B; ++b) h->lora_row_slots[b] = -1;
+        for (HostRow& r : h->rows) r.slot = -1;
         if (h->lora_slot_of_seq) CTTS_HIP_CHECK(hipMemset(h->lora_slot_of_seq, 0xFF, CTTS_MAX_B * 4));
-        return 0;
+        return refresh_rows(h);
     };
     if (!slots || B <= 0) return clear_rows();
     if (B > CTTS_MAX_B) { ctts_set_error("set_row_adapters: B=%d > %d", B, CTTS_MAX_B); return 1; }
@@ -736,13 +753,9 @@ extern "C" int ctts_gpt_set_row_adapters(ctts_gpt* h, const int32_t* slots, int 
     std::vector<int> tab(CTTS_MAX_B, -1);
     for (int b = 0; b < B; ++b) tab[b] = slots[b] < 0 ? -1 : slots[b];
     CTTS_HIP_CHECK(hipMemcpy(h->lora_slot_of_seq, tab.data(), CTTS_MAX_B * 4, hipMemcpyHostToDevice));
-    h->lora_slot_host = tab;
-    h->lora_req_host = tab;
-    for (int b = 0; b < CTTS_MAX_B; ++b) h->lora_row_slots[b] = (signed char)tab[b];      // rows == sequences until a compaction
-    h->lora_rows = 1;
-    h->lora_mlp = 0;
-    for (int b = 0; b < B; ++b) if (lora_slot_has_mlp(h, tab[b])) h->lora_mlp = 1;
-    return lora_ensure_mlp_terms(h);
+    h->lora_slot_host = h->req.slots = tab;
+    for (HostRow& r : h->rows) r.slot = tab[r.seq];      // (a row's slot is its lane's, always: compaction moves the row, the lane table stays)
+    return lora_summary(h, B, [&tab](int b) { return tab[b]; });      // the sequences of the request: the next begin seats them (seat_row_adapters)
 }
 
 // ---- per-utterance sampling knobs (RowSampling, common.h) ----------------------------------------
@@ -789,24 +802,35 @@ static int check_knobs(const ctts_row_sampling& p, int max_new, const char* who,
 }
 extern "C" int ctts_gpt_set_row_sampling(ctts_gpt* h, const ctts_row_sampling* per_seq, int B) {
     if (!h) { ctts_set_error("set_row_sampling: null handle"); return 1; }
-    if (!per_seq || B <= 0) { h->knobs_req.clear(); return 0; }
+    if (!per_seq || B <= 0) { h->req.knobs.clear(); return 0; }
     if (B > CTTS_MAX_B) { ctts_set_error("set_row_sampling: B=%d > %d", B, CTTS_MAX_B); return 1; }
-    h->knobs_req.assign(B, RowSampling{});
-    for (int b = 0; b < B; ++b) h->knobs_req[b] = knobs_of_abi(per_seq[b]);      // checked by begin, against that call's max_new_token
+    h->req.knobs.assign(B, RowSampling{});
+    for (int b = 0; b < B; ++b) h->req.knobs[b] = knobs_of_abi(per_seq[b]);      // checked by begin, against that call's max_new_token
+    return 0;
+}
+// The `rows` argument of admit / cancel / admit_sampling / admit_modes / admit_adapters: every entry a row of the batch and, with `distinct`, none named twice; entry(i)
+// checks what else the caller holds for entry i, right after its row (the first fault of the first faulty entry is the one reported)
+static int rows_only(int) { return 0; }
+template <class Entry = int (*)(int)>
+static int check_rows(const ctts_gpt* h, const char* who, int n, const int32_t* rows, bool distinct, Entry entry = rows_only) {
+    bool named[CTTS_MAX_B] = {};
+    for (int i = 0; i < n; ++i) {
+        if (rows[i] < 0 || rows[i] >= h->B) { ctts_set_error("%s: row %d of %d", who, rows[i], h->B); return 1; }
+        if (distinct && named[rows[i]]) { ctts_set_error("%s: row %d named twice", who, rows[i]); return 1; }
+        named[rows[i]] = true;
+        if (entry(i)) return 1;
+    }
     return 0;
 }
 extern "C" int ctts_gpt_admit_sampling(ctts_gpt* h, int n, const int32_t* rows, const ctts_row_sampling* p, void* stream) {
     (void)stream;        // host-side request: the next ctts_gpt_admit uploads the entries
     if (!h || h->B == 0 || !rows || !p || n < 0) { ctts_set_error("admit_sampling: call begin first / null argument"); return 1; }
     if (h->text_mode) { ctts_set_error("admit_sampling: per-utterance sampling parameters are code mode only (the refine-text pass keeps the call's values)"); return 1; }
-    for (int i = 0; i < n; ++i) {
-        if (rows[i] < 0 || rows[i] >= h->B) { ctts_set_error("admit_sampling: row %d of %d", rows[i], h->B); return 1; }
-        if (check_knobs(p[i], h->sc.max_new, "admit_sampling", i)) return 1;
-    }
+    if (check_rows(h, "admit_sampling", n, rows, false, [&](int i) { return check_knobs(p[i], h->sc.max_new, "admit_sampling", i); })) return 1;
     for (int i = 0; i < n; ++i) {
         bool found = false;
-        for (auto& e : h->knobs_admit) if (e.first == rows[i]) { e.second = knobs_of_abi(p[i]); found = true; }
-        if (!found) h->knobs_admit.emplace_back(rows[i], knobs_of_abi(p[i]));
+        for (auto& e : h->next.knobs) if (e.first == rows[i]) { e.second = knobs_of_abi(p[i]); found = true; }
+        if (!found) h->next.knobs.emplace_back(rows[i], knobs_of_abi(p[i]));
     }
     return 0;
 }
@@ -1237,8 +1261,9 @@ static LayerPlan plan_layers(const ctts_gpt* h, int R, bool decode, DecodePath p
     return p;
 }
 
-// 20 decoder layers on R rows of residual stream x (llama.py:719-749 per layer); st != nullptr: a decode step on `path`, else a prompt pass ({1, 0})
-static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* rope_rows, int R, DecodePath path, const DevState* st, hipStream_t s, StreamForm* form = nullptr) {
+// 20 decoder layers on R rows of residual stream x (llama.py:719-749 per layer); st != nullptr: a decode step on `path`, else a prompt pass ({1, 0}) over rows of
+// T_rows tokens per sequence (prompt_passes)
+static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* rope_rows, int R, DecodePath path, const DevState* st, hipStream_t s, StreamForm* form = nullptr, int T_rows = 0) {
     const LayerPlan p = plan_layers(h, R, st != nullptr, path);
     const int dt = h->cfg.dtype, S = p.S, nbg = p.nbg, NB = 16 * nbg, chunks = p.chunks, dts = p.dts;
     const bool lora = p.lora, lmlp = p.lmlp, splitd = p.splitd, prepack = p.prepack, pfg = p.pfg, pfs = p.pfs, xhm = p.xhm, spd = p.spd;
@@ -1256,8 +1281,8 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
             pa.epoch = h->pl_epoch; pa.error = h->pl_error; pa.done = &st->all_done; pa.ts = h->pl_ts_on ? h->pl_ts : nullptr; pa.eps = 1e-6f; pa.sched = h->persist_sched; pa.pace = p.pace; pa.fault = h->persist_fault; pa.delay_att = h->persist_delay_att; pa.delay = h->persist_delay; pa.delay_act = p.delay_act; pa.delay_x = h->persist_delay_x; pa.nap = h->persist_nap; pa.nap_qkv = h->persist_nap_qkv; pa.poll = p.poll;
             if (lora) {
                 // per-utterance adapters: the rows' slots travel in the arguments (part of the decode-graph key), the operands are read from the resident tables
-                pa.lora = 1; pa.lslots = 0; pa.delay_u = p.delay_u;
-                for (int r = 0; r < PL_MAXR; ++r) pa.lslots |= (unsigned long long)(unsigned char)(r < R ? h->lora_row_slots[r] : -1) << (8 * r);
+                pa.lora = 1; pa.delay_u = p.delay_u; static_assert(sizeof(pa.lslots) == PL_MAXR, "PersistArgs.lslots: byte r = row r's slot");
+                row_slot_bytes(h, (signed char*)&pa.lslots, PL_MAXR);
                 pa.la_qkv_stride = (size_t)CTTS_MAX_ADAPTERS * 3 * 16 * h->H; pa.la_stride = (size_t)CTTS_MAX_ADAPTERS * 4 * 16 * h->H;
                 pa.la_qkv = h->lora_Af + pa.la_qkv_stride * l; pa.la = h->lora_A + pa.la_stride * l; pa.lb = h->lora_B + pa.la_stride * l;
                 pa.lscale = h->lora_scale + (size_t)l * CTTS_MAX_ADAPTERS * 4; pa.g_u = pa.g_part + PL_G_PART;
@@ -1292,7 +1317,7 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
         if (lfold) {
             LoraFold lf = {};
             lf.A = h->lora_A + lora_l; lf.B = h->lora_B + lora_l; lf.scale = h->lora_scale + (size_t)l * CTTS_MAX_ADAPTERS * 4; lf.lnw = h->ln1 + (size_t)l * h->H;
-            memcpy(lf.slots, h->lora_row_slots, sizeof(lf.slots)); static_assert(sizeof(lf.ranks) == CTTS_MAX_ADAPTERS * 4, "LoraFold.ranks");
+            row_slot_bytes(h, lf.slots, CTTS_MAX_B); static_assert(sizeof(lf.ranks) == CTTS_MAX_ADAPTERS * 4, "LoraFold.ranks");
             if (!h->lora_rank.empty()) memcpy(lf.ranks, &h->lora_rank[(size_t)l * CTTS_MAX_ADAPTERS * 4], sizeof(lf.ranks));
             lf.g = h->lora_g; lf.g_o = h->lora_g + (size_t)CTTS_MAX_B * 3 * h->H; lf.err = h->pl_error; lf.layer = l; lf.diag = h->lora_fold;
             g1.lf = lf; g1.lora_w = 3 * NB;
@@ -1317,7 +1342,7 @@ static int run_layers(ctts_gpt* h, float* x, const RowMeta* meta, const float* r
         AttnArgs at = {};
         at.q = h->q_buf; at.k_cache = g1.k_cache; at.v_cache = g1.v_cache; at.Lmax = h->cfg.max_seq; at.NH = h->NH; at.R = R; at.S = S;
         at.meta = meta; at.st = st; at.part_ml = h->part_ml; at.part_o = h->part_o; at.wide_blocks = p.wide_blocks; at.anchor = p.anchor;
-        if (st == nullptr) { at.T = h->pre_T; at.row0 = (int)(meta - h->meta_pre); }       // prompt pass: position of this pass in the flattened [B][T] prompt
+        if (st == nullptr) { at.T = T_rows; at.row0 = (int)(meta - h->meta_pre); }       // prompt pass: position of this pass in the flattened [B][T] prompt
         at.packed_out = (S == 1) ? h->attn_packed : nullptr; at.nbg = nbg; at.packed_split = spd ? 1 : 0;
         if (prompt_attention_kind(dt, R, at.T, at.anchor, pfs && S == 1) == ATTN_SPLIT) { if (launch_attention_split(at, h->sp_x_hi, h->sp_x_lo, s)) return 1; }      // writes o_proj's head / tail operand images directly
         else if (launch_attention(dt, at, s)) return 1;
@@ -1456,10 +1481,10 @@ static int reset_state(ctts_gpt* h, bool keep_draw, hipStream_t s) {
     CTTS_HIP_CHECK(hipMemsetAsync(h->io.finish, 0, h->B * 4, s));
     CTTS_HIP_CHECK(hipMemsetAsync(h->io.end_idx, 0, h->B * 4, s));
     if (!keep_draw) {       // begin: {fin 0, end 0, attempt 0, limit, utterance id} per row (pageable source: staged before the call returns)
-        CTTS_HIP_CHECK(hipMemcpyAsync(h->finend, h->rows_host.data(), h->B * sizeof(RowState), hipMemcpyHostToDevice, s));
+        CTTS_HIP_CHECK(hipMemcpyAsync(h->finend, h->finend_host.data(), h->B * sizeof(RowState), hipMemcpyHostToDevice, s));
     } else {
         if (launch_restart_rows(h->finend, h->B, s)) return 1;
-        h->row_ctx.assign(h->B, h->T);
+        for (HostRow& r : h->rows) r.ctx = h->T;
     }      // ensure_non_empty regenerate: rows that ended at step 0 move on to their next noise attempt
     CTTS_HIP_CHECK(hipMemsetAsync(h->hist_ring, 0xFF, (size_t)h->B * CTTS_NUM_VQ * 16 * 4, s));      // -1: no id sampled yet
     return 0;
@@ -1467,20 +1492,16 @@ static int reset_state(ctts_gpt* h, bool keep_draw, hipStream_t s) {
 
 // per-utterance adapters of sequences 0..B-1 for a call that starts a prompt pass (begin, score): the call starts from what ctts_gpt_set_row_adapters requested.
 // (lora_rows is the LIVE state: ctts_gpt_compact clears it once every adapter-carrying row has left the batch and ctts_gpt_admit_adapters rewrites the tables --
-// a second generate() after ONE set_row_adapters() call used to run without its adapters, silently)
+// a second generate() after ONE set_row_adapters() call used to run without its adapters, silently)  begin has its rows by now, row b on lane b; score seats none
 static int seat_row_adapters(ctts_gpt* h, int B, const char* who, hipStream_t s) {
     if (h->lora_slot_host.empty()) return 0;
-    if (h->lora_req_host.empty()) h->lora_slot_host.assign(CTTS_MAX_B, -1);
-    else h->lora_slot_host = h->lora_req_host;
-    bool any = false;
-    for (int b = 0; b < CTTS_MAX_B; ++b) { h->lora_row_slots[b] = (signed char)h->lora_slot_host[b]; any = any || (b < B && h->lora_slot_host[b] >= 0); }
-    h->lora_rows = any ? 1 : 0;
-    h->lora_mlp = 0;
-    for (int b = 0; b < B; ++b) if (lora_slot_has_mlp(h, h->lora_slot_host[b])) h->lora_mlp = 1;
-    if (lora_ensure_mlp_terms(h)) { h->lora_rows = 0; h->lora_mlp = 0; h->B = 0; return 1; }
-    if (h->lora_rows && h->batch_inv) {
-        h->lora_rows = 0; h->lora_mlp = 0; h->B = 0;
-        ctts_set_error("%s: per-utterance adapters (ctts_gpt_set_row_adapters) are outside the %s contract; set the option to 0 or merge the adapter", who, inv_name(h));
+    if (h->req.slots.empty()) h->lora_slot_host.assign(CTTS_MAX_B, -1);
+    else h->lora_slot_host = h->req.slots;
+    for (HostRow& r : h->rows) r.slot = h->lora_slot_host[r.seq];
+    const bool failed = lora_summary(h, B, [h](int b) { return h->lora_slot_host[b]; }) != 0;      // (of the sequences: the same as of begin's rows)
+    if (failed || (h->lora_rows && h->batch_inv)) {
+        if (!failed) ctts_set_error("%s: per-utterance adapters (ctts_gpt_set_row_adapters) are outside the %s contract; set the option to 0 or merge the adapter", who, inv_name(h));
+        h->rows.clear(); h->lora_rows = 0; h->lora_mlp = 0; h->B = 0;
         return 1;
     }
     if (h->lora_slot_of_seq)        // (pageable source: staged before the call returns)
@@ -1494,7 +1515,7 @@ static int seat_row_adapters(ctts_gpt* h, int B, const char* who, hipStream_t s)
 // Shared prompt passes: sequences that name one prompt run it through the prompt pass once, in the lane of the first of them; kv_share.hip hands the others a copy.
 extern "C" int ctts_gpt_share_prompts(ctts_gpt* h, int n, const int32_t* prompt_of, int n_prompts) {
     if (!h) { ctts_set_error("share_prompts: null handle"); return 1; }
-    h->share_req.clear(); h->share_req_P = 0;
+    h->next.share.clear(); h->next.share_P = 0;      // every call drops the pending table first, a refused one (n < 0 included) too
     if (!prompt_of || n == 0) return 0;
     if (n < 1 || n > h->cfg.max_batch || n_prompts < 1 || n_prompts > n) {
         ctts_set_error("share_prompts: n=%d sequences (max_batch %d) on n_prompts=%d prompts: need 1 <= n_prompts <= n <= max_batch", n, h->cfg.max_batch, n_prompts);
@@ -1507,9 +1528,24 @@ extern "C" int ctts_gpt_share_prompts(ctts_gpt* h, int n, const int32_t* prompt_
     }
     for (int p = 0; p < n_prompts; ++p) if (!named[p]) { ctts_set_error("share_prompts: prompt %d is named by no sequence", p); return 1; }
     if (!h->share_dev && dev_alloc(h, (void**)&h->share_dev, (size_t)SH_INTS * 4)) return 1;
-    h->share_req.assign(prompt_of, prompt_of + n);
-    h->share_req_P = n_prompts;
+    h->next.share.assign(prompt_of, prompt_of + n);
+    h->next.share_P = n_prompts;
     return 0;
+}
+// What share_prompts / admit_sampling / admit_modes named is for the NEXT begin / admit alone, whether it goes through or fails: the call takes it all first, so no later call picks up a stale entry
+static NextCall take_next_call(ctts_gpt* h) {
+    NextCall taken;
+    if (h) std::swap(taken, h->next);
+    return taken;
+}
+// Any generate state ends here: ctts_gpt_begin before it builds the next one, ctts_gpt_score because it overwrites the KV lanes and the prompt workspaces (text_mode, sc, io: begin rewrites them)
+static void end_generate_state(ctts_gpt* h) {
+    h->B = 0; h->B0 = 0; h->T = 0; h->rows.clear();
+    h->admitted = false; h->sampled = false;
+    h->segs.clear(); h->pp_rows = 0;  // (debug_read "decode_plan" / "prompt_plan": nothing planned, no prompt pass yet)
+    h->share_P = 0; h->share_groups = 0;
+    h->text_rows_on = 0;              // every begin switches text rows off again: ctts_gpt_enable_text_rows follows it
+    (void)refresh_rows(h);            // no rows: no text row, no adapter row (nothing to allocate)
 }
 // the table of one call (kernels.h SH_*): `lanes[i]` = KV lane of the call's i-th sequence.  The prompt pass runs under the leader's adapter slot, so a group shares one slot or none.
 static int share_plan(ctts_gpt* h, const std::vector<int>& prompt_of, int P, const int* lanes, const char* who, hipStream_t s) {
@@ -1551,11 +1587,10 @@ static int share_kv(ctts_gpt* h, int span, hipStream_t s) {
     return launch_kv_share(a, h->L * 2 * h->NH, s);
 }
 
-extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, const ctts_sampler_cfg* sc, const ctts_gen_io* io, void* stream) {
-    // what ctts_gpt_share_prompts named is for THIS call only, whether it goes through or fails below
-    std::vector<int> share;
-    int share_P = 0;
-    if (h) { share.swap(h->share_req); share_P = h->share_req_P; h->share_req_P = 0; }
+// ctts_gpt_begin with the requests it took.  The share table is spent whatever happens.  The admission requests (req.modes, req.knobs) are cleared HERE, at the point
+// from which the call has dropped them even if it fails further down; what a failed call leaves in `req` goes back to the handle (ctts_gpt_begin).
+static int begin_state(ctts_gpt* h, int B, int T, const int32_t* mask, const ctts_sampler_cfg* sc, const ctts_gen_io* io, void* stream, NextCall& req) {
+    const std::vector<int>& share = req.share; const int share_P = req.share_P;
     if (!h || !h->finalized || !h->kv || !h->rope) { ctts_set_error("begin: handle not ready (finalize / bind_kv / set_rope)"); return 1; }
     if (!mask || !sc || !io || !io->ids || !io->finish || !io->end_idx) { ctts_set_error("begin: null argument"); return 1; }
     CTTS_RANGE("ctts_gpt_begin");               // reference: nvtx "adjust_buffer" / "set_tensors" (trt_models/predictor.py:142,159)
@@ -1569,21 +1604,22 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
     }
     // row modes of this call (ctts_gpt_set_row_modes): checked before anything changes
     bool any_text = false;
-    for (int b = 0; b < B && b < (int)h->modes_req.size(); ++b) any_text = any_text || h->modes_req[b] == 1;
+    for (int b = 0; b < B && b < (int)h->req.modes.size(); ++b) any_text = any_text || h->req.modes[b] == 1;
     if (any_text) {
         if (sc->infer_text) { ctts_set_error("begin: text rows (ctts_gpt_set_row_modes) live in a code-mode call; this call's own infer_text is 1 -- every row of it is a text row already"); return 1; }
         if (!h->whead_text || !h->emb_text) { ctts_set_error("begin: a text row (ctts_gpt_set_row_modes) needs head_text.* and emb_text.weight"); return 1; }
         if (io->noise != nullptr) { ctts_set_error("begin: text rows (ctts_gpt_set_row_modes) need device noise (caller-supplied noise is laid out for one mode's rows)"); return 1; }
         if (!share.empty()) { ctts_set_error("begin: shared prompt passes (ctts_gpt_share_prompts) are for code rows; this call seats a text row (ctts_gpt_set_row_modes)"); return 1; }
         const RowSampling call_knobs = knobs_of_cfg(cfg_of_abi(*sc));      // (set_row_sampling names every sequence: an entry equal to the call's values is no knob of its own)
-        for (int b = 0; b < B && b < (int)h->knobs_req.size() && b < (int)h->modes_req.size(); ++b)
-            if (h->modes_req[b] == 1 && !same_knobs(h->knobs_req[b], call_knobs)) {
+        for (int b = 0; b < B && b < (int)h->req.knobs.size() && b < (int)h->req.modes.size(); ++b)
+            if (h->req.modes[b] == 1 && !same_knobs(h->req.knobs[b], call_knobs)) {
                 ctts_set_error("begin: sequence %d is a text row (ctts_gpt_set_row_modes) and carries per-row sampling knobs (ctts_gpt_set_row_sampling); text rows keep the values of ctts_gpt_enable_text_rows", b);
                 return 1;
             }
     }
-    h->text_mode = sc->infer_text ? 1 : 0;
-    h->text_rows_on = 0; h->text_live = 0; h->modes_admit.clear();      // every begin switches text rows off again: ctts_gpt_enable_text_rows follows it
+    // From here on the call's mode is written, the text rows are off and the modes named for an admission dropped -- for the previous state too, should a refusal below leave it standing (as always)
+    h->text_mode = sc->infer_text ? 1 : 0; h->text_rows_on = 0; h->text_live = 0;
+    req.modes.clear();
     if (h->text_mode) {
         if (!h->whead_text || !h->emb_text) { ctts_set_error("begin: infer_text needs head_text.* and emb_text.weight"); return 1; }
         if (sc->use_penalty) { ctts_set_error("begin: infer_text supports repetition_penalty == 1 only (the reference's processor mis-broadcasts the [B,n,1] history in this mode)"); return 1; }
@@ -1598,42 +1634,35 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
         ctts_set_error("begin: batch_invariant needs the head / tail weight images, and a weight of this checkpoint is beyond the fp16 range (x 64)");
         return 1;
     }
-    if (!h->knobs_req.empty()) {       // per-utterance sampling knobs (ctts_gpt_set_row_sampling)
+    if (!h->req.knobs.empty()) {       // per-utterance sampling knobs (ctts_gpt_set_row_sampling)
         if (h->text_mode) { ctts_set_error("begin: per-utterance sampling parameters (set_row_sampling) are code mode only; the refine-text pass (infer_text) keeps the call's values"); return 1; }
-        for (int b = 0; b < B && b < (int)h->knobs_req.size(); ++b) {
+        for (int b = 0; b < B && b < (int)h->req.knobs.size(); ++b) {
             ctts_row_sampling p;
-            memcpy(&p, &h->knobs_req[b], sizeof(p));
+            memcpy(&p, &h->req.knobs[b], sizeof(p));
             if (check_knobs(p, sc->max_new_token, "begin (set_row_sampling)", b)) return 1;
         }
     }
     hipStream_t s = (hipStream_t)stream;
+    end_generate_state(h);
     h->B = B; h->B0 = B; h->T = T; h->io = *io;
-    h->admitted = false;
-    h->sampled = false;
-    h->segs.clear();                  // (debug_read "decode_plan": nothing planned yet for this batch)
-    h->pp_rows = 0;                   // (debug_read "prompt_plan": no prompt pass yet)
-    h->rows_host.assign(B, RowState{});
-    for (int b = 0; b < B; ++b) {
-        RowState& r = h->rows_host[b];
+    h->finend_host.assign(B, RowState{}); h->seq_host.resize(B);
+    for (int b = 0; b < B; ++b) {       // sequence b sits in row b and KV lane b
+        RowState& r = h->finend_host[b];
         const unsigned long long uid = io->utt_ids ? io->utt_ids[b] : (unsigned long long)b;
         int lim = io->row_limits ? io->row_limits[b] : sc->max_new_token;
         r.limit = lim < 1 ? 1 : (lim > sc->max_new_token ? sc->max_new_token : lim);
         r.uid_lo = (unsigned)uid; r.uid_hi = (unsigned)(uid >> 32);
         r.out = b;
-        r.mode = (any_text && b < (int)h->modes_req.size() && h->modes_req[b] == 1) ? 1 : 0;
+        r.mode = (any_text && b < (int)h->req.modes.size() && h->req.modes[b] == 1) ? 1 : 0;
+        h->rows.push_back(HostRow{b, T, T + r.limit, r.mode, -1});
+        h->seq_host[b] = b;
     }
-    h->row_mode.assign(B, 0);
-    for (int b = 0; b < B; ++b) { h->row_mode[b] = h->rows_host[b].mode; h->text_live += h->rows_host[b].mode; }
-    h->row_seq.resize(B); h->row_ctx.assign(B, T); h->row_cap.resize(B);
-    for (int b = 0; b < B; ++b) { h->row_seq[b] = b; h->row_cap[b] = T + h->rows_host[b].limit; }
-    if (seat_row_adapters(h, B, "begin", s)) return 1;
-    h->share_P = 0; h->share_groups = 0;
-    if (!share.empty()) {       // sequence b sits in row b and KV lane b
-        if (share_plan(h, share, share_P, h->row_seq.data(), "begin", s)) { h->B = 0; return 1; }
+    if (refresh_rows(h) || seat_row_adapters(h, B, "begin", s)) return 1;
+    if (!share.empty()) {
+        if (share_plan(h, share, share_P, h->seq_host.data(), "begin", s)) { h->B = 0; h->rows.clear(); return 1; }
         h->share_P = share_P;
     }
     const int* share_dev = h->share_P ? h->share_dev : nullptr;
-    h->pre_T = T;
     h->io.utt_ids = nullptr; h->io.row_limits = nullptr;      // host arrays are consumed here, not kept
     h->sc = cfg_of_abi(*sc);
     SamplerDyn d = {};
@@ -1643,18 +1672,15 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
     CTTS_HIP_CHECK(hipMemcpyAsync(h->dyn, &d, sizeof(d), hipMemcpyHostToDevice, s));       // pageable source: staged before the call returns
     // the rows' sampling knobs: the call's values, then what set_row_sampling requested per sequence
     h->knobs_host.assign(B, knobs_of_cfg(h->sc));
-    for (int b = 0; b < B && b < (int)h->knobs_req.size(); ++b) h->knobs_host[b] = h->knobs_req[b];
-    h->knobs_admit.clear();
+    for (int b = 0; b < B && b < (int)h->req.knobs.size(); ++b) h->knobs_host[b] = h->req.knobs[b];
+    req.knobs.clear();               // the new rows have their knobs: what was named for an admission into the previous state is dropped
     CTTS_HIP_CHECK(hipMemcpyAsync(h->knobs, h->knobs_host.data(), (size_t)B * sizeof(RowSampling), hipMemcpyHostToDevice, s));
     if (launch_fill_meta(h->meta_pre, h->meta_dec0, h->st, mask, B, T, h->rope, h->rope_pre, share_dev, h->share_P ? h->share_P : B, s)) return 1;
     if (h->batch_inv) {
         // the prompt is laid out like an admission of every row (ctts_gpt_admit): T - 1 prompt rows per sequence for the prompt pass, the decode rows at the last
         // token (slot T - 1: the same RowMeta as meta_dec0) with its RoPE row -- ctts_gpt_prefill fills x_dec with the last tokens' embeddings
-        h->pre_T = T - 1;
-        h->keep_host.resize(B);
-        for (int b = 0; b < B; ++b) h->keep_host[b] = b;
-        CTTS_HIP_CHECK(hipMemcpyAsync(h->keep_dev, h->keep_host.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));      // rows == KV lanes
-        CTTS_HIP_CHECK(hipMemcpyAsync(h->cfin, h->rows_host.data(), (size_t)B * sizeof(RowState), hipMemcpyHostToDevice, s));
+        CTTS_HIP_CHECK(hipMemcpyAsync(h->keep_dev, h->seq_host.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));      // rows == KV lanes
+        CTTS_HIP_CHECK(hipMemcpyAsync(h->cfin, h->finend_host.data(), (size_t)B * sizeof(RowState), hipMemcpyHostToDevice, s));
         AdmitArgs a = {};
         a.mask = mask; a.emb = nullptr; a.rows = h->keep_dev; a.seqs = h->keep_dev; a.fresh = h->cfin; a.n = B; a.T = T; a.H = h->H;
         a.pm = h->meta_pre; a.rope_pre = h->rope_pre; a.dm = h->meta_dec; a.rope_dec = h->rope_dec; a.x_dec = h->x_dec; a.ring = h->hist_ring; a.finend = h->finend;
@@ -1666,6 +1692,49 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
     if (h->pl_error) CTTS_HIP_CHECK(hipMemsetAsync(h->pl_error, 0, 4, s));
     return reset_state(h, false, s);
 }
+extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, const ctts_sampler_cfg* sc, const ctts_gen_io* io, void* stream) {
+    NextCall req = take_next_call(h);
+    const int rc = begin_state(h, B, T, mask, sc, io, stream, req);
+    // A refused begin hands back the admission requests it had not dropped yet (begin_state): refused before it touches anything, it leaves the previous generate
+    // state standing, and what ctts_gpt_admit_sampling / ctts_gpt_admit_modes named for that state's next admission with it.  The share table never goes back.
+    if (rc && h) { h->next.knobs = std::move(req.knobs); h->next.modes = std::move(req.modes); }
+    return rc;
+}
+
+// The one prompt-pass loop (prefill, the invariant prefill, score, admit): R prompt rows of T_rows tokens per sequence, laid out from meta_pre[0] on, through the layers
+// in passes of at most pass_rows rows.  stage(r0, n) fills x_pre[0, n) with rows r0 .. r0 + n - 1, after(r0, n) takes what the layers left there.
+template <class Stage, class After>
+static int prompt_passes(ctts_gpt* h, long R, int T_rows, hipStream_t s, Stage stage, After after) {
+    for (long r0 = 0; r0 < R; r0 += h->pass_rows) {
+        const int n = (int)(R - r0 < h->pass_rows ? R - r0 : h->pass_rows);
+        if (stage(r0, n) || run_layers(h, h->x_pre, h->meta_pre + r0, h->rope_pre + (size_t)r0 * 64, n, DecodePath{1, 0}, nullptr, s, nullptr, T_rows) || after(r0, n)) return 1;
+    }
+    return 0;
+}
+// stage: rows of the caller's [.][T] embeddings as they lie (prefill, score)
+static int stage_rows(ctts_gpt* h, const float* emb, long r0, int n, hipStream_t s) {
+    CTTS_HIP_CHECK(hipMemcpyAsync(h->x_pre, emb + (size_t)r0 * h->H, (size_t)n * h->H * 4, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+// stage: rows of the [.][T - 1] layout -- every sequence without its last token -- from [.][T] embeddings (the invariant prefill; ctts_gpt_admit: one pass, one 2-D copy)
+static int stage_rows_but_last(ctts_gpt* h, const float* emb, int T, long r0, int n, hipStream_t s) {
+    const long Tm = T - 1, H = h->H;
+    for (long r = r0; r < r0 + n;) {             // x_pre[0, n) <- prompt rows r0 .. r0 + n - 1
+        const long b = r / Tm, t = r % Tm, left = r0 + n - r;
+        if (t == 0 && left >= Tm) {
+            const long nb = left / Tm;
+            CTTS_HIP_CHECK(hipMemcpy2DAsync(h->x_pre + (size_t)(r - r0) * H, (size_t)Tm * H * 4, emb + (size_t)b * T * H, (size_t)T * H * 4, (size_t)Tm * H * 4, nb,
+                                            hipMemcpyDeviceToDevice, s));
+            r += nb * Tm;
+        } else {
+            const long len = (Tm - t < left) ? Tm - t : left;
+            CTTS_HIP_CHECK(hipMemcpyAsync(h->x_pre + (size_t)(r - r0) * H, emb + ((size_t)b * T + t) * H, (size_t)len * H * 4, hipMemcpyDeviceToDevice, s));
+            r += len;
+        }
+    }
+    return 0;
+}
+static int no_after(long, int) { return 0; }
 
 // batch_invariant prompt pass: the first T - 1 tokens of every sequence, laid out [B][T - 1] (ctts_gpt_begin), in passes of at most pass_rows rows; the last
 // token's embedding becomes the decode row's input, which ctts_gpt_sample runs through the first layer pass -- the admission path (ctts_gpt_admit), so a begun
@@ -1674,24 +1743,8 @@ extern "C" int ctts_gpt_begin(ctts_gpt* h, int B, int T, const int32_t* mask, co
 static int prefill_invariant(ctts_gpt* h, const float* emb, hipStream_t s) {
     const int B = h->B, T = h->T, Tm = T - 1, H = h->H, P = h->share_P ? h->share_P : B;
     const long R = (long)P * Tm;
-    h->pp_rows = R; h->pp_T = h->pre_T;
-    for (long r0 = 0; r0 < R; r0 += h->pass_rows) {
-        const int n = (int)(R - r0 < h->pass_rows ? R - r0 : h->pass_rows);
-        for (long r = r0; r < r0 + n;) {             // x_pre[0, n) <- prompt rows r0 .. r0 + n - 1 of the [B][T - 1] layout (emb is [B][T])
-            const long b = r / Tm, t = r % Tm, left = r0 + n - r;
-            if (t == 0 && left >= Tm) {
-                const long nb = left / Tm;
-                CTTS_HIP_CHECK(hipMemcpy2DAsync(h->x_pre + (size_t)(r - r0) * H, (size_t)Tm * H * 4, emb + (size_t)b * T * H, (size_t)T * H * 4, (size_t)Tm * H * 4, nb,
-                                                hipMemcpyDeviceToDevice, s));
-                r += nb * Tm;
-            } else {
-                const long len = (Tm - t < left) ? Tm - t : left;
-                CTTS_HIP_CHECK(hipMemcpyAsync(h->x_pre + (size_t)(r - r0) * H, emb + ((size_t)b * T + t) * H, (size_t)len * H * 4, hipMemcpyDeviceToDevice, s));
-                r += len;
-            }
-        }
-        if (run_layers(h, h->x_pre, h->meta_pre + r0, h->rope_pre + (size_t)r0 * 64, n, DecodePath{1, 0}, nullptr, s)) return 1;
-    }
+    h->pp_rows = R; h->pp_T = Tm;
+    if (prompt_passes(h, R, Tm, s, [&](long r0, int n) { return stage_rows_but_last(h, emb, T, r0, n, s); }, no_after)) return 1;
     if (h->share_P) {
         if (launch_share_rows(emb + (size_t)Tm * H, (size_t)T * H, h->share_dev + SH_PROMPT, h->x_dec, B, H, s) || share_kv(h, Tm, s)) return 1;
     } else
@@ -1707,16 +1760,11 @@ extern "C" int ctts_gpt_prefill(ctts_gpt* h, const float* emb, void* stream) {
     if (h->batch_inv) return prefill_invariant(h, emb, s);
     // shared prompt passes: P prompts in the leaders' lanes; their last residual rows land in the leaders' decode rows, the followers get a copy of both
     const int P = h->share_P ? h->share_P : h->B;
-    const int R = P * h->T;
-    const int PASS_ROWS = h->pass_rows;
-    h->pp_rows = R; h->pp_T = h->pre_T;
-    for (int r0 = 0; r0 < R; r0 += PASS_ROWS) {
-        const int n = (R - r0 < PASS_ROWS) ? R - r0 : PASS_ROWS;
-        CTTS_HIP_CHECK(hipMemcpyAsync(h->x_pre, emb + (size_t)r0 * h->H, (size_t)n * h->H * 4, hipMemcpyDeviceToDevice, s));
-        if (run_layers(h, h->x_pre, h->meta_pre + r0, h->rope_pre + (size_t)r0 * 64, n, DecodePath{1, 0}, nullptr, s)) return 1;
-        // rows (b, T-1) that live in this pass -> x_dec[b]  (indices computed on the device: the call stays asynchronous)
-        if (launch_gather_last_rows(h->x_pre, h->x_dec, P, h->T, r0, n, h->H, h->share_P ? h->share_dev + SH_LEADER : nullptr, s)) return 1;
-    }
+    const long R = (long)P * h->T;
+    h->pp_rows = R; h->pp_T = h->T;
+    // after a pass: rows (b, T-1) that live in it -> x_dec[b]  (indices computed on the device: the call stays asynchronous)
+    if (prompt_passes(h, R, h->T, s, [&](long r0, int n) { return stage_rows(h, emb, r0, n, s); }, [&](long r0, int n) {
+            return launch_gather_last_rows(h->x_pre, h->x_dec, P, h->T, (int)r0, n, h->H, h->share_P ? h->share_dev + SH_LEADER : nullptr, s); })) return 1;
     if (h->share_P && (launch_share_rows(h->x_dec, (size_t)h->H, h->share_dev + SH_LEAD_OF, h->x_dec, h->B, h->H, s) || share_kv(h, h->T, s))) return 1;
     // keep a copy of the prompt's last residual rows for ensure_non_empty restarts
     CTTS_HIP_CHECK(hipMemcpyAsync(h->x_last, h->x_dec, (size_t)h->B * h->H * 4, hipMemcpyDeviceToDevice, s));
@@ -1746,8 +1794,8 @@ extern "C" int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* mask, co
     }
     CTTS_RANGE("ctts_gpt_score");
     hipStream_t s = (hipStream_t)stream;
-    h->B = 0; h->admitted = false; h->share_P = 0;      // the KV lanes and the prompt workspaces are overwritten: any generate() state ends here
-    h->text_mode = 0; h->text_rows_on = 0; h->text_live = 0;
+    end_generate_state(h);            // the KV lanes and the prompt workspaces are overwritten
+    h->text_mode = 0;
     if (seat_row_adapters(h, B, "score", s)) return 1;
     const int NV = h->NVQ * h->V;
     if (h->score_oidx == nullptr) {
@@ -1759,7 +1807,6 @@ extern "C" int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* mask, co
     // entries j >= n_b: logprob 0, argmax -1
     CTTS_HIP_CHECK(hipMemsetAsync(logprob, 0, (size_t)B * max_targets * CTTS_NUM_VQ * 4, s));
     CTTS_HIP_CHECK(hipMemsetAsync(argmax, 0xFF, (size_t)B * max_targets * CTTS_NUM_VQ * 4, s));
-    h->pre_T = T;
     if (launch_fill_meta(h->meta_pre, h->meta_dec0, h->st, mask, B, T, h->rope, h->rope_pre, nullptr, B, s)) return 1;
     const long R = (long)B * T;
     h->pp_rows = R; h->pp_T = T;
@@ -1767,10 +1814,7 @@ extern "C" int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* mask, co
     const int nbg = h->batch_inv ? 1 : 2;
     ScoreRows sr = {};
     sr.B = B; sr.max_targets = max_targets;
-    for (long r0 = 0; r0 < R; r0 += h->pass_rows) {
-        const int n = (int)(R - r0 < h->pass_rows ? R - r0 : h->pass_rows);
-        CTTS_HIP_CHECK(hipMemcpyAsync(h->x_pre, emb + (size_t)r0 * h->H, (size_t)n * h->H * 4, hipMemcpyDeviceToDevice, s));
-        if (run_layers(h, h->x_pre, h->meta_pre + r0, h->rope_pre + (size_t)r0 * 64, n, DecodePath{1, 0}, nullptr, s)) return 1;
+    return prompt_passes(h, R, T, s, [&](long r0, int n) { return stage_rows(h, emb, r0, n, s); }, [&](long r0, int n) {
         // the scored rows of this pass: sequence b's rows [b T + T - n_b, b T + T) clipped to [r0, r0 + n)
         sr.cum[0] = 0;
         for (int b = 0; b < B; ++b) {
@@ -1790,8 +1834,8 @@ extern "C" int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* mask, co
             if (launch_gemm(h->cfg.dtype, nbg, PRO_NORM, EPI_LOGITS, a, (m + 16 * nbg - 1) / (16 * nbg), s)) return 1;
             if (launch_score_reduce(h->score_logits, h->score_oidx, targets, logprob, argmax, m, h->V, NV, s)) return 1;
         }
-    }
-    return 0;
+        return 0;
+    });
 }
 
 static int run_decode_step(ctts_gpt* h, DecodePath path, hipStream_t s);
@@ -1812,27 +1856,27 @@ extern "C" int ctts_gpt_set_logprob_out(ctts_gpt* h, float* lp_raw, float* lp_sa
 // ---- text rows beside code rows (include/ctts_hip.h; RowState.mode) --------------------------------------------------------------------------------------------
 extern "C" int ctts_gpt_set_row_modes(ctts_gpt* h, const int32_t* modes, int B) {
     if (!h) { ctts_set_error("set_row_modes: null handle"); return 1; }
-    if (!modes || B <= 0) { h->modes_req.clear(); return 0; }
+    if (!modes || B <= 0) { h->req.modes.clear(); return 0; }
     if (B > CTTS_MAX_B) { ctts_set_error("set_row_modes: B=%d > %d", B, CTTS_MAX_B); return 1; }
     for (int b = 0; b < B; ++b) if (modes[b] != 0 && modes[b] != 1) { ctts_set_error("set_row_modes: sequence %d: mode %d (0 = code, 1 = text)", b, modes[b]); return 1; }
-    h->modes_req.assign(modes, modes + B);
+    h->req.modes.assign(modes, modes + B);
     return 0;
 }
 extern "C" int ctts_gpt_admit_modes(ctts_gpt* h, int n, const int32_t* rows, const int32_t* modes, void* stream) {
     (void)stream;        // host-side request: the next ctts_gpt_admit seats the modes
     if (!h || h->B == 0 || !rows || !modes || n < 0) { ctts_set_error("admit_modes: call begin first / null argument"); return 1; }
     bool any = false;
-    for (int i = 0; i < n; ++i) {
-        if (rows[i] < 0 || rows[i] >= h->B) { ctts_set_error("admit_modes: row %d of %d", rows[i], h->B); return 1; }
-        if (modes[i] != 0 && modes[i] != 1) { ctts_set_error("admit_modes: entry %d: mode %d (0 = code, 1 = text)", i, modes[i]); return 1; }
-        any = any || modes[i] == 1;
-    }
+    if (check_rows(h, "admit_modes", n, rows, false, [&](int i) {
+            if (modes[i] != 0 && modes[i] != 1) { ctts_set_error("admit_modes: entry %d: mode %d (0 = code, 1 = text)", i, modes[i]); return 1; }
+            any = any || modes[i] == 1;
+            return 0;
+        })) return 1;
     if (any && h->text_mode) { ctts_set_error("admit_modes: this call's own infer_text is 1: every row of it is a text row already; text rows beside code rows live in a code-mode call"); return 1; }
     if (any && !h->text_rows_on) { ctts_set_error("admit_modes: a mode-1 row needs ctts_gpt_enable_text_rows first (after ctts_gpt_begin, before the row is seated)"); return 1; }
     for (int i = 0; i < n; ++i) {
         bool found = false;
-        for (auto& e : h->modes_admit) if (e.first == rows[i]) { e.second = modes[i]; found = true; }
-        if (!found) h->modes_admit.emplace_back(rows[i], modes[i]);
+        for (auto& e : h->next.modes) if (e.first == rows[i]) { e.second = modes[i]; found = true; }
+        if (!found) h->next.modes.emplace_back(rows[i], modes[i]);
     }
     return 0;
 }
@@ -1865,8 +1909,8 @@ extern "C" int ctts_gpt_enable_text_rows(ctts_gpt* h, const ctts_sampler_cfg* ts
     // text rows that begin seated (ctts_gpt_set_row_modes): their limit is the text rows' own (begin clamped it to the code call's)
     if (h->text_live > 0) {
         for (int b = 0; b < h->B; ++b)
-            if (h->rows_host[b].mode == 1 && h->rows_host[b].limit > h->sc_text.max_new) { h->rows_host[b].limit = h->sc_text.max_new; h->row_cap[b] = h->T + h->sc_text.max_new; }
-        CTTS_HIP_CHECK(hipMemcpyAsync(h->finend, h->rows_host.data(), (size_t)h->B * sizeof(RowState), hipMemcpyHostToDevice, s));
+            if (h->finend_host[b].mode == 1 && h->finend_host[b].limit > h->sc_text.max_new) { h->finend_host[b].limit = h->sc_text.max_new; h->rows[b].cap = h->T + h->sc_text.max_new; }
+        CTTS_HIP_CHECK(hipMemcpyAsync(h->finend, h->finend_host.data(), (size_t)h->B * sizeof(RowState), hipMemcpyHostToDevice, s));
     }
     h->text_rows_on = 1;
     return 0;
@@ -1899,11 +1943,9 @@ extern "C" int ctts_gpt_restart(ctts_gpt* h, void* stream) {
 // the longest one after `n_steps` more steps picks the attention's key-split count
 static int advance_rows(ctts_gpt* h, int n_steps) {
     int longest = 1;
-    for (int r = 0; r < h->B; ++r) {
-        int c = h->row_ctx[r] + n_steps;
-        if (c > h->row_cap[r]) c = h->row_cap[r];
-        h->row_ctx[r] = c;
-        if (c > longest) longest = c;
+    for (HostRow& r : h->rows) {
+        r.ctx = std::min(r.ctx + n_steps, r.cap);
+        if (r.ctx > longest) longest = r.ctx;
     }
     return longest;
 }
@@ -1997,7 +2039,7 @@ static int ensure_graph(ctts_gpt* h, DecodePath path, int n_steps) {
     char sig[160];
     snprintf(sig, sizeof(sig), "%d|%d|%p|%d|%d|%d|%d|%d", h->B, h->text_mode + 2 * (h->text_live > 0 ? 1 : 0), (void*)h->kv, path.splits, h->lora_rows + 2 * h->lora_mlp, h->opt_gen, path.persist, n_steps);      // (+ 2: a mixed step, two more launches)      // (diagnostic switches are fixed at create)
     std::string key(sig);
-    if (h->lora_rows) key.append((const char*)h->lora_row_slots, (size_t)h->B);      // the rows' adapter slots are kernel arguments of the folded launches (LoraFold)
+    if (h->lora_rows) { signed char slots[CTTS_MAX_B]; row_slot_bytes(h, slots, h->B); key.append((const char*)slots, (size_t)h->B); }      // the rows' adapter slots are kernel arguments of the folded launches (LoraFold)
     if (h->graph_gen != h->opt_gen || h->graphs.size() >= 96) {
         // graphs captured under other option / adapter settings are dead weight (loading one adapter bumps opt_gen ~80 times), and the cache is bounded: a serving
         // process cycles through few (batch, mode) shapes.  Replays of the dropped graphs may still be in flight (generate() keeps two chunks enqueued): drain first.
@@ -2031,7 +2073,7 @@ static void plan_decode(ctts_gpt* h, int n_steps) {
     h->segs.clear();
     for (int i = 1; i <= n_steps; ++i) {
         int longest = 1;
-        for (int r = 0; r < h->B; ++r) { const int c = std::min(h->row_ctx[r] + i, h->row_cap[r]); if (c > longest) longest = c; }
+        for (const HostRow& r : h->rows) longest = std::max(longest, std::min(r.ctx + i, r.cap));
         const DecodePath path = pick_decode_path(h, longest + 1);
         if (!h->segs.empty() && h->segs.back().path.splits == path.splits && h->segs.back().path.persist == path.persist) ++h->segs.back().n;
         else h->segs.push_back({1, path});
@@ -2112,14 +2154,6 @@ extern "C" int ctts_gpt_rows_enqueue(ctts_gpt* h, int32_t* host_pinned_2B, void*
     return 0;
 }
 
-// per-utterance adapters: the engine keeps the LoRA launches only while a live row carries an adapter
-static void lora_refresh(ctts_gpt* h) {
-    bool any = false;
-    bool mlp = false;
-    for (int r = 0; r < h->B; ++r) { any = any || h->lora_row_slots[r] >= 0; mlp = mlp || lora_slot_has_mlp(h, h->lora_row_slots[r]); }
-    h->lora_rows = any ? 1 : 0;
-    h->lora_mlp = mlp ? 1 : 0;
-}
 extern "C" int ctts_gpt_compact(ctts_gpt* h, const int32_t* keep_rows, int n_keep, void* stream) {
     if (!h || !keep_rows || h->B == 0) { ctts_set_error("compact: call begin first"); return 1; }
     if (n_keep < 1 || n_keep > h->B) { ctts_set_error("compact: n_keep=%d of %d rows", n_keep, h->B); return 1; }
@@ -2131,44 +2165,33 @@ extern "C" int ctts_gpt_compact(ctts_gpt* h, const int32_t* keep_rows, int n_kee
     CTTS_HIP_CHECK(hipMemcpyAsync(h->keep_dev, h->keep_host.data(), (size_t)n_keep * 4, hipMemcpyHostToDevice, s));
     if (launch_compact_rows(h->keep_dev, n_keep, h->H, h->x_dec, h->rope_dec, h->meta_dec, h->hist_ring, h->finend, h->knobs, h->cx, h->crope, h->cmeta, h->cring, h->cfin,
                             h->cknobs, h->st, s)) return 1;
-    for (int i = 0; i < n_keep; ++i) { h->row_seq[i] = h->row_seq[keep_rows[i]]; h->row_ctx[i] = h->row_ctx[keep_rows[i]]; h->row_cap[i] = h->row_cap[keep_rows[i]]; }
-    if (!h->row_mode.empty()) {      // the rows' modes move with them; a batch that dropped its last text row is an ordinary code batch again
-        h->text_live = 0;
-        for (int i = 0; i < n_keep; ++i) { h->row_mode[i] = h->row_mode[keep_rows[i]]; h->text_live += h->row_mode[i]; }
-        h->row_mode.resize(n_keep);
-    }
-    if (!h->lora_slot_host.empty()) for (int i = 0; i < n_keep; ++i) h->lora_row_slots[i] = (signed char)h->lora_slot_host[h->row_seq[i]];
-    h->B = n_keep;
-    if (h->lora_rows) lora_refresh(h);
-    return 0;
+    for (int i = 0; i < n_keep; ++i) h->rows[i] = h->rows[keep_rows[i]];      // (ascending: keep_rows[i] >= i)
+    h->rows.resize(n_keep); h->B = n_keep;
+    // a batch that dropped its last text row is an ordinary code batch again; the LoRA launches stay only while a live row carries an adapter
+    return refresh_rows(h);
 }
-
 
 // Adapter slots of the utterances the NEXT ctts_gpt_admit call seats in `rows` (-1 = none); rows not named keep theirs.  The slot follows the row's KV
 // lane (the prompt pass of the admitted rows looks it up by sequence, lora.hip) and the row itself (the decode launches carry the rows' slots in their
 // arguments, lora_worker.h).  When no live row has an adapter any more the engine drops back to the plain launches.
 extern "C" int ctts_gpt_admit_adapters(ctts_gpt* h, int n, const int32_t* rows, const int32_t* slots, void* stream) {
     if (!h || h->B == 0 || !rows || !slots) { ctts_set_error("admit_adapters: call begin first / null argument"); return 1; }
-    if (h->lora_slot_host.empty()) {
-        h->lora_slot_host.assign(CTTS_MAX_B, -1);
-        for (int b = 0; b < CTTS_MAX_B; ++b) h->lora_row_slots[b] = -1;
-    }
+    if (h->lora_slot_host.empty()) h->lora_slot_host.assign(CTTS_MAX_B, -1);      // (the rows' slots are -1 then)
     bool any = false;
-    for (int i = 0; i < n; ++i) {
-        if (rows[i] < 0 || rows[i] >= h->B || slots[i] >= CTTS_MAX_ADAPTERS) { ctts_set_error("admit_adapters: row %d / slot %d out of range", rows[i], slots[i]); return 1; }
+    for (int i = 0; i < n; ++i) {       // (one message for a row or a slot out of range)
+        if (slots[i] >= CTTS_MAX_ADAPTERS || check_rows(h, "admit_adapters", 1, rows + i, false)) { ctts_set_error("admit_adapters: row %d / slot %d out of range", rows[i], slots[i]); return 1; }
         any = any || slots[i] >= 0;
     }
     if (any && h->batch_inv) { ctts_set_error("admit_adapters: per-utterance adapters are outside the %s contract; set the option to 0 or merge the adapter", inv_name(h)); return 1; }
     if (any && lora_ensure_storage(h)) return 1;
     for (int i = 0; i < n; ++i) {
         const int sl = slots[i] < 0 ? -1 : slots[i];
-        h->lora_slot_host[h->row_seq[rows[i]]] = sl;
-        h->lora_row_slots[rows[i]] = (signed char)sl;
+        h->rows[rows[i]].slot = sl;
+        h->lora_slot_host[h->rows[rows[i]].seq] = sl;
     }
     if (h->lora_slot_of_seq)        // (pageable source: staged before the call returns)
         CTTS_HIP_CHECK(hipMemcpyAsync(h->lora_slot_of_seq, h->lora_slot_host.data(), CTTS_MAX_B * 4, hipMemcpyHostToDevice, (hipStream_t)stream));
-    lora_refresh(h);
-    return lora_ensure_mlp_terms(h);
+    return refresh_rows(h);
 }
 
 // Continuous batching (no counterpart in the reference, whose slices run to their slowest row, pipeline:391-397 / gpt.py:527-546): `n` new
@@ -2179,15 +2202,8 @@ extern "C" int ctts_gpt_admit_adapters(ctts_gpt* h, int n, const int32_t* rows, 
 extern "C" int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, const int32_t* mask, const float* emb, const uint64_t* utt_ids,
                               const int32_t* row_limits, const int32_t* out_index, const int32_t* attempts, void* stream) {
     if (!h || h->B == 0) { ctts_set_error("admit: call begin first"); return 1; }
-    // what ctts_gpt_admit_sampling named is for THIS admission only, whether it goes through or fails below: a later admit never picks up a stale entry
-    std::vector<std::pair<int, RowSampling>> named;
-    named.swap(h->knobs_admit);
-    std::vector<std::pair<int, int>> modes;      // ... and what ctts_gpt_admit_modes named
-    modes.swap(h->modes_admit);
-    std::vector<int> share;                      // ... and so is what ctts_gpt_share_prompts named
-    share.swap(h->share_req);
-    const int share_P = h->share_req_P;
-    h->share_req_P = 0;
+    const NextCall req = take_next_call(h);      // for THIS admission only, whether it goes through or fails below
+    const std::vector<int>& share = req.share; const int share_P = req.share_P;
     if (!share.empty() && (int)share.size() != n) { ctts_set_error("admit: ctts_gpt_share_prompts named the prompts of %d sequences, this call seats n=%d", (int)share.size(), n); return 1; }
     if (!share.empty() && h->text_mode) { ctts_set_error("admit: shared prompt passes (ctts_gpt_share_prompts) are code mode only"); return 1; }
     const int P = share.empty() ? n : share_P;   // prompts: mask [P][T], emb [P][T][H]
@@ -2204,10 +2220,8 @@ extern "C" int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, co
     std::vector<int>& seqs = h->seq_host;
     seqs.assign(n, 0);
     h->fresh_host.assign(n, RowState{});
-    for (int i = 0; i < n; ++i) {
-        if (rows[i] < 0 || rows[i] >= h->B) { ctts_set_error("admit: row %d of %d", rows[i], h->B); return 1; }
-        for (int j = 0; j < i; ++j) if (rows[j] == rows[i]) { ctts_set_error("admit: row %d named twice", rows[i]); return 1; }
-        seqs[i] = h->row_seq[rows[i]];
+    if (check_rows(h, "admit", n, rows, true, [&](int i) {
+        seqs[i] = h->rows[rows[i]].seq;
         RowState& r = h->fresh_host[i];
         int lim = row_limits ? row_limits[i] : h->sc.max_new;
         r.limit = lim < 1 ? 1 : (lim > h->sc.max_new ? h->sc.max_new : lim);
@@ -2215,21 +2229,22 @@ extern "C" int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, co
         r.attempt = attempts ? attempts[i] : 0;
         r.out = out_index[i];
         if (r.out < 0) { ctts_set_error("admit: negative output index"); return 1; }
-        for (const auto& e : modes) if (e.first == rows[i]) r.mode = e.second;
+        for (const auto& e : req.modes) if (e.first == rows[i]) r.mode = e.second;
         if (r.mode == 1) {
             if (!h->text_rows_on) { ctts_set_error("admit: row %d is to hold a text utterance (ctts_gpt_admit_modes) but ctts_gpt_enable_text_rows has not been called for this generate state", rows[i]); return 1; }
             if (!share.empty()) { ctts_set_error("admit: shared prompt passes (ctts_gpt_share_prompts) are for code rows; row %d is to hold a text utterance (ctts_gpt_admit_modes)", rows[i]); return 1; }
-            for (const auto& e : named) if (e.first == rows[i]) {
+            for (const auto& e : req.knobs) if (e.first == rows[i]) {
                 ctts_set_error("admit: row %d is to hold a text utterance (ctts_gpt_admit_modes) and carries per-row sampling knobs (ctts_gpt_admit_sampling); text rows keep the values of ctts_gpt_enable_text_rows", rows[i]);
                 return 1;
             }
             if (r.limit > h->sc_text.max_new) r.limit = h->sc_text.max_new;      // the text ids array is [n_out][max_new_text][4]
         }
-    }
+        return 0;
+    })) return 1;
     // the new rows' sampling knobs: what ctts_gpt_admit_sampling named for the row, else the call's values (never the finished utterance's)
     h->knobs_host.assign(n, knobs_of_cfg(h->sc));
     for (int i = 0; i < n; ++i)
-        for (const auto& e : named) if (e.first == rows[i]) h->knobs_host[i] = e.second;
+        for (const auto& e : req.knobs) if (e.first == rows[i]) h->knobs_host[i] = e.second;
     if (!share.empty() && share_plan(h, share, P, seqs.data(), "admit", s)) return 1;
     int* rows_dev = h->keep_dev;
     int* seqs_dev = h->cring;                    // (compaction scratch: consumed in stream order)
@@ -2244,24 +2259,16 @@ extern "C" int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, co
     a.pm = h->meta_pre; a.rope_pre = h->rope_pre; a.dm = h->meta_dec; a.rope_dec = h->rope_dec; a.x_dec = h->x_dec; a.ring = h->hist_ring; a.finend = h->finend;
     a.rope = h->rope; a.st = h->st; a.finish = h->io.finish; a.end_idx = h->io.end_idx; a.share = share.empty() ? nullptr : h->share_dev;
     if (launch_admit_rows(a, s)) return 1;
-    const int R = P * (T - 1);
+    const long R = (long)P * (T - 1);
     if (R > 0) {
-        // prompt rows [n][T-1] <- emb[i][0 .. T-2]
-        CTTS_HIP_CHECK(hipMemcpy2DAsync(h->x_pre, (size_t)(T - 1) * h->H * 4, emb, (size_t)T * h->H * 4, (size_t)(T - 1) * h->H * 4, P, hipMemcpyDeviceToDevice, s));
-        const int keepT = h->pre_T;
-        h->pre_T = T - 1;
-        const int rc = run_layers(h, h->x_pre, h->meta_pre, h->rope_pre, R, DecodePath{1, 0}, nullptr, s);
-        h->pre_T = keepT;
-        if (rc) return 1;
+        // prompt rows [P][T-1] <- emb[i][0 .. T-2]: one pass (R <= pass_rows was checked above), which leaves the "prompt_plan" of the last prefill as it is
+        if (prompt_passes(h, R, T - 1, s, [&](long r0, int m) { return stage_rows_but_last(h, emb, T, r0, m, s); }, no_after)) return 1;
         if (!share.empty() && share_kv(h, T - 1, s)) return 1;      // the followers' lanes <- the leaders' span [0, T - 1)
     }
-    for (int i = 0; i < n; ++i) { h->row_ctx[rows[i]] = T; h->row_cap[rows[i]] = T + h->fresh_host[i].limit; }
-    h->row_mode.resize(h->B, 0);
-    for (int i = 0; i < n; ++i) h->row_mode[rows[i]] = h->fresh_host[i].mode;      // (a row handed to a code utterance stops counting as a text row here)
-    h->text_live = 0;
-    for (int r = 0; r < h->B; ++r) h->text_live += h->row_mode[r];
+    // the rows' records: the lane and the adapter slot (ctts_gpt_admit_adapters) stay, the rest is the new utterance's (a row handed to a code utterance stops counting as a text row here)
+    for (int i = 0; i < n; ++i) { HostRow& r = h->rows[rows[i]]; r.ctx = T; r.cap = T + h->fresh_host[i].limit; r.mode = h->fresh_host[i].mode; }
     h->admitted = true;
-    return 0;
+    return refresh_rows(h);
 }
 
 // Elastic batch (no counterpart in the reference): n dead rows behind the decode batch, for the ctts_gpt_admit that follows.  A dead row runs through the layers
@@ -2276,15 +2283,11 @@ extern "C" int ctts_gpt_grow(ctts_gpt* h, int n, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     const int B = h->B;
     bool used[CTTS_MAX_B] = {};
-    for (int r = 0; r < B; ++r) used[h->row_seq[r]] = true;
-    h->row_seq.resize(B + n); h->row_ctx.resize(B + n); h->row_cap.resize(B + n);
-    h->row_mode.resize(B); h->row_mode.resize(B + n, 0);      // dead rows are code rows
+    for (const HostRow& r : h->rows) used[r.seq] = true;
     h->seq_host.assign(n, 0);
     for (int i = 0, lane = 0; i < n; ++i, ++lane) {
         while (used[lane]) ++lane;               // (B + n <= max_batch and the rows' lanes are distinct: n free lanes exist below max_batch)
         h->seq_host[i] = lane;
-        h->row_seq[B + i] = lane; h->row_ctx[B + i] = 1; h->row_cap[B + i] = 1;      // parked on slot 0
-        h->lora_row_slots[B + i] = -1;
         if (!h->lora_slot_host.empty()) h->lora_slot_host[lane] = -1;
     }
     if (!h->lora_slot_host.empty() && h->lora_slot_of_seq)
@@ -2297,9 +2300,10 @@ extern "C" int ctts_gpt_grow(ctts_gpt* h, int n, void* stream) {
     a.dm = h->meta_dec; a.rope_dec = h->rope_dec; a.x_dec = h->x_dec; a.ring = h->hist_ring; a.finend = h->finend;
     a.knobs = h->knobs; a.call_knobs = h->cknobs; a.rope = h->rope; a.st = h->st;
     if (launch_grow_rows(a, s)) return 1;
+    for (int i = 0; i < n; ++i) h->rows.push_back(HostRow{h->seq_host[i], 1, 1, 0, -1});      // parked on slot 0 of its lane; a dead row is a code row without an adapter
     h->B = B + n;
     h->admitted = true;                          // x_last / meta_dec0 no longer describe the rows: no ctts_gpt_restart
-    return 0;
+    return refresh_rows(h);
 }
 
 // Ends the utterances in `rows` where they stand (a client went away): the rows become ordinary finished rows -- they write nothing more, rows_enqueue reports
@@ -2307,12 +2311,7 @@ extern "C" int ctts_gpt_grow(ctts_gpt* h, int n, void* stream) {
 extern "C" int ctts_gpt_cancel(ctts_gpt* h, int n, const int32_t* rows, void* stream) {
     if (!h || h->B == 0) { ctts_set_error("cancel: no generate state (call ctts_gpt_begin first)"); return 1; }
     if (n < 1 || !rows) { ctts_set_error("cancel: n=%d rows / null argument", n); return 1; }
-    bool named[CTTS_MAX_B] = {};
-    for (int i = 0; i < n; ++i) {
-        if (rows[i] < 0 || rows[i] >= h->B) { ctts_set_error("cancel: row %d of %d", rows[i], h->B); return 1; }
-        if (named[rows[i]]) { ctts_set_error("cancel: row %d named twice", rows[i]); return 1; }
-        named[rows[i]] = true;
-    }
+    if (check_rows(h, "cancel", n, rows, true)) return 1;
     CTTS_RANGE("ctts_gpt_cancel");
     hipStream_t s = (hipStream_t)stream;
     h->keep_host.assign(rows, rows + n);
