@@ -5,11 +5,8 @@
 #define PL_GEMV_BLOCKS 192                 // workgroups that own weight slices
 #define PL_ATT_BLOCKS 64                   // workgroups that own one (row, head) of the attention
 #define PL_BLOCKS (PL_GEMV_BLOCKS + PL_ATT_BLOCKS)
-#ifndef PL_EW_ONE_ROW
-#define PL_EW_ONE_ROW 4                    // edge waves per workgroup at ONE row (A/B builds: tools/build_variant.sh ew2 -DPL_EW_ONE_ROW=2).  ms/step at batch 1, same box,
-#endif                                     //   2 / 4 edge waves: 0.2781 / 0.2685, 0.2784 / 0.2705 (round 5); at 2-4 rows four waves also removed every spill
-#define PL_EDGE_WAVES(R) ((R) == 1 ? PL_EW_ONE_ROW : 4)
-#define PL_THREADS(R) ((8 + PL_EDGE_WAVES(R)) * 64)        // 8 compute waves + 4 edge waves (round 4: 2)
+#define PL_EDGE_WAVES 4                    // edge waves per workgroup, at every row count (two until round 5: DESIGN section 5)
+#define PL_THREADS ((8 + PL_EDGE_WAVES) * 64)              // 8 compute waves + 4 edge waves
 #define PL_THREADS_MAX 768
 #define PL_H 768
 #define PL_I 3072
@@ -67,13 +64,13 @@ struct PersistArgs {
     const int* done;                // DevState.all_done
     unsigned long long* ts;         // diagnostics: [256][10] wall_clock64 marks per workgroup (last layer), or null
     float eps;
-    int sched;                      // weight request schedule of the compute waves (persist_layer.hip: 1 or 2)
+    int sched;                      // weight request schedule of the compute waves (persist_layer.hip: 1, 2 or 3 = paced)
     int pace;                       // SCHED 3: s_sleep(2) units (~128 cycles each) between two paced weight requests of a compute wave
     int delay_act, delay_x, nap_qkv;   // (x1 edge: delay; act edge: delay_act; layer-output edge: delay_x; poll interval of the attention workgroups' q|k|v sweep)
     int delay_att, delay;           // ~128-cycle units an edge wave sleeps before it starts polling the attention edge / the other edges (the data cannot be there yet)
     int nap;                        // ~128-cycle units between two poll passes of a GEMV edge wave
     int fault;                      // test hook: > 0 = one workgroup withholds a hand-off in layer fault - 1 (the give-up path must end the step, not hang it)
-    int poll;                       // bit 0: watch one sentinel granule per producer before the full sweep of an edge
+    int poll;                       // option "persistent_poll": not read by the kernels (the sentinel watch went with the two-edge-wave workgroups); the field keeps the argument offsets
     // per-utterance LoRA adapters inside the launch (round 6; the LORA kernels, paced schedule): row r adds scale * B (A h) of adapter slot lslots[r] to q / k / v / o_proj
     int lora;                       // 1: some decode row carries an adapter
     int delay_u;                    //   ~128-cycle units an edge wave sleeps before it polls the u granules (they are published ~0.4 us after the gather completes)

@@ -27,6 +27,7 @@
 // a per-device file lock keeps other processes off the mode, and decode calls of one process that launch persistent kernels take turns (gpt_engine.hip PersistTurn).
 #include "kernels.h"
 #include "persist.h"
+#include <utility>
 
 typedef unsigned long long u64;
 
@@ -40,6 +41,16 @@ typedef unsigned long long u64;
 typedef __attribute__((address_space(3))) int pl_lds_int;
 #define PL_ABORT_GET(p_) __hip_atomic_load((pl_lds_int*)(p_), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
 #define PL_ABORT_SET(p_) __hip_atomic_store((pl_lds_int*)(p_), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+// The end of every poll pass that did not find its granules.  Give up after PL_SPIN_LIMIT passes, on the workgroup's flag, or (looked at every 1024 passes) on the engine's
+// error word: lane 0 of the wave reports `code_` (the first report stays), raises the workgroup's flag, and the wave leaves through `exit_`.  Statements in the poll
+// loop's own scope, not an inline function: as a function (five forms tried), and even as a block of its own, every instantiation compiles to different code.
+#define PL_SPIN_GIVEUP(spins_, err_, code_, abort_s_, exit_) \
+        bool giveup_ = (spins_) >= PL_SPIN_LIMIT || PL_ABORT_GET(abort_s_) != 0; \
+        if (!giveup_ && ((spins_) & 1023u) == 1023u) giveup_ = __hip_atomic_load(err_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0; \
+        if (giveup_) { \
+            if ((threadIdx.x & 63) == 0) { atomicCAS(err_, 0, code_); PL_ABORT_SET(abort_s_); } \
+            exit_; \
+        }
 __device__ inline void store_granule(u64* g, unsigned tag, float v) {
     __hip_atomic_store(g, ((u64)tag << 32) | (u64)__builtin_bit_cast(unsigned, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -62,12 +73,7 @@ __device__ inline bool sweep(const u64* base, unsigned lane_elem, OffFn off, uns
             ok = ok && ((unsigned)(x >> 32) == tag);
         }
         if (__all(ok)) return true;
-        bool giveup = spins >= PL_SPIN_LIMIT || PL_ABORT_GET(abort_s) != 0;
-        if (!giveup && (spins & 1023u) == 1023u) giveup = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-        if (giveup) {
-            if ((threadIdx.x & 63) == 0) { atomicCAS(err, 0, code); PL_ABORT_SET(abort_s); }
-            return false;
-        }
+        PL_SPIN_GIVEUP(spins, err, code, abort_s, return false)
         for (int z = 0; z < nap; ++z) __builtin_amdgcn_s_sleep(2);
     }
 }
@@ -92,12 +98,7 @@ __device__ inline bool sweep_buf(const u64* base, unsigned n_granules, unsigned 
             ok = ok && (x[1] == tag);
         }
         if (__all(ok)) return true;
-        bool giveup = spins >= PL_SPIN_LIMIT || PL_ABORT_GET(abort_s) != 0;
-        if (!giveup && (spins & 1023u) == 1023u) giveup = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-        if (giveup) {
-            if ((threadIdx.x & 63) == 0) { atomicCAS(err, 0, code); PL_ABORT_SET(abort_s); }
-            return false;
-        }
+        PL_SPIN_GIVEUP(spins, err, code, abort_s, return false)
         for (int z = 0; z < nap; ++z) __builtin_amdgcn_s_sleep(2);
     }
 }
@@ -109,16 +110,13 @@ __device__ inline bool sweep_buf(const u64* base, unsigned n_granules, unsigned 
     ((R >= PL_BUF_MIN_R) ? sweep_buf<N_>(base_, (unsigned)(count_), lane_elem_, off_, tag_, v_, a.error, code_, abort_s, a.nap) \
                        : sweep<N_>(base_, lane_elem_, off_, tag_, v_, a.error, code_, abort_s, a.nap))
 
-// ---- 16-byte act granules (round 6, PL_ACT16).  The act edge is the fattest gather of a layer: every GEMV workgroup needs all 3072 R SwiGLU outputs, as 8-byte
+// ---- 16-byte act granules (round 6; up to PL_A16_MAXR rows).  The act edge is the fattest gather of a layer: every GEMV workgroup needs all 3072 R SwiGLU outputs, as 8-byte
 // {tag, value} granules that is 12 R loads per edge lane and 24.6 KB R per workgroup and layer (4.7 MB R across the chip per poll pass).  Here a producer workgroup
 // packs its 16 outputs of a row into SIX 16-byte granules {v0, v1, v2, check} (the sixth holds one value and two zeros), check = tag + bits(v0) + bits(v1) + bits(v2):
 // 4.5 R loads per lane, 18.4 KB R per workgroup.  Nothing in the ISA promises that a lane's 16-byte store is seen whole by another CU, so the tag is not a
 // plain word: a reader accepts a granule only if check - bits(v0) - bits(v1) - bits(v2) == tag, which a mix of two generations fails (unless the mixed-in words are
 // equal anyway); tools/mb/tear16.hip measures how often that would matter on this chip.  Layout: g_act16[(row * 192 + producer) * 6 + slot], i.e. granule f of the flat
 // array holds columns 16 (f / 6) + 3 (f % 6) + {0, 1, 2} of the [R][3072] act rows -- edge lane e reads f = e + NE k, consecutive lanes consecutive granules.
-#ifndef PL_ACT16
-#define PL_ACT16 1
-#endif
 #define PL_A16_SLOTS 6
 #ifndef PL_A16_MAXR
 #define PL_A16_MAXR PL_MAXR_ONE
@@ -149,12 +147,7 @@ __device__ __forceinline__ bool sweep16(const void* base, unsigned total, unsign
             else ok = ok && (x[3] - x[0] - x[1] - x[2] == tag);
         }
         if (__all(ok)) return true;
-        bool giveup = spins >= PL_SPIN_LIMIT || PL_ABORT_GET(abort_s) != 0;
-        if (!giveup && (spins & 1023u) == 1023u) giveup = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-        if (giveup) {
-            if ((threadIdx.x & 63) == 0) { atomicCAS(err, 0, code); PL_ABORT_SET(abort_s); }
-            return false;
-        }
+        PL_SPIN_GIVEUP(spins, err, code, abort_s, return false)
         for (int z = 0; z < nap; ++z) __builtin_amdgcn_s_sleep(2);
     }
 }
@@ -177,24 +170,6 @@ __device__ __forceinline__ void act16_chunk(const void* g_act, int e, unsigned t
             d[0] = __builtin_bit_cast(float, w0);
             if (s < 5) { d[1] = __builtin_bit_cast(float, w1); d[2] = __builtin_bit_cast(float, w2); }
         }
-    }
-}
-
-// Before a wave sweeps ALL its granules of an edge it watches one "sentinel" granule per producer workgroup that feeds it (the last one that producer
-// stores): 96 eight-byte loads per pass instead of up to 3072.  A hint only -- stores of different lanes land in any order -- the sweep that follows checks
-// every tag; bounded, silent (the sweep reports).
-template <typename OffFn>
-__device__ inline void watch_sentinels(const u64* base, OffFn off, int n, unsigned tag, int lane, int* abort_s) {
-    const u64* p0 = base + ((lane < n) ? off(lane) : 0);
-    const u64* p1 = base + ((lane + 64 < n) ? off(lane + 64) : 0);
-    asm volatile("" : "+v"(p0), "+v"(p1));
-#pragma unroll 1
-    for (unsigned spins = 0; spins < 8192u; ++spins) {
-        bool ok = true;
-        if (lane < n) ok = (unsigned)(__hip_atomic_load(p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 32) == tag;
-        if (lane + 64 < n) ok = ok && ((unsigned)(__hip_atomic_load(p1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 32) == tag);
-        if (__all(ok) || PL_ABORT_GET(abort_s) != 0) return;
-        __builtin_amdgcn_s_sleep(2);
     }
 }
 
@@ -248,55 +223,35 @@ template <int CTRL, int C> __device__ inline void pl_rs_step(float* v, bool f) {
         }
     } else v[0] += dpp_f<CTRL>(v[0]);
 }
-// ---- phase trim (SCHED 3): links of a phase's serial chain that the result needs but the path "gather complete -> granule published" does not.  Each has its own
-// switch for A/B builds (tools/build_variant.sh NAME -DPL_...=0); none changes an operand or the order of an addition.
-//   PL_EARLY_ARRIVE: an edge wave announces its gather (xs written) BEFORE it reduces the rows' sums of squares: the compute waves need xs, only the epilogue needs ssq
-//                    (R wave_sums of ~45 dependent instructions each leave the path in front of q|k|v, gate|up and the heads).
-//   PL_RS_EARLY:     the epilogue lanes compute the norm factor 1 / sqrtf(ssq / 768 + eps) while the compute waves multiply instead of behind B2: the edge waves count
-//                    their finished ssq rows in a second LDS counter (abort_s[2]) and the waves that own epilogue lanes wait for it (bounded, honours the give-up flag).
-//   PL_BAR_WAKE:     B1 ends in the hardware barrier for all waves of the workgroup (edge waves right behind their arrive, compute waves once their paced requests
-//                    are out) instead of a sleep-and-poll of the counter by every compute wave; the counter stays as the pacing loop's early exit.
-//   PL_A16_DPP:      the two neighbours a 16-byte act granule collects come through DPP row shifts (a decode row's 16 lanes are one DPP row) instead of ds_bpermute.
-// The LORA kernels keep the old order for the first two: their compute waves 6 / 7 read ssq in phase A (the normalised input of u = A h), i.e. ssq is on THEIR path.
-// The first two apply to the ONE-row kernels only (PL_TRIM_NORM_MAXR).  The rows' sums of squares are written `ssp += v * v`, which hipcc contracts to FMAs; in
+// ---- phase trim (SCHED 3): links of a phase's serial chain that the result needs but the path "gather complete -> granule published" does not.  None changes an
+// operand or the order of an addition (measurements and the arms that lost: DESIGN section 5).
+//   * ONE-row kernels without adapters (EARLY: R <= PL_TRIM_NORM_MAXR): an edge wave announces its gather (xs written) BEFORE it reduces the rows' sums of squares:
+//     the compute waves need xs, only the epilogue needs ssq (R wave_sums of ~45 dependent instructions each leave the path in front of q|k|v, gate|up and the heads).
+//   * B1 ends in the hardware barrier for all waves of the workgroup (edge waves right behind their arrive, compute waves once their paced requests are out): a phase
+//     starts when the last edge wave is done, not when the last of eight pollers notices.  The arrive counter stays as the pacing loop's early exit.
+//   * The two neighbours a 16-byte act granule collects come through DPP row shifts (a decode row's 16 lanes are one DPP row), not ds_bpermute.
+// The LORA kernels announce behind the sums: their compute waves 6 / 7 read ssq in phase A (the normalised input of u = A h), i.e. ssq is on THEIR path.
+// Why one row only: the rows' sums of squares are written `ssp += v * v`, which hipcc contracts to FMAs; in
 // `v0 * v0 + v1 * v1` either product may become the FMA's addend, and which one hipcc picks per row and gather changed as soon as the code around the gather moved:
-// with both items on, the 2-, 5-, 6- and 8-row kernels (fp32 and fp16) produced hiddens an ulp-level rounding away from the previous build's (token ids
-// unchanged; tests/test_gpu_persist_phase_trim.py), and six of them reserved a 36-byte private segment for a spill slot nothing uses.  The one-row kernels compile to
-// the same sums.  (Pinning the association with __fmul_rn / fmaf would end the dependence, but not on the bits every instantiation produces today.)
-#ifndef PL_EARLY_ARRIVE
-#define PL_EARLY_ARRIVE 1
-#endif
-#ifndef PL_RS_EARLY
-#define PL_RS_EARLY 0                        // OFF: measured beside PL_EARLY_ARRIVE it costs what that one gains (profiles/persist_phase_trim_marks.jsonl): wave 8 then
-#endif                                       //   reduces its sums, waits for the three other waves' and divides in a row -- longer than the one-row q|k|v products it hides behind
+// with the early announcement at every row count, the 2-, 5-, 6- and 8-row kernels (fp32 and fp16) produced hiddens an ulp-level rounding away from the previous build's
+// (token ids unchanged; tests/test_gpu_persist_phase_trim.py), and six of them reserved a 36-byte private segment for a spill slot nothing uses.  The one-row kernels
+// compile to the same sums.  (Pinning the association with __fmul_rn / fmaf would end the dependence, but not on the bits every instantiation produces today.)
 #ifndef PL_TRIM_NORM_MAXR
-#define PL_TRIM_NORM_MAXR 1                  // rows up to which the first two apply (above: from 2 rows on they do not leave the outputs bit-identical)
+#define PL_TRIM_NORM_MAXR 1                  // rows up to which an edge wave announces its gather before its norm sums (above: from 2 rows on the outputs do not stay bit-identical)
 #endif
-#ifndef PL_BAR_WAKE
-#define PL_BAR_WAKE 1
-#endif
-#ifndef PL_A16_DPP
-#define PL_A16_DPP 1
-#endif
-// ---- attention trim: the same for the attention workgroups' path "q gathered -> granule published" (switches as above; outputs bit-identical).
-//   PL_KV_AFTER_PUBLISH: the compute waves request the next layer's cached K / V rows behind a third barrier (B3) that wave 8 joins right behind its last hand-off
-//                        of the layer (the g_att store; a split s > 0: its g_part stores; split 0 first finishes its gather of the partials), not at B2: the ~160 KB
-//                        burst no longer sits in the CU's memory queue in front of the publish store and the partials' polls.
+// ---- attention trim: the same for the attention workgroups' path "q gathered -> granule published" (outputs bit-identical).
+//   The compute waves request the next layer's cached K / V rows behind a third barrier (B3) that wave 8 joins right behind its last hand-off of the layer (the g_att
+//   store; a split s > 0: its g_part stores; split 0 first finishes its gather of the partials), not at B2: the ~160 KB burst no longer sits in the CU's memory queue
+//   in front of the publish store and the partials' polls.
 // (Two more links were built, measured and removed, DESIGN section 5: wave 8 forming the rescale factors from early-stored wave maxima beside the exp / PV pass -- an LDS
 //  counter, a bounded wait and a second code path around B2 for no gain alone on any command line --, and the weights' cross-lane sum in front of the PV FMAs -- the
 //  scheduler keeps the 20-instruction sum in one piece in front of the four packed FMAs of an iteration, and its register takes the fp16 6- and 7-row kernels to 129.)
-#ifndef PL_KV_AFTER_PUBLISH
-#define PL_KV_AFTER_PUBLISH 1
-#endif
 #define PL_DPP_ROW_SHL(n_) (0x100 + (n_))    // lane i of a 16-lane row reads lane i + n; lanes past the row read 0 (bound_ctrl)
 __device__ inline float pl_row_shl1(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), PL_DPP_ROW_SHL(1), 0xF, 0xF, true)); }
 __device__ inline float pl_row_shl2(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), PL_DPP_ROW_SHL(2), 0xF, 0xF, true)); }
 #define PL_FRONT_BYTES 4096                 // 16 + (384 + 512 + 16 + 16) * 4 = 3728, rounded
-#ifndef PL_TAIL_ALL
-#define PL_TAIL_ALL 1
-#endif
 #ifndef PL_TAIL_IT
-#define PL_TAIL_IT 4                        // 6..8 rows: iterations of 8 keys per compute wave that wait in LDS (4 KB each) -- 4 x 8 x 4 = 128 keys per item behind the 192 in registers
+#define PL_TAIL_IT 4                        // iterations of 8 keys per compute wave that wait in LDS (4 KB each) -- 4 x 8 x 4 = 128 keys per item behind the 192 in registers
 #endif
 #define PL_RED_FLOATS (8 * 32 * 4)          // [compute wave][value < 32][16-lane row]: two groups of <= 16 values per wave (gate|up: pair 0 | pair 1)
 template <int P> __device__ inline void pl_reduce_store(float (&v)[P], float* red, int wave, int lane, int base = 0) {
@@ -364,12 +319,7 @@ __device__ inline bool sweep_masked(const u64* base, unsigned lane_elem, bool va
             }
         }
         if (__all(ok)) return true;
-        bool giveup = spins >= PL_SPIN_LIMIT || PL_ABORT_GET(abort_s) != 0;
-        if (!giveup && (spins & 1023u) == 1023u) giveup = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-        if (giveup) {
-            if ((threadIdx.x & 63) == 0) { atomicCAS(err, 0, code); PL_ABORT_SET(abort_s); }
-            return false;
-        }
+        PL_SPIN_GIVEUP(spins, err, code, abort_s, return false)
         for (int z = 0; z < nap; ++z) __builtin_amdgcn_s_sleep(2);
     }
 }
@@ -383,18 +333,16 @@ __device__ inline bool sweep_masked(const u64* base, unsigned lane_elem, bool va
 template <int R, int SCHED, typename WT, bool LORA = false>
 __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs a) {
     static_assert(!LORA || SCHED == 3, "per-utterance adapters: the paced schedule only");
-    constexpr bool EARLY = PL_EARLY_ARRIVE != 0 && SCHED == 3 && !LORA && R <= PL_TRIM_NORM_MAXR;      // (phase trim, above)
-    constexpr bool RSE = PL_RS_EARLY != 0 && SCHED == 3 && !LORA && R <= PL_TRIM_NORM_MAXR;
-    constexpr bool BARW = PL_BAR_WAKE != 0 && SCHED == 3;
+    constexpr bool EARLY = SCHED == 3 && !LORA && R <= PL_TRIM_NORM_MAXR;      // an edge wave announces its gather before its norm sums (phase trim, above)
     typedef typename PlW<WT>::frag wfrag;
-    // Edge waves per workgroup: 2 at one row, 4 at 2..4 rows (round 5).  A gather is 768 R (3072 R for the act rows) granules over the edge lanes; with two waves the
-    // per-lane share grew with the rows (6 R and 24 R loads per lane, the act rows one sweep after the other) -- +4.3 us of the +9.2 us per layer between 1 and 4 rows.
-    constexpr bool A16 = PL_ACT16 != 0 && R <= PL_A16_MAXR;      // 16-byte act granules (measured: -1.5 % per step at 1..5 rows, +1 % / +4.5 % at 6 / 8 rows)
-    constexpr int EW = PL_EDGE_WAVES(R), NE = 64 * EW, GX = 768 / NE;      // edge lanes; granules per lane and row of a 768-wide gather (6 or 3)
+    // Four edge waves per workgroup.  A gather is 768 R (3072 R for the act rows) granules over the edge lanes; with two waves (round 4) the per-lane share grew
+    // with the rows (6 R and 24 R loads per lane, the act rows one sweep after the other) -- +4.3 us of the +9.2 us per layer between 1 and 4 rows.
+    constexpr bool A16 = R <= PL_A16_MAXR;      // 16-byte act granules (measured: -1.5 % per step at 1..5 rows, +1 % / +4.5 % at 6 / 8 rows)
+    constexpr int EW = PL_EDGE_WAVES, NE = 64 * EW, GX = 768 / NE;      // edge lanes; granules per lane and row of a 768-wide gather (3)
     constexpr size_t BLOCK_BYTES = (size_t)PL_BLOCK_BYTES / 4 * sizeof(WT), LAYER_BYTES = PL_LAYER_BYTES / 4 * sizeof(WT);
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // LDS: [front block: give-up flag + the attention workgroups' scratch][GEMV workgroups: xs | red | ssq | xres   /   attention workgroups of the 6..8-row kernels: the K / V tail]
-    int* const abort_s = (int*)smem;                      // [4]: [0] give-up flag, [1] SCHED 3: gathers completed by the edge waves (EW per phase), [2] PL_RS_EARLY: ssq rows complete (EW per norm)
+    // LDS: [front block: give-up flag + the attention workgroups' scratch][GEMV workgroups: xs | red | ssq | xres   /   attention workgroups: the K / V tail]
+    int* const abort_s = (int*)smem;                      // [4]: [0] give-up flag, [1] SCHED 3: gathers completed by the edge waves (EW per phase), [2], [3] unused ([2] stays zeroed: see DESIGN section 5)
     float* const att_s = (float*)(abort_s + 4);           // attention workgroups: q[2][64] | k_new[2][64] | v_new[2][64] | the waves' outputs [8][64], maxima [8], sums [8]
     float* const xs = (float*)(smem + PL_FRONT_BYTES);    // activations of the current phase [R][768] ([R][3072] for the down projection)
     float* const red = xs + R * PL_I;                     // compute waves' results [8 waves][16 values][4 rows of 16 lanes] (pl_reduce_store / pl_red)
@@ -411,6 +359,8 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
     unsigned long long t_mark[10];
 #define PL_MARK(i) do { if (a.ts != nullptr) t_mark[i] = wall_clock64(); } while (0)
     PL_MARK(0);
+    // a row's norm factor from the four edge waves' shares of its sum of squares (llama.py:82-87; the weight is folded into W's columns)
+#define PL_RS(r_) (1.0f / sqrtf(((ssq[r_] + ssq[R + (r_)]) + (ssq[2 * R + (r_)] + ssq[3 * R + (r_)])) / (float)PL_H + a.eps))
     if (tid == 0) { abort_s[0] = 0; abort_s[1] = 0; abort_s[2] = 0; }
 
     if (b < PL_GEMV_BLOCKS) {
@@ -479,10 +429,9 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                 const int pace = a.pace;                      // x 128 cycles between two requests of a wave
 #define PL_PACE_BEGIN() const int tgt_ = EW * (++phase); bool ready_ = __hip_atomic_load(arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= tgt_
 #define PL_PIECE(stmt_) do { stmt_; if (!ready_) { for (int z_ = 0; z_ < pace; ++z_) __builtin_amdgcn_s_sleep(2); ready_ = __hip_atomic_load(arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= tgt_; } } while (0)
-                // B1: (PL_BAR_WAKE) the hardware barrier of all waves -- the edge waves join it right behind their arrive, so a phase starts when the last edge wave is
+                // B1: the hardware barrier of all waves -- the edge waves join it right behind their arrive, so a phase starts when the last edge wave is
                 // done, not when the last of eight pollers notices; only LDS is waited for (the weight requests stay in flight: no vmcnt)
-#define PL_PACE_END() do { if constexpr (BARW) { (void)ready_; asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); } \
-        else { while (!ready_) { __builtin_amdgcn_s_sleep(1); ready_ = __hip_atomic_load(arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= tgt_; } asm volatile("" ::: "memory"); } } while (0)
+#define PL_PACE_END() do { (void)ready_; asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); } while (0)
                 for (int l = 0; l < NL; ++l) {
                     const char* const wn = wb + LAYER_BYTES;
                     const bool more = l + 1 < NL;
@@ -501,7 +450,7 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
 #pragma unroll
                             for (int j = 0; j < 3; ++j) acc = dot4(lr.qa(q_w, j), ((const f32x4*)(xs + lq_r * PL_H))[64 * j + lane], acc);
                             acc = wave_sum(acc);
-                            const float rs = 1.0f / sqrtf((EW == 2 ? ssq[lq_r] + ssq[R + lq_r] : (ssq[lq_r] + ssq[R + lq_r]) + (ssq[2 * R + lq_r] + ssq[3 * R + lq_r])) / (float)PL_H + a.eps);
+                            const float rs = PL_RS(lq_r);
                             if (lane == 0) store_granule(a.g_u + lq_r * 64 + lq_tk, tag0c + (unsigned)l, (acc * rs) * lq_scale);
                         }
 #pragma unroll
@@ -565,11 +514,7 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                         for (int j = 0; j < 6; ++j) PL_PIECE(d_w[j] = __builtin_nontemporal_load((const wfrag*)wb + od + j * 64));
                         PL_PACE_END();
                     }
-#ifdef PL_EXP_E2
-                    if constexpr (R == 5) {
-#else
                     if constexpr (R >= 5) {
-#endif
                         // (register allocation, measured: at 5 rows this form compiles without spills and the one below with 27-55; at 4 rows it is the other way round)
                         float pv[2][pl_pow2(2 * R)];
 #pragma unroll
@@ -781,20 +726,10 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
             // ------------------------------------------------ edge wave: gathers, epilogues, publishing
 #define PL_B1() do { if (SCHED == 3) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
         if (lane == 0) __hip_atomic_fetch_add((__attribute__((address_space(3))) int*)(abort_s + 1), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
-        if constexpr (BARW) asm volatile("s_barrier" ::: "memory"); } \
+        asm volatile("s_barrier" ::: "memory"); } \
         else __syncthreads(); } while (0)
-            // the norm sums of a gathered [R][768]: this wave's share of every row's sum of squares -> ssq[ew][r]; PL_RS_EARLY: counted, so that the epilogue lanes
-            // can form the norm factor before B2 (PL_SSQ_WAIT: bounded; a give-up elsewhere in the workgroup ends it)
-            typedef __attribute__((address_space(3))) int pl_lds_cnt;
-#define PL_SSQ_COUNT() do { if constexpr (RSE) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-        if (lane == 0) __hip_atomic_fetch_add((pl_lds_cnt*)(abort_s + 2), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); } } while (0)
-#define PL_SSQ_STORE() do { _Pragma("unroll") for (int r = 0; r < R; ++r) { const float s_ = wave_sum(ssp[r]); if (lane == 0) ssq[ew * R + r] = s_; } PL_SSQ_COUNT(); } while (0)
-#define PL_SSQ_WAIT(code_, norms_) do { const int t2_ = EW * (norms_);      /* norms gathered so far: two per layer (x, x + attention) + the heads' */ \
-        for (unsigned sp_ = 0; __hip_atomic_load((pl_lds_cnt*)(abort_s + 2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < t2_; ++sp_) { \
-            if (sp_ >= PL_SPIN_LIMIT || PL_ABORT_GET(abort_s) != 0) { if (lane == 0) { atomicCAS(a.error, 0, code_); PL_ABORT_SET(abort_s); } break; } \
-            __builtin_amdgcn_s_sleep(1); } \
-        asm volatile("" ::: "memory"); } while (0)
-#define PL_RS(r_) (1.0f / sqrtf((EW == 2 ? ssq[r_] + ssq[R + (r_)] : (ssq[r_] + ssq[R + (r_)]) + (ssq[2 * R + (r_)] + ssq[3 * R + (r_)])) / (float)PL_H + a.eps))
+            // the norm sums of a gathered [R][768]: this wave's share of every row's sum of squares -> ssq[ew][r]
+#define PL_SSQ_STORE() do { _Pragma("unroll") for (int r = 0; r < R; ++r) { const float s_ = wave_sum(ssp[r]); if (lane == 0) ssq[ew * R + r] = s_; } } while (0)
 
             const int ew = wave - 8, e = ew * 64 + lane;      // 0..127
             const int hh = b >> 4, jj = b & 15;               // q | k | v rows of this workgroup: head hh, dims (2jj, 2jj+1, +32) / v dims 4jj..4jj+3
@@ -843,7 +778,6 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                 }
             }
             __syncthreads();                                  // S0
-            if constexpr (!EARLY) PL_SSQ_COUNT();             // (counted behind S0: thread 0 zeroes the counter in front of it)
             PL_MARK(1);
             const size_t kv_per = a.kv_per;                   // floats between K and V of a layer (and half the distance between layers)
             for (int l = 0; l < NL; ++l) {
@@ -852,8 +786,6 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                 if (l > 0) {
                     // ---- edge 1: the previous layer's output, published by the 192 GEMV workgroups -> xs, sums of squares
                     for (int z = 0; z < a.delay_x; ++z) __builtin_amdgcn_s_sleep(2);
-                    // (producers of this wave's columns e + 128 k: workgroups 16 (2 m + ew) + t; each stores its 4 columns of every row in one instruction)
-                    if (EW == 2 && (a.poll & 1)) watch_sentinels(a.g_x, [ew](int i) { return (R - 1) * PL_H + 4 * (16 * (2 * (i >> 4) + ew) + (i & 15)) + 3; }, 96, tag - 1u, lane, abort_s);
                     float v[GX * R];
                     const bool got = PL_SWEEP(GX * R, a.g_x, PL_G_X, (unsigned)e, [](int k) { return (k / GX) * PL_H + NE * (k % GX); }, tag - 1u, v, 1);
                     (void)got;
@@ -878,11 +810,6 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                     if (last) PL_MARK(2);
                     PL_B1();                                  // B1(A): the gather is in LDS
                 }
-                float rsA = 0.f;                              // PL_RS_EARLY: the norm factor, formed while the compute waves multiply
-                if constexpr (RSE) if (ew * 64 < 6 * R) {
-                    PL_SSQ_WAIT(1, 2 * l + 1);
-                    if (doA) rsA = PL_RS(rA);
-                }
                 float lda = 0.f, ldb = 0.f;                   // LORA: this lane's two rows' scale * B (A h) (pipeline:420-432, per row)
                 float uq[LORA ? 16 : 1];
                 const int slA = (LORA && doA) ? pl_slot(a.lslots, rA) : -1;
@@ -900,7 +827,7 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                     }
                 }
                 if (doA) {
-                    const float rs = RSE ? rsA : PL_RS(rA);          // llama.py:82-87 (the weight is folded into W's columns)
+                    const float rs = PL_RS(rA);
                     const float va = pl_red(red, pwA, rA) * rs + lda, vb = pl_red(red, pwA, R + rA) * rs + ldb;
                     float ya = va, yb = vb;
                     int which, dA, dB;
@@ -923,8 +850,6 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                 // ---- phase C: attention output -> o_proj + residual
                 for (int z = 0; z < a.delay_att; ++z) __builtin_amdgcn_s_sleep(2);      // the attention cannot have published yet: do not poll into the weight stream
                 {
-                    // (this wave's columns belong to the heads 2 m + ew: one sentinel per (row, head))
-                    if (EW == 2 && (a.poll & 1)) watch_sentinels(a.g_att, [ew](int i) { return (i / 6) * PL_H + 64 * (2 * (i % 6) + ew) + 63; }, 6 * R, tag, lane, abort_s);
                     float v[GX * R];
                     const bool got = PL_SWEEP(GX * R, a.g_att, PL_G_ATT, (unsigned)e, [](int k) { return (k / GX) * PL_H + NE * (k % GX); }, tag, v, 3);
                     (void)got;
@@ -960,7 +885,6 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                 // ---- phase D: x + attention -> RMSNorm, gate | up, SiLU * up
                 for (int z = 0; z < a.delay; ++z) __builtin_amdgcn_s_sleep(2);
                 {
-                    if (EW == 2 && (a.poll & 1)) watch_sentinels(a.g_x1, [ew](int i) { return (R - 1) * PL_H + 4 * (16 * (2 * (i >> 4) + ew) + (i & 15)) + 3; }, 96, tag, lane, abort_s);
                     float v[GX * R];
                     const bool got = PL_SWEEP(GX * R, a.g_x1, PL_G_X1, (unsigned)e, [](int k) { return (k / GX) * PL_H + NE * (k % GX); }, tag, v, 4);
                     (void)got;
@@ -981,36 +905,30 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                     if (last) PL_MARK(6);
                     PL_B1();                                  // B1(D): the gather is in LDS
                 }
-                float rsD = 0.f;
-                if constexpr (RSE) if (ew * 64 < 16 * R) {
-                    PL_SSQ_WAIT(4, 2 * l + 2);
-                    if (e < 16 * R) rsD = PL_RS(e >> 4);
-                }
                 __syncthreads();                              // B2(D)
                 if constexpr (A16) {
                     float av = 0.f;
                     const int pi = e & 15, r = e >> 4;
                     if (e < 16 * R) {
                         const int w = pi >> 1, p = pi & 1;
-                        const float rs = RSE ? rsD : PL_RS(r);
+                        const float rs = PL_RS(r);
                         const float gv = pl_red(red, w, 16 * p + r) * rs, uv = pl_red(red, w, 16 * p + R + r) * rs;
                         av = (gv / (1.0f + expf(-gv))) * uv;                                                                    // llama.py:214
                     }
                     // the 16 lanes of a decode row: lane pi = 3 s collects (pi, pi + 1, pi + 2) and stores granule s
-                    const float a1 = PL_A16_DPP ? pl_row_shl1(av) : __shfl_down(av, 1), a2 = PL_A16_DPP ? pl_row_shl2(av) : __shfl_down(av, 2);
+                    const float a1 = pl_row_shl1(av), a2 = pl_row_shl2(av);
                     if (e < 16 * R && pi % 3 == 0)
                         store_granule16(a.g_act, PL_GEMV_BLOCKS * PL_A16_SLOTS * R, (unsigned)pl_opq<(R > PL_MAXR_ONE)>((r * PL_GEMV_BLOCKS + b) * PL_A16_SLOTS + pi / 3), tag,
                                         av, (pi + 1 < 16) ? a1 : 0.f, (pi + 2 < 16) ? a2 : 0.f);
                 } else if (e < 16 * R) {
                     const int pi = e & 15, r = e >> 4, w = pi >> 1, p = pi & 1;
-                    const float rs = RSE ? rsD : PL_RS(r);
+                    const float rs = PL_RS(r);
                     const float gv = pl_red(red, w, 16 * p + r) * rs, uv = pl_red(red, w, 16 * p + R + r) * rs;
                     store_granule(a.g_act + (size_t)pl_opq<(R > PL_MAXR_ONE)>(r * PL_I + 16 * b + pi), tag, (gv / (1.0f + expf(-gv))) * uv);       // llama.py:214
                 }
                 if (last) PL_MARK(7);
                 // ---- phase E: silu(gate) * up [R][3072] -> down + residual
                 for (int z = 0; z < a.delay_act; ++z) __builtin_amdgcn_s_sleep(2);
-                // (producers of this wave's columns e + 128 k: workgroups 8 k + 4 ew + t, t < 4; each stores its 16 columns of every row in one instruction)
                 if constexpr (A16) {
                     constexpr int TOT = PL_GEMV_BLOCKS * PL_A16_SLOTS * R, NK = (TOT + NE - 1) / NE;      // granules; per lane
                     constexpr int NC = (NK + PL_A16_CHUNK - 1) / PL_A16_CHUNK, CH = (NK + NC - 1) / NC;       // sweeps; granules per lane and sweep (4 registers each)
@@ -1021,30 +939,7 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                     if constexpr (NC > 4) act16_chunk<4 * CH, NK - 4 * CH, NE, TOT>(a.g_act, e, tag, (__attribute__((address_space(3))) float*)xs, a.error, abort_s, a.nap);
                     static_assert(NC <= 5, "act gather: more chunks");
                 } else {
-                if (EW == 2 && (a.poll & 1)) watch_sentinels(a.g_act, [ew](int i) { return (R - 1) * PL_I + 16 * (8 * (i >> 2) + 4 * ew + (i & 3)) + 15; }, 96, tag, lane, abort_s);
-                if constexpr (EW == 2) {
-#pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        float v[24];
-                        const bool got = sweep<24>(a.g_act, (unsigned)(r * PL_I + e), [](int k) { return 128 * k; }, tag, v, a.error, 5, abort_s, a.nap);
-                        (void)got;
-#pragma unroll
-                        for (int k = 0; k < 24; ++k) xs[r * PL_I + 128 * k + e] = v[k];
-                    }
-                } else {
-                    // four edge waves: 12 granules per lane and row -> two rows per sweep (24 granules in flight per lane, as before), R / 2 round trips instead of R
-#ifdef PL_EXP_E1
-                    if constexpr (R > PL_MAXR_ONE) {
-#pragma unroll
-                        for (int r = 0; r < R; ++r) {
-                            float v[12];
-                            const bool got = PL_SWEEP(12, a.g_act, PL_G_ACT, (unsigned)(r * PL_I + e), [](int k) { return 256 * k; }, tag, v, 5);
-                            (void)got;
-#pragma unroll
-                            for (int k = 0; k < 12; ++k) xs[r * PL_I + 256 * k + e] = v[k];
-                        }
-                    } else
-#endif
+                    // 8-byte granules: 12 per lane and row -> two rows per sweep (24 granules in flight per lane), R / 2 round trips instead of R
 #pragma unroll
                     for (int r = 0; r + 1 < R; r += 2) {
                         float v[24];
@@ -1053,11 +948,7 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
 #pragma unroll
                         for (int k = 0; k < 24; ++k) xs[(r + k / 12) * PL_I + 256 * (k % 12) + e] = v[k];
                     }
-#ifdef PL_EXP_E1
-                    if constexpr ((R & 1) != 0 && R <= PL_MAXR_ONE) {
-#else
                     if constexpr ((R & 1) != 0) {
-#endif
                         constexpr int r = R - 1;
                         float v[12];
                         const bool got = PL_SWEEP(12, a.g_act, PL_G_ACT, (unsigned)(r * PL_I + e), [](int k) { return 256 * k; }, tag, v, 5);
@@ -1065,7 +956,6 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
 #pragma unroll
                         for (int k = 0; k < 12; ++k) xs[r * PL_I + 256 * k + e] = v[k];
                     }
-                }
                 }
                 if (last) PL_MARK(8);
                 PL_B1();                                      // B1(E): the gather is in LDS
@@ -1106,15 +996,10 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                 if constexpr (EARLY) PL_B1();                 // B1(H): announced before the rows' wave sums
                 PL_SSQ_STORE();
                 if constexpr (!EARLY) PL_B1();                // B1(H)
-                float rsH = 0.f;
-                if constexpr (RSE) if (ew * 64 < PL_HEAD_ROWS * R) {
-                    PL_SSQ_WAIT(1, 2 * NL + 1);
-                    if (e < PL_HEAD_ROWS * R) rsH = PL_RS(e / PL_HEAD_ROWS);
-                }
                 __syncthreads();                              // B2(H)
                 if (e < PL_HEAD_ROWS * R) {
                     const int rr = e % PL_HEAD_ROWS, r = e / PL_HEAD_ROWS, col = PL_HEAD_ROWS * b + rr;
-                    const float rs = RSE ? rsH : PL_RS(r);          // llama.py:1002 (the weight is folded into the heads' columns)
+                    const float rs = PL_RS(r);                      // llama.py:1002 (the weight is folded into the heads' columns)
                     if (col < a.n_valid) a.logits[(size_t)r * a.n_valid + col] = pl_red(red, rr >> 1, (rr & 1) * R + r) * rs;
                 }
                 if (e < 4 * R) {
@@ -1122,7 +1007,7 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                     float* const hid_out = ((SamplerDynPtr)a.dyn)->hidden_out;
                     if (hid_out != nullptr && hst.x == 0) {
                         const int i = e & 3, r = e >> 2;
-                        const float rs = 1.0f / sqrtf((EW == 2 ? ssq[r] + ssq[R + r] : (ssq[r] + ssq[R + r]) + (ssq[2 * R + r] + ssq[3 * R + r])) / (float)PL_H + a.eps);
+                        const float rs = PL_RS(r);
                         hid_out[(size_t)hout * ((SamplerDynPtr)a.dyn)->hidden_stride + (size_t)hst.y * PL_H + 4 * b + i] = lnf_v * (xres[4 * r + i] * rs);
                     }
                 }
@@ -1162,8 +1047,7 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
     float* const mm = mo + 512;                               // [8] the waves' maxima
     float* const ml = mm + 8;                                 // [8] the waves' sums
     const size_t kv_per = a.kv_per;
-    // attention trim (above).  B3 exists in every layer but the launch's last, for every wave of the workgroup alike
-    constexpr bool KVP = PL_KV_AFTER_PUBLISH != 0;
+    // B3 (attention trim, above) exists in every layer but the launch's last, for every wave of the workgroup alike
     if (wave < 8) {
         // Round 5 layout: the scores come from K rows held 8 dims per lane (key group = lane / 8, a 3-step DPP sum per key), the output from V rows held ONE DIM PER
         // LANE (8 keys x PRE registers): a key's weight reaches all lanes through v_readlane and the wave's output is one register per lane -- no cross-lane sums of
@@ -1174,12 +1058,12 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
         const int grp = lane >> 3, sub = lane & 7;
         const size_t head_base = ((size_t)m.seq * PL_NH + hh) * a.Lmax * CTTS_HEAD_DIM;
         constexpr int PRE = 6;                                // iterations requested before the query exists: 8 (PAIR: 4) waves x 8 keys x 6 = 384 (192) keys
-        // Round 6, PAIR: NT more iterations per wave wait in LDS.  With two items per workgroup the registers hold 192 keys of an item; at the bench window's context
+        // Round 6: NT more iterations per wave wait in LDS (PAIR: 128 more keys per item; the one-item workgroups of 1..5 rows: 8 waves x 4 x 8 = 256).  With two items per workgroup the registers hold 192 keys of an item; at the bench window's context
         // (~310) the other ~120 streamed BEHIND the query, one dependent HBM round trip per layer (+2.5 us: the 5 -> 6 row step was +24 %).  LDS-DMA (global_load_lds_dwordx4)
         // needs no registers: a lane fetches exactly the 16-byte pieces it will read back itself (K: its 8 dims of its key group; V: rows of 64 floats, read one dim per
         // lane), so the image is lane-linear and every read is conflict-free -- LDS as an asynchronously filled extension of the register file.  The GEMV workgroups' xs
         // block is idle in an attention workgroup: 8 waves x NT x 4 KB.
-        constexpr int NT = (PAIR || PL_TAIL_ALL) ? PL_TAIL_IT : 0, PT = PRE + NT;      // (PL_TAIL_ALL: also the one-item workgroups of 1..5 rows: 8 waves x 4 x 8 = 256 more keys)
+        constexpr int NT = PL_TAIL_IT, PT = PRE + NT;
         constexpr int TB = sizeof(WT) == 4 ? 4096 : 2048;     // bytes of one LDS iteration: K 8 keys x 64 dims | V 8 keys x 64 dims
         typedef __attribute__((address_space(3))) char lds_c;
         typedef __attribute__((address_space(1))) const void* gptr_t;
@@ -1332,7 +1216,7 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
             PL_AMARK(6);
             __syncthreads();                                  // B2
             if (l + 1 < NL) {
-                if constexpr (KVP) __syncthreads();           // B3: wave 8 has issued the layer's last hand-off
+                __syncthreads();                              // B3: wave 8 has issued the layer's last hand-off
                 PL_DMA_KV(l + 1); PL_LOAD_KV(l + 1);          // the next layer's cached rows: a whole layer ahead of its query (B2: every LDS read of this layer is done)
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -1391,10 +1275,7 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                             }
                         }
                         if (__all(okk)) break;
-                        typedef __attribute__((address_space(3))) int lds_i;
-                        bool giveup = spins >= PL_SPIN_LIMIT || __hip_atomic_load((lds_i*)abort_s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0;
-                        if (!giveup && (spins & 1023u) == 1023u) giveup = __hip_atomic_load(a.error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-                        if (giveup) { if (lane == 0) { atomicCAS(a.error, 0, 6); __hip_atomic_store((lds_i*)abort_s, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); } break; }
+                        PL_SPIN_GIVEUP(spins, a.error, 6, abort_s, break)
                         __builtin_amdgcn_s_sleep(2);
                     }
 #pragma unroll
@@ -1410,7 +1291,7 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
                 }
                 store_granule(a.g_att + (size_t)r * PL_H + hh * CTTS_HEAD_DIM + lane, tag, O / L);
             }
-            if constexpr (KVP) { if (l + 1 < NL) __syncthreads(); }      // B3: the layer's last hand-off is issued -- the compute waves request the next layer's cached rows
+            if (l + 1 < NL) __syncthreads();                  // B3: the layer's last hand-off is issued -- the compute waves request the next layer's cached rows
             if (l + 1 == NL && wave == 8) PL_MARK(2);
         }
         if (a.ts != nullptr && lane == 0 && wave == 8) {
@@ -1422,7 +1303,7 @@ __global__ __launch_bounds__(PL_LB) void persist_layer_kernel(const PersistArgs 
         for (int l = 0; l < NL; ++l) {
             __syncthreads();                                  // B1
             __syncthreads();                                  // B2
-            if constexpr (KVP) { if (l + 1 < NL) __syncthreads(); }      // B3
+            if (l + 1 < NL) __syncthreads();                  // B3
         }
     }
 }
@@ -1495,70 +1376,36 @@ int launch_persist_repack(int half_w, const void* qkv, const void* o, const void
 }
 
 static size_t persist_lds_bytes(int R) {
-    const size_t gemv = (size_t)(R * PL_I + PL_RED_FLOATS + 4 * R + 4 * R + 256 * R) * 4, tail = (R > PL_MAXR_ONE || PL_TAIL_ALL) ? (size_t)8 * PL_TAIL_IT * 4096 : 0;
+    const size_t gemv = (size_t)(R * PL_I + PL_RED_FLOATS + 4 * R + 4 * R + 256 * R) * 4, tail = (size_t)8 * PL_TAIL_IT * 4096;
     return PL_FRONT_BYTES + (gemv > tail ? gemv : tail);
 }
 
-template <int R, int SCHED, typename WT, bool LORA = false>
-static int persist_launch_t(const PersistArgs& a, hipStream_t s, bool configure_only) {
-    auto kern = persist_layer_kernel<R, SCHED, WT, LORA>;
-    if (configure_only) { CTTS_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)persist_lds_bytes(R))); return 0; }
-    hipLaunchKernelGGL(kern, dim3(PL_BLOCKS), dim3(PL_THREADS(R)), persist_lds_bytes(R), s, a);
-    CTTS_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-template <int SCHED, typename WT>
-static int persist_launch_r(int R, const PersistArgs& a, hipStream_t s, bool cfg) {
-    // exact row counts: a spare row would append stale K / V rows to a live cache lane
-    if constexpr (SCHED == 3) if (!cfg && a.lora) {      // per-utterance adapters: the LORA kernels
-        switch (R) {
-            case 1: return persist_launch_t<1, 3, WT, true>(a, s, false);
-            case 2: return persist_launch_t<2, 3, WT, true>(a, s, false);
-            case 3: return persist_launch_t<3, 3, WT, true>(a, s, false);
-            case 4: return persist_launch_t<4, 3, WT, true>(a, s, false);
-            case 5: return persist_launch_t<5, 3, WT, true>(a, s, false);
-            case 6: return persist_launch_t<6, 3, WT, true>(a, s, false);
-            case 7: return persist_launch_t<7, 3, WT, true>(a, s, false);
-            case 8: return persist_launch_t<8, 3, WT, true>(a, s, false);
-        }
-    }
-    if (cfg) {
-        if constexpr (SCHED == 3) {
-            const int rl = persist_launch_t<1, 3, WT, true>(a, s, true) | persist_launch_t<2, 3, WT, true>(a, s, true) | persist_launch_t<3, 3, WT, true>(a, s, true) | persist_launch_t<4, 3, WT, true>(a, s, true) |
-                           persist_launch_t<5, 3, WT, true>(a, s, true) | persist_launch_t<6, 3, WT, true>(a, s, true) | persist_launch_t<7, 3, WT, true>(a, s, true) | persist_launch_t<8, 3, WT, true>(a, s, true);
-            if (rl) return rl;
-        }
-        int rc = persist_launch_t<1, SCHED, WT>(a, s, true) | persist_launch_t<2, SCHED, WT>(a, s, true) | persist_launch_t<3, SCHED, WT>(a, s, true) | persist_launch_t<4, SCHED, WT>(a, s, true) |
-                 persist_launch_t<5, SCHED, WT>(a, s, true);
-        if constexpr (SCHED == 3) rc |= persist_launch_t<6, 3, WT>(a, s, true) | persist_launch_t<7, 3, WT>(a, s, true) | persist_launch_t<8, 3, WT>(a, s, true);
-        return rc;
-    }
-    switch (R) {
-        case 1: return persist_launch_t<1, SCHED, WT>(a, s, false);
-        case 2: return persist_launch_t<2, SCHED, WT>(a, s, false);
-        case 3: return persist_launch_t<3, SCHED, WT>(a, s, false);
-        case 4: return persist_launch_t<4, SCHED, WT>(a, s, false);
-        case 5: return persist_launch_t<5, SCHED, WT>(a, s, false);
-    }
-    if constexpr (SCHED == 3) {      // 6..8 rows (two attention items per workgroup): the paced schedule only
-        switch (R) {
-            case 6: return persist_launch_t<6, 3, WT>(a, s, false);
-            case 7: return persist_launch_t<7, 3, WT>(a, s, false);
-            case 8: return persist_launch_t<8, 3, WT>(a, s, false);
-        }
-    }
-    ctts_set_error("persistent layer: %d rows (max %d; 6+ rows need the paced schedule)", R, PL_MAXR);
-    return 1;
-}
+// ---- dispatch: one table of the 42 instantiations, built at compile time.  Exact row counts: a spare row would append stale K / V rows to a live cache lane.
+typedef void (*PersistKernel)(const PersistArgs);
+struct PersistRow { PersistKernel k[PL_MAXR]; };          // [R - 1]; null: no such kernel
+template <int SCHED, typename WT, bool LORA, int... R0>
+constexpr PersistRow persist_row(std::integer_sequence<int, R0...>) { return {{persist_layer_kernel<R0 + 1, SCHED, WT, LORA>...}}; }
+// rows of the table, in the order the kernels have in the code object: fp32 schedule 1, schedule 2 (up to PL_MAXR_ONE rows), then schedule 3 as [half weights][plain after LORA]
+static constexpr PersistRow persist_table[6] = {
+    persist_row<1, float, false>(std::make_integer_sequence<int, PL_MAXR_ONE>()), persist_row<2, float, false>(std::make_integer_sequence<int, PL_MAXR_ONE>()),
+    persist_row<3, float, true>(std::make_integer_sequence<int, PL_MAXR>()),      persist_row<3, float, false>(std::make_integer_sequence<int, PL_MAXR>()),
+    persist_row<3, half_t, true>(std::make_integer_sequence<int, PL_MAXR>()),     persist_row<3, half_t, false>(std::make_integer_sequence<int, PL_MAXR>())};
 
 int persist_configure() {
-    PersistArgs a = {};
-    return persist_launch_r<1, float>(1, a, nullptr, true) | persist_launch_r<2, float>(1, a, nullptr, true) | persist_launch_r<3, float>(1, a, nullptr, true) |
-           persist_launch_r<3, half_t>(1, a, nullptr, true);
+    for (const PersistRow& row : persist_table)
+        for (int R = 1; R <= PL_MAXR; ++R)
+            if (row.k[R - 1] != nullptr)
+                CTTS_HIP_CHECK(hipFuncSetAttribute((const void*)row.k[R - 1], hipFuncAttributeMaxDynamicSharedMemorySize, (int)persist_lds_bytes(R)));
+    return 0;
 }
 
 int launch_persist_layer(int R, const PersistArgs& a, hipStream_t s) {
     if (a.lora && a.sched != 3) { ctts_set_error("persistent layer: per-utterance adapters need the paced schedule"); return 1; }
-    if (a.half_w) return persist_launch_r<3, half_t>(R, a, s, false);          // fp16 engines: the paced schedule only
-    return (a.sched == 1) ? persist_launch_r<1, float>(R, a, s, false) : (a.sched == 2) ? persist_launch_r<2, float>(R, a, s, false) : persist_launch_r<3, float>(R, a, s, false);
+    const bool paced = a.half_w || (a.sched != 1 && a.sched != 2);      // fp16 engines: the paced schedule only
+    const PersistRow& row = persist_table[paced ? 2 + 2 * (a.half_w ? 1 : 0) + (a.lora ? 0 : 1) : a.sched - 1];
+    const PersistKernel kern = (R >= 1 && R <= PL_MAXR) ? row.k[R - 1] : nullptr;
+    if (kern == nullptr) { ctts_set_error("persistent layer: %d rows (max %d; 6+ rows need the paced schedule)", R, PL_MAXR); return 1; }
+    hipLaunchKernelGGL(kern, dim3(PL_BLOCKS), dim3(PL_THREADS), persist_lds_bytes(R), s, a);
+    CTTS_HIP_CHECK(hipGetLastError());
+    return 0;
 }

@@ -1,4 +1,4 @@
-"""The persistent decode launch after the attention workgroups' critical path was trimmed (persist_layer.hip: PL_KV_AFTER_PUBLISH -- the next layer's cached K / V rows
+"""The persistent decode launch after the attention workgroups' critical path was trimmed (persist_layer.hip, "attention trim": the next layer's cached K / V rows
 are requested behind a third workgroup barrier, B3, that wave 8 joins behind its last hand-off of the layer): the link moves memory requests off the path between
 "q gathered" and "granule published" and changes no operand, rounding or order of an addition, so every output bit must be the one the launch produced before it.
 

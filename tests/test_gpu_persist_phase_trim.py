@@ -1,5 +1,5 @@
-"""The persistent decode launch after its phases' in-workgroup critical paths were trimmed (persist_layer.hip: PL_EARLY_ARRIVE, PL_BAR_WAKE, PL_A16_DPP;
-PL_RS_EARLY is built off): the trim moves work off the path between "gather complete" and "granule published" and changes no arithmetic, so every output bit must be
+"""The persistent decode launch after its phases' in-workgroup critical paths were trimmed (persist_layer.hip, "phase trim": the one-row kernels announce a
+gather before its norm sums, B1 is the hardware barrier, the act publish shifts by DPP): the trim moves work off the path between "gather complete" and "granule published" and changes no arithmetic, so every output bit must be
 the one the launch produced before it.
 
 Each case (1, 2, 5, 6, 8 rows; fp32 and fp16 engines; prompt 40, 24 new tokens, device noise with a fixed seed; one case with per-utterance adapters on the

@@ -268,12 +268,47 @@ def test_fp16_engines_use_the_persistent_launch_too():
         g.close()
 
 
+def test_fp16_launch_at_four_and_seven_rows():
+    """The two fp16 kernels without adapters that no other case launches (1, 3 rows: above; 2, 5, 6, 8: tests/test_gpu_persist_phase_trim.py): 4 and 7 rows of a
+    6-layer fp16 engine against its launch chain (persistent_rows=0), 12 tokens behind an 18-token prompt.  The launch ran and gave up nowhere; the hiddens of the
+    steps whose inputs are still identical on both paths (the agreeing leading tokens + 1) lie within the fast mode's 2e-3 relative rms."""
+    import ctypes as C
+    from chatttsplus_amd import _lib
+    from chatttsplus_amd.hip_models import GPT
+    cfg = dict(synth.GPT_REAL); cfg["num_hidden_layers"] = 6
+    g = GPT(dict(LLAMA, num_hidden_layers=6), max_batch=8, max_seq_len=96, weight_dtype="fp16")
+
+    def state():
+        buf = np.zeros(8, dtype=np.uint8); got = C.c_size_t(0)
+        _lib.check(g._lib.ctts_gpt_debug_read(g._h, b"pl_state", buf.ctypes.data_as(C.c_void_p), 8, C.byref(got), g._stream()), "debug_read")
+        return int(buf.view(np.uint32)[0]), int(buf.view(np.uint32)[1])      # launch counter, error word
+
+    try:
+        g.load_state_dict(synth.gpt_state_dict(cfg, 1234))
+        for B in (4, 7):
+            pad = [(3 * b) % 5 for b in range(B)]
+            g.set_option("persistent_rows", 0)
+            c_ids, c_h = _gen(g, B, 18, 12, pad)
+            g.set_option("persistent_rows", 8)
+            e0, _ = state()
+            p_ids, p_h = _gen(g, B, 18, 12, pad)
+            e1, err = state()
+            assert err == 0 and e1 > e0, f"B={B}: the persistent launch did not run (launch counter {e0} -> {e1}, error word {err})"
+            for b in range(B):
+                same = int((p_ids[b] == c_ids[b]).all(-1).to(torch.int32).cumprod(0).sum())
+                n = min(same + 1, 12)
+                rel = float((p_h[b][:n] - c_h[b][:n]).pow(2).mean().sqrt() / c_h[b][:n].pow(2).mean().sqrt())
+                assert rel <= 2e-3, f"B={B} row {b}: hidden states {rel} away from the fp16 launch chain over the {n} steps with identical inputs"
+    finally:
+        g.close()
+
+
 @pytest.mark.parametrize("wd", ["fp32", "fp16"])
 def test_per_utterance_adapters_ride_inside_the_persistent_launch(wd):
     """Round 6: rows that carry a LoRA adapter (pipeline:420-432 per row instead of per batch) stay on the persistent launch -- waves 6 / 7 of
     the GEMV workgroups compute u = A h, the edge lanes add scale * B u to their q / k / v / o_proj rows (persist_layer.hip LORA).  Against the launch chain's worker
     workgroups (lora_worker.h; itself held to the per-row merged-weights oracle by tests/test_gpu_pipeline.py): fp32 token ids identical, hiddens <= 5e-5;
-    fp16: first hidden states within 2e-3.  1..8 rows, rows with different adapters / ranks / none, with and without graphs."""
+    fp16: first hidden states within 2e-3.  Every row count 1..8, rows with different adapters / ranks / none, with and without graphs."""
     import ctypes as C
     from chatttsplus_amd import _lib
     from chatttsplus_amd.hip_models import GPT
@@ -308,7 +343,7 @@ def test_per_utterance_adapters_ride_inside_the_persistent_launch(wd):
         g.set_row_adapters(None)
         return out
 
-    for B, slots in ((1, [1]), (2, [0, -1]), (3, [2, 1, 0]), (5, [0, 1, -1, 2, 1]), (6, [1, -1, 0, 0, 2, -1]), (8, [0, 1, 2, -1, 1, 0, -1, 2])):
+    for B, slots in ((1, [1]), (2, [0, -1]), (3, [2, 1, 0]), (4, [2, -1, 0, 1]), (5, [0, 1, -1, 2, 1]), (6, [1, -1, 0, 0, 2, -1]), (7, [0, 1, -1, 2, 2, -1, 1]), (8, [0, 1, 2, -1, 1, 0, -1, 2])):
         ref = run(B, slots, 0, True)
         e0, _ = epoch()
         for graphs in (True, False):

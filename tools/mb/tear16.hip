@@ -1,5 +1,5 @@
 // Microbenchmark: is a 16-byte aligned, 16-byte wide store of one lane (buffer_store_dwordx4 sc1) ever OBSERVED TORN by a 16-byte sc1 load of a lane on another
-// CU / XCD of a gfx950?  (Nothing in the ISA promises it; the persistent decode launch's 16-byte act granules, persist_layer.hip PL_ACT16, carry a checksum word
+// CU / XCD of a gfx950?  (Nothing in the ISA promises it; the persistent decode launch's 16-byte act granules (persist_layer.hip) carry a checksum word
 // for that reason -- this program says how often the check would have to fire.)
 // Writers: W workgroups, every lane owns one 16-byte slot and stores {i, i ^ A, i ^ B, i ^ C} for i = 1 .. ITER with no waits in between (so that several stores
 // to one slot are in flight at once).  Readers: all other workgroups re-read every slot until the writers are done and classify each value they see:

@@ -56,7 +56,7 @@ def granules(g):
     val, tag = raw[:, 0].copy().view(np.float32), raw[:, 1].copy()
     o = [0, G_QKV, G_QKV + G_ATT, G_QKV + G_ATT + G_X1, G_QKV + G_ATT + G_X1 + G_ACT]
     gs = [(val[o[i]:o[i + 1]], tag[o[i]:o[i + 1]]) for i in range(4)]
-    # the act rows travel as 16-byte granules {v0, v1, v2, tag + bits(v0) + bits(v1) + bits(v2)}, six per (row, producer workgroup) (persist_layer.hip PL_ACT16):
+    # the act rows travel as 16-byte granules {v0, v1, v2, tag + bits(v0) + bits(v1) + bits(v2)}, six per (row, producer workgroup) (persist_layer.hip, "16-byte act granules"):
     # granule f holds columns 16 (f / 6) + 3 (f % 6) + {0, 1, 2} of the [rows][3072] array; unpack to one (value, tag) per column
     a16 = raw[o[3]:o[4]].reshape(-1)[:MAXR * 192 * 6 * 4].reshape(-1, 4)
     tg = (a16[:, 3] - a16[:, 0] - a16[:, 1] - a16[:, 2]).astype(np.uint32)
