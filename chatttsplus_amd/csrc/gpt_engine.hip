@@ -268,6 +268,14 @@ struct ctts_gpt {
     // shared prompt passes (ctts_gpt_share_prompts; kv_share.hip)
     std::vector<int> share_tab;                  //   host image of share_dev for the call that consumed the request (kernels.h SH_*)
     int* share_dev = nullptr;                    //   device table [SH_INTS], allocated by the first ctts_gpt_share_prompts
+    // guided refine-text (kernels.h GuideTab): the table is allocated by the first ctts_gpt_set_text_guide (4.2 MB; engines that never call it keep their footprint),
+    // the records are uploaded through a pinned ring (a slot is reused only after its copies have run)
+    GuideTab* guide_tab = nullptr;
+    std::vector<int> guide_len;                  //   host mirror of rec[slot].n for the current call
+    int* guide_pin = nullptr;
+    hipEvent_t guide_ev[4] = {};
+    bool guide_pin_used[4] = {};
+    unsigned guide_pin_next = 0;
     std::vector<void*> owned;                    // every device buffer of the engine (dev_alloc)
     RowRequests req;                             // what the callers asked for: "the following begin calls"
     NextCall next;                               //   ... and the next ctts_gpt_begin / ctts_gpt_admit alone
@@ -282,6 +290,7 @@ struct ctts_gpt {
     int share_P = 0, share_groups = 0;           // prompts of the current ctts_gpt_begin (0 = every sequence runs its own prompt; read by ctts_gpt_prefill), those with at least one follower
     long pp_rows = 0; int pp_T = 0;              // the last ctts_gpt_prefill / ctts_gpt_score call: its prompt rows and their tokens per sequence (debug_read "prompt_plan", "meta_pre", "x_pre"); 0 rows = none since begin
     int text_mode = 0, text_rows_on = 0;         // the call's own infer_text; the state has its text block (ctts_gpt_enable_text_rows; begin switches it off again)
+    int guide_on = 0;                            // guided refine-text (ctts_gpt_set_text_guide): the text sampler runs its GUIDED instantiation -- part of the graph key; begin switches it off again
     // ... and what refresh_rows derives from `rows`: which launches a step takes is decided from these
     int text_live = 0;                           // rows whose mode is 1, finished ones included ("text_rows_live"): > 0 = the step is MIXED -- two more launches (text head, text sampler)
     int lora_rows = 0;                           // 1: a row carries an adapter slot; before rows exist (ctts_gpt_set_row_adapters, ctts_gpt_score) the sequences of the request do
@@ -527,6 +536,8 @@ extern "C" void ctts_gpt_destroy(ctts_gpt* h) {
     for (auto& kv : h->graphs) { (void)hipGraphExecDestroy(kv.second.exec); (void)hipGraphDestroy(kv.second.graph); }
     for (void* b : h->owned) (void)hipFree(b);
     if (h->host_pin) (void)hipHostFree(h->host_pin);
+    if (h->guide_pin) (void)hipHostFree(h->guide_pin);
+    for (hipEvent_t e : h->guide_ev) if (e) (void)hipEventDestroy(e);
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -1465,6 +1476,7 @@ static int run_sample_phase(ctts_gpt* h, StreamForm form, hipStream_t s) {
     sa.text_mode = h->text_mode; sa.mixed = mixed ? 1 : 0;
     sa.emb_code = h->text_mode ? h->emb_text : h->emb_code; sa.H = h->H; sa.x_next = h->x_dec; sa.meta = h->meta_dec; sa.rope = h->rope; sa.rope_rows = h->rope_dec;
     sa.hist_ring = h->hist_ring; sa.finend = h->finend;
+    sa.guided = h->guide_on;                     // (read by the text sampler's launch only)
     if (launch_sampler(sa, h->B, s)) return 1;
     if (!mixed) return 0;
     sa.dyn = h->dyn_text; sa.logits = h->logits_text; sa.V = h->vocab_text_head; sa.text_mode = 1; sa.emb_code = h->emb_text;
@@ -1483,7 +1495,7 @@ static int reset_state(ctts_gpt* h, bool keep_draw, hipStream_t s) {
     if (!keep_draw) {       // begin: {fin 0, end 0, attempt 0, limit, utterance id} per row (pageable source: staged before the call returns)
         CTTS_HIP_CHECK(hipMemcpyAsync(h->finend, h->finend_host.data(), h->B * sizeof(RowState), hipMemcpyHostToDevice, s));
     } else {
-        if (launch_restart_rows(h->finend, h->B, s)) return 1;
+        if (launch_restart_rows(h->finend, h->B, h->guide_on ? h->guide_tab : nullptr, s)) return 1;
         for (HostRow& r : h->rows) r.ctx = h->T;
     }      // ensure_non_empty regenerate: rows that ended at step 0 move on to their next noise attempt
     CTTS_HIP_CHECK(hipMemsetAsync(h->hist_ring, 0xFF, (size_t)h->B * CTTS_NUM_VQ * 16 * 4, s));      // -1: no id sampled yet
@@ -1545,6 +1557,7 @@ static void end_generate_state(ctts_gpt* h) {
     h->segs.clear(); h->pp_rows = 0;  // (debug_read "decode_plan" / "prompt_plan": nothing planned, no prompt pass yet)
     h->share_P = 0; h->share_groups = 0;
     h->text_rows_on = 0;              // every begin switches text rows off again: ctts_gpt_enable_text_rows follows it
+    h->guide_on = 0;                  // ... and the guide (begin rewrites the per-call block with a null table): ctts_gpt_set_text_guide follows it
     (void)refresh_rows(h);            // no rows: no text row, no adapter row (nothing to allocate)
 }
 // the table of one call (kernels.h SH_*): `lanes[i]` = KV lane of the call's i-th sequence.  The prompt pass runs under the leader's adapter slot, so a group shares one slot or none.
@@ -1913,7 +1926,100 @@ extern "C" int ctts_gpt_enable_text_rows(ctts_gpt* h, const ctts_sampler_cfg* ts
         CTTS_HIP_CHECK(hipMemcpyAsync(h->finend, h->finend_host.data(), (size_t)h->B * sizeof(RowState), hipMemcpyHostToDevice, s));
     }
     h->text_rows_on = 1;
+    h->guide_on = 0;                  // (the block was rewritten with a null table: ctts_gpt_set_text_guide follows this call)
     return 0;
+}
+
+// ---- guided refine-text (include/ctts_hip.h; kernels.h GuideTab) -----------------------------------------------------------------------------------------------
+#define GUIDE_PIN_INTS 65536      // ints per slot of the pinned upload ring (4 slots; a record is at most 1024 ints)
+// The per-call part is checked here for the hook as well: free ids distinct, in range, none the EOS.
+static int check_free_ids(const char* who, const int32_t* free_ids, int n_free, int max_run, int eos, int vocab) {
+    if (n_free < 0 || n_free > CTTS_GUIDE_MAX_FREE) { ctts_set_error("%s: %d free ids (at most %d)", who, n_free, CTTS_GUIDE_MAX_FREE); return 1; }
+    if (n_free > 0 && !free_ids) { ctts_set_error("%s: null free_ids", who); return 1; }
+    if (max_run < 0) { ctts_set_error("%s: max_run = %d (must be >= 0)", who, max_run); return 1; }
+    for (int i = 0; i < n_free; ++i) {
+        if (free_ids[i] < 0 || free_ids[i] >= vocab) { ctts_set_error("%s: free id %d outside 0..%d", who, free_ids[i], vocab - 1); return 1; }
+        if (free_ids[i] == eos) { ctts_set_error("%s: free id %d is the EOS token (the guide ends a row by EOS alone)", who, free_ids[i]); return 1; }
+        for (int j = 0; j < i; ++j) if (free_ids[j] == free_ids[i]) { ctts_set_error("%s: free id %d is listed twice", who, free_ids[i]); return 1; }
+    }
+    return 0;
+}
+static int check_guide_src(const char* who, int i, const int32_t* src, int n, int limit, int eos, int vocab) {
+    if (n > CTTS_GUIDE_MAX_SRC) { ctts_set_error("%s: entry %d: source of %d ids (at most %d)", who, i, n, CTTS_GUIDE_MAX_SRC); return 1; }
+    if (n + 1 > limit) { ctts_set_error("%s: entry %d: a source of %d ids needs %d tokens (the source and EOS), the row's limit is %d", who, i, n, n + 1, limit); return 1; }
+    for (int k = 0; k < n; ++k) {
+        if (src[k] < 0 || src[k] >= vocab) { ctts_set_error("%s: entry %d: source id %d outside 0..%d", who, i, src[k], vocab - 1); return 1; }
+        if (src[k] == eos) { ctts_set_error("%s: entry %d: source id %d is the EOS token", who, i, src[k]); return 1; }
+    }
+    return 0;
+}
+
+extern "C" int ctts_gpt_set_text_guide(ctts_gpt* h, const int32_t* free_ids, int n_free, int max_run, void* stream) {
+    if (!h || h->B == 0) { ctts_set_error("set_text_guide: no generate state (call ctts_gpt_begin first)"); return 1; }
+    if (!h->text_mode && !h->text_rows_on) { ctts_set_error("set_text_guide: a guide is for text rows: the call must be an infer_text call, or ctts_gpt_enable_text_rows must come first (a guide on a code row)"); return 1; }
+    if (h->io.noise != nullptr && !h->text_mode) { ctts_set_error("set_text_guide: guides in a code call need device noise (caller-supplied noise is laid out for one mode's rows)"); return 1; }
+    const SamplerCfgDev& tsc = h->text_mode ? h->sc : h->sc_text;
+    if (check_free_ids("set_text_guide", free_ids, n_free, max_run, tsc.eos, h->vocab_text_head)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    if (!h->guide_tab && dev_alloc(h, (void**)&h->guide_tab, sizeof(GuideTab))) return 1;
+    if (!h->guide_pin) {
+        CTTS_HIP_CHECK(hipHostMalloc((void**)&h->guide_pin, (size_t)4 * GUIDE_PIN_INTS * 4, hipHostMallocDefault));
+        for (hipEvent_t& e : h->guide_ev) CTTS_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    // every slot starts unguided (n = 0); then the header
+    CTTS_HIP_CHECK(hipMemsetAsync(h->guide_tab, 0, sizeof(GuideTab), s));
+    int hdr[4 + CTTS_GUIDE_MAX_FREE] = {n_free, max_run, 0, 0};
+    for (int i = 0; i < n_free; ++i) hdr[4 + i] = free_ids[i];
+    CTTS_HIP_CHECK(hipMemcpyAsync(h->guide_tab, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));       // pageable source: staged before the call returns
+    GuideTab* const p = h->guide_tab;
+    CTTS_HIP_CHECK(hipMemcpyAsync((char*)(h->text_mode ? h->dyn : h->dyn_text) + offsetof(SamplerDyn, guide), &p, sizeof(p), hipMemcpyHostToDevice, s));
+    h->guide_len.assign(CTTS_GUIDE_SLOTS, 0);
+    h->guide_on = 1;
+    return 0;
+}
+
+extern "C" int ctts_gpt_set_guides(ctts_gpt* h, int n, const int32_t* out_slots, const int32_t* src_concat, const int32_t* src_off, void* stream) {
+    if (!h || h->B == 0) { ctts_set_error("set_guides: no generate state (call ctts_gpt_begin first)"); return 1; }
+    if (!h->guide_on) { ctts_set_error("set_guides: guides without the per-call part: call ctts_gpt_set_text_guide first (after ctts_gpt_begin / ctts_gpt_enable_text_rows)"); return 1; }
+    if (n < 0 || (n > 0 && (!out_slots || !src_off))) { ctts_set_error("set_guides: bad argument"); return 1; }
+    const SamplerCfgDev& tsc = h->text_mode ? h->sc : h->sc_text;
+    const bool seated = !h->sampled && !h->admitted;      // begin's rows are still what finend_host describes
+    for (int i = 0; i < n; ++i) {
+        const int slot = out_slots[i], len = src_off[i + 1] - src_off[i];
+        if (slot < 0 || slot >= CTTS_GUIDE_SLOTS) { ctts_set_error("set_guides: entry %d: output slot %d outside 0..%d (the guide table's extent)", i, slot, CTTS_GUIDE_SLOTS - 1); return 1; }
+        if (len < 0 || (len > 0 && !src_concat)) { ctts_set_error("set_guides: entry %d: bad source extent", i); return 1; }
+        if (len == 0) continue;
+        int limit = tsc.max_new;
+        if (seated)
+            for (int b = 0; b < h->B && b < (int)h->finend_host.size(); ++b) {
+                const RowState& r = h->finend_host[b];
+                if (r.out != slot) continue;
+                if (!h->text_mode && r.mode == 0) { ctts_set_error("set_guides: entry %d: output slot %d is held by a code row (a guide on a code row)", i, slot); return 1; }
+                limit = r.limit < limit ? r.limit : limit;
+            }
+        if (check_guide_src("set_guides", i, src_concat + src_off[i], len, limit, tsc.eos, h->vocab_text_head)) return 1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    int slot = -1, used = 0;
+    auto close_slot = [&]() -> int {
+        if (slot >= 0 && used > 0) { CTTS_HIP_CHECK(hipEventRecord(h->guide_ev[slot], s)); h->guide_pin_used[slot] = true; }
+        return 0;
+    };
+    for (int i = 0; i < n; ++i) {
+        const int len = src_off[i + 1] - src_off[i], ints = 4 + len;
+        if (slot < 0 || used + ints > GUIDE_PIN_INTS) {
+            if (close_slot()) return 1;
+            slot = (int)(h->guide_pin_next++ % 4); used = 0;
+            if (h->guide_pin_used[slot]) CTTS_HIP_CHECK(hipEventSynchronize(h->guide_ev[slot]));
+        }
+        int* p = h->guide_pin + (size_t)slot * GUIDE_PIN_INTS + used;
+        p[0] = len; p[1] = 0; p[2] = 0; p[3] = 0;                      // a fresh record: cur = run = 0
+        for (int k = 0; k < len; ++k) p[4 + k] = src_concat[src_off[i] + k];
+        CTTS_HIP_CHECK(hipMemcpyAsync(&h->guide_tab->rec[out_slots[i]], p, (size_t)ints * 4, hipMemcpyHostToDevice, s));
+        used += ints;
+        h->guide_len[out_slots[i]] = len;
+    }
+    return close_slot();
 }
 
 extern "C" int ctts_gpt_sample(ctts_gpt* h, void* stream) {
@@ -2037,7 +2143,7 @@ static int graph_span(const ctts_gpt* h, DecodePath path, int left) {
 
 static int ensure_graph(ctts_gpt* h, DecodePath path, int n_steps) {
     char sig[160];
-    snprintf(sig, sizeof(sig), "%d|%d|%p|%d|%d|%d|%d|%d", h->B, h->text_mode + 2 * (h->text_live > 0 ? 1 : 0), (void*)h->kv, path.splits, h->lora_rows + 2 * h->lora_mlp, h->opt_gen, path.persist, n_steps);      // (+ 2: a mixed step, two more launches)      // (diagnostic switches are fixed at create)
+    snprintf(sig, sizeof(sig), "%d|%d|%p|%d|%d|%d|%d|%d", h->B, h->text_mode + 2 * (h->text_live > 0 ? 1 : 0) + 4 * h->guide_on, (void*)h->kv, path.splits, h->lora_rows + 2 * h->lora_mlp, h->opt_gen, path.persist, n_steps);      // (+ 2: a mixed step, two more launches)      // (diagnostic switches are fixed at create)
     std::string key(sig);
     if (h->lora_rows) { signed char slots[CTTS_MAX_B]; row_slot_bytes(h, slots, h->B); key.append((const char*)slots, (size_t)h->B); }      // the rows' adapter slots are kernel arguments of the folded launches (LoraFold)
     if (h->graph_gen != h->opt_gen || h->graphs.size() >= 96) {
@@ -2238,6 +2344,14 @@ extern "C" int ctts_gpt_admit(ctts_gpt* h, int n, const int32_t* rows, int T, co
                 return 1;
             }
             if (r.limit > h->sc_text.max_new) r.limit = h->sc_text.max_new;      // the text ids array is [n_out][max_new_text][4]
+        }
+        // the guide ctts_gpt_set_guides named for the row's output slot: text rows only, and the source and its EOS fit the row's limit
+        if (h->guide_on && r.out < CTTS_GUIDE_SLOTS && h->guide_len[r.out] > 0) {
+            if (!h->text_mode && r.mode == 0) { ctts_set_error("admit: row %d is to hold a code utterance at output slot %d, which carries a guide (a guide on a code row)", rows[i], r.out); return 1; }
+            if (h->guide_len[r.out] + 1 > r.limit) {
+                ctts_set_error("admit: row %d: the guide at output slot %d has a source of %d ids and needs %d tokens (the source and EOS), the row's limit is %d", rows[i], r.out, h->guide_len[r.out], h->guide_len[r.out] + 1, r.limit);
+                return 1;
+            }
         }
         return 0;
     })) return 1;
@@ -2461,6 +2575,78 @@ extern "C" int ctts_sampler_run_rows_lp(const ctts_sampler_cfg* sc, const ctts_r
                                         const float* q, int rows, int vocab, int step, int32_t* idx, float* lp_raw, float* lp_sampled, void* stream) {
     if (!per_seq) { ctts_set_error("sampler_run_rows_lp: null argument"); return 1; }
     return sampler_run_standalone(sc, per_seq, logits, history, hist_len, q, rows, vocab, step, idx, lp_raw, lp_sampled, stream, "sampler_run_rows_lp");
+}
+
+// Stand-alone guided text sampler (a test hook, synchronous): one step of sampler_text_kernel<true> -- the generate kernel itself, not a copy of its arithmetic -- on
+// a one-step state built here: row r is a live text row at output slot r, at its own step, with its guide record at the given cursor.  Host arrays in, host arrays out.
+extern "C" int ctts_sampler_run_text_guided(const ctts_sampler_cfg* sc, const float* logits, const float* q, int rows, int vocab, const int32_t* free_ids, int n_free,
+                                            int max_run, const int32_t* src_concat, const int32_t* src_off, const int32_t* cur, const int32_t* run, const int32_t* step,
+                                            const int32_t* limit, int32_t* idx_out, int32_t* cur_out, int32_t* run_out, void* stream) {
+    const char* who = "sampler_run_text_guided";
+    if (!sc || !logits || !q || !src_concat || !src_off || !cur || !run || !step || !limit || !idx_out || !cur_out || !run_out) { ctts_set_error("%s: null argument", who); return 1; }
+    if (rows < 1 || rows > CTTS_GUIDE_SLOTS) { ctts_set_error("%s: rows=%d outside 1..%d", who, rows, CTTS_GUIDE_SLOTS); return 1; }
+    if (!sc->infer_text || sc->use_penalty) { ctts_set_error("%s: sc must be the refine-text pass's parameters (infer_text = 1, no repetition penalty)", who); return 1; }
+    if (vocab < 1 || sc->eos_token < 0 || sc->eos_token >= vocab) { ctts_set_error("%s: eos out of range", who); return 1; }
+    if (check_free_ids(who, free_ids, n_free, max_run, sc->eos_token, vocab)) return 1;
+    int max_new = 1;
+    for (int r = 0; r < rows; ++r) {
+        const int n = src_off[r + 1] - src_off[r];
+        if (n < 1) { ctts_set_error("%s: row %d: a source of %d ids (n == 0 is an unguided row: not served by this hook)", who, r, n); return 1; }
+        if (limit[r] < 1 || limit[r] > 4096) { ctts_set_error("%s: row %d: limit %d outside 1..4096", who, r, limit[r]); return 1; }
+        if (check_guide_src(who, r, src_concat + src_off[r], n, limit[r], sc->eos_token, vocab)) return 1;
+        if (cur[r] < 0 || cur[r] > n || run[r] < 0 || step[r] < 0 || step[r] >= limit[r]) { ctts_set_error("%s: row %d: cur=%d run=%d step=%d outside the guide (n=%d, limit=%d)", who, r, cur[r], run[r], step[r], n, limit[r]); return 1; }
+        max_new = limit[r] > max_new ? limit[r] : max_new;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    // one scratch block: [guide header + rows records][SamplerDyn][DevState][RowState x rows][RowMeta x rows][rope 2 x 64][rope rows][ids][finish][end_idx][x_next]
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t o_tab = 0, o_dyn = up(offsetof(GuideTab, rec) + (size_t)rows * sizeof(GuideRec)), o_st = o_dyn + up(sizeof(SamplerDyn)), o_rs = o_st + up(sizeof(DevState)),
+                 o_meta = o_rs + up((size_t)rows * sizeof(RowState)), o_rope = o_meta + up((size_t)rows * sizeof(RowMeta)), o_rr = o_rope + up(128 * 4),
+                 o_ids = o_rr + up((size_t)rows * 64 * 4), o_fin = o_ids + up((size_t)rows * max_new * CTTS_NUM_VQ * 4), o_end = o_fin + up((size_t)rows * 4),
+                 o_x = o_end + up((size_t)rows * 4), total = o_x + 256;
+    std::vector<char> img(o_rope, 0);                       // host image of everything up to the RoPE table; the rest is zero-filled on the device
+    GuideTab* ht = (GuideTab*)(img.data() + o_tab);
+    ht->n_free = n_free; ht->max_run = max_run;
+    for (int i = 0; i < n_free; ++i) ht->free_ids[i] = free_ids[i];
+    RowState* hr = (RowState*)(img.data() + o_rs);
+    for (int r = 0; r < rows; ++r) {
+        GuideRec& g = ht->rec[r];
+        g.n = src_off[r + 1] - src_off[r]; g.cur = cur[r]; g.run = run[r];
+        for (int k = 0; k < g.n; ++k) g.src[k] = src_concat[src_off[r] + k];
+        hr[r].end = step[r]; hr[r].limit = limit[r]; hr[r].out = r; hr[r].uid_lo = (unsigned)r;
+    }
+    char* dev = nullptr;
+    CTTS_HIP_CHECK(hipMalloc((void**)&dev, total));
+    int rc = 1;
+    do {
+        SamplerDyn d = {};
+        d.cfg = cfg_of_abi(*sc); d.cfg.max_new = max_new; d.n_draws = 1; d.ids = (int*)(dev + o_ids); d.finish = (int*)(dev + o_fin); d.end_idx = (int*)(dev + o_end);
+        d.noise = q; d.rows0 = rows; d.guide = (GuideTab*)(dev + o_tab);
+        memcpy(img.data() + o_dyn, &d, sizeof(d));
+        DevState* hs = (DevState*)(img.data() + o_st);
+        hs->B = rows;
+        if (hipMemsetAsync(dev + o_rope, 0, total - o_rope, s) != hipSuccess || hipMemcpyAsync(dev, img.data(), o_rope, hipMemcpyHostToDevice, s) != hipSuccess) { ctts_set_error("%s: upload failed", who); break; }
+        SamplerArgs sa = {};
+        sa.dyn = (const SamplerDyn*)(dev + o_dyn); sa.logits = logits; sa.V = vocab; sa.B = rows; sa.st = (DevState*)(dev + o_st);
+        sa.text_mode = 1; sa.mixed = 0; sa.guided = 1;
+        sa.emb_code = logits; sa.H = 0; sa.x_next = (float*)(dev + o_x);            // H = 0: no next-input row is written
+        sa.meta = (RowMeta*)(dev + o_meta); sa.rope = (const float*)(dev + o_rope); sa.rope_rows = (float*)(dev + o_rr); sa.finend = (RowState*)(dev + o_rs);
+        if (launch_sampler(sa, rows, s)) break;
+        std::vector<int> ids((size_t)rows * max_new * CTTS_NUM_VQ);
+        if (hipMemcpyAsync(ids.data(), dev + o_ids, ids.size() * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipMemcpyAsync(img.data(), dev + o_tab, o_dyn, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+            ctts_set_error("%s: %s", who, hipGetErrorString(hipGetLastError()));
+            break;
+        }
+        for (int r = 0; r < rows; ++r) {
+            idx_out[r] = ids[((size_t)r * max_new + step[r]) * CTTS_NUM_VQ];
+            cur_out[r] = ht->rec[r].cur; run_out[r] = ht->rec[r].run;
+        }
+        rc = 0;
+    } while (false);
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(dev);
+    return rc;
 }
 
 extern "C" int ctts_gpt_time_decode(ctts_gpt* h, int n_steps, float* ms_per_step, void* stream) {

@@ -129,6 +129,23 @@ struct SamplerCfgDev {      // mirrors ctts_sampler_cfg
     int max_new;
 };
 
+// Guided refine-text (include/ctts_hip.h ctts_gpt_set_text_guide): the call's free set and one record per OUTPUT SLOT (RowState.out), so the records follow an
+// utterance through compact / grow / cancel / admit like the log-prob buffers do.  A record is 4 KB: {n, -, cur, run} and the source ids behind them.
+#define CTTS_GUIDE_SLOTS 1024       // output slots that may carry a guide (a row at a higher slot is unguided)
+#define CTTS_GUIDE_MAX_SRC 1020     // source ids per utterance
+#define CTTS_GUIDE_MAX_FREE 64
+struct GuideRec {
+    int n;                  // source length; 0 = the utterance at this slot is unguided
+    int pad;
+    int cur, run;           // source ids emitted so far; free ids since the last source id (the sampler's, 8-byte aligned: one vector store)
+    int src[CTTS_GUIDE_MAX_SRC];
+};
+struct GuideTab {
+    int n_free, max_run, pad[2];
+    int free_ids[CTTS_GUIDE_MAX_FREE];
+    GuideRec rec[CTTS_GUIDE_SLOTS];
+};
+
 // Everything one generate()/sampler call may change without changing the launch geometry.  It lives in DEVICE memory
 // (ctts_gpt_begin rewrites it) and the kernels read it through the constant address space (scalar loads), so a captured
 // decode graph never bakes in a caller's buffers or sampling parameters and is replayed across calls.
@@ -146,6 +163,7 @@ struct SamplerDyn {
                             //   indexed by utterance when finished rows are compacted away
     float* lp_raw;          // [B][max_new][4] like `ids`, or null: log-probs of the sampled ids (ctts_gpt_set_logprob_out; begin resets both to null)
     float* lp_sampled;
+    GuideTab* guide;        // guided refine-text (text rows only), or null = off (begin / ctts_gpt_enable_text_rows reset it to null)
 };
 #define CTTS_CONST_AS __attribute__((address_space(4)))
 typedef const CTTS_CONST_AS SamplerDyn* SamplerDynPtr;
@@ -176,6 +194,7 @@ struct SamplerArgs {
     const RowSampling* seq_knobs;   // ctts_sampler_run_rows: [rows / 4] knobs per sequence (null: every row uses dyn->cfg)
     float* lp_raw_out;      // ctts_sampler_run_rows_lp: [rows] log-probs of idx_out (either may be null)
     float* lp_sampled_out;
+    int guided;             // generate mode, text kernel: the call has a guide (dyn->guide != null): sampler_text_kernel<true>
 };
 
 int launch_gemm(int dtype, int nbg, int pro, int epi, const GemmArgs& a, int chunks, hipStream_t s);
@@ -248,7 +267,7 @@ int launch_fill_meta(RowMeta* prefill_meta, RowMeta* decode_meta, DevState* st, 
                      hipStream_t s);
 int launch_embed_prompt(const int* ids, const int* text_mask, const float* emb_text, const float* emb_code, const float* spk, int spk_id,
                         float* out, int rows, int T, int V, int H, hipStream_t s);
-int launch_restart_rows(RowState* rows, int B, hipStream_t s);
+int launch_restart_rows(RowState* rows, int B, GuideTab* guide, hipStream_t s);      // guide (or null): the restarted rows' cursors go back to 0 as well
 // ctts_gpt_admit: n new utterances take over decode rows `rows[i]` (KV lanes `seqs[i]`); prompt rows (all but the last token) -> pm / rope_pre
 struct AdmitArgs {
     const int* mask;        // [n][T] device

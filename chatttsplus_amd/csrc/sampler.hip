@@ -471,6 +471,12 @@ __device__ inline unsigned long long block_max_u64_alt(BlockRed& r, unsigned lon
     return m;
 }
 
+// GUIDED (SamplerArgs.guided; include/ctts_hip.h "Guided refine-text"): a row whose OUTPUT SLOT carries a guide record (kernels.h GuideTab) samples from the
+// allowed set A of its step only.  Elements outside A are treated exactly as elements j >= V are -- not valid, -inf -- so only the <= 65 logits of A are loaded and
+// everything below the load is the unguided arithmetic over A.  The test is uniform over the block; a row without a record takes the unguided load.
+// GUIDED = false is the kernel as it was: every guided line is compiled out.  The body stays in the kernel on purpose: moved into an inlined device function the
+// unguided instantiation allocates 125 VGPRs instead of 116 (and spills 80 SGPRs instead of 54), so the stand-alone hook launches THIS kernel on a one-step state.
+template <bool GUIDED>
 __global__ __launch_bounds__(1024) void sampler_text_kernel(const SamplerArgs a) {
     __shared__ BlockRed red;
     __shared__ int pos_s;
@@ -490,11 +496,46 @@ __global__ __launch_bounds__(1024) void sampler_text_kernel(const SamplerArgs a)
     const float T = d->cfg.temperature[0];
     float x[TVPT];
     unsigned valid = 0;
+    // the record of the row's slot; its values are clamped to the record's extent, so a record that is being rewritten for the slot's next utterance while a
+    // finished row still samples cannot send a load out of bounds (a finished row stores nothing)
+    GuideRec* rec = nullptr;
+    int g_cur = 0, g_run = 0, standin = 0;       // standin: what the race returns when every ratio is 0 or NaN -- the id the automaton needs next, never id 0
+    bool at_end = false, eos_removable = true;
+    if (GUIDED) {
+        GuideTab* gt = d->guide;
+        if (gt != nullptr && seq >= 0 && seq < CTTS_GUIDE_SLOTS) {
+            const int4 gh = *(const int4*)&gt->rec[seq];
+            const int n = min(gh.x, CTTS_GUIDE_MAX_SRC);
+            if (n > 0) {
+                rec = &gt->rec[seq];
+                g_cur = min(max(gh.z, 0), n); g_run = max(gh.w, 0);
+                at_end = g_cur >= n;
+                standin = min(max(at_end ? d->cfg.eos : rec->src[g_cur], 0), V - 1);      // (the host checked the source ids against V: the clamp is never taken)
+                const int left = rs_in.limit - step;                                    // steps the row may still take, this one included
+                const bool free_ok = g_run < gt->max_run && (at_end ? (left > 1) : (left - (n - g_cur + 1) > 0));
+                const int nf = free_ok ? min(max(gt->n_free, 0), CTTS_GUIDE_MAX_FREE) : 0;
+                eos_removable = nf > 0;                                                 // min_new_token removes EOS only while another element of A remains
+                if ((standin & 1023) == tid) valid |= 1u << (standin >> 10);
+                for (int m = 0; m < nf; ++m) {
+                    const int j = gt->free_ids[m];
+                    if ((j & 1023) == tid) valid |= 1u << (j >> 10);
+                }
+            }
+        }
+    }
+    if (GUIDED && rec != nullptr) {
+#pragma unroll
+        for (int i = 0; i < TVPT; ++i) {
+            if (tid + 1024 * i >= V) valid &= ~(1u << i);                               // (the host checked every id of A against V: never taken)
+            x[i] = ((valid >> i) & 1u) ? __fdiv_rn(lg[tid + 1024 * i], T) : -INFINITY;
+        }
+    } else {
 #pragma unroll
     for (int i = 0; i < TVPT; ++i) {
         const int j = tid + 1024 * i;
         if (j < V) { x[i] = __fdiv_rn(lg[j], T); valid |= 1u << i; }          // gpt.py:469
         else x[i] = -INFINITY;
+    }
     }
     float mx = -INFINITY;
 #pragma unroll
@@ -613,7 +654,7 @@ __global__ __launch_bounds__(1024) void sampler_text_kernel(const SamplerArgs a)
     }
     }
     __syncthreads();                                                 // the last round's slot reads are done before `red` is reused
-    if (step < d->cfg.min_new && tid == (d->cfg.eos & 1023)) kept &= ~(1u << (d->cfg.eos >> 10));      // gpt.py:477-478
+    if (step < d->cfg.min_new && tid == (d->cfg.eos & 1023) && (!GUIDED || eos_removable)) kept &= ~(1u << (d->cfg.eos >> 10));      // gpt.py:477-478
     float m2 = -INFINITY;
 #pragma unroll
     for (int i = 0; i < TVPT; ++i) if ((kept >> i) & 1u) m2 = fmaxf(m2, x[i]);
@@ -638,11 +679,19 @@ __global__ __launch_bounds__(1024) void sampler_text_kernel(const SamplerArgs a)
                 qq = device_exp_noise(d->seed, rs_in.uid_lo, rs_in.uid_hi, 4u, (unsigned)step, (unsigned)rs_in.attempt, j);
             }
             const float e = expf(x[i] - m2);
-            bkey = umax64(bkey, ((unsigned long long)f32_key(__fdiv_rn(e * inv2, qq)) << 32) | (unsigned)(0x7FFFFFFF - j));
+            float ratio = __fdiv_rn(e * inv2, qq);
+            if (GUIDED && rec != nullptr && !(ratio > 0.f)) ratio = 0.f;      // a NaN ratio never wins a guided race (the stand-in rule below)
+            bkey = umax64(bkey, ((unsigned long long)f32_key(ratio) << 32) | (unsigned)(0x7FFFFFFF - j));
         }
     }
     bkey = block_max_u64(red, bkey, lane, wave);
-    const int idx = 0x7FFFFFFF - (int)(unsigned)bkey;
+    int idx = 0x7FFFFFFF - (int)(unsigned)bkey;
+    if (GUIDED && rec != nullptr) {
+        if ((unsigned)(bkey >> 32) <= f32_key(0.f)) idx = standin;            // every ratio 0 or NaN
+        // the automaton's step (uniform over the block): a source match takes precedence over the free set; EOS changes nothing (the row finishes)
+        if (!at_end && idx == standin) { g_cur += 1; g_run = 0; }
+        else if (idx != d->cfg.eos) g_run += 1;
+    }
     // next input = emb_text[idx]  (gpt.py:400-401); ids buffer keeps the reference's [.., num_vq] layout (gpt.py:492-494)
     for (int k = tid; k < a.H; k += 1024) a.x_next[(size_t)b * a.H + k] = a.emb_code[(size_t)idx * a.H + k];
     if (tid < CTTS_NUM_VQ && rs_in.fin == 0) d->ids[((size_t)seq * d->cfg.max_new + step) * CTTS_NUM_VQ + tid] = idx;      // (a finished row's tokens are never read: gpt.py:295-297)
@@ -654,6 +703,7 @@ __global__ __launch_bounds__(1024) void sampler_text_kernel(const SamplerArgs a)
         if (!fin) d->end_idx[seq] = end_out;
         fin = fin || (end_out >= rs_in.limit);                                        // the row's own token limit (<= max_new_token, the loop bound of gpt.py:389)
         if (!was) d->finish[seq] = eos ? 1 : 0;
+        if (GUIDED && rec != nullptr && !was) *(int2*)&rec->cur = make_int2(g_cur, g_run);      // the cursor of the row's next step (a finished row's slot may be another utterance's by now)
         ((int2*)(a.finend + b))[0] = make_int2(fin ? (eos ? 3 : 1) : 0, end_out);
         RowMeta m = a.meta[b];
         if (!was) { m.pos += 1; m.slot += 1; a.meta[b] = m; }                         // a finished row stays on its last slot (like the code sampler's rows)
@@ -732,7 +782,8 @@ int launch_sampler(const SamplerArgs& a, int blocks, hipStream_t s) {
     if (!a.text_mode && a.V > 64 * VPL) { ctts_set_error("sampler: vocab %d > %d", a.V, 64 * VPL); return 1; }
     if (a.st != nullptr && a.text_mode) {
         if (a.V > 1024 * TVPT) { ctts_set_error("text sampler: vocab %d > %d", a.V, 1024 * TVPT); return 1; }
-        hipLaunchKernelGGL(sampler_text_kernel, dim3(a.B), dim3(1024), 0, s, a);
+        if (a.guided) hipLaunchKernelGGL(sampler_text_kernel<true>, dim3(a.B), dim3(1024), 0, s, a);
+        else hipLaunchKernelGGL(sampler_text_kernel<false>, dim3(a.B), dim3(1024), 0, s, a);
     } else if (a.st != nullptr && a.mixed) hipLaunchKernelGGL(sampler_generate_kernel<true>, dim3(a.B), dim3(256), 0, s, (const int*)a.st, a.logits, a.dyn, (const RowMeta*)a.meta, a.V, (const int*)a.hist_ring, (const RowState*)a.finend, a);
     else if (a.st != nullptr) hipLaunchKernelGGL(sampler_generate_kernel<false>, dim3(a.B), dim3(256), 0, s, (const int*)a.st, a.logits, a.dyn, (const RowMeta*)a.meta, a.V, (const int*)a.hist_ring, (const RowState*)a.finend, a);
     else hipLaunchKernelGGL(sampler_rows_kernel, dim3(blocks), dim3(256), 0, s, a);
@@ -745,16 +796,18 @@ int launch_sampler(const SamplerArgs& a, int blocks, hipStream_t s) {
 // ensure_non_empty regenerate (gpt.py:496-525): every row starts over; a row that itself ended at step 0 moves on to its next noise
 // attempt, the others keep theirs (device noise: they re-draw the very token they drew before -- a row's result does not depend on
 // which other rows shared its batch)
-__global__ void restart_rows_kernel(RowState* rows, int B) {
+// A guided text row (kernels.h GuideTab; guide != null) starts its source over as well.
+__global__ void restart_rows_kernel(RowState* rows, int B, GuideTab* guide) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     RowState r = rows[b];
     r.attempt += (r.fin & 2) ? 1 : 0;
     r.fin = 0; r.end = 0;
     rows[b] = r;
+    if (guide != nullptr && r.out >= 0 && r.out < CTTS_GUIDE_SLOTS) *(int2*)&guide->rec[r.out].cur = make_int2(0, 0);
 }
-int launch_restart_rows(RowState* rows, int B, hipStream_t s) {
-    hipLaunchKernelGGL(restart_rows_kernel, dim3((B + 63) / 64), dim3(64), 0, s, rows, B);
+int launch_restart_rows(RowState* rows, int B, GuideTab* guide, hipStream_t s) {
+    hipLaunchKernelGGL(restart_rows_kernel, dim3((B + 63) / 64), dim3(64), 0, s, rows, B, guide);
     CTTS_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -694,7 +694,7 @@ def text_rows_cfg(text_rows, num_vq: int = 4) -> _lib.SamplerCfg:
     """open_session(text_rows=...): the refine pass's sampler configuration (infer_text = 1) from a dict or an object carrying TEXT_ROWS_KEYS -- built the way
     generate(infer_text=True) builds its own: gen_logits for top_P / top_K (no repetition penalty in this mode), sampler_cfg_from_objects for the rest"""
     if isinstance(text_rows, dict):
-        bad = sorted(set(text_rows) - set(TEXT_ROWS_KEYS))
+        bad = sorted(set(text_rows) - set(TEXT_ROWS_KEYS) - {"guide"})      # ("guide": a TextGuide, read by open_session itself)
         if bad:
             raise _lib.HipBackendError(f"open_session: text_rows: unknown key(s) {bad}; the keys are {list(TEXT_ROWS_KEYS)}")
         get = text_rows.get
@@ -706,6 +706,119 @@ def text_rows_cfg(text_rows, num_vq: int = 4) -> _lib.SamplerCfg:
     w, p = gen_logits(0, top_P=get("top_P", 0.7), top_K=get("top_K", 20), repetition_penalty=None)
     t = get("temperature", 0.7)
     return sampler_cfg_from_objects(0.7 if t is None else t, int(get("eos_token")), int(get("max_new_token")), int(get("min_new_token", 0) or 0), w, p, num_vq, infer_text=True)
+
+
+# -- guided refine-text (include/ctts_hip.h "Guided refine-text"): the host side of the contract, pure Python ------------------------------------------------------
+GUIDE_MAX_FREE, GUIDE_MAX_SRC, GUIDE_SLOTS = 64, 1020, 1024
+
+
+class TextGuide:
+    """The per-call part of a guide: `free_ids` (at most 64 distinct token ids the model may insert between source tokens -- [uv_break], [laugh], ...) and
+    `max_run`, the most consecutive free tokens allowed.  A guided text row emits its source ids in order, free ids interleaved, then EOS."""
+
+    def __init__(self, free_ids, max_run: int = 2):
+        ids = [int(i) for i in free_ids]
+        if len(ids) > GUIDE_MAX_FREE:
+            raise _lib.HipBackendError(f"TextGuide: {len(ids)} free ids (at most {GUIDE_MAX_FREE})")
+        if len(set(ids)) != len(ids):
+            raise _lib.HipBackendError("TextGuide: a free id is listed twice")
+        if any(i < 0 for i in ids):
+            raise _lib.HipBackendError("TextGuide: negative free id")
+        if int(max_run) < 0:
+            raise _lib.HipBackendError(f"TextGuide: max_run={max_run} (must be >= 0)")
+        self.free_ids, self.max_run = tuple(ids), int(max_run)
+
+    def check(self, eos: int, vocab: int, who: str = "text_guide") -> None:
+        """the refusals that need the call: a free id equal to EOS or outside the text vocabulary"""
+        for i in self.free_ids:
+            if i == int(eos):
+                raise _lib.HipBackendError(f"{who}: free id {i} is the EOS token (the guide ends a row by EOS alone)")
+            if i >= int(vocab):
+                raise _lib.HipBackendError(f"{who}: free id {i} outside 0..{int(vocab) - 1}")
+
+    def __repr__(self):
+        return f"TextGuide(free_ids={list(self.free_ids)}, max_run={self.max_run})"
+
+
+def check_guide_src(src, limit: int, eos: int, vocab: int, who: str = "guide_src") -> List[int]:
+    """One utterance's source ids as a list, or the refusal: empty, longer than the table's record, n + 1 > the row's limit, an id out of range or the EOS"""
+    ids = [int(i) for i in (src.tolist() if hasattr(src, "tolist") else src)]
+    n = len(ids)
+    if n < 1:
+        raise _lib.HipBackendError(f"{who}: an empty source (n == 0); pass None for an unguided utterance")
+    if n > GUIDE_MAX_SRC:
+        raise _lib.HipBackendError(f"{who}: a source of {n} ids (at most {GUIDE_MAX_SRC})")
+    if n + 1 > int(limit):
+        raise _lib.HipBackendError(f"{who}: a source of {n} ids needs {n + 1} tokens (the source and EOS), the row's limit is {int(limit)}")
+    for i in ids:
+        if i < 0 or i >= int(vocab):
+            raise _lib.HipBackendError(f"{who}: source id {i} outside 0..{int(vocab) - 1}")
+        if i == int(eos):
+            raise _lib.HipBackendError(f"{who}: source id {i} is the EOS token")
+    return ids
+
+
+def guide_free_ok(cur: int, run: int, t: int, limit: int, n: int, max_run: int) -> bool:
+    """May the row insert a free token at its own step t?  Only while the source still to come and the EOS fit behind it"""
+    if run >= max_run:
+        return False
+    if cur < n:
+        return (limit - t) - ((n - cur) + 1) > 0          # slack > 0
+    return limit - t > 1
+
+
+def guide_standin(cur: int, n: int, src, eos: int) -> int:
+    """the id the automaton needs next: what the race returns when every ratio is 0 or NaN"""
+    return int(src[cur]) if cur < n else int(eos)
+
+
+def guide_allowed(cur: int, run: int, t: int, limit: int, n: int, max_run: int, src, free_ids, eos: int) -> List[int]:
+    """The allowed set A of the row's step t, ascending: {src[cur]} (EOS once the source is out) plus the free set while guide_free_ok"""
+    a = {guide_standin(cur, n, src, eos)}
+    if guide_free_ok(cur, run, t, limit, n, max_run):
+        a.update(int(f) for f in free_ids)
+    return sorted(a)
+
+
+def guide_eos_removable(cur: int, run: int, t: int, limit: int, n: int, max_run: int, free_ids) -> bool:
+    """The min_new_token rule removes EOS only while another element of A remains (EOS is in A only once the source is out)"""
+    return len(free_ids) > 0 and guide_free_ok(cur, run, t, limit, n, max_run)
+
+
+def guide_step(cur: int, run: int, t: int, limit: int, n: int, max_run: int, idx: int, src=None, eos: int = -1):
+    """The automaton's update after the draw of `idx` at step t: (cur, run, finished).  A source match takes precedence when src[cur] is also a free id."""
+    if cur < n and int(idx) == int(src[cur]):
+        return cur + 1, 0, False
+    if int(idx) == int(eos):
+        return cur, run, True
+    return cur, run + 1, False
+
+
+def resolve_guides(text_guide, guide_src, n: int, infer_text: bool, eos: int, vocab: int, limits, who: str = "generate"):
+    """generate*(text_guide=, guide_src=): the sources per sequence (a list of n lists / None), or None when the call has no guide.  Refused here: a guide on a code
+    call, sources without the per-call part, a wrong count, and per sequence what check_guide_src refuses against the sequence's own limit."""
+    if text_guide is None:
+        if guide_src is not None and any(s is not None for s in guide_src):
+            raise _lib.HipBackendError(f"{who}: guide_src without text_guide (guides without the per-call part): pass text_guide=TextGuide(free_ids, max_run)")
+        return None
+    if not isinstance(text_guide, TextGuide):
+        raise _lib.HipBackendError(f"{who}: text_guide must be a TextGuide")
+    if not infer_text:
+        raise _lib.HipBackendError(f"{who}: text_guide is for the refine-text pass (infer_text=True); a guide on a code row is not offered")
+    text_guide.check(eos, vocab, who)
+    srcs = [None] * n if guide_src is None else list(guide_src)
+    if len(srcs) != n:
+        raise _lib.HipBackendError(f"{who}: guide_src has {len(srcs)} entries for {n} sequences")
+    return [None if s is None else check_guide_src(s, limits[i], eos, vocab, f"{who}: guide_src[{i}]") for i, s in enumerate(srcs)]
+
+
+def guide_arrays(slots, srcs):
+    """(out_slots, src_concat, src_off) int32 arrays of one ctts_gpt_set_guides call; srcs[i] None / empty = slot i is unguided (a fresh, empty record)"""
+    off, cat = [0], []
+    for s in srcs:
+        cat.extend([] if s is None else [int(i) for i in s])
+        off.append(len(cat))
+    return (np.ascontiguousarray(slots, dtype=np.int32), np.ascontiguousarray(cat if cat else [0], dtype=np.int32), np.ascontiguousarray(off, dtype=np.int32))
 
 
 @dataclass(repr=False, eq=False)
@@ -891,8 +1004,9 @@ class DecodeSession:
     code-mode session also serves refine-text utterances as text rows beside the code rows (submit(mode="text"); ctts_gpt_enable_text_rows)."""
 
     def __init__(self, gpt: "GPT", sc, seed: int, rows: int, out_slots: int, return_hidden: bool, return_logprobs: bool, ensure_non_empty: bool, max_restarts: int = 64,
-                 text_sc=None, own_slots: bool = False, admit_min: int = 1, share=None, hold=None):
+                 text_sc=None, own_slots: bool = False, admit_min: int = 1, share=None, hold=None, guide: Optional[TextGuide] = None):
         self.gpt, self.sc, self.seed = gpt, sc, int(seed)
+        self.guide = guide                         # guided refine-text: the call's TextGuide (text rows of a code session, or every row of an infer_text one)
         self.max_new = int(sc.max_new_token)
         self.text_sc = text_sc
         try:
@@ -909,7 +1023,7 @@ class DecodeSession:
         self.compactions: List[tuple] = []         # (steps launched, rows kept) per compaction
         self.shared_prompts: List[tuple] = []      # (rows, prompts) per begin / admit of a state with shared prompt passes
         self.launched = 0
-        self._req = {}                             # ticket -> (prompt [T, H] on the device, attended length n <= T, knobs or None, adapter slot or None, mode 0 / 1)
+        self._req = {}                             # ticket -> (prompt [T, H] on the device, attended length n <= T, knobs or None, adapter slot or None, mode 0 / 1, guide source or None)
         self._ring = ReportRing(2 * int(rows))      # the row reports of the two chunks in flight
         self._share, self._hold = share, hold
         self._adapters = False                     # an utterance of this session named an adapter slot: every admission names its rows' slots from then on
@@ -930,8 +1044,11 @@ class DecodeSession:
 
     # -- requests ---------------------------------------------------------------------------------
     def submit(self, emb: torch.Tensor, mask: torch.Tensor, utt_id: int, limit: Optional[int] = None, sampling=None, adapter_slot: Optional[int] = None,
-               mode: str = "code", stream: Optional[str] = None, stream_batch: Optional[int] = None, stream_hidden: bool = True, stream_lookback: int = 0) -> int:
-        """`stream_lookback` (stream="exact"): each window is vocoded from max(0, s0 - stream_lookback) (SessionWindow.v0), for a consumer that filters across
+               mode: str = "code", stream: Optional[str] = None, stream_batch: Optional[int] = None, stream_hidden: bool = True, stream_lookback: int = 0,
+               guide_src=None) -> int:
+        """`guide_src` (mode="text", sessions opened with text_rows=dict(..., guide=TextGuide)): the utterance's source token ids -- its result is provably these
+        ids in order with only the guide's free ids inserted, ended by EOS; None = it samples freely.
+        `stream_lookback` (stream="exact"): each window is vocoded from max(0, s0 - stream_lookback) (SessionWindow.v0), for a consumer that filters across
         window boundaries (the output resampler).  `stream` "exact" / "eager" (SessionBook): sample windows of this utterance become due while it decodes, see take_windows(); `stream_batch` tokens between
         windows (default: the session's); `stream_hidden` = the windows are vocoded from hidden rows (needs return_hidden), False = from the ids.
         Queues one utterance: emb [T, H] (GPT.__call__), mask [T] left padded.  `limit` <= max_new_token, `sampling` a dict as in sampling_per_row,
@@ -947,6 +1064,13 @@ class DecodeSession:
             raise _lib.HipBackendError("submit: per-utterance sampling parameters are for code utterances; a text utterance keeps the session's text_rows values")
         if stream is not None and mode == "text":
             raise _lib.HipBackendError("submit: stream= is for code utterances; a text row produces no audio")
+        if guide_src is not None:
+            if mode != "text":
+                raise _lib.HipBackendError("submit: guide_src is for text utterances (mode=\"text\"); a guide on a code row is not offered")
+            if self.guide is None:
+                raise _lib.HipBackendError("submit: guide_src needs a session opened with text_rows=dict(..., guide=TextGuide(...)) (guides without the per-call part)")
+            tmax = int(self.text_sc.max_new_token)
+            guide_src = check_guide_src(guide_src, tmax if limit is None else min(max(int(limit), 1), tmax), int(self.text_sc.eos_token), g.num_text_tokens, "submit: guide_src")
         if stream is not None and stream_hidden and self.hid is None:
             raise _lib.HipBackendError("submit: stream= vocodes hidden rows: open the session with return_hidden=True (or pass stream_hidden=False to stream from the ids)")
         emb = torch.as_tensor(emb)
@@ -962,20 +1086,20 @@ class DecodeSession:
         if slot >= 0 and g.invariant_option():
             raise _lib.HipBackendError(f"submit: per-utterance adapters are outside the {g.invariant_option()} contract; merge the adapter (with_lora) or set the option to 0")
         tk = self._enqueue(emb[emb.shape[0] - n:].to(g.device, dtype=torch.float32).contiguous(), n, utt_id, limit, knobs, slot if slot >= 0 else None, mode,
-                           stream, stream_batch, stream_lookback)
+                           stream, stream_batch, stream_lookback, guide_src=guide_src)
         if stream is not None:
             self._stream_mode[tk] = stream
         return tk
 
     def _enqueue(self, prompt: torch.Tensor, n: int, utt_id: int, limit, knobs, adapter: Optional[int], mode: str = "code", stream=None, stream_batch=None,
-                 stream_lookback: int = 0) -> int:
+                 stream_lookback: int = 0, guide_src=None) -> int:
         """One ticket: `prompt` [T, H] on the device, of which the last `n` rows are attended (rows before them are the caller's left padding); `adapter` None =
         the utterance names none (an int, -1 included, makes every later seating name its rows' slots)"""
         try:
             tk = self.book.submit(max(int(n), 1), utt_id, limit, mode, stream=stream, stream_batch=stream_batch, stream_lookback=stream_lookback)
         except ValueError as e:
             raise _lib.HipBackendError(str(e)) from None
-        self._req[tk] = (prompt, int(n), knobs, adapter, 1 if mode == "text" else 0)
+        self._req[tk] = (prompt, int(n), knobs, adapter, 1 if mode == "text" else 0, guide_src)
         if adapter is not None and not self._adapters:
             self._adapters = True
             if self._hold is not None:
@@ -1030,7 +1154,11 @@ class DecodeSession:
             base = row_sampling_from_values(self.sc, None, g.num_vq)
             knobs = (_lib.RowSampling * k)(*[req[tk][2] or base for tk in tks])
         modes = arr([req[tk][4] for tk in tks])
+        guide = getattr(self, "guide", None)        # guided refine-text: every seated slot is named, so a re-used slot never keeps its predecessor's record
+        gsrcs = [req[tk][5] for tk in tks] if guide is not None else None
         if not begin:
+            if guide is not None:
+                g._set_guides(st, outs.tolist(), gsrcs)
             if slots is not None:
                 _lib.check(lib.ctts_gpt_admit_adapters(h, k, ptr(rows), ptr(slots), st), "admit_adapters")
             if knobs is not None:         # (re-admissions of ensure_non_empty included: the utterance keeps its own knobs)
@@ -1046,7 +1174,8 @@ class DecodeSession:
             self.admissions.append((self.launched, k))
             return
         g._begin_state(st, k, Ta, mask, emb, self.sc, self.out.io(self.max_new, self.seed, uids, lims), self.out, knobs=knobs, modes=modes if modes.any() else None,
-                       adapters=None if slots is None else slots.tolist(), share=share, text_sc=self.text_sc)
+                       adapters=None if slots is None else slots.tolist(), share=share, text_sc=self.text_sc,
+                       guide=None if guide is None else (guide, outs.tolist(), gsrcs))
         _lib.check(lib.ctts_gpt_sample(h, st), "sample")
         self.launched = 1
         self.batch_trace.append((self.launched, k))
@@ -1503,8 +1632,10 @@ class GPT:
                  min_new_token=0, logits_warpers=[], logits_processors=[], infer_text=False, return_attn=False,
                  return_hidden=False, stream=False, show_tqdm=True, ensure_non_empty=True, stream_batch=24,
                  context=None, noise="auto", seed: Optional[int] = None, max_restarts: int = 64, utt_ids=None, max_new_tokens_per_row=None,
-                 sampling_per_row=None, return_logprobs=False, prompt_of=None):
-        """`prompt_of` (shared prompt passes, ctts_gpt_share_prompts; code mode): a list of length B naming each sequence's prompt; `emb` / `inputs_ids` /
+                 sampling_per_row=None, return_logprobs=False, prompt_of=None, text_guide=None, guide_src=None):
+        """`text_guide` (a TextGuide; infer_text=True) with `guide_src` = one list of source token ids or None per sequence: a guided sequence's ids are provably
+        its source ids in order, with only the guide's free ids inserted, ended by EOS (include/ctts_hip.h "Guided refine-text"); None = the sequence samples freely.
+        `prompt_of` (shared prompt passes, ctts_gpt_share_prompts; code mode): a list of length B naming each sequence's prompt; `emb` / `inputs_ids` /
         `attention_mask` then have one row per PROMPT, every per-row argument (`utt_ids`, `max_new_tokens_per_row`, `sampling_per_row`) and every output has length
         B.  The first sequence of a prompt runs the prompt pass, the others receive a copy of its KV lane; `shared_prompts` records (rows, prompts) of the call.
         `return_logprobs`: every yielded GenerationOutputs (the partial ones of stream=True too) carries `logprobs`, `sampled_logprobs` and
@@ -1531,13 +1662,30 @@ class GPT:
                                     max_new_token=max_new_token, min_new_token=min_new_token, logits_warpers=logits_warpers, logits_processors=logits_processors,
                                     infer_text=infer_text, noise=noise, seed=seed, utt_ids=utt_ids, row_limits=max_new_tokens_per_row,
                                     sampling_per_row=sampling_per_row, prompt_of=prompt_of)
+            limits = [int(call.sc.max_new_token)] * call.B if call.row_limits is None else [min(max(int(v), 1), int(call.sc.max_new_token)) for v in call.row_limits]
+            srcs = resolve_guides(text_guide, guide_src, call.B, bool(infer_text), int(call.sc.eos_token), self.num_text_tokens, limits, "generate")
             yield from self._generate(call, emb, inputs_ids, attention_mask, context or Context(), stream, stream_batch, ensure_non_empty, max_restarts,
-                                      return_hidden, bool(return_logprobs))
+                                      return_hidden, bool(return_logprobs), guide=None if srcs is None else (text_guide, list(range(call.B)), srcs))
 
-    def _begin_state(self, st, k: int, T: int, mask, emb, sc, io, out: OutBuffers, knobs=None, modes=None, adapters=None, share=None, text_sc=None) -> None:
+    def _set_text_guide(self, st, tg: TextGuide) -> None:
+        f = np.ascontiguousarray(list(tg.free_ids) or [0], dtype=np.int32)
+        _lib.check(self._lib.ctts_gpt_set_text_guide(self._h, f.ctypes.data_as(C.c_void_p), len(tg.free_ids), tg.max_run, st), "set_text_guide")
+
+    def _set_guides(self, st, slots, srcs) -> None:
+        """Names the sources of the utterances at output `slots` (srcs[i] None = unguided: a fresh, empty record).  A slot beyond the guide table carries no record
+        and needs none while it is unguided; a guided one there is refused by the engine."""
+        named = [(int(s), src) for s, src in zip(slots, srcs) if src is not None or int(s) < GUIDE_SLOTS]
+        if not named:
+            return
+        sl, cat, off = guide_arrays([s for s, _ in named], [src for _, src in named])
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _lib.check(self._lib.ctts_gpt_set_guides(self._h, len(named), p(sl), p(cat), p(off), st), "set_guides")
+
+    def _begin_state(self, st, k: int, T: int, mask, emb, sc, io, out: OutBuffers, knobs=None, modes=None, adapters=None, share=None, text_sc=None, guide=None) -> None:
         """Creates a generate state for k rows (generate() and a session's first seating): stages `adapters` (slot per row; sticky: the caller's EngineHold resets
-        it), `knobs` (ctts_row_sampling [k]), `modes` (int32 [k]) and `share` (prompt per row int32 [k], prompts), then ctts_gpt_begin, the text rows, the log-prob
-        outputs of `out` and the prompt pass.  Nothing staged for a begin outlives it, whether or not begin took it: a later plain call finds nothing pending."""
+        it), `knobs` (ctts_row_sampling [k]), `modes` (int32 [k]) and `share` (prompt per row int32 [k], prompts), then ctts_gpt_begin, the text rows, the guide
+        (`guide` = (TextGuide, output slots, sources or None per slot)), the log-prob outputs of `out` and the prompt pass.  Nothing staged for a begin outlives
+        it, whether or not begin took it: a later plain call finds nothing pending."""
         lib, h = self._lib, self._h
         try:
             if adapters is not None:
@@ -1555,6 +1703,9 @@ class GPT:
             lib.ctts_gpt_share_prompts(h, 0, None, 0)
         if text_sc is not None:                    # (after begin, which creates the state; before the first sample, which a begun text row needs it for)
             _lib.check(lib.ctts_gpt_enable_text_rows(h, C.byref(text_sc), out.tids.data_ptr(), st), "enable_text_rows")
+        if guide is not None:                      # (after the text rows; before the first sample: begin's guided rows start from their records)
+            self._set_text_guide(st, guide[0])
+            self._set_guides(st, guide[1], guide[2])
         if out.lps is not None:
             _lib.check(lib.ctts_gpt_set_logprob_out(h, out.lps[0].data_ptr(), out.lps[1].data_ptr(), st), "set_logprob_out")
         _lib.check(lib.ctts_gpt_prefill(h, emb.data_ptr(), st), "prefill")
@@ -1567,7 +1718,7 @@ class GPT:
         _lib.check(self._lib.ctts_gpt_progress(self._h, C.byref(steps), C.byref(alld), st), "progress")
         return steps.value
 
-    def _generate(self, call, emb, inputs_ids, attention_mask, context, stream, stream_batch, ensure_non_empty, max_restarts, return_hidden, return_logprobs):
+    def _generate(self, call, emb, inputs_ids, attention_mask, context, stream, stream_batch, ensure_non_empty, max_restarts, return_hidden, return_logprobs, guide=None):
         """generate() on a held engine: setup, step 0 with its restarts, the streamed or the pipelined loop, the end of the state"""
         lib, h, dev, B, T = self._lib, self._h, self.device, call.B, int(inputs_ids.shape[1])
         infer_text, max_new = bool(call.sc.infer_text), int(call.sc.max_new_token)
@@ -1588,7 +1739,7 @@ class GPT:
         with torch.cuda.device(dev):
             st = self._stream()
             tick("setup")
-            self._begin_state(st, B, T, mask, emb, call.sc, io, out, knobs=call.knobs, share=call.share)
+            self._begin_state(st, B, T, mask, emb, call.sc, io, out, knobs=call.knobs, share=call.share, guide=guide)
             tick("begin+prefill")
             # step 0 with the batch-wide ensure_non_empty regenerate (gpt.py:496-525): while a sequence's first token is EOS, every sequence samples again
             used, steps, alld = 0, C.c_int32(0), C.c_int32(0)
@@ -1678,7 +1829,8 @@ class GPT:
                       attention_mask: Optional[torch.Tensor] = None, max_new_token=2048, min_new_token=0, logits_warpers=[],
                       logits_processors=[], return_hidden=False, ensure_non_empty=True, context=None, seed: Optional[int] = None,
                       max_restarts: int = 64, utt_ids=None, max_new_tokens_per_row=None, rows: Optional[int] = None, admit_min: Optional[int] = None,
-                      on_done=None, infer_text: bool = False, adapter_slots=None, sampling_per_row=None, return_logprobs=False, prompt_of=None) -> GenerationOutputs:
+                      on_done=None, infer_text: bool = False, adapter_slots=None, sampling_per_row=None, return_logprobs=False, prompt_of=None,
+                      text_guide=None, guide_src=None) -> GenerationOutputs:
         """N utterances (left-padded prompts emb[N,T,H], like generate()) through `rows` <= max_batch decode rows: whenever utterances
         finish, queued ones take over their rows (ctts_gpt_admit) instead of the whole slice waiting for its slowest row as the reference's
         slices of 4 do (pipeline:391-397, gpt.py:527-546); once the queue is empty finished rows are compacted away (ctts_gpt_compact).
@@ -1699,7 +1851,8 @@ class GPT:
                                       min_new_token=min_new_token, logits_warpers=logits_warpers, logits_processors=logits_processors,
                                       return_hidden=return_hidden, ensure_non_empty=ensure_non_empty, context=context, seed=seed, max_restarts=max_restarts,
                                       utt_ids=utt_ids, max_new_tokens_per_row=max_new_tokens_per_row, rows=rows, admit_min=admit_min, infer_text=infer_text,
-                                      adapter_slots=adapter_slots, sampling_per_row=sampling_per_row, return_logprobs=return_logprobs, prompt_of=prompt_of)
+                                      adapter_slots=adapter_slots, sampling_per_row=sampling_per_row, return_logprobs=return_logprobs, prompt_of=prompt_of,
+                                      text_guide=text_guide, guide_src=guide_src)
         try:
             while True:
                 ev = next(gen)
@@ -1712,8 +1865,9 @@ class GPT:
     def generate_many_iter(self, emb, inputs_ids, temperature, eos_token, attention_mask=None, max_new_token=2048, min_new_token=0, logits_warpers=[],
                            logits_processors=[], return_hidden=False, ensure_non_empty=True, context=None, seed=None, max_restarts: int = 64,
                            utt_ids=None, max_new_tokens_per_row=None, rows=None, admit_min=None, infer_text: bool = False, progress: bool = False,
-                           adapter_slots=None, sampling_per_row=None, return_logprobs=False, prompt_of=None):
-        """generate_many as a generator: yields [(utterance index, ids [n,4] long, hiddens [n,768] or None)] for the utterances that completed
+                           adapter_slots=None, sampling_per_row=None, return_logprobs=False, prompt_of=None, text_guide=None, guide_src=None):
+        """`text_guide` / `guide_src`: as in generate() (infer_text=True): an admitted utterance brings its own source (ctts_gpt_set_guides before its admit).
+        generate_many as a generator: yields [(utterance index, ids [n,4] long, hiddens [n,768] or None)] for the utterances that completed
         since the last yield -- while the rest keeps decoding (what was yielded is final: its rows were written before the report that showed
         the utterance finished) -- and returns (StopIteration.value) the GenerationOutputs of all N utterances.
         `infer_text=True`: the refine-text pass (gpt.py infer_text: the 21178-way text head, one id per step) through the same row re-use; ids are [n].
@@ -1727,11 +1881,11 @@ class GPT:
             return (yield from self._generate_many(emb, inputs_ids, temperature, eos_token, attention_mask, int(max_new_token), min_new_token, logits_warpers,
                                                    logits_processors, return_hidden, ensure_non_empty, context or Context(), seed, max_restarts, utt_ids,
                                                    max_new_tokens_per_row, rows, admit_min, bool(infer_text), bool(progress), adapter_slots,
-                                                   sampling_per_row, bool(return_logprobs), prompt_of))
+                                                   sampling_per_row, bool(return_logprobs), prompt_of, text_guide, guide_src))
 
     def _generate_many(self, emb, inputs_ids, temperature, eos_token, attention_mask, max_new_token, min_new_token, logits_warpers, logits_processors,
                        return_hidden, ensure_non_empty, context, seed, max_restarts, utt_ids, row_limits, rows, admit_min, infer_text=False, progress=False,
-                       adapter_slots=None, sampling_per_row=None, return_logprobs=False, prompt_of=None):
+                       adapter_slots=None, sampling_per_row=None, return_logprobs=False, prompt_of=None, text_guide=None, guide_src=None):
         """The request as a client of the DecodeSession driver: prepares the utterances, submits them in their order of service (position j of that order is
         ticket j and output slot j) and translates what the driver delivers into generate_many_iter's events"""
         dev = self.device
@@ -1757,6 +1911,7 @@ class GPT:
         uids = [int(u) for u in utt_ids] if utt_ids is not None else list(range(N))
         lims = [min(max(int(v), 1), max_new_token) for v in row_limits] if row_limits is not None else [max_new_token] * N
         assert len(uids) == N and len(lims) == N
+        srcs = resolve_guides(text_guide, guide_src, N, infer_text, int(eos_token), self.num_text_tokens, lims, "generate_many")
         slots = [None] * N
         if adapter_slots is not None:
             slots = [-1 if a is None or int(a) < 0 else int(a) for a in adapter_slots]
@@ -1772,11 +1927,11 @@ class GPT:
         else:
             back = list(range(N))                                  # ticket (= output slot) -> utterance index: every index handed back is mapped through it
         with torch.cuda.device(dev):
-            ses = DecodeSession(self, sc, seed, R, N, return_hidden, return_logprobs, ensure_non_empty, max_restarts, own_slots=True, admit_min=admit_min,
+            ses = DecodeSession(self, sc, seed, R, N, return_hidden, return_logprobs, ensure_non_empty, max_restarts, own_slots=True, admit_min=admit_min, guide=None if srcs is None else text_guide,
                                 share=None if pof is None else ([pof[u] for u in back], n_prompts, [slots[u] for u in back] if adapter_slots is not None else None))
             self.admissions, self.compactions, self.shared_prompts = ses.admissions, ses.compactions, ses.shared_prompts
             for u in back:
-                ses._enqueue(emb[u if pof is None else pof[u]], lens[u], uids[u], lims[u], knobs[u], slots[u])
+                ses._enqueue(emb[u if pof is None else pof[u]], lens[u], uids[u], lims[u], knobs[u], slots[u], guide_src=None if srcs is None else srcs[u])
 
             def event(r, n=None):
                 """one utterance of a yielded list: (index[, tokens so far], ids, hiddens[, its GenerationOutputs so far])"""
@@ -1821,13 +1976,18 @@ class GPT:
             raise _lib.HipBackendError(f"open_session: out_slots={out_slots} (at least one)")
         sc = sampler_cfg_from_objects(temperature, int(eos_token), int(max_new_token), min_new_token, logits_warpers, logits_processors, self.num_vq)
         text_sc = text_rows_cfg(text_rows, self.num_vq) if text_rows is not None else None
+        guide = None if text_rows is None else (text_rows.get("guide") if isinstance(text_rows, dict) else getattr(text_rows, "guide", None))
+        if guide is not None:
+            if not isinstance(guide, TextGuide):
+                raise _lib.HipBackendError("open_session: text_rows: guide must be a TextGuide")
+            guide.check(int(text_sc.eos_token), self.num_text_tokens, "open_session: text_rows: guide")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         hold = self._hold("GPT.open_session: GPT.generate is already running on this engine (or on an engine sharing its KV cache): exhaust or close "
                           "the previous generator / session first")
         try:
             with torch.cuda.device(self.device):
-                ses = DecodeSession(self, sc, seed, rows, out_slots, bool(return_hidden), bool(return_logprobs), bool(ensure_non_empty), text_sc=text_sc, hold=hold)
+                ses = DecodeSession(self, sc, seed, rows, out_slots, bool(return_hidden), bool(return_logprobs), bool(ensure_non_empty), text_sc=text_sc, hold=hold, guide=guide)
         except BaseException:
             hold.release()
             raise

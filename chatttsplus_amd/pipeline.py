@@ -68,7 +68,7 @@ class TorchSeedContext:                        # reference commons/utils.py:48-5
 
 # gen_logits and its scalar carriers live beside the sampler configuration they feed (hip_models/gpt.py): one conversion for a call's knobs and for an
 # utterance's (sampling_per_row)
-from .hip_models.gpt import LORA_TARGETS, _RepPenalty, _TopK, _TopP, check_lora_shapes, gen_logits, refuse_out_of_scope  # noqa: E402,F401
+from .hip_models.gpt import LORA_TARGETS, TextGuide, _RepPenalty, _TopK, _TopP, check_lora_shapes, gen_logits, refuse_out_of_scope  # noqa: E402,F401
 from .hip_models.vocoder import prefix_samples, prefix_tokens  # noqa: E402
 
 
@@ -165,6 +165,65 @@ def _decode_refined(tok, ids_list) -> List[str]:
     return tok.decode([i[i.less(tok.break_0_ids)] for i in ids_list])
 
 
+# -- guided refine-text (refine_guided=; GPT TextGuide): the refined text is provably the submitted tokens, with only prosody tokens inserted ----------------------
+REFINE_FREE_TOKENS = ("[uv_break]", "[v_break]", "[lbreak]", "[llbreak]", "[laugh]")
+
+
+def _token_id(tok, name: str) -> Optional[int]:
+    """the id of a token the tokenizer knows, None for a name that maps to the unknown id"""
+    bt = tok._tokenizer
+    i = bt.convert_tokens_to_ids(name)
+    return None if i is None or i == getattr(bt, "unk_token_id", None) else int(i)
+
+
+def default_text_guide(tok, max_run: int = 2) -> TextGuide:
+    """refine_guided=True: the free set is the ids of REFINE_FREE_TOKENS the tokenizer knows (names that map to the unknown id are skipped; none left is an error)"""
+    ids = [i for i in (_token_id(tok, n) for n in REFINE_FREE_TOKENS) if i is not None]
+    if not ids:
+        raise _lib.HipBackendError(f"refine_guided=True: the tokenizer knows none of {list(REFINE_FREE_TOKENS)}; pass a TextGuide(free_ids, max_run)")
+    return TextGuide(list(dict.fromkeys(ids)), max_run)
+
+
+def resolve_refine_guided(value, tok) -> Optional[TextGuide]:
+    """refine_guided = False / None | True | TextGuide -> the guide of the refine pass, or None"""
+    if value is None or value is False:
+        return None
+    if value is True:
+        return default_text_guide(tok)
+    if isinstance(value, TextGuide):
+        return value
+    raise _lib.HipBackendError(f"refine_guided={value!r} (False, True or a TextGuide)")
+
+
+def refine_sources(tok, input_ids, attention_mask) -> List[List[int]]:
+    """The source of every row of a refine prompt, read off the prompt's own ids: the ids strictly between [Sbreak] and [Pbreak] of the row's attended tokens --
+    the very tokenisation the model sees.  input_ids [B, T] or [B, T, num_vq] (left padded), attention_mask [B, T]."""
+    sb, pb = _token_id(tok, "[Sbreak]"), _token_id(tok, "[Pbreak]")
+    if sb is None or pb is None:
+        raise _lib.HipBackendError("refine_guided: the tokenizer does not know [Sbreak] / [Pbreak]")
+    ids = torch.as_tensor(input_ids).cpu()
+    ids = ids[..., 0] if ids.dim() == 3 else ids
+    att = torch.as_tensor(attention_mask).cpu()
+    out = []
+    for r in range(ids.shape[0]):
+        row = ids[r][att[r] != 0].tolist()
+        if sb not in row or pb not in row[row.index(sb) + 1:]:
+            raise _lib.HipBackendError(f"refine_guided: row {r} of the refine prompt has no [Sbreak] ... [Pbreak] span")
+        a = row.index(sb)
+        out.append([int(i) for i in row[a + 1: row.index(pb, a + 1)]])
+    return out
+
+
+def check_refine_sources(srcs, max_new_token: int, what: str = "refine_guided") -> None:
+    """by utterance: an empty sentence, or a max_new_token below the sentence's n + 1 (its tokens and [Ebreak])"""
+    for u, s in enumerate(srcs):
+        if len(s) < 1:
+            raise _lib.HipBackendError(f"{what}: utterance {u} has no token between [Sbreak] and [Pbreak]")
+        if int(max_new_token) < len(s) + 1:
+            raise _lib.HipBackendError(f"{what}: utterance {u} has {len(s)} tokens and needs max_new_token >= {len(s) + 1} (its tokens and [Ebreak]); "
+                                       f"params_refine_text.max_new_token is {int(max_new_token)}")
+
+
 def _draw_request_seed() -> int:
     """A request's device-noise seed where the caller names none: ONE draw from torch's CPU generator (torch.manual_seed / TorchSeedContext reproduce the request)."""
     return int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -202,6 +261,8 @@ class _Request:
     n_cand: int; return_details: bool; select: Optional[Callable]; share_prompt: Optional[bool]; ids_sink: Optional[list]
     overlap_vocoder: bool; vocoder_chunk: object
     sample_rate: Optional[int] = None                   # infer(sample_rate=): the rate the waveforms leave at; None = the vocoder's own 24 kHz
+    refine_guide: Optional[TextGuide] = None            # infer(refine_guided=): the refine pass's guide (resolve_refine_guided); None = free sampling, as ever
+    guide_kw = property(lambda self: {} if self.refine_guide is None else dict(guide=self.refine_guide))      # _refine_text's extra keyword: none without a guide (the call as it was)
     device_noise = property(lambda self: self.n_cand > 1 or self.noise_mode == "device")      # (details path) device noise whatever the slice's size
 
     def rows(self, idx, adapters: bool = False, params: bool = True) -> dict:
@@ -351,9 +412,12 @@ class SynthSession:
     are slices of different prefix waveforms: no single waveform to resample, refused."""
 
     def __init__(self, pipe, gpt, params: InferCodeParams, use_decoder: bool, rows, seed, return_details: bool, refine: Optional[RefineTextParams] = None,
-                 sample_rate: Optional[int] = None):
+                 sample_rate: Optional[int] = None, refine_guided=False):
         self.pipe, self.gpt, self.params, self.use_decoder, self.return_details = pipe, gpt, params, bool(use_decoder), bool(return_details)
         self.refine = refine
+        self.refine_guide = resolve_refine_guided(refine_guided, pipe.models_dict["tokenizer"])      # the refine stage's guide; None = free sampling
+        if self.refine_guide is not None and refine is None:
+            raise _lib.HipBackendError("open_session: refine_guided needs refine=RefineTextParams(...)")
         self.sample_rate = None if sample_rate is None else pipe.output_rate(sample_rate, "open_session")      # None: the vocoder's own 24 kHz
         self._rates = {}                           # code-stage ticket -> its output rate (tickets at 24 kHz are not in it)
         self._emitted = {}                         # code-stage ticket of a resampled "exact" utterance -> J, the output samples emitted so far
@@ -364,6 +428,8 @@ class SynthSession:
                 raise _lib.HipBackendError("open_session: refine.repetition_penalty must be 1 (the refine-text pass supports no repetition penalty)")
             text_rows = dict(temperature=refine.temperature, top_P=refine.top_P, top_K=refine.top_K, eos_token=pipe.models_dict["tokenizer"].eos_token,
                              max_new_token=refine.max_new_token, min_new_token=refine.min_new_token)
+            if self.refine_guide is not None:
+                text_rows["guide"] = self.refine_guide
         self.session = gpt.open_session(torch.tensor(temperature), num_code, params.max_new_token, min_new_token=params.min_new_token, logits_warpers=warpers,
                                         logits_processors=processors, return_hidden=self.use_decoder, return_logprobs=self.return_details, seed=seed, rows=rows,
                                         ensure_non_empty=params.ensure_non_empty, text_rows=text_rows)
@@ -390,8 +456,10 @@ class SynthSession:
 
     def submit(self, text: str, params=None, lora_path: Optional[str] = None, utt_id: Optional[int] = None, max_new_token: Optional[int] = None,
                refine: Optional[bool] = None, stream: Optional[str] = None, stream_batch: Optional[int] = None, pcm16: bool = False,
-               sample_rate: Optional[int] = None) -> int:
-        """`sample_rate`: this utterance's output rate in Hz (default: the session's; 24000 = the vocoder's own, today's path): with stream=None or "exact".
+               sample_rate: Optional[int] = None, refine_guided: Optional[bool] = None) -> int:
+        """`refine_guided` (None = as the session was opened): guide this utterance's refine stage by its own tokens (True needs a session opened with
+        refine_guided=); False = it samples freely.
+        `sample_rate`: this utterance's output rate in Hz (default: the session's; 24000 = the vocoder's own, today's path): with stream=None or "exact".
         `stream` "exact" or "eager": poll() returns this ticket's audio as SessionChunks while it decodes (class docstring; "exact" is the one to use unless the
         reference's windows are wanted); `stream_batch`: tokens between chunks (default: the session's params.stream_batch); `pcm16`: its chunks are int16 PCM.
         Queues one text.  `params`: this utterance's overrides (an InferCodeParams or a dict, checked by per_utterance_overrides: sampling knobs,
@@ -435,8 +503,15 @@ class SynthSession:
             # stage 1: the refine prompt as a text row (pipeline:237-277).  No per-utterance adapter: infer() refines on the base weights (_refine_text); a session
             # opened with lora_path runs on the merged engine in both stages
             input_ids, attention_mask, text_mask = pipe._refine_prompt([t], self.refine)
+            guided = (self.refine_guide is not None) if refine_guided is None else bool(refine_guided)
+            if guided and self.refine_guide is None:
+                raise _lib.HipBackendError("submit: refine_guided=True needs a session opened with refine_guided=True | TextGuide(...)")
+            src = None
+            if guided:
+                src = refine_sources(pipe.models_dict["tokenizer"], input_ids, attention_mask)[0]
+                check_refine_sources([src], self.refine.max_new_token, "submit: refine_guided")
             emb = gpt(input_ids, text_mask)
-            tk = self.session.submit(emb[0], attention_mask[0], int(utt_id), mode="text")
+            tk = self.session.submit(emb[0], attention_mask[0], int(utt_id), mode="text", **({} if src is None else dict(guide_src=src)))
             self._refining[tk] = dict(diff=diff, slot=slot, utt_id=int(utt_id), streaming=streaming, rate=rate)      # (the refine stage streams nothing)
             return tk
         return self._submit_code(t, diff, slot, int(utt_id), streaming, rate)
@@ -977,19 +1052,25 @@ class ChatTTSPlusPipeline:
         return tok.encode([f"[Sbreak]{i}[Pbreak]{params.prompt}" for i in text], gpt.num_vq, device=self.device)
 
     @torch.no_grad()
-    def _refine_text(self, text, params: RefineTextParams, continuous_rows: int = 0, seed=None, utt_ids=None):
+    def _refine_text(self, text, params: RefineTextParams, continuous_rows: int = 0, seed=None, utt_ids=None, guide: Optional[TextGuide] = None):
         """pipeline:237-277: "[Sbreak]{text}[Pbreak]{prompt}" -> GPT.generate(infer_text=True) on the 21178-way text head.
         `continuous_rows` > 0 (no counterpart in the reference, which refines slice by slice): all sentences of the request through that many decode
-        rows with row re-use (GPT.generate_many, device noise keyed by utterance id: a sentence's refined text does not depend on its neighbours)."""
+        rows with row re-use (GPT.generate_many, device noise keyed by utterance id: a sentence's refined text does not depend on its neighbours).
+        `guide` (refine_guided=): every sentence is guided by its own tokens, read off the refine prompt (refine_sources)."""
         gpt, tok = self.models_dict["gpt"], self.models_dict["tokenizer"]
         input_ids, attention_mask, text_mask = self._refine_prompt(text, params)
+        gkw = {}
+        if guide is not None:
+            srcs = refine_sources(tok, input_ids, attention_mask)
+            check_refine_sources(srcs, params.max_new_token)
+            gkw = dict(text_guide=guide, guide_src=srcs)
         warpers, processors = gen_logits(num_code=tok.len, top_P=params.top_P, top_K=params.top_K, repetition_penalty=params.repetition_penalty)
         emb = gpt(input_ids, text_mask)
         kw = dict(temperature=torch.tensor([params.temperature]), eos_token=tok.eos_token, attention_mask=attention_mask, max_new_token=params.max_new_token,
                   min_new_token=params.min_new_token, logits_warpers=warpers, logits_processors=processors, ensure_non_empty=params.ensure_non_empty, infer_text=True)
         if continuous_rows > 0:
-            return gpt.generate_many(emb, input_ids, seed=seed, utt_ids=utt_ids, rows=continuous_rows, **kw)
-        return next(gpt.generate(emb, input_ids, stream=False, show_tqdm=params.show_tqdm, **kw))
+            return gpt.generate_many(emb, input_ids, seed=seed, utt_ids=utt_ids, rows=continuous_rows, **kw, **gkw)
+        return next(gpt.generate(emb, input_ids, stream=False, show_tqdm=params.show_tqdm, **kw, **gkw))
 
     def _codes_synth(self):
         """The "decode codes" model of use_decoder=False (pipeline:292: decoder = models_dict["dvae_encode"], i.e. the DVAE_full checkpoint
@@ -1191,7 +1272,8 @@ class ChatTTSPlusPipeline:
                         noise_seed=kwargs.get("noise_seed"), use_decoder=use_decoder, skip_refine_text=skip_refine_text, refine_text_only=refine_text_only,
                         continuous=kwargs.get("continuous"), n_cand=n_cand, return_details=bool(kwargs.get("return_details")), select=kwargs.get("select"),
                         share_prompt=kwargs.get("share_prompt"), ids_sink=kwargs.get("_ids_sink"), overlap_vocoder=bool(kwargs.get("overlap_vocoder", False)),
-                        vocoder_chunk=kwargs.get("vocoder_chunk", 32), sample_rate=rate)
+                        vocoder_chunk=kwargs.get("vocoder_chunk", 32), sample_rate=rate,
+                        refine_guide=None if skip_refine_text else resolve_refine_guided(kwargs.get("refine_guided"), self.models_dict["tokenizer"]))
 
     def _infer_sliced(self, req: _Request):
         """pipeline:391-470: slices of slice_size utterances, each waiting for its slowest row; one list of waveforms per slice (stream=True: [B, samples]
@@ -1202,7 +1284,7 @@ class ChatTTSPlusPipeline:
             idx = range(ii, min(ii + req.slice_size, len(req.texts)))
             text = [req.texts[i] for i in idx]
             if not req.skip_refine_text:                                                   # pipeline:399-411
-                text = _decode_refined(self.models_dict["tokenizer"], self._refine_text(text, req.params_refine_text).ids)
+                text = _decode_refined(self.models_dict["tokenizer"], self._refine_text(text, req.params_refine_text, **req.guide_kw).ids)
                 if req.refine_text_only:
                     yield text
             if req.refine_text_only:
@@ -1256,7 +1338,7 @@ class ChatTTSPlusPipeline:
         texts = list(req.texts)
         if not req.skip_refine_text:
             # pipeline:399-411 for the whole request at once, `slice_size` rows kept busy (noise keyed by utterance id on stream 4: a sentence's refined text does not depend on the batch)
-            refined = self._refine_text(texts, req.params_refine_text, continuous_rows=req.slice_size, seed=seed, utt_ids=req.utt_ids)
+            refined = self._refine_text(texts, req.params_refine_text, continuous_rows=req.slice_size, seed=seed, utt_ids=req.utt_ids, **req.guide_kw)
             texts = _decode_refined(self.models_dict["tokenizer"], refined.ids)
             if req.refine_text_only:
                 yield texts
@@ -1382,9 +1464,9 @@ class ChatTTSPlusPipeline:
         texts = list(req.texts)
         if not req.skip_refine_text:                 # once per utterance, in the batches the plain call refines in
             if cont:
-                texts = _decode_refined(tok, self._refine_text(texts, req.params_refine_text, continuous_rows=slice_size, seed=seed, utt_ids=req.utt_ids).ids)
+                texts = _decode_refined(tok, self._refine_text(texts, req.params_refine_text, continuous_rows=slice_size, seed=seed, utt_ids=req.utt_ids, **req.guide_kw).ids)
             else:
-                texts = [t for ii in range(0, n_utt, slice_size) for t in _decode_refined(tok, self._refine_text(texts[ii:ii + slice_size], req.params_refine_text).ids)]
+                texts = [t for ii in range(0, n_utt, slice_size) for t in _decode_refined(tok, self._refine_text(texts[ii:ii + slice_size], req.params_refine_text, **req.guide_kw).ids)]
         texts = [_with_uv_break(t) for t in texts]
         read_option = getattr(gpt, "get_option", None)           # (an engine object without options shares only when asked to)
         share = resolve_share_prompt(req.share_prompt, n_cand, n_cand > 1 and read_option is not None and read_option("batch_invariant"))
@@ -1506,7 +1588,7 @@ class ChatTTSPlusPipeline:
 
     # -- serving session (no counterpart in the reference) ------------------------------------------------------------------------
     def open_session(self, params_infer_code: Optional[InferCodeParams] = None, use_decoder: bool = True, lora_path: Optional[str] = None, rows: Optional[int] = None,
-                     seed: Optional[int] = None, return_details: bool = False, refine: Optional[RefineTextParams] = None, sample_rate: Optional[int] = None,
+                     seed: Optional[int] = None, return_details: bool = False, refine: Optional[RefineTextParams] = None, sample_rate: Optional[int] = None, refine_guided=False,
                      **out_of_scope) -> SynthSession:
         """A SynthSession: submit(text) / cancel(ticket) / poll() / drain() / close() while the engine keeps decoding -- the decode batch grows when texts arrive
         and shrinks when they end.  `params_infer_code` are the session's values (speaker included; a random one is sampled if it names none), `lora_path` one
@@ -1523,7 +1605,7 @@ class ChatTTSPlusPipeline:
         params = dataclasses.replace(params_infer_code if params_infer_code is not None else InferCodeParams())
         if params.spk_emb is None and params.spk_smp is None:
             params.spk_emb = self.sample_random_speaker()
-        return SynthSession(self, self._gpt_for_lora(lora_path), params, use_decoder, rows, seed, return_details, refine=refine, sample_rate=sample_rate)
+        return SynthSession(self, self._gpt_for_lora(lora_path), params, use_decoder, rows, seed, return_details, refine=refine, sample_rate=sample_rate, refine_guided=refine_guided)
 
     # -- multi-GPU: utterance sharding (BASELINE configs[3]: batch 256 over 8 GPUs) --------------------------------
     @torch.no_grad()
@@ -1546,6 +1628,10 @@ class ChatTTSPlusPipeline:
             raise _lib.HipBackendError("infer_sharded serves one generation per utterance and returns waveforms: num_candidates > 1 and return_details are "
                                        "refused (rank the candidates with infer() on one rank)")
         kwargs.pop("num_candidates", None); kwargs.pop("return_details", None)
+        if kwargs.get("refine_guided") not in (None, False):
+            raise _lib.HipBackendError("infer_sharded(refine_guided=...) is not offered: guided refinement is served by infer() and by sessions "
+                                       "(open_session(refine=..., refine_guided=...))")
+        kwargs.pop("refine_guided", None)
         if kwargs.get("sample_rate") is not None and int(kwargs["sample_rate"]) != NATIVE_RATE:
             raise _lib.HipBackendError(f"infer_sharded(sample_rate={kwargs['sample_rate']}) is not offered: the generated lengths every rank exchanges are read off "
                                        "its 24 kHz waveforms; resample a rank's waveforms with pipe.resampler(rate).resample(wavs)")

@@ -454,6 +454,41 @@ int ctts_gpt_enable_text_rows(ctts_gpt* h, const ctts_sampler_cfg* text_sc, int3
 int ctts_gpt_set_row_modes(ctts_gpt* h, const int32_t* modes, int B);
 int ctts_gpt_admit_modes(ctts_gpt* h, int n, const int32_t* rows, const int32_t* modes, void* stream);
 
+/* Guided refine-text (no counterpart in the reference, whose refine pass samples freely over the 21178-way head and may drop, change or invent words): a GUIDE
+ * makes a text row's output provably its source ids in order, with only ids of a small free set inserted, ended by EOS ([Ebreak]).  The state machine runs on the
+ * device, inside the text sampler: the allowed set of a step depends on what the row drew one step earlier, and decode steps run as captured graphs.
+ * Per call:       `free` = at most 64 distinct ids, each != eos and < vocab_text; max_run >= 0 = the most consecutive free ids allowed.
+ * Per utterance:  src int32 [n], 1 <= n (at most 1020), n + 1 <= the row's limit, no id the EOS; device state cur (source ids emitted so far) and run (free ids
+ *                 since the last source id), both starting at 0.
+ * At the row's own step t, with limit L: need = n - cur, slack = (L - t) - (need + 1).
+ *   Allowed set A   cur <  n:  A = {src[cur]}, plus `free` if run < max_run and slack > 0
+ *                   cur == n:  A = {eos},      plus `free` if run < max_run and L - t > 1
+ *   Arithmetic      elements outside A are treated exactly as elements j >= V are (not valid, -inf, before the division by the temperature); softmax, top-P,
+ *                   top-K and the final race are the unguided arithmetic over A.  Only the <= 65 logits of A are loaded.
+ *   min_new_token   removes EOS only while another element of A remains.
+ *   Stand-in        when every race ratio is 0 or NaN (a NaN ratio counts as 0), the stand-in is src[cur] (EOS when cur == n), never id 0.
+ *   Update          idx == src[cur] with cur < n: cur++, run = 0 (the source match takes precedence when src[cur] is also in `free`);
+ *                   idx == eos: the row finishes; anything else: run++.
+ *   Guarantees      a guided row always finishes by a sampled EOS within its limit (finish == 1); its ids are src with free ids interleaved; no run of free ids is
+ *                   longer than max_run; it never ends at step 0, so ensure_non_empty never triggers on it.
+ * The records are keyed by OUTPUT SLOT (the utterance's index in ids / finish / end_idx), like the log-prob buffers: compact, grow, cancel and admit need nothing
+ * extra.  The table serves output slots 0..1023; the per-call block the sampler reads (SamplerDyn) holds its address, null = off.  Whether a step is guided is part
+ * of the decode graphs' key.  Guided and unguided text rows may share a batch: a row whose slot has no record (n == 0) takes the unguided path, a test that is
+ * uniform over its workgroup.  The unguided instantiation of the kernel is the kernel as it was.
+ *   set_text_guide  the per-call part.  After ctts_gpt_begin of an infer_text call; for text rows in a code call after ctts_gpt_enable_text_rows.  Every slot
+ *                   starts unguided.  Every ctts_gpt_begin (and ctts_gpt_enable_text_rows) switches the feature off again.
+ *   set_guides      HOST out_slots [n], src_concat, src_off [n + 1]: the sources of the utterances at those output slots (entry i: src_concat[src_off[i] ..
+ *                   src_off[i + 1])); a length of 0 = unguided.  Call it before the first sample, or before the ctts_gpt_admit that seats them; a slot that is
+ *                   re-used gets a fresh record (cur = run = 0) -- name a re-used slot for its unguided successor too (length 0).  Asynchronous: the records go
+ *                   through a pinned ring.  ctts_gpt_restart zeroes cur / run of the rows it restarts.
+ * Refused, each with a message, before any launch: a free id equal to EOS, out of range or listed twice; more than 64 free ids; max_run < 0; a source id out of
+ * range or equal to EOS; n + 1 > the row's limit (by set_guides for begin's rows, by ctts_gpt_admit for the rows it seats); an output slot >= 1024; caller-supplied
+ * noise with guides in a code call; guides without the per-call part; a guide on a code row (set_text_guide in a code call without text rows; set_guides / admit on a
+ * slot a code row holds).
+ * Not offered: a gathered text head that computes only the logits of A (the head still streams its whole matrix); log-probs of text rows; guides for code rows. */
+int ctts_gpt_set_text_guide(ctts_gpt* h, const int32_t* free_ids_host, int n_free, int max_run, void* stream);
+int ctts_gpt_set_guides(ctts_gpt* h, int n, const int32_t* out_slots_host, const int32_t* src_concat_host, const int32_t* src_off_host, void* stream);
+
 /* Shared prompt passes (no counterpart in the reference): sequences with ONE prompt -- the N candidates of an utterance, one text at several temperatures or
  * noise keys -- run it through the prompt pass once.  One-shot, like ctts_gpt_admit_sampling: names, for the NEXT ctts_gpt_begin (B == n) or ctts_gpt_admit
  * (its n == n), which prompt each sequence has.  prompt_of HOST [n], values in [0, n_prompts); every prompt named at least once.  While pending, the call's mask
@@ -517,6 +552,15 @@ int ctts_sampler_run_rows(const ctts_sampler_cfg* sc, const ctts_row_sampling* p
 int ctts_sampler_run_rows_lp(const ctts_sampler_cfg* sc, const ctts_row_sampling* per_seq, const float* logits_dev, const int32_t* history_dev,
                              int hist_len, const float* q_dev, int rows, int vocab, int step, int32_t* idx_dev, float* lp_raw_out, float* lp_sampled_out,
                              void* stream);
+
+/* Guided text sampler, stand-alone (a test hook, synchronous): ONE step of the generate-mode text kernel's guided instantiation -- the kernel itself, launched on
+ * a one-step state the call builds -- on caller-supplied logits fp32 [rows][vocab] and noise q fp32 [rows][vocab] (device).  Row r carries the guide src_concat
+ * [src_off[r] .. src_off[r + 1]) at cursor (cur[r], run[r]), at its own step[r] < limit[r]; all of these are HOST arrays, as are the results: the sampled id and the
+ * cursor after the draw.  sc = the refine pass's parameters (infer_text = 1).  Refused by name: n == 0, n + 1 > limit, and everything ctts_gpt_set_text_guide /
+ * ctts_gpt_set_guides refuse. */
+int ctts_sampler_run_text_guided(const ctts_sampler_cfg* sc, const float* logits_dev, const float* q_dev, int rows, int vocab, const int32_t* free_ids_host, int n_free,
+                                 int max_run, const int32_t* src_concat_host, const int32_t* src_off_host, const int32_t* cur_host, const int32_t* run_host,
+                                 const int32_t* step_host, const int32_t* limit_host, int32_t* idx_out_host, int32_t* cur_out_host, int32_t* run_out_host, void* stream);
 
 /* last measured average duration (ms) of one captured decode step, measured with hipEvents on the launch
  * stream around `n` graph replays; used by bench.py for the roofline object. */
