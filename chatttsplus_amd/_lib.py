@@ -124,8 +124,11 @@ SYMBOLS = [
     ("ctts_gpt_set_text_guide", C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     ("ctts_gpt_set_guides", C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     ("ctts_sampler_run_text_guided", C.c_int, [C.POINTER(SamplerCfg), _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("ctts_sampler_run_text_lp", C.c_int, [C.POINTER(SamplerCfg), _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("ctts_gpt_share_prompts", C.c_int, [_P, C.c_int, _P, C.c_int]),
     ("ctts_gpt_set_logprob_out", C.c_int, [_P, _P, _P, _P]),
+    ("ctts_gpt_set_text_logprob_out", C.c_int, [_P, _P, _P, _P]),
+    ("ctts_gpt_score_text", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
     ("ctts_gpt_logits", C.c_int, [_P, _P, _P]),
     ("ctts_gpt_force_ids", C.c_int, [_P, _P, _P]),
     ("ctts_sampler_run", C.c_int, [C.POINTER(SamplerCfg), _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P]),

@@ -265,6 +265,10 @@ struct ctts_gpt {
     // allocated by the first score call (engines that never score keep their footprint)
     float *score_x = nullptr, *score_logits = nullptr; int* score_oidx = nullptr;
     size_t score_bytes = 0;
+    // ctts_gpt_score_text: gathered rows [chunk][H], text-head logits [chunk][vocab_text_head], output entries [chunk], chunk = min(max_batch, SCORE_ROWS) rows
+    // ("score_text_chunk") -- allocated by the first ctts_gpt_score_text call (at most 128 x 21178 fp32 = 10.8 MB; every other engine keeps its footprint)
+    float *score_text_x = nullptr, *score_text_logits = nullptr; int* score_text_oidx = nullptr;
+    int score_text_chunk = 0;
     // shared prompt passes (ctts_gpt_share_prompts; kv_share.hip)
     std::vector<int> share_tab;                  //   host image of share_dev for the call that consumed the request (kernels.h SH_*)
     int* share_dev = nullptr;                    //   device table [SH_INTS], allocated by the first ctts_gpt_share_prompts
@@ -329,6 +333,7 @@ extern "C" int ctts_gpt_create(const ctts_gpt_cfg* c, ctts_gpt** out) {
     h->cfg = *c;
     h->H = c->hidden; h->I = c->inter; h->NH = c->heads; h->L = c->layers; h->V = c->vocab_code; h->NVQ = c->num_vq;
     h->esz = (c->dtype == CTTS_DTYPE_F16) ? 2 : 4;
+    h->score_text_chunk = c->max_batch < SCORE_ROWS ? c->max_batch : SCORE_ROWS;
     h->split_rows = 8;                                           // both dtypes (the comment at split_rows)
     // both dtypes since round 5 (fp16 engines: half weights + half K / V in the image, fp32 activations).  fp16: up to 5 rows -- ms/step launch chain / persistent launch on the
     // final round-5 kernel (four edge waves, joint row sums; profiles/r05_step_time_vs_batch_fp16.jsonl): batch 1 0.370 / 0.235, 2: 0.393 / 0.276, 3: 0.423 / 0.312, 4: 0.425 / 0.346,
@@ -484,6 +489,7 @@ static const OptRow g_options[] = {
     {"graph_steps", &ctts_gpt::graph_steps, OPT_RANGE(1, 64), OPT_RW, 0, HOOK_NONE},
     {"graph_steps_persistent", &ctts_gpt::graph_steps_persist, OPT_RANGE(1, 64), OPT_RW, 0, HOOK_NONE},
     {"text_rows_live", &ctts_gpt::text_live, OPT_ANY, OPT_R, 0, HOOK_NONE},    // read only: rows of the decode batch whose mode is 1 (ctts_gpt_enable_text_rows); > 0 = every step runs the text head and the text sampler too
+    {"score_text_chunk", &ctts_gpt::score_text_chunk, OPT_ANY, OPT_R, 0, HOOK_NONE},      // read only: rows per text-head launch of ctts_gpt_score_text (= max_batch: the decode step's launch shape)
     {"lora_mlp_live", &ctts_gpt::lora_mlp, OPT_ANY, OPT_R, 0, HOOK_NONE},      // read only: 1 while a live row's adapter names gate / up / down (the two MLP launches per layer run, decode on the launch chain)
 };
 // the name under which this engine's dtype takes the contract (error messages)
@@ -1866,6 +1872,85 @@ extern "C" int ctts_gpt_set_logprob_out(ctts_gpt* h, float* lp_raw, float* lp_sa
     return 0;
 }
 
+// Log-probs of the text rows' sampled ids (include/ctts_hip.h): the same two words of the block the TEXT sampler reads -- the call's own block of an infer_text
+// call (where the code entry point above refuses), the text block of a code call with text rows (which the code sampler never reads).  begin and
+// ctts_gpt_enable_text_rows rewrite their block whole: both destinations are null again.
+extern "C" int ctts_gpt_set_text_logprob_out(ctts_gpt* h, float* lp_raw, float* lp_sampled, void* stream) {
+    if (!h || h->B == 0) { ctts_set_error("set_text_logprob_out: no generate state (call ctts_gpt_begin first)"); return 1; }
+    if (!h->text_mode && !h->text_rows_on) { ctts_set_error("set_text_logprob_out: a code call without text rows: the call must be an infer_text call, or ctts_gpt_enable_text_rows must come first"); return 1; }
+    if (h->sampled) { ctts_set_error("set_text_logprob_out: called after the first ctts_gpt_sample / ctts_gpt_decode of this call; set the buffers right after ctts_gpt_begin / ctts_gpt_enable_text_rows"); return 1; }
+    float* const p[2] = {lp_raw, lp_sampled};
+    SamplerDyn* const blk = h->text_mode ? h->dyn : h->dyn_text;
+    CTTS_HIP_CHECK(hipMemcpyAsync((char*)blk + offsetof(SamplerDyn, lp_raw), p, sizeof(p), hipMemcpyHostToDevice, (hipStream_t)stream));      // pageable source: staged before the call returns
+    return 0;
+}
+
+// Teacher-forced scoring under the refine-text head (include/ctts_hip.h ctts_gpt_score_text): ctts_gpt_score's prompt pass and gather, then the text-head launch of a
+// decode step (run_heads' text shape: PRO_NORM / EPI_LOGITS over whead_text, 16-row chunks under batch_invariant) on at most max_batch gathered rows at a time into a
+// logits scratch of its own, and score.hip's one-row-per-workgroup reduce.  The scratch is allocated on the first call: an engine that never scores text allocates
+// what it always did.
+extern "C" int ctts_gpt_score_text(ctts_gpt* h, int B, int T, const int32_t* mask, const float* emb, const int32_t* targets, const int32_t* n_targets, int max_targets,
+                                   float* logprob, int32_t* argmax, void* stream) {
+    if (!h || !h->finalized || !h->kv || !h->rope) { ctts_set_error("score_text: handle not ready (finalize / bind_kv / set_rope)"); return 1; }
+    if (!h->whead_text || !h->emb_text) { ctts_set_error("score_text: the engine has no text head (head_text.* and emb_text.weight are needed)"); return 1; }
+    if (!mask || !emb || !targets || !n_targets || !logprob || !argmax) { ctts_set_error("score_text: null argument"); return 1; }
+    if (B < 1 || B > h->cfg.max_batch) { ctts_set_error("score_text: B=%d outside 1..max_batch=%d", B, h->cfg.max_batch); return 1; }
+    if (T < 1 || T > h->cfg.max_seq) { ctts_set_error("score_text: T=%d outside 1..max_seq=%d", T, h->cfg.max_seq); return 1; }
+    if (max_targets < 1) { ctts_set_error("score_text: max_targets=%d < 1", max_targets); return 1; }
+    for (int b = 0; b < B; ++b) {
+        const int nb = n_targets[b];
+        if (nb < 1 || nb > T || nb > max_targets) {
+            ctts_set_error("score_text: n_targets[%d]=%d outside 1..min(T=%d, max_targets=%d)", b, nb, T, max_targets);
+            return 1;
+        }
+    }
+    if (h->batch_inv && h->cfg.dtype == CTTS_DTYPE_F32 && !(h->split_ok && h->wsplit)) {
+        ctts_set_error("score_text: batch_invariant needs the head / tail weight images, and a weight of this checkpoint is beyond the fp16 range (x 64)");
+        return 1;
+    }
+    CTTS_RANGE("ctts_gpt_score_text");
+    hipStream_t s = (hipStream_t)stream;
+    end_generate_state(h);            // the KV lanes and the prompt workspaces are overwritten
+    h->text_mode = 0;
+    if (seat_row_adapters(h, B, "score_text", s)) return 1;
+    const int NV = h->vocab_text_head, CH = h->score_text_chunk;
+    if (h->score_text_oidx == nullptr) {
+        if (!h->score_text_x && dev_alloc(h, (void**)&h->score_text_x, (size_t)CH * h->H * 4)) return 1;
+        if (!h->score_text_logits && dev_alloc(h, (void**)&h->score_text_logits, (size_t)CH * NV * 4)) return 1;
+        if (dev_alloc(h, (void**)&h->score_text_oidx, (size_t)CH * 4)) return 1;
+    }
+    // entries j >= n_b: logprob 0, argmax -1
+    CTTS_HIP_CHECK(hipMemsetAsync(logprob, 0, (size_t)B * max_targets * 4, s));
+    CTTS_HIP_CHECK(hipMemsetAsync(argmax, 0xFF, (size_t)B * max_targets * 4, s));
+    if (launch_fill_meta(h->meta_pre, h->meta_dec0, h->st, mask, B, T, h->rope, h->rope_pre, nullptr, B, s)) return 1;
+    const long R = (long)B * T;
+    h->pp_rows = R; h->pp_T = T;
+    const int nbg = h->batch_inv ? 1 : 2;
+    ScoreRows sr = {};
+    sr.B = B; sr.max_targets = max_targets;
+    return prompt_passes(h, R, T, s, [&](long r0, int n) { return stage_rows(h, emb, r0, n, s); }, [&](long r0, int n) {
+        sr.cum[0] = 0;
+        for (int b = 0; b < B; ++b) {
+            const long s0 = (long)b * T + T - n_targets[b], s1 = (long)b * T + T;
+            const long lo = s0 > r0 ? s0 : r0, hi = s1 < r0 + n ? s1 : r0 + n;
+            const int cnt = hi > lo ? (int)(hi - lo) : 0;
+            sr.first[b] = cnt ? (int)(lo - r0) : 0;
+            sr.j0[b] = cnt ? (int)(lo - s0) : 0;
+            sr.cum[b + 1] = sr.cum[b] + cnt;
+        }
+        for (int g0 = 0; g0 < sr.cum[B]; g0 += CH) {
+            const int m = sr.cum[B] - g0 < CH ? sr.cum[B] - g0 : CH;
+            if (launch_score_gather(h->x_pre, h->score_text_x, h->score_text_oidx, g0, m, sr, s)) return 1;
+            GemmArgs a = {};
+            a.R = m; a.eps = 1e-6f; a.W = h->whead_text; a.n_row_tiles = (NV + 15) / 16; a.K = h->H; a.x = h->score_text_x; a.lnw = h->lnf;
+            a.logits = h->score_text_logits; a.n_valid = NV;
+            if (launch_gemm(h->cfg.dtype, nbg, PRO_NORM, EPI_LOGITS, a, (m + 16 * nbg - 1) / (16 * nbg), s)) return 1;
+            if (launch_score_text_reduce(h->score_text_logits, h->score_text_oidx, targets, logprob, argmax, m, NV, s)) return 1;
+        }
+        return 0;
+    });
+}
+
 // ---- text rows beside code rows (include/ctts_hip.h; RowState.mode) --------------------------------------------------------------------------------------------
 extern "C" int ctts_gpt_set_row_modes(ctts_gpt* h, const int32_t* modes, int B) {
     if (!h) { ctts_set_error("set_row_modes: null handle"); return 1; }
@@ -2449,6 +2534,7 @@ extern "C" int ctts_gpt_debug_read(ctts_gpt* h, const char* name, void* out, siz
     else if (n == "pl_ts" && h->pl_ts) { src = h->pl_ts; nb = (size_t)PL_BLOCKS * 10 * 8; }
     else if (n == "xh") { src = h->xh; nb = (size_t)2 * 48 * 1024; }
     else if (n == "ssq") { src = h->ssq; nb = (size_t)32 * 48 * 4; }
+    else if (n == "guide_tab" && h->guide_tab) { src = h->guide_tab; nb = sizeof(GuideTab); }        // header, free ids, one 4 KB record {n, -, cur, run, src...} per output slot
     else if (n == "pl_state" && h->pl_epoch) {
         unsigned* o = (unsigned*)out;
         if (max_bytes < 8) { ctts_set_error("debug_read: buffer too small"); return 1; }
@@ -2579,40 +2665,49 @@ extern "C" int ctts_sampler_run_rows_lp(const ctts_sampler_cfg* sc, const ctts_r
 
 // Stand-alone guided text sampler (a test hook, synchronous): one step of sampler_text_kernel<true> -- the generate kernel itself, not a copy of its arithmetic -- on
 // a one-step state built here: row r is a live text row at output slot r, at its own step, with its guide record at the given cursor.  Host arrays in, host arrays out.
-extern "C" int ctts_sampler_run_text_guided(const ctts_sampler_cfg* sc, const float* logits, const float* q, int rows, int vocab, const int32_t* free_ids, int n_free,
-                                            int max_run, const int32_t* src_concat, const int32_t* src_off, const int32_t* cur, const int32_t* run, const int32_t* step,
-                                            const int32_t* limit, int32_t* idx_out, int32_t* cur_out, int32_t* run_out, void* stream) {
-    const char* who = "sampler_run_text_guided";
-    if (!sc || !logits || !q || !src_concat || !src_off || !cur || !run || !step || !limit || !idx_out || !cur_out || !run_out) { ctts_set_error("%s: null argument", who); return 1; }
+// `guided` = false (ctts_sampler_run_text_lp without a source): sampler_text_kernel<false> on rows without records.  lp_raw_out / lp_sampled_out (host, [rows], either
+// may be null): the log-probs the step wrote next to the id (ctts_gpt_set_text_logprob_out); both null = the launch of a call without the feature.
+static int run_text_step(const char* who, bool guided, const ctts_sampler_cfg* sc, const float* logits, const float* q, int rows, int vocab, const int32_t* free_ids, int n_free,
+                         int max_run, const int32_t* src_concat, const int32_t* src_off, const int32_t* cur, const int32_t* run, const int32_t* step,
+                         const int32_t* limit, int32_t* idx_out, int32_t* cur_out, int32_t* run_out, float* lp_raw_out, float* lp_sampled_out, void* stream) {
+    if (!sc || !logits || !q || !step || !limit || !idx_out) { ctts_set_error("%s: null argument", who); return 1; }
+    if (guided && (!src_concat || !src_off || !cur || !run || !cur_out || !run_out)) { ctts_set_error("%s: null argument", who); return 1; }
     if (rows < 1 || rows > CTTS_GUIDE_SLOTS) { ctts_set_error("%s: rows=%d outside 1..%d", who, rows, CTTS_GUIDE_SLOTS); return 1; }
     if (!sc->infer_text || sc->use_penalty) { ctts_set_error("%s: sc must be the refine-text pass's parameters (infer_text = 1, no repetition penalty)", who); return 1; }
     if (vocab < 1 || sc->eos_token < 0 || sc->eos_token >= vocab) { ctts_set_error("%s: eos out of range", who); return 1; }
-    if (check_free_ids(who, free_ids, n_free, max_run, sc->eos_token, vocab)) return 1;
+    if (vocab > 1024 * 21) { ctts_set_error("%s: vocab %d > %d", who, vocab, 1024 * 21); return 1; }
+    if (guided && check_free_ids(who, free_ids, n_free, max_run, sc->eos_token, vocab)) return 1;
     int max_new = 1;
     for (int r = 0; r < rows; ++r) {
+        if (limit[r] < 1 || limit[r] > 4096) { ctts_set_error("%s: row %d: limit %d outside 1..4096", who, r, limit[r]); return 1; }
+        if (step[r] < 0 || step[r] >= limit[r]) { ctts_set_error("%s: row %d: step=%d outside 0..limit-1 (limit=%d)", who, r, step[r], limit[r]); return 1; }
+        max_new = limit[r] > max_new ? limit[r] : max_new;
+        if (!guided) continue;
         const int n = src_off[r + 1] - src_off[r];
         if (n < 1) { ctts_set_error("%s: row %d: a source of %d ids (n == 0 is an unguided row: not served by this hook)", who, r, n); return 1; }
-        if (limit[r] < 1 || limit[r] > 4096) { ctts_set_error("%s: row %d: limit %d outside 1..4096", who, r, limit[r]); return 1; }
         if (check_guide_src(who, r, src_concat + src_off[r], n, limit[r], sc->eos_token, vocab)) return 1;
-        if (cur[r] < 0 || cur[r] > n || run[r] < 0 || step[r] < 0 || step[r] >= limit[r]) { ctts_set_error("%s: row %d: cur=%d run=%d step=%d outside the guide (n=%d, limit=%d)", who, r, cur[r], run[r], step[r], n, limit[r]); return 1; }
-        max_new = limit[r] > max_new ? limit[r] : max_new;
+        if (cur[r] < 0 || cur[r] > n || run[r] < 0) { ctts_set_error("%s: row %d: cur=%d run=%d step=%d outside the guide (n=%d, limit=%d)", who, r, cur[r], run[r], step[r], n, limit[r]); return 1; }
     }
     hipStream_t s = (hipStream_t)stream;
-    // one scratch block: [guide header + rows records][SamplerDyn][DevState][RowState x rows][RowMeta x rows][rope 2 x 64][rope rows][ids][finish][end_idx][x_next]
+    // one scratch block: [guide header + rows records][SamplerDyn][DevState][RowState x rows][RowMeta x rows][rope 2 x 64][rope rows][ids][finish][end_idx][x_next][lp_raw][lp_sampled]
     auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     const size_t o_tab = 0, o_dyn = up(offsetof(GuideTab, rec) + (size_t)rows * sizeof(GuideRec)), o_st = o_dyn + up(sizeof(SamplerDyn)), o_rs = o_st + up(sizeof(DevState)),
                  o_meta = o_rs + up((size_t)rows * sizeof(RowState)), o_rope = o_meta + up((size_t)rows * sizeof(RowMeta)), o_rr = o_rope + up(128 * 4),
                  o_ids = o_rr + up((size_t)rows * 64 * 4), o_fin = o_ids + up((size_t)rows * max_new * CTTS_NUM_VQ * 4), o_end = o_fin + up((size_t)rows * 4),
-                 o_x = o_end + up((size_t)rows * 4), total = o_x + 256;
+                 o_x = o_end + up((size_t)rows * 4), o_lp = o_x + 256, lp_bytes = up((size_t)rows * max_new * 4), total = o_lp + 2 * lp_bytes;
     std::vector<char> img(o_rope, 0);                       // host image of everything up to the RoPE table; the rest is zero-filled on the device
     GuideTab* ht = (GuideTab*)(img.data() + o_tab);
-    ht->n_free = n_free; ht->max_run = max_run;
-    for (int i = 0; i < n_free; ++i) ht->free_ids[i] = free_ids[i];
+    if (guided) {
+        ht->n_free = n_free; ht->max_run = max_run;
+        for (int i = 0; i < n_free; ++i) ht->free_ids[i] = free_ids[i];
+    }
     RowState* hr = (RowState*)(img.data() + o_rs);
     for (int r = 0; r < rows; ++r) {
-        GuideRec& g = ht->rec[r];
-        g.n = src_off[r + 1] - src_off[r]; g.cur = cur[r]; g.run = run[r];
-        for (int k = 0; k < g.n; ++k) g.src[k] = src_concat[src_off[r] + k];
+        if (guided) {
+            GuideRec& g = ht->rec[r];
+            g.n = src_off[r + 1] - src_off[r]; g.cur = cur[r]; g.run = run[r];
+            for (int k = 0; k < g.n; ++k) g.src[k] = src_concat[src_off[r] + k];
+        }
         hr[r].end = step[r]; hr[r].limit = limit[r]; hr[r].out = r; hr[r].uid_lo = (unsigned)r;
     }
     char* dev = nullptr;
@@ -2621,32 +2716,52 @@ extern "C" int ctts_sampler_run_text_guided(const ctts_sampler_cfg* sc, const fl
     do {
         SamplerDyn d = {};
         d.cfg = cfg_of_abi(*sc); d.cfg.max_new = max_new; d.n_draws = 1; d.ids = (int*)(dev + o_ids); d.finish = (int*)(dev + o_fin); d.end_idx = (int*)(dev + o_end);
-        d.noise = q; d.rows0 = rows; d.guide = (GuideTab*)(dev + o_tab);
+        d.noise = q; d.rows0 = rows; d.guide = guided ? (GuideTab*)(dev + o_tab) : nullptr;
+        d.lp_raw = lp_raw_out ? (float*)(dev + o_lp) : nullptr; d.lp_sampled = lp_sampled_out ? (float*)(dev + o_lp + lp_bytes) : nullptr;
         memcpy(img.data() + o_dyn, &d, sizeof(d));
         DevState* hs = (DevState*)(img.data() + o_st);
         hs->B = rows;
         if (hipMemsetAsync(dev + o_rope, 0, total - o_rope, s) != hipSuccess || hipMemcpyAsync(dev, img.data(), o_rope, hipMemcpyHostToDevice, s) != hipSuccess) { ctts_set_error("%s: upload failed", who); break; }
         SamplerArgs sa = {};
         sa.dyn = (const SamplerDyn*)(dev + o_dyn); sa.logits = logits; sa.V = vocab; sa.B = rows; sa.st = (DevState*)(dev + o_st);
-        sa.text_mode = 1; sa.mixed = 0; sa.guided = 1;
+        sa.text_mode = 1; sa.mixed = 0; sa.guided = guided ? 1 : 0;
         sa.emb_code = logits; sa.H = 0; sa.x_next = (float*)(dev + o_x);            // H = 0: no next-input row is written
         sa.meta = (RowMeta*)(dev + o_meta); sa.rope = (const float*)(dev + o_rope); sa.rope_rows = (float*)(dev + o_rr); sa.finend = (RowState*)(dev + o_rs);
         if (launch_sampler(sa, rows, s)) break;
         std::vector<int> ids((size_t)rows * max_new * CTTS_NUM_VQ);
+        std::vector<float> lps(2 * lp_bytes / 4);
         if (hipMemcpyAsync(ids.data(), dev + o_ids, ids.size() * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipMemcpyAsync(lps.data(), dev + o_lp, 2 * lp_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipMemcpyAsync(img.data(), dev + o_tab, o_dyn, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
             ctts_set_error("%s: %s", who, hipGetErrorString(hipGetLastError()));
             break;
         }
         for (int r = 0; r < rows; ++r) {
             idx_out[r] = ids[((size_t)r * max_new + step[r]) * CTTS_NUM_VQ];
-            cur_out[r] = ht->rec[r].cur; run_out[r] = ht->rec[r].run;
+            if (guided) { cur_out[r] = ht->rec[r].cur; run_out[r] = ht->rec[r].run; }
+            if (lp_raw_out) lp_raw_out[r] = lps[(size_t)r * max_new + step[r]];
+            if (lp_sampled_out) lp_sampled_out[r] = lps[lp_bytes / 4 + (size_t)r * max_new + step[r]];
         }
         rc = 0;
     } while (false);
     (void)hipStreamSynchronize(s);
     (void)hipFree(dev);
     return rc;
+}
+extern "C" int ctts_sampler_run_text_guided(const ctts_sampler_cfg* sc, const float* logits, const float* q, int rows, int vocab, const int32_t* free_ids, int n_free,
+                                            int max_run, const int32_t* src_concat, const int32_t* src_off, const int32_t* cur, const int32_t* run, const int32_t* step,
+                                            const int32_t* limit, int32_t* idx_out, int32_t* cur_out, int32_t* run_out, void* stream) {
+    if (!src_concat) { ctts_set_error("sampler_run_text_guided: null argument"); return 1; }
+    return run_text_step("sampler_run_text_guided", true, sc, logits, q, rows, vocab, free_ids, n_free, max_run, src_concat, src_off, cur, run, step, limit, idx_out, cur_out,
+                         run_out, nullptr, nullptr, stream);
+}
+// The same step with the log-probs of the returned id (a test hook, synchronous).  src_concat == NULL: unguided rows through sampler_text_kernel<false> (the guide
+// arguments and cur_out / run_out are ignored); otherwise the guided instantiation as above.
+extern "C" int ctts_sampler_run_text_lp(const ctts_sampler_cfg* sc, const float* logits, const float* q, int rows, int vocab, const int32_t* free_ids, int n_free,
+                                        int max_run, const int32_t* src_concat, const int32_t* src_off, const int32_t* cur, const int32_t* run, const int32_t* step,
+                                        const int32_t* limit, int32_t* idx_out, int32_t* cur_out, int32_t* run_out, float* lp_raw_out, float* lp_sampled_out, void* stream) {
+    return run_text_step("sampler_run_text_lp", src_concat != nullptr, sc, logits, q, rows, vocab, free_ids, n_free, max_run, src_concat, src_off, cur, run, step, limit,
+                         idx_out, cur_out, run_out, lp_raw_out, lp_sampled_out, stream);
 }
 
 extern "C" int ctts_gpt_time_decode(ctts_gpt* h, int n_steps, float* ms_per_step, void* stream) {

@@ -307,6 +307,8 @@ struct ScoreRows {
 };
 int launch_score_gather(const float* x_pre, float* dst, int* oidx, int g0, int m, const ScoreRows& sr, hipStream_t s);
 int launch_score_reduce(const float* logits, const int* oidx, const int* targets, float* logprob, int* argmax, int m, int V, int n_valid, hipStream_t s);
+// ctts_gpt_score_text: one V-wide text-head row per workgroup; logprob / argmax are [B][max_targets] (one column)
+int launch_score_text_reduce(const float* logits, const int* oidx, const int* targets, float* logprob, int* argmax, int m, int V, hipStream_t s);
 int launch_compact_rows(const int* keep, int n_keep, int H, float* x, float* rope_rows, RowMeta* meta, int* ring, RowState* fin, RowSampling* knobs,
                         float* cx, float* crope, RowMeta* cmeta, int* cring, RowState* cfin, RowSampling* cknobs, DevState* st, hipStream_t s);
 int gemm_configure();

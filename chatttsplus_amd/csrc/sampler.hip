@@ -695,6 +695,36 @@ __global__ __launch_bounds__(1024) void sampler_text_kernel(const SamplerArgs a)
     // next input = emb_text[idx]  (gpt.py:400-401); ids buffer keeps the reference's [.., num_vq] layout (gpt.py:492-494)
     for (int k = tid; k < a.H; k += 1024) a.x_next[(size_t)b * a.H + k] = a.emb_code[(size_t)idx * a.H + k];
     if (tid < CTTS_NUM_VQ && rs_in.fin == 0) d->ids[((size_t)seq * d->cfg.max_new + step) * CTTS_NUM_VQ + tid] = idx;      // (a finished row's tokens are never read: gpt.py:295-297)
+    // Log-probs of the returned id (include/ctts_hip.h ctts_gpt_set_text_logprob_out): [slot][step], one value per step, next to the id and under its condition.
+    // The destinations are the lp_raw / lp_sampled words of the block THIS kernel reads (the call's own block of an infer_text call, the text block beside code
+    // rows: the code sampler never sees them), null = off -- scalar loads, tests uniform over the block.  Both are computed after the race from what it left
+    // behind and feed nothing back; the reductions are one block per row in a fixed order, so the values do not depend on the batch.
+    //   lp_sampled  the thread that owns the id: log(e * inv2), the expression its ratio was formed from; an id outside the kept set (element 0 standing in, a
+    //               guided stand-in that top-P / top-K / min_new_token removed or whose e underflowed) -> log 0 = -inf
+    //   lp_raw      log_softmax over the FULL raw row at the id, before the temperature: a second and third pass over the row in L2 (a guided row loaded only its
+    //               allowed set; re-reading keeps x[] out of the live range for every row)
+    float* const lp_raw_out = d->lp_raw;
+    float* const lp_smp_out = d->lp_sampled;
+    if (rs_in.fin == 0 && (lp_raw_out != nullptr || lp_smp_out != nullptr)) {
+        const size_t at = (size_t)seq * d->cfg.max_new + step;
+        if (lp_smp_out != nullptr && tid == (idx & 1023)) {
+            float xe = 0.f;
+            bool in_kept = false;
+#pragma unroll
+            for (int i = 0; i < TVPT; ++i)
+                if (i == (idx >> 10)) { xe = x[i]; in_kept = (kept >> i) & 1u; }
+            lp_smp_out[at] = in_kept ? logf(expf(xe - m2) * inv2) : -INFINITY;
+        }
+        if (lp_raw_out != nullptr) {
+            float rm = -INFINITY;
+            for (int j = tid; j < V; j += 1024) rm = fmaxf(rm, lg[j]);
+            rm = block_max_f(red, rm, lane, wave);
+            float rsum = 0.f;
+            for (int j = tid; j < V; j += 1024) rsum += expf(lg[j] - rm);
+            rsum = block_sum_f(red, rsum, lane, wave);
+            if (tid == 0) lp_raw_out[at] = (lg[idx] - rm) - logf(rsum);
+        }
+    }
     if (tid == 0) {
         const bool was = rs_in.fin != 0;
         const bool eos = (rs_in.fin & 2) != 0 || (idx == d->cfg.eos);                // gpt.py:490-491

@@ -53,6 +53,48 @@ __global__ __launch_bounds__(256) void score_reduce_kernel(const float* logits, 
     }
 }
 
+// ctts_gpt_score_text: one row of V (21178) raw text-head logits per workgroup of 4 waves.  The same reduction as above a level higher: per thread a strided
+// pass for the key of the first largest logit (f32_key | ~index), the wave reduction, the 4 wave results through LDS in wave order; then sum expf(lg - mx) in fp32
+// the same way (thread: ascending k; wave_sum; waves 0..3 in order -- a fixed order, so a row's value does not depend on the rows beside it).
+// A target outside [0, V) gives NaN and -1 and reads no logit.
+__global__ __launch_bounds__(256) void score_text_reduce_kernel(const float* logits, const int* oidx, const int* targets, float* logprob, int* argmax, int V) {
+    __shared__ unsigned long long key_s[4];
+    __shared__ float sum_s[4];
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* lg = logits + (size_t)i * V;
+    unsigned long long best = 0ull;
+    for (int k = tid; k < V; k += 256) {
+        const unsigned long long key = ((unsigned long long)f32_key(lg[k]) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)k);
+        best = umax64(best, key);
+    }
+    best = wave_max_u64(best);
+    if (lane == 0) key_s[wave] = best;
+    __syncthreads();
+    best = umax64(umax64(key_s[0], key_s[1]), umax64(key_s[2], key_s[3]));
+    const float mx = key_f32((unsigned)(best >> 32));
+    const int am = (int)(0xFFFFFFFFu - (unsigned)best);
+    float s = 0.f;
+    for (int k = tid; k < V; k += 256) s += expf(lg[k] - mx);
+    s = wave_sum(s);
+    if (lane == 0) sum_s[wave] = s;
+    __syncthreads();
+    if (tid == 0) {
+        s = ((sum_s[0] + sum_s[1]) + sum_s[2]) + sum_s[3];
+        const int o = oidx[i];
+        const int t = targets[o];
+        const bool ok = (t >= 0 && t < V);
+        logprob[o] = ok ? (lg[ok ? t : 0] - mx) - logf(s) : __builtin_nanf("");
+        argmax[o] = ok ? am : -1;
+    }
+}
+
+int launch_score_text_reduce(const float* logits, const int* oidx, const int* targets, float* logprob, int* argmax, int m, int V, hipStream_t s) {
+    if (m <= 0) return 0;
+    hipLaunchKernelGGL(score_text_reduce_kernel, dim3(m), dim3(256), 0, s, logits, oidx, targets, logprob, argmax, V);
+    CTTS_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 int launch_score_gather(const float* x_pre, float* dst, int* oidx, int g0, int m, const ScoreRows& sr, hipStream_t s) {
     if (m <= 0) return 0;
     hipLaunchKernelGGL(score_gather_kernel, dim3(m), dim3(192), 0, s, x_pre, dst, oidx, g0, sr);

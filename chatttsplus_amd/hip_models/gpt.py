@@ -44,6 +44,8 @@ class GenerationOutputs:          # gpt.py:280-284
     #   logprobs          log_softmax(raw code logits)[id]: what GPT.score gives for the same token
     #   sampled_logprobs  log p(id) under the distribution the sampler drew from (after temperature, repetition penalty, top-P, top-K, min_new_token)
     #   final_logprobs    [2, 4] (raw, sampled) of the step that sampled EOS -- its ids are not part of ids[b] -- or None for a sequence that ended by its limit
+    # return_text_logprobs=True with infer_text=True: the same three fields with ONE value per step -- [n_b], [n_b], [2] -- under the text head
+    #   (ctts_gpt_set_text_logprob_out): logprobs is what GPT.score_text gives for the same token
     logprobs: Optional[List[torch.Tensor]] = None
     sampled_logprobs: Optional[List[torch.Tensor]] = None
     final_logprobs: Optional[List[Optional[torch.Tensor]]] = None
@@ -130,6 +132,44 @@ def score_inputs(input_ids: torch.Tensor, attention_mask: torch.Tensor, text_mas
         out_tm[b, T - n:] = tms[b]
         targets[b, :int(nt[b])] = tgts[b].to(torch.int32)
     return dict(ids=out_ids, mask=out_mask, text_mask=out_tm, targets=targets, n_targets=nt)
+
+
+def score_text_inputs(input_ids: torch.Tensor, attention_mask: torch.Tensor, refined, eos_token: int, append_eos: bool = True):
+    """The text twin of score_inputs, host helper of GPT.score_text (CPU): utterance i's refined text ids [n_i] follow its left-padded refine prompt (input_ids
+    [B, T, num_vq], attention_mask [B, T], as Tokenizer.encode gives them for the refine pass: every row a text row); the joined sequences are left padded again.
+    Returns dict(ids [B, T', num_vq], mask [B, T'] int32, text_mask [B, T'] bool (True on every real row), targets [B, max_targets] int32, n_targets [B] int32).
+      append_eos=True:  every refined id is an input row (the id on every column, as the refine pass feeds it back: emb_text[id]) and the targets are the ids
+                        followed by `eos_token` ([Ebreak]), n_b = n_i + 1: the log-probs generate(infer_text=True, return_text_logprobs=True) wrote, final one included.
+      append_eos=False: the targets are the ids, n_b = n_i; the last id is not fed as input.
+    Target j of sequence b is predicted by row T' - n_b + j (ctts_gpt_score_text)."""
+    ids = torch.as_tensor(input_ids).cpu()
+    mask = torch.as_tensor(attention_mask).cpu().to(torch.int64)
+    if ids.dim() != 3 or mask.shape != ids.shape[:2]:
+        raise ValueError(f"score_text_inputs: input_ids [B, T, num_vq] with attention_mask [B, T] (got {tuple(ids.shape)}, {tuple(mask.shape)})")
+    B, nvq = int(ids.shape[0]), int(ids.shape[2])
+    if len(refined) != B:
+        raise ValueError(f"score_text_inputs: {len(refined)} refined sequences for {B} prompts")
+    _check_left_padded(mask)
+    seqs, tgts = [], []
+    for b in range(B):
+        c = torch.as_tensor(refined[b]).cpu().to(ids.dtype).flatten()
+        if not append_eos and c.numel() < 1:
+            raise ValueError(f"score_text_inputs: refined[{b}] is empty and append_eos is off: nothing to score")
+        pad = int((mask[b] == 0).sum())
+        inp = c if append_eos else c[:-1]
+        seqs.append(torch.cat([ids[b, pad:], inp[:, None].expand(-1, nvq)], 0))
+        tgts.append(torch.cat([c, torch.full((1,), int(eos_token), dtype=c.dtype)], 0) if append_eos else c)
+    T = max(int(s.shape[0]) for s in seqs)
+    nt = torch.tensor([int(t.shape[0]) for t in tgts], dtype=torch.int32)
+    out_ids = torch.zeros(B, T, nvq, dtype=ids.dtype)
+    out_mask = torch.zeros(B, T, dtype=torch.int32)
+    targets = torch.zeros(B, int(nt.max()), dtype=torch.int32)
+    for b in range(B):
+        n = int(seqs[b].shape[0])
+        out_ids[b, T - n:] = seqs[b]
+        out_mask[b, T - n:] = 1
+        targets[b, :int(nt[b])] = tgts[b].to(torch.int32)
+    return dict(ids=out_ids, mask=out_mask, text_mask=out_mask.bool(), targets=targets, n_targets=nt)
 
 
 def _check_left_padded(mask: torch.Tensor) -> None:
@@ -669,6 +709,7 @@ class SessionBook:
 
 # arguments of generate() / generate_many() / infer() that a session refuses by name (GPT.open_session, ChatTTSPlusPipeline.open_session)
 SESSION_OUT_OF_SCOPE = {"prompt_of": "shared prompt passes", "share_prompt": "shared prompt passes", "num_candidates": "num_candidates / shared prompt passes",
+                        "refine_candidates": "ranked refine candidates",
                         "noise": "caller-supplied noise", "stream": "session-wide streaming windows", "stream_batch": "session-wide streaming windows",
                         "sharded": "infer_sharded", "infer_text": "the refine-text pass inside a code session",
                         "refine_text_only": "the refine-text pass inside a code session", "params_refine_text": "the refine-text pass inside a code session"}
@@ -681,7 +722,7 @@ def refuse_out_of_scope(kw: dict, instead: str) -> None:
         if name not in SESSION_OUT_OF_SCOPE:
             raise TypeError(f"open_session() got an unexpected keyword argument {name!r}")
         off = value is None or value is False or (name == "noise" and isinstance(value, str) and value == "device") or \
-            (name == "num_candidates" and isinstance(value, int) and value == 1)
+            (name in ("num_candidates", "refine_candidates") and isinstance(value, int) and value == 1)
         if not off:
             per_utt = "; streaming is asked per utterance at submit(stream=\"exact\" | \"eager\")" if name in ("stream", "stream_batch") else ""
             raise _lib.HipBackendError(f"open_session: {SESSION_OUT_OF_SCOPE[name]} ({name}=) is not offered inside a session; {instead}{per_utt}")
@@ -835,7 +876,8 @@ class SessionResult:
     finished_by_eos: bool = False
     cancelled: bool = False
     attempt: int = 0              # first-token-EOS regenerations before this result (ensure_non_empty)
-    mode: str = "code"            # "text": a refine-text utterance -- ids is [n] (as generate(infer_text=True) returns them), no hiddens, no log-probs
+    mode: str = "code"            # "text": a refine-text utterance -- ids is [n] (as generate(infer_text=True) returns them), no hiddens; log-probs [n] / [n] / [2]
+                                  #   only where the session was opened with return_text_logprobs (return_logprobs stays code-only)
 
 
 @dataclass(repr=False, eq=False)
@@ -866,8 +908,13 @@ class OutBuffers:
     a session, finish / end_idx per slot -- and the GenIO that names them.  Uninitialised: only [s, :end_idx[s]] is ever read, and every one of those rows was
     written by the step that produced it (the default max_new_token = 2048 made zero-filling a 201 MB write per call at batch 32)."""
 
-    def __init__(self, n: int, max_new: int, gpt: "GPT", hidden: bool, logprobs: bool, text_new: Optional[int] = None):
+    def __init__(self, n: int, max_new: int, gpt: "GPT", hidden: bool, logprobs: bool, text_new: Optional[int] = None, text_logprobs: bool = False,
+                 infer_text: bool = False):
+        """`text_logprobs`: the text rows' (raw, sampled) log-probs [2, n, steps], one value per step, beside the text ids: steps = `text_new` for the text rows of
+        a code state, `max_new` for a state whose own mode is `infer_text`; a code state without text rows has none"""
         dev, NVQ = gpt.device, gpt.num_vq
+        t_steps = text_new if text_new else (max_new if infer_text else None)
+        self.tlps = torch.empty(2, n, t_steps, dtype=torch.float32, device=dev) if (text_logprobs and t_steps) else None
         self.ids = torch.empty(n, max_new, NVQ, dtype=torch.int32, device=dev)
         self.hid = torch.empty(n, max_new, gpt.model_dim, dtype=torch.float32, device=dev) if hidden else None
         self.lps = torch.empty(2, n, max_new, NVQ, dtype=torch.float32, device=dev) if logprobs else None
@@ -885,11 +932,15 @@ class OutBuffers:
         """(ids, hiddens, logprobs, sampled_logprobs, final_logprobs) of slot s's first n tokens: the ids as long (gpt.py:295-297), the rest views, None what the
         state does not return.  `first_column`: ids [n] of a refine-text state (gpt.py:298-299); `text_row`: those of a session's text row.  The step that sampled
         EOS wrote its log-probs at index n (its ids are not part of the sequence): final_logprobs, a clone, where `eos` says so and the row exists."""
+        t = self.tlps
+        tl = (None, None, None) if t is None else (t[0, s, :n], t[1, s, :n], t[:, s, n].clone() if (eos and n < t.shape[2]) else None)
         if text_row:
-            return self.tids[s, :n, 0].to(torch.long), None, None, None, None
+            return (self.tids[s, :n, 0].to(torch.long), None) + tl
         ids = self.ids[s, :n].to(torch.long)
         ids = ids[:, 0] if first_column else ids
         hid = self.hid[s, :n] if self.hid is not None else None
+        if first_column and t is not None:             # a refine-text state: the text sampler's log-probs, one value per step
+            return (ids, hid) + tl
         if self.lps is None:
             return ids, hid, None, None, None
         return ids, hid, self.lps[0, s, :n], self.lps[1, s, :n], self.lps[:, s, n].clone() if (eos and n < self.lps.shape[2]) else None
@@ -1004,7 +1055,8 @@ class DecodeSession:
     code-mode session also serves refine-text utterances as text rows beside the code rows (submit(mode="text"); ctts_gpt_enable_text_rows)."""
 
     def __init__(self, gpt: "GPT", sc, seed: int, rows: int, out_slots: int, return_hidden: bool, return_logprobs: bool, ensure_non_empty: bool, max_restarts: int = 64,
-                 text_sc=None, own_slots: bool = False, admit_min: int = 1, share=None, hold=None, guide: Optional[TextGuide] = None):
+                 text_sc=None, own_slots: bool = False, admit_min: int = 1, share=None, hold=None, guide: Optional[TextGuide] = None,
+                 return_text_logprobs: bool = False):
         self.gpt, self.sc, self.seed = gpt, sc, int(seed)
         self.guide = guide                         # guided refine-text: the call's TextGuide (text rows of a code session, or every row of an infer_text one)
         self.max_new = int(sc.max_new_token)
@@ -1015,7 +1067,10 @@ class DecodeSession:
         except ValueError as e:
             raise _lib.HipBackendError(f"open_session: {e}") from None
         # (the text rows' ids share the slots of `ids`: a slot is held by one utterance of either kind)
-        self.out = OutBuffers(out_slots, self.max_new, gpt, return_hidden, return_logprobs, None if text_sc is None else int(text_sc.max_new_token))
+        if return_text_logprobs and text_sc is None and not sc.infer_text:
+            raise _lib.HipBackendError("return_text_logprobs: a code call without text rows (infer_text=True, or a session opened with text_rows=...)")
+        self.out = OutBuffers(out_slots, self.max_new, gpt, return_hidden, return_logprobs, None if text_sc is None else int(text_sc.max_new_token),
+                              text_logprobs=bool(return_text_logprobs), infer_text=bool(sc.infer_text))
         self.ids, self.hid = self.out.ids, self.out.hid
         self.chunk = max(4, min(gpt.chunk_steps, gpt.compact_chunk))
         self.batch_trace: List[tuple] = []         # (steps launched, rows) at every change of the row count
@@ -1632,8 +1687,10 @@ class GPT:
                  min_new_token=0, logits_warpers=[], logits_processors=[], infer_text=False, return_attn=False,
                  return_hidden=False, stream=False, show_tqdm=True, ensure_non_empty=True, stream_batch=24,
                  context=None, noise="auto", seed: Optional[int] = None, max_restarts: int = 64, utt_ids=None, max_new_tokens_per_row=None,
-                 sampling_per_row=None, return_logprobs=False, prompt_of=None, text_guide=None, guide_src=None):
-        """`text_guide` (a TextGuide; infer_text=True) with `guide_src` = one list of source token ids or None per sequence: a guided sequence's ids are provably
+                 sampling_per_row=None, return_logprobs=False, prompt_of=None, text_guide=None, guide_src=None, return_text_logprobs=False):
+        """`return_text_logprobs` (infer_text=True; a separate opt-in -- `return_logprobs` keeps refusing infer_text): `logprobs` / `sampled_logprobs` are [n] per
+        sequence, `final_logprobs` [2] where the row ended by EOS, written by the text sampler (ctts_gpt_set_text_logprob_out); ids are bit-identical without it.
+        `text_guide` (a TextGuide; infer_text=True) with `guide_src` = one list of source token ids or None per sequence: a guided sequence's ids are provably
         its source ids in order, with only the guide's free ids inserted, ended by EOS (include/ctts_hip.h "Guided refine-text"); None = the sequence samples freely.
         `prompt_of` (shared prompt passes, ctts_gpt_share_prompts; code mode): a list of length B naming each sequence's prompt; `emb` / `inputs_ids` /
         `attention_mask` then have one row per PROMPT, every per-row argument (`utt_ids`, `max_new_tokens_per_row`, `sampling_per_row`) and every output has length
@@ -1656,6 +1713,8 @@ class GPT:
             raise _lib.HipBackendError("return_attn=True is unsupported (the reference's eager attention path is broken, SURVEY F2)")
         if return_logprobs and infer_text:
             raise _lib.HipBackendError("return_logprobs: the refine-text pass (infer_text=True) returns no log-probs; code mode only")
+        if return_text_logprobs and not infer_text:
+            raise _lib.HipBackendError("return_text_logprobs: a code call without text rows (infer_text=True, or a session opened with text_rows=...)")
         with self._hold("GPT.generate is already running on this engine (or on an engine sharing its KV cache): exhaust or close the previous generator first"):
             call = resolve_generate(int(inputs_ids.shape[0]), self.max_batch, self.num_vq, self.num_audio_tokens, self.num_text_tokens,
                                     self.dtype_code == _lib.DTYPE_F16 and bool(self.invariant_option()), temperature=temperature, eos_token=eos_token,
@@ -1665,7 +1724,8 @@ class GPT:
             limits = [int(call.sc.max_new_token)] * call.B if call.row_limits is None else [min(max(int(v), 1), int(call.sc.max_new_token)) for v in call.row_limits]
             srcs = resolve_guides(text_guide, guide_src, call.B, bool(infer_text), int(call.sc.eos_token), self.num_text_tokens, limits, "generate")
             yield from self._generate(call, emb, inputs_ids, attention_mask, context or Context(), stream, stream_batch, ensure_non_empty, max_restarts,
-                                      return_hidden, bool(return_logprobs), guide=None if srcs is None else (text_guide, list(range(call.B)), srcs))
+                                      return_hidden, bool(return_logprobs), guide=None if srcs is None else (text_guide, list(range(call.B)), srcs),
+                                      return_text_logprobs=bool(return_text_logprobs))
 
     def _set_text_guide(self, st, tg: TextGuide) -> None:
         f = np.ascontiguousarray(list(tg.free_ids) or [0], dtype=np.int32)
@@ -1708,6 +1768,9 @@ class GPT:
             self._set_guides(st, guide[1], guide[2])
         if out.lps is not None:
             _lib.check(lib.ctts_gpt_set_logprob_out(h, out.lps[0].data_ptr(), out.lps[1].data_ptr(), st), "set_logprob_out")
+        tlps = getattr(out, "tlps", None)          # the text rows' log-probs: a separate opt-in (after begin / the text rows, which reset it; before the first sample)
+        if tlps is not None:
+            _lib.check(lib.ctts_gpt_set_text_logprob_out(h, tlps[0].data_ptr(), tlps[1].data_ptr(), st), "set_text_logprob_out")
         _lib.check(lib.ctts_gpt_prefill(h, emb.data_ptr(), st), "prefill")
 
     def _end_state(self, st) -> int:
@@ -1718,14 +1781,15 @@ class GPT:
         _lib.check(self._lib.ctts_gpt_progress(self._h, C.byref(steps), C.byref(alld), st), "progress")
         return steps.value
 
-    def _generate(self, call, emb, inputs_ids, attention_mask, context, stream, stream_batch, ensure_non_empty, max_restarts, return_hidden, return_logprobs, guide=None):
+    def _generate(self, call, emb, inputs_ids, attention_mask, context, stream, stream_batch, ensure_non_empty, max_restarts, return_hidden, return_logprobs, guide=None,
+                  return_text_logprobs=False):
         """generate() on a held engine: setup, step 0 with its restarts, the streamed or the pipelined loop, the end of the state"""
         lib, h, dev, B, T = self._lib, self._h, self.device, call.B, int(inputs_ids.shape[1])
         infer_text, max_new = bool(call.sc.infer_text), int(call.sc.max_new_token)
         self.compactions, self.shared_prompts = [], [] if call.share is None else [(B, call.share[1])]
         mask = torch.ones(int(inputs_ids.shape[0]), T, dtype=torch.int32, device=dev) if attention_mask is None else attention_mask.to(dev).to(torch.int32).contiguous()
         emb = emb.to(dev, dtype=torch.float32).contiguous()
-        out = OutBuffers(B, max_new, self, return_hidden, return_logprobs)
+        out = OutBuffers(B, max_new, self, return_hidden, return_logprobs, text_logprobs=return_text_logprobs, infer_text=infer_text)
         feed = NoiseFeed(self, call.noise, max_new + max_restarts, B * call.rows_per_seq, call.V, max(int(self.chunk_steps), int(stream_batch) if stream else 1, 1))
         io = out.io(feed.n_draws, call.seed, call.utt_ids, call.row_limits, feed.buf)
         tm = self.host_timing = {}
@@ -1830,7 +1894,7 @@ class GPT:
                       logits_processors=[], return_hidden=False, ensure_non_empty=True, context=None, seed: Optional[int] = None,
                       max_restarts: int = 64, utt_ids=None, max_new_tokens_per_row=None, rows: Optional[int] = None, admit_min: Optional[int] = None,
                       on_done=None, infer_text: bool = False, adapter_slots=None, sampling_per_row=None, return_logprobs=False, prompt_of=None,
-                      text_guide=None, guide_src=None) -> GenerationOutputs:
+                      text_guide=None, guide_src=None, return_text_logprobs=False) -> GenerationOutputs:
         """N utterances (left-padded prompts emb[N,T,H], like generate()) through `rows` <= max_batch decode rows: whenever utterances
         finish, queued ones take over their rows (ctts_gpt_admit) instead of the whole slice waiting for its slowest row as the reference's
         slices of 4 do (pipeline:391-397, gpt.py:527-546); once the queue is empty finished rows are compacted away (ctts_gpt_compact).
@@ -1852,7 +1916,7 @@ class GPT:
                                       return_hidden=return_hidden, ensure_non_empty=ensure_non_empty, context=context, seed=seed, max_restarts=max_restarts,
                                       utt_ids=utt_ids, max_new_tokens_per_row=max_new_tokens_per_row, rows=rows, admit_min=admit_min, infer_text=infer_text,
                                       adapter_slots=adapter_slots, sampling_per_row=sampling_per_row, return_logprobs=return_logprobs, prompt_of=prompt_of,
-                                      text_guide=text_guide, guide_src=guide_src)
+                                      text_guide=text_guide, guide_src=guide_src, return_text_logprobs=return_text_logprobs)
         try:
             while True:
                 ev = next(gen)
@@ -1865,8 +1929,10 @@ class GPT:
     def generate_many_iter(self, emb, inputs_ids, temperature, eos_token, attention_mask=None, max_new_token=2048, min_new_token=0, logits_warpers=[],
                            logits_processors=[], return_hidden=False, ensure_non_empty=True, context=None, seed=None, max_restarts: int = 64,
                            utt_ids=None, max_new_tokens_per_row=None, rows=None, admit_min=None, infer_text: bool = False, progress: bool = False,
-                           adapter_slots=None, sampling_per_row=None, return_logprobs=False, prompt_of=None, text_guide=None, guide_src=None):
-        """`text_guide` / `guide_src`: as in generate() (infer_text=True): an admitted utterance brings its own source (ctts_gpt_set_guides before its admit).
+                           adapter_slots=None, sampling_per_row=None, return_logprobs=False, prompt_of=None, text_guide=None, guide_src=None,
+                           return_text_logprobs=False):
+        """`return_text_logprobs` (infer_text=True): as `return_logprobs`, with the text sampler's one-value-per-step log-probs ([n], [n], [2]).
+        `text_guide` / `guide_src`: as in generate() (infer_text=True): an admitted utterance brings its own source (ctts_gpt_set_guides before its admit).
         generate_many as a generator: yields [(utterance index, ids [n,4] long, hiddens [n,768] or None)] for the utterances that completed
         since the last yield -- while the rest keeps decoding (what was yielded is final: its rows were written before the report that showed
         the utterance finished) -- and returns (StopIteration.value) the GenerationOutputs of all N utterances.
@@ -1877,15 +1943,18 @@ class GPT:
         logprobs, sampled_logprobs, final_logprobs: lists of one), and the returned GenerationOutputs carries the three fields for all N."""
         if return_logprobs and infer_text:
             raise _lib.HipBackendError("return_logprobs: the refine-text pass (infer_text=True) returns no log-probs; code mode only")
+        if return_text_logprobs and not infer_text:
+            raise _lib.HipBackendError("return_text_logprobs: a code call without text rows (infer_text=True, or a session opened with text_rows=...)")
         with self._hold("GPT.generate is already running on this engine (or on an engine sharing its KV cache)", adapter_slots is not None and "adapters"):
             return (yield from self._generate_many(emb, inputs_ids, temperature, eos_token, attention_mask, int(max_new_token), min_new_token, logits_warpers,
                                                    logits_processors, return_hidden, ensure_non_empty, context or Context(), seed, max_restarts, utt_ids,
                                                    max_new_tokens_per_row, rows, admit_min, bool(infer_text), bool(progress), adapter_slots,
-                                                   sampling_per_row, bool(return_logprobs), prompt_of, text_guide, guide_src))
+                                                   sampling_per_row, bool(return_logprobs), prompt_of, text_guide, guide_src, bool(return_text_logprobs)))
 
     def _generate_many(self, emb, inputs_ids, temperature, eos_token, attention_mask, max_new_token, min_new_token, logits_warpers, logits_processors,
                        return_hidden, ensure_non_empty, context, seed, max_restarts, utt_ids, row_limits, rows, admit_min, infer_text=False, progress=False,
-                       adapter_slots=None, sampling_per_row=None, return_logprobs=False, prompt_of=None, text_guide=None, guide_src=None):
+                       adapter_slots=None, sampling_per_row=None, return_logprobs=False, prompt_of=None, text_guide=None, guide_src=None,
+                       return_text_logprobs=False):
         """The request as a client of the DecodeSession driver: prepares the utterances, submits them in their order of service (position j of that order is
         ticket j and output slot j) and translates what the driver delivers into generate_many_iter's events"""
         dev = self.device
@@ -1927,7 +1996,7 @@ class GPT:
         else:
             back = list(range(N))                                  # ticket (= output slot) -> utterance index: every index handed back is mapped through it
         with torch.cuda.device(dev):
-            ses = DecodeSession(self, sc, seed, R, N, return_hidden, return_logprobs, ensure_non_empty, max_restarts, own_slots=True, admit_min=admit_min, guide=None if srcs is None else text_guide,
+            ses = DecodeSession(self, sc, seed, R, N, return_hidden, return_logprobs, ensure_non_empty, max_restarts, own_slots=True, admit_min=admit_min, guide=None if srcs is None else text_guide, return_text_logprobs=return_text_logprobs,
                                 share=None if pof is None else ([pof[u] for u in back], n_prompts, [slots[u] for u in back] if adapter_slots is not None else None))
             self.admissions, self.compactions, self.shared_prompts = ses.admissions, ses.compactions, ses.shared_prompts
             for u in back:
@@ -1936,7 +2005,7 @@ class GPT:
             def event(r, n=None):
                 """one utterance of a yielded list: (index[, tokens so far], ids, hiddens[, its GenerationOutputs so far])"""
                 one = (GenerationOutputs(ids=[r.ids], attentions=[], hiddens=[r.hiddens] if r.hiddens is not None else [], logprobs=[r.logprobs],
-                                         sampled_logprobs=[r.sampled_logprobs], final_logprobs=[r.final_logprobs]),) if return_logprobs else ()
+                                         sampled_logprobs=[r.sampled_logprobs], final_logprobs=[r.final_logprobs]),) if (return_logprobs or return_text_logprobs) else ()
                 return (back[r.ticket],) + (() if n is None else (n,)) + (r.ids, r.hiddens) + one
 
             n_done = 0
@@ -1957,8 +2026,10 @@ class GPT:
     # -- serving session (ctts_gpt_grow / ctts_gpt_cancel) ------------------------------------------------------------------------
     def open_session(self, temperature, eos_token, max_new_token, min_new_token=0, logits_warpers=[], logits_processors=[], return_hidden=False,
                      return_logprobs=False, seed: Optional[int] = None, rows: Optional[int] = None, out_slots: Optional[int] = None, ensure_non_empty=True,
-                     text_rows=None, **out_of_scope) -> DecodeSession:
-        """Opens a DecodeSession: a generate state that stays open while utterances are submitted (submit), cancelled (cancel) and delivered (step / drain).  The
+                     text_rows=None, return_text_logprobs=False, **out_of_scope) -> DecodeSession:
+        """`return_text_logprobs` (with `text_rows`): a text utterance's SessionResult carries logprobs / sampled_logprobs [n] and final_logprobs [2] under the text
+        head (ctts_gpt_set_text_logprob_out); code rows and `return_logprobs` are unaffected.
+        Opens a DecodeSession: a generate state that stays open while utterances are submitted (submit), cancelled (cancel) and delivered (step / drain).  The
         sampling arguments are the call's values, as in generate_many; an utterance may bring its own (submit(sampling=...)).  `rows` <= max_batch bounds the
         decode batch (default max_batch), `out_slots` the utterances whose results are held at once (default 2 * rows; slots are recycled once a result has been
         cloned out).  Holds the engine until close(): generate* and score raise meanwhile.  Not offered inside a session, each refused with a message:
@@ -1987,7 +2058,8 @@ class GPT:
                           "the previous generator / session first")
         try:
             with torch.cuda.device(self.device):
-                ses = DecodeSession(self, sc, seed, rows, out_slots, bool(return_hidden), bool(return_logprobs), bool(ensure_non_empty), text_sc=text_sc, hold=hold, guide=guide)
+                ses = DecodeSession(self, sc, seed, rows, out_slots, bool(return_hidden), bool(return_logprobs), bool(ensure_non_empty), text_sc=text_sc, hold=hold, guide=guide,
+                                    return_text_logprobs=bool(return_text_logprobs))
         except BaseException:
             hold.release()
             raise
@@ -2045,14 +2117,57 @@ class GPT:
         nll, acc, loss, accuracy = score_reduce(lps, ams, [tg[b, :n[b]] for b in range(B)])
         return ScoreOutputs(logprob=lps, argmax=ams, nll=nll, seq_accuracy=acc, loss=loss, accuracy=accuracy)
 
+    @torch.no_grad()
+    def score_text(self, emb: torch.Tensor, attention_mask: torch.Tensor, targets: torch.Tensor, n_targets) -> ScoreOutputs:
+        """score() under the refine-text head (ctts_gpt_score_text): targets [B, max_targets] text ids, target j of sequence b predicted by row T - n_b + j
+        (score_text_inputs builds the four arguments from a refine prompt and refined ids).  logprob[b] / argmax[b] are [n_b]; logprob is the `logprobs` that
+        generate(infer_text=True, return_text_logprobs=True) returned for the same tokens.  Refused on an engine without head_text / emb_text."""
+        with self._hold("GPT.score_text: a generate() generator is live on this engine (or on an engine sharing its KV cache), whose KV lanes "
+                        "scoring would overwrite: exhaust or close it first"):
+            dev = self.device
+            emb = emb.to(dev, dtype=torch.float32).contiguous()
+            if emb.dim() != 3 or emb.shape[2] != self.model_dim:
+                raise ValueError(f"score_text: emb must be [B, T, {self.model_dim}] (got {tuple(emb.shape)})")
+            B, T = int(emb.shape[0]), int(emb.shape[1])
+            mask = torch.as_tensor(attention_mask)
+            if tuple(mask.shape) != (B, T):
+                raise ValueError(f"score_text: attention_mask must be [{B}, {T}] (got {tuple(mask.shape)})")
+            _check_left_padded(mask)
+            tg = torch.as_tensor(targets).cpu().to(torch.int64)
+            nt = torch.as_tensor(n_targets).cpu().to(torch.int64).flatten()
+            if tg.dim() != 2 or tg.shape[0] != B or nt.numel() != B:
+                raise ValueError(f"score_text: targets must be [{B}, max_targets] and n_targets [{B}] (got {tuple(tg.shape)}, {tuple(nt.shape)})")
+            maxt = int(tg.shape[1])
+            for b in range(B):
+                n = int(nt[b])
+                if n < 1 or n > T or n > maxt:
+                    raise ValueError(f"score_text: n_targets[{b}] = {n} outside 1..min(T={T}, max_targets={maxt})")
+            if B > self.max_batch or T > self.max_seq:
+                raise ValueError(f"score_text: B={B} T={T} exceed max_batch={self.max_batch} / max_seq_len={self.max_seq}")
+            msk = mask.to(dev).to(torch.int32).contiguous()
+            tgd = tg.to(torch.int32).to(dev).contiguous()
+            nta = np.ascontiguousarray(nt.numpy(), dtype=np.int32)
+            lp = torch.empty(B, maxt, dtype=torch.float32, device=dev)
+            am = torch.empty(B, maxt, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(self._lib.ctts_gpt_score_text(self._h, B, T, msk.data_ptr(), emb.data_ptr(), tgd.data_ptr(), nta.ctypes.data_as(C.c_void_p), maxt,
+                                                         lp.data_ptr(), am.data_ptr(), self._stream()), "score_text")
+            lp, am = lp.cpu(), am.cpu().to(torch.long)
+            n = nt.tolist()
+            lps = [lp[b, :n[b]] for b in range(B)]
+            ams = [am[b, :n[b]] for b in range(B)]
+            nll, acc, loss, accuracy = score_reduce(lps, ams, [tg[b, :n[b]] for b in range(B)])
+            return ScoreOutputs(logprob=lps, argmax=ams, nll=nll, seq_accuracy=acc, loss=loss, accuracy=accuracy)
+
     @staticmethod
     def _outputs(out: OutBuffers, infer_text: bool = False, order=None) -> GenerationOutputs:
         """All sequences of a generate state (gpt.py:295-305); `order[b]` = the output slot of sequence b (default b).  final_logprobs: where the finish flag is set"""
         n = out.end_idx.cpu().tolist()
-        eos = out.finish.cpu().tolist() if out.lps is not None else [0] * len(n)
+        with_lp = out.lps is not None or (infer_text and out.tlps is not None)
+        eos = out.finish.cpu().tolist() if with_lp else [0] * len(n)
         rows = [out.take(s, n[s], bool(eos[s]), infer_text) for s in (order if order is not None else range(len(n)))]
         ids, hid, lp, slp, flp = ([r[i] for r in rows] for i in range(5))
-        if out.lps is None:
+        if not with_lp:
             return GenerationOutputs(ids=ids, attentions=[], hiddens=hid if out.hid is not None else [])
         return GenerationOutputs(ids=ids, attentions=[], hiddens=hid if out.hid is not None else [], logprobs=lp, sampled_logprobs=slp, final_logprobs=flp)
 

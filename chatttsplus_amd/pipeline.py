@@ -262,7 +262,9 @@ class _Request:
     overlap_vocoder: bool; vocoder_chunk: object
     sample_rate: Optional[int] = None                   # infer(sample_rate=): the rate the waveforms leave at; None = the vocoder's own 24 kHz
     refine_guide: Optional[TextGuide] = None            # infer(refine_guided=): the refine pass's guide (resolve_refine_guided); None = free sampling, as ever
+    refine_cand: int = 1                                # infer(refine_candidates=N): every text is refined N times, the best mean raw log-prob feeds the code pass
     guide_kw = property(lambda self: {} if self.refine_guide is None else dict(guide=self.refine_guide))      # _refine_text's extra keyword: none without a guide (the call as it was)
+    cand_kw = property(lambda self: {} if self.refine_cand <= 1 else dict(n_cand=self.refine_cand))          # ... and none without refine candidates
     device_noise = property(lambda self: self.n_cand > 1 or self.noise_mode == "device")      # (details path) device noise whatever the slice's size
 
     def rows(self, idx, adapters: bool = False, params: bool = True) -> dict:
@@ -302,7 +304,9 @@ class CandidateDetails:
 class InferDetails:
     """What infer(return_details=True) yields instead of the bare list of waveforms.  Per utterance (lists in input order): `wavs`, `ids`, `logprobs`,
     `sampled_logprobs`, `mean_logprob` (the length-normalised raw score: the negative of ScoreOutputs.nll for the same tokens).  With num_candidates:
-    `candidate` (the chosen index), `candidate_scores` ([N] mean log-probs) and `candidates` (the N CandidateDetails, hiddens dropped)."""
+    `candidate` (the chosen index), `candidate_scores` ([N] mean log-probs) and `candidates` (the N CandidateDetails, hiddens dropped).  Where the refine-text
+    pass ran: `refined_logprobs` (per utterance the raw log-probs [m] of its refined ids under the text head, the step that sampled [Ebreak] included) and
+    `refined_mean_logprob` (their mean: the score refine_candidates ranks by); None when the pass was skipped."""
     wavs: list
     ids: List[torch.Tensor]
     logprobs: List[torch.Tensor]
@@ -311,6 +315,58 @@ class InferDetails:
     candidate: Optional[List[int]] = None
     candidate_scores: Optional[List[torch.Tensor]] = None
     candidates: Optional[List[List[CandidateDetails]]] = None
+    refined_logprobs: Optional[List[torch.Tensor]] = None
+    refined_mean_logprob: Optional[List[float]] = None
+
+
+@dataclass(repr=False, eq=False)
+class RefinedTexts:
+    """What the refine pass hands on (_refine_text with log-probs or candidates): per text the winner's `ids` [n], its raw `logprobs` [m] (m = n + 1 where it
+    ended by [Ebreak]: the stopping step counts) and their mean; with refine_candidates the chosen index and the [N] scores per text."""
+    ids: List[torch.Tensor]
+    logprobs: List[torch.Tensor]
+    mean_logprob: List[float]
+    candidate: Optional[List[int]] = None
+    candidate_scores: Optional[List[torch.Tensor]] = None
+
+
+def check_refine_candidates(refine_candidates, utt_ids, stream: bool, noise_mode, slice_size: int) -> int:
+    """Validates infer(refine_candidates=N); returns N.  Each refusal is a HipBackendError that says what is refused."""
+    try:
+        n = int(refine_candidates)
+    except (TypeError, ValueError):
+        n = 0
+    if n < 1 or n != refine_candidates:
+        raise _lib.HipBackendError(f"refine_candidates must be an integer >= 1 (got {refine_candidates!r})")
+    if n > 1:
+        if stream:
+            raise _lib.HipBackendError("refine_candidates > 1 needs stream=False: the refinements are ranked once all of them are complete")
+        if not (isinstance(noise_mode, str) and noise_mode in ("auto", "device")):
+            raise _lib.HipBackendError('refine_candidates > 1 needs device noise (noise="device" or "auto"): host noise is indexed by batch row, not keyed by utterance id')
+        if n > int(slice_size):
+            raise _lib.HipBackendError(f"refine_candidates={n} exceeds slice_size={slice_size}: the refinements of a text share one decode batch")
+        if n >= (1 << (64 - CANDIDATE_SHIFT)):
+            raise _lib.HipBackendError(f"refine_candidates must be below {1 << (64 - CANDIDATE_SHIFT)}")
+        big = [int(u) for u in utt_ids if int(u) >= (1 << CANDIDATE_SHIFT) or int(u) < 0]
+        if big:
+            raise _lib.HipBackendError(f"refine_candidates > 1: utterance id {big[0]} is not below 2^{CANDIDATE_SHIFT} (the candidate index takes the bits above)")
+    return n
+
+
+def rank_refinements(ids, logprobs, final_logprobs, n_cand: int) -> RefinedTexts:
+    """Rows laid out text-major ([text 0 candidate 0, text 0 candidate 1, ...]): per text the candidate with the highest length-normalised mean raw log-prob,
+    the [Ebreak] step included (select_candidate's tie rule: the lowest index; a candidate without a step ranks last)."""
+    raw = [torch.cat([lp.cpu().flatten(), fl[0:1].cpu().flatten()]) if fl is not None else lp.cpu().flatten() for lp, fl in zip(logprobs, final_logprobs)]
+    means = [mean_logprob(r) for r in raw]
+    out = RefinedTexts(ids=[], logprobs=[], mean_logprob=[], candidate=[], candidate_scores=[])
+    for j in range(len(ids) // n_cand):
+        sc = means[j * n_cand:(j + 1) * n_cand]
+        k = select_candidate(sc)
+        out.ids.append(ids[j * n_cand + k]); out.logprobs.append(raw[j * n_cand + k]); out.mean_logprob.append(sc[k])
+        out.candidate.append(k); out.candidate_scores.append(torch.tensor(sc, dtype=torch.float64))
+    if n_cand == 1:
+        out.candidate = out.candidate_scores = None
+    return out
 
 
 def candidate_utt_id(utt_id: int, k: int) -> int:
@@ -1016,6 +1072,25 @@ class ChatTTSPlusPipeline:
                 gpt.set_row_adapters(None)
 
     @torch.no_grad()
+    def score_text(self, text, refined, params_refine_text: Optional[RefineTextParams] = None, lora_path: Optional[str] = None):
+        """Teacher-forced scoring of refined texts under the refine-text head (the text twin of score(); no counterpart in the reference): the prompt of every
+        text is built exactly as the refine pass builds it ("[Sbreak]{text}[Pbreak]{prompt}"), `refined[i]` follows it -- a string (tokenised without special
+        tokens, as the tokenizer decodes the pass's output) or a sequence of text ids -- then [Ebreak], and GPT.score_text returns each token's log-probability
+        and argmax under the raw text head (ScoreOutputs: logprob[i] / argmax[i] are [n_i + 1]; -nll[i] is the score refine_candidates ranks by).  `text` is
+        taken as given (infer() normalises its texts before it refines them).  `lora_path`: one merged adapter for the call."""
+        params = params_refine_text if params_refine_text is not None else RefineTextParams()
+        texts = text if isinstance(text, list) else [text]
+        refined = refined if isinstance(refined, list) and (len(refined) == 0 or isinstance(refined[0], (str, list, tuple, torch.Tensor))) else [refined]
+        if len(refined) != len(texts):
+            raise ValueError(f"score_text: {len(refined)} refined sequences for {len(texts)} texts")
+        gpt = self._gpt_for_lora(lora_path)
+        tok = self.models_dict["tokenizer"]
+        ids = [torch.as_tensor(tok._tokenizer(r, add_special_tokens=False)["input_ids"] if isinstance(r, str) else r, dtype=torch.long).flatten() for r in refined]
+        input_ids, attention_mask, _ = self._refine_prompt(texts, params)
+        si = hip_models.gpt.score_text_inputs(input_ids, attention_mask, ids, int(tok.eos_token))
+        return gpt.score_text(gpt(si["ids"], si["text_mask"]), si["mask"], si["targets"], si["n_targets"])
+
+    @torch.no_grad()
     def _infer_code(self, text, stream: bool, return_hidden: bool, params: InferCodeParams, gpt=None, prompts=None, voices=None, **gen_kwargs):
         """pipeline:157-235 -- same argument plumbing; the GPT object is the hip backend.  `gen_kwargs` (noise, seed, utt_ids, sampling_per_row) ride
         through to GPT.generate: the device noise stream of an utterance is keyed by the request seed and its global utterance id.  `prompts`: one
@@ -1052,25 +1127,41 @@ class ChatTTSPlusPipeline:
         return tok.encode([f"[Sbreak]{i}[Pbreak]{params.prompt}" for i in text], gpt.num_vq, device=self.device)
 
     @torch.no_grad()
-    def _refine_text(self, text, params: RefineTextParams, continuous_rows: int = 0, seed=None, utt_ids=None, guide: Optional[TextGuide] = None):
+    def _refine_text(self, text, params: RefineTextParams, continuous_rows: int = 0, seed=None, utt_ids=None, guide: Optional[TextGuide] = None, n_cand: int = 1,
+                     want_logprobs: bool = False, gpt=None):
         """pipeline:237-277: "[Sbreak]{text}[Pbreak]{prompt}" -> GPT.generate(infer_text=True) on the 21178-way text head.
         `continuous_rows` > 0 (no counterpart in the reference, which refines slice by slice): all sentences of the request through that many decode
         rows with row re-use (GPT.generate_many, device noise keyed by utterance id: a sentence's refined text does not depend on its neighbours).
-        `guide` (refine_guided=): every sentence is guided by its own tokens, read off the refine prompt (refine_sources)."""
-        gpt, tok = self.models_dict["gpt"], self.models_dict["tokenizer"]
+        `guide` (refine_guided=): every sentence is guided by its own tokens, read off the refine prompt (refine_sources).
+        `want_logprobs` / `n_cand` > 1 (return_details, refine_candidates=N): the call returns a RefinedTexts instead of the GenerationOutputs -- the pass runs with
+        return_text_logprobs; with N candidates every text is laid out N times as ordinary text rows under the utterance ids candidate_utt_id(u, k) (candidate 0
+        is the plain refinement), device noise keyed by `seed`, through `continuous_rows` rows with row re-use, and rank_refinements picks the winners.  With a
+        guide every candidate holds the source tokens: the ranking chooses among the insertions.  No prompt pass is shared (ctts_gpt_share_prompts refuses infer_text)."""
+        gpt, tok = gpt or self.models_dict["gpt"], self.models_dict["tokenizer"]
+        want_logprobs = want_logprobs or getattr(self, "_refine_details", False)      # (_infer_details with return_details)
         input_ids, attention_mask, text_mask = self._refine_prompt(text, params)
+        if n_cand > 1:
+            rep = torch.arange(len(text), device=input_ids.device).repeat_interleave(n_cand)
+            input_ids, attention_mask, text_mask = input_ids[rep], attention_mask[rep], text_mask[rep]
+            utt_ids = [candidate_utt_id(u, k) for u in (utt_ids if utt_ids is not None else range(len(text))) for k in range(n_cand)]
         gkw = {}
         if guide is not None:
             srcs = refine_sources(tok, input_ids, attention_mask)
             check_refine_sources(srcs, params.max_new_token)
             gkw = dict(text_guide=guide, guide_src=srcs)
+        if want_logprobs or n_cand > 1:
+            gkw["return_text_logprobs"] = True
         warpers, processors = gen_logits(num_code=tok.len, top_P=params.top_P, top_K=params.top_K, repetition_penalty=params.repetition_penalty)
         emb = gpt(input_ids, text_mask)
         kw = dict(temperature=torch.tensor([params.temperature]), eos_token=tok.eos_token, attention_mask=attention_mask, max_new_token=params.max_new_token,
                   min_new_token=params.min_new_token, logits_warpers=warpers, logits_processors=processors, ensure_non_empty=params.ensure_non_empty, infer_text=True)
         if continuous_rows > 0:
-            return gpt.generate_many(emb, input_ids, seed=seed, utt_ids=utt_ids, rows=continuous_rows, **kw, **gkw)
-        return next(gpt.generate(emb, input_ids, stream=False, show_tqdm=params.show_tqdm, **kw, **gkw))
+            res = gpt.generate_many(emb, input_ids, seed=seed, utt_ids=utt_ids, rows=continuous_rows, **kw, **gkw)
+        else:
+            res = next(gpt.generate(emb, input_ids, stream=False, show_tqdm=params.show_tqdm, **kw, **gkw))
+        if not (want_logprobs or n_cand > 1):
+            return res
+        return rank_refinements(res.ids, res.logprobs, res.final_logprobs, n_cand)
 
     def _codes_synth(self):
         """The "decode codes" model of use_decoder=False (pipeline:292: decoder = models_dict["dvae_encode"], i.e. the DVAE_full checkpoint
@@ -1260,6 +1351,8 @@ class ChatTTSPlusPipeline:
                 params_infer_code = dataclasses.replace(params_infer_code, spk_emb=self._speaker_rows(params_infer_code.spk_emb, diffs))
         # return_details / num_candidates (no counterpart in the reference): log-probs written by the sampler, N candidates per utterance ranked by them
         n_cand = check_candidate_request(kwargs.get("num_candidates", 1), utt_ids, stream, noise_mode)
+        # refine_candidates (the text twin): every text refined N times as ordinary text rows, ranked by the text sampler's raw log-probs; the winner feeds the code pass
+        refine_cand = check_refine_candidates(kwargs.get("refine_candidates", 1), utt_ids, stream, noise_mode, slice_size)
         # sample_rate (no counterpart in the reference, which delivers 24 kHz): the finished waveforms resampled on the device; the pair is refused here, before any decoding
         rate = self.output_rate(kwargs.get("sample_rate"), "infer")
         if rate is not None and stream:
@@ -1272,7 +1365,7 @@ class ChatTTSPlusPipeline:
                         noise_seed=kwargs.get("noise_seed"), use_decoder=use_decoder, skip_refine_text=skip_refine_text, refine_text_only=refine_text_only,
                         continuous=kwargs.get("continuous"), n_cand=n_cand, return_details=bool(kwargs.get("return_details")), select=kwargs.get("select"),
                         share_prompt=kwargs.get("share_prompt"), ids_sink=kwargs.get("_ids_sink"), overlap_vocoder=bool(kwargs.get("overlap_vocoder", False)),
-                        vocoder_chunk=kwargs.get("vocoder_chunk", 32), sample_rate=rate,
+                        vocoder_chunk=kwargs.get("vocoder_chunk", 32), sample_rate=rate, refine_cand=1 if skip_refine_text else refine_cand,
                         refine_guide=None if skip_refine_text else resolve_refine_guided(kwargs.get("refine_guided"), self.models_dict["tokenizer"]))
 
     def _infer_sliced(self, req: _Request):
@@ -1284,7 +1377,11 @@ class ChatTTSPlusPipeline:
             idx = range(ii, min(ii + req.slice_size, len(req.texts)))
             text = [req.texts[i] for i in idx]
             if not req.skip_refine_text:                                                   # pipeline:399-411
-                text = _decode_refined(self.models_dict["tokenizer"], self._refine_text(text, req.params_refine_text, **req.guide_kw).ids)
+                ckw = {}
+                if req.refine_cand > 1:            # N refinements per text through slice_size rows, device noise keyed by candidate_utt_id
+                    seed = seed if seed is not None else _draw_request_seed()
+                    ckw = dict(continuous_rows=req.slice_size, seed=seed, utt_ids=[req.utt_ids[i] for i in idx], **req.cand_kw)
+                text = _decode_refined(self.models_dict["tokenizer"], self._refine_text(text, req.params_refine_text, **req.guide_kw, **ckw).ids)
                 if req.refine_text_only:
                     yield text
             if req.refine_text_only:
@@ -1338,7 +1435,7 @@ class ChatTTSPlusPipeline:
         texts = list(req.texts)
         if not req.skip_refine_text:
             # pipeline:399-411 for the whole request at once, `slice_size` rows kept busy (noise keyed by utterance id on stream 4: a sentence's refined text does not depend on the batch)
-            refined = self._refine_text(texts, req.params_refine_text, continuous_rows=req.slice_size, seed=seed, utt_ids=req.utt_ids, **req.guide_kw)
+            refined = self._refine_text(texts, req.params_refine_text, continuous_rows=req.slice_size, seed=seed, utt_ids=req.utt_ids, **req.guide_kw, **req.cand_kw)
             texts = _decode_refined(self.models_dict["tokenizer"], refined.ids)
             if req.refine_text_only:
                 yield texts
@@ -1462,18 +1559,34 @@ class ChatTTSPlusPipeline:
         if seed is None and req.noise_mode in ("auto", "device") and (req.device_noise or cont or min(per_slice, n_utt) * n_cand > 4):
             seed = _draw_request_seed()
         texts = list(req.texts)
-        if not req.skip_refine_text:                 # once per utterance, in the batches the plain call refines in
-            if cont:
-                texts = _decode_refined(tok, self._refine_text(texts, req.params_refine_text, continuous_rows=slice_size, seed=seed, utt_ids=req.utt_ids, **req.guide_kw).ids)
-            else:
-                texts = [t for ii in range(0, n_utt, slice_size) for t in _decode_refined(tok, self._refine_text(texts[ii:ii + slice_size], req.params_refine_text, **req.guide_kw).ids)]
+        refined = None
+        if not req.skip_refine_text:                 # once per utterance (refine_candidates: N times), in the batches the plain call refines in
+            # return_details: the pass also returns its log-probs (RefinedTexts).  Asked through the instance, not through a keyword: the calls below are the
+            # plain request's, argument for argument
+            self._refine_details = bool(req.return_details)
+            try:
+                if cont:
+                    parts = [self._refine_text(texts, req.params_refine_text, continuous_rows=slice_size, seed=seed, utt_ids=req.utt_ids, **req.guide_kw, **req.cand_kw)]
+                else:
+                    parts = []
+                    for ii in range(0, n_utt, slice_size):
+                        ckw = {}
+                        if req.refine_cand > 1:
+                            seed = seed if seed is not None else _draw_request_seed()
+                            ckw = dict(continuous_rows=slice_size, seed=seed, utt_ids=req.utt_ids[ii:ii + slice_size], **req.cand_kw)
+                        parts.append(self._refine_text(texts[ii:ii + slice_size], req.params_refine_text, **req.guide_kw, **ckw))
+            finally:
+                self._refine_details = False
+            texts = [t for p in parts for t in _decode_refined(tok, p.ids)]
+            if req.return_details and all(isinstance(p, RefinedTexts) for p in parts):
+                refined = ([lp for p in parts for lp in p.logprobs], [m for p in parts for m in p.mean_logprob])
         texts = [_with_uv_break(t) for t in texts]
         read_option = getattr(gpt, "get_option", None)           # (an engine object without options shares only when asked to)
         share = resolve_share_prompt(req.share_prompt, n_cand, n_cand > 1 and read_option is not None and read_option("batch_invariant"))
         for us in ([range(n_utt)] if cont else [range(ii, min(ii + per_slice, n_utt)) for ii in range(0, n_utt, per_slice)]):
             cands = self._run_candidates(req, texts, list(us), seed, cont, share)
             if cands is not None:
-                yield self._pick_candidates(req, list(us), cands)
+                yield self._pick_candidates(req, list(us), cands, refined)
 
     def _run_candidates(self, req: _Request, texts, us, seed, cont: bool, share: bool):
         """utterances `us` x n_cand candidates as one list of rows (utterance-major) -> one CandidateDetails per row; None: ensure_non_empty gave up (gpt.py:525)"""
@@ -1515,7 +1628,7 @@ class ChatTTSPlusPipeline:
                                                           mean_logprob=mean_logprob(res.logprobs[r]), final_logprobs=res.final_logprobs[r],
                                                           hiddens=res.hiddens[r] if use_decoder else None) for r in range(len(rows))]
 
-    def _pick_candidates(self, req: _Request, us, cands):
+    def _pick_candidates(self, req: _Request, us, cands, refined=None):
         """the winner of every utterance of `us` among its n_cand CandidateDetails (`select` or select_candidate), vocoded: a list of waveforms or InferDetails"""
         n_cand, use_decoder = req.n_cand, req.use_decoder
         chosen, scores = [], []
@@ -1535,6 +1648,8 @@ class ChatTTSPlusPipeline:
             return wavs
         det = InferDetails(wavs=wavs, ids=[w.ids for w in win], logprobs=[w.logprobs for w in win], sampled_logprobs=[w.sampled_logprobs for w in win],
                            mean_logprob=[w.mean_logprob for w in win])
+        if refined is not None:                      # the refine pass ran: the raw log-probs of each utterance's refined ids ([Ebreak] step included) and their mean
+            det.refined_logprobs, det.refined_mean_logprob = [refined[0][u] for u in us], [refined[1][u] for u in us]
         if n_cand > 1:
             det.candidate, det.candidate_scores = chosen, scores
             det.candidates = [[dataclasses.replace(c, hiddens=None) for c in cands[j * n_cand:(j + 1) * n_cand]] for j in range(len(us))]
@@ -1628,6 +1743,10 @@ class ChatTTSPlusPipeline:
             raise _lib.HipBackendError("infer_sharded serves one generation per utterance and returns waveforms: num_candidates > 1 and return_details are "
                                        "refused (rank the candidates with infer() on one rank)")
         kwargs.pop("num_candidates", None); kwargs.pop("return_details", None)
+        if kwargs.get("refine_candidates", 1) != 1:
+            raise _lib.HipBackendError("infer_sharded(refine_candidates=...) is not offered: text log-probs are not exchanged between ranks (rank the "
+                                       "refinements with infer() on one rank)")
+        kwargs.pop("refine_candidates", None)
         if kwargs.get("refine_guided") not in (None, False):
             raise _lib.HipBackendError("infer_sharded(refine_guided=...) is not offered: guided refinement is served by infer() and by sessions "
                                        "(open_session(refine=..., refine_guided=...))")

@@ -332,6 +332,20 @@ int ctts_gpt_prefill(ctts_gpt* h, const float* emb_dev, void* stream);
 int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* attention_mask_dev, const float* emb_dev, const int32_t* targets_dev,
                    const int32_t* n_targets_host, int max_targets, float* logprob_dev, int32_t* argmax_dev, void* stream);
 
+/* Teacher-forced scoring under the refine-text head: ctts_gpt_score's layout and position rule -- the final-normed hidden row at T - n_b + j predicts target j --
+ * with targets int32 [B][max_targets] and ONE column of results:
+ *     logprob[b][j] = log_softmax(head_text(hidden))[targets[b][j]]   on the raw vocab_text_head-wide row;   argmax[b][j] = the first index of its largest logit
+ * both [B][max_targets] device.  Entries j >= n_b are written as 0 and -1; a target outside [0, vocab_text_head) gives NaN and -1 (no logit is read for it).
+ * The gathered rows go through the text-head launch of a decode step (final RMSNorm + weight-normed head_text, PRO_NORM / EPI_LOGITS) in chunks of at most
+ * max_batch rows (option "score_text_chunk", read only) into a logits scratch, which one workgroup per row reduces (first index of the maximum, sum of expf in
+ * fp32): log-probs agree with the lp_raw that ctts_gpt_set_text_logprob_out wrote for the same tokens to the decode-against-prompt-pass tolerance.  The first
+ * call allocates the scratch, max_batch x (hidden + vocab_text_head + 1) words (11 MB at 128 rows); engines that never call it allocate nothing more.
+ * Per-sequence adapter slots (ctts_gpt_set_row_adapters) are honoured; the call ENDS any generate state; fp32 and fp16 engines.  Errors naming the limit as
+ * ctts_gpt_score's, and: an engine without head_text.* / emb_text.weight.  Asynchronous: never synchronises.  A fused head with an online log-sum-exp that never
+ * writes the logits is the faster shape for long targets and is not built here (it changes the summation order against the decode step). */
+int ctts_gpt_score_text(ctts_gpt* h, int B, int T, const int32_t* attention_mask_dev, const float* emb_dev, const int32_t* targets_dev,
+                        const int32_t* n_targets_host, int max_targets, float* logprob_dev, int32_t* argmax_dev, void* stream);
+
 /* Sample phase for the current hidden rows: final RMSNorm + 4 folded heads + sampler chain +
  * EOS/finish bookkeeping + next-token embedding (gpt.py:422-494,527-532).  Used once after prefill
  * (step 0) and again after an ensure_non_empty restart (gpt.py:496-525). */
@@ -443,7 +457,8 @@ int ctts_gpt_admit_sampling(ctts_gpt* h, int n, const int32_t* rows, const ctts_
  * the stack's output in the launch's granules, not in the residual rows the text head reads), so at <= 2 rows the code heads are a third extra launch.  Every row takes
  * its arrival ticket once per step, in the kernel of its mode; the last arriver advances the step.  Unmixed steps launch exactly what they did.  Device noise:
  * stream 4 of (seed, utterance id) for a text row, streams 0-3 for a code row, so one utterance id may serve a refine stage and a code stage.
- * Log-probs (ctts_gpt_set_logprob_out) stay code-only: a text row writes none.  A text row's adapter slot is an argument like any row's (admit_adapters).
+ * Log-probs of the code entry point (ctts_gpt_set_logprob_out) stay code-only: a text row writes none there; a text row's own log-probs are a separate opt-in,
+ * ctts_gpt_set_text_logprob_out, after enable_text_rows.  A text row's adapter slot is an argument like any row's (admit_adapters).
  * Every ctts_gpt_begin switches the feature off again.  Under "batch_invariant" a text row's ids equal those of its batch-1 infer_text call bit for bit, and the
  * code rows' results do not depend on the text rows beside them.
  * Refused, each with a message: a mode-1 row without enable_text_rows; an engine without head_text / emb_text; use_penalty in text_sc; caller-supplied noise;
@@ -485,7 +500,8 @@ int ctts_gpt_admit_modes(ctts_gpt* h, int n, const int32_t* rows, const int32_t*
  * range or equal to EOS; n + 1 > the row's limit (by set_guides for begin's rows, by ctts_gpt_admit for the rows it seats); an output slot >= 1024; caller-supplied
  * noise with guides in a code call; guides without the per-call part; a guide on a code row (set_text_guide in a code call without text rows; set_guides / admit on a
  * slot a code row holds).
- * Not offered: a gathered text head that computes only the logits of A (the head still streams its whole matrix); log-probs of text rows; guides for code rows. */
+ * Not offered: a gathered text head that computes only the logits of A (the head still streams its whole matrix); guides for code rows.  Log-probs of guided
+ * (and unguided) text rows: ctts_gpt_set_text_logprob_out below. */
 int ctts_gpt_set_text_guide(ctts_gpt* h, const int32_t* free_ids_host, int n_free, int max_run, void* stream);
 int ctts_gpt_set_guides(ctts_gpt* h, int n, const int32_t* out_slots_host, const int32_t* src_concat_host, const int32_t* src_off_host, void* stream);
 
@@ -524,6 +540,26 @@ int ctts_gpt_share_prompts(ctts_gpt* h, int n, const int32_t* prompt_of_host, in
  * first sample. */
 int ctts_gpt_set_logprob_out(ctts_gpt* h, float* lp_raw_dev, float* lp_sampled_dev, void* stream);
 
+/* Log-probs of the refine-text pass: the text twin of ctts_gpt_set_logprob_out, a separate opt-in (the code entry point keeps refusing infer_text, and keeps
+ * writing nothing for text rows).  Per (utterance, step), for the id the text sampler returned at the row's own step:
+ *   lp_raw      log_softmax(raw text-head logits)[id] over the FULL vocab_text_head-wide row, before the division by the temperature -- for guided rows too (a
+ *               guided row samples from its <= 65 allowed logits; for lp_raw it reads its whole row once more): the quantity ctts_gpt_score_text returns for
+ *               the same token
+ *   lp_sampled  log p(id) under the distribution the race drew from: logf(expf(x[id] - m2) * inv2) over the kept set, after temperature, guide mask, top-P,
+ *               top-K and the min_new_token rule.  An id outside the kept set gives -inf: the unguided stand-in (element 0, when every ratio is 0 or NaN), a
+ *               guided stand-in (src[cur] / EOS) that the warpers removed or whose probability underflowed to 0
+ * Both buffers are fp32 [n_out][text max_new_token] device memory -- ONE value per step -- indexed by the utterance's output slot like the text ids (an infer_text
+ * call: ctts_gen_io.ids' extent and the call's max_new_token; text rows in a code call: the extent of text_ids_dev and text_sc.max_new_token).  Either may be
+ * NULL.  The values are stored next to the id, under the id's condition, with ctts_gpt_set_logprob_out's rules: the step that samples EOS is written at end_idx;
+ * a finished row writes nothing; unsampled entries keep the caller's fill; a restart or a re-admission with attempt + 1 overwrites from step 0.  They feed nothing
+ * back into the sampling arithmetic: ids, finish, end_idx and guide cursors are bit-identical with and without them, and a call that does not ask runs the same
+ * launches.  The pointers live in the per-call block the text sampler reads (null = off; tests uniform over the workgroup), so captured decode graphs are shared
+ * between calls with and without them.  One workgroup per row, fixed reduction order: under "batch_invariant" / "schedule_invariant" both values are part of the
+ * CONTRACT.  Caller-supplied noise is allowed (an infer_text call): the values do not depend on where the noise comes from.
+ * Valid after ctts_gpt_begin of an infer_text call, or after ctts_gpt_enable_text_rows in a code call, and before the first ctts_gpt_sample / ctts_gpt_decode;
+ * begin and enable_text_rows reset both to NULL.  Refused by name: no generate state; a code call without text rows; a call after the first sample. */
+int ctts_gpt_set_text_logprob_out(ctts_gpt* h, float* lp_raw_dev, float* lp_sampled_dev, void* stream);
+
 /* Non-blocking variant: enqueues a copy of {steps_done, draws, all_finished, -} into 4 int32 of PINNED host memory; the
  * caller records an event after it and reads the words once the event has completed -- lets the host keep one chunk of
  * decode steps in flight while it inspects the previous one. */
@@ -561,6 +597,14 @@ int ctts_sampler_run_rows_lp(const ctts_sampler_cfg* sc, const ctts_row_sampling
 int ctts_sampler_run_text_guided(const ctts_sampler_cfg* sc, const float* logits_dev, const float* q_dev, int rows, int vocab, const int32_t* free_ids_host, int n_free,
                                  int max_run, const int32_t* src_concat_host, const int32_t* src_off_host, const int32_t* cur_host, const int32_t* run_host,
                                  const int32_t* step_host, const int32_t* limit_host, int32_t* idx_out_host, int32_t* cur_out_host, int32_t* run_out_host, void* stream);
+
+/* ... one step of the text kernel with the log-probs of the returned id (ctts_gpt_set_text_logprob_out's definitions; a test hook, synchronous).  src_concat_host
+ * == NULL: unguided rows through the unguided instantiation (the guide arguments and cur_out / run_out are ignored and may be NULL); otherwise the guided one,
+ * as above.  lp_raw_out_host / lp_sampled_out_host fp32 [rows], HOST; either may be NULL, both NULL = the launch of a call without the feature. */
+int ctts_sampler_run_text_lp(const ctts_sampler_cfg* sc, const float* logits_dev, const float* q_dev, int rows, int vocab, const int32_t* free_ids_host, int n_free,
+                             int max_run, const int32_t* src_concat_host, const int32_t* src_off_host, const int32_t* cur_host, const int32_t* run_host,
+                             const int32_t* step_host, const int32_t* limit_host, int32_t* idx_out_host, int32_t* cur_out_host, int32_t* run_out_host,
+                             float* lp_raw_out_host, float* lp_sampled_out_host, void* stream);
 
 /* last measured average duration (ms) of one captured decode step, measured with hipEvents on the launch
  * stream around `n` graph replays; used by bench.py for the roofline object. */
