@@ -54,6 +54,10 @@ __device__ inline void cnx_split4(const f32x4 v, half4& hi, half4& lo) {
         hi[j] = (half_t)c;
         lo[j] = (half_t)(c - (float)hi[j]);
     }
+    // fmaxf(NaN, a) = a: the clamp would turn a NaN into -65504.  The four values are four K entries of ONE frame's row of the next GEMM, whose outputs a single NaN
+    // makes NaN throughout: one unordered-compare per pair and one select per four values put it back (cheaper than a select per element)
+    const bool nan = __builtin_isunordered(v[0], v[1]) | __builtin_isunordered(v[2], v[3]);
+    hi[0] = nan ? (half_t)__builtin_nanf("") : hi[0];
 }
 
 // WT = n tiles and frame groups per wave: 4 (128 x 128 blocks) or 2 (64 x 64 blocks on a ring of four 16 KB stages: four times the blocks for the small batches of

@@ -649,7 +649,10 @@ int ctts_voc_set_weight(ctts_voc* h, const char* name, const float* data, size_t
 int ctts_voc_finalize(ctts_voc* h);
 
 /* DVAE.forward(mode="decode") (dvae.py:272-291): hidden fp32 [n][768] device (one utterance) ->
- * mel fp32 [100][2n] device. */
+ * mel fp32 [100][2n] device.
+ * Range (both calls below and the batched ones): the GEMMs keep fp32-level accuracy while their input activations lie in about
+ * [2^-7, 65504] in magnitude; larger values (+-inf included) are clamped to +-65504, a row that is uniformly smaller loses accuracy
+ * as 2^-25 / |x|, and NaN propagates to the output (it is not an error). */
 int ctts_dvae_decode(ctts_voc* h, const float* hidden_dev, int n_tokens, float* mel_dev, void* stream);
 /* vocos.Vocos.decode (pipeline:303): mel fp32 [100][F] device -> wav fp32 [hop*(F-1)] device */
 int ctts_vocos_decode(ctts_voc* h, const float* mel_dev, int frames, float* wav_dev, void* stream);

@@ -417,34 +417,40 @@ class OracleGPT:
 # DVAE decoder (models/dvae.py)
 # ----------------------------------------------------------------------------------------------
 
-def _convnext(sd, p, x, dilation, kernel=7):
-    """ConvNeXtBlock.forward (dvae.py:48-63; Vocos' block is the dilation=1 case)."""
+def _cast(sd, dtype):
+    """State dict as tensors of `dtype` (float32: what every function below has always computed in; float64: the high-precision reference)."""
+    return {k: _t(v).to(dtype) for k, v in sd.items()}
+
+
+def _convnext(sd, p, x, dilation, kernel=7, dtype=torch.float32):
+    """ConvNeXtBlock.forward (dvae.py:48-63; Vocos' block is the dilation=1 case).  `sd`: tensors of `dtype` already (_cast)."""
+    w = lambda k: sd[p + k].to(dtype)
     C = x.shape[1]
-    y = F.conv1d(x, sd[p + "dwconv.weight"], sd[p + "dwconv.bias"], padding=dilation * (kernel // 2),
+    y = F.conv1d(x, w("dwconv.weight"), w("dwconv.bias"), padding=dilation * (kernel // 2),
                  dilation=dilation, groups=C)
     y = y.transpose(1, 2)
-    y = F.layer_norm(y, (C,), sd[p + "norm.weight"], sd[p + "norm.bias"], eps=1e-6)
-    y = F.linear(y, sd[p + "pwconv1.weight"], sd[p + "pwconv1.bias"])
+    y = F.layer_norm(y, (C,), w("norm.weight"), w("norm.bias"), eps=1e-6)
+    y = F.linear(y, w("pwconv1.weight"), w("pwconv1.bias"))
     y = F.gelu(y)
-    y = F.linear(y, sd[p + "pwconv2.weight"], sd[p + "pwconv2.bias"])
-    y = y * sd[p + "gamma"]
+    y = F.linear(y, w("pwconv2.weight"), w("pwconv2.bias"))
+    y = y * w("gamma")
     return y.transpose(1, 2) + x
 
 
 @torch.no_grad()
-def dvae_decode(sd: Dict[str, np.ndarray], hidden: torch.Tensor) -> torch.Tensor:
+def dvae_decode(sd: Dict[str, np.ndarray], hidden: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
     """DVAE.forward(mode="decode") with vq_layer=None (dvae.py:272-291).
     hidden [n, 768] (one utterance's GPT hiddens) -> mel [100, 2n].  The pipeline passes
-    hiddens.permute(1,0)[None] = [1,768,n] (pipeline:298-300)."""
-    sd = {k: _t(v).float() for k, v in sd.items()}
-    inp = _t(hidden).float().permute(1, 0)[None]                                       # [1,768,n]
+    hiddens.permute(1,0)[None] = [1,768,n] (pipeline:298-300).  `dtype=torch.float64`: weights and arithmetic in float64."""
+    sd = _cast(sd, dtype)
+    inp = _t(hidden).to(dtype).permute(1, 0)[None]                                     # [1,768,n]
     x = inp.view(inp.size(0), 2, inp.size(1) // 2, inp.size(2)).permute(0, 2, 3, 1).flatten(2)   # [1,384,2n]
     y = F.conv1d(x, sd["decoder.conv_in.0.weight"], sd["decoder.conv_in.0.bias"], padding=1)
     y = F.gelu(y)
     y = F.conv1d(y, sd["decoder.conv_in.2.weight"], sd["decoder.conv_in.2.bias"], padding=1)
     n_layer = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("decoder.decoder_block."))
     for i in range(n_layer):
-        y = _convnext(sd, f"decoder.decoder_block.{i}.", y, dilation=2)
+        y = _convnext(sd, f"decoder.decoder_block.{i}.", y, dilation=2, dtype=dtype)
     y = F.conv1d(y, sd["decoder.conv_out.weight"])
     y = F.conv1d(y, sd["out_conv.weight"], padding=1)
     return (y * sd["coef"])[0]                                                         # [100, 2n]
@@ -527,11 +533,11 @@ def gfsq_quantize(x: torch.Tensor, sd, levels=(5, 5, 5, 5), G: int = 2, R: int =
     return torch.stack(out, 0), torch.stack(lat, 0)                              # [G*R, T] (row = g * R + r), [G, T, D]
 
 
-def gfsq_latent_from_indices(ids: torch.Tensor, levels=(5, 5, 5, 5), G: int = 2, R: int = 2) -> torch.Tensor:
+def gfsq_latent_from_indices(ids: torch.Tensor, levels=(5, 5, 5, 5), G: int = 2, R: int = 2, dtype=torch.float32) -> torch.Tensor:
     """ResidualFSQ.get_output_from_indices restated up to project_out (GFSQ._embed, dvae.py:85-96): index -> per-dimension level
     (index // basis) % levels -> code (level - half_width) / half_width, summed over the R quantizers with scale (levels-1)^-r."""
     lv = torch.tensor(levels, dtype=torch.int64)
-    hw = torch.tensor([l // 2 for l in levels], dtype=torch.float32)
+    hw = torch.tensor([l // 2 for l in levels], dtype=dtype)
     basis = torch.cumprod(torch.tensor([1] + list(levels[:-1]), dtype=torch.int64), 0)
     ids = _t(ids).to(torch.int64)
     lat = []
@@ -539,24 +545,24 @@ def gfsq_latent_from_indices(ids: torch.Tensor, levels=(5, 5, 5, 5), G: int = 2,
         acc = 0
         for r in range(R):
             level = (ids[g * R + r][:, None] // basis[None, :]) % lv[None, :]
-            acc = acc + ((level.float() - hw) / hw) * (lv.float() - 1) ** (-r)
+            acc = acc + ((level.to(dtype) - hw) / hw) * (lv.to(dtype) - 1) ** (-r)
         lat.append(acc)
     return torch.stack(lat, 0)
 
 
 @torch.no_grad()
-def dvae_decode_codes(sd: Dict[str, np.ndarray], ids: torch.Tensor, levels=(5, 5, 5, 5), G: int = 2, R: int = 2) -> torch.Tensor:
+def dvae_decode_codes(sd: Dict[str, np.ndarray], ids: torch.Tensor, levels=(5, 5, 5, 5), G: int = 2, R: int = 2, dtype=torch.float32) -> torch.Tensor:
     """DVAE.forward decode WITH a quantiser (dvae.py:272-291; the use_decoder=False branch, pipeline:292,435-439): ids [n, G*R] (one
     utterance's generated code ids) -> GFSQ._embed (dvae.py:85-96 -> GroupedResidualFSQ.get_output_from_indices, vector_quantize_pytorch
     1.17.8, third party: parity unpinned) = per group project_out(sum of the R residual codes), groups concatenated -> the decoder
     stack (pinned on the reference's module: tests/golden/dvae_full_decode_real.npz) -> mel [100, 2n]."""
     ids = _t(ids).to(torch.int64)
-    lat = gfsq_latent_from_indices(ids.t().contiguous(), levels, G, R)                  # [G, n, 4]; row g*R + r of ids.T = codebook r of group g
-    feats = [F.linear(lat[g], _t(sd[f"vq_layer.quantizer.rvqs.{g}.project_out.weight"]).float(),
-                      _t(sd[f"vq_layer.quantizer.rvqs.{g}.project_out.bias"]).float()) for g in range(G)]
+    lat = gfsq_latent_from_indices(ids.t().contiguous(), levels, G, R, dtype)                # [G, n, 4]; row g*R + r of ids.T = codebook r of group g
+    feats = [F.linear(lat[g], _t(sd[f"vq_layer.quantizer.rvqs.{g}.project_out.weight"]).to(dtype),
+                      _t(sd[f"vq_layer.quantizer.rvqs.{g}.project_out.bias"]).to(dtype)) for g in range(G)]
     feat = torch.cat(feats, dim=-1)                                                     # [n, dim * G] (= feat.transpose(1, 2) of _embed, per frame)
     dec = {k: v for k, v in sd.items() if k.startswith("decoder.") or k in ("out_conv.weight", "coef")}
-    return dvae_decode(dec, feat)
+    return dvae_decode(dec, feat, dtype=dtype)
 
 
 @torch.no_grad()
@@ -586,34 +592,35 @@ def dvae_encode(sd: Dict[str, np.ndarray], wav: torch.Tensor, pre_bound: bool = 
 # ----------------------------------------------------------------------------------------------
 
 @torch.no_grad()
-def vocos_backbone(sd, mel: torch.Tensor) -> torch.Tensor:
+def vocos_backbone(sd, mel: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
     """VocosBackbone.forward: embed conv k7 p3 -> LN -> 8 ConvNeXt (dil 1) -> final LN.  mel [100,F] -> [F,512]."""
-    x = F.conv1d(mel[None], sd["backbone.embed.weight"], sd["backbone.embed.bias"], padding=3)
+    sd = _cast(sd, dtype)
+    x = F.conv1d(_t(mel).to(dtype)[None], sd["backbone.embed.weight"], sd["backbone.embed.bias"], padding=3)
     C = x.shape[1]
     x = F.layer_norm(x.transpose(1, 2), (C,), sd["backbone.norm.weight"], sd["backbone.norm.bias"], eps=1e-6).transpose(1, 2)
     n_layer = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("backbone.convnext."))
     for i in range(n_layer):
-        x = _convnext(sd, f"backbone.convnext.{i}.", x, dilation=1)
+        x = _convnext(sd, f"backbone.convnext.{i}.", x, dilation=1, dtype=dtype)
     x = F.layer_norm(x.transpose(1, 2), (C,), sd["backbone.final_layer_norm.weight"], sd["backbone.final_layer_norm.bias"], eps=1e-6)
     return x[0]
 
 
 @torch.no_grad()
-def vocos_head_spec(sd, feats: torch.Tensor):
+def vocos_head_spec(sd, feats: torch.Tensor, dtype=torch.float32):
     """ISTFTHead.forward up to the complex spectrogram: Linear(512->n_fft+2); mag = clip(exp(.), max=1e2);
     S = mag * (cos p + i sin p).  Returns (real, imag) each [n_fft/2+1, F]."""
-    x = F.linear(feats, sd["head.out.weight"], sd["head.out.bias"]).transpose(0, 1)    # [1026, F]
+    x = F.linear(_t(feats).to(dtype), _t(sd["head.out.weight"]).to(dtype), _t(sd["head.out.bias"]).to(dtype)).transpose(0, 1)    # [1026, F]
     mag, p = x.chunk(2, dim=0)
     mag = torch.clip(torch.exp(mag), max=1e2)
     return mag * torch.cos(p), mag * torch.sin(p)
 
 
 @torch.no_grad()
-def vocos_decode(sd: Dict[str, np.ndarray], mel: torch.Tensor, n_fft: int = 1024, hop: int = 256) -> torch.Tensor:
+def vocos_decode(sd: Dict[str, np.ndarray], mel: torch.Tensor, n_fft: int = 1024, hop: int = 256, dtype=torch.float32) -> torch.Tensor:
     """vocos.Vocos.decode(mel[1,100,F]) -> wav [hop*(F-1)]  (called at pipeline:303).
-    ISTFT with padding="center" == torch.istft(S, n_fft, hop, n_fft, window, center=True)."""
-    sd = {k: _t(v).float() for k, v in sd.items()}
-    re, im = vocos_head_spec(sd, vocos_backbone(sd, _t(mel).float()))
+    ISTFT with padding="center" == torch.istft(S, n_fft, hop, n_fft, window, center=True).  `dtype=torch.float64`: weights and arithmetic in float64."""
+    sd = _cast(sd, dtype)
+    re, im = vocos_head_spec(sd, vocos_backbone(sd, _t(mel).to(dtype), dtype=dtype), dtype=dtype)
     S = torch.complex(re, im)[None]
     return torch.istft(S, n_fft, hop, n_fft, sd["head.istft.window"], center=True)[0]
 

@@ -14,6 +14,24 @@ def load_golden(name):
     return z, meta
 
 
+def per_frame_err(got, ref64, axis_len):
+    """Per-frame error of a vocoder output against its float64 reference, relative to the rms of the WHOLE reference.
+    A mel [axis_len = 100][F]: per frame f the rms over the channels of got - ref64.  A waveform [S]: the same per segment of axis_len (= hop = 256)
+    consecutive samples.  Dividing by the global rms (not the frame's own) keeps a silent frame from blowing the ratio up, and taking the maximum over
+    the result lets no frame's absolute error hide in an average.  A NaN anywhere in `got` gives a NaN entry (np.max then returns NaN)."""
+    got = np.asarray(got, dtype=np.float64)
+    ref = np.asarray(ref64, dtype=np.float64)
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    d = got - ref
+    if d.ndim == 2:
+        assert d.shape[0] == axis_len, (d.shape, axis_len)
+        e = np.sqrt(np.mean(np.square(d), axis=0))
+    else:
+        assert d.ndim == 1 and d.size and d.size % axis_len == 0, (d.shape, axis_len)
+        e = np.sqrt(np.mean(np.square(d.reshape(-1, axis_len)), axis=1))
+    return e / np.sqrt(np.mean(np.square(ref)))
+
+
 def gen_case_inputs(meta, cfg):
     """Regenerates weights / prompt / speaker of a generate() golden from its stored seeds."""
     sd = synth.gpt_state_dict(cfg, int(meta["weight_seed"]))
