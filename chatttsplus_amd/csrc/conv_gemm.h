@@ -99,7 +99,9 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmF32Args a) {
                 if (EPI == EP_GAMMA_RESID) v = __fadd_rn(__fmul_rn(v, a.gamma[n]), Rb[(size_t)m * a.ldr + n]);
                 if (EPI == EP_SCALE_T) { Cb[(size_t)n * M + m] = v * a.scale[n]; continue; }     // mel [n_mels][F_z]
                 if (EPI == EP_SCALE) v *= a.scale[n];
-                if (EPI == EP_LOGCLIP_DIV) v = logf(fmaxf(v, 1e-5f)) / a.scale[n];      // log(clip(mel, 1e-5)) / coef (dvae.py:196-198,264-266)
+                // log(clip(mel, 1e-5)) / coef (dvae.py:196-198,264-266).  torch.clip keeps a NaN; fmaxf(NaN, a) = a would turn a corrupt clip into the silence
+                // floor log(1e-5).  The select keeps NaN (the compare is false), clips -inf, and equals fmaxf for every other value.
+                if (EPI == EP_LOGCLIP_DIV) v = logf(v < 1e-5f ? 1e-5f : v) / a.scale[n];
                 Cb[(size_t)m * a.ldc + n] = v;
             }
         }
@@ -212,7 +214,7 @@ __global__ __launch_bounds__(256) void gemm_split_kernel(const GemmF32Args a) {
                 if (EPI == EP_GAMMA_RESID) v = __fadd_rn(__fmul_rn(v, a.gamma[n]), Rb[(size_t)m * a.ldr + n]);
                 if (EPI == EP_SCALE_T) { Cb[(size_t)n * M + m] = v * a.scale[n]; continue; }     // mel [n_mels][F_z]
                 if (EPI == EP_SCALE) v *= a.scale[n];
-                if (EPI == EP_LOGCLIP_DIV) v = logf(fmaxf(v, 1e-5f)) / a.scale[n];
+                if (EPI == EP_LOGCLIP_DIV) v = logf(v < 1e-5f ? 1e-5f : v) / a.scale[n];      // NaN stays NaN, as in gemm_f32_kernel
                 Cb[(size_t)m * a.ldc + n] = v;
             }
         }

@@ -95,6 +95,12 @@ __global__ void mel_out_kernel(const float* melcl, float* mel, int F, int n_mels
 // GFSQ.forward (dvae.py:94-126) -> GroupedResidualFSQ: group g = channels [g*per, (g+1)*per); project_in to 4 dims; two
 // residual FSQ layers, levels 5^4: code = rint(tanh(z) * 2.002) / 2, index = sum (2 code + 2) * 5^j, scale_r = 4^-r.
 // One wave per (frame, group).
+// Non-finite audio: a NaN or +-inf sample makes every mel frame whose window covers it NaN (the STFT row holds NaN or inf, the filterbank's zeros turn inf into NaN,
+// and the mel epilogue's clip keeps NaN as torch.clip does); the conv stack spreads it over its receptive field.  A (frame, group) whose projected z is not
+// finite gets id -1 in all R rows -- never a value in [0, 625) -- so that the caller can refuse the clip.  Finite clips are untouched.
+__device__ inline bool gfsq_nonfinite(const float (&z)[4]) {
+    return !(__builtin_isfinite(z[0]) && __builtin_isfinite(z[1]) && __builtin_isfinite(z[2]) && __builtin_isfinite(z[3]));
+}
 __global__ __launch_bounds__(64) void gfsq_kernel(const float* feat, const float* w, const float* b, int* ids, int T, int per, int ld, int R, int pre_bound) {
     const int t = blockIdx.x, g = blockIdx.y, lane = threadIdx.x;
     const float* x = feat + (size_t)t * ld + (size_t)g * per;
@@ -107,6 +113,10 @@ __global__ __launch_bounds__(64) void gfsq_kernel(const float* feat, const float
 #pragma unroll
     for (int j = 0; j < 4; ++j) z[j] = wave_sum(z[j]) + b[g * 4 + j];
     if (lane != 0) return;
+    if (gfsq_nonfinite(z)) {                                       // rintf(NaN) cast to int would be a plausible id
+        for (int r = 0; r < R; ++r) ids[(size_t)(g * R + r) * T + t] = -1;
+        return;
+    }
     const float half_l = 2.002f;                                   // (levels - 1) * (1 + 1e-3) / 2 in fp32
     float res[4];
 #pragma unroll
@@ -197,6 +207,10 @@ __global__ __launch_bounds__(64) void gfsq_batch_kernel(const EncUtt* U, const f
 #pragma unroll
     for (int j = 0; j < 4; ++j) z[j] = wave_sum(z[j]) + b[g * 4 + j];
     if (lane != 0) return;
+    if (gfsq_nonfinite(z)) {
+        for (int r = 0; r < R; ++r) u.ids[(size_t)(g * R + r) * T + t] = -1;
+        return;
+    }
     const float half_l = 2.002f;
     float res[4];
 #pragma unroll

@@ -96,7 +96,11 @@ class DVAEEncoder:
 
     @torch.inference_mode()
     def encode(self, wav: torch.Tensor, return_debug: bool = False):
-        """wav [n] fp32 @ 24 kHz -> codes int32 [G*R, T] on the device (+ (log-mel / coef [100, F], features [T, 1024]))."""
+        """wav [n] fp32 @ 24 kHz -> codes int32 [G*R, T] on the device (+ (log-mel / coef [100, F], features [T, 1024])).
+        Non-finite audio is not an error here (nothing is brought to the host): every mel frame whose 1024-sample window covers a NaN or infinite sample is NaN,
+        the other mel frames are untouched, and every code frame whose features are not finite has id -1 in all rows of the affected groups -- never an id in
+        [0, 625).  encode_batch does the same per clip and leaves the other clips of the batch bit-identical.  The pipeline's callers go through
+        pipeline.encode_clips, which refuses such a clip by index."""
         if not self._finalized:
             raise _lib.HipBackendError("DVAE encoder weights not loaded")
         wav = wav.to(self.device, dtype=torch.float32).contiguous().view(-1)

@@ -101,6 +101,18 @@ class ClonedVoice:
         return {"spk_smp": self.spk_smp, "txt_smp": self.txt_smp, "spk_emb": None}
 
 
+def encode_clips(enc, wavs, what: str = "clip") -> List[torch.Tensor]:
+    """The one door from the clip encoder to the host: DVAEEncoder.encode_batch(wavs) -> one code tensor int32 [num_vq, T_i] per clip, on the CPU.  The encoder marks a
+    code frame whose features are not finite (a NaN or infinite sample in the clip: a bad decode, an overflowed resampler) with id -1; such a clip would otherwise
+    be written into a prompt string as plausible codes (codec.encode_prompt casts to uint16).  It is refused here, by index."""
+    codes = [c.cpu() for c in enc.encode_batch(wavs)]
+    for i, c in enumerate(codes):
+        bad = int((c < 0).any(0).sum())
+        if bad:
+            raise _lib.HipBackendError(f"{what} {i}: {bad} of {c.shape[1]} code frames are not finite -- the waveform holds NaN or infinite samples")
+    return codes
+
+
 def utterance_voices(base, diffs) -> Optional[list]:
     """params_per_utterance entries (per_utterance_overrides) -> one (speaker tag, txt_smp, spk_smp) per utterance, None when no entry touches spk_smp / txt_smp.
     An utterance that sets its own spk_smp speaks without a speaker vector ([empty_spk]; setting both is refused by per_utterance_overrides); every other utterance
@@ -950,8 +962,8 @@ class ChatTTSPlusPipeline:
         if enc is None:
             raise _lib.HipBackendError("zero-shot speaker needs the dvae_encode checkpoint (DVAE_full.pt) configured with infer_type 'hip'")
         wav = torch.as_tensor(wav, dtype=torch.float32)
-        codes = enc.encode_batch([wav.view(-1)])[0]             # the entry clone_voices batches over, with B = 1
-        return codec.encode_prompt(codes.cpu())
+        codes = encode_clips(enc, [wav.view(-1)])[0]            # the entry clone_voices batches over, with B = 1
+        return codec.encode_prompt(codes)
 
     @staticmethod
     def _load_clip(path, wav=None, sample_rate=None) -> torch.Tensor:
@@ -988,8 +1000,8 @@ class ChatTTSPlusPipeline:
                 wavs.append(self._load_clip(None, c, r))
         if not wavs:
             return []
-        codes = enc.encode_batch(wavs)
-        return [ClonedVoice(spk_smp=codec.encode_prompt(c.cpu()), txt_smp=t or "", _codes=c.cpu().to(torch.int64)) for c, t in zip(codes, texts)]
+        codes = encode_clips(enc, wavs)
+        return [ClonedVoice(spk_smp=codec.encode_prompt(c), txt_smp=t or "", _codes=c.to(torch.int64)) for c, t in zip(codes, texts)]
 
     def sample_random_speaker(self) -> str:
         return self._encode_spk_emb(self._sample_random_speaker())
@@ -1048,7 +1060,7 @@ class ChatTTSPlusPipeline:
             if enc is None:
                 raise _lib.HipBackendError("score(wavs=...) needs the dvae_encode checkpoint (DVAE_full.pt) configured with infer_type 'hip'")
             clips = [torch.as_tensor(w, dtype=torch.float32).view(-1) for w in (wavs if isinstance(wavs, list) else [wavs])]
-            codes = [c.t().cpu() for c in enc.encode_batch(clips)] if clips else []      # one encoder call; [4, n] (sample_audio_speaker) -> [n, 4]
+            codes = [c.t() for c in encode_clips(enc, clips, "score: waveform")] if clips else []      # one encoder call; [4, n] (sample_audio_speaker) -> [n, 4]
         elif not isinstance(codes, list):
             codes = [codes]
         if len(codes) != len(texts):

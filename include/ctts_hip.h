@@ -719,7 +719,10 @@ int ctts_enc_set_weight(ctts_enc* h, const char* name, const float* host_data, s
 int ctts_enc_finalize(ctts_enc* h);
 /* wav: n_samples fp32 on the device (mono, 24 kHz).  ids: int32 [G*R][T] on the device, T = ((1 + n_samples/hop) - 2)/2 + 1,
  * row g*R + r like GFSQ.forward's `ind` (dvae.py:108-113,126).  Optional test hooks (device, may be null):
- * mel_out [n_mels][F] = log-mel / coef, feat_out [T][enc_odim] = encoder output. */
+ * mel_out [n_mels][F] = log-mel / coef, feat_out [T][enc_odim] = encoder output.
+ * Non-finite audio (this call and the batched one): a NaN or +-inf sample is not an error.  Every mel frame whose 1024-sample window covers it is
+ * NaN (the clip at 1e-5 keeps NaN, as torch.clip does), the other mel frames are untouched, and every (code frame, group) whose projected
+ * features are not finite gets id -1 in all R rows -- never an id in [0, 625): the caller decides (the pipeline refuses the clip). */
 int ctts_dvae_encode(ctts_enc* h, const float* wav, int n_samples, int32_t* ids, float* mel_out, float* feat_out, void* stream);
 /* The same for B clips in one launch sequence (grid.z / grid.y = utterance, per-utterance frame and code counts from device tables uploaded
  * once per call): per batch it replaces B calls of sample_audio_speaker (pipelines/chattts_plus_pipeline.py:279-284) = B runs of

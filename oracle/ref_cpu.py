@@ -478,14 +478,36 @@ def mel_filterbank(n_freqs: int = 513, n_mels: int = 100, sample_rate: int = 240
     return torch.clamp(torch.min(down, up), min=0.0)
 
 
+def dft_basis(n_fft: int, window: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """Windowed forward real-DFT basis [2 * (n_fft // 2 + 1), n_fft]: rows k < NB are w[n] cos(2 pi k n / N), rows NB + k are -w[n] sin(2 pi k n / N).
+    Angles in float64 from the exactly reduced (k n) % N, then cast to `dtype` -- the formulation of the HIP encoder (csrc/encoder.hip)."""
+    k = torch.arange(n_fft // 2 + 1, dtype=torch.int64)
+    n = torch.arange(n_fft, dtype=torch.int64)
+    ang = 2.0 * math.pi * ((k[:, None] * n[None, :]) % n_fft).double() / n_fft
+    w = window.double()
+    return torch.cat([w * torch.cos(ang), -w * torch.sin(ang)], 0).to(dtype)
+
+
 @torch.no_grad()
-def mel_features(wav: torch.Tensor, n_fft: int = 1024, hop: int = 256, n_mels: int = 100, sample_rate: int = 24000) -> torch.Tensor:
-    """MelSpectrogramFeatures.forward (dvae.py:171-199): log(clip(mel_spec(audio), 1e-5)); wav [n] -> [n_mels, 1 + n // hop]."""
-    wav = _t(wav).float()
-    window = torch.hann_window(n_fft, periodic=True)
-    spec = torch.stft(wav, n_fft, hop_length=hop, win_length=n_fft, window=window, center=True, pad_mode="reflect",
-                      normalized=False, onesided=True, return_complex=True).abs()                        # power = 1
-    mel = torch.matmul(spec.transpose(-1, -2), mel_filterbank(n_fft // 2 + 1, n_mels, sample_rate)).transpose(-1, -2)
+def mel_features(wav: torch.Tensor, n_fft: int = 1024, hop: int = 256, n_mels: int = 100, sample_rate: int = 24000, dtype=torch.float32,
+                 form: str = "fft") -> torch.Tensor:
+    """MelSpectrogramFeatures.forward (dvae.py:171-199): log(clip(mel_spec(audio), 1e-5)); wav [n] -> [n_mels, 1 + n // hop].
+    `dtype=torch.float64`: the float32 window and filterbank VALUES (they are the extractor's constants) and all arithmetic in float64.
+    `form`: "fft" is torch.stft; "dft" restates it as reflect-pad -> unfold(n_fft, hop) -> matmul with dft_basis -> sqrt(re^2 + im^2), the formulation of
+    the HIP encoder: the same numbers in float64 (<= 1e-9), another rounding pattern in float32 (a 1024-term dot product instead of an FFT)."""
+    wav = _t(wav).to(dtype)
+    window = torch.hann_window(n_fft, periodic=True).to(dtype)
+    if form == "fft":
+        spec = torch.stft(wav, n_fft, hop_length=hop, win_length=n_fft, window=window, center=True, pad_mode="reflect",
+                          normalized=False, onesided=True, return_complex=True).abs()                    # power = 1
+    elif form == "dft":
+        nb = n_fft // 2 + 1
+        xp = F.pad(wav[None, None], (n_fft // 2, n_fft // 2), mode="reflect")[0, 0]
+        ri = torch.matmul(xp.unfold(0, n_fft, hop), dft_basis(n_fft, torch.hann_window(n_fft, periodic=True), dtype).t())   # [F, 2 NB]
+        spec = torch.sqrt(ri[:, :nb] ** 2 + ri[:, nb:] ** 2).t()
+    else:
+        raise ValueError(f"mel_features: form {form!r}")
+    mel = torch.matmul(spec.transpose(-1, -2), mel_filterbank(n_fft // 2 + 1, n_mels, sample_rate).to(dtype)).transpose(-1, -2)
     return torch.log(torch.clip(mel, min=1e-5))
 
 
@@ -497,7 +519,7 @@ def fsq_bound(z: torch.Tensor, levels: torch.Tensor, eps: float = 1e-3) -> torch
     return (z + shift).tanh() * half_l - offset
 
 
-def gfsq_indices(x: torch.Tensor, sd, levels=(5, 5, 5, 5), G: int = 2, R: int = 2, pre_bound: bool = True) -> torch.Tensor:
+def gfsq_indices(x: torch.Tensor, sd, levels=(5, 5, 5, 5), G: int = 2, R: int = 2, pre_bound: bool = True, dtype=torch.float32) -> torch.Tensor:
     """GFSQ.forward (dvae.py:94-126) on x [T, G*dim_g] -> indices [G*R, T] (ind.permute(1,2,0,3).view(...).transpose).
     Per group: ResidualFSQ = project_in (Linear dim_g -> len(levels)), then R FSQ layers on residual / scale_r with
     scale_r = (levels - 1) ** -r; FSQ: codes = round(bound(z)) / (levels // 2); index = sum((codes * hw + hw) * basis),
@@ -505,31 +527,37 @@ def gfsq_indices(x: torch.Tensor, sd, levels=(5, 5, 5, 5), G: int = 2, R: int = 
     loop (`residual = first(self.layers).bound(x)`); later releases replaced that by an optional soft clamp and start from
     `residual = x`.  1.17.8 cannot be inspected offline: True is our best knowledge of that release, both variants are
     implemented (oracle and HIP) and frozen in tests/golden/dvae_encode_real.npz (`ids_pre_bound` / `ids`)."""
-    return gfsq_quantize(x, sd, levels, G, R, pre_bound)[0]
+    return gfsq_quantize(x, sd, levels, G, R, pre_bound, dtype=dtype)[0]
 
 
-def gfsq_quantize(x: torch.Tensor, sd, levels=(5, 5, 5, 5), G: int = 2, R: int = 2, pre_bound: bool = True):
+def gfsq_quantize(x: torch.Tensor, sd, levels=(5, 5, 5, 5), G: int = 2, R: int = 2, pre_bound: bool = True, dtype=torch.float32, return_pre: bool = False):
     """gfsq_indices plus the quantised latent the indices stand for: (indices [G*R, T], latent [G, T, len(levels)]) with
     latent_g = sum_r codes_r * scale_r in the projected (FSQ) space -- what ResidualFSQ returns before project_out and what
-    get_output_from_indices rebuilds from the indices alone (GFSQ._embed, dvae.py:85-96)."""
-    lv = torch.tensor(levels, dtype=torch.float32)
-    hw = torch.tensor([l // 2 for l in levels], dtype=torch.float32)
-    basis = torch.cumprod(torch.tensor([1] + list(levels[:-1]), dtype=torch.float32), 0)
+    get_output_from_indices rebuilds from the indices alone (GFSQ._embed, dvae.py:85-96).  `dtype`: weights, x and arithmetic in that type.
+    `return_pre`: a third result, the values each digit is rounded from, bound(residual / scale_r) = tanh(residual / scale_r) * 2.002 as [G, R, T, len(levels)]."""
+    lv = torch.tensor(levels, dtype=dtype)
+    hw = torch.tensor([l // 2 for l in levels], dtype=dtype)
+    basis = torch.cumprod(torch.tensor([1] + list(levels[:-1]), dtype=dtype), 0)
+    x = _t(x).to(dtype)
     per = x.shape[-1] // G
-    out, lat = [], []
+    out, lat, pre = [], [], []
     for g in range(G):
-        w, b = _t(sd[f"vq_layer.quantizer.rvqs.{g}.project_in.weight"]).float(), _t(sd[f"vq_layer.quantizer.rvqs.{g}.project_in.bias"]).float()
+        w, b = _t(sd[f"vq_layer.quantizer.rvqs.{g}.project_in.weight"]).to(dtype), _t(sd[f"vq_layer.quantizer.rvqs.{g}.project_in.bias"]).to(dtype)
         z = F.linear(x[..., g * per:(g + 1) * per], w, b)
         residual = fsq_bound(z, lv) if pre_bound else z
         acc = torch.zeros_like(z)
         for r in range(R):
             scale = (lv - 1) ** (-r)
-            codes = torch.round(fsq_bound(residual / scale, lv)) / hw
+            p = fsq_bound(residual / scale, lv)
+            pre.append(p)
+            codes = torch.round(p) / hw
             idx = ((codes * hw + hw) * basis).sum(-1).to(torch.int32)
             residual = residual - codes * scale
             acc = acc + codes * scale
             out.append(idx)
         lat.append(acc)
+    if return_pre:
+        return torch.stack(out, 0), torch.stack(lat, 0), torch.stack(pre, 0).view(G, R, *pre[0].shape)
     return torch.stack(out, 0), torch.stack(lat, 0)                              # [G*R, T] (row = g * R + r), [G, T, D]
 
 
@@ -566,25 +594,26 @@ def dvae_decode_codes(sd: Dict[str, np.ndarray], ids: torch.Tensor, levels=(5, 5
 
 
 @torch.no_grad()
-def dvae_encoder_features(sd: Dict[str, np.ndarray], mel: torch.Tensor) -> torch.Tensor:
-    """mel [100, F] -> encoder output [1024, F // 2]: div by coef, downsample_conv, DVAEDecoder-as-encoder (dvae.py:263-268)."""
-    sd = {k: _t(v).float() for k, v in sd.items()}
-    x = (_t(mel).float() / sd["coef"].view(-1, 1))[None]
+def dvae_encoder_features(sd: Dict[str, np.ndarray], mel: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """mel [100, F] -> encoder output [1024, F // 2]: div by coef, downsample_conv, DVAEDecoder-as-encoder (dvae.py:263-268).
+    `dtype=torch.float64`: weights and arithmetic in float64."""
+    sd = _cast(sd, dtype)
+    x = (_t(mel).to(dtype) / sd["coef"].view(-1, 1))[None]
     x = F.gelu(F.conv1d(x, sd["downsample_conv.0.weight"], sd["downsample_conv.0.bias"], stride=1, padding=1))
     x = F.gelu(F.conv1d(x, sd["downsample_conv.2.weight"], sd["downsample_conv.2.bias"], stride=2, padding=1))
     y = F.gelu(F.conv1d(x, sd["encoder.conv_in.0.weight"], sd["encoder.conv_in.0.bias"], padding=1))
     y = F.conv1d(y, sd["encoder.conv_in.2.weight"], sd["encoder.conv_in.2.bias"], padding=1)
     n_layer = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("encoder.decoder_block."))
     for i in range(n_layer):
-        y = _convnext(sd, f"encoder.decoder_block.{i}.", y, dilation=2)
+        y = _convnext(sd, f"encoder.decoder_block.{i}.", y, dilation=2, dtype=dtype)
     return F.conv1d(y, sd["encoder.conv_out.weight"])[0]
 
 
 @torch.no_grad()
-def dvae_encode(sd: Dict[str, np.ndarray], wav: torch.Tensor, pre_bound: bool = True) -> torch.Tensor:
+def dvae_encode(sd: Dict[str, np.ndarray], wav: torch.Tensor, pre_bound: bool = True, dtype=torch.float32) -> torch.Tensor:
     """DVAE.forward(mode="encode") (dvae.py:263-270): wav [n] @ 24 kHz -> audio-prompt codes [4, T] (values < 625)."""
-    feat = dvae_encoder_features(sd, mel_features(wav))
-    return gfsq_indices(feat.transpose(0, 1), {k: _t(v).float() for k, v in sd.items()}, pre_bound=pre_bound)
+    feat = dvae_encoder_features(sd, mel_features(wav, dtype=dtype), dtype=dtype)
+    return gfsq_indices(feat.transpose(0, 1), sd, pre_bound=pre_bound, dtype=dtype)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -110,3 +110,63 @@ def test_code_prompt_builds_every_row_with_its_own_voice(tmp_path):
         ids1, att1, tm1 = pipe._code_prompt([t], old, G())          # the voice given the old way, batch 1
         pad = ids.shape[1] - ids1.shape[1]
         assert torch.equal(ids[i, pad:], ids1[0]) and torch.equal(att[i, pad:], att1[0]) and torch.equal(tm[i, pad:], tm1[0]) and not bool(att[i, :pad].any()), i
+
+
+class _FakeEncoder:
+    """Stands in for DVAEEncoder.encode_batch: clip i -> codes [4, 3 + i]; the clips listed in `bad` carry the encoder's mark of non-finite features, id -1."""
+
+    def __init__(self, bad=()):
+        self.bad, self.calls = set(bad), 0
+
+    def encode_batch(self, wavs):
+        self.calls += 1
+        out = []
+        for i, _ in enumerate(wavs):
+            c = torch.randint(0, 625, (4, 3 + i), generator=torch.Generator().manual_seed(i), dtype=torch.int32)
+            if i in self.bad:
+                c[:, 1] = -1
+            out.append(c)
+        return out
+
+
+def test_encode_clips_refuses_a_clip_with_negative_codes():
+    from chatttsplus_amd.pipeline import encode_clips
+    wavs = [torch.zeros(600)] * 3
+    clean = encode_clips(_FakeEncoder(), wavs)
+    assert [tuple(c.shape) for c in clean] == [(4, 3), (4, 4), (4, 5)] and all(c.dtype == torch.int32 and c.device.type == "cpu" for c in clean)
+    assert all(torch.equal(a, b) for a, b in zip(clean, _FakeEncoder().encode_batch(wavs)))
+    with pytest.raises(_lib.HipBackendError, match=r"clip 1: 1 of 4 code frames"):
+        encode_clips(_FakeEncoder(bad=[1]), wavs)
+    with pytest.raises(_lib.HipBackendError, match=r"clip 0"):                    # the first bad clip is the one named
+        encode_clips(_FakeEncoder(bad=[0, 2]), wavs)
+    one = torch.full((4, 3), 7, dtype=torch.int32)
+    one[2, 0] = -1                                                               # a single negative id (one group of one frame) is enough
+
+    class One:
+        def encode_batch(self, wavs):
+            return [one]
+    with pytest.raises(_lib.HipBackendError, match=r"clip 0: 1 of 3"):
+        encode_clips(One(), wavs[:1])
+
+
+def test_every_caller_of_the_clip_encoder_goes_through_the_check():
+    """sample_audio_speaker, clone_voices and score(wavs=) refuse a clip whose codes are negative instead of writing it into a prompt string (astype("<u2") would
+    turn -1 into 65535) or scoring it."""
+    from chatttsplus_amd.pipeline import ChatTTSPlusPipeline
+    pipe = object.__new__(ChatTTSPlusPipeline)
+    pipe.device = torch.device("cpu")
+    good, bad = _FakeEncoder(), _FakeEncoder(bad=[1])
+    pipe.models_dict = {"dvae_encode": good}
+    s = pipe.sample_audio_speaker(torch.zeros(600))
+    assert torch.equal(codec.decode_prompt(s), good.encode_batch([None])[0].to(torch.int64))
+    voices = pipe.clone_voices([torch.zeros(600), torch.zeros(700)], ["a", "b"])
+    assert [v.codes.shape[1] for v in voices] == [3, 4] and voices[0].spk_smp == s and voices[1].txt_smp == "b"
+    assert torch.equal(codec.decode_prompt(voices[1].spk_smp), voices[1].codes)
+    pipe.models_dict = {"dvae_encode": bad}
+    with pytest.raises(_lib.HipBackendError, match="clip 1"):
+        pipe.clone_voices([torch.zeros(600), torch.zeros(700)], ["a", "b"])
+    with pytest.raises(_lib.HipBackendError, match="score: waveform 1"):
+        pipe.score(["a", "b"], wavs=[torch.zeros(600), torch.zeros(700)])
+    pipe.models_dict = {"dvae_encode": _FakeEncoder(bad=[0])}
+    with pytest.raises(_lib.HipBackendError, match="clip 0"):
+        pipe.sample_audio_speaker(torch.zeros(600))
