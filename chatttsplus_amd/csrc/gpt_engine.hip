@@ -261,13 +261,11 @@ struct ctts_gpt {
     int graph_steps_persist = 16;                // ... and per graph of the persistent paths (2 nodes per step: 32 nodes): the replay gap is 8.1 us whatever the graph
                                                  // holds (profiles/r05_trace_gaps_b1.json), 2.0 us per step at 4 steps, 0.5 us at 16
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // ctts_gpt_score: the gathered scored rows [SCORE_ROWS][H], their head logits [SCORE_ROWS][4 * V] and output entries [SCORE_ROWS] --
-    // allocated by the first score call (engines that never score keep their footprint)
-    float *score_x = nullptr, *score_logits = nullptr; int* score_oidx = nullptr;
-    size_t score_bytes = 0;
-    // ctts_gpt_score_text: gathered rows [chunk][H], text-head logits [chunk][vocab_text_head], output entries [chunk], chunk = min(max_batch, SCORE_ROWS) rows
-    // ("score_text_chunk") -- allocated by the first ctts_gpt_score_text call (at most 128 x 21178 fp32 = 10.8 MB; every other engine keeps its footprint)
-    float *score_text_x = nullptr, *score_text_logits = nullptr; int* score_text_oidx = nullptr;
+    // scoring scratch (score_rows), one per head, each allocated by its head's first call (engines that never score, or never score text, keep their footprint):
+    // the gathered scored rows [chunk][H], their head logits [chunk][logits width] and output entries [chunk]
+    struct ScoreScratch { float *x = nullptr, *logits = nullptr; int* oidx = nullptr; };
+    ScoreScratch score_code;                     // ctts_gpt_score: chunk = SCORE_ROWS, 4 * V wide
+    ScoreScratch score_text;                     // ctts_gpt_score_text: chunk = min(max_batch, SCORE_ROWS) ("score_text_chunk"), vocab_text_head wide (at most 128 x 21178 fp32 = 10.8 MB)
     int score_text_chunk = 0;
     // shared prompt passes (ctts_gpt_share_prompts; kv_share.hip)
     std::vector<int> share_tab;                  //   host image of share_dev for the call that consumed the request (kernels.h SH_*)
@@ -839,16 +837,17 @@ static int check_rows(const ctts_gpt* h, const char* who, int n, const int32_t* 
     }
     return 0;
 }
+// a NextCall list holds one entry per row: the last value named for it
+template <typename V> static void name_row(std::vector<std::pair<int, V>>& list, int row, const V& v) {
+    for (auto& e : list) if (e.first == row) { e.second = v; return; }
+    list.emplace_back(row, v);
+}
 extern "C" int ctts_gpt_admit_sampling(ctts_gpt* h, int n, const int32_t* rows, const ctts_row_sampling* p, void* stream) {
     (void)stream;        // host-side request: the next ctts_gpt_admit uploads the entries
     if (!h || h->B == 0 || !rows || !p || n < 0) { ctts_set_error("admit_sampling: call begin first / null argument"); return 1; }
     if (h->text_mode) { ctts_set_error("admit_sampling: per-utterance sampling parameters are code mode only (the refine-text pass keeps the call's values)"); return 1; }
     if (check_rows(h, "admit_sampling", n, rows, false, [&](int i) { return check_knobs(p[i], h->sc.max_new, "admit_sampling", i); })) return 1;
-    for (int i = 0; i < n; ++i) {
-        bool found = false;
-        for (auto& e : h->next.knobs) if (e.first == rows[i]) { e.second = knobs_of_abi(p[i]); found = true; }
-        if (!found) h->next.knobs.emplace_back(rows[i], knobs_of_abi(p[i]));
-    }
+    for (int i = 0; i < n; ++i) name_row(h->next.knobs, rows[i], knobs_of_abi(p[i]));
     return 0;
 }
 
@@ -1790,46 +1789,57 @@ extern "C" int ctts_gpt_prefill(ctts_gpt* h, const float* emb, void* stream) {
     return 0;
 }
 
-// Teacher-forced scoring (include/ctts_hip.h ctts_gpt_score): the prompt pass of ctts_gpt_prefill over [B][T], then per pass the scored rows (the last
-// n_b of sequence b) are gathered SCORE_ROWS at a time, the final RMSNorm + code heads run on them (the decode heads' launch, PRO_NORM / EPI_LOGITS, here on
-// up to SCORE_ROWS rows: every row index it forms is size_t, bounded by R, and it reads no decode state -- st, dyn, rows null) and score.hip reduces the logits.
-extern "C" int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* mask, const float* emb, const int32_t* targets, const int32_t* n_targets, int max_targets,
-                              float* logprob, int32_t* argmax, void* stream) {
-    if (!h || !h->finalized || !h->kv || !h->rope) { ctts_set_error("score: handle not ready (finalize / bind_kv / set_rope)"); return 1; }
-    if (!mask || !emb || !targets || !n_targets || !logprob || !argmax) { ctts_set_error("score: null argument"); return 1; }
-    if (B < 1 || B > h->cfg.max_batch) { ctts_set_error("score: B=%d outside 1..max_batch=%d", B, h->cfg.max_batch); return 1; }
-    if (T < 1 || T > h->cfg.max_seq) { ctts_set_error("score: T=%d outside 1..max_seq=%d", T, h->cfg.max_seq); return 1; }
-    if (max_targets < 1) { ctts_set_error("score: max_targets=%d < 1", max_targets); return 1; }
+// Teacher-forced scoring (include/ctts_hip.h ctts_gpt_score, ctts_gpt_score_text): one path, two heads.  The prompt pass of ctts_gpt_prefill over [B][T], then per
+// pass the scored rows (the last n_b of sequence b) are gathered `chunk` at a time, the final RMSNorm + the head run on them (the decode heads' launch, PRO_NORM /
+// EPI_LOGITS: every row index it forms is size_t, bounded by R, and it reads no decode state -- st, dyn, rows null) and score.hip reduces the logits.
+struct ScoreHead {
+    const char* name;                            // "score" / "score_text": the prefix of every message; "ctts_gpt_" + name is the profiler range
+    const void* W;                               // head weights
+    int NV, V;                                   // logits width; the vocabulary a target indexes (one codebook of the four / the whole text row)
+    int cols;                                    // results per target: logprob / argmax are [B][max_targets][cols]
+    int chunk;                                   // rows per heads launch: bounds the scratch
+    ctts_gpt::ScoreScratch* scratch;
+    int (*reduce)(const float* logits, const int* oidx, const int* targets, float* logprob, int* argmax, int m, int V, int n_valid, hipStream_t s);
+};
+static bool score_ready(const ctts_gpt* h, const char* name) {
+    if (h && h->finalized && h->kv && h->rope) return true;
+    ctts_set_error("%s: handle not ready (finalize / bind_kv / set_rope)", name);
+    return false;
+}
+static int score_rows(ctts_gpt* h, const ScoreHead& hd, int B, int T, const int32_t* mask, const float* emb, const int32_t* targets, const int32_t* n_targets, int max_targets,
+                      float* logprob, int32_t* argmax, hipStream_t s) {
+    if (!mask || !emb || !targets || !n_targets || !logprob || !argmax) { ctts_set_error("%s: null argument", hd.name); return 1; }
+    if (B < 1 || B > h->cfg.max_batch) { ctts_set_error("%s: B=%d outside 1..max_batch=%d", hd.name, B, h->cfg.max_batch); return 1; }
+    if (T < 1 || T > h->cfg.max_seq) { ctts_set_error("%s: T=%d outside 1..max_seq=%d", hd.name, T, h->cfg.max_seq); return 1; }
+    if (max_targets < 1) { ctts_set_error("%s: max_targets=%d < 1", hd.name, max_targets); return 1; }
     for (int b = 0; b < B; ++b) {
         const int nb = n_targets[b];
         if (nb < 1 || nb > T || nb > max_targets) {
-            ctts_set_error("score: n_targets[%d]=%d outside 1..min(T=%d, max_targets=%d)", b, nb, T, max_targets);
+            ctts_set_error("%s: n_targets[%d]=%d outside 1..min(T=%d, max_targets=%d)", hd.name, b, nb, T, max_targets);
             return 1;
         }
     }
     if (h->batch_inv && h->cfg.dtype == CTTS_DTYPE_F32 && !(h->split_ok && h->wsplit)) {
-        ctts_set_error("score: batch_invariant needs the head / tail weight images, and a weight of this checkpoint is beyond the fp16 range (x 64)");
+        ctts_set_error("%s: batch_invariant needs the head / tail weight images, and a weight of this checkpoint is beyond the fp16 range (x 64)", hd.name);
         return 1;
     }
-    CTTS_RANGE("ctts_gpt_score");
-    hipStream_t s = (hipStream_t)stream;
+    CTTS_RANGE((std::string("ctts_gpt_") + hd.name).c_str());
     end_generate_state(h);            // the KV lanes and the prompt workspaces are overwritten
     h->text_mode = 0;
-    if (seat_row_adapters(h, B, "score", s)) return 1;
-    const int NV = h->NVQ * h->V;
-    if (h->score_oidx == nullptr) {
-        if (!h->score_x && dev_alloc(h, (void**)&h->score_x, (size_t)SCORE_ROWS * h->H * 4)) return 1;
-        if (!h->score_logits && dev_alloc(h, (void**)&h->score_logits, (size_t)SCORE_ROWS * NV * 4)) return 1;
-        if (dev_alloc(h, (void**)&h->score_oidx, (size_t)SCORE_ROWS * 4)) return 1;
-        h->score_bytes = (size_t)SCORE_ROWS * (h->H + NV + 1) * 4;
+    if (seat_row_adapters(h, B, hd.name, s)) return 1;
+    ctts_gpt::ScoreScratch& sc = *hd.scratch;
+    if (sc.oidx == nullptr) {
+        if (!sc.x && dev_alloc(h, (void**)&sc.x, (size_t)hd.chunk * h->H * 4)) return 1;
+        if (!sc.logits && dev_alloc(h, (void**)&sc.logits, (size_t)hd.chunk * hd.NV * 4)) return 1;
+        if (dev_alloc(h, (void**)&sc.oidx, (size_t)hd.chunk * 4)) return 1;
     }
     // entries j >= n_b: logprob 0, argmax -1
-    CTTS_HIP_CHECK(hipMemsetAsync(logprob, 0, (size_t)B * max_targets * CTTS_NUM_VQ * 4, s));
-    CTTS_HIP_CHECK(hipMemsetAsync(argmax, 0xFF, (size_t)B * max_targets * CTTS_NUM_VQ * 4, s));
+    CTTS_HIP_CHECK(hipMemsetAsync(logprob, 0, (size_t)B * max_targets * hd.cols * 4, s));
+    CTTS_HIP_CHECK(hipMemsetAsync(argmax, 0xFF, (size_t)B * max_targets * hd.cols * 4, s));
     if (launch_fill_meta(h->meta_pre, h->meta_dec0, h->st, mask, B, T, h->rope, h->rope_pre, nullptr, B, s)) return 1;
     const long R = (long)B * T;
     h->pp_rows = R; h->pp_T = T;
-    // batch_invariant: the heads on 16-row chunks whatever the block holds (as run_heads pins nbg = 1); the chunk of SCORE_ROWS rows only bounds the scratch
+    // batch_invariant: the heads on 16-row chunks whatever the block holds (as run_heads pins nbg = 1); the chunk only bounds the scratch
     const int nbg = h->batch_inv ? 1 : 2;
     ScoreRows sr = {};
     sr.B = B; sr.max_targets = max_targets;
@@ -1844,17 +1854,35 @@ extern "C" int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* mask, co
             sr.j0[b] = cnt ? (int)(lo - s0) : 0;
             sr.cum[b + 1] = sr.cum[b] + cnt;
         }
-        for (int g0 = 0; g0 < sr.cum[B]; g0 += SCORE_ROWS) {
-            const int m = sr.cum[B] - g0 < SCORE_ROWS ? sr.cum[B] - g0 : SCORE_ROWS;
-            if (launch_score_gather(h->x_pre, h->score_x, h->score_oidx, g0, m, sr, s)) return 1;
+        for (int g0 = 0; g0 < sr.cum[B]; g0 += hd.chunk) {
+            const int m = sr.cum[B] - g0 < hd.chunk ? sr.cum[B] - g0 : hd.chunk;
+            if (launch_score_gather(h->x_pre, sc.x, sc.oidx, g0, m, sr, s)) return 1;
             GemmArgs a = {};
-            a.R = m; a.eps = 1e-6f; a.W = h->whead; a.n_row_tiles = (NV + 15) / 16; a.K = h->H; a.x = h->score_x; a.lnw = h->lnf;
-            a.logits = h->score_logits; a.n_valid = NV;
+            a.R = m; a.eps = 1e-6f; a.W = hd.W; a.n_row_tiles = (hd.NV + 15) / 16; a.K = h->H; a.x = sc.x; a.lnw = h->lnf;
+            a.logits = sc.logits; a.n_valid = hd.NV;
             if (launch_gemm(h->cfg.dtype, nbg, PRO_NORM, EPI_LOGITS, a, (m + 16 * nbg - 1) / (16 * nbg), s)) return 1;
-            if (launch_score_reduce(h->score_logits, h->score_oidx, targets, logprob, argmax, m, h->V, NV, s)) return 1;
+            if (hd.reduce(sc.logits, sc.oidx, targets, logprob, argmax, m, hd.V, hd.NV, s)) return 1;
         }
         return 0;
     });
+}
+// the code heads: SCORE_ROWS rows per launch, four codebooks of V in one 4 * V wide row
+extern "C" int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* mask, const float* emb, const int32_t* targets, const int32_t* n_targets, int max_targets,
+                              float* logprob, int32_t* argmax, void* stream) {
+    if (!score_ready(h, "score")) return 1;
+    const ScoreHead hd = {"score", h->whead, h->NVQ * h->V, h->V, CTTS_NUM_VQ, SCORE_ROWS, &h->score_code, launch_score_reduce};
+    return score_rows(h, hd, B, T, mask, emb, targets, n_targets, max_targets, logprob, argmax, (hipStream_t)stream);
+}
+// the refine-text head: the text-head launch of a decode step (run_heads' text shape) on at most max_batch rows at a time, score.hip's one-row-per-workgroup reduce
+static int reduce_text(const float* logits, const int* oidx, const int* targets, float* logprob, int* argmax, int m, int V, int, hipStream_t s) {
+    return launch_score_text_reduce(logits, oidx, targets, logprob, argmax, m, V, s);
+}
+extern "C" int ctts_gpt_score_text(ctts_gpt* h, int B, int T, const int32_t* mask, const float* emb, const int32_t* targets, const int32_t* n_targets, int max_targets,
+                                   float* logprob, int32_t* argmax, void* stream) {
+    if (!score_ready(h, "score_text")) return 1;
+    if (!h->whead_text || !h->emb_text) { ctts_set_error("score_text: the engine has no text head (head_text.* and emb_text.weight are needed)"); return 1; }
+    const ScoreHead hd = {"score_text", h->whead_text, h->vocab_text_head, h->vocab_text_head, 1, h->score_text_chunk, &h->score_text, reduce_text};
+    return score_rows(h, hd, B, T, mask, emb, targets, n_targets, max_targets, logprob, argmax, (hipStream_t)stream);
 }
 
 static int run_decode_step(ctts_gpt* h, DecodePath path, hipStream_t s);
@@ -1885,72 +1913,6 @@ extern "C" int ctts_gpt_set_text_logprob_out(ctts_gpt* h, float* lp_raw, float* 
     return 0;
 }
 
-// Teacher-forced scoring under the refine-text head (include/ctts_hip.h ctts_gpt_score_text): ctts_gpt_score's prompt pass and gather, then the text-head launch of a
-// decode step (run_heads' text shape: PRO_NORM / EPI_LOGITS over whead_text, 16-row chunks under batch_invariant) on at most max_batch gathered rows at a time into a
-// logits scratch of its own, and score.hip's one-row-per-workgroup reduce.  The scratch is allocated on the first call: an engine that never scores text allocates
-// what it always did.
-extern "C" int ctts_gpt_score_text(ctts_gpt* h, int B, int T, const int32_t* mask, const float* emb, const int32_t* targets, const int32_t* n_targets, int max_targets,
-                                   float* logprob, int32_t* argmax, void* stream) {
-    if (!h || !h->finalized || !h->kv || !h->rope) { ctts_set_error("score_text: handle not ready (finalize / bind_kv / set_rope)"); return 1; }
-    if (!h->whead_text || !h->emb_text) { ctts_set_error("score_text: the engine has no text head (head_text.* and emb_text.weight are needed)"); return 1; }
-    if (!mask || !emb || !targets || !n_targets || !logprob || !argmax) { ctts_set_error("score_text: null argument"); return 1; }
-    if (B < 1 || B > h->cfg.max_batch) { ctts_set_error("score_text: B=%d outside 1..max_batch=%d", B, h->cfg.max_batch); return 1; }
-    if (T < 1 || T > h->cfg.max_seq) { ctts_set_error("score_text: T=%d outside 1..max_seq=%d", T, h->cfg.max_seq); return 1; }
-    if (max_targets < 1) { ctts_set_error("score_text: max_targets=%d < 1", max_targets); return 1; }
-    for (int b = 0; b < B; ++b) {
-        const int nb = n_targets[b];
-        if (nb < 1 || nb > T || nb > max_targets) {
-            ctts_set_error("score_text: n_targets[%d]=%d outside 1..min(T=%d, max_targets=%d)", b, nb, T, max_targets);
-            return 1;
-        }
-    }
-    if (h->batch_inv && h->cfg.dtype == CTTS_DTYPE_F32 && !(h->split_ok && h->wsplit)) {
-        ctts_set_error("score_text: batch_invariant needs the head / tail weight images, and a weight of this checkpoint is beyond the fp16 range (x 64)");
-        return 1;
-    }
-    CTTS_RANGE("ctts_gpt_score_text");
-    hipStream_t s = (hipStream_t)stream;
-    end_generate_state(h);            // the KV lanes and the prompt workspaces are overwritten
-    h->text_mode = 0;
-    if (seat_row_adapters(h, B, "score_text", s)) return 1;
-    const int NV = h->vocab_text_head, CH = h->score_text_chunk;
-    if (h->score_text_oidx == nullptr) {
-        if (!h->score_text_x && dev_alloc(h, (void**)&h->score_text_x, (size_t)CH * h->H * 4)) return 1;
-        if (!h->score_text_logits && dev_alloc(h, (void**)&h->score_text_logits, (size_t)CH * NV * 4)) return 1;
-        if (dev_alloc(h, (void**)&h->score_text_oidx, (size_t)CH * 4)) return 1;
-    }
-    // entries j >= n_b: logprob 0, argmax -1
-    CTTS_HIP_CHECK(hipMemsetAsync(logprob, 0, (size_t)B * max_targets * 4, s));
-    CTTS_HIP_CHECK(hipMemsetAsync(argmax, 0xFF, (size_t)B * max_targets * 4, s));
-    if (launch_fill_meta(h->meta_pre, h->meta_dec0, h->st, mask, B, T, h->rope, h->rope_pre, nullptr, B, s)) return 1;
-    const long R = (long)B * T;
-    h->pp_rows = R; h->pp_T = T;
-    const int nbg = h->batch_inv ? 1 : 2;
-    ScoreRows sr = {};
-    sr.B = B; sr.max_targets = max_targets;
-    return prompt_passes(h, R, T, s, [&](long r0, int n) { return stage_rows(h, emb, r0, n, s); }, [&](long r0, int n) {
-        sr.cum[0] = 0;
-        for (int b = 0; b < B; ++b) {
-            const long s0 = (long)b * T + T - n_targets[b], s1 = (long)b * T + T;
-            const long lo = s0 > r0 ? s0 : r0, hi = s1 < r0 + n ? s1 : r0 + n;
-            const int cnt = hi > lo ? (int)(hi - lo) : 0;
-            sr.first[b] = cnt ? (int)(lo - r0) : 0;
-            sr.j0[b] = cnt ? (int)(lo - s0) : 0;
-            sr.cum[b + 1] = sr.cum[b] + cnt;
-        }
-        for (int g0 = 0; g0 < sr.cum[B]; g0 += CH) {
-            const int m = sr.cum[B] - g0 < CH ? sr.cum[B] - g0 : CH;
-            if (launch_score_gather(h->x_pre, h->score_text_x, h->score_text_oidx, g0, m, sr, s)) return 1;
-            GemmArgs a = {};
-            a.R = m; a.eps = 1e-6f; a.W = h->whead_text; a.n_row_tiles = (NV + 15) / 16; a.K = h->H; a.x = h->score_text_x; a.lnw = h->lnf;
-            a.logits = h->score_text_logits; a.n_valid = NV;
-            if (launch_gemm(h->cfg.dtype, nbg, PRO_NORM, EPI_LOGITS, a, (m + 16 * nbg - 1) / (16 * nbg), s)) return 1;
-            if (launch_score_text_reduce(h->score_text_logits, h->score_text_oidx, targets, logprob, argmax, m, NV, s)) return 1;
-        }
-        return 0;
-    });
-}
-
 // ---- text rows beside code rows (include/ctts_hip.h; RowState.mode) --------------------------------------------------------------------------------------------
 extern "C" int ctts_gpt_set_row_modes(ctts_gpt* h, const int32_t* modes, int B) {
     if (!h) { ctts_set_error("set_row_modes: null handle"); return 1; }
@@ -1971,11 +1933,7 @@ extern "C" int ctts_gpt_admit_modes(ctts_gpt* h, int n, const int32_t* rows, con
         })) return 1;
     if (any && h->text_mode) { ctts_set_error("admit_modes: this call's own infer_text is 1: every row of it is a text row already; text rows beside code rows live in a code-mode call"); return 1; }
     if (any && !h->text_rows_on) { ctts_set_error("admit_modes: a mode-1 row needs ctts_gpt_enable_text_rows first (after ctts_gpt_begin, before the row is seated)"); return 1; }
-    for (int i = 0; i < n; ++i) {
-        bool found = false;
-        for (auto& e : h->next.modes) if (e.first == rows[i]) { e.second = modes[i]; found = true; }
-        if (!found) h->next.modes.emplace_back(rows[i], modes[i]);
-    }
+    for (int i = 0; i < n; ++i) name_row(h->next.modes, rows[i], (int)modes[i]);
     return 0;
 }
 extern "C" int ctts_gpt_enable_text_rows(ctts_gpt* h, const ctts_sampler_cfg* tsc, int32_t* text_ids_dev, void* stream) {

@@ -107,13 +107,23 @@ def score_inputs(input_ids: torch.Tensor, attention_mask: torch.Tensor, text_mas
     if len(codes) != B:
         raise ValueError(f"score_inputs: {len(codes)} code sequences for {B} prompts")
     _check_left_padded(mask)
-    seqs, tms, tgts = [], [], []
+    conts = []
     for b in range(B):
         c = torch.as_tensor(codes[b]).cpu().to(ids.dtype)
         if c.dim() != 2 or c.shape[1] != nvq:
             raise ValueError(f"score_inputs: codes[{b}] must be [n, {nvq}] (got {tuple(c.shape)})")
         if not append_eos and c.shape[0] < 1:
             raise ValueError(f"score_inputs: codes[{b}] is empty and append_eos is off: nothing to score")
+        conts.append(c)
+    return _join_scored(ids, mask, tm, conts, eos_token, append_eos)
+
+
+def _join_scored(ids, mask, tm, conts, eos_token, append_eos):
+    """The strip / append / re-pad work of score_inputs and score_text_inputs: prompt b without its left pad, then conts[b] [n_b, num_vq] (all of it under
+    append_eos, where the targets end in a row of EOS; else without its last row), left padded again to the longest -> score_inputs' dict."""
+    B, nvq = int(ids.shape[0]), int(ids.shape[2])
+    seqs, tms, tgts = [], [], []
+    for b, c in enumerate(conts):
         pad = int((mask[b] == 0).sum())
         inp = c if append_eos else c[:-1]
         seqs.append(torch.cat([ids[b, pad:], inp], 0))
@@ -150,26 +160,14 @@ def score_text_inputs(input_ids: torch.Tensor, attention_mask: torch.Tensor, ref
     if len(refined) != B:
         raise ValueError(f"score_text_inputs: {len(refined)} refined sequences for {B} prompts")
     _check_left_padded(mask)
-    seqs, tgts = [], []
+    conts = []
     for b in range(B):
         c = torch.as_tensor(refined[b]).cpu().to(ids.dtype).flatten()
         if not append_eos and c.numel() < 1:
             raise ValueError(f"score_text_inputs: refined[{b}] is empty and append_eos is off: nothing to score")
-        pad = int((mask[b] == 0).sum())
-        inp = c if append_eos else c[:-1]
-        seqs.append(torch.cat([ids[b, pad:], inp[:, None].expand(-1, nvq)], 0))
-        tgts.append(torch.cat([c, torch.full((1,), int(eos_token), dtype=c.dtype)], 0) if append_eos else c)
-    T = max(int(s.shape[0]) for s in seqs)
-    nt = torch.tensor([int(t.shape[0]) for t in tgts], dtype=torch.int32)
-    out_ids = torch.zeros(B, T, nvq, dtype=ids.dtype)
-    out_mask = torch.zeros(B, T, dtype=torch.int32)
-    targets = torch.zeros(B, int(nt.max()), dtype=torch.int32)
-    for b in range(B):
-        n = int(seqs[b].shape[0])
-        out_ids[b, T - n:] = seqs[b]
-        out_mask[b, T - n:] = 1
-        targets[b, :int(nt[b])] = tgts[b].to(torch.int32)
-    return dict(ids=out_ids, mask=out_mask, text_mask=out_mask.bool(), targets=targets, n_targets=nt)
+        conts.append(c[:, None].expand(-1, nvq))
+    out = _join_scored(ids, mask, mask.bool(), conts, eos_token, append_eos)
+    return dict(out, text_mask=out["mask"].bool(), targets=out["targets"][:, :, 0].contiguous())
 
 
 def _check_left_padded(mask: torch.Tensor) -> None:
@@ -2074,90 +2072,57 @@ class GPT:
         is predicted by row T - n_b + j (score_inputs builds all four from a prompt and codes).  Positions are cumsum(mask) - 1 as in generate(), so a
         sequence scores the same alone as inside a padded batch.  Per-utterance adapters (set_row_adapters) apply per sequence.  Ends nothing a caller
         holds: refused while a generate() generator is live on this engine or on one sharing its KV cache.  Returns ScoreOutputs on the CPU."""
-        with self._hold("GPT.score: a generate() generator is live on this engine (or on an engine sharing its KV cache), whose KV lanes "
-                        "scoring would overwrite: exhaust or close it first"):
-            return self._score(emb, attention_mask, targets, n_targets)
+        return self._score(emb, attention_mask, targets, n_targets, "score", self._lib.ctts_gpt_score, self.num_vq, self.num_audio_tokens)
 
-    def _score(self, emb, attention_mask, targets, n_targets) -> ScoreOutputs:
-        dev = self.device
-        emb = emb.to(dev, dtype=torch.float32).contiguous()
-        if emb.dim() != 3 or emb.shape[2] != self.model_dim:
-            raise ValueError(f"score: emb must be [B, T, {self.model_dim}] (got {tuple(emb.shape)})")
-        B, T = int(emb.shape[0]), int(emb.shape[1])
-        mask = torch.as_tensor(attention_mask)
-        if tuple(mask.shape) != (B, T):
-            raise ValueError(f"score: attention_mask must be [{B}, {T}] (got {tuple(mask.shape)})")
-        _check_left_padded(mask)
-        tg = torch.as_tensor(targets).cpu().to(torch.int64)
-        nt = torch.as_tensor(n_targets).cpu().to(torch.int64).flatten()
-        if tg.dim() != 3 or tg.shape[0] != B or tg.shape[2] != self.num_vq or nt.numel() != B:
-            raise ValueError(f"score: targets must be [{B}, max_targets, {self.num_vq}] and n_targets [{B}] (got {tuple(tg.shape)}, {tuple(nt.shape)})")
-        maxt = int(tg.shape[1])
-        for b in range(B):
-            n = int(nt[b])
-            if n < 1 or n > T or n > maxt:
-                raise ValueError(f"score: n_targets[{b}] = {n} outside 1..min(T={T}, max_targets={maxt})")
-            t = tg[b, :n]
-            if bool(((t < 0) | (t >= self.num_audio_tokens)).any()):
-                raise ValueError(f"score: a target of sequence {b} is outside [0, {self.num_audio_tokens})")
-        if B > self.max_batch or T > self.max_seq:
-            raise ValueError(f"score: B={B} T={T} exceed max_batch={self.max_batch} / max_seq_len={self.max_seq}")
-        msk = mask.to(dev).to(torch.int32).contiguous()
-        tgd = tg.to(torch.int32).to(dev).contiguous()
-        nta = np.ascontiguousarray(nt.numpy(), dtype=np.int32)
-        lp = torch.empty(B, maxt, self.num_vq, dtype=torch.float32, device=dev)
-        am = torch.empty(B, maxt, self.num_vq, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.ctts_gpt_score(self._h, B, T, msk.data_ptr(), emb.data_ptr(), tgd.data_ptr(), nta.ctypes.data_as(C.c_void_p), maxt,
-                                                lp.data_ptr(), am.data_ptr(), self._stream()), "score")
-        lp, am = lp.cpu(), am.cpu().to(torch.long)
-        n = nt.tolist()
-        lps = [lp[b, :n[b]] for b in range(B)]
-        ams = [am[b, :n[b]] for b in range(B)]
-        nll, acc, loss, accuracy = score_reduce(lps, ams, [tg[b, :n[b]] for b in range(B)])
-        return ScoreOutputs(logprob=lps, argmax=ams, nll=nll, seq_accuracy=acc, loss=loss, accuracy=accuracy)
-
-    @torch.no_grad()
-    def score_text(self, emb: torch.Tensor, attention_mask: torch.Tensor, targets: torch.Tensor, n_targets) -> ScoreOutputs:
-        """score() under the refine-text head (ctts_gpt_score_text): targets [B, max_targets] text ids, target j of sequence b predicted by row T - n_b + j
-        (score_text_inputs builds the four arguments from a refine prompt and refined ids).  logprob[b] / argmax[b] are [n_b]; logprob is the `logprobs` that
-        generate(infer_text=True, return_text_logprobs=True) returned for the same tokens.  Refused on an engine without head_text / emb_text."""
-        with self._hold("GPT.score_text: a generate() generator is live on this engine (or on an engine sharing its KV cache), whose KV lanes "
+    def _score(self, emb, attention_mask, targets, n_targets, name, fn, cols, vocab) -> ScoreOutputs:
+        """The one path of score (cols = num_vq: targets [B, max_targets, cols], refused on the host outside [0, vocab)) and score_text (cols = vocab = None: targets
+        [B, max_targets], passed through to the kernel's NaN / -1) around the C entry point `fn`; `name` prefixes the messages."""
+        with self._hold(f"GPT.{name}: a generate() generator is live on this engine (or on an engine sharing its KV cache), whose KV lanes "
                         "scoring would overwrite: exhaust or close it first"):
             dev = self.device
             emb = emb.to(dev, dtype=torch.float32).contiguous()
             if emb.dim() != 3 or emb.shape[2] != self.model_dim:
-                raise ValueError(f"score_text: emb must be [B, T, {self.model_dim}] (got {tuple(emb.shape)})")
+                raise ValueError(f"{name}: emb must be [B, T, {self.model_dim}] (got {tuple(emb.shape)})")
             B, T = int(emb.shape[0]), int(emb.shape[1])
             mask = torch.as_tensor(attention_mask)
             if tuple(mask.shape) != (B, T):
-                raise ValueError(f"score_text: attention_mask must be [{B}, {T}] (got {tuple(mask.shape)})")
+                raise ValueError(f"{name}: attention_mask must be [{B}, {T}] (got {tuple(mask.shape)})")
             _check_left_padded(mask)
             tg = torch.as_tensor(targets).cpu().to(torch.int64)
             nt = torch.as_tensor(n_targets).cpu().to(torch.int64).flatten()
-            if tg.dim() != 2 or tg.shape[0] != B or nt.numel() != B:
-                raise ValueError(f"score_text: targets must be [{B}, max_targets] and n_targets [{B}] (got {tuple(tg.shape)}, {tuple(nt.shape)})")
+            tail = (cols,) if cols else ()
+            if tg.dim() != 2 + len(tail) or tg.shape[0] != B or tuple(tg.shape[2:]) != tail or nt.numel() != B:
+                raise ValueError(f"{name}: targets must be [{', '.join(map(str, (B, 'max_targets') + tail))}] and n_targets [{B}] (got {tuple(tg.shape)}, {tuple(nt.shape)})")
             maxt = int(tg.shape[1])
             for b in range(B):
                 n = int(nt[b])
                 if n < 1 or n > T or n > maxt:
-                    raise ValueError(f"score_text: n_targets[{b}] = {n} outside 1..min(T={T}, max_targets={maxt})")
+                    raise ValueError(f"{name}: n_targets[{b}] = {n} outside 1..min(T={T}, max_targets={maxt})")
+                t = tg[b, :n]
+                if vocab is not None and bool(((t < 0) | (t >= vocab)).any()):
+                    raise ValueError(f"{name}: a target of sequence {b} is outside [0, {vocab})")
             if B > self.max_batch or T > self.max_seq:
-                raise ValueError(f"score_text: B={B} T={T} exceed max_batch={self.max_batch} / max_seq_len={self.max_seq}")
+                raise ValueError(f"{name}: B={B} T={T} exceed max_batch={self.max_batch} / max_seq_len={self.max_seq}")
             msk = mask.to(dev).to(torch.int32).contiguous()
             tgd = tg.to(torch.int32).to(dev).contiguous()
             nta = np.ascontiguousarray(nt.numpy(), dtype=np.int32)
-            lp = torch.empty(B, maxt, dtype=torch.float32, device=dev)
-            am = torch.empty(B, maxt, dtype=torch.int32, device=dev)
+            lp = torch.empty((B, maxt) + tail, dtype=torch.float32, device=dev)
+            am = torch.empty((B, maxt) + tail, dtype=torch.int32, device=dev)
             with torch.cuda.device(dev):
-                _lib.check(self._lib.ctts_gpt_score_text(self._h, B, T, msk.data_ptr(), emb.data_ptr(), tgd.data_ptr(), nta.ctypes.data_as(C.c_void_p), maxt,
-                                                         lp.data_ptr(), am.data_ptr(), self._stream()), "score_text")
+                _lib.check(fn(self._h, B, T, msk.data_ptr(), emb.data_ptr(), tgd.data_ptr(), nta.ctypes.data_as(C.c_void_p), maxt, lp.data_ptr(), am.data_ptr(), self._stream()), name)
             lp, am = lp.cpu(), am.cpu().to(torch.long)
             n = nt.tolist()
             lps = [lp[b, :n[b]] for b in range(B)]
             ams = [am[b, :n[b]] for b in range(B)]
             nll, acc, loss, accuracy = score_reduce(lps, ams, [tg[b, :n[b]] for b in range(B)])
             return ScoreOutputs(logprob=lps, argmax=ams, nll=nll, seq_accuracy=acc, loss=loss, accuracy=accuracy)
+
+    @torch.no_grad()
+    def score_text(self, emb: torch.Tensor, attention_mask: torch.Tensor, targets: torch.Tensor, n_targets) -> ScoreOutputs:
+        """score() under the refine-text head (ctts_gpt_score_text): targets [B, max_targets] text ids, target j of sequence b predicted by row T - n_b + j
+        (score_text_inputs builds the four arguments from a refine prompt and refined ids).  logprob[b] / argmax[b] are [n_b]; logprob is the `logprobs` that
+        generate(infer_text=True, return_text_logprobs=True) returned for the same tokens.  Refused on an engine without head_text / emb_text."""
+        return self._score(emb, attention_mask, targets, n_targets, "score_text", self._lib.ctts_gpt_score_text, None, None)
 
     @staticmethod
     def _outputs(out: OutBuffers, infer_text: bool = False, order=None) -> GenerationOutputs:

@@ -335,13 +335,13 @@ int ctts_gpt_score(ctts_gpt* h, int B, int T, const int32_t* attention_mask_dev,
 /* Teacher-forced scoring under the refine-text head: ctts_gpt_score's layout and position rule -- the final-normed hidden row at T - n_b + j predicts target j --
  * with targets int32 [B][max_targets] and ONE column of results:
  *     logprob[b][j] = log_softmax(head_text(hidden))[targets[b][j]]   on the raw vocab_text_head-wide row;   argmax[b][j] = the first index of its largest logit
- * both [B][max_targets] device.  Entries j >= n_b are written as 0 and -1; a target outside [0, vocab_text_head) gives NaN and -1 (no logit is read for it).
+ * both [B][max_targets] device; unused entries and out-of-range targets (here: outside [0, vocab_text_head)) as in ctts_gpt_score.
  * The gathered rows go through the text-head launch of a decode step (final RMSNorm + weight-normed head_text, PRO_NORM / EPI_LOGITS) in chunks of at most
  * max_batch rows (option "score_text_chunk", read only) into a logits scratch, which one workgroup per row reduces (first index of the maximum, sum of expf in
  * fp32): log-probs agree with the lp_raw that ctts_gpt_set_text_logprob_out wrote for the same tokens to the decode-against-prompt-pass tolerance.  The first
  * call allocates the scratch, max_batch x (hidden + vocab_text_head + 1) words (11 MB at 128 rows); engines that never call it allocate nothing more.
- * Per-sequence adapter slots (ctts_gpt_set_row_adapters) are honoured; the call ENDS any generate state; fp32 and fp16 engines.  Errors naming the limit as
- * ctts_gpt_score's, and: an engine without head_text.* / emb_text.weight.  Asynchronous: never synchronises.  A fused head with an online log-sum-exp that never
+ * Everything else -- adapter slots, the end of any generate state, engines, asynchrony, errors -- is ctts_gpt_score's: the two entry points share one routine
+ * (gpt_engine.hip score_rows).  One more error: an engine without head_text.* / emb_text.weight.  A fused head with an online log-sum-exp that never
  * writes the logits is the faster shape for long targets and is not built here (it changes the summation order against the decode step). */
 int ctts_gpt_score_text(ctts_gpt* h, int B, int T, const int32_t* attention_mask_dev, const float* emb_dev, const int32_t* targets_dev,
                         const int32_t* n_targets_host, int max_targets, float* logprob_dev, int32_t* argmax_dev, void* stream);

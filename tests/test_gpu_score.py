@@ -211,6 +211,36 @@ def test_score_batch_invariant_bit_identical():
         assert torch.equal(res.argmax[row], ref.argmax[0]), f"B={B} row {row}: argmax differs"
 
 
+def boundary_case():
+    """Nine unpadded sequences of 256 tokens with 2298 targets: more scored rows in ONE pass than a heads launch takes (SCORE_ROWS = 2048 in gpt_engine.hip), sequence 8
+    straddling row 2048 of the gathered rows.  -> ids, mask, text_mask, targets, n_targets"""
+    B, T = 9, 256
+    n = [256] * 7 + [250, 256]
+    assert sum(n) > 2048 and sum(n[:8]) < 2048
+    gen = torch.Generator().manual_seed(57)
+    ids = torch.randint(0, CFG4["num_text_tokens"], (B, T, 1), generator=gen).expand(-1, -1, 4).contiguous()
+    targets = torch.randint(0, 625, (B, T, 4), generator=gen, dtype=torch.int32)
+    return ids, torch.ones(B, T, dtype=torch.int32), torch.ones(B, T, dtype=torch.bool), targets, torch.tensor(n, dtype=torch.int32)
+
+
+def test_score_chunk_boundary_schedule_independent():
+    """boundary_case under batch_invariant: the nine scored together equal, bit for bit, the same sequences scored as eight and one"""
+    ids, mask, tm, targets, nt = boundary_case()
+    B, T = mask.shape
+    assert (B, T) == (9, 256) and int(nt.sum()) > 2048
+    g = engine(options={"batch_invariant": 1}, max_batch=B, max_seq=T)
+    emb = g(ids, tm)
+    whole = g.score(emb, mask, targets, nt)
+    plan = g.prompt_plan()
+    assert plan["passes"] == 1 and plan["rows_full"] >= B * T          # one pass holds all nine, so its 2298 scored rows take two heads launches
+    parts = [g.score(emb[lo:hi], mask[lo:hi], targets[lo:hi], nt[lo:hi]) for lo, hi in ((0, 8), (8, 9))]
+    for b in range(B):
+        part, row = (parts[0], b) if b < 8 else (parts[1], 0)
+        assert whole.logprob[b].shape == (int(nt[b]), 4)
+        assert torch.equal(whole.logprob[b], part.logprob[row]), f"sequence {b}: logprob not bit-identical"
+        assert torch.equal(whole.argmax[b], part.argmax[row]), f"sequence {b}: argmax differs"
+
+
 # ---- 5. per-utterance adapters -------------------------------------------------------------------------------------------------------------
 def test_score_adapters_vs_merged():
     rng = np.random.Generator(np.random.Philox(key=83))
